@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- region-of-interest throughput of the GenArchBench hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bsw|...] [--items M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bsw|...] [--items M] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints
+the result line.  --full adds everything else: the parity check against the oracle, the host-pointer ROI, the CPU
+baseline and, for the default workload, the suite of the other configurations.
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already
 resident in HBM (the reference's ROI likewise excludes file parsing).  The default
@@ -12,7 +16,8 @@ full-size input of its own).
 
 Output contract: the LAST line of stdout is ONE compact JSON object (< 4 KB: metric, value, unit,
 n_gpus, steps, warmup, ms_per_step, scaling, dtype, config, roofline, cpu_baseline, parity and a
-short `extra`).  Every other configuration of the suite is printed BEFORE it as a line of its own
+short `extra`; cpu_baseline and parity are null without --full).  With --full every other
+configuration of the suite is printed BEFORE it as a line of its own
 ({"suite": "<name>", ...}) and the full detail of everything goes to bench_suite.json next to this
 file -- one grep-able timing line per run, as the reference's drivers print theirs
 (bsw/src/main_banded.cpp:411-426, chain/src/main.cpp:201).
@@ -205,6 +210,9 @@ class BswWorkload:
             self.kernel_ms.append(st["kernel_ms"])
         self.cells = st["cells"]
 
+    def outputs(self):
+        return {"score": self.score.cpu().numpy()}
+
     def check(self):
         """property check at full size + oracle check on a slice (the checker is not timed)"""
         from oracle import pyoracle
@@ -356,6 +364,9 @@ class ChainWorkload:
             self.kernel_ms.append(st["kernel_ms"])
         self.evals = st["evals"]
 
+    def outputs(self):
+        return {"score": self.score.cpu().numpy(), "parent": self.parent.cpu().numpy()}
+
     def check(self):
         from oracle import pyoracle
         from tools import gabgen
@@ -503,6 +514,9 @@ class BpmWorkload:
         if timed:
             self.kernel_ms.append(st["kernel_ms"]); self.total_ms.append(st["total_ms"])
         self.stats = st
+
+    def outputs(self):
+        return {"score": self.score.cpu().numpy()}
 
     def check(self):
         from oracle import pyoracle
@@ -741,6 +755,16 @@ class WfaWorkload:
             self.kernel_ms.append(st["kernel_ms"]); self.total_ms.append(st["total_ms"])
         self.stats = st
 
+    def outputs(self):
+        # every score and CIGAR length; the CIGARs themselves of the first 20 000 pairs (the slice check() compares), the
+        # written bytes of each pair's slot only
+        ln = self.ops_len.cpu().numpy()
+        n = min(20000, self.items)
+        end = int(self.off[n - 1] + self.batch.pat_len[n - 1] + self.batch.txt_len[n - 1])
+        ops = self.ops[:end].cpu().numpy()
+        head = np.concatenate([ops[self.off[i]:self.off[i] + ln[i]] for i in range(n)])
+        return {"score": self.score.cpu().numpy(), "ops_len": ln, "cigar_ops_first_pairs": head}
+
     def check(self):
         from oracle import pyoracle
         from tools import gabgen
@@ -917,6 +941,21 @@ class FmiWorkload:
             self.kernel_ms.append(st["kernel_ms"])
         self.stats = st
 
+    def outputs(self):
+        # SMEMs per read for every read; the records themselves of the first 20 000 reads (the slice check() compares)
+        import ctypes as C
+        from genarchbench_amd.fmi import SMEM_DTYPE
+        d_out, d_off, n = self.result
+        hip = C.CDLL("libamdhip64.so")
+        off = np.zeros(self.items + 1, np.int64)
+        assert hip.hipMemcpy(off.ctypes.data_as(C.c_void_p), C.c_void_p(d_off), C.c_size_t(8 * (self.items + 1)), C.c_int(2)) == 0
+        k = int(off[min(20000, self.items)])
+        host = np.zeros(max(k, 1), SMEM_DTYPE)
+        assert hip.hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(d_out), C.c_size_t(k * 40), C.c_int(2)) == 0
+        out = {"smems_per_read": np.diff(off)}
+        out.update({f"smem_{f}_first_reads": host[f][:k] for f in ("rid", "m", "n", "k", "l", "s")})
+        return out
+
     def check(self):
         import ctypes as C
         from oracle import pyoracle
@@ -1079,6 +1118,18 @@ class FmiSaWorkload(FmiWorkload):
             self.kernel_ms.append(st["kernel_ms"])
         self.stats = st
 
+    def outputs(self):
+        # coordinates per SMEM for every SMEM; the coordinates themselves of the first 200 000 SMEMs (the slice check() compares)
+        import ctypes as C
+        d_co, d_off, tot = self.sa_result
+        hip = C.CDLL("libamdhip64.so")
+        off = np.zeros(self.nsmem + 1, np.int64)
+        assert hip.hipMemcpy(off.ctypes.data_as(C.c_void_p), C.c_void_p(d_off), C.c_size_t(8 * (self.nsmem + 1)), C.c_int(2)) == 0
+        k = int(off[min(200000, self.nsmem)])
+        co = np.zeros(max(k, 1), np.int64)
+        assert hip.hipMemcpy(co.ctypes.data_as(C.c_void_p), C.c_void_p(d_co), C.c_size_t(8 * k), C.c_int(2)) == 0
+        return {"coords_per_smem": np.diff(off), "coords_first_smems": co[:k]}
+
     def check(self):
         import ctypes as C
         from oracle import pyoracle
@@ -1175,6 +1226,10 @@ class ParseBswWorkload:
     def after_step(self, timed):
         if timed:
             self.kernel_ms.append(self.ps.last_stats()["kernel_ms"])
+
+    def outputs(self):
+        got = self.ps.bsw_to_host(self.pk)
+        return {f: got[f][:self.pk.n] for f in ("len1", "len2", "h0")}
 
     def check(self):
         from tools import gabgen
@@ -1293,9 +1348,31 @@ def plan_shard(W, items, ctx, scaling):
     return count, first, None, items
 
 
-def run_workload(W, items, steps, warmup, ctx, args, with_cpu=True, with_host=True):
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs arrays together
+
+
+def dump_outputs(arrays, d, suffix=""):
+    """--dump-outputs: every array as <d>/<name><suffix>.npy in float32 (float64 where an integer needs more than float32's 24
+    bits); over DUMP_LIMIT in all, every array is cut down to the same fraction, a fixed-seed sample of its elements in order"""
+    os.makedirs(d, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        big = a.dtype.kind in "iu" and a.size and int(np.abs(a.astype(np.float64)).max()) >= 1 << 24
+        conv[name] = a.astype(np.float64 if big or a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    for name, a in conv.items():
+        if total > DUMP_LIMIT:
+            k = int(a.size * DUMP_LIMIT / total)
+            a = a[np.sort(np.random.default_rng(12345).choice(a.size, k, replace=False))]
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
+    log(f"outputs of the last timed step written to {d}: {', '.join(conv)}" + (" (sampled)" if total > DUMP_LIMIT else ""))
+
+
+def run_workload(W, items, steps, warmup, ctx, args, with_cpu=True, with_host=True, dump=None):
     """one workload, the bench contract's way: W untimed warm-up steps, K timed steps between barrier + synchronize on both
-    sides, MAX over ranks.  Returns the result dict on rank 0 (None elsewhere)."""
+    sides, MAX over ranks.  Returns the result dict on rank 0 (None elsewhere).  Without --full that is all it does (and writes
+    the last step's outputs to `dump`); the parity check, the host-pointer ROI and the CPU baseline run with --full only."""
     import torch
     rank, world, dev, dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["dist"]
     scaling = args.scaling if world > 1 else "weak"            # at N = 1 the two coincide; the line says "weak" as before
@@ -1329,8 +1406,12 @@ def run_workload(W, items, steps, warmup, ctx, args, with_cpu=True, with_host=Tr
     elapsed, total_units = aggregate(elapsed, units, dist if world > 1 else None, ctx.get("agg_dev", dev))
 
     mark(f"{steps} timed steps done")
-    verdict = None if args.no_check else wl.check()
-    mark("parity check done")
+    if dump:
+        dump_outputs(wl.outputs(), dump, "" if world == 1 else f".rank{rank}")
+    verdict = None
+    if args.full and not args.no_check:
+        verdict = wl.check()
+        mark("parity check done")
     per_rank = None
     if world > 1:                                             # who was the slowest, and on how much work (informative)
         per_rank = [None] * world
@@ -1376,7 +1457,7 @@ def run_workload(W, items, steps, warmup, ctx, args, with_cpu=True, with_host=Tr
         # BASELINE.md 3.5 also asks for the fraction of the MEASURED copy bandwidth (6.29 TB/s, MI355X_MICROARCH.md)
         if out["roofline"].get("unit") == "GB/s" and out["roofline"].get("achieved") is not None:
             out["roofline"]["frac_of_measured_copy_6290"] = round(out["roofline"]["achieved"] / 6290.0, 6)
-        if with_host and world == 1 and callable(getattr(wl, "host_roi", None)) and not args.no_host_roi:
+        if args.full and with_host and world == 1 and callable(getattr(wl, "host_roi", None)) and not args.no_host_roi:
             # SURVEY.md 8d's ROI -- what a drop-in driver times: host pointers in, host pointers out (PCIe both ways); never `value`
             try:
                 out["extra"]["roi_incl_pcie"] = wl.host_roi()
@@ -1386,7 +1467,7 @@ def run_workload(W, items, steps, warmup, ctx, args, with_cpu=True, with_host=Tr
             mark("host-pointer ROI done")
         if world > 1:
             out["cpu_baseline"] = None                     # timed at N = 1 only (the other ranks would wait for rank 0's host cores)
-        if with_cpu and world == 1 and not args.no_cpu_baseline:
+        if args.full and with_cpu and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = wl.cpu_baseline(host_cores())
             out["cpu_baseline"]["host_threads_visible"] = os.cpu_count()      # `cores` of these were used (cgroup quota)
             mark("cpu baseline done")
@@ -1511,11 +1592,18 @@ def main():
     ap.add_argument("--shard", default=None, metavar="R/N",
                     help="(one GPU) process only rank R's share of an N-GPU strong-scaling run: what that rank would spend; "
                          "T / max over R of these times is the N-GPU figure the sharding can reach")
-    ap.add_argument("--no-suite", action="store_true", help="headline only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-roi", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the oracle, the host-pointer ROI, the CPU baseline and (default workload) "
+                         "the suite; without it a run is set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--no-suite", action="store_true", help="(--full) headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full)")
+    ap.add_argument("--no-host-roi", action="store_true", help="(--full)")
+    ap.add_argument("--no-check", action="store_true", help="(--full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # the GPU box shows every hardware thread of the host but grants a CPU quota: without this the OpenMP generators and
     # the oracle would start one thread per visible CPU (256 threads on a 16-core quota)
     os.environ.setdefault("OMP_NUM_THREADS", str(host_cores()))
@@ -1566,10 +1654,10 @@ def main():
 
     try:
         W = WORKLOADS[args.workload or "bsw"]
-        out = run_workload(W, args.items or W.default_items, args.steps, args.warmup, ctx, args)
+        out = run_workload(W, args.items or W.default_items, args.steps, args.warmup, ctx, args, dump=args.dump_outputs)
 
         suite = {}
-        if args.workload is None and not args.items and not args.no_suite and not args.shard:
+        if args.full and args.workload is None and not args.items and not args.no_suite and not args.shard:
             for name, wname, items, steps in SUITE:
                 go = [time.time() - t_start < SUITE_BUDGET_S]
                 if world > 1:

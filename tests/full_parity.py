@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Full-size parity: every item of the LARGE bench configurations against the oracle (run on the GPU box, repo root).
 
-bench.py checks a slice per run (its check is outside the timed region but still has to stay short); this is the one-off
+bench.py --full checks a slice per run (its check is outside the timed region but still has to stay short); this is the one-off
 exhaustive version: all 10 M bsw / bpm / bitpal pairs, all 1 M wfa pairs (scores, lengths and every CIGAR byte), all
 10 000 chain / fast-chain calls, all 10 M fmi reads (77 M SMEM records).  Writes a summary to stdout;
 profiles/rNN_full_size_parity.md keeps the last one of each round.
@@ -127,7 +127,7 @@ def main():
             e.close()
         del ref, idx, reads, w
     if "fmi" in which:
-        # fmi-large: all 10 M reads against the 256 Mbp index (bench.py checks the first 20 000 per run)
+        # fmi-large: all 10 M reads against the 256 Mbp index (bench.py --full checks the first 20 000 per run)
         import ctypes as C
         from tools import mkindex
         from genarchbench_amd.fmi import FMI_search

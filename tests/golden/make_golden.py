@@ -189,7 +189,50 @@ def make_fmi(m):
         os.remove(fa + ext)
 
 
-MAKERS = {"bsw": make_bsw, "chain": make_chain, "bpm": make_bpm, "wfa": make_wfa, "fmi": make_fmi}
+def make_live(m):
+    """the reference's outputs for the inputs the test_*_matches_live_reference tests generate (they compare the oracle with
+    these, and with the reference itself where oracle/_ref is built), as arrays in one compressed live.npz; the inputs are not
+    stored: the generators reproduce them"""
+    import tempfile
+    import numpy as np
+    from tests.util import read_bsw_full, read_chain_output, read_scores
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        p, o = os.path.join(td, "in.txt"), os.path.join(td, "out.txt")
+        gabgen.write_text("bsw", p, 993, 4096, 1)
+        full = {how: subprocess.run([pyoracle.ref_path("bsw_full_ref_avx2"), p, how], capture_output=True, text=True, check=True).stdout
+                for how in ("scalar", "vector")}
+        assert full["scalar"] == full["vector"], "reference scalar / vector disagree on the full result"
+        open(o, "w").write(full["scalar"])
+        out["bsw_full"] = read_bsw_full(o)
+        gabgen.write_text("bsw", p, 991, 4096, 1)
+        r = subprocess.run([pyoracle.ref_path("bsw_ref_avx2"), "-pairs", p, "-t", "2", "-b", "256"], capture_output=True, text=True, check=True)
+        open(o, "w").write("\n".join([l for l in r.stderr.splitlines() if "score=" in l][:4096]) + "\n")
+        out["bsw_scores"] = read_scores(o)
+        m["bsw_live"] = {"generator": "tools/gen gabgen bsw", "mode": 1, "n": 4096, "seed": {"full": 993, "scores": 991},
+                         "command": "bsw_ref_avx2 -pairs <in> -t 2 -b 256 ; grep score= stderr -> live.npz bsw_scores",
+                         "full_command": "bsw_full_ref_avx2 <in> scalar|vector (identical output) -> live.npz bsw_full [n, 6]"}
+        gabgen.write_text("chain", p, 77, 12, 1, 800, 7000)
+        for tag, exe in (("chain", "chain_ref"), ("fastchain", "fastchain_ref_avx2")):
+            subprocess.run([pyoracle.ref_path(exe), "-i", p, "-o", o, "-t", "2"], capture_output=True, check=True)
+            out[f"{tag}_score"], out[f"{tag}_parent"] = read_chain_output(o)
+        m["chain_live"] = {"generator": "tools/gen gabgen chain", "seed": 77, "ncalls": 12, "mode": 1, "nmin": 800, "nmax": 7000,
+                           "command": "chain_ref | fastchain_ref_avx2 -i <in> -o <out> -t 2 -> live.npz {chain,fastchain}_{score,parent}"}
+        ref = gabgen.fmi_ref(71, 60000, 10)
+        reads = gabgen.fmi_reads(72, ref, 800, 30, 200)
+        fa, fq = os.path.join(td, "r.fa"), os.path.join(td, "q.fq")
+        gabgen.fmi_write_fasta(fa, ref); gabgen.fmi_write_fastq(fq, reads)
+        subprocess.run([pyoracle.ref_path("bwa_mem2_index_ref"), "index", fa], capture_output=True, check=True)
+        r = subprocess.run([pyoracle.ref_path("fmi_ref"), fa, fq, "32", "19", "1"], capture_output=True, text=True, check=True)
+        lines = r.stdout.splitlines()
+        assert not any("realloc" in l for l in lines[:8])
+        out["fmi_text"] = np.frombuffer(("\n".join(lines[6:]) + "\n").encode(), np.uint8)
+        m["fmi_live"] = {"generator": "tools/gen gabgen fmi_ref(71, 60000, 10) + fmi_reads(72, ref, 800, 30, 200)",
+                         "command": "bwa_mem2_index_ref index <fa> ; fmi_ref <fa> <fq> 32 19 1 ; stdout from line 7 on -> live.npz fmi_text (bytes)"}
+    np.savez_compressed(os.path.join(HERE, "live.npz"), **out)
+
+
+MAKERS = {"bsw": make_bsw, "chain": make_chain, "bpm": make_bpm, "wfa": make_wfa, "fmi": make_fmi, "live": make_live}
 
 if __name__ == "__main__":
     pyoracle.build(with_ref=True)

@@ -1,5 +1,5 @@
 """CPU: the bsw oracle (oracle/bsw.c) against the golden vectors produced by the compiled reference,
-and against the compiled reference run live when oracle/_ref is present."""
+and against the compiled reference run live as well when oracle/_ref is present."""
 import subprocess
 
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from oracle import pyoracle
 from tools import gabgen
-from tests.util import GOLDEN, read_bsw_full, read_bsw_input, read_scores
+from tests.util import GOLDEN, live, read_bsw_full, read_bsw_input, read_scores
 
 
 @pytest.mark.parametrize("name", ["bsw_bench", "bsw_adv"])
@@ -30,15 +30,18 @@ def test_oracle_full_result_matches_golden(name):
     np.testing.assert_array_equal(want[:, 0], read_scores(f"{GOLDEN}/{name}.expected.txt"))
 
 
-@pytest.mark.skipif(pyoracle.ref_path("bsw_full_ref_avx2") is None, reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("how", ["scalar", "vector"])
 def test_oracle_full_result_matches_live_reference(tmp_path, how):
-    """fresh seed, adversarial mode: six fields straight against the reference's class"""
+    """fresh seed, adversarial mode: six fields against the reference's class -- its output as recorded in tests/golden
+    (make_golden.py live: scalar and vector identical), and the class itself run live where oracle/_ref is built"""
     n, seed = 4096, 993
-    p = str(tmp_path / "in.txt")
-    gabgen.write_text("bsw", p, seed, n, 1)
-    r = subprocess.run([pyoracle.ref_path("bsw_full_ref_avx2"), p, how], capture_output=True, text=True, check=True)
-    want = np.array([[int(v) for v in l.split()[1:]] for l in r.stdout.splitlines()], np.int32)
+    want = live("bsw_full")
+    if pyoracle.ref_path("bsw_full_ref_avx2"):
+        p = str(tmp_path / "in.txt")
+        gabgen.write_text("bsw", p, seed, n, 1)
+        r = subprocess.run([pyoracle.ref_path("bsw_full_ref_avx2"), p, how], capture_output=True, text=True, check=True)
+        np.testing.assert_array_equal(np.array([[int(v) for v in l.split()[1:]] for l in r.stdout.splitlines()], np.int32), want)
+    assert want.shape == (n, 6)
     np.testing.assert_array_equal(pyoracle.bsw(gabgen.bsw(seed, n, 1)), want)
 
 
@@ -71,14 +74,17 @@ def test_oracle_edge_cases():
     assert out[4, 0] == 3 and out[5, 0] == 5
 
 
-@pytest.mark.skipif(pyoracle.ref_path("bsw_ref_avx2") is None, reason="oracle/_ref not built (no /root/reference)")
 def test_oracle_matches_live_reference(tmp_path):
-    """fresh seed, adversarial mode, straight against the compiled reference"""
+    """fresh seed, adversarial mode, against the compiled reference: its output as recorded in tests/golden (make_golden.py
+    live), and the reference itself run live where oracle/_ref is built"""
     n, seed = 4096, 991
-    p = str(tmp_path / "in.txt")
-    gabgen.write_text("bsw", p, seed, n, 1)
-    r = subprocess.run([pyoracle.ref_path("bsw_ref_avx2"), "-pairs", p, "-t", "2", "-b", "256"],
-                       capture_output=True, text=True, check=True)
-    want = np.array([int(l.split("=")[1]) for l in r.stderr.splitlines() if "score=" in l][:n], np.int32)
+    want = live("bsw_scores")
+    if pyoracle.ref_path("bsw_ref_avx2"):
+        p = str(tmp_path / "in.txt")
+        gabgen.write_text("bsw", p, seed, n, 1)
+        r = subprocess.run([pyoracle.ref_path("bsw_ref_avx2"), "-pairs", p, "-t", "2", "-b", "256"],
+                           capture_output=True, text=True, check=True)
+        np.testing.assert_array_equal(np.array([int(l.split("=")[1]) for l in r.stderr.splitlines() if "score=" in l][:n], np.int32), want)
+    assert len(want) == n
     got = pyoracle.bsw(gabgen.bsw(seed, n, 1))[:, 0]
     np.testing.assert_array_equal(got, want)

@@ -9,7 +9,7 @@ that fits here).  It runs here as ONE child process (a second GPU p
 test runner, inside the box's process guard) so that its 10 M-pair buffers are gone when it returns.
 r04: fmi-large ITSELF is the second test -- the 256 Mbp index, all 10 M reads of 151 bp, every field of every one
 of the ~77 M SMEMs against the oracle on all host threads (~3 minutes of oracle time: fmi/fmi.cpp:288-348 is the reference loop);
-bench.py still checks the first 20 000 reads of every run.
+bench.py --full still checks the first 20 000 reads of every run.
 """
 import os
 import subprocess

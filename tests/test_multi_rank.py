@@ -196,7 +196,7 @@ def test_two_ranks_real_engines_one_gpu(workload, items, scaling):
     env = dict(os.environ, GAB_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         "--master-port", free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--items", str(items),
-                        "--scaling", scaling, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-roi"],
+                        "--scaling", scaling, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-roi"],
                        env=dict(env, GAB_BENCH_SUITE_JSON=os.devnull), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = r.stdout.splitlines()[-1]                   # the contract: the headline is the LAST line of stdout

@@ -32,6 +32,13 @@ def read_scores(path):
     return np.array([out[i] for i in range(len(out))], np.int32)
 
 
+def live(name):
+    """an array of tests/golden/live.npz: the reference's outputs for the inputs of the test_*_matches_live_reference tests
+    (make_golden.py live)"""
+    with np.load(os.path.join(GOLDEN, "live.npz")) as z:
+        return z[name]
+
+
 def read_bsw_full(path):
     """'[i] score qle tle gtle gscore max_off' lines (oracle/ref_harness/bsw_full_ref.cpp) -> int32 [n, 6]"""
     rows = [[int(v) for v in line.split()[1:]] for line in open(path) if line.startswith("[")]
