@@ -14,9 +14,11 @@
 //   2. bsw_dp  -- one wave (= one workgroup) per 64 sorted pairs.  The H/E row of every
 //                 lane lives in LDS as [column][lane] dwords (bank = lane, conflict-free
 //                 for any per-lane column), H and E packed as two u16 in one dword when
-//                 max(h0) + 256*max(mat) fits 15 bits (the reference's own int16 lanes),
-//                 else two dwords.  LDS is sized per launch from the query-length class, so
-//                 short queries get up to 8 waves/CU and 256-base queries still fit.
+//                 max(h0) + qcap*max(mat) fits 15 bits (the reference's own int16 lanes),
+//                 else two dwords (bsw_dp8: one byte each when it fits 8 bits); max(h0) is that
+//                 of the launch's pairs, qcap the bound of its longest class.  LDS is sized per
+//                 launch from the query-length class, so short queries get up to 8 waves/CU
+//                 and 256-base queries still fit.
 //   Results are scattered back by pair id, so the output order is the input order.
 //
 // Roofline: integer-VALU / LDS bound (~20 VALU + 1 LDS read + 1 LDS write per DP cell,
@@ -46,10 +48,9 @@ struct BswConst {
 
 struct BswStats {          // device-side, zeroed per run
     unsigned long long cells;
-    int32_t max_h0;
+    int32_t max_h0[kNumClasses];   // largest h0 per query-length class: the cell width of each class's DP launch depends on it
     int32_t bad;           // number of pairs that failed validation
     int32_t first_bad;     // smallest failing index + 1
-    int32_t pad;
 };
 GAB_STATIC_ATOMIC64(BswStats, cells);
 
@@ -81,9 +82,11 @@ static_assert((kNumKeys & (kNumKeys - 1)) == 0, "bsw_hslot needs a power-of-two 
 // The value the histogram atomic returns is the pair's rank inside its bucket: it is kept, so that the scatter pass
 // needs no second round of 10 M atomics (each pass was atomic-throughput bound at ~13 G/s).
 __global__ __launch_bounds__(256) void bsw_hist(BswIO io, uint32_t *hist, uint32_t *rank, BswStats *st) {
+    __shared__ int cls_h0[kNumClasses];      // largest h0 per query-length class among this workgroup's pairs
+    if (threadIdx.x < kNumClasses) cls_h0[threadIdx.x] = 0;
+    __syncthreads();
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int mh = 0;
     for (; i < io.n; i += stride) {
         int ql = io.len2[i], tl = io.len1[i], h = io.h0[i];
         int64_t ro = io.ref_off[i], qo = io.qry_off[i];
@@ -97,12 +100,11 @@ __global__ __launch_bounds__(256) void bsw_hist(BswIO io, uint32_t *hist, uint32
             rank[i] = ~0u;                 // (the scatter pass is already queued behind this one: it must not place this pair)
             continue;
         }
-        mh = h > mh ? h : mh;
+        if (h > 0) atomicMax(&cls_h0[(ql - 1) / kClassStep], h);
         rank[i] = atomicAdd(&hist[bsw_hslot(bsw_key(ql, tl, h))], 1u);
     }
-    // wave max of h0, one atomic per wave
-    for (int o = 32; o > 0; o >>= 1) { int v = __shfl_xor(mh, o); mh = v > mh ? v : mh; }
-    if ((threadIdx.x & 63) == 0 && mh > 0) atomicMax(&st->max_h0, mh);
+    __syncthreads();
+    if (threadIdx.x < kNumClasses && cls_h0[threadIdx.x] > 0) atomicMax(&st->max_h0[threadIdx.x], cls_h0[threadIdx.x]);
 }
 
 // ---- pass 2: exclusive scan of the 65536 bins ----------------------------------------------
@@ -689,6 +691,7 @@ extern "C" int gab_bsw_run_device(gab_bsw *h, const uint8_t *ref, int64_t ref_by
                                   const uint8_t *qry, int64_t qry_bytes, const int64_t *qry_off,
                                   const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n,
                                   int32_t *score_out, gab_bsw_result *result_out, void *stream_) {
+    if (h) gab_tuning_refresh(&h->tun);
     return bsw_run_device_impl(h, ref, ref_bytes, ref_off, qry, qry_bytes, qry_off, len1, len2, h0, n, score_out, result_out, stream_, 0, 0,
                                ref_bytes, qry_bytes);
 }
@@ -746,8 +749,10 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
                       h->h_stats->bad, h->h_stats->first_bad - 1, GAB_BSW_MAX_QLEN, GAB_BSW_MAX_TLEN);
         return GAB_EINVAL;
     }
-    // 16-bit packing is valid iff every H/E value < 2^15: H <= h0 + qlen * max_sc
-    const bool wide = (int64_t)h->h_stats->max_h0 + (int64_t)GAB_BSW_MAX_QLEN * h->cst.max_sc > 32767;
+    int max_h0 = 0;
+    for (int cls = 0; cls < kNumClasses; cls++) max_h0 = h->h_stats->max_h0[cls] > max_h0 ? h->h_stats->max_h0[cls] : max_h0;
+    const bool sym = h->cst.o_del + h->cst.e_del == h->cst.o_ins + h->cst.e_ins;
+    const bool ms1 = h->cst.max_sc <= 1;
 
     GAB_HIP(hipEventRecord(h->ev[1], s));
     GAB_HIP(hipEventRecord(h->fork, s));
@@ -768,11 +773,15 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
         const int blocks = (int)gab_ceil_div(ke - kb, 64);
         s = (nlaunch % (gab_bsw::kAux + 1)) ? h->aux[nlaunch % (gab_bsw::kAux + 1) - 1] : s_main;
         nlaunch++;
-        // 8-bit cells when every H/E value of this class fits a byte: H <= h0 + qlen * max_sc
-        if ((int64_t)h->h_stats->max_h0 + (int64_t)qcap * h->cst.max_sc <= 255 && h->cst.max_sc >= 0) {
+        // every H / E value of the launch is at most h0 + qlen * max_sc (max_sc >= 0: bsw_create starts its max at 0):
+        // 8-bit cells when that fits a byte, 16-bit packed cells when it fits 15 bits, else 32-bit cells
+        const int64_t hmax = (int64_t)(one_launch ? max_h0 : h->h_stats->max_h0[cls]) + (int64_t)qcap * h->cst.max_sc;
+        const bool wide = hmax > 32767;
+        if (h->tun.bsw_trace)     // GAB_BSW_TRACE: which DP kernel each launch runs
+            fprintf(stderr, "[gab_bsw_dp %p] class %d qcap %d pairs %lld bits %d sym %d ms1 %d\n", (void *)h, cls, qcap,
+                    (long long)(ke - kb), hmax <= 255 ? 8 : wide ? 32 : 16, (int)sym, (int)ms1);
+        if (hmax <= 255 && h->cst.max_sc >= 0) {
             const size_t lds8 = sizeof(uint32_t) * 64 * ((size_t)(qcap + 2) / 2 + ((size_t)(qcap + 1) / 2 + 3) / 4 + 1);
-            const bool sym = h->cst.o_del + h->cst.e_del == h->cst.o_ins + h->cst.e_ins;
-            const bool ms1 = h->cst.max_sc <= 1;
             auto kern = sym ? (ms1 ? bsw_dp8<true, true> : bsw_dp8<true, false>) : (ms1 ? bsw_dp8<false, true> : bsw_dp8<false, false>);
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds8, s, io, h->cst, d_recs, kb, ke, qcap,
                                score_out, result_out, d_stats);

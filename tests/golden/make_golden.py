@@ -6,7 +6,7 @@ oracle/_ref/ by `make -C oracle ref`).  Inputs come from the seeded generators i
 tools/gen; expected outputs are what the reference binaries print.  Nothing from
 the reference's sources is stored here -- only inputs and the outputs it produced.
 
-    python tests/golden/make_golden.py [bsw ...]
+    python tests/golden/make_golden.py [bsw|chain|bpm|wfa|fmi|live|params ...]
 """
 import json
 import os
@@ -232,7 +232,43 @@ def make_live(m):
     np.savez_compressed(os.path.join(HERE, "live.npz"), **out)
 
 
-MAKERS = {"bsw": make_bsw, "chain": make_chain, "bpm": make_bpm, "wfa": make_wfa, "fmi": make_fmi, "live": make_live}
+def make_params(m):
+    """the reference's scalarBandedSWA (all six fields) at every parameter set of tests/util.py BSW_PARAM_SETS, on the pairs of
+    tests/util.py bsw_param_input(), as one int32 array [set, pair, field] in bsw_params.npz (the inputs are not stored: the
+    generators and the hand-made list reproduce them).  Off the driver's defaults the reference's vector getScores16 does not
+    always agree with its own scalar path: the rows where it differs are counted per set in MANIFEST.json"""
+    import tempfile
+    import numpy as np
+    from tests.util import BSW_PARAM_SETS, bsw_full_ref_params_line, bsw_param_input, read_bsw_full
+    batch = bsw_param_input()
+    scalar, vdiff, vdiff_score = [], [], []
+    with tempfile.TemporaryDirectory() as td:
+        p, o = os.path.join(td, "in.txt"), os.path.join(td, "out.txt")
+        batch.write_text(p)
+        for ps in BSW_PARAM_SETS:
+            res = {}
+            for isa in ("avx2", "avx512"):
+                for how in ("scalar", "vector"):
+                    r = subprocess.run([pyoracle.ref_path("bsw_full_ref_" + isa), p, how] + [str(v) for v in ps],
+                                       capture_output=True, text=True, check=True)
+                    assert bsw_full_ref_params_line(*ps) in r.stderr, "oracle/_ref predates the harness's parameters: rebuild it"
+                    open(o, "w").write(r.stdout)
+                    res[isa, how] = read_bsw_full(o)
+            assert np.array_equal(res["avx2", "scalar"], res["avx512", "scalar"]), "reference scalar path depends on the ISA build"
+            s, v = res["avx2", "scalar"], res["avx2", "vector"]
+            assert s.shape == (batch.n, 6)
+            scalar.append(s)
+            vdiff.append(int((s != v).any(axis=1).sum()))
+            vdiff_score.append(int((s[:, 0] != v[:, 0]).sum()))
+    np.savez_compressed(os.path.join(HERE, "bsw_params.npz"), sets=np.array(BSW_PARAM_SETS, np.int32), full=np.stack(scalar))
+    m["bsw_params"] = {"input": "tests/util.py bsw_param_input(): gabgen bsw (995, 1024, mode 1) + (996, 256, mode 0) + bsw_handmade_pairs()",
+                       "n": int(batch.n), "sets": "tests/util.py BSW_PARAM_SETS (a b ambig o_del e_del o_ins e_ins zdrop end_bonus w)",
+                       "command": "bsw_full_ref_<avx2|avx512> <in> scalar <set> (identical output) -> bsw_params.npz full [set, pair, 6]",
+                       "vector_rows_differing": vdiff, "vector_scores_differing": vdiff_score,
+                       "vector_command": "bsw_full_ref_avx2 <in> vector <set>: rows where getScores16 differs from scalarBandedSWA, per set"}
+
+
+MAKERS = {"bsw": make_bsw, "chain": make_chain, "bpm": make_bpm, "wfa": make_wfa, "fmi": make_fmi, "live": make_live, "params": make_params}
 
 if __name__ == "__main__":
     pyoracle.build(with_ref=True)

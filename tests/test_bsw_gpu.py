@@ -91,7 +91,8 @@ def test_max_lengths(sw):
 def test_other_penalties():
     from genarchbench_amd.bsw import BandedPairWiseSW, bwa_fill_scmat
     batch = gabgen.bsw(41, 5000, 1)
-    # (the byte-cell kernel is compiled per o_del + e_del == o_ins + e_ins and per "no score above 1": all four meet here)
+    # (mode 1 draws h0 up to 1000, and the cell width follows max(h0): every set here runs the 16-bit kernel -- the four byte-cell
+    # variants, the 32-bit kernel and the cell-width limits are covered by test_bsw_kernels_gpu.py)
     for (a, b, go, ge, amb, zd, w, d_ins) in [(2, 3, 5, 2, -2, 50, 30, 1), (1, 1, 0, 1, 0, 0, 100, 1), (3, 5, 7, 3, -1, 200, 5, 1),
                                              (2, 3, 5, 2, -2, 50, 30, 0), (1, 4, 6, 1, -1, 100, 100, 0)]:
         s = BandedPairWiseSW(go, ge, go + d_ins, ge, zd, 5, bwa_fill_scmat(a, b, amb), w)

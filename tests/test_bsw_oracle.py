@@ -1,13 +1,15 @@
 """CPU: the bsw oracle (oracle/bsw.c) against the golden vectors produced by the compiled reference,
 and against the compiled reference run live as well when oracle/_ref is present."""
 import subprocess
+import warnings
 
 import numpy as np
 import pytest
 
 from oracle import pyoracle
 from tools import gabgen
-from tests.util import GOLDEN, live, read_bsw_full, read_bsw_input, read_scores
+from tests.util import (BSW_PARAM_SETS, GOLDEN, bsw_full_ref_params_line, bsw_oracle_params, bsw_param_input, live,
+                        read_bsw_full, read_bsw_input, read_scores)
 
 
 @pytest.mark.parametrize("name", ["bsw_bench", "bsw_adv"])
@@ -88,3 +90,53 @@ def test_oracle_matches_live_reference(tmp_path):
     assert len(want) == n
     got = pyoracle.bsw(gabgen.bsw(seed, n, 1))[:, 0]
     np.testing.assert_array_equal(got, want)
+
+
+@pytest.fixture(scope="module")
+def param_golden():
+    with np.load(f"{GOLDEN}/bsw_params.npz") as z:
+        return z["sets"], z["full"]
+
+
+@pytest.mark.parametrize("k", range(len(BSW_PARAM_SETS)), ids=["-".join(map(str, s)) for s in BSW_PARAM_SETS])
+def test_oracle_full_result_matches_reference_at_other_parameters(tmp_path, param_golden, k):
+    """off the driver's defaults (a b ambig o_del e_del o_ins e_ins zdrop end_bonus w): six fields against the reference's
+    scalarBandedSWA -- its output as recorded in tests/golden (make_golden.py params), and the harness run live where oracle/_ref
+    is built.  (The reference's vector getScores16 is not the truth here: it differs from its own scalar path at most of these
+    sets, MANIFEST.json bsw_params.)"""
+    sets, full = param_golden
+    ps = BSW_PARAM_SETS[k]
+    assert tuple(int(v) for v in sets[k]) == ps, "BSW_PARAM_SETS no longer matches bsw_params.npz"
+    batch = bsw_param_input()
+    want = full[k]
+    assert want.shape == (batch.n, 6)
+    np.testing.assert_array_equal(pyoracle.bsw(batch, bsw_oracle_params(*ps)), want)
+    if pyoracle.ref_path("bsw_full_ref_avx2"):
+        p = str(tmp_path / "in.txt")
+        batch.write_text(p)
+        r = subprocess.run([pyoracle.ref_path("bsw_full_ref_avx2"), p, "scalar"] + [str(v) for v in ps],
+                           capture_output=True, text=True, check=True)
+        if bsw_full_ref_params_line(*ps) not in r.stderr:
+            # a binary of oracle/_ref built from the harness before it took parameters (the reference is needed to build it
+            # again): it computes the driver's defaults whatever it is given, so it says nothing about this set
+            warnings.warn("oracle/_ref/bsw_full_ref_avx2 predates the harness's parameters: live comparison not run "
+                          "(make -C oracle ref where the reference is present)")
+            return
+        np.testing.assert_array_equal(np.array([[int(v) for v in l.split()[1:]] for l in r.stdout.splitlines()], np.int32), want)
+        if k == 0:      # the driver's defaults: the same output as the harness without the ten numbers
+            assert subprocess.run([pyoracle.ref_path("bsw_full_ref_avx2"), p, "scalar"], capture_output=True, text=True,
+                                  check=True).stdout == r.stdout
+
+
+def test_param_golden_covers_the_edges(param_golden):
+    """the recorded sets reach the corners of the parameter space the kernels specialise on"""
+    sets, _ = param_golden
+    a, b, amb, od, ed, oi, ei, zd, eb, w = sets.T
+    assert len(sets) == len(BSW_PARAM_SETS) >= 12
+    assert (np.maximum(a, 0) == 0).any() and (a == 127).any() and (b == 128).any()
+    assert (od == 0).any() and (zd == 0).any() and (zd == 1).any() and (w == 0).any() and (w >= 2000).any()
+    assert (eb < 0).any() and (eb >= 1000).any() and (od + ed != oi + ei).any() and (od != oi).any()
+    batch = bsw_param_input()
+    hasn = lambda s, o, l: [(s[o[i]:o[i] + l[i]] == 4).any() for i in range(batch.n)]
+    assert np.logical_and(hasn(batch.ref, batch.ref_off, batch.len1), hasn(batch.qry, batch.qry_off, batch.len2)).any()
+
