@@ -824,18 +824,22 @@ extern "C" void gab_bpm_destroy(gab_bpm *h) {
 
 template <int W>
 static void launch_score(hipStream_t s, const BpmIO &io, const uint32_t *perm, uint32_t kb, uint32_t ke, int32_t *score,
-                         uint32_t *wl, uint32_t *wl_counter, BpmCounters *ct, int max_plen, bool blocks64) {
+                         uint32_t *wl, uint32_t *wl_counter, BpmCounters *ct, int max_plen, bool blocks64, bool trace, int slice) {
     if (ke <= kb) return;      // (blocks64 = GAB_BPM_SCORE64: the 64-row block form, kept under test)
     const dim3 grid((ke - kb + kBlock - 1) / kBlock);
+    const bool odd = max_plen <= 32 * (2 * W - 1);                          // the class's longest pattern fits 2W - 1 words
+    if (trace)      // GAB_BPM_TRACE: which score kernel each launch runs
+        fprintf(stderr, "[gab_bpm] score class %d slice %d pairs %u..%u kernel %s<%d>\n", W, slice, kb, ke,
+                blocks64 ? "bpm_score" : W <= 3 ? "bpm_score32" : "bpm_score32_wide", blocks64 ? W : odd ? 2 * W - 1 : 2 * W);
     if (blocks64)
         hipLaunchKernelGGL(bpm_score<W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
     else if constexpr (W <= 3) {
-        if (max_plen <= 32 * (2 * W - 1))                                     // the class's longest pattern fits 2W - 1 words
+        if (odd)
             hipLaunchKernelGGL(bpm_score32<2 * W - 1>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
         else
             hipLaunchKernelGGL(bpm_score32<2 * W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
     } else {
-        if (max_plen <= 32 * (2 * W - 1))
+        if (odd)
             hipLaunchKernelGGL(bpm_score32_wide<2 * W - 1>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
         else
             hipLaunchKernelGGL(bpm_score32_wide<2 * W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
@@ -844,13 +848,17 @@ static void launch_score(hipStream_t s, const BpmIO &io, const uint32_t *perm, u
 // the score kernel of one slice on `s`, its band kernel on `sb` behind the event
 template <int W>
 static int launch_slice(hipStream_t s, hipStream_t sb, hipEvent_t scored, const BpmIO &io, const uint32_t *perm, uint32_t kb,
-                        uint32_t ke, int32_t *score, uint32_t *wl, uint32_t *wl_counter, int cols, uint32_t *wl1, BpmCounters *ct, int max_plen, bool blocks64) {
+                        uint32_t ke, int32_t *score, uint32_t *wl, uint32_t *wl_counter, int cols, uint32_t *wl1, BpmCounters *ct, int max_plen, bool blocks64,
+                        bool trace, int slice) {
     if (ke <= kb) return GAB_OK;
-    launch_score<W>(s, io, perm, kb, ke, score, wl, wl_counter, ct, max_plen, blocks64);
+    launch_score<W>(s, io, perm, kb, ke, score, wl, wl_counter, ct, max_plen, blocks64, trace, slice);
     GAB_HIP(hipEventRecord(scored, s));
     GAB_HIP(hipStreamWaitEvent(sb, scored, 0));
     const size_t lds = sizeof(uint64_t) * 64 * (4 * W + 1) + sizeof(uint16_t) * 64 * (size_t)cols;
-    if (max_plen <= 32 * (2 * W - 1))
+    const bool odd = max_plen <= 32 * (2 * W - 1);
+    if (trace)
+        fprintf(stderr, "[gab_bpm] band class %d slice %d pairs %u..%u kernel bpm_band<%d>\n", W, slice, kb, ke, odd ? 2 * W - 1 : 2 * W);
+    if (odd)
         hipLaunchKernelGGL(bpm_band<2 * W - 1>, dim3((ke - kb + 63) / 64), dim3(64), lds, sb, io, wl, wl_counter, cols, score, wl1, ct);
     else
         hipLaunchKernelGGL(bpm_band<2 * W>, dim3((ke - kb + 63) / 64), dim3(64), lds, sb, io, wl, wl_counter, cols, score, wl1, ct);
@@ -938,10 +946,10 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
             const uint32_t ke = cstart[W] + std::min<uint32_t>(ccount[W], (uint32_t)(k + 1) * per);
             uint32_t *wl = d_wl + kb, *cnt = &d_ct->wl_slice[W][k], *wl1 = d_wl1 + cstart[W];
             switch (W) {
-                case 1: rc = launch_slice<1>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[1], h->tun.bpm_score64); break;
-                case 2: rc = launch_slice<2>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[2], h->tun.bpm_score64); break;
-                case 3: rc = launch_slice<3>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[3], h->tun.bpm_score64); break;
-                default: rc = launch_slice<4>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[4], h->tun.bpm_score64); break;
+                case 1: rc = launch_slice<1>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[1], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
+                case 2: rc = launch_slice<2>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[2], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
+                case 3: rc = launch_slice<3>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[3], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
+                default: rc = launch_slice<4>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[4], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
             }
             if (rc) return rc;
         }
@@ -967,6 +975,7 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
             const uint32_t *list = d_wl1 + cstart[W];
             ulonglong2 *hist = h->scratch.as<ulonglong2>();
             const dim3 g(slots / kBlock), blk(kBlock);
+            if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] window class %d slots %u kernel bpm_win<%d>\n", W, slots, W);
             switch (W) {
                 case 1: hipLaunchKernelGGL(bpm_win<1>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[1], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
                 case 2: hipLaunchKernelGGL(bpm_win<2>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[2], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
@@ -984,6 +993,7 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
             const uint32_t *list = d_wl2 + cstart[W];
             uint64_t *hist = h->scratch.as<uint64_t>();
             const dim3 g(slots / kBlock), blk(kBlock);
+            if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class %d slots %u kernel bpm_full<%d>\n", W, slots, W);
             switch (W) {
                 case 1: hipLaunchKernelGGL(bpm_full<1>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[1], hist, (const int64_t *)nullptr, score_out, d_ct); break;
                 case 2: hipLaunchKernelGGL(bpm_full<2>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[2], hist, (const int64_t *)nullptr, score_out, d_ct); break;
@@ -1024,6 +1034,7 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
                 if (rc) return rc;
                 d_sb = (int64_t *)(h->scratch.as<char>() + ((used * 8 + 63) & ~(size_t)63));
                 GAB_HIP(hipMemcpyAsync(d_sb, sb.data(), nb * 8, hipMemcpyHostToDevice, s));
+                if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class 0 pairs %u..%u kernel bpm_full<0>\n", k0, k1);
                 launch_full<0>(s, io, d_perm + cstart[0] + k0, (uint32_t)nb, h->scratch.as<uint64_t>(), d_sb, score_out, d_ct);
                 GAB_HIP(hipStreamSynchronize(s));      // sb (host) and the scratch are reused by the next batch
                 k0 = k1;
@@ -1033,6 +1044,17 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
     GAB_HIP(hipGetLastError());
     GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(BpmCounters), hipMemcpyDeviceToHost, s));
     GAB_HIP(hipEventRecord(h->ev[3], s));
+    if (h->tun.bpm_trace) {     // GAB_BPM_TRACE: the stage each class's pairs ended in (one synchronisation per call)
+        GAB_HIP(hipStreamSynchronize(s));
+        for (int c : order) {
+            if (!ccount[c]) continue;
+            uint32_t queued = 0;
+            for (int k = 0; k < kSlices; k++) queued += h->h_ct->wl_slice[c][k];
+            fprintf(stderr, "[gab_bpm] class %d pairs %u queued %u band_miss %u window_miss %u\n", c, ccount[c], queued,
+                    h->h_ct->wl1_count[c], h->h_ct->wl2_count[c]);
+        }
+        fprintf(stderr, "[gab_bpm] steps score %llu later %llu\n", h->h_ct->steps, h->h_ct->full_steps);
+    }
     h->last_full = (int64_t)ccount[0];      // (+ the pairs the band kernels queued: added from the counters in gab_bpm_last_stats)
     h->have_stats = true;
     return GAB_OK;

@@ -115,6 +115,7 @@ void gab_tuning_load(gab_tuning *t) {
     auto num = [](const char *name, long long unset) { const char *e = getenv(name); return e ? atoll(e) : unset; };
     t->bsw_trace = on("GAB_BSW_TRACE"); t->bsw_full_scan = on("GAB_BSW_FULL_SCAN");
     t->bpm_score64 = on("GAB_BPM_SCORE64"); t->bitpal_no_bv = on("GAB_BITPAL_NO_BV"); t->bpm_slices = (int)num("GAB_BPM_SLICES", 0);
+    t->bpm_trace = on("GAB_BPM_TRACE");
     if (const char *e = getenv("GAB_WFA_TUNE")) {
         t->wfa_tuned = true;
         const int k = sscanf(e, "%d,%d,%d,%d,%d,%d,%d", &t->wfa_tune[0], &t->wfa_tune[1], &t->wfa_tune[2], &t->wfa_tune[3], &t->wfa_tune[4], &t->wfa_tune[5], &t->wfa_tune[6]);

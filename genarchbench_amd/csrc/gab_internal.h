@@ -91,7 +91,7 @@ struct gab_tuning {
     // bsw
     bool bsw_trace = false, bsw_full_scan = false;
     // bpm / bitpal
-    bool bpm_score64 = false, bitpal_no_bv = false;
+    bool bpm_score64 = false, bitpal_no_bv = false, bpm_trace = false;
     int bpm_slices = 0;                              // 0 = by batch size
     // wfa
     bool wfa_tuned = false, wfa_no_static = false, wfa_trace = false;

@@ -4,7 +4,7 @@ import pytest
 
 from oracle import pyoracle
 from tools import gabgen
-from tests.util import GOLDEN, read_scores
+from tests.util import GOLDEN, bpm_model_steps, read_scores
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,8 @@ def test_vs_oracle(eng, seed, n, mode, plen):
     got = eng.benchmark_edit_bpm(batch)
     np.testing.assert_array_equal(got, want)
     st = eng.last_stats()
-    assert st["block_steps"] >= steps          # queued pairs are stepped twice (score pass + full pass)
+    assert st["block_steps"] >= steps          # queued pairs are stepped once more by every stage they pass through
+    assert st["block_steps"] == bpm_model_steps(batch)      # ... exactly as often as the model of the cascade says (tests/util.py)
 
 
 def test_block_form_score_kernel(eng, monkeypatch):

@@ -177,3 +177,207 @@ def bsw_oracle_params(a, b, ambig, o_del, e_del, o_ins, e_ins, zdrop, end_bonus,
     p = pyoracle.bsw_params(a, b, o_del, e_del, ambig, zdrop, end_bonus, w)
     p.o_ins, p.e_ins = o_ins, e_ins
     return p
+
+
+# ---------------------------------------------------------------- bpm: a CPU model of the GPU cascade (genarchbench_amd/csrc/bpm.hip)
+# A pair with W = ceil(plen / 64) <= 4 is scored by bpm_score32<D> (or bpm_score<W>), which finishes it when both strings are
+# upper-case ACGT; the others go to bpm_band<D> (8 rows around the diagonal per column), from there to bpm_win<W> (64 rows) when the
+# backtrace leaves the band, and to bpm_full<W> (complete columns) when it leaves the window.  W > 4: bpm_full<0> only.
+BPM_STAGES = ("score", "band", "window", "full", "generic")
+_BPM_CODE = {ord("A"): 0, ord("a"): 0, ord("C"): 1, ord("c"): 1, ord("G"): 2, ord("g"): 2, ord("T"): 3, ord("t"): 3}   # else 4
+
+
+def bpm_band_start(col, cshift, W):
+    """first of the 8 rows bpm_band keeps of column `col` (its start())"""
+    return min(max(col + cshift - 4, 0), 64 * W - 8)
+
+
+def bpm_win_start(col, cshift, W):
+    """first of the 64 rows bpm_win keeps of column `col` (bpm_win_start<W>)"""
+    return min(max(col + cshift - 32, 0), 64 * W - 64)
+
+
+def bpm_model(p, t):
+    """one pair (bytes, len(t) <= len(p), the driver's swap applied) -> (printed score, stage that finishes it, block steps).
+
+    The columns are Myers' Pv / Mv as ONE Python integer each, advanced from the reference's 64-row match masks: one flat table of
+    4 words per block plus one, where code 4 (not ACGT/acgt) of block b lands on code 0 of block b + 1 and that of the last block on
+    the extra word (oracle/bpm.c).  The backtrace is the reference's (edit_bpm.c:289-313): Pv of column h + 1, then Mv of column h,
+    else a diagonal step that counts when the raw bytes differ.  The stage is the first one whose rows hold every step of that walk
+    (both columns of a step, the kernels' miss checks); the steps are tlen x W per stage passed (tlen x W once for W > 4)."""
+    n, m = len(p), len(t)
+    assert 1 <= n and 0 <= m <= n
+    W = (n + 63) // 64
+    flat = [0] * (4 * W + 1)
+    for i, ch in enumerate(p):
+        flat[(i >> 6) * 4 + _BPM_CODE.get(ch, 4)] |= 1 << (i & 63)
+    if n & 63:                                        # rows n .. 64W - 1 match every code 0..3 (edit_bpm.c:106-113)
+        pad = ((1 << 64) - 1) & ~((1 << (n & 63)) - 1)
+        for c in range(4):
+            flat[(W - 1) * 4 + c] |= pad
+    eq = [sum(flat[b * 4 + c] << (64 * b) for b in range(W)) for c in range(5)]
+    full = (1 << (64 * W)) - 1
+    P, M = full, 0
+    Pc, Mc = [P], [M]
+    for ch in t:
+        Eq = eq[_BPM_CODE.get(ch, 4)]
+        Xv = Eq | M
+        Xh = ((((Eq & P) + P) ^ P) | Eq) & full
+        Ph = M | (~(Xh | P) & full)
+        Mh = P & Xh
+        Ph = ((Ph << 1) | 1) & full
+        Mh = (Mh << 1) & full
+        P = Mh | (~(Xv | Ph) & full)
+        M = Ph & Xv
+        Pc.append(P); Mc.append(M)
+    cshift = (n - m) // 2
+    in_band = in_win = True
+    ops, v, h = 0, n - 1, m - 1
+    while v >= 0 and h >= 0:
+        if in_band:
+            r1, rh = bpm_band_start(h + 1, cshift, W), bpm_band_start(h, cshift, W)
+            in_band = r1 <= v < r1 + 8 and rh <= v < rh + 8
+        if in_win:
+            r1, rh = bpm_win_start(h + 1, cshift, W), bpm_win_start(h, cshift, W)
+            in_win = r1 <= v < r1 + 64 and rh <= v < rh + 64
+        if Pc[h + 1] >> v & 1:
+            ops += 1; v -= 1
+        elif Mc[h] >> v & 1:
+            ops += 1; h -= 1
+        else:
+            ops += t[h] != p[v]; h -= 1; v -= 1
+    score = -(ops + (h + 1) + (v + 1))
+    if W > 4:
+        return score, "generic", m * W
+    if set(p) <= set(b"ACGT") and set(t) <= set(b"ACGT"):
+        return score, "score", m * W
+    stage = "band" if in_band else "window" if in_win else "full"
+    return score, stage, m * W * (BPM_STAGES.index(stage) + 1)
+
+
+def bpm_model_batch(batch):
+    """bpm_model over a PairBatch (identical pairs computed once) -> (scores int32, stages list, block steps)"""
+    memo = {}
+    scores = np.empty(batch.n, np.int32)
+    stages = []
+    steps = 0
+    for i in range(batch.n):
+        pt = batch.pair(i)
+        r = memo.get(pt)
+        if r is None:
+            r = memo[pt] = bpm_model(*pt)
+        scores[i] = r[0]; stages.append(r[1]); steps += r[2]
+    return scores, stages, steps
+
+
+def bpm_census(batch, stages):
+    """per W class (0 = W > 4), what GAB_BPM_TRACE reports: {cls: (pairs, queued by the score stage, band misses, window misses)}"""
+    out = {}
+    for n, st in zip(batch.pat_len.tolist(), stages):
+        W = (n + 63) // 64
+        c = W if W <= 4 else 0
+        a = out.setdefault(c, [0, 0, 0, 0])
+        a[0] += 1
+        a[1] += st in ("band", "window", "full")
+        a[2] += st in ("window", "full")
+        a[3] += st == "full"
+    return {c: tuple(a) for c, a in out.items()}
+
+
+def parse_bpm_trace(text):
+    """GAB_BPM_TRACE lines of ONE call -> (census {cls: (pairs, queued, band misses, window misses)}, [(stage, cls, slice or -1, kernel), ...] launched)"""
+    census, launches = {}, []
+    for line in text.splitlines():
+        m = re.match(r"\[gab_bpm\] class (\d+) pairs (\d+) queued (\d+) band_miss (\d+) window_miss (\d+)", line)
+        if m:
+            census[int(m.group(1))] = tuple(int(x) for x in m.group(2, 3, 4, 5))
+            continue
+        m = re.match(r"\[gab_bpm\] (score|band|window|full) class (\d+) (?:slice (\d+) )?.*kernel (\S+)$", line)
+        if m:
+            launches.append((m.group(1), int(m.group(2)), int(m.group(3) or -1), m.group(4)))
+    return census, launches
+
+
+def _bpm_acgt(n, seed):
+    rng = np.random.default_rng(seed)
+    return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].tobytes()
+
+
+def bpm_handmade_pairs():
+    """pairs built to sit right at the cascade's miss checks -> [(pattern, text, stage it was built for)].
+
+    Each is a random ACGT pattern with ONE unclean base (N, or a lower-case letter) and a text that is the pattern with a run of k
+    bases deleted (the walk runs k rows above the diagonal; cshift = k / 2 centres the band: k <= 6 stays in the 8-row band, k <= 62
+    in the 64-row window) or inserted (k rows below it, cshift = 0: k <= 3 band, k <= 31 window; a deletion of k at the far end
+    keeps tlen = plen).  Class 1's window is all 64 rows: nothing of it reaches bpm_full<1>."""
+    out = []
+
+    def mark(p, at, ch=b"N"):
+        return p[:at] + ch + p[at + 1:]
+
+    def deletion(n, at, k, mk, ch=b"N", seed=0):
+        p = mark(_bpm_acgt(n, seed), mk, ch)
+        return p, p[:at] + p[at + k:]
+
+    def insertion(n, at, k, mk, ch=b"N", seed=0, gap=None):
+        # k bases inserted into the text at `at`, k deleted from it `gap` bases further on (default: at the far end)
+        p = mark(_bpm_acgt(n, seed), mk, ch)
+        b = n - k if gap is None else at + gap
+        return p, p[:at] + _bpm_acgt(k, seed + 1) + p[at:b] + p[b + k:]
+
+    for W in (1, 2, 3, 4):
+        for n in sorted({64 * W, 64 * W - 5, 64 * W - 31, 64 * W - 32, 64 * (W - 1) + 1} - {0}):
+            if n < 24:
+                continue
+            at = n // 2
+            for k, st in ((6, "band"), (7, "window")):
+                out.append((*deletion(n, at, k, n // 5, seed=n + k), st))
+                out.append((*deletion(n, at, k, n - 1, b"g", seed=n + k + 100), st))
+            for k, st in ((3, "band"), (4, "window")):
+                out.append((*insertion(n, at, k, n // 5, seed=n + k + 200), st))
+            if n >= 96:
+                for k, st in ((62, "window"), (63, "full")):
+                    out.append((*deletion(n, (n - k) // 2, k, 3, seed=n + k + 300), st))
+            if n >= 160:            # (the first seed whose edit distance is the 2k indels, not fewer chance substitutions)
+                for k, st in ((31, "window"), (32, "full")):
+                    seed = n + k + 400
+                    while -bpm_model(*insertion(n, 4, k, n - 3, b"C", seed=seed, gap=n - 2 * k - 8))[0] != 2 * k:
+                        seed += 1
+                    out.append((*insertion(n, 4, k, n - 3, b"c", seed=seed, gap=n - 2 * k - 8), st))
+    # tlen 0 and 1, tlen << plen; the band clamp at row 0 holds the walk of (8, 1): its column 0 alone would start at row -1
+    p = _bpm_acgt(256, 7)
+    for n in (1, 8, 9, 64, 65, 200, 256):
+        out.append((mark(p[:n], n // 2), b"", "band"))
+    out.append((mark(p[:8], 2), p[7:8], "band"))
+    out.append((mark(p[:9], 2), p[8:9], "window"))
+    out.append((mark(p[:60], 2, b"a"), p[58:60], "window"))
+    out.append((mark(p[:200], 2), p[190:200], "full"))
+    out.append((mark(p[:256], 2), p[255:256], "full"))
+    # N / lower-case on both sides of every 64-row block boundary and in the last block (code 4 of a block aliases onto the next
+    # block's 'A' mask), two deleted bases: band
+    for n in (256, 200):
+        for mk in sorted({63, 64, 127, 128, 191, 192, n - 1, n - 2} & set(range(n))):
+            for ch in (b"N", b"t"):
+                q = mark(_bpm_acgt(n, 900 + mk), mk, ch)
+                out.append((q, q[:n // 3] + q[n // 3 + 2:], "band"))
+    return out
+
+
+def bpm_model_steps(batch):
+    """the block steps of bpm_model_batch(batch) alone: clean pairs of W <= 4 and pairs of W > 4 step tlen x W once and need no
+    model run (cleanliness from the slabs with numpy), the others go through bpm_model"""
+    def unclean(slab, off, ln):
+        bad = np.ones(256, bool)
+        bad[np.frombuffer(b"ACGT", np.uint8)] = False
+        c = np.concatenate([[0], np.cumsum(bad[slab])])
+        return (c[off + ln] - c[off]) > 0
+    pl, tl = batch.pat_len.astype(np.int64), batch.txt_len.astype(np.int64)
+    W = (pl + 63) // 64
+    steps = int((tl * W).sum())
+    memo = {}
+    for i in np.flatnonzero((unclean(batch.pat, batch.pat_off, pl) | unclean(batch.txt, batch.txt_off, tl)) & (W <= 4)).tolist():
+        pt = batch.pair(i)
+        if pt not in memo:
+            memo[pt] = bpm_model(*pt)[2]
+        steps += memo[pt] - int(tl[i] * W[i])
+    return steps
