@@ -1,0 +1,299 @@
+/* kmer-cnt -- drop-in driver of the kmer-cnt benchmark (Flye's solid k-mer counter) on MI355X.
+ *
+ *     kmer-cnt --reads a.fasta[,b.fastq.gz,...] --config F [--kmer K] [--min-read N] [--min-ovlp N] [--threads T] [--log F] [--debug]
+ *
+ * Options, the "Hash size: N" / "Total k-mers N" debug lines and the "Kernel time: %.3f sec" line on stderr are those of the
+ * reference's driver (kmer-cnt/kmer_cnt.cpp:47-125, 155-337; the two counts: kmer-cnt/vertex_index.cpp:858-859).  --threads only
+ * shaped the CPU scheduling and is accepted and ignored.  One GPU: partial tables of several GPUs would need a merge.
+ *
+ * Outside the region of interest, as in the reference: the config file (key = value lines, '#' comments, "%include other.cfg"
+ * relative to the including file, kmer-cnt/config.h:36-72; only kmer_size and use_minimizers are read), then every reads file
+ * in the order given, FASTA (multi-line) or FASTQ by its suffix, plain or gzip (kmer-cnt/sequence_container.cpp:22-46, 159-308).
+ * A byte that is not one of ACGTacgt: the reference means to replace it by "ACGT"[rand() % 4] (validateSequence,
+ * kmer-cnt/sequence_container.cpp:318-328), but its test compares a size_t table entry of -1 with -1U, which never holds where
+ * size_t has 64 bits (and kmer-cnt/kmer.h:14 asserts that it has), so nothing is replaced and rand() is never called.  The 2-bit
+ * packing then ORs that all-ones entry, shifted to the base's place, into the record's 32-base word
+ * (kmer-cnt/sequence.h:54-69): the unknown base AND every base after it up to the end of that word read as T.  This driver does
+ * the same to the record's text (positions counted from the start of the record, its lines joined), which is what makes its
+ * numbers equal the reference's on reads with N.  Reads LONGER than max(--min-read, --min-ovlp) are kept
+ * (kmer-cnt/kmer_cnt.cpp:205, kmer-cnt/sequence_container.cpp:100-106).
+ * Inside it: ONE gab_kmer_count over the kept reads (the copy of the reads to the GPU included), where the reference runs
+ * vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).
+ */
+#define GAB_ENERGY_STREAM stderr      /* where the reference prints "Energy consumption:" in this driver */
+#include "../common/gab_driver.h"
+#include <getopt.h>
+#include <time.h>
+#include <zlib.h>
+
+static int g_debug = 0;
+static FILE *g_log = NULL;
+
+/* Logger::debug (kmer-cnt/logger.h:82-96): "[YYYY-MM-DD HH:MM:SS] DEBUG: text" on stderr with --debug, always into the --log file */
+static void log_debug(const char *fmt, ...) {
+    char stamp[64], text[1024];
+    time_t t = time(NULL);
+    strftime(stamp, sizeof stamp, "[%Y-%m-%d %H:%M:%S]", localtime(&t));
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof text, fmt, ap);
+    va_end(ap);
+    if (g_debug) fprintf(stderr, "%s DEBUG: %s\n", stamp, text);
+    if (g_log) fprintf(g_log, "%s DEBUG: %s\n", stamp, text);
+}
+static void die(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    fprintf(stderr, "ERROR: ");
+    vfprintf(stderr, fmt, ap);
+    fprintf(stderr, "\n");
+    va_end(ap);
+    exit(EXIT_FAILURE);
+}
+
+/* ---- config ---------------------------------------------------------------------------------------------------------------------- */
+typedef struct { int have_kmer_size, have_use_minimizers; double kmer_size, use_minimizers; } kc_config;
+static char *trim(char *s) {
+    while (*s == ' ' || *s == '\t' || *s == '\r' || *s == '\n') s++;
+    char *e = s + strlen(s);
+    while (e > s && (e[-1] == ' ' || e[-1] == '\t' || e[-1] == '\r' || e[-1] == '\n')) *--e = 0;
+    return s;
+}
+static void config_load(const char *path, kc_config *cfg, int depth) {
+    if (depth > 16) die("config files include each other more than 16 deep: %s", path);
+    FILE *f = fopen(path, "r");
+    if (!f) die("Can't open config file: %s", path);
+    log_debug("Loading %s", path);
+    const char *slash = strrchr(path, '/');
+    const size_t dirlen = slash ? (size_t)(slash - path) + 1 : 0;
+    char line[4096];
+    while (fgets(line, sizeof line, f)) {
+        char *s = line;
+        s[strcspn(s, "\r\n")] = 0;
+        if (!*s || *s == '#') continue;
+        if (strncmp(s, "%include", 8) == 0) {
+            char *name = trim(s + 8);
+            if (!*name) die("Error parsing config file %s: %%include without a file name", path);
+            char *sub = (char *)malloc(dirlen + strlen(name) + 1);
+            memcpy(sub, path, dirlen);
+            strcpy(sub + dirlen, name);
+            config_load(sub, cfg, depth + 1);
+            free(sub);
+            continue;
+        }
+        char *eq = strchr(s, '=');
+        if (!eq || strchr(eq + 1, '=')) die("Error parsing config file %s: '%s'", path, s);
+        *eq = 0;
+        const char *key = trim(s), *val = trim(eq + 1);
+        log_debug("\t%s=%s", key, val);
+        if (strcmp(key, "kmer_size") == 0) { cfg->kmer_size = atof(val); cfg->have_kmer_size = 1; }
+        else if (strcmp(key, "use_minimizers") == 0) { cfg->use_minimizers = atof(val); cfg->have_use_minimizers = 1; }
+    }
+    fclose(f);
+}
+
+/* ---- reads ----------------------------------------------------------------------------------------------------------------------- */
+typedef struct { char *seq; size_t bytes, cap; int64_t *off; int32_t *len; int64_t n, ncap, seen; } kc_reads;
+typedef struct { char *p; size_t n, cap; } kc_buf;
+static void buf_add(kc_buf *b, const char *s, size_t n) {
+    if (b->n + n + 1 > b->cap) {
+        b->cap = (b->n + n + 1) * 2 + 4096;
+        b->p = (char *)realloc(b->p, b->cap);
+        if (!b->p) die("out of memory");
+    }
+    memcpy(b->p + b->n, s, n);
+    b->n += n;
+    b->p[b->n] = 0;
+}
+static inline int is_base(unsigned char c) { c &= 0xDF; return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
+/* what the reference's packing makes of a byte outside ACGTacgt (see the head of this file): T from there to the end of the
+ * record's 32-base word */
+static void unknown_to_t(char *s, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!is_base((unsigned char)s[i])) {
+            size_t e = (i / 32 + 1) * 32;
+            if (e > n) e = n;
+            memset(s + i, 'T', e - i);
+            i = e - 1;
+        }
+}
+static void record_done(kc_reads *R, char *s, size_t n, int64_t min_len) {
+    R->seen++;
+    unknown_to_t(s, n);
+    if ((int64_t)n <= min_len) return;
+    if (n > (size_t)INT32_MAX) die("a read of %zu bases: longer than this driver takes", n);
+    if (R->bytes + n > R->cap) {
+        R->cap = (R->bytes + n) * 2 + (1 << 20);
+        R->seq = (char *)realloc(R->seq, R->cap);
+        if (!R->seq) die("out of memory");
+    }
+    if (R->n == R->ncap) {
+        R->ncap = R->ncap * 2 + 1024;
+        R->off = (int64_t *)realloc(R->off, (size_t)R->ncap * sizeof(int64_t));
+        R->len = (int32_t *)realloc(R->len, (size_t)R->ncap * sizeof(int32_t));
+        if (!R->off || !R->len) die("out of memory");
+    }
+    memcpy(R->seq + R->bytes, s, n);
+    R->off[R->n] = (int64_t)R->bytes; R->len[R->n] = (int32_t)n;
+    R->bytes += n; R->n++;
+}
+/* one line without its "\n" / "\r\n" into *line; returns 0 at the end of the file */
+static int next_line(gzFile f, char *chunk, int chunk_bytes, kc_buf *line) {
+    line->n = 0;
+    if (line->p) line->p[0] = 0;
+    int got = 0;
+    while (gzgets(f, chunk, chunk_bytes)) {
+        got = 1;
+        const size_t n = strlen(chunk);
+        buf_add(line, chunk, n);
+        if (n && chunk[n - 1] == '\n') { line->p[--line->n] = 0; break; }
+    }
+    if (got && line->n && line->p[line->n - 1] == '\r') line->p[--line->n] = 0;
+    return got;
+}
+static int is_fasta(const char *name) {
+    char base[4096];
+    snprintf(base, sizeof base, "%s", name);
+    size_t n = strlen(base);
+    if (n > 3 && strcmp(base + n - 3, ".gz") == 0) base[n - 3] = 0;
+    const char *dot = strrchr(base, '.');
+    if (dot && (strcmp(dot + 1, "fasta") == 0 || strcmp(dot + 1, "fa") == 0)) return 1;
+    if (dot && (strcmp(dot + 1, "fastq") == 0 || strcmp(dot + 1, "fq") == 0)) return 0;
+    die("Can't identify input file type: %s", name);
+    return 0;
+}
+static void load_file(const char *name, kc_reads *R, int64_t min_len) {
+    const int fasta = is_fasta(name);
+    gzFile f = gzopen(name, "rb");
+    if (!f) die("Can't open reads file %s", name);
+    gzbuffer(f, 1 << 20);
+    const int chunk_bytes = 1 << 20;
+    char *chunk = (char *)malloc((size_t)chunk_bytes);
+    kc_buf line = {0, 0, 0}, seq = {0, 0, 0};
+    int have_header = 0, state = 0;
+    long line_no = 1;
+    while (next_line(f, chunk, chunk_bytes, &line)) {
+        if (fasta) {
+            if (line.n == 0) continue;
+            if (line.p[0] == '>') {
+                if (have_header) {
+                    if (seq.n == 0) die("parse error in %s on line %ld: empty sequence", name, line_no);
+                    record_done(R, seq.p, seq.n, min_len);
+                    seq.n = 0;
+                }
+                if (line.n < 2 || line.p[1] == ' ' || line.p[1] == '\t') die("parse error in %s on line %ld: empty header", name, line_no);
+                have_header = 1;
+            } else {
+                buf_add(&seq, line.p, line.n);
+            }
+        } else {
+            if (line.n == 0) { state = (state + 1) % 4; continue; }      /* (the reference steps its state on an empty line too) */
+            if (state == 0) {
+                if (line.p[0] != '@') die("parse error in %s on line %ld: Fastq format error", name, line_no);
+                if (line.n < 2 || line.p[1] == ' ' || line.p[1] == '\t') die("parse error in %s on line %ld: empty header", name, line_no);
+            } else if (state == 1) {
+                record_done(R, line.p, line.n, min_len);
+            } else if (state == 2 && line.p[0] != '+') die("parse error in %s on line %ld: Fastq format error", name, line_no);
+            state = (state + 1) % 4;
+        }
+        line_no++;
+    }
+    if (fasta) {
+        if (seq.n == 0) die("parse error in %s on line %ld: empty sequence", name, line_no);
+        if (!have_header) die("parse error in %s on line %ld: Fasta format error", name, line_no);
+        record_done(R, seq.p, seq.n, min_len);
+    }
+    gzclose(f);
+    free(chunk); free(line.p); free(seq.p);
+}
+
+static void usage(void) {
+    fprintf(stderr, "Usage: kmer-cnt  --reads path --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
+                    "\t\t[--threads num] [--log path] [--debug] [-h]\n\n"
+                    "Required arguments:\n"
+                    "  --reads path\tcomma-separated list of read files (FASTA / FASTQ, plain or gzip)\n"
+                    "  --config path\tpath to the config file\n\n"
+                    "Optional arguments:\n"
+                    "  --kmer size\tk-mer size, 1..%d [default = kmer_size of the config file]\n"
+                    "  --min-ovlp size\tminimum overlap between reads [default = 5000]\n"
+                    "  --min-read length\treads not longer than max(this, --min-ovlp) are dropped [default = 0]\n"
+                    "  --debug \t\tenable debug output [default = false]\n"
+                    "  --log log_file\toutput log to file [default = not set]\n"
+                    "  --threads num_threads\taccepted and ignored (the count runs on one GPU)\n", GAB_KMER_MAX_K);
+}
+
+int main(int argc, char **argv) {
+    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, c, idx = 0;
+    const char *reads = NULL, *config = NULL, *logfile = NULL;
+    static struct option lo[] = {{"reads", required_argument, 0, 0}, {"config", required_argument, 0, 0}, {"min-read", required_argument, 0, 0},
+                                 {"log", required_argument, 0, 0}, {"threads", required_argument, 0, 0}, {"kmer", required_argument, 0, 0},
+                                 {"min-ovlp", required_argument, 0, 0}, {"debug", no_argument, 0, 0}, {0, 0, 0, 0}};
+    while ((c = getopt_long(argc, argv, "h", lo, &idx)) != -1) {
+        if (c == 'h') { usage(); return 0; }
+        if (c != 0) { usage(); return 1; }
+        const char *name = lo[idx].name;
+        if (!strcmp(name, "kmer")) kmer = atoi(optarg);
+        else if (!strcmp(name, "min-read")) min_read = atoi(optarg);
+        else if (!strcmp(name, "threads")) threads = atoi(optarg);
+        else if (!strcmp(name, "min-ovlp")) min_ovlp = atoi(optarg);
+        else if (!strcmp(name, "log")) logfile = optarg;
+        else if (!strcmp(name, "debug")) g_debug = 1;
+        else if (!strcmp(name, "reads")) reads = optarg;
+        else if (!strcmp(name, "config")) config = optarg;
+    }
+    (void)threads;
+    if (!reads || !*reads || !config || !*config) { usage(); return 1; }
+    if (logfile && !(g_log = fopen(logfile, "a"))) die("Can't open log file %s", logfile);
+
+    kc_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    config_load(config, &cfg, 0);
+    if (kmer == -1) {
+        if (!cfg.have_kmer_size) die("No such parameter: kmer_size (give --kmer or set it in %s)", config);
+        kmer = (int)cfg.kmer_size;
+    }
+    if (cfg.have_use_minimizers && cfg.use_minimizers != 0.0)
+        die("use_minimizers = 1 selects the minimizer index (buildIndexMinimizers), which this driver does not build; set use_minimizers = 0");
+    if (kmer < 1 || kmer > GAB_KMER_MAX_K) die("Can't use flat counter for k-mer size > %d (k = %d; supported 1..%d)", GAB_KMER_MAX_K, kmer, GAB_KMER_MAX_K);
+    log_debug("Running with k-mer size: %d", kmer);
+
+    const int64_t min_len = min_read > min_ovlp ? min_read : min_ovlp;
+    kc_reads R;
+    memset(&R, 0, sizeof R);
+    fprintf(stderr, "Reading sequences\n");
+    char *list = strdup(reads);
+    for (char *tok = list, *next; tok; tok = next) {       /* (the reference splits on ',' and keeps empty names: they fail to open) */
+        next = strchr(tok, ',');
+        if (next) *next++ = 0;
+        load_file(tok, &R, min_len);
+    }
+    free(list);
+    log_debug("Reads: %lld of %lld records kept, %zu bases", (long long)R.n, (long long)R.seen, R.bytes);
+
+    gab_kmer *h = NULL;
+    GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(0), &h), "gab_kmer_create");
+    GAB_DIE_IF(gab_kmer_reserve(h, R.n, (int64_t)R.bytes), "gab_kmer_reserve");        /* buffers before the region of interest */
+    if (R.bytes) gab_pin(R.seq, R.bytes);
+    gab_kmer_result res;
+    memset(&res, 0xff, sizeof res);
+
+    const double t0 = gab_now();
+    gab_roi_begin();
+    GAB_DIE_IF(gab_kmer_count(h, R.seq, R.off, R.len, R.n, kmer, (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len), &res), "gab_kmer_count");
+    log_debug("Hash size: %lld", (long long)res.hash_size);
+    log_debug("Total k-mers %lld", (long long)res.total_kmers);
+    gab_roi_end();
+    const double t1 = gab_now();
+
+    int64_t probes = 0, merged = 0;
+    float kernel_ms = 0, total_ms = 0;
+    if (gab_kmer_last_stats(h, &probes, &merged, &kernel_ms, &total_ms) == 0)
+        log_debug("Distinct k-mers: %lld, positions: %lld, largest count: %lld; device: count stage %.3f ms, call %.3f ms", (long long)res.distinct,
+                  (long long)res.positions, (long long)res.max_count, kernel_ms, total_ms);
+    fprintf(stderr, "Kernel time: %.3f sec\n", t1 - t0);
+    if (R.bytes) gab_unpin(R.seq);
+    gab_kmer_destroy(h);
+    free(R.seq); free(R.off); free(R.len);
+    if (g_log) fclose(g_log);
+    return 0;
+}

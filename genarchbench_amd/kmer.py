@@ -1,0 +1,105 @@
+"""Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import GabError, check, lib
+
+RUN = 64        # GAB_KMER_RUN: positions per GPU lane (what last_stats()["merged"] is defined by)
+MAX_K = 17      # GAB_KMER_MAX_K
+
+
+class _Result(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("reads_kept", "positions", "distinct", "total_kmers", "hash_size", "max_count")]
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def pack_reads(reads):
+    """list of bytes -> (seq uint8, off int64, len int32), reads back to back"""
+    ln = np.array([len(r) for r in reads], np.int32)
+    off = np.zeros(len(reads), np.int64)
+    if len(reads) > 1:
+        off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+    seq = np.frombuffer(b"".join(reads), np.uint8).copy() if len(reads) else np.zeros(0, np.uint8)
+    return seq, off, ln
+
+
+class KmerCounter:
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        check(lib().gab_kmer_create(C.c_int(device), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gab_kmer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reserve(self, max_reads, max_seq_bytes):
+        check(lib().gab_kmer_reserve(self._h, C.c_int64(max_reads), C.c_int64(max_seq_bytes)))
+
+    @staticmethod
+    def _dict(res):
+        return {f: getattr(res, f) for f, _ in _Result._fields_}
+
+    def count(self, reads, k, min_len=5000):
+        """reads: list of bytes, or a packed (seq, off, len) triple of numpy arrays -> the six result fields; only reads LONGER than
+        min_len are counted"""
+        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
+        seq = np.ascontiguousarray(seq, np.uint8); off = np.ascontiguousarray(off, np.int64); ln = np.ascontiguousarray(ln, np.int32)
+        res = _Result(*([-12345] * 6))
+        check(lib().gab_kmer_count(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int32(min_len), C.byref(res)))
+        return self._dict(res)
+
+    def count_device(self, seq, off, ln, k, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: uint8 / int64 / int32"""
+        res = _Result(*([-12345] * 6))
+        check(lib().gab_kmer_count_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
+                                          C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int32(min_len), C.byref(res),
+                                          C.c_void_p(stream)))
+        return self._dict(res)
+
+    def spectrum(self, nbins):
+        hist = np.full(nbins, -12345, np.int64)
+        check(lib().gab_kmer_spectrum(self._h, _p(hist), C.c_int32(nbins)))
+        return hist
+
+    def query(self, kmers):
+        kmers = np.ascontiguousarray(kmers, np.uint64)
+        out = np.full(kmers.size, 0xDEADBEEF, np.uint32)
+        check(lib().gab_kmer_query(self._h, _p(kmers), C.c_int64(kmers.size), _p(out)))
+        return out
+
+    def dump(self, capacity=None):
+        """-> (k-mers uint64 ascending, counts uint32); capacity: room offered on the first try (grown once when it is too little)"""
+        n = C.c_int64(-1)
+        cap = 0 if capacity is None else int(capacity)
+        while True:
+            kmers = np.full(cap, 0xDEADBEEFDEADBEEF, np.uint64); counts = np.full(cap, 0xDEADBEEF, np.uint32)
+            rc = lib().gab_kmer_dump(self._h, _p(kmers), _p(counts), C.c_int64(cap), C.byref(n))
+            if rc == -34 and n.value > cap:      # GAB_ERANGE: the needed size came back
+                cap = n.value
+                continue
+            check(rc)
+            return kmers[:n.value], counts[:n.value]
+
+    def dump_into(self, kmers, counts):
+        """one raw call: (return code, needed size)"""
+        n = C.c_int64(-1)
+        rc = lib().gab_kmer_dump(self._h, _p(kmers), _p(counts), C.c_int64(kmers.size), C.byref(n))
+        return rc, n.value
+
+    def last_stats(self):
+        pr = C.c_int64(0); mg = C.c_int64(0); kms = C.c_float(0); tms = C.c_float(0)
+        check(lib().gab_kmer_last_stats(self._h, C.byref(pr), C.byref(mg), C.byref(kms), C.byref(tms)))
+        a = C.c_float(0); b = C.c_float(0); c = C.c_float(0)
+        check(lib().gab_kmer_last_phases(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"probes": pr.value, "merged": mg.value, "kernel_ms": kms.value, "total_ms": tms.value,
+                "pack_ms": a.value, "count_ms": b.value, "reduce_ms": c.value}
+
+
+__all__ = ["KmerCounter", "GabError", "pack_reads", "RUN", "MAX_K"]

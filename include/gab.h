@@ -368,6 +368,62 @@ int gab_fmi_sa_lookup_device(gab_fmi *h, const gab_smem *d_smems, int64_t n, int
 /* last look-up: LF-mapping steps taken (one random 64-byte CP_OCC record each) and kernel ms */
 int gab_fmi_last_sa_stats(gab_fmi *h, int64_t *lf_steps, float *kernel_ms);
 
+/* ---- kmer-cnt: exact canonical k-mer counting (Flye's solid k-mer counter) ----------------------------
+ * Replaces  vertexIndex.countKmers()                                kmer-cnt/kmer_cnt.cpp:290
+ *           -> KmerCounter::count(true), the COUNT_VERSION == 3 body kmer-cnt/vertex_index.cpp:787-860
+ *           (k-mer arithmetic and standardForm: kmer-cnt/kmer.h:22-64; the iterator whose end is the last position, so that a
+ *            read of length L yields L - k k-mers: kmer-cnt/kmer.h:177-198).
+ * Reads are ASCII, read i = seq[off[i] .. +len[i]), bytes ACGTacgt only: what the reference makes of any other byte
+ * (validateSequence, kmer-cnt/sequence_container.cpp:318-328, and the 2-bit packing, kmer-cnt/sequence.h:54-69: INTEGRATION.md)
+ * is a property of its file reader and stays in the driver.
+ * Only reads with len > min_len_exclusive are counted (loadFromFile, kmer-cnt/sequence_container.cpp:100-106), forward strand only
+ * (kmer-cnt/vertex_index.cpp:812), every k-mer in its canonical form (the smaller of itself and its reverse complement, first base in
+ * the most significant digit, A C G T = 0 1 2 3).
+ * The reference keeps one WRAPPING 8-bit counter per possible k-mer; this library counts exactly, in a table sized from the
+ * input, and derives the reference's two printed numbers from the exact count c(x) of every canonical k-mer x:
+ *     total_kmers ("Total k-mers", increments that saw 0)   = sum over x of ceil(c(x) / 256)
+ *     hash_size   ("Hash size", keys that saw 255)          = #{x : c(x) >= 256}
+ * distinct, max_count, the spectrum, query and dump are what the reference's getFreq declines to give for this version
+ * (kmer-cnt/vertex_index.cpp:863-891).  1 <= k <= 17 as in the reference (kmer-cnt/vertex_index.cpp:793-796); fewer than 2^32 k-mer
+ * positions per call.  A call with no reads, with no read longer than k, or with every read filtered returns zeros.
+ * Two calls on one handle are independent; the table of the last call stays in the handle for spectrum / query / dump, which
+ * return GAB_EINVAL before the first successful count.
+ */
+#define GAB_KMER_MAX_K 17
+#define GAB_KMER_RUN 64   /* consecutive positions of a read that one GPU lane walks and merges (see gab_kmer_last_stats) */
+typedef struct gab_kmer gab_kmer;
+typedef struct {
+    int64_t reads_kept;    /* reads with len > min_len_exclusive */
+    int64_t positions;     /* sum over the kept reads of max(len - k, 0) */
+    int64_t distinct, total_kmers, hash_size, max_count;
+} gab_kmer_result;
+int gab_kmer_create(int device, gab_kmer **out);
+void gab_kmer_destroy(gab_kmer *h);
+/* optional, outside the timed region: device buffers for calls of up to max_reads reads in max_seq_bytes of sequence (see gab_bsw_reserve) */
+int gab_kmer_reserve(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes);
+/* host pointers; a byte outside ACGTacgt in any read (kept or not) -> GAB_EINVAL, the message names the first such read */
+int gab_kmer_count(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                   int32_t min_len_exclusive, gab_kmer_result *res);
+/* device pointers; seq_bytes = size of the slab (bounds validation: off + len <= seq_bytes).  Copies off / len to the host
+ * (the tiling of the reads is planned there) and synchronises `stream` before it returns; res is a HOST pointer. */
+int gab_kmer_count_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len,
+                          int64_t n_reads, int k, int32_t min_len_exclusive, gab_kmer_result *res, void *stream);
+/* hist[c] = number of canonical k-mers seen exactly c times, c = 1 .. nbins - 2; hist[nbins - 1] = those seen >= nbins - 1 times;
+ * hist[0] = 0 (k-mers that never occur are not enumerated).  nbins >= 2, host pointer. */
+int gab_kmer_spectrum(gab_kmer *h, int64_t *hist, int32_t nbins);
+/* counts[i] = c(canonical form of kmers[i]) under the k of the last count, 0 if absent; a value >= 4^k -> GAB_EINVAL.  Host pointers. */
+int gab_kmer_query(gab_kmer *h, const uint64_t *kmers, int64_t n, uint32_t *counts);
+/* every counted canonical k-mer with its count, ascending by k-mer; *nout = their number (= distinct); when that exceeds
+ * `capacity` nothing is written and the call returns GAB_ERANGE: call again with *nout of room.  Host pointers. */
+int gab_kmer_dump(gab_kmer *h, uint64_t *kmers, uint32_t *counts, int64_t capacity, int64_t *nout);
+/* last count: 128-byte table lines the inserts visited (>= positions - merged; the excess is lines found full), positions
+ * merged into their predecessor because it had the same canonical k-mer and lay in the same lane's run (runs start at the
+ * multiples of GAB_KMER_RUN within a read), device time of the count stage (table clear + extract-and-count kernel) and of the
+ * whole call from the first copy of the plan to the result (HIP events, ms) */
+int gab_kmer_last_stats(gab_kmer *h, int64_t *probes, int64_t *merged, float *kernel_ms, float *total_ms);
+/* last count, per stage (HIP events, ms): 2-bit packing, clear + extract-and-count, the reduction over the table */
+int gab_kmer_last_phases(gab_kmer *h, float *pack_ms, float *count_ms, float *reduce_ms);
+
 /* ---- input parsers ---------------------------------------------------------
  * The reference drivers parse their text inputs on the host, line by line, outside the region of interest
  * (bsw: loadPairs, bsw/src/main_banded.cpp:164-206 -- fgets + sscanf per pair; bpm / wfa: getline per line,

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Throughput of the k-mer counter (gab_kmer_*) on a generated E. coli-like read set.  Standalone; needs a GPU.
+
+    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--out kmer_bench.json]
+
+The read set: a 4.6 Mbp random genome, reads of 5 .. 20 kb at 50x, both strands, 10 % errors (substitutions, seeded).
+For k = 17 and 15 it reports, warm, as the median of the repeats:
+    resident      reads already on the GPU (gab_kmer_count_device): k-mer positions per second over the call's device time
+    host          reads in pageable host memory (gab_kmer_count): positions per second over the wall time of the call
+and the device time of the stages -- 2-bit packing, table clear + extract-and-count (one kernel), reduction -- with the table
+lines visited per insert.  The first call's result is compared with the numpy model of tests/kmer_model.py when --check is given
+(minutes of CPU time at this size).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def ecoli_like_reads(seed=4600000, genome_len=4_600_000, coverage=50, error=0.10):
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    genome = acgt[rng.integers(0, 4, genome_len)]
+    reads, total = [], 0
+    while total < coverage * genome_len:
+        ln = int(rng.integers(5001, 20001))
+        at = int(rng.integers(0, genome_len - ln))
+        a = genome[at:at + ln].copy()
+        hit = np.flatnonzero(rng.random(ln) < error)
+        a[hit] = acgt[rng.integers(0, 4, hit.size)]
+        r = a.tobytes()
+        if rng.integers(0, 2):
+            r = r.translate(COMP)[::-1]
+        reads.append(r)
+        total += ln
+    return reads
+
+
+def write_fasta(path, reads):
+    with open(path, "wb") as f:
+        for i, r in enumerate(reads):
+            f.write(b">r%d\n%s\n" % (i, r))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--coverage", type=int, default=50)
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import genarchbench_amd  # noqa: F401  (before torch: it sets the runtime's default for pageable copies)
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("kmer_bench.py needs a GPU: there is nothing to measure without one")
+    from genarchbench_amd.kmer import KmerCounter, pack_reads
+
+    reads = ecoli_like_reads(coverage=a.coverage)
+    seq, off, ln = pack_reads(reads)
+    d_seq, d_off, d_len = (torch.from_numpy(x).cuda() for x in (seq, off, ln))
+    kc = KmerCounter()
+    kc.reserve(len(reads), seq.size)
+    out = {"reads": len(reads), "bases": int(seq.size), "repeats": a.repeats, "warmup": a.warmup, "k": {}}
+    for k in (17, 15):
+        row = {}
+        res = None
+        for mode in ("resident", "host"):
+            samples = []
+            for it in range(a.warmup + a.repeats):
+                t0 = time.perf_counter()
+                res = kc.count_device(d_seq, d_off, d_len, k) if mode == "resident" else kc.count((seq, off, ln), k)
+                wall = time.perf_counter() - t0
+                st = kc.last_stats()
+                if it >= a.warmup:
+                    samples.append((st["total_ms"] * 1e-3 if mode == "resident" else wall, wall, st))
+            pos = res["positions"]
+            t = statistics.median(s[0] for s in samples)
+            row[mode] = {"positions_per_s": pos / t, "seconds_median": t, "seconds_min": min(s[0] for s in samples), "seconds_max": max(s[0] for s in samples),
+                         "wall_seconds_median": statistics.median(s[1] for s in samples),
+                         "pack_ms": statistics.median(s[2]["pack_ms"] for s in samples),
+                         "count_ms": statistics.median(s[2]["count_ms"] for s in samples),
+                         "reduce_ms": statistics.median(s[2]["reduce_ms"] for s in samples)}
+        st = kc.last_stats()
+        inserts = res["positions"] - st["merged"]
+        row["result"] = res
+        row["inserts"] = inserts
+        row["lines_per_insert"] = st["probes"] / max(inserts, 1)
+        row["inserts_per_s_in_count_stage"] = inserts / (row["resident"]["count_ms"] * 1e-3)
+        if a.check:
+            from tests import kmer_model
+            m = kmer_model.model(reads, k)
+            row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
+        out["k"][str(k)] = row
+    kc.close()
+    line = json.dumps(out, sort_keys=True)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
