@@ -21,6 +21,27 @@
 //                 and 256-base queries still fit.
 //   Results are scattered back by pair id, so the output order is the input order.
 //
+// Early exit of score-only calls (result_out == nullptr; the six-field result takes gscore / gtle ties from later rows and
+// keeps the reference's sweep).  The score is the largest H over all rows, and in seed extension the reference window is
+// longer than the read: once the query is used up the remaining rows only carry E values that decay by e_del per row, never
+// z-drop at the default penalties and never beat `best`.  After row i, with the band trimmed to the new [beg, end],
+// R = tlen - 1 - i rows left and Hd[j] = H(i, j - 1) the stored diagonal of column j, let
+//     pot(j) = Hd[j] + max_sc * min(R, qlen - j)   (0 when Hd[j] == 0).
+// The row loop ends when  max( max_{beg <= j <= end} pot(j),  boundary,  stale_pot ) <= best, where
+//     boundary  = hb + max_sc * min(R, qlen) while beg == 0 and hb = h0 - o_del - e_del * (i + 2) > 0 (next row's left edge),
+//     stale_pot = running max of best + max_sc * (qlen - (i + w + 1)), folded in whenever the band clamp end > i + w + 1
+//                 fires: that clamp cuts live cells (each <= best then) which a later, wider row reads again; the zero
+//                 trimming leaves only zeros behind.
+// Proof that no later row exceeds the bound: every DP move keeps value + max_sc * min(rows left, columns left) from growing --
+//   a diagonal step gains at most max_sc and uses a row and a column; an E step loses value and uses a row, an F step loses
+//   value and uses a column; a zero diagonal yields M = 0.
+//   E cells need no term: Ev[j] <= H(i, j) - e_del = Hd[j + 1] - e_del, and column j + 1's diagonal has as many columns left.
+//   `best` only changes on a strictly larger row maximum, so a sweep that stops there returns the reference's score.
+// The pass over the band runs only in rows that did not raise `best` and whose maximum cell alone passes the test
+// (rowmax + max_sc * min(R, qlen - 1 - rowmax_j) <= best): never inside the matching region, about once per pair behind it.
+// On the read-like generator input it removes 23 % of the DP cells and 36 % of the rows (profiles/bsw_early_exit.md);
+// tools/gen/bsw_exit_model.c is the CPU model of the rule that the tests pin the cell counter to.
+//
 // Roofline: integer-VALU / LDS bound (~20 VALU + 1 LDS read + 1 LDS write per DP cell,
 // ~7.4 k cells per ~210 input bytes); HBM traffic is the algorithmic minimum
 // len1 + len2 + 12 B per pair plus the 4-byte permutation entry.
@@ -223,6 +244,8 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
 
         int best = h0, best_i = -1, best_j = -1, g_i = -1, gscore = -1, max_off = 0;
         int beg = 0, end = qlen;
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit of the header comment applies
+        int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
         uint32_t tw = load_u32_unaligned(t);       // 4 reference bases, refreshed every 4 rows
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
             rlo = tc == 3 ? c.row_lo[3] : rlo; rhi = tc == 3 ? c.row_hi[3] : rhi;
 
             if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) end = i + w + 1;
+            if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + c.max_sc * (qlen - end)); }
             if (end > qlen) end = qlen;
             int hleft = 0;
             if (beg == 0) { hleft = h0 - (c.o_del + e_del * (i + 1)); hleft = hleft > 0 ? hleft : 0; }
@@ -278,14 +301,20 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 gscore = hleft > gscore ? hleft : gscore;
             }
             if (rowmax == 0) break;
+            const int rows_left = tlen - 1 - i;
+            bool try_exit = false;
             if (rowmax > best) {
                 best = rowmax; best_i = i; best_j = rowmax_j;
                 int off = rowmax_j - i; off = off < 0 ? -off : off;
                 max_off = off > max_off ? off : max_off;
-            } else if (c.zdrop > 0) {
-                int di = i - best_i, dj = rowmax_j - best_j;
-                if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
-                else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
+            } else {
+                if (c.zdrop > 0) {
+                    int di = i - best_i, dj = rowmax_j - best_j;
+                    if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
+                    else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
+                }
+                // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
+                try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
             // trim all-zero cells from both band edges (bandedSWA.cpp:234-237)
             if (WIDE) {
@@ -298,6 +327,18 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 for (j = end; j >= beg && H[j * 64] == 0u; j--) {}
             }
             end = j + 2 < qlen ? j + 2 : qlen;
+            if (try_exit) {
+                int bound = stale_pot;
+                if (beg == 0) {
+                    const int hb = h0 - c.o_del - e_del * (i + 2);
+                    if (hb > 0) bound = max(bound, hb + c.max_sc * min(rows_left, qlen));
+                }
+                for (j = beg; j <= end && bound <= best; j++) {
+                    const int hd = WIDE ? (int)H[j * 64] : (int)(H[j * 64] & 0xffffu);
+                    if (hd) bound = max(bound, hd + c.max_sc * min(rows_left, qlen - j));
+                }
+                if (bound <= best) break;
+            }
         }
         score_out[id] = best;
         if (result_out) {
@@ -440,6 +481,8 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         }
         int best = h0, best_i = -1, best_j = -1, g_i = -1, gscore = -1, max_off = 0;
         int beg = 0, end = qlen;
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit of the header comment applies
+        int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
         uint32_t tw = load_u32_unaligned(t);
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -449,7 +492,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             const uint2 rr = *reinterpret_cast<const uint2 *>(&row_tab[2 * (tc < 4 ? tc : 4)]);
             const uint32_t rlo = rr.x, rhi = rr.y;
             if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) end = i + w + 1;
+            if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + c.max_sc * (qlen - end)); }
             if (end > qlen) end = qlen;
             int hleft = 0;
             if (beg == 0) { hleft = h0 - (c.o_del + e_del * (i + 1)); hleft = hleft > 0 ? hleft : 0; }
@@ -547,14 +590,20 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 gscore = hleft > gscore ? hleft : gscore;
             }
             if (rowmax == 0) break;
+            const int rows_left = tlen - 1 - i;
+            bool try_exit = false;
             if (rowmax > best) {
                 best = rowmax; best_i = i; best_j = rowmax_j;
                 int off = rowmax_j - i; off = off < 0 ? -off : off;
                 max_off = off > max_off ? off : max_off;
-            } else if (c.zdrop > 0) {
-                int di = i - best_i, dj = rowmax_j - best_j;
-                if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
-                else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
+            } else {
+                if (c.zdrop > 0) {
+                    int di = i - best_i, dj = rowmax_j - best_j;
+                    if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
+                    else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
+                }
+                // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
+                try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
             // Band trimming (bandedSWA.cpp:234-237).  The four cells next to either edge are fetched in ONE LDS round
             // trip (whole pair words; cells outside [beg, end] only ever shorten the count and the clamps below undo
@@ -577,6 +626,31 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 j = j > beg - 1 ? j : beg - 1;
             }
             end = j + 2 < qlen ? j + 2 : qlen;
+            if (try_exit) {
+                int bound = stale_pot;
+                if (beg == 0) {
+                    const int hb = h0 - c.o_del - e_del * (i + 2);
+                    if (hb > 0) bound = max(bound, hb + c.max_sc * min(rows_left, qlen));
+                }
+                if (bound <= best) {
+                    // pot() of columns 2p (low half) and 2p + 1 (high half) of every pair word that holds a cell of [beg, end];
+                    // the halves outside the band are masked to Hd = 0.  All halves stay below 2^15: Hd <= 255,
+                    // max_sc * (columns left) <= max_sc * qcap <= 255.
+                    const int pb = beg >> 1, pe = end >> 1;
+                    const uint32_t r2 = as_u32(pk_splat(rows_left)), m2 = as_u32(pk_splat(c.max_sc));
+                    uint32_t cl2 = (uint32_t)(qlen - 2 * pb) | (uint32_t)(qlen - 2 * pb - 1) << 16;    // columns left, per half
+                    uint32_t acc = 0;
+                    for (int p = pb; p <= pe; p++, cl2 -= 0x00020002u) {
+                        uint32_t d2 = CW[p * 64] & 0x00ff00ffu;
+                        if (p == pb && (beg & 1)) d2 &= 0xffff0000u;
+                        if (p == pe && !(end & 1)) d2 &= 0x0000ffffu;
+                        const uint32_t gain = pk_mul_lo(pk_min_u16(cl2, r2), m2);
+                        acc = pk_max_i16(acc, pk_mul_lo(add_u32_v(d2, gain), pk_min_u16_1(d2)));
+                    }
+                    bound = max(bound, max((int)(acc & 0xffffu), (int)(acc >> 16)));
+                }
+                if (bound <= best) break;
+            }
         }
         score_out[id] = best;
         if (result_out) {

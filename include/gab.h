@@ -115,7 +115,11 @@ int gab_bsw_run_device(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes, const 
 
 /* Counters of the last run on this handle (for the roofline report): number of DP
  * cells evaluated (sum over rows of band width) and device time of the dominant kernel
- * as measured with HIP events on the run's stream (ms). */
+ * as measured with HIP events on the run's stream (ms).
+ * `cells` counts the cells the kernels evaluated.  With result_out given that is the
+ * reference's own count.  A score-only call (gab_bsw_run, or gab_bsw_run_device with
+ * result_out NULL) ends a pair's row loop once no later row can raise its score, so it
+ * evaluates -- and counts -- fewer cells than the reference does for the same scores. */
 int gab_bsw_last_stats(gab_bsw *h, int64_t *cells, float *kernel_ms, float *total_ms);
 
 /* ---- chain / fast-chain: minimap2 seed chaining ------------------------------------

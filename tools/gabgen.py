@@ -103,6 +103,18 @@ def bsw_from_arrays(refs, qrys, h0s):
     return BswBatch(ref, ref_off, qry, qry_off, len1, len2, np.array(h0s, np.int32))
 
 
+def bsw_exit_model(batch, params, early_exit=True):
+    """CPU model of the bsw kernels' score-only early exit (tools/gen/bsw_exit_model.c) -> per-pair (score, rows swept, DP cells
+    evaluated, cells read by the bound passes); params is a ctypes struct laid out like gab_bsw_params (include/gab.h).
+    early_exit=False: the reference's full sweep"""
+    n = batch.n
+    score = np.zeros(n, np.int32); rows = np.zeros(n, np.int32); cells = np.zeros(n, np.int64); pass_cells = np.zeros(n, np.int64)
+    lib().gab_bsw_exit_model(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
+                             _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if early_exit else 0), _p(score), _p(rows),
+                             _p(cells), _p(pass_cells))
+    return score, rows, cells, pass_cells
+
+
 def write_text(bench, path, seed, n, mode=0, *extra):
     build()
     subprocess.check_call([os.path.join(_GEN_DIR, "gabgen"), bench, path, str(seed), str(n), str(mode)]

@@ -1,0 +1,142 @@
+/* CPU model of the score-only early exit of the bsw DP kernels (genarchbench_amd/csrc/bsw.hip) -- TEST INFRASTRUCTURE ONLY.
+ *
+ * The scalar banded Smith-Waterman (BandedPairWiseSW::scalarBandedSWA of the reference), restated with the upper-bound exit
+ * exactly as the kernels apply it, so
+ * that a test can pin the kernels' cell counter to the rule.  After row i (band trimmed to the new [beg, end], R = tlen - 1 - i
+ * rows left) a stored cell Hd[j] = H(i, j - 1) can still lead to at most
+ *     pot(j) = Hd[j] + max_sc * min(R, qlen - j)        (0 when Hd[j] == 0: a zero diagonal yields M = 0)
+ * in a later row.  The row loop ends when no source exceeds `best`:
+ *     max( max_{beg <= j <= end} pot(j),
+ *          hb + max_sc * min(R, qlen)   while beg == 0 and hb = h0 - o_del - e_del * (i + 2) > 0    (left boundary, next row),
+ *          stale_pot )  <=  best
+ * stale_pot is the running maximum of best + max_sc * (qlen - (i + w + 1)), folded in whenever the band clamp end > i + w + 1
+ * fires (it cuts live cells, each at most `best`, which a later, wider row reads again).
+ * The bound is evaluated only in rows that did not raise `best` and whose maximum cell alone passes it:
+ *     rowmax + max_sc * min(R, qlen - 1 - rowmax_j) <= best.
+ * With early_exit == 0 these are the score, rows and cells of the reference's full sweep. */
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+typedef struct {                      /* same layout as gab_bsw_params (include/gab.h) and the CPU checker's parameter struct */
+    int32_t o_del, e_del, o_ins, e_ins, zdrop, end_bonus, w;
+    int8_t mat[25];
+} gab_bsw_model_params;
+
+static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0,
+                      int early_exit, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells) {
+    const int oe_del = p->o_del + p->e_del, oe_ins = p->o_ins + p->e_ins;
+    const int e_del = p->e_del, e_ins = p->e_ins;
+    int64_t ncell = 0, npass = 0;
+
+    memset(Hd, 0, sizeof(int32_t) * (size_t)(qlen + 1));
+    memset(Ev, 0, sizeof(int32_t) * (size_t)(qlen + 1));
+    Hd[0] = h0;
+    if (qlen >= 1) Hd[1] = h0 > oe_ins ? h0 - oe_ins : 0;
+    for (int j = 2; j <= qlen && Hd[j - 1] > e_ins; j++) Hd[j] = Hd[j - 1] - e_ins;
+
+    int max_sc = 0;
+    for (int k = 0; k < 25; k++) if (p->mat[k] > max_sc) max_sc = p->mat[k];
+    int w = p->w;
+    int lim = (int)((double)(qlen * max_sc + p->end_bonus - p->o_ins) / e_ins + 1.);
+    if (lim < 1) lim = 1;
+    if (w > lim) w = lim;
+    lim = (int)((double)(qlen * max_sc + p->end_bonus - p->o_del) / e_del + 1.);
+    if (lim < 1) lim = 1;
+    if (w > lim) w = lim;
+
+    int best = h0, best_i = -1, best_j = -1, stale_pot = 0;
+    int beg = 0, end = qlen, i;
+    for (i = 0; i < tlen; i++) {
+        const int8_t *srow = p->mat + 5 * (target[i] > 4 ? 4 : target[i]);
+        const int R = tlen - 1 - i;
+        if (beg < i - w) beg = i - w;
+        if (end > i + w + 1) {
+            end = i + w + 1;
+            int sp = best + max_sc * (qlen - end);
+            if (sp > stale_pot) stale_pot = sp;
+        }
+        if (end > qlen) end = qlen;
+        int hleft = 0;
+        if (beg == 0) {
+            hleft = h0 - (p->o_del + e_del * (i + 1));
+            if (hleft < 0) hleft = 0;
+        }
+        int f = 0, rowmax = 0, rowmax_j = -1, j;
+        for (j = beg; j < end; j++) {
+            int diag = Hd[j], e = Ev[j];
+            Hd[j] = hleft;
+            int M = diag ? diag + srow[query[j] > 4 ? 4 : query[j]] : 0;
+            int h = M > e ? M : e;
+            if (f > h) h = f;
+            hleft = h;
+            if (!(rowmax > h)) rowmax_j = j;
+            if (h > rowmax) rowmax = h;
+            int t = M - oe_del; if (t < 0) t = 0;
+            e -= e_del; if (t > e) e = t;
+            Ev[j] = e;
+            t = M - oe_ins; if (t < 0) t = 0;
+            f -= e_ins; if (t > f) f = t;
+        }
+        ncell += (end > beg) ? end - beg : 0;
+        Hd[end] = hleft; Ev[end] = 0;
+        if (rowmax == 0) { i++; break; }
+        int try_exit = 0;
+        if (rowmax > best) {
+            best = rowmax; best_i = i; best_j = rowmax_j;
+        } else {
+            if (p->zdrop > 0) {
+                int di = i - best_i, dj = rowmax_j - best_j;
+                if (di > dj) {
+                    if (best - rowmax - (di - dj) * e_del > p->zdrop) { i++; break; }
+                } else {
+                    if (best - rowmax - (dj - di) * e_ins > p->zdrop) { i++; break; }
+                }
+            }
+            int cl = qlen - 1 - rowmax_j;
+            try_exit = early_exit && rowmax + max_sc * (R < cl ? R : cl) <= best;
+        }
+        for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
+        beg = j;
+        for (j = end; j >= beg && Hd[j] == 0 && Ev[j] == 0; j--) {}
+        end = j + 2 < qlen ? j + 2 : qlen;
+        if (try_exit) {
+            int bound = stale_pot;
+            if (beg == 0) {
+                int hb = h0 - p->o_del - e_del * (i + 2);
+                if (hb > 0) { hb += max_sc * (R < qlen ? R : qlen); if (hb > bound) bound = hb; }
+            }
+            for (j = beg; j <= end; j++) {
+                int cl = qlen - j;
+                int pot = Hd[j] ? Hd[j] + max_sc * (R < cl ? R : cl) : 0;
+                if (pot > bound) bound = pot;
+            }
+            npass += end >= beg ? end - beg + 1 : 0;
+            if (bound <= best) { i++; break; }
+        }
+    }
+    *score = best; *rows = i; *cells = ncell; *pass_cells = npass;
+}
+
+/* per pair: score, rows swept, DP cells evaluated, cells read by the bound passes */
+void gab_bsw_exit_model(const gab_bsw_model_params *p, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry,
+                        const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n,
+                        int early_exit, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells) {
+#pragma omp parallel
+    {
+        int cap = 512;
+        int32_t *buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
+#pragma omp for schedule(dynamic, 256)
+        for (int64_t k = 0; k < n; k++) {
+            int ql = len2[k];
+            if (ql > cap) {
+                cap = ql;
+                free(buf);
+                buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
+            }
+            model_one(p, ql, qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], early_exit, buf, buf + ql + 1, &score[k],
+                      &rows[k], &cells[k], &pass_cells[k]);
+        }
+        free(buf);
+    }
+}
