@@ -1069,6 +1069,19 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
     const uint32_t n_lds = h->h_ct->n_lds, n_big = h->h_ct->n_big;
     const int seqp = ((h->h_ct->max_plen + kSeqPad + 8) + 15) & ~15, seqt = ((h->h_ct->max_tlen + kSeqPad + 8) + 15) & ~15;
     int64_t requeued = 0;
+    // GAB_WFA_TRACE: one record per launch, printed after the call's last synchronisation.  in_tier / left_tier >= 0: the count is
+    // tier_over[that index] (read back with the counters anyway), in_tier = -2: all eligible pairs, left_tier = -2: n_over
+    const bool trace = h->tun.wfa_trace;
+    struct TraceLaunch { char kernel[40]; long long pool, dir, in, left, resumed; int in_tier, left_tier; };
+    std::vector<TraceLaunch> tl;
+    std::vector<WfResume> tl_hdr;                            // the first static launch's hand-over headers (trace only)
+    auto note = [&](const char *templ, int g, const char *a, const char *b, long long pool, long long dir, int in_tier, int left_tier, long long in) {
+        TraceLaunch t; memset(&t, 0, sizeof t);
+        if (g) snprintf(t.kernel, sizeof t.kernel, "%s<%d,%s%s%s>", templ, g, a, *b ? "," : "", b);
+        else snprintf(t.kernel, sizeof t.kernel, "%s<%s>", templ, a);
+        t.pool = pool; t.dir = dir; t.in = in; t.left = -1; t.resumed = -1; t.in_tier = in_tier; t.left_tier = left_tier;
+        tl.push_back(t);
+    };
 
     GAB_HIP(hipEventRecord(h->ev[1], s));
     // LDS passes: (1) four pairs per wave with one-byte offsets -- complete mode: wfa_lds_static with a ~1.5 K and then a 3 K
@@ -1157,6 +1170,15 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
                                k == 0 ? d_hdr : nullptr, k == 0 ? d_slots : nullptr, slots, (uint32_t)pools[0]);
             GAB_HIP(hipGetLastError());
             if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
+            if (trace) {
+                note("wfa_lds_static", groups[0] == 8 ? 8 : 16, tier ? "true" : "false", "", pools[k], static_rows, tier ? tier - 1 : -2, tier, cnt);
+                if (k == 0 && two && slots) {               // the headers before a later kernel reuses the scratch buffer
+                    tl_hdr.resize(slots);
+                    GAB_HIP(hipMemcpyAsync(tl_hdr.data(), d_hdr, sizeof(WfResume) * slots, hipMemcpyDeviceToHost, s));
+                    GAB_HIP(hipStreamSynchronize(s));
+                }
+                if (k == 1) tl.back().resumed = 0;
+            }
             after_launch();
         }
     }
@@ -1175,6 +1197,7 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
                            pool_bytes[pass] / (bytes ? 1 : 2), (uint32_t)per_group, nxt, &d_ct->tier_over[tier], d_ct, h->steps.as<uint8_t>());
         GAB_HIP(hipGetLastError());
         if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
+        if (trace) note("wfa_lds", G, h->adaptive ? "true" : "false", bytes ? "OffB" : "int16_t", pool_bytes[pass] / (bytes ? 1 : 2), dir_cap, tier ? tier - 1 : -2, tier, cnt);
         after_launch();
     }
     // r04: what the last LDS tier leaves (almost never anything) goes to the global-history kernel WITHOUT asking the device how
@@ -1192,6 +1215,7 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
         hipLaunchKernelGGL(h->adaptive ? wfa_global<true> : wfa_global<false>, dim3(blocks0), dim3(64), 0, s, io, h->pen, cur, 0u, (const uint32_t *)&d_ct->tier_over[tier - 1],
                            h->scratch.as<int32_t>(), per_block0, (int)dir_cap0, (int)pool_cap0, nxt, d_ct);
         GAB_HIP(hipGetLastError());
+        if (trace) note("wfa_global", 0, h->adaptive ? "true" : "false", "", pool_cap0, dir_cap0, tier - 1, -2, 0);
         first_global_done = true;
     }
     if (tier) {
@@ -1200,6 +1224,12 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
         if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
         GAB_HIP(hipStreamSynchronize(s));
         for (int k = 0; k < tier; k++) requeued += h->h_ct->tier_over[k];
+        for (TraceLaunch &t : tl) {
+            if (t.in_tier >= 0) t.in = h->h_ct->tier_over[t.in_tier];
+            t.left = t.left_tier >= 0 ? h->h_ct->tier_over[t.left_tier] : h->h_ct->n_over;
+            if (t.resumed == 0)
+                for (size_t k = 0; k < tl_hdr.size() && k < h->h_ct->tier_over[0]; k++) t.resumed += tl_hdr[k].row > 0;
+        }
         cnt = first_global_done ? h->h_ct->n_over : h->h_ct->tier_over[tier - 1];
         if (first_global_done) { requeued += cnt; std::swap(cur, nxt); }      // (what overflowed the first global pass sits in nxt)
     }
@@ -1229,10 +1259,12 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
             hipLaunchKernelGGL(h->adaptive ? wfa_global<true> : wfa_global<false>, dim3(blocks), dim3(64), 0, s, io, h->pen, list, c, (const uint32_t *)nullptr, h->scratch.as<int32_t>(),
                                per_block, (int)dir_cap, (int)pool_cap, spill, d_ct);
             GAB_HIP(hipGetLastError());
+            if (trace) note("wfa_global", 0, h->adaptive ? "true" : "false", "", pool_cap, dir_cap, -1, -2, c);
             hipLaunchKernelGGL(wfa_sum_work, dim3(1), dim3(kWorkSlots), 0, s, d_ct);
             GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(WfaCounters), hipMemcpyDeviceToHost, s));
             GAB_HIP(hipStreamSynchronize(s));
             c = h->h_ct->n_over;
+            if (trace) tl.back().left = c;
             requeued += c;
             std::swap(list, spill);
             pool_cap *= 8; dir_cap *= 4;
@@ -1243,6 +1275,15 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
     if (!tier || n_big) GAB_HIP(hipStreamSynchronize(s));      // (with LDS tiers and no long pairs the counters have been read after the last kernel)
     h->last_requeued = requeued;
     h->have_stats = true;
+    if (trace) {
+        for (size_t k = 0; k < tl.size(); k++) {
+            const TraceLaunch &t = tl[k];
+            fprintf(stderr, "[gab_wfa] launch %zu kernel %s pool %lld dir %lld in %lld left %lld", k, t.kernel, t.pool, t.dir, t.in, t.left);
+            if (t.resumed >= 0) fprintf(stderr, " resumed %lld", t.resumed);
+            fputc('\n', stderr);
+        }
+        fprintf(stderr, "[gab_wfa] n_lds %u n_big %u requeued %lld\n", n_lds, n_big, (long long)requeued);
+    }
     return GAB_OK;
 }
 

@@ -381,3 +381,528 @@ def bpm_model_steps(batch):
             memo[pt] = bpm_model(*pt)[2]
         steps += memo[pt] - int(tl[i] * W[i])
     return steps
+
+
+# ---------------------------------------------------------------- wfa: a CPU model of the GPU cascade (genarchbench_amd/csrc/wfa.hip)
+# A pair is finished by the first launch whose limits hold its wavefront history.  The model runs the forward recurrence of gap-affine
+# WFA (no backtrace) on a whole batch at once -- one numpy array of diagonals per score, a row per pair -- and keeps, per pair, what the
+# limits are about: the final score, the number of scores that have a wavefront, the offsets allocated up to the final score, the
+# largest M offset and the work count (cells computed + bases matched).  Which launches a call makes and what each can hold is restated
+# from the host code by wfa_plan; wfa_tier_of puts the two together.
+WFA_NULL = -10
+WFA_LDS_MAX_LEN = 2040                    # longer sequences go straight to wfa_global
+WFA_OFFB_MAX, WFA_OFFB_SAFE = 245, 240    # one-byte offsets: the largest value, and the M offset above which a byte tier gives up
+
+
+def wfa_rows(pen, max_rows=240, max_score=1024, table=True):
+    """the row table of complete mode: [(score, lo, hi, has I / D, used_end)] per score that has a wavefront, from the penalties alone.
+    lo / hi grow by one around the sources' range, M takes hi - lo + 1 offsets and I and D as many each when a gap source exists.
+    table=True stops where gab_wfa_create's table does (240 rows, score 1 024, 60 000 offsets, 120 diagonals to either side);
+    table=False goes on to max_score: the history every kernel allocates, whatever holds it."""
+    x, o, e = pen
+    oe = o + e
+    ent = {0: (0, 0, False)}
+    rows = [(0, 0, 0, False, 1)]
+    used = 1
+    for sc in range(1, max_score + 1):
+        if table and len(rows) >= max_rows:
+            break
+        ms, mg, ie = ent.get(sc - x), ent.get(sc - oe), ent.get(sc - e)
+        if ie is not None and not ie[2]:
+            ie = None
+        src = [s for s in (ms, mg, ie) if s is not None]
+        if not src:
+            continue
+        lo, hi = min([s[0] for s in src] + [1] * (len(src) < 3)) - 1, max([s[1] for s in src] + [-1] * (len(src) < 3)) + 1
+        gap = mg is not None or ie is not None
+        used += (hi - lo + 1) * (3 if gap else 1)
+        if table and (used > 60000 or lo < -120 or hi > 120):
+            break
+        ent[sc] = (lo, hi, gap)
+        rows.append((sc, lo, hi, gap, used))
+    return rows
+
+
+def _wfa_pad(seqs, fill, left, right):
+    """[n, left + longest + right] uint8: the sequences behind `left` bytes of `fill`, `fill` behind them"""
+    out = np.full((len(seqs), left + max([len(s) for s in seqs] + [0]) + right), fill, np.uint8)
+    for i, s in enumerate(seqs):
+        out[i, left:left + len(s)] = np.frombuffer(s, np.uint8)
+    return out
+
+
+def wfa_model(pats, txts, pen, reduction=None):
+    """lists of patterns and texts (bytes) -> dict of int64 arrays, one entry per pair:
+      score  the final score
+      rows   the scores up to it that have a wavefront (the final one's index in wfa_rows is rows - 1)
+      used   the offsets allocated up to it: 1 for score 0, then width x (1 + has I + has D) per wavefront, the width from the
+             (reduced) lo / hi of the sources
+      max_m  the largest M offset after extension, over every diagonal computed
+      work   sum of the widths computed + bases matched by the extensions
+    A single pair may be given as two bytes objects.  The strings behave as if padded with 'X' (pattern) and 'Y' (text); a missing
+    source reads as offset -10; reduction = (min_wavefront_length, max_distance_threshold) drops, after each extension, the outer
+    diagonals whose distance to the end lags more than the threshold behind the best one (never diagonal tlen - plen's side)."""
+    if isinstance(pats, (bytes, bytearray)):
+        r = wfa_model([bytes(pats)], [bytes(txts)], pen, reduction)
+        return {k: int(v[0]) for k, v in r.items()}
+    x, o, e = pen
+    oe = o + e
+    n = len(pats)
+    out = {k: np.zeros(n, np.int64) for k in ("score", "rows", "used", "max_m", "work")}
+    if n == 0:
+        return out
+    longest = np.array([max(len(p), len(t)) for p, t in zip(pats, txts)])
+    if longest.max() > 512 and longest.min() <= 512:        # a few long pairs among short ones: apart, or every row is padded to them
+        for part in (np.flatnonzero(longest <= 512), np.flatnonzero(longest > 512)):
+            r = wfa_model([pats[i] for i in part], [txts[i] for i in part], pen, reduction)
+            for k in out:
+                out[k][part] = r[k]
+        return out
+    PAD = 40
+    P, T = _wfa_pad(pats, ord("X"), PAD, PAD), _wfa_pad(txts, ord("Y"), PAD, PAD)
+    ids = np.arange(n)
+    plen = np.array([len(p) for p in pats], np.int64); tlen = np.array([len(t) for t in txts], np.int64)
+    ak = tlen - plen
+    R = 8                                              # diagonals -R .. R are column k + R of the arrays
+    NEG = np.iinfo(np.int64).min // 2
+    used = np.ones(n, np.int64); nrows = np.ones(n, np.int64); work = np.zeros(n, np.int64); max_m = np.full(n, NEG, np.int64)
+
+    def blank(m):
+        return np.full((m, 2 * R + 1), WFA_NULL, np.int64)
+
+    def extend(Mw, lo, hi):
+        """extend every diagonal lo .. hi of Mw in place -> bases matched per pair"""
+        kk = np.arange(-R, R + 1)
+        rr, cc = np.nonzero((kk[None, :] >= lo[:, None]) & (kk[None, :] <= hi[:, None]))
+        off = Mw[rr, cc]
+        start = off.copy()
+        live = np.arange(len(rr))
+        L = 4
+        while len(live):
+            r_, o_ = rr[live], off[live]
+            j = np.arange(L)
+            v = np.clip(o_ - kk[cc[live]] + PAD, 0, P.shape[1] - 1)[:, None] + j
+            h = np.clip(o_ + PAD, 0, T.shape[1] - 1)[:, None] + j
+            eq = P[r_[:, None], np.minimum(v, P.shape[1] - 1)] == T[r_[:, None], np.minimum(h, T.shape[1] - 1)]
+            run = np.where(eq.all(1), L, eq.argmin(1))
+            off[live] += run
+            live = live[run == L]
+            L = 16
+        Mw[rr, cc] = off
+        return np.bincount(rr, off - start, len(Mw)).astype(np.int64)
+
+    # per score that has a wavefront: [M, I, D, lo, hi, has gap], rows = the pairs still running
+    M0 = blank(n); M0[:, R] = 0
+    hist = {0: [M0, None, None, np.zeros(n, np.int64), np.zeros(n, np.int64), False]}
+    score = 0
+    while True:
+        cur = hist.get(score)
+        if cur is not None:
+            Mw, _, _, lo, hi, _ = cur
+            work += extend(Mw, lo, hi)
+            m = len(Mw)
+            kk = np.arange(-R, R + 1)[None, :]
+            inr = (kk >= lo[:, None]) & (kk <= hi[:, None])
+            max_m = np.maximum(max_m, np.where(inr, Mw, NEG).max(1))
+            at_ak = np.where((lo <= ak) & (ak <= hi), Mw[np.arange(m), np.clip(ak + R, 0, 2 * R)], WFA_NULL)
+            done = at_ak >= tlen
+            if reduction is not None:
+                min_len, max_dist = reduction
+                dist = np.maximum(plen[:, None] - (Mw - kk), tlen[:, None] - Mw)
+                min_d = np.minimum(np.where(inr, dist, np.iinfo(np.int64).max).min(1), np.maximum(plen, tlen))
+                good = inr & (dist - min_d[:, None] <= max_dist)
+                big = 4 * R
+                top = np.minimum(ak - 1, hi)
+                first = np.where(good & (kk < top[:, None]), kk, big).min(1)          # first good diagonal below top
+                nlo = np.where(first < big, first, np.maximum(top, lo))
+                bottom = np.maximum(ak + 1, nlo)
+                last = np.where(good & (kk > bottom[:, None]), kk, -big).max(1)
+                nhi = np.where(last > -big, last, np.minimum(bottom, hi))
+                apply = (hi - lo + 1 >= min_len) & ~done
+                nlo, nhi = np.where(apply, nlo, lo), np.where(apply, nhi, hi)
+                drop = inr & ((kk < nlo[:, None]) | (kk > nhi[:, None]))
+                for w in cur[:3]:
+                    if w is not None:
+                        w[drop] = WFA_NULL
+                cur[3], cur[4] = lo, hi = nlo, nhi
+            if done.any():
+                fin = ids[done]
+                out["score"][fin] = score; out["rows"][fin] = nrows[done]; out["used"][fin] = used[done]
+                out["max_m"][fin] = max_m[done]; out["work"][fin] = work[done]
+                keep = ~done
+                ids, plen, tlen, ak = ids[keep], plen[keep], tlen[keep], ak[keep]
+                used, nrows, work, max_m = used[keep], nrows[keep], work[keep], max_m[keep]
+                P, T = P[keep], T[keep]
+                for ent in hist.values():
+                    for q in range(5):
+                        if ent[q] is not None:
+                            ent[q] = ent[q][keep]
+                if len(ids) == 0:
+                    return out
+        score += 1
+        for old in [s for s in hist if s < score - max(x, oe, e)]:
+            del hist[old]
+        ms, mg, ie = hist.get(score - x), hist.get(score - oe), hist.get(score - e)
+        if ie is not None and not ie[5]:
+            ie = None
+        if ms is None and mg is None and ie is None:
+            continue
+        m = len(ids)
+        # (a missing source counts as the empty range lo = 1, hi = -1: it matters once a reduction has pushed lo above 1)
+        lo = np.minimum.reduce([s[3] if s is not None else np.ones(m, np.int64) for s in (ms, mg, ie)]) - 1
+        hi = np.maximum.reduce([s[4] if s is not None else -np.ones(m, np.int64) for s in (ms, mg, ie)]) + 1
+        if max(int(-lo.min()), int(hi.max())) + 1 > R:           # more diagonals: re-centre the history
+            grow = R
+            for ent in hist.values():
+                for q in range(3):
+                    if ent[q] is not None:
+                        ent[q] = np.pad(ent[q], ((0, 0), (grow, grow)), constant_values=WFA_NULL)
+            R += grow
+            ms, mg, ie = hist.get(score - x), hist.get(score - oe), hist.get(score - e)
+            if ie is not None and not ie[5]:
+                ie = None
+        kk = np.arange(-R, R + 1)[None, :]
+        inr = (kk >= lo[:, None]) & (kk <= hi[:, None])
+        gap = mg is not None or ie is not None
+        # the sources hold -10 outside their (reduced) ranges, so a shifted read is the range-checked read
+        best = np.full((m, 2 * R + 1), WFA_NULL, np.int64)
+        if ms is not None:
+            in_ms = (kk >= ms[3][:, None]) & (kk <= ms[4][:, None])
+            best = np.where(in_ms, ms[0] + 1, WFA_NULL)
+        Iw = Dw = None
+        if gap:
+            null = blank(m)
+            mgm = mg[0] if mg is not None else null
+            iei = ie[1] if ie is not None else null
+            ied = ie[2] if ie is not None else null
+            Iw = blank(m); Dw = blank(m)
+            Iw[:, 1:] = np.maximum(mgm[:, :-1], iei[:, :-1]) + 1           # from diagonal k - 1
+            Iw[:, 0] = WFA_NULL + 1
+            Dw[:, :-1] = np.maximum(mgm[:, 1:], ied[:, 1:])                # from diagonal k + 1
+            best = np.maximum(best, np.maximum(Iw, Dw))
+            Iw[~inr] = WFA_NULL; Dw[~inr] = WFA_NULL
+        best[~inr] = WFA_NULL
+        width = hi - lo + 1
+        used += width * (3 if gap else 1)
+        work += width
+        nrows += 1
+        hist[score] = [best, Iw, Dw, lo, hi, gap]
+
+
+def wfa_pad_bytes(batch):
+    """bool per pair: the pattern holds the text's padding byte 'Y' or the text the pattern's 'X' (the static tiers pass such pairs on)"""
+    def has(slab, off, ln, ch):
+        c = np.concatenate([[0], np.cumsum(slab == ch)])
+        return (c[off + ln] - c[off]) > 0
+    return has(batch.pat, batch.pat_off, batch.pat_len.astype(np.int64), ord("Y")) | has(batch.txt, batch.txt_off, batch.txt_len.astype(np.int64), ord("X"))
+
+
+def wfa_plan(batch, pen, adaptive=False, knobs=None):
+    """the launches gab_wfa_run_device makes for the pairs with both strings <= 2040 bases, from the longest such pattern and text:
+    -> dict with `launches` = [(kernel, pool in offsets, directory size or static_rows), ...] up to and including the first wfa_global
+    launch, and the host's intermediate values (seqp, seqt, byte_ok, static_rows, static_pool, use_static, slots, n_lds, n_big).
+    knobs = {"GAB_WFA_NO_STATIC": 1, "GAB_WFA_POOL2": offsets, "GAB_WFA_SLOTS": slots} as the environment would set them."""
+    knobs = knobs or {}
+    pl, tl = batch.pat_len.astype(np.int64), batch.txt_len.astype(np.int64)
+    lds = (pl <= WFA_LDS_MAX_LEN) & (tl <= WFA_LDS_MAX_LEN)
+    n_lds, n_big = int(lds.sum()), int((~lds).sum())
+    max_plen, max_tlen = (int(pl[lds].max()), int(tl[lds].max())) if n_lds else (0, 0)
+    seqp, seqt = (max_plen + 32 + 8 + 15) & ~15, (max_tlen + 32 + 8 + 15) & ~15
+    A = "true" if adaptive else "false"
+    dir0 = 48 if adaptive else 56
+    room = 2496 - dir0 * (16 if adaptive else 4) - (seqp + seqt)       # LDS budget per pair of the byte tier
+    byte_ok = room >= 1024
+    byte_pool = min(room & ~15, 2032)
+    if byte_ok and max_tlen + dir0 + 2 > WFA_OFFB_MAX:
+        byte_ok = False
+    if not byte_ok:
+        dir0 = 48
+    static_rows = min(len(wfa_rows(pen)), WFA_OFFB_MAX - 2 - max_tlen) if not adaptive else 0
+    static_pool = min(1568 - (seqp + seqt), 4080) & ~15
+    use_static = (not adaptive and byte_pool != 0 and not knobs.get("GAB_WFA_NO_STATIC") and static_rows >= 16 and static_pool >= 1024)
+    launches, slots = [], 0
+    if n_lds:
+        if use_static:
+            pool2 = int(knobs.get("GAB_WFA_POOL2", 2560))
+            launches.append(("wfa_lds_static<16,false>", static_pool, static_rows))
+            if pool2 > static_pool:
+                launches.append(("wfa_lds_static<16,true>", pool2, static_rows))
+                slots = min(n_lds, max(65536, n_lds // 8)) & ~7
+                if "GAB_WFA_SLOTS" in knobs:
+                    slots = min(n_lds, int(knobs["GAB_WFA_SLOTS"]))
+        else:
+            launches.append((f"wfa_lds<16,{A},OffB>", min(byte_pool, 2046), dir0) if byte_ok else (f"wfa_lds<16,{A},int16_t>", 1024, dir0))
+        launches.append((f"wfa_lds<64,{A},int16_t>", 6144, 128))
+        launches.append((f"wfa_lds<64,{A},int16_t>", 49152, 640))
+        launches.append((f"wfa_global<{A}>", 1 << 20, 4096))
+    return dict(launches=launches, seqp=seqp, seqt=seqt, byte_ok=byte_ok, static_rows=static_rows, static_pool=static_pool,
+                use_static=use_static, slots=slots, n_lds=n_lds, n_big=n_big, adaptive=adaptive)
+
+
+def wfa_launch_holds(launch, model, pad_byte, rows_table):
+    """bool per pair: this launch (kernel, pool, directory / rows) finishes the pair.
+    A static launch gives up on a padding byte, on an M offset > 240, when the table's used_end of the final row exceeds the pool and
+    when that row is not below static_rows; wfa_lds / wfa_global when the final score is not below the directory size (the score
+    steps visit every score that has a wavefront), when the offsets allocated exceed the pool, and -- one-byte offsets -- on an M
+    offset > 240."""
+    kernel, pool, dirsz = launch
+    if kernel.startswith("wfa_lds_static"):
+        row = model["rows"] - 1
+        ok = ~pad_byte & (model["max_m"] <= WFA_OFFB_SAFE) & (row < dirsz)
+        used_end = np.array([r[4] for r in rows_table], np.int64)[np.minimum(row, len(rows_table) - 1)]
+        return ok & (used_end <= pool)
+    ok = (model["score"] < dirsz) & (model["used"] <= pool)
+    if kernel.endswith("OffB>"):
+        ok &= model["max_m"] <= WFA_OFFB_SAFE
+    return ok
+
+
+def wfa_tier_of(batch, pen, model, plan):
+    """-> (tier int array: index into `launches` of the launch that finishes each pair, launches = [(kernel, pool, directory, pairs in,
+    pairs left), ...] in launch order).  The plan's launches come first; what the first wfa_global leaves gets rounds with 8 x the
+    pool and 4 x the directory (at most 2^22 scores) until nothing is left, then the pairs too long for LDS get rounds of their own
+    from 2^20 offsets / 4 096 scores."""
+    pl, tl = batch.pat_len.astype(np.int64), batch.txt_len.astype(np.int64)
+    lds = (pl <= WFA_LDS_MAX_LEN) & (tl <= WFA_LDS_MAX_LEN)
+    pad = wfa_pad_bytes(batch)
+    table = wfa_rows(pen)
+    A = "true" if plan["adaptive"] else "false"
+    tier = np.full(batch.n, -1, np.int64)
+    out = []
+
+    def run(launch, todo):
+        ok = wfa_launch_holds(launch, model, pad, table) & todo
+        tier[ok] = len(out)
+        out.append(launch + (int(todo.sum()), int((todo & ~ok).sum())))
+        return todo & ~ok
+
+    todo = lds.copy()
+    for launch in plan["launches"]:
+        todo = run(launch, todo)
+    for first, todo in ((not plan["launches"], todo), (True, ~lds)):
+        pool, dirsz = (1 << 20, 4096) if first else (1 << 23, 4 * 4096)
+        while todo.any():
+            todo = run((f"wfa_global<{A}>", pool, dirsz), todo)
+            pool, dirsz = pool * 8, min(dirsz * 4, 1 << 22)
+    return tier, out
+
+
+def parse_wfa_trace(text):
+    """GAB_WFA_TRACE lines of ONE gab_wfa_run_device call -> ([(kernel, pool, directory, pairs in, pairs left, resumed or None), ...],
+    {"n_lds", "n_big", "requeued"})"""
+    launches, tail = [], None
+    for line in text.splitlines():
+        m = re.match(r"\[gab_wfa\] launch (\d+) kernel (\S+) pool (\d+) dir (\d+) in (\d+) left (\d+)(?: resumed (\d+))?$", line)
+        if m:
+            assert int(m.group(1)) == len(launches), line
+            launches.append((m.group(2),) + tuple(int(v) for v in m.group(3, 4, 5, 6)) + (None if m.group(7) is None else int(m.group(7)),))
+            continue
+        m = re.match(r"\[gab_wfa\] n_lds (\d+) n_big (\d+) requeued (\d+)$", line)
+        if m:
+            tail = dict(zip(("n_lds", "n_big", "requeued"), (int(v) for v in m.groups())))
+    return launches, tail
+
+
+def wfa_fit(pen, pool, max_score=4096):
+    """(the last score whose history fits `pool` offsets, the next score that has a wavefront) by the recurrence of wfa_rows"""
+    rows = wfa_rows(pen, max_score=max_score, table=False)
+    k = max(i for i, r in enumerate(rows) if r[4] <= pool)
+    return rows[k][0], rows[k + 1][0]
+
+
+_WFA_ACGT = np.frombuffer(b"ACGT", np.uint8)
+
+
+def wfa_mutated(rng, n, err, cut=None):
+    """a random n-base pattern and a text copied from it with `err` errors per base (a third each deletions, insertions and
+    substitutions), the text cut to `cut` bases"""
+    p = _WFA_ACGT[rng.integers(0, 4, n)].tobytes()
+    t = bytearray()
+    for c in p:
+        r = rng.random()
+        if r < err / 3:
+            continue
+        if r < 2 * err / 3:
+            t.append(b"ACGT"[int(rng.integers(0, 4))])
+        t.append(c if r > err else b"ACGT"[int(rng.integers(0, 4))])
+    return p, bytes(t if cut is None else t[:cut])
+
+
+WFA_CENSUS_RATES = (0.0, 0.02, 0.05, 0.08, 0.12, 0.2, 0.35, 0.6)
+
+
+def wfa_census_pairs(n, seed, rates=WFA_CENSUS_RATES, long_pairs=0):
+    """n pairs: patterns of 100 .. 151 bases, texts mutated copies cut to 180 bases, the error rates in turn; `long_pairs` pairs of
+    more than 2 040 bases (1 % errors) spread among them -> (patterns, texts)"""
+    rng = np.random.default_rng(seed)
+    pats, txts = [], []
+    for i in range(n):
+        p, t = wfa_mutated(rng, int(rng.integers(100, 152)), rates[i % len(rates)], 180)
+        pats.append(p); txts.append(t)
+    for k in range(long_pairs):
+        p, t = wfa_mutated(rng, 2041 + 150 * k + int(rng.integers(0, 100)), 0.01)
+        at = (k + 1) * n // (long_pairs + 1)
+        pats.insert(at, p); txts.insert(at, t)
+    return pats, txts
+
+
+def wfa_scored_pair(score, seed, n=150):
+    """an n-base pair built for `score` under (4, 6, 2): score / 4 substitutions two bases apart, or -- score = 2 (mod 4) -- (score - 10)
+    / 4 of them and one 2-base gap behind them.  (Whether a pair really scores that is for the oracle to say: tests/test_wfa_oracle.py
+    asks it.)"""
+    assert score % 2 == 0 and (score % 4 == 0 or score >= 10)
+    rng = np.random.default_rng(seed)
+    p = rng.integers(0, 4, n)
+    subs = score // 4 if score % 4 == 0 else (score - 10) // 4
+    assert 3 + 2 * subs < n - 16
+    t = p.copy()
+    at = 3 + 2 * np.arange(subs)
+    t[at] = (t[at] + 1 + rng.integers(0, 3, subs)) % 4
+    if score % 4:
+        t = np.delete(t, [n - 12, n - 11])
+    return _WFA_ACGT[p].tobytes(), _WFA_ACGT[t].tobytes()
+
+
+WFA_BIG_PENALTIES = ((50, 60, 20), (300, 400, 150), (1000, 1500, 500))       # the directory binds, not the pool
+WFA_SMALL_PENALTIES = ((1, 1, 1), (2, 3, 1), (5, 8, 3), (3, 1, 4))
+WFA_PENALTIES = ((4, 6, 2),) + WFA_SMALL_PENALTIES + WFA_BIG_PENALTIES
+WFA_REDUCTIONS = ((10, 50), (5, 3), (1, 0))
+
+
+def wfa_penalty_pairs(seed=31, n=150):
+    """an identical pair, one / two / three substitutions, a 1-base gap, a 2-base gap, a 1-base insertion plus a 2-base deletion
+    -> (patterns, texts, lambda pen: the scores they were built for)"""
+    rng = np.random.default_rng(seed)
+    p = rng.integers(0, 4, n)
+
+    def sub(t, at):
+        t = t.copy(); t[at] = (t[at] + 1) % 4
+        return t
+    ins = np.insert(p, 40, (p[40] + 1) % 4)               # (a base that differs from its right neighbour's: the gap cannot slide into a match)
+    txts = [p, sub(p, [30]), sub(p, [30, 70]), sub(p, [30, 70, 110]), np.delete(p, 60), np.delete(p, [60, 61]), np.delete(ins, [100, 101])]
+    built = lambda pen: [0, pen[0], 2 * pen[0], 3 * pen[0], pen[1] + pen[2], pen[1] + 2 * pen[2], 2 * pen[1] + 3 * pen[2]]
+    return [_WFA_ACGT[p].tobytes()] * len(txts), [_WFA_ACGT[t].tobytes() for t in txts], built
+
+
+def wfa_limit_pairs(tmax, n=600):
+    """n pairs whose longest text is exactly tmax: patterns of tmax - 25 .. tmax bases, mutated texts cut to tmax, then texts at the
+    limit, pure insertions and pairs far beyond 16 score rows"""
+    rng = np.random.default_rng(tmax)
+    pats, txts = [], []
+    while len(pats) < n - 5:
+        p, t = wfa_mutated(rng, int(rng.integers(tmax - 25, tmax + 1)), float(rng.choice([0.0, 0.01, 0.03, 0.06, 0.12])), tmax)
+        pats.append(p); txts.append(t)
+    pats += [b"ACGT" * 50, b"A" * (tmax - 30), b"ACGTTGCA" * 25]
+    txts += [(b"ACGT" * 60)[:tmax], b"A" * tmax, (b"ACGTTGCA" * 30)[:tmax]]
+    for err in (0.3, 0.5):
+        p, t = wfa_mutated(rng, tmax - 20, err, tmax)
+        pats.append(p); txts.append(t)
+    return pats, txts
+
+
+def wfa_padding_tail_pairs(n=200):
+    """n easy pairs and, among them, pairs whose pattern ends in the text's padding byte 'Y' (the extension runs on past the end of
+    the text: M offsets of 236 .. 246, on both sides of the 240 a byte tier accepts) or whose text ends in the pattern's 'X'"""
+    rng = np.random.default_rng(77)
+    pats, txts = wfa_census_pairs(n, 78, rates=(0.0, 0.02, 0.05))
+    for k, extra in enumerate((56, 59, 60, 61, 62, 66)):
+        p, t = wfa_mutated(rng, 180, 0.0)
+        at = (k + 1) * n // 8
+        pats.insert(at, p + b"Y" * extra); txts.insert(at, t)
+        p, t = wfa_mutated(rng, 150, 0.02, 170)
+        pats.insert(at, p); txts.insert(at, t + b"X" * (extra - 50))
+    return pats, txts
+
+
+_wfa_cases = None
+
+
+def wfa_tier_cases():
+    """the batches of tests/test_wfa_tiers_gpu.py: name -> (patterns, texts, penalties, reduction or None, knobs).  Built once."""
+    global _wfa_cases
+    if _wfa_cases is not None:
+        return _wfa_cases
+    C = {}
+    base_p, base_t = wfa_census_pairs(1500, 1)
+    # a. the census: every kind of launch of the default plan, and three pairs too long for the LDS kernels
+    cp, ct = list(base_p), list(base_t)
+    rng = np.random.default_rng(5)
+    for k in range(3):
+        p, t = wfa_mutated(rng, 2041 + 200 * k + int(rng.integers(0, 100)), 0.01)
+        cp.insert((k + 1) * 375, p); ct.insert((k + 1) * 375, t)
+    C["census"] = (cp, ct, (4, 6, 2), None, {})
+    k1_p, k1_t = base_p[:1000], base_t[:1000]
+    # b. one pair on each side of every pool limit of the default plan, in random places among 200 easy pairs
+    easy_p, easy_t = wfa_census_pairs(200, 3, rates=(0.0, 0.02, 0.05))
+    plan = wfa_plan(gabgen.pairs_from_lists(easy_p, easy_t), (4, 6, 2))
+    bound = []
+    for _, pool, _ in plan["launches"][:-1]:
+        bound += [wfa_scored_pair(s, 7000 + s) + (s,) for s in wfa_fit((4, 6, 2), pool)]
+    bp, bt = list(easy_p), list(easy_t)
+    for (p, t, _), at in zip(bound, np.random.default_rng(4).integers(0, 200, len(bound))):
+        bp.insert(int(at), p); bt.insert(int(at), t)
+    C["boundary"] = (bp, bt, (4, 6, 2), None, {})
+    C["boundary_pairs"] = bound
+    # c. penalties under which the directory sizes 56 / 128 / 640 / 4 096 bind; the small sets on the census recipe
+    for pen in WFA_BIG_PENALTIES:
+        pp, pt, _ = wfa_penalty_pairs()
+        C["pen_%d_%d_%d" % pen] = (pp, pt, pen, None, {})
+    C["pen_50_60_20_nostatic"] = (pp, pt, (50, 60, 20), None, {"GAB_WFA_NO_STATIC": 1})       # (its table has rows enough for the static tier)
+    for pen in WFA_SMALL_PENALTIES:
+        C["census1000_%d_%d_%d" % pen] = (k1_p, k1_t, pen, None, {})
+    # d. the longest text on both sides of the switch that turns the static tier off; M offsets on both sides of 240 in a byte tier
+    for tmax in (227, 228):
+        C["tmax%d" % tmax] = wfa_limit_pairs(tmax) + ((4, 6, 2), None, {})
+    C["tmax228_adaptive_10_50"] = C["tmax228"][:2] + ((4, 6, 2), (10, 50), {})                  # wfa_lds<16,true,int16_t>
+    C["offb_exit"] = wfa_padding_tail_pairs() + ((4, 6, 2), None, {"GAB_WFA_NO_STATIC": 1})
+    # e. adaptive mode: the pool need depends on the data
+    for red in WFA_REDUCTIONS[:2]:
+        C["adaptive_%d_%d" % red] = (k1_p + [b[0] for b in bound], k1_t + [b[1] for b in bound], (4, 6, 2), red, {})
+    # g. more pairs than the grids of the chained launches (also f: more pairs leave the first launch than GAB_WFA_SLOTS = 1002)
+    gp, gt = wfa_census_pairs(3000, 2, rates=(0.1, 0.1, 0.25, 0.1, 0.1, 0.25, 0.1, 0.1, 0.6, 0.25))
+    C["grid"] = (gp, gt, (4, 6, 2), None, {})
+    # f. resume and restart
+    for slots in (0, 3, 1002):
+        C["slots_%d" % slots] = (gp, gt, (4, 6, 2), None, {"GAB_WFA_SLOTS": slots})
+    for pool2 in (1024, 4080):
+        C["pool2_%d" % pool2] = (k1_p, k1_t, (4, 6, 2), None, {"GAB_WFA_POOL2": pool2})
+    _wfa_cases = C
+    return C
+
+
+_wfa_models = {}
+
+
+def wfa_case_model(name):
+    """one case of wfa_tier_cases, run through the model once -> (PairBatch, penalties, reduction, knobs, model, plan, tier, launches)"""
+    pats, txts, pen, red, knobs = wfa_tier_cases()[name]
+    key = (id(pats), pen, red)
+    if key not in _wfa_models:
+        batch = gabgen.pairs_from_lists(pats, txts)
+        _wfa_models[key] = (batch, wfa_model(pats, txts, pen, red))
+    batch, model = _wfa_models[key]
+    plan = wfa_plan(batch, pen, red is not None, knobs)
+    tier, launches = wfa_tier_of(batch, pen, model, plan)
+    return batch, pen, red, knobs, model, plan, tier, launches
+
+
+WFA_CASE_NAMES = (["census", "boundary"] + ["pen_%d_%d_%d" % p for p in WFA_BIG_PENALTIES] + ["pen_50_60_20_nostatic"] + ["census1000_%d_%d_%d" % p for p in WFA_SMALL_PENALTIES] +
+                  ["tmax227", "tmax228", "tmax228_adaptive_10_50", "offb_exit", "adaptive_10_50", "adaptive_5_3", "grid", "slots_0", "slots_3", "slots_1002", "pool2_1024", "pool2_4080"])
+
+
+def wfa_expected_resumed(name):
+    """(fewest, most) pairs the chained static launch of a case can resume, or None when its plan has no such launch.  A pair the
+    first launch leaves is resumed when it stopped for want of pool room (not for a padding byte, a large offset or the end of the
+    row table) and its place in the overflow list is below the slot count; the places are taken in arrival order, so the two
+    numbers differ only when some pairs left cannot be resumed AND there are fewer slots than pairs left."""
+    batch, pen, red, knobs, model, plan, tier, launches = wfa_case_model(name)
+    if len(launches) < 2 or not launches[1][0].startswith("wfa_lds_static"):
+        return None
+    table = wfa_rows(pen)
+    r_pool = min(i for i, r in enumerate(table) if r[4] > launches[0][1])
+    lds = (batch.pat_len <= WFA_LDS_MAX_LEN) & (batch.txt_len <= WFA_LDS_MAX_LEN)
+    left = lds & (tier != 0)
+    sure = left & ~wfa_pad_bytes(batch) & (model["max_m"] <= WFA_OFFB_SAFE) & (r_pool < launches[0][2])
+    maybe = left & ~wfa_pad_bytes(batch) & (model["max_m"] > WFA_OFFB_SAFE) & (r_pool < launches[0][2])
+    n_left, n_sure, n_maybe, slots = int(left.sum()), int(sure.sum()), int(maybe.sum()), plan["slots"]
+    return max(0, min(slots, n_left) - (n_left - n_sure)), min(slots, n_sure + n_maybe)
