@@ -22,6 +22,7 @@
 // Roofline: plen + tlen + 4 algorithmic bytes per pair (the row string is really streamed once per 32-column chunk:
 // 3.1 x, profiles/r01_hbm_traffic.md) against 3.5 VALU per DP cell: integer-VALU bound, ~93 % of the issue rate.
 #include "gab_internal.h"
+#include "gab_pair_stage.h"
 #include "gab_bitvec.h"
 #include <algorithm>
 #include <new>
@@ -478,48 +479,17 @@ extern "C" int gab_bitpal_run(gab_bitpal *h, const char *pat, const int64_t *pat
     if (n == 0) return GAB_OK;
     GAB_CHECK(pat && pat_off && pat_len && txt && txt_off && txt_len && score_out, "gab_bitpal_run: NULL buffer");
     gab_device_guard g(h->device);
-    int64_t pb = 0, tb = 0, pa = INT64_MAX, ta = INT64_MAX;
-    for (int64_t i = 0; i < n; i++) {
-        GAB_CHECK(pat_off[i] >= 0 && txt_off[i] >= 0 && pat_len[i] >= 0 && txt_len[i] >= 0,
-                  "gab_bitpal_run: negative offset/length at pair %lld", (long long)i);
-        pb = std::max(pb, pat_off[i] + pat_len[i]); tb = std::max(tb, txt_off[i] + txt_len[i]);
-        pa = std::min(pa, pat_off[i]); ta = std::min(ta, txt_off[i]);
-    }
-    pa &= ~(int64_t)255; ta &= ~(int64_t)255;      // stage only the referenced window [min, max) of each slab
-    // one slab for both with overlapping windows (the drivers' pair files: '>' and '<' lines interleaved): staged once, not twice
-    const bool shared = pat == txt && std::max(pb, tb) - std::min(pa, ta) <= (pb - pa) + (tb - ta);
-    if (shared) { pa = ta = std::min(pa, ta); pb = tb = std::max(pb, tb); }
-    const size_t ppad = ((size_t)(pb - pa) + 3 + 255) & ~(size_t)255, tpad = shared ? 0 : ((size_t)(tb - ta) + 3 + 255) & ~(size_t)255;
-    const size_t nn = (size_t)n;
-    size_t o = 0;
-    const size_t o_p = o; o += ppad;
-    const size_t o_t = o; o += tpad;
-    const size_t o_po = o; o += 8 * nn;
-    const size_t o_to = o; o += 8 * nn;
-    const size_t o_pl = o; o += 4 * nn;
-    const size_t o_tl = o; o += 4 * nn;
-    const size_t o_sc = o; o += 4 * nn;
-    int rc = h->io.reserve(o);
+    const gab_host_pairs in = {pat, pat_off, pat_len, txt, txt_off, txt_len, n};
+    gab_pair_window w;
+    int rc = gab_pair_scan("gab_bitpal_run", in, &w);
     if (rc) return rc;
-    char *b = h->io.as<char>();
-    hipStream_t s = nullptr;
-    if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    {   // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
-        std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
-        GAB_HIP(hipMemcpyAsync(b + o_p, pat + pa, (size_t)(pb - pa), hipMemcpyHostToDevice, s));
-        if (!shared) GAB_HIP(hipMemcpyAsync(b + o_t, txt + ta, (size_t)(tb - ta), hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_po, pat_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_to, txt_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_pl, pat_len, 4 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_tl, txt_len, 4 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    rc = gab_bitpal_run_device(h, b + o_p - pa, pa + (int64_t)ppad, (const int64_t *)(b + o_po), (const int32_t *)(b + o_pl),
-                               (shared ? b + o_p : b + o_t) - ta, ta + (int64_t)(shared ? ppad : tpad), (const int64_t *)(b + o_to), (const int32_t *)(b + o_tl), n,
-                               (int32_t *)(b + o_sc), s);
+    const gab_pair_layout L = gab_pair_layout_of(GAB_STAGE_SCORES, w.ppad, w.tpad, (size_t)n);
+    gab_staged_pairs d;
+    if ((rc = gab_pair_upload(h->io, h->hs, h->device, in, w, L, &d)) != GAB_OK) return rc;
+    rc = gab_bitpal_run_device(h, d.pat, d.pat_bytes, d.pat_off, d.pat_len, d.txt, d.txt_bytes, d.txt_off, d.txt_len, n, (int32_t *)(d.b + L.sc), d.s);
     if (rc) return rc;
-    GAB_HIP(hipMemcpyAsync(score_out, b + o_sc, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipStreamSynchronize(s));
+    GAB_HIP(hipMemcpyAsync(score_out, d.b + L.sc, 4 * (size_t)n, hipMemcpyDeviceToHost, d.s));
+    GAB_HIP(hipStreamSynchronize(d.s));
     return GAB_OK;
 }
 
@@ -529,7 +499,7 @@ extern "C" int gab_bitpal_reserve(gab_bitpal *h, int64_t max_pairs, int64_t max_
     GAB_CHECK(max_pairs >= 0 && max_pairs < (1ll << 31) && max_seq_bytes >= 0, "gab_bitpal_reserve: size out of range");
     gab_device_guard g(h->device);
     const size_t nn = (size_t)max_pairs;
-    int rc = h->io.reserve(std::max<size_t>(2 * (((size_t)max_seq_bytes + 3 + 511) & ~(size_t)255) + 28 * nn + 1024, (size_t)4 << 20));
+    int rc = h->io.reserve(gab_pair_reserve_bytes(GAB_STAGE_SCORES, max_pairs, max_seq_bytes));
     if (rc) return rc;
     if ((rc = h->ws.reserve(sizeof(BpCounters) + 512 + 3 * 4 * nn)) != GAB_OK) return rc;
     hipStream_t s = nullptr;

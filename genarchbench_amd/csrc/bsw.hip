@@ -892,8 +892,7 @@ extern "C" int gab_bsw_run(gab_bsw *h, const uint8_t *ref, const int64_t *ref_of
     gab_device_guard g(h->device);
     gab_tuning_refresh(&h->tun);
     const bool trace = h->tun.bsw_trace;      // GAB_BSW_TRACE, diagnosis: per-phase wall times of this call on stderr
-    auto now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_0 = now();
+    const double t_0 = gab_now_ms();
     // extent of the two slabs actually referenced: only [min, max) is staged, so a driver can hand a window
     // of a big input (absolute offsets) to each GPU without re-basing its offset arrays.  A scan of all n offsets here is
     // ~1 ms per million pairs of serial host work inside the caller's ROI, and the device validates every pair against the
@@ -937,7 +936,7 @@ extern "C" int gab_bsw_run(gab_bsw *h, const uint8_t *ref, const int64_t *ref_of
     char *b = h->io.as<char>();
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    const double t_1 = now();
+    const double t_1 = gab_now_ms();
     {   // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
         std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
         GAB_HIP(hipMemcpyAsync(b + o_ref, ref + ra, (size_t)(rb - ra), hipMemcpyHostToDevice, s));
@@ -950,7 +949,7 @@ extern "C" int gab_bsw_run(gab_bsw *h, const uint8_t *ref, const int64_t *ref_of
         GAB_HIP(hipStreamSynchronize(s));
     }
     double t_2 = 0;
-    if (trace) { GAB_HIP(hipStreamSynchronize(s)); t_2 = now(); }
+    if (trace) { GAB_HIP(hipStreamSynchronize(s)); t_2 = gab_now_ms(); }
     // virtual slab origins: device address of byte 0 of the caller's slabs
     rc = bsw_run_device_impl(h, (const uint8_t *)(b + o_ref) - ra, ra + (int64_t)rpad, (const int64_t *)(b + o_roff),
                              (const uint8_t *)(b + o_qry) - qa, qa + (int64_t)qpad, (const int64_t *)(b + o_qoff),
@@ -963,12 +962,12 @@ extern "C" int gab_bsw_run(gab_bsw *h, const uint8_t *ref, const int64_t *ref_of
     }
     if (rc) return rc;
     double t_3 = 0;
-    if (trace) { GAB_HIP(hipStreamSynchronize(s)); t_3 = now(); }
+    if (trace) { GAB_HIP(hipStreamSynchronize(s)); t_3 = gab_now_ms(); }
     GAB_HIP(hipMemcpyAsync(score_out, b + o_sc, 4 * nn, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipStreamSynchronize(s));
     if (trace)
         fprintf(stderr, "[gab_bsw_run %p] %lld pairs: host scan %.2f ms, H2D of %.1f MB %.2f ms, sort + DP %.2f ms, D2H %.2f ms\n", (void *)h,
-                (long long)n, t_1 - t_0, (double)((rb - ra) + (qb - qa) + 28 * n) / 1e6, t_2 - t_1, t_3 - t_2, now() - t_3);
+                (long long)n, t_1 - t_0, (double)((rb - ra) + (qb - qa) + 28 * n) / 1e6, t_2 - t_1, t_3 - t_2, gab_now_ms() - t_3);
     return GAB_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stddef.h>
+#include <time.h>
 #include <mutex>
 #include "../../include/gab.h"
 
@@ -81,6 +82,7 @@ int gab_check_device(int device);
 bool gab_is_pinned(const void *p);      // hipHostMalloc'ed / registered host memory (direct DMA) or pageable
 
 static inline int64_t gab_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline double gab_now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }      // the wall times of the *_TRACE lines
 
 // ---- experiment knobs and test hooks -------------------------------------------------------------------------------
 // Every GAB_* environment switch the entry points honour lives in this ONE struct; gab_tuning_load (gab_core.hip) is the only

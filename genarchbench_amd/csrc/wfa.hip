@@ -27,6 +27,7 @@
 // Roofline: plen + tlen + |cigar| + 4 bytes of HBM traffic per pair; the work is latency-bound
 // LDS traffic (sum over scores of the wavefront width + the extended matches).
 #include "gab_internal.h"
+#include "gab_pair_stage.h"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -1296,56 +1297,58 @@ extern "C" int gab_wfa_run(gab_wfa *h, const char *pat, const int64_t *pat_off, 
     GAB_CHECK(pat && pat_off && pat_len && txt && txt_off && txt_len && ops_out && ops_off && ops_len_out && score_out,
               "gab_wfa_run: NULL buffer");
     gab_device_guard g(h->device);
-    int64_t pb = 0, tb = 0, ob = 0, pa = INT64_MAX, ta = INT64_MAX, oa = INT64_MAX;
-    for (int64_t i = 0; i < n; i++) {
-        GAB_CHECK(pat_off[i] >= 0 && txt_off[i] >= 0 && ops_off[i] >= 0 && pat_len[i] >= 0 && txt_len[i] >= 0,
-                  "gab_wfa_run: negative offset/length at pair %lld", (long long)i);
-        pb = std::max(pb, pat_off[i] + pat_len[i]); tb = std::max(tb, txt_off[i] + txt_len[i]);
-        ob = std::max(ob, ops_off[i] + pat_len[i] + txt_len[i]);
-        pa = std::min(pa, pat_off[i]); ta = std::min(ta, txt_off[i]); oa = std::min(oa, ops_off[i]);
-    }
-    pa &= ~(int64_t)255; ta &= ~(int64_t)255;   // stage only the referenced windows (oa stays exact: it is written back)
-    // one slab for both with overlapping windows (the drivers' pair files: '>' and '<' lines interleaved): staged once, not twice
-    const bool shared = pat == txt && std::max(pb, tb) - std::min(pa, ta) <= (pb - pa) + (tb - ta);
-    if (shared) { pa = ta = std::min(pa, ta); pb = tb = std::max(pb, tb); }
-    const size_t ppad = ((size_t)(pb - pa) + 3 + 255) & ~(size_t)255, tpad = shared ? 0 : ((size_t)(tb - ta) + 3 + 255) & ~(size_t)255;
-    const size_t opad = ((size_t)(ob - oa) + 255) & ~(size_t)255, nn = (size_t)n;
-    size_t o = 0;
-    const size_t o_p = o; o += ppad;
-    const size_t o_t = o; o += tpad;
-    const size_t o_ops = o; o += opad;
-    const size_t o_po = o; o += 8 * nn;
-    const size_t o_to = o; o += 8 * nn;
-    const size_t o_oo = o; o += 8 * nn;
-    const size_t o_pl = o; o += 4 * nn;
-    const size_t o_tl = o; o += 4 * nn;
-    const size_t o_ol = o; o += 4 * nn;
-    const size_t o_sc = o; o += 4 * nn;
-    int rc = h->io.reserve(o);
+    const gab_host_pairs in = {pat, pat_off, pat_len, txt, txt_off, txt_len, n};
+    gab_pair_window w;
+    int64_t ob = 0, oa = INT64_MAX;             // the window of the operations (oa stays exact: it is written back)
+    int rc = gab_pair_scan("gab_wfa_run", in, &w, [&](int64_t i) {
+        ob = std::max(ob, ops_off[i] + pat_len[i] + txt_len[i]); oa = std::min(oa, ops_off[i]);
+        return ops_off[i] >= 0;
+    });
     if (rc) return rc;
-    char *b = h->io.as<char>();
-    hipStream_t s = nullptr;
-    if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    {   // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
-        std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
-        GAB_HIP(hipMemcpyAsync(b + o_p, pat + pa, (size_t)(pb - pa), hipMemcpyHostToDevice, s));
-        if (!shared) GAB_HIP(hipMemcpyAsync(b + o_t, txt + ta, (size_t)(tb - ta), hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_po, pat_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_to, txt_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_oo, ops_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_pl, pat_len, 4 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_tl, txt_len, 4 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    rc = gab_wfa_run_device(h, b + o_p - pa, pa + (int64_t)ppad, (const int64_t *)(b + o_po), (const int32_t *)(b + o_pl),
-                            (shared ? b + o_p : b + o_t) - ta, ta + (int64_t)(shared ? ppad : tpad), (const int64_t *)(b + o_to), (const int32_t *)(b + o_tl), n, b + o_ops - oa,
-                            (const int64_t *)(b + o_oo), (int32_t *)(b + o_ol), (int32_t *)(b + o_sc), s);
+    const size_t nn = (size_t)n;
+    const gab_pair_layout L = gab_pair_layout_of(GAB_STAGE_OPS, w.ppad, w.tpad, nn, gab_pad256((size_t)(ob - oa)));
+    gab_staged_pairs d;
+    if ((rc = gab_pair_upload(h->io, h->hs, h->device, in, w, L, &d, ops_off)) != GAB_OK) return rc;
+    char *b = d.b;
+    rc = gab_wfa_run_device(h, d.pat, d.pat_bytes, d.pat_off, d.pat_len, d.txt, d.txt_bytes, d.txt_off, d.txt_len, n, b + L.ops - oa,
+                            (const int64_t *)(b + L.oo), (int32_t *)(b + L.ol), (int32_t *)(b + L.sc), d.s);
     if (rc) return rc;
     // only each pair's own operations are defined; copy the window back and let the caller read ops_len[i] bytes per pair
-    GAB_HIP(hipMemcpyAsync(ops_out + oa, b + o_ops, (size_t)(ob - oa), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(ops_len_out, b + o_ol, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(score_out, b + o_sc, 4 * nn, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(ops_out + oa, b + L.ops, (size_t)(ob - oa), hipMemcpyDeviceToHost, d.s));
+    GAB_HIP(hipMemcpyAsync(ops_len_out, b + L.ol, 4 * nn, hipMemcpyDeviceToHost, d.s));
+    GAB_HIP(hipMemcpyAsync(score_out, b + L.sc, 4 * nn, hipMemcpyDeviceToHost, d.s));
+    GAB_HIP(hipStreamSynchronize(d.s));
+    return GAB_OK;
+}
+
+// The second half of gab_wfa_run_packed / gab_wfa_run_packed_device (`who`): the operations gab_wfa_run_device left on the device
+// (`ops`, `ops_off`, lengths at L.ol of the staging buffer `b`) as run-length text at L.text, then the total, the text's offsets and
+// lengths and the scores to the host, and the text itself when it fits `capacity` -- else GAB_ERANGE, *total says what would.
+// t_small (may be NULL): the time the small arrays had arrived at.
+static int wfa_pack_text(gab_wfa *h, const char *who, hipStream_t s, char *b, const gab_pair_layout &L, const char *ops, const int64_t *ops_off,
+                         int64_t n, char *cigar_out, int64_t capacity, int64_t *cigar_off_out, int32_t *cigar_len_out, int32_t *score_out,
+                         int64_t *total, double *t_small = nullptr) {
+    const size_t nn = (size_t)n;
+    GAB_HIP(hipMemsetAsync(b + L.cur, 0, 8, s));
+    hipLaunchKernelGGL(wfa_rle_pack, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, ops, ops_off, (const int32_t *)(b + L.ol), (uint32_t)n, b + L.text,
+                       (unsigned long long)capacity, (unsigned long long *)(b + L.cur), (int64_t *)(b + L.co), (int32_t *)(b + L.cl));
+    GAB_HIP(hipGetLastError());
+    unsigned long long *h_cur = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->h_ct) + 128);
+    GAB_HIP(hipMemcpyAsync(h_cur, b + L.cur, 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(cigar_off_out, b + L.co, 8 * nn, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(cigar_len_out, b + L.cl, 4 * nn, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(score_out, b + L.sc, 4 * nn, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipStreamSynchronize(s));
+    if (t_small) *t_small = gab_now_ms();
+    *total = (int64_t)*h_cur;
+    if (*total > capacity) {
+        gab_set_error("%s: %lld bytes of CIGAR text do not fit the caller's %lld", who, (long long)*total, (long long)capacity);
+        return GAB_ERANGE;
+    }
+    if (*total) {
+        GAB_HIP(hipMemcpyAsync(cigar_out, b + L.text, (size_t)*total, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+    }
     return GAB_OK;
 }
 
@@ -1363,17 +1366,16 @@ extern "C" int gab_wfa_run_packed(gab_wfa *h, const char *pat, const int64_t *pa
     gab_device_guard g(h->device);
     gab_tuning_refresh(&h->tun);
     const bool trace = h->tun.wfa_trace;      // GAB_WFA_TRACE, diagnosis: per-phase wall times of this call on stderr
-    auto now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_0 = now();
-    int64_t pb = 0, tb = 0, pa = INT64_MAX, ta = INT64_MAX, stride = 0, room = 0;
-    for (int64_t i = 0; i < n; i++) {
-        GAB_CHECK(pat_off[i] >= 0 && txt_off[i] >= 0 && pat_len[i] >= 0 && txt_len[i] >= 0,
-                  "gab_wfa_run_packed: negative offset/length at pair %lld", (long long)i);
-        pb = std::max(pb, pat_off[i] + pat_len[i]); tb = std::max(tb, txt_off[i] + txt_len[i]);
-        pa = std::min(pa, pat_off[i]); ta = std::min(ta, txt_off[i]);
+    const double t_0 = gab_now_ms();
+    const gab_host_pairs in = {pat, pat_off, pat_len, txt, txt_off, txt_len, n};
+    gab_pair_window w;
+    int64_t stride = 0, room = 0;
+    int rc = gab_pair_scan("gab_wfa_run_packed", in, &w, [&](int64_t i) {
         stride = std::max<int64_t>(stride, (int64_t)pat_len[i] + txt_len[i]);
         room += (((int64_t)pat_len[i] + txt_len[i]) + 7) & ~(int64_t)7;
-    }
+        return true;
+    });
+    if (rc) return rc;
     stride = (stride + 7) & ~(int64_t)7;
     // operation room on the device: a fixed stride per pair (no offset array to build or copy) unless one long pair among
     // short ones would make that more than twice the sum of the pairs' own rooms -- then exact offsets, built here
@@ -1384,80 +1386,28 @@ extern "C" int gab_wfa_run_packed(gab_wfa *h, const char *pat, const int64_t *pa
         int64_t at = 0;
         for (int64_t i = 0; i < n; i++) { exact[(size_t)i] = at; at += (((int64_t)pat_len[i] + txt_len[i]) + 7) & ~(int64_t)7; }
     }
-    pa &= ~(int64_t)255; ta &= ~(int64_t)255;
-    const bool shared = pat == txt && std::max(pb, tb) - std::min(pa, ta) <= (pb - pa) + (tb - ta);
-    if (shared) { pa = ta = std::min(pa, ta); pb = tb = std::max(pb, tb); }
-    const size_t ppad = ((size_t)(pb - pa) + 3 + 255) & ~(size_t)255, tpad = shared ? 0 : ((size_t)(tb - ta) + 3 + 255) & ~(size_t)255;
-    const size_t nn = (size_t)n, opad = ((size_t)(fixed ? stride * n : room) + 16 + 255) & ~(size_t)255, cpad = ((size_t)capacity + 255) & ~(size_t)255;
-    size_t o = 0;
-    const size_t o_p = o; o += ppad;
-    const size_t o_t = o; o += tpad;
-    const size_t o_ops = o; o += opad;
-    const size_t o_txt = o; o += cpad;
-    const size_t o_po = o; o += 8 * nn;
-    const size_t o_to = o; o += 8 * nn;
-    const size_t o_oo = o; o += 8 * nn;
-    const size_t o_co = o; o += 8 * nn;
-    const size_t o_pl = o; o += 4 * nn;
-    const size_t o_tl = o; o += 4 * nn;
-    const size_t o_ol = o; o += 4 * nn;
-    const size_t o_cl = o; o += 4 * nn;
-    const size_t o_sc = o; o += 4 * nn;
-    o = (o + 255) & ~(size_t)255;                  // (a 64-bit atomic lives here)
-    const size_t o_cur = o; o += 256;
-    GAB_CHECK_ATOMIC64(o_cur);                       // wfa_rle_pack's 64-bit cursor
-    int rc = h->io.reserve(o);
-    if (rc) return rc;
-    char *b = h->io.as<char>();
-    hipStream_t s = nullptr;
-    if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    const double t_1 = now();
-    double t_gate = 0;
-    {   // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
-        std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
-        t_gate = now();
-        GAB_HIP(hipMemcpyAsync(b + o_p, pat + pa, (size_t)(pb - pa), hipMemcpyHostToDevice, s));
-        if (!shared) GAB_HIP(hipMemcpyAsync(b + o_t, txt + ta, (size_t)(tb - ta), hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_po, pat_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_to, txt_off, 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_pl, pat_len, 4 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_tl, txt_len, 4 * nn, hipMemcpyHostToDevice, s));
-        if (!fixed) GAB_HIP(hipMemcpyAsync(b + o_oo, exact.data(), 8 * nn, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    const double t_2 = now();
-    const unsigned grid = (unsigned)((nn + 255) / 256);
-    if (fixed) hipLaunchKernelGGL(wfa_fill_stride, dim3(grid), dim3(256), 0, s, (int64_t *)(b + o_oo), (uint32_t)n, stride);
+    const size_t nn = (size_t)n;
+    const gab_pair_layout L = gab_pair_layout_of(GAB_STAGE_TEXT, w.ppad, w.tpad, nn, gab_pad256((size_t)(fixed ? stride * n : room) + 16), gab_pad256((size_t)capacity));
+    GAB_CHECK_ATOMIC64(L.cur);                       // wfa_rle_pack's 64-bit cursor
+    gab_staged_pairs d;
+    double t_up[2] = {0, 0};                         // buffers ready, copy gate obtained
+    if ((rc = gab_pair_upload(h->io, h->hs, h->device, in, w, L, &d, fixed ? nullptr : exact.data(), true, t_up)) != GAB_OK) return rc;
+    const double t_2 = gab_now_ms();
+    char *b = d.b;
+    if (fixed) hipLaunchKernelGGL(wfa_fill_stride, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, d.s, (int64_t *)(b + L.oo), (uint32_t)n, stride);
     GAB_HIP(hipGetLastError());
-    rc = gab_wfa_run_device(h, b + o_p - pa, pa + (int64_t)ppad, (const int64_t *)(b + o_po), (const int32_t *)(b + o_pl),
-                            (shared ? b + o_p : b + o_t) - ta, ta + (int64_t)(shared ? ppad : tpad), (const int64_t *)(b + o_to), (const int32_t *)(b + o_tl), n, b + o_ops,
-                            (const int64_t *)(b + o_oo), (int32_t *)(b + o_ol), (int32_t *)(b + o_sc), s);
+    rc = gab_wfa_run_device(h, d.pat, d.pat_bytes, d.pat_off, d.pat_len, d.txt, d.txt_bytes, d.txt_off, d.txt_len, n, b + L.ops,
+                            (const int64_t *)(b + L.oo), (int32_t *)(b + L.ol), (int32_t *)(b + L.sc), d.s);
     if (rc) return rc;
-    GAB_HIP(hipMemsetAsync(b + o_cur, 0, 8, s));
-    hipLaunchKernelGGL(wfa_rle_pack, dim3(grid), dim3(256), 0, s, (const char *)(b + o_ops), (const int64_t *)(b + o_oo), (const int32_t *)(b + o_ol),
-                       (uint32_t)n, b + o_txt, (unsigned long long)capacity, (unsigned long long *)(b + o_cur), (int64_t *)(b + o_co), (int32_t *)(b + o_cl));
-    GAB_HIP(hipGetLastError());
-    unsigned long long *h_cur = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->h_ct) + 128);
-    GAB_HIP(hipMemcpyAsync(h_cur, b + o_cur, 8, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(cigar_off_out, b + o_co, 8 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(cigar_len_out, b + o_cl, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(score_out, b + o_sc, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipStreamSynchronize(s));
-    const double t_3 = now();
-    const int64_t total = (int64_t)*h_cur;
+    int64_t total = 0; double t_3 = 0;
+    rc = wfa_pack_text(h, "gab_wfa_run_packed", d.s, b, L, b + L.ops, (const int64_t *)(b + L.oo), n, cigar_out, capacity, cigar_off_out, cigar_len_out,
+                       score_out, &total, &t_3);
     if (cigar_bytes) *cigar_bytes = total;
-    if (total > capacity) {
-        gab_set_error("gab_wfa_run_packed: %lld bytes of CIGAR text do not fit the caller's %lld", (long long)total, (long long)capacity);
-        return GAB_ERANGE;
-    }
-    if (total) {
-        GAB_HIP(hipMemcpyAsync(cigar_out, b + o_txt, (size_t)total, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
+    if (rc) return rc;
     if (trace)
         fprintf(stderr, "[gab_wfa_run_packed %p] %lld pairs: host scan + buffers %.2f ms, wait for the copy gate %.2f ms, H2D of %.1f MB %.2f ms, "
-                        "kernels + small D2H %.2f ms, D2H of %.1f MB of text %.2f ms (t0 = %.2f)\n", (void *)h, (long long)n, t_1 - t_0, t_gate - t_1,
-                (double)((pb - pa) + 24 * n) / 1e6, t_2 - t_gate, t_3 - t_2, (double)total / 1e6, now() - t_3, t_0);
+                        "kernels + small D2H %.2f ms, D2H of %.1f MB of text %.2f ms (t0 = %.2f)\n", (void *)h, (long long)n, t_up[0] - t_0, t_up[1] - t_up[0],
+                (double)((w.pb - w.pa) + 24 * n) / 1e6, t_2 - t_up[1], t_3 - t_2, (double)total / 1e6, gab_now_ms() - t_3, t_0);
     return GAB_OK;
 }
 
@@ -1476,46 +1426,24 @@ extern "C" int gab_wfa_run_packed_device(gab_wfa *h, const char *pat, int64_t pa
     GAB_CHECK(pat && pat_off && pat_len && txt && txt_off && txt_len && ops && ops_off && cigar_off_out && cigar_len_out && score_out &&
               capacity >= 0 && (cigar_out || capacity == 0), "gab_wfa_run_packed_device: NULL buffer");
     gab_device_guard g(h->device);
-    const size_t nn = (size_t)n, cpad = ((size_t)capacity + 255) & ~(size_t)255;
-    size_t o = 0;
-    const size_t o_txt = o; o += cpad;
-    const size_t o_co = o; o += 8 * nn;
-    const size_t o_ol = o; o += 4 * nn;
-    const size_t o_cl = o; o += 4 * nn;
-    const size_t o_sc = o; o += 4 * nn;
-    o = (o + 255) & ~(size_t)255;                  // (a 64-bit atomic lives here)
-    const size_t o_cur = o; o += 256;
-    GAB_CHECK_ATOMIC64(o_cur);
-    int rc = h->io.reserve(o);
+    const size_t nn = (size_t)n;
+    gab_stage_bump a;                             // (no pairs to stage: the text, its index, the lengths and scores, the cursor)
+    gab_pair_layout L = {};
+    L.text = a.region(gab_pad256((size_t)capacity)); L.co = a.a8(nn);
+    L.ol = a.a4(nn); L.cl = a.a4(nn); L.sc = a.a4(nn); L.cur = a.cursor();
+    GAB_CHECK_ATOMIC64(L.cur);
+    int rc = h->io.reserve(a.o);
     if (rc) return rc;
     char *b = h->io.as<char>();
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    rc = gab_wfa_run_device(h, pat, pat_bytes, pat_off, pat_len, txt, txt_bytes, txt_off, txt_len, n, ops, ops_off, (int32_t *)(b + o_ol),
-                            (int32_t *)(b + o_sc), s);
+    rc = gab_wfa_run_device(h, pat, pat_bytes, pat_off, pat_len, txt, txt_bytes, txt_off, txt_len, n, ops, ops_off, (int32_t *)(b + L.ol),
+                            (int32_t *)(b + L.sc), s);
     if (rc) return rc;
-    const unsigned grid = (unsigned)((nn + 255) / 256);
-    GAB_HIP(hipMemsetAsync(b + o_cur, 0, 8, s));
-    hipLaunchKernelGGL(wfa_rle_pack, dim3(grid), dim3(256), 0, s, (const char *)ops, ops_off, (const int32_t *)(b + o_ol), (uint32_t)n, b + o_txt,
-                       (unsigned long long)capacity, (unsigned long long *)(b + o_cur), (int64_t *)(b + o_co), (int32_t *)(b + o_cl));
-    GAB_HIP(hipGetLastError());
-    unsigned long long *h_cur = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->h_ct) + 128);
-    GAB_HIP(hipMemcpyAsync(h_cur, b + o_cur, 8, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(cigar_off_out, b + o_co, 8 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(cigar_len_out, b + o_cl, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(score_out, b + o_sc, 4 * nn, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipStreamSynchronize(s));
-    const int64_t total = (int64_t)*h_cur;
+    int64_t total = 0;
+    rc = wfa_pack_text(h, "gab_wfa_run_packed_device", s, b, L, ops, ops_off, n, cigar_out, capacity, cigar_off_out, cigar_len_out, score_out, &total);
     if (cigar_bytes) *cigar_bytes = total;
-    if (total > capacity) {
-        gab_set_error("gab_wfa_run_packed_device: %lld bytes of CIGAR text do not fit the caller's %lld", (long long)total, (long long)capacity);
-        return GAB_ERANGE;
-    }
-    if (total) {
-        GAB_HIP(hipMemcpyAsync(cigar_out, b + o_txt, (size_t)total, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    return GAB_OK;
+    return rc;
 }
 
 // see gab_bpm_reserve; max_ops_bytes = the room of the CIGAR operations (pattern + text length per pair)
@@ -1524,8 +1452,8 @@ extern "C" int gab_wfa_reserve(gab_wfa *h, int64_t max_pairs, int64_t max_seq_by
     GAB_CHECK(max_pairs >= 0 && max_pairs < (1ll << 31) && max_seq_bytes >= 0 && max_ops_bytes >= 0, "gab_wfa_reserve: size out of range");
     gab_device_guard g(h->device);
     const size_t nn = (size_t)max_pairs;
-    int rc = h->io.reserve(std::max<size_t>(2 * (((size_t)max_seq_bytes + 3 + 511) & ~(size_t)255) + (((size_t)max_ops_bytes + 511) & ~(size_t)255) + 60 * nn + 2048,
-                                            (size_t)4 << 20));
+    // gab_wfa_run_packed's layout (gab_wfa_run's is part of it) with 8 bytes of printed text per pair: more text than that and the first call grows the buffer
+    int rc = h->io.reserve(gab_pair_reserve_bytes(GAB_STAGE_TEXT, max_pairs, max_seq_bytes, gab_pad256((size_t)max_ops_bytes + 256), gab_pad256(8 * nn)));
     if (rc) return rc;
     if ((rc = h->ws.reserve(kCountersBytes + kSlotsBytes + 3 * 4 * nn + 1024)) != GAB_OK) return rc;
     {   // the hand-over slots of the two static tiers (gab_wfa_run_device: headers of all pairs + a pool per slot): 80 MB for a
