@@ -1,10 +1,14 @@
 /* kmer-cnt -- drop-in driver of the kmer-cnt benchmark (Flye's solid k-mer counter) on MI355X.
  *
  *     kmer-cnt --reads a.fasta[,b.fastq.gz,...] --config F [--kmer K] [--min-read N] [--min-ovlp N] [--threads T] [--log F] [--debug]
+ *              [-g N | --gpus N]
  *
  * Options, the "Hash size: N" / "Total k-mers N" debug lines and the "Kernel time: %.3f sec" line on stderr are those of the
  * reference's driver (kmer-cnt/kmer_cnt.cpp:47-125, 155-337; the two counts: kmer-cnt/vertex_index.cpp:858-859).  --threads only
- * shaped the CPU scheduling and is accepted and ignored.  One GPU: partial tables of several GPUs would need a merge.
+ * shaped the CPU scheduling and is accepted and ignored.  -g N / --gpus N (default $GAB_GPUS, else 1): N GPUs, each counting one
+ * of N partitions of the KEY space (include/gab.h: gab_kmer_count_part) -- every GPU walks all reads and inserts only the k-mers
+ * whose hash falls into its partition, so the partial results are disjoint: the two printed numbers add, and no GPU talks to
+ * another.
  *
  * Outside the region of interest, as in the reference: the config file (key = value lines, '#' comments, "%include other.cfg"
  * relative to the including file, kmer-cnt/config.h:36-72; only kmer_size and use_minimizers are read), then every reads file
@@ -17,8 +21,8 @@
  * the same to the record's text (positions counted from the start of the record, its lines joined), which is what makes its
  * numbers equal the reference's on reads with N.  Reads LONGER than max(--min-read, --min-ovlp) are kept
  * (kmer-cnt/kmer_cnt.cpp:205, kmer-cnt/sequence_container.cpp:100-106).
- * Inside it: ONE gab_kmer_count over the kept reads (the copy of the reads to the GPU included), where the reference runs
- * vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).
+ * Inside it: ONE gab_kmer_count_part per GPU over the kept reads, all at once (that GPU's copy of the reads included), where the
+ * reference runs vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).  -g 1 is one gab_kmer_count_part(0 of 1) = gab_kmer_count.
  */
 #define GAB_ENERGY_STREAM stderr      /* where the reference prints "Energy consumption:" in this driver */
 #include "../common/gab_driver.h"
@@ -209,7 +213,7 @@ static void load_file(const char *name, kc_reads *R, int64_t min_len) {
 
 static void usage(void) {
     fprintf(stderr, "Usage: kmer-cnt  --reads path --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
-                    "\t\t[--threads num] [--log path] [--debug] [-h]\n\n"
+                    "\t\t[--threads num] [--log path] [--debug] [-g num | --gpus num] [-h]\n\n"
                     "Required arguments:\n"
                     "  --reads path\tcomma-separated list of read files (FASTA / FASTQ, plain or gzip)\n"
                     "  --config path\tpath to the config file\n\n"
@@ -219,17 +223,31 @@ static void usage(void) {
                     "  --min-read length\treads not longer than max(this, --min-ovlp) are dropped [default = 0]\n"
                     "  --debug \t\tenable debug output [default = false]\n"
                     "  --log log_file\toutput log to file [default = not set]\n"
-                    "  --threads num_threads\taccepted and ignored (the count runs on one GPU)\n", GAB_KMER_MAX_K);
+                    "  --threads num_threads\taccepted and ignored (the count runs on the GPUs)\n"
+                    "  -g, --gpus num\tGPUs to count on, each one partition of the k-mers [default = $GAB_GPUS, else 1]\n", GAB_KMER_MAX_K);
+}
+
+/* one partition per logical GPU, run by gab_run_parts */
+typedef struct {
+    gab_kmer **h; gab_kmer_result *res; int *rc; char (*err)[512];
+    const kc_reads *R; int kmer, nparts; int32_t min_len;
+} kc_parts;
+static void count_part(int g, void *arg) {
+    kc_parts *P = (kc_parts *)arg;
+    P->rc[g] = gab_kmer_count_part(P->h[g], P->R->seq, P->R->off, P->R->len, P->R->n, P->kmer, P->min_len, g, P->nparts, &P->res[g]);
+    if (P->rc[g]) snprintf(P->err[g], sizeof P->err[g], "%s", gab_last_error());      /* (the message is the calling thread's) */
 }
 
 int main(int argc, char **argv) {
-    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, c, idx = 0;
+    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, c, idx = 0;
     const char *reads = NULL, *config = NULL, *logfile = NULL;
     static struct option lo[] = {{"reads", required_argument, 0, 0}, {"config", required_argument, 0, 0}, {"min-read", required_argument, 0, 0},
                                  {"log", required_argument, 0, 0}, {"threads", required_argument, 0, 0}, {"kmer", required_argument, 0, 0},
-                                 {"min-ovlp", required_argument, 0, 0}, {"debug", no_argument, 0, 0}, {0, 0, 0, 0}};
-    while ((c = getopt_long(argc, argv, "h", lo, &idx)) != -1) {
+                                 {"min-ovlp", required_argument, 0, 0}, {"debug", no_argument, 0, 0}, {"gpus", required_argument, 0, 'g'},
+                                 {0, 0, 0, 0}};
+    while ((c = getopt_long(argc, argv, "hg:", lo, &idx)) != -1) {
         if (c == 'h') { usage(); return 0; }
+        if (c == 'g') { gpus_flag = atoi(optarg); if (gpus_flag < 1) { usage(); return 1; } continue; }
         if (c != 0) { usage(); return 1; }
         const char *name = lo[idx].name;
         if (!strcmp(name, "kmer")) kmer = atoi(optarg);
@@ -270,29 +288,57 @@ int main(int argc, char **argv) {
     free(list);
     log_debug("Reads: %lld of %lld records kept, %zu bases", (long long)R.n, (long long)R.seen, R.bytes);
 
-    gab_kmer *h = NULL;
-    GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(0), &h), "gab_kmer_create");
-    GAB_DIE_IF(gab_kmer_reserve(h, R.n, (int64_t)R.bytes), "gab_kmer_reserve");        /* buffers before the region of interest */
+    int ngpus = gab_pick_gpus(gpus_flag);
+    if (ngpus > GAB_KMER_MAX_PARTS) ngpus = GAB_KMER_MAX_PARTS;
+    log_debug("Counting on %d GPU(s), one key-space partition each", ngpus);
+    gab_kmer **hs = (gab_kmer **)calloc((size_t)ngpus, sizeof *hs);
+    gab_kmer_result *part_res = (gab_kmer_result *)calloc((size_t)ngpus, sizeof *part_res);
+    int *part_rc = (int *)calloc((size_t)ngpus, sizeof *part_rc);
+    char (*part_err)[512] = (char (*)[512])calloc((size_t)ngpus, 512);
+    if (!hs || !part_res || !part_rc || !part_err) die("out of memory");
+    for (int g = 0; g < ngpus; g++) {                                                  /* buffers before the region of interest */
+        GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(g), &hs[g]), "gab_kmer_create");
+        GAB_DIE_IF(gab_kmer_reserve_part(hs[g], R.n, (int64_t)R.bytes, ngpus), "gab_kmer_reserve_part");
+    }
     if (R.bytes) gab_pin(R.seq, R.bytes);
+    kc_parts P = {hs, part_res, part_rc, part_err, &R, kmer, ngpus, (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len)};
     gab_kmer_result res;
-    memset(&res, 0xff, sizeof res);
+    memset(&res, 0, sizeof res);
 
     const double t0 = gab_now();
-    gab_roi_begin();
-    GAB_DIE_IF(gab_kmer_count(h, R.seq, R.off, R.len, R.n, kmer, (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len), &res), "gab_kmer_count");
+    gab_roi_begin_n(ngpus);
+    if (ngpus == 1) count_part(0, &P);
+    else gab_run_parts(ngpus, count_part, &P);
+    for (int g = 0; g < ngpus; g++) {
+        if (part_rc[g]) { fprintf(stderr, "ERROR: gab_kmer_count_part failed (%d): %s\n", part_rc[g], part_err[g]); exit(EXIT_FAILURE); }
+        /* disjoint partitions of the keys: the counts add, the largest count is the largest of them */
+        res.reads_kept = part_res[g].reads_kept; res.positions = part_res[g].positions;
+        res.distinct += part_res[g].distinct; res.total_kmers += part_res[g].total_kmers; res.hash_size += part_res[g].hash_size;
+        if (part_res[g].max_count > res.max_count) res.max_count = part_res[g].max_count;
+    }
     log_debug("Hash size: %lld", (long long)res.hash_size);
     log_debug("Total k-mers %lld", (long long)res.total_kmers);
     gab_roi_end();
     const double t1 = gab_now();
 
-    int64_t probes = 0, merged = 0;
-    float kernel_ms = 0, total_ms = 0;
-    if (gab_kmer_last_stats(h, &probes, &merged, &kernel_ms, &total_ms) == 0)
-        log_debug("Distinct k-mers: %lld, positions: %lld, largest count: %lld; device: count stage %.3f ms, call %.3f ms", (long long)res.distinct,
-                  (long long)res.positions, (long long)res.max_count, kernel_ms, total_ms);
+    float kernel_ms = 0, total_ms = 0;                                                  /* the slowest partition's */
+    int retried = 0;
+    for (int g = 0; g < ngpus; g++) {
+        float km = 0, tm = 0;
+        int rt = 0;
+        if (gab_kmer_last_stats(hs[g], NULL, NULL, &km, &tm) == 0 && gab_kmer_last_part(hs[g], NULL, NULL, NULL, &rt) == 0) {
+            if (km > kernel_ms) kernel_ms = km;
+            if (tm > total_ms) total_ms = tm;
+            retried += rt;
+        }
+    }
+    log_debug("Distinct k-mers: %lld, positions: %lld, largest count: %lld; device: count stage %.3f ms, call %.3f ms", (long long)res.distinct,
+              (long long)res.positions, (long long)res.max_count, kernel_ms, total_ms);
+    if (retried) log_debug("%d partition(s) filled their first table and were counted again in a larger one", retried);
     fprintf(stderr, "Kernel time: %.3f sec\n", t1 - t0);
     if (R.bytes) gab_unpin(R.seq);
-    gab_kmer_destroy(h);
+    for (int g = 0; g < ngpus; g++) gab_kmer_destroy(hs[g]);
+    free(hs); free(part_res); free(part_rc); free(part_err);
     free(R.seq); free(R.off); free(R.len);
     if (g_log) fclose(g_log);
     return 0;

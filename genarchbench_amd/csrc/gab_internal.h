@@ -112,6 +112,8 @@ struct gab_tuning {
     int fmi_lds_entries = 0, fmi_waves = 0, fmi_wide = 1, fmi_wide_cap = 0, fmi_kmer_depth = -1;      // (depth: -1 = unset)
     bool fmi_wide_lists = false, fmi_debug = false;
     long long fmi_batch = 0, fmi_scratch_mb = 0;
+    // kmer-cnt
+    bool kmer_part_floor = false;                    // GAB_KMER_PART_FLOOR: a partitioned count starts in the 16-line floor table
 };
 void gab_tuning_load(gab_tuning *t);
 bool gab_tuning_live();                             // $GAB_TUNING_LIVE

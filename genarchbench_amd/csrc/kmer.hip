@@ -20,6 +20,10 @@
 //   kmer_reduce   one pass over the table: distinct, sum ceil(c / 256), #(c >= 256), largest count; per-wave partial sums, one
 //                 atomic per wave and value
 // gab_kmer_spectrum / gab_kmer_query / gab_kmer_dump read the table of the last count; it stays in the handle until the next one.
+//
+// Several GPUs split the KEYS, not the reads (gab_kmer_count_part): every GPU walks all reads and inserts only the canonical k-mers
+// whose hash falls into its partition, into a table sized for that share.  The partial results are disjoint, so nothing is merged
+// and no GPU talks to another; what N GPUs add is atomic throughput, what each of them repeats is the extraction.
 #include "gab_internal.h"
 #include <string.h>
 #include <rocprim/rocprim.hpp>
@@ -48,19 +52,33 @@ struct KmerCounters {
     unsigned long long probes, merged;     // table lines visited by the inserts; equal-neighbour merges inside the lanes' runs
     unsigned long long distinct, total_kmers, hash_size, max_count;
     unsigned long long bad_query;          // lowest index of a query >= 4^k (~0 = none)
-    uint32_t dump_n, pad;
+    uint32_t dump_n;
+    uint32_t overflow;                     // a bounded insert gave up: the partition's table is full (the host repeats the call)
 };
 GAB_STATIC_ATOMIC64(KmerCounters, bad_read);
 GAB_STATIC_ATOMIC64(KmerCounters, bad_query);
 
 struct KmerTile { int32_t read, start; };  // positions [start, start + kTile) of a kept read
 
-__device__ __forceinline__ uint64_t kmer_hash(uint64_t key) {
+__host__ __device__ __forceinline__ uint64_t kmer_hash(uint64_t key) {
     uint64_t h = key * 0x9E3779B97F4A7C15ull;
     h ^= h >> 29;
     h *= 0xBF58476D1CE4E5B9ull;
     return h ^ (h >> 32);
 }
+__host__ __device__ __forceinline__ uint64_t kmer_mulhi(uint64_t a, uint64_t b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+// Key-space partitions: h * nparts is a 128-bit product whose high word is the partition, in [0, nparts), and whose low word -- the
+// fraction of the way through that partition -- is as uniform as h itself, so it picks the line of the partition's own table.
+// (Taking the line from h unchanged would put a partition's keys into 1 / nparts of its lines.)  nparts = 1: part 0, and the line
+// of every key is the line it always had.
+__host__ __device__ __forceinline__ uint32_t kmer_part_of_hash(uint64_t h, uint32_t nparts) { return (uint32_t)kmer_mulhi(h, nparts); }
+__host__ __device__ __forceinline__ uint64_t kmer_line_of_hash(uint64_t h, uint32_t nparts, uint64_t nlines) { return kmer_mulhi(h * nparts, nlines); }
 __device__ __forceinline__ uint64_t kmer_line_of(uint64_t key, uint64_t nlines) { return __umul64hi(kmer_hash(key), nlines); }
 
 // ---- pack: thread = one output word of one read ------------------------------------------------------------------------------------
@@ -96,9 +114,14 @@ __global__ __launch_bounds__(kBlock) void kmer_pack(const char *__restrict__ seq
 // a stale view can only show a taken slot as empty, never the reverse, so that start is at or below the line's true first empty slot --
 // and it passes a slot only after the compare-and-swap (or a load) has shown it taken by ANOTHER key, which is final.  It leaves
 // a line only after all eight slots were seen taken by other keys.
-__device__ __forceinline__ void kmer_insert(KmerLine *table, uint64_t nlines, uint64_t key, uint32_t n, uint32_t &probes) {
+// kBounded (a partition's table, whose size is a forecast of the partition's share of the keys): the walk gives up once it has
+// left `limit` lines, or as soon as it leaves a line after another lane gave up, and raises ct->overflow; the host then repeats the
+// call with a table that cannot fill.  Slots never go back to empty, so `limit` = nlines full lines mean a full table.
+template <bool kBounded>
+__device__ __forceinline__ void kmer_insert(KmerLine *table, uint64_t nlines, uint64_t line, uint64_t key, uint32_t n, uint32_t &probes,
+                                            uint64_t limit, KmerCounters *ct) {
     const unsigned long long stored = key + 1;
-    uint64_t line = kmer_line_of(key, nlines);
+    uint64_t left = 0;
     for (;;) {
         probes++;
         KmerLine *L = table + line;
@@ -118,13 +141,20 @@ __device__ __forceinline__ void kmer_insert(KmerLine *table, uint64_t nlines, ui
                 const unsigned long long seen = atomicCAS(&L->key[s], 0ull, stored);
                 if (seen == 0 || seen == stored) { atomicAdd(&L->cnt[s], n); return; }
             }
+        if constexpr (kBounded) {
+            if (++left >= limit || __hip_atomic_load(&ct->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { atomicOr(&ct->overflow, 1u); return; }
+        }
         line = line + 1 == nlines ? 0 : line + 1;
     }
 }
 
+// kPart = false: the whole key space in one table (part, nparts and limit are not read).  kPart = true: the lane still merges equal
+// neighbours first, then hashes the (key, n) run it flushes -- one hash per run, not per base -- and inserts it only when the key
+// falls into `part`; `merged` and `probes` count the runs and inserts of that partition alone, so both add up over the partitions.
+template <bool kPart>
 __global__ __launch_bounds__(kBlock) void kmer_count(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
                                                      const KmerTile *__restrict__ tiles, int64_t n_tiles, int k, KmerLine *table, uint64_t nlines,
-                                                     KmerCounters *ct) {
+                                                     KmerCounters *ct, uint32_t part, uint32_t nparts, uint64_t limit) {
     const int lane = threadIdx.x & 63;
     const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     uint32_t probes = 0, merged = 0;
@@ -154,18 +184,28 @@ __global__ __launch_bounds__(kBlock) void kmer_count(const uint32_t *__restrict_
             }
             uint64_t cur = ~0ull;
             uint32_t n = 0;
+            auto flush = [&]() {
+                if constexpr (!kPart) kmer_insert<false>(table, nlines, kmer_line_of(cur, nlines), cur, n, probes, 0, ct);
+                else {
+                    const uint64_t h = kmer_hash(cur);
+                    if (kmer_part_of_hash(h, nparts) == part) {
+                        merged += n - 1;
+                        kmer_insert<true>(table, nlines, kmer_line_of_hash(h, nparts, nlines), cur, n, probes, limit, ct);
+                    }
+                }
+            };
             for (int32_t p = p0; p < p1; p++) {
                 const uint64_t c = next_base();
                 fw = ((fw << 2) | c) & mask;
                 rc = (rc >> 2) | ((3ull - c) << top);
                 const uint64_t key = fw < rc ? fw : rc;
-                if (key == cur) { n++; merged++; }
+                if (key == cur) { n++; if constexpr (!kPart) merged++; }
                 else {
-                    if (n) kmer_insert(table, nlines, cur, n, probes);
+                    if (n) flush();
                     cur = key; n = 1;
                 }
             }
-            if (n) kmer_insert(table, nlines, cur, n, probes);
+            if (n) flush();
         }
     }
     // per-wave sums, one atomic per wave and value
@@ -242,16 +282,19 @@ __device__ __forceinline__ uint64_t kmer_revcomp(uint64_t x, int k) {
 }
 
 __global__ __launch_bounds__(kBlock) void kmer_query(const KmerLine *__restrict__ table, uint64_t nlines, int k, const uint64_t *__restrict__ kmers,
-                                                     int64_t n, uint32_t *__restrict__ counts, KmerCounters *ct) {
+                                                     int64_t n, uint32_t *__restrict__ counts, KmerCounters *ct, uint32_t part, uint32_t nparts) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const uint64_t x = kmers[i];
     if (x >> (2 * k)) { counts[i] = 0; atomicMin(&ct->bad_query, (unsigned long long)i); return; }
     const uint64_t r = kmer_revcomp(x, k);
     const unsigned long long stored = (x < r ? x : r) + 1;
-    uint64_t line = kmer_line_of(stored - 1, nlines);
+    const uint64_t h = kmer_hash(stored - 1);
+    if (kmer_part_of_hash(h, nparts) != part) { counts[i] = 0; return; }       // another partition's key
+    uint64_t line = kmer_line_of_hash(h, nparts, nlines);
     uint32_t c = 0;
-    for (uint64_t visited = 0; visited < nlines; visited++) {      // (a table is at most half full, table_lines: the walk ends at an empty slot)
+    // (the walk ends at an empty slot; a partition's table may hold no empty slot near this line, or none at all: nlines lines at most)
+    for (uint64_t visited = 0; visited < nlines; visited++) {
         const KmerLine *L = table + line;
         bool done = false;
 #pragma unroll
@@ -306,12 +349,31 @@ struct gab_kmer {
     int64_t probes = 0, merged = 0;
     float phase_ms[3] = {0, 0, 0}, total_ms = 0;
     int sweep_blocks = 2048;           // grid of the kernels that sweep the table
+    int part = 0, nparts = 1;          // what the last count ran as (gab_kmer_last_part)
+    bool retried = false;              // ... and whether its first table filled up and the call was repeated
+    gab_tuning tun = gab_tuning_loaded();      // experiment knobs, read when the handle is made
 };
 
 static uint64_t table_lines(int64_t positions, int k) {
     // at most min(positions, 4^k) distinct keys; half full at worst, so every probe sequence ends at an empty slot
     const uint64_t keys = std::min<uint64_t>((uint64_t)positions, 1ull << (2 * k));
     return std::max<uint64_t>(16, (2 * keys + kSlots - 1) / kSlots);
+}
+// The first table of a partitioned call: room for the partition's even share of the keys plus a quarter (kPartSlack) plus 64 keys,
+// at half full like the whole table.  The share of a partition is binomial around the even share; a quarter covers 6 standard
+// deviations from 576 keys per partition on, the 64 keys cover them below that (6 sqrt(n) - n / 4 <= 36).  Keys that the hash
+// spreads worse than that fill the table: the bounded insert says so and the call is repeated with table_lines, which cannot fill.
+// Never more than table_lines; nparts = 1 gives table_lines itself.
+static uint64_t part_table_lines(int64_t positions, int k, int nparts) {
+    const uint64_t keys = std::min<uint64_t>((uint64_t)positions, 1ull << (2 * k));
+    const uint64_t share = (keys + (uint64_t)nparts - 1) / (uint64_t)nparts;
+    const uint64_t room = share + share / 4 + 64;
+    return std::min<uint64_t>(table_lines(positions, k), std::max<uint64_t>(16, (2 * room + kSlots - 1) / kSlots));
+}
+constexpr uint64_t kProbeCap = 1024;   // lines a bounded insert walks in a first-attempt table before it calls the table full
+static int kmer_check_parts(const char *fn, int nparts) {
+    GAB_CHECK(nparts >= 1 && nparts <= GAB_KMER_MAX_PARTS, "%s: nparts = %d, supported 1..%d", fn, nparts, GAB_KMER_MAX_PARTS);
+    return GAB_OK;
 }
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static unsigned sweep_grid(const gab_kmer *h) {
@@ -348,25 +410,53 @@ extern "C" void gab_kmer_destroy(gab_kmer *h) {
     delete h;
 }
 
-extern "C" int gab_kmer_reserve(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes) {
+extern "C" int gab_kmer_part_of(uint64_t canonical_kmer, int nparts) {
+    int rc = kmer_check_parts("gab_kmer_part_of", nparts);
+    if (rc) return rc;
+    return (int)kmer_part_of_hash(kmer_hash(canonical_kmer), (uint32_t)nparts);
+}
+
+extern "C" int gab_kmer_parts_of(const uint64_t *canonical_kmers, int64_t n, int nparts, int32_t *parts) {
+    int rc = kmer_check_parts("gab_kmer_parts_of", nparts);
+    if (rc) return rc;
+    GAB_CHECK(n >= 0 && (n == 0 || (canonical_kmers && parts)), "gab_kmer_parts_of: NULL or negative argument");
+    for (int64_t i = 0; i < n; i++) parts[i] = (int32_t)kmer_part_of_hash(kmer_hash(canonical_kmers[i]), (uint32_t)nparts);
+    return GAB_OK;
+}
+
+extern "C" int64_t gab_kmer_table_slots(int64_t positions, int k, int nparts) {
+    int rc = kmer_check_parts("gab_kmer_table_slots", nparts);
+    if (rc) return rc;
+    GAB_CHECK(positions >= 0 && k >= 1 && k <= GAB_KMER_MAX_K, "gab_kmer_table_slots: positions = %lld, k = %d (k: 1..%d)", (long long)positions, k,
+              GAB_KMER_MAX_K);
+    return (int64_t)(part_table_lines(std::max<int64_t>(positions, 1), k, nparts) * kSlots);
+}
+
+extern "C" int gab_kmer_reserve(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes) { return gab_kmer_reserve_part(h, max_reads, max_seq_bytes, 1); }
+
+extern "C" int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes, int nparts) {
     if (!h || max_reads < 0 || max_seq_bytes < 0) { gab_set_error("gab_kmer_reserve: bad argument"); return GAB_EINVAL; }
+    int rc = kmer_check_parts("gab_kmer_reserve_part", nparts);
+    if (rc) return rc;
     gab_device_guard g(h->device);
-    int rc;
     const size_t words = (size_t)max_seq_bytes / 16 + (size_t)max_reads + 1;
     const size_t tiles = (size_t)max_seq_bytes / kTile + (size_t)max_reads + 1;
     if ((rc = h->io.reserve(align256((size_t)max_seq_bytes + 64) + align256((size_t)max_reads * 8) + align256((size_t)max_reads * 4)))) return rc;
     if ((rc = h->packed.reserve(words * 4))) return rc;
     if ((rc = h->plan.reserve(align256(((size_t)max_reads + 1) * 8) + tiles * sizeof(KmerTile)))) return rc;
-    if ((rc = h->table.reserve((size_t)table_lines(std::max<int64_t>(max_seq_bytes, 1), GAB_KMER_MAX_K) * sizeof(KmerLine)))) return rc;
+    if ((rc = h->table.reserve((size_t)part_table_lines(std::max<int64_t>(max_seq_bytes, 1), GAB_KMER_MAX_K, nparts) * sizeof(KmerLine)))) return rc;
     hipStream_t s;
     if ((rc = h->hs.get(&s))) return rc;
     return gab_warm_copy_engines(s, h->io.p, h->io.cap);
 }
 
 // d_*: device; off / len: the same two arrays on the host
+// part / nparts: the partition of the key space this call counts (0 / 1: all of it, in the unpartitioned kernel)
 static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
-                           const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive, gab_kmer_result *res, hipStream_t s) {
+                           const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res,
+                           hipStream_t s) {
     h->counted = false;
+    gab_tuning_refresh(&h->tun);
     // plan on the host: word offset of every read, tiles of the kept ones
     std::vector<int64_t> woff((size_t)n_reads + 1);
     std::vector<KmerTile> tiles;
@@ -388,7 +478,8 @@ static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, co
     woff[(size_t)n_reads] = words;
     GAB_CHECK(positions < (1ll << 32), "gab_kmer_count: %lld k-mer positions in one call (limit 2^32: the counts are 32-bit)", (long long)positions);
     const int64_t n_tiles = (int64_t)tiles.size();
-    const uint64_t nlines = table_lines(std::max<int64_t>(positions, 1), k);
+    // GAB_KMER_PART_FLOOR: the first table of a partitioned call is the 16-line floor (test hook of the repeat below)
+    uint64_t nlines = nparts > 1 && h->tun.kmer_part_floor ? 16 : part_table_lines(std::max<int64_t>(positions, 1), k, nparts);
     int rc;
     const size_t tiles_at = align256(((size_t)n_reads + 1) * 8);
     if ((rc = h->packed.reserve((size_t)words * 4 + 4))) return rc;
@@ -397,7 +488,6 @@ static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, co
     int64_t *d_woff = h->plan.as<int64_t>();
     KmerTile *d_tiles = reinterpret_cast<KmerTile *>(h->plan.as<char>() + tiles_at);
     KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    KmerLine *table = h->table.as<KmerLine>();
     uint32_t *packed = h->packed.as<uint32_t>();
 
     GAB_HIP(hipEventRecord(h->ev[0], s));
@@ -411,32 +501,56 @@ static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, co
         hipLaunchKernelGGL(kmer_pack, dim3((unsigned)gab_ceil_div(words, kBlock)), dim3(kBlock), 0, s, d_seq, d_off, d_len, d_woff, n_reads, words, packed, d_ct);
     GAB_HIP(hipEventRecord(h->ev[1], s));
     // (a bad byte packs as some base: the count below runs on it harmlessly and the call fails after the one synchronisation)
-    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
-    if (n_tiles)
-        hipLaunchKernelGGL(kmer_count, dim3((unsigned)gab_ceil_div(n_tiles, kBlock / 64)), dim3(kBlock), 0, s, packed, d_woff, d_len, d_tiles, n_tiles, k, table,
-                           nlines, d_ct);
-    GAB_HIP(hipEventRecord(h->ev[2], s));
-    h->nlines = nlines;
-    hipLaunchKernelGGL(kmer_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
-    GAB_HIP(hipEventRecord(h->ev[3], s));
-    GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipEventRecord(h->ev[4], s));
-    GAB_HIP(hipStreamSynchronize(s));
-    GAB_HIP(hipGetLastError());
+    // A partition's first table is a forecast (part_table_lines) and its inserts are bounded: when one gave up, the host sees
+    // ct->overflow after the call's one synchronisation and runs clear, count and reduce once more in a table of table_lines lines,
+    // which is at most half full whatever the hash does.  (After such a repeat pack_ms includes the first attempt.)
+    h->retried = false;
+    for (int attempt = 0;; attempt++) {
+        if (attempt && (rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+        KmerLine *table = h->table.as<KmerLine>();
+        GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+        if (n_tiles) {
+            const dim3 grid((unsigned)gab_ceil_div(n_tiles, kBlock / 64));
+            if (nparts == 1)
+                hipLaunchKernelGGL(kmer_count<false>, grid, dim3(kBlock), 0, s, packed, d_woff, d_len, d_tiles, n_tiles, k, table, nlines, d_ct, 0u, 1u,
+                                   (uint64_t)0);
+            else
+                hipLaunchKernelGGL(kmer_count<true>, grid, dim3(kBlock), 0, s, packed, d_woff, d_len, d_tiles, n_tiles, k, table, nlines, d_ct, (uint32_t)part,
+                                   (uint32_t)nparts, attempt ? nlines : std::min<uint64_t>(nlines, kProbeCap));
+        }
+        GAB_HIP(hipEventRecord(h->ev[2], s));
+        h->nlines = nlines;
+        hipLaunchKernelGGL(kmer_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+        GAB_HIP(hipEventRecord(h->ev[3], s));
+        GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipEventRecord(h->ev[4], s));
+        GAB_HIP(hipStreamSynchronize(s));
+        GAB_HIP(hipGetLastError());
+        GAB_CHECK(h->h_ct->bad_read == ~0ull, "gab_kmer_count: read %lld holds a byte outside ACGTacgt (a driver replaces such bytes before the call)",
+                  (long long)h->h_ct->bad_read);
+        if (!h->h_ct->overflow) break;
+        GAB_CHECK(attempt == 0, "gab_kmer_count: internal error: a table of %llu lines for %lld positions filled up", (unsigned long long)nlines,
+                  (long long)positions);
+        h->retried = true;
+        nlines = table_lines(std::max<int64_t>(positions, 1), k);
+        *h->h_ct = zero;
+        GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
+        GAB_HIP(hipEventRecord(h->ev[1], s));
+    }
     const KmerCounters &c = *h->h_ct;
-    GAB_CHECK(c.bad_read == ~0ull, "gab_kmer_count: read %lld holds a byte outside ACGTacgt (a driver replaces such bytes before the call)",
-              (long long)c.bad_read);
     h->last = gab_kmer_result{kept, positions, (int64_t)c.distinct, (int64_t)c.total_kmers, (int64_t)c.hash_size, (int64_t)c.max_count};
     h->probes = (int64_t)c.probes; h->merged = (int64_t)c.merged;
     for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&h->phase_ms[i], h->ev[i], h->ev[i + 1]);
     (void)hipEventElapsedTime(&h->total_ms, h->ev[0], h->ev[4]);
-    h->k = k; h->counted = true;
+    h->k = k; h->part = part; h->nparts = nparts; h->counted = true;
     if (res) *res = h->last;
     return GAB_OK;
 }
 
-static int kmer_check_args(gab_kmer *h, const void *off, const void *len, int64_t n_reads, int k) {
+static int kmer_check_args(gab_kmer *h, const void *off, const void *len, int64_t n_reads, int k, int part, int nparts) {
     GAB_CHECK(h && n_reads >= 0 && (n_reads == 0 || (off && len)), "gab_kmer_count: NULL or negative argument");
+    GAB_CHECK(nparts >= 1 && nparts <= GAB_KMER_MAX_PARTS && part >= 0 && part < nparts,
+              "gab_kmer_count_part: part = %d, nparts = %d (0 <= part < nparts, nparts: 1..%d)", part, nparts, GAB_KMER_MAX_PARTS);
     GAB_CHECK(k >= 1 && k <= GAB_KMER_MAX_K, "gab_kmer_count: k = %d, supported 1..%d (the reference's flat counter, kmer-cnt/vertex_index.cpp:793-796)", k,
               GAB_KMER_MAX_K);
     return GAB_OK;
@@ -444,7 +558,12 @@ static int kmer_check_args(gab_kmer *h, const void *off, const void *len, int64_
 
 extern "C" int gab_kmer_count_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
                                      int32_t min_len_exclusive, gab_kmer_result *res, void *stream) {
-    int rc = kmer_check_args(h, off, len, n_reads, k);
+    return gab_kmer_count_part_device(h, seq, seq_bytes, off, len, n_reads, k, min_len_exclusive, 0, 1, res, stream);
+}
+
+extern "C" int gab_kmer_count_part_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads,
+                                          int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res, void *stream) {
+    int rc = kmer_check_args(h, off, len, n_reads, k, part, nparts);
     if (rc) return rc;
     GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_count_device: bad sequence slab");
     gab_device_guard g(h->device);
@@ -456,12 +575,17 @@ extern "C" int gab_kmer_count_device(gab_kmer *h, const char *seq, int64_t seq_b
         GAB_HIP(hipMemcpyAsync(h_len.data(), len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
         GAB_HIP(hipStreamSynchronize(s));
     }
-    return kmer_count_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, min_len_exclusive, res, s);
+    return kmer_count_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, min_len_exclusive, part, nparts, res, s);
 }
 
 extern "C" int gab_kmer_count(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
                               gab_kmer_result *res) {
-    int rc = kmer_check_args(h, off, len, n_reads, k);
+    return gab_kmer_count_part(h, seq, off, len, n_reads, k, min_len_exclusive, 0, 1, res);
+}
+
+extern "C" int gab_kmer_count_part(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
+                                   int part, int nparts, gab_kmer_result *res) {
+    int rc = kmer_check_args(h, off, len, n_reads, k, part, nparts);
     if (rc) return rc;
     gab_device_guard g(h->device);
     hipStream_t s;
@@ -491,7 +615,7 @@ extern "C" int gab_kmer_count(gab_kmer *h, const char *seq, const int64_t *off, 
         }
         GAB_HIP(hipStreamSynchronize(s));
     }
-    return kmer_count_impl(h, d_seq, (int64_t)span, d_off, d_len, rel.data(), len, n_reads, k, min_len_exclusive, res, s);
+    return kmer_count_impl(h, d_seq, (int64_t)span, d_off, d_len, rel.data(), len, n_reads, k, min_len_exclusive, part, nparts, res, s);
 }
 
 #define KMER_NEED_COUNT(fn) GAB_CHECK(h && h->counted, fn ": no finished gab_kmer_count on this handle")
@@ -528,7 +652,8 @@ extern "C" int gab_kmer_query(gab_kmer *h, const uint64_t *kmers, int64_t n, uin
     h->h_ct->bad_query = ~0ull;
     GAB_HIP(hipMemcpyAsync(&d_ct->bad_query, &h->h_ct->bad_query, 8, hipMemcpyHostToDevice, s));
     GAB_HIP(hipMemcpyAsync(d_k, kmers, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kmer_query, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, d_k, n, d_c, d_ct);
+    hipLaunchKernelGGL(kmer_query, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, d_k, n, d_c, d_ct,
+                       (uint32_t)h->part, (uint32_t)h->nparts);
     GAB_HIP(hipMemcpyAsync(&h->h_ct->bad_query, &d_ct->bad_query, 8, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipMemcpyAsync(counts, d_c, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipStreamSynchronize(s));
@@ -581,5 +706,14 @@ extern "C" int gab_kmer_last_phases(gab_kmer *h, float *pack_ms, float *count_ms
     if (pack_ms) *pack_ms = h->phase_ms[0];
     if (count_ms) *count_ms = h->phase_ms[1];
     if (reduce_ms) *reduce_ms = h->phase_ms[2];
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
+    KMER_NEED_COUNT("gab_kmer_last_part");
+    if (part) *part = h->part;
+    if (nparts) *nparts = h->nparts;
+    if (table_slots) *table_slots = (int64_t)(h->nlines * kSlots);
+    if (retried) *retried = h->retried ? 1 : 0;
     return GAB_OK;
 }

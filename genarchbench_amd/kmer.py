@@ -1,5 +1,7 @@
-"""Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI."""
+"""Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI, whole or in key-space partitions
+(include/gab.h: gab_kmer_count_part)."""
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -7,6 +9,7 @@ from ._lib import GabError, check, lib
 
 RUN = 64        # GAB_KMER_RUN: positions per GPU lane (what last_stats()["merged"] is defined by)
 MAX_K = 17      # GAB_KMER_MAX_K
+MAX_PARTS = 64  # GAB_KMER_MAX_PARTS
 
 
 class _Result(C.Structure):
@@ -25,6 +28,24 @@ def pack_reads(reads):
         off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
     seq = np.frombuffer(b"".join(reads), np.uint8).copy() if len(reads) else np.zeros(0, np.uint8)
     return seq, off, ln
+
+
+def part_of(kmers, nparts):
+    """canonical k-mers (uint64 array) -> the partition of each, 0 .. nparts - 1 (int32 array); host arithmetic, no GPU"""
+    kmers = np.ascontiguousarray(kmers, np.uint64)
+    out = np.full(kmers.size, -12345, np.int32)
+    check(lib().gab_kmer_parts_of(_p(kmers), C.c_int64(kmers.size), C.c_int(nparts), _p(out)))
+    return out
+
+
+def table_slots(positions, k, nparts):
+    """table slots the first attempt of a partitioned count over `positions` k-mer positions allocates; no GPU"""
+    fn = lib().gab_kmer_table_slots
+    fn.restype = C.c_int64
+    n = fn(C.c_int64(positions), C.c_int(k), C.c_int(nparts))
+    if n < 0:
+        check(int(n))
+    return int(n)
 
 
 class KmerCounter:
@@ -62,6 +83,33 @@ class KmerCounter:
                                           C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int32(min_len), C.byref(res),
                                           C.c_void_p(stream)))
         return self._dict(res)
+
+    def reserve_part(self, max_reads, max_seq_bytes, nparts):
+        check(lib().gab_kmer_reserve_part(self._h, C.c_int64(max_reads), C.c_int64(max_seq_bytes), C.c_int(nparts)))
+
+    def count_part(self, reads, k, part, nparts, min_len=5000):
+        """count() for partition `part` of `nparts` of the key space: reads_kept and positions are the whole call's, the other four
+        fields the partition's, and the handle then holds the partition (spectrum, query, dump, last_stats)"""
+        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
+        seq = np.ascontiguousarray(seq, np.uint8); off = np.ascontiguousarray(off, np.int64); ln = np.ascontiguousarray(ln, np.int32)
+        res = _Result(*([-12345] * 6))
+        check(lib().gab_kmer_count_part(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int32(min_len), C.c_int(part),
+                                        C.c_int(nparts), C.byref(res)))
+        return self._dict(res)
+
+    def count_part_device(self, seq, off, ln, k, part, nparts, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: uint8 / int64 / int32"""
+        res = _Result(*([-12345] * 6))
+        check(lib().gab_kmer_count_part_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
+                                               C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int32(min_len), C.c_int(part),
+                                               C.c_int(nparts), C.byref(res), C.c_void_p(stream)))
+        return self._dict(res)
+
+    def last_part(self):
+        """what the last count ran as: its partition, the slots of the table it ended in, whether its first table filled up and it ran again"""
+        part = C.c_int(-1); nparts = C.c_int(-1); slots = C.c_int64(-1); retried = C.c_int(-1)
+        check(lib().gab_kmer_last_part(self._h, C.byref(part), C.byref(nparts), C.byref(slots), C.byref(retried)))
+        return {"part": part.value, "nparts": nparts.value, "table_slots": slots.value, "retried": retried.value}
 
     def spectrum(self, nbins):
         hist = np.full(nbins, -12345, np.int64)
@@ -102,4 +150,78 @@ class KmerCounter:
                 "pack_ms": a.value, "count_ms": b.value, "reduce_ms": c.value}
 
 
-__all__ = ["KmerCounter", "GabError", "pack_reads", "RUN", "MAX_K"]
+class KmerCounterSet:
+    """One count over several GPUs without a merge: handle i, on devices[i], counts partition i of len(devices) of the key space.
+    Every handle walks all reads; no handle needs anything from another.  A device may appear more than once (several partitions on
+    one card, one after the other or side by side)."""
+
+    def __init__(self, devices):
+        devices = list(devices)
+        if not 1 <= len(devices) <= MAX_PARTS:
+            raise ValueError(f"KmerCounterSet: {len(devices)} devices, supported 1..{MAX_PARTS}")
+        self.parts = []
+        try:
+            for d in devices:
+                self.parts.append(KmerCounter(d))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for kc in self.parts:
+            kc.close()
+        self.parts = []
+
+    def reserve(self, max_reads, max_seq_bytes):
+        for kc in self.parts:
+            kc.reserve_part(max_reads, max_seq_bytes, len(self.parts))
+
+    def count(self, reads, k, min_len=5000):
+        """every partition at once, one host thread per handle -> the six fields of the whole input"""
+        packed = reads if isinstance(reads, tuple) else pack_reads(reads)
+        n = len(self.parts)
+        out = [None] * n
+
+        def run(i):
+            try:
+                out[i] = self.parts[i].count_part(packed, k, i, n, min_len)
+            except Exception as e:      # (handed to the caller's thread below)
+                out[i] = e
+        threads = [threading.Thread(target=run, args=(i,)) for i in range(1, n)]
+        for t in threads:
+            t.start()
+        run(0)
+        for t in threads:
+            t.join()
+        for r in out:
+            if isinstance(r, Exception):
+                raise r
+        both = {f: out[0][f] for f in ("reads_kept", "positions")}
+        both.update({f: sum(r[f] for r in out) for f in ("distinct", "total_kmers", "hash_size")})
+        both["max_count"] = max(r["max_count"] for r in out)
+        return both
+
+    def spectrum(self, nbins):
+        return sum(kc.spectrum(nbins) for kc in self.parts)
+
+    def query(self, kmers):
+        """a k-mer is counted by one partition and 0 in every other: the sum is its count"""
+        kmers = np.ascontiguousarray(kmers, np.uint64)
+        out = np.zeros(kmers.size, np.uint32)
+        for kc in self.parts:
+            out += kc.query(kmers)
+        return out
+
+    def dump(self):
+        """-> (k-mers uint64 ascending, counts uint32): the partitions' sorted lists, merged"""
+        lists = [kc.dump() for kc in self.parts]
+        kmers = np.concatenate([d[0] for d in lists]); counts = np.concatenate([d[1] for d in lists])
+        order = np.argsort(kmers, kind="stable")      # (the lists are disjoint and sorted: a merge, done by numpy's run-aware sort)
+        return kmers[order], counts[order]
+
+    def last_stats(self):
+        """one row per partition: last_stats() and last_part() of its handle"""
+        return [dict(kc.last_stats(), **kc.last_part()) for kc in self.parts]
+
+
+__all__ = ["KmerCounter", "KmerCounterSet", "GabError", "pack_reads", "part_of", "table_slots", "RUN", "MAX_K", "MAX_PARTS"]

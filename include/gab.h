@@ -428,6 +428,35 @@ int gab_kmer_last_stats(gab_kmer *h, int64_t *probes, int64_t *merged, float *ke
 /* last count, per stage (HIP events, ms): 2-bit packing, clear + extract-and-count, the reduction over the table */
 int gab_kmer_last_phases(gab_kmer *h, float *pack_ms, float *count_ms, float *reduce_ms);
 
+/* Key-space partitions: one count split over several GPUs (or several calls) without a merge.  A hash of the canonical k-mer puts
+ * it into one of nparts partitions; a call with (part, nparts) walks ALL reads and counts only the k-mers of its partition, in a
+ * table sized for that share.  The partitions are disjoint, so over part = 0 .. nparts - 1 distinct, total_kmers, hash_size and the
+ * spectrum add, max_count is the largest, the sorted dumps interleave, and a query is answered by exactly one partition.  No call
+ * needs anything from another.  nparts = 1, part = 0 is gab_kmer_count itself. */
+#define GAB_KMER_MAX_PARTS 64
+/* Plain host arithmetic, no GPU needed.  The partition of a canonical k-mer, 0 .. nparts - 1 (GAB_EINVAL for nparts outside
+ * 1 .. GAB_KMER_MAX_PARTS); the same for n of them; the table slots the first attempt of a partitioned call over `positions`
+ * k-mer positions allocates (16 bytes each): the even share of min(positions, 4^k) keys plus a quarter plus 64, at half full, never
+ * more than the unpartitioned table and that table for nparts = 1. */
+int gab_kmer_part_of(uint64_t canonical_kmer, int nparts);
+int gab_kmer_parts_of(const uint64_t *canonical_kmers, int64_t n, int nparts, int32_t *parts);
+int64_t gab_kmer_table_slots(int64_t positions, int k, int nparts);
+/* gab_kmer_count / gab_kmer_count_device for partition `part` of `nparts`.  reads_kept and positions are those of the whole call,
+ * the same on every partition; distinct, total_kmers, hash_size and max_count are the partition's.  Afterwards the handle holds
+ * the partition: gab_kmer_spectrum and gab_kmer_dump return its bins and its sorted k-mers, gab_kmer_query its count for a k-mer it
+ * owns and 0 for any other, gab_kmer_last_stats the table lines its own inserts visited and the merges of its own k-mers (both add
+ * up over the partitions).  Nothing but the hash bounds a partition's share of the keys: should the table fill up, the call
+ * notices after its one synchronisation and runs once more with the unpartitioned table size, which cannot (gab_kmer_last_part).
+ * part < 0, part >= nparts, nparts < 1 or nparts > GAB_KMER_MAX_PARTS -> GAB_EINVAL. */
+int gab_kmer_count_part(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                        int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res);
+int gab_kmer_count_part_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len,
+                               int64_t n_reads, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res, void *stream);
+/* gab_kmer_reserve with the table of one partition of nparts */
+int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes, int nparts);
+/* what the last count ran as: its partition, the slots of the table it ended in, and whether it was repeated (0 / 1) */
+int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried);
+
 /* ---- input parsers ---------------------------------------------------------
  * The reference drivers parse their text inputs on the host, line by line, outside the region of interest
  * (bsw: loadPairs, bsw/src/main_banded.cpp:164-206 -- fgets + sscanf per pair; bpm / wfa: getline per line,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the k-mer counter (gab_kmer_*) on a generated E. coli-like read set.  Standalone; needs a GPU.
 
-    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--out kmer_bench.json]
+    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--parts 1,2,4,8] [--out kmer_bench.json]
 
 The read set: a 4.6 Mbp random genome, reads of 5 .. 20 kb at 50x, both strands, 10 % errors (substitutions, seeded).
 For k = 17 and 15 it reports, warm, as the median of the repeats:
@@ -10,6 +10,12 @@ For k = 17 and 15 it reports, warm, as the median of the repeats:
 and the device time of the stages -- 2-bit packing, table clear + extract-and-count (one kernel), reduction -- with the table
 lines visited per insert.  The first call's result is compared with the numpy model of tests/kmer_model.py when --check is given
 (minutes of CPU time at this size).
+
+--parts N[,N...]: for every N, each of the N key-space partitions (gab_kmer_count_part) is run ON ITS OWN on the one GPU, resident,
+the same warm-up and repeats: what one GPU of N would do, every GPU walking all reads and inserting its share of the k-mers.  Per
+partition the stage times, and per N the slowest partition's call time with the positions per second it would give -- a ONE-GPU
+FORECAST of an N-GPU run, not a measurement of one (no second card, no shared host link).  As N grows the count stage tends to
+what extraction alone costs: the floor no number of GPUs gets under.
 """
 import argparse
 import json
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--coverage", type=int, default=50)
+    ap.add_argument("--parts", default="", help="comma-separated partition counts to forecast, e.g. 1,2,4,8")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -102,6 +109,32 @@ def main():
             m = kmer_model.model(reads, k)
             row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
         out["k"][str(k)] = row
+    if a.parts:
+        out["parts"] = {}
+        for nparts in [int(x) for x in a.parts.split(",")]:
+            kc.reserve_part(len(reads), seq.size, nparts)
+            per_k = {}
+            for k in (17, 15):
+                rows = []
+                for part in range(nparts):
+                    samples = []
+                    for it in range(a.warmup + a.repeats):
+                        res = kc.count_part_device(d_seq, d_off, d_len, k, part, nparts)
+                        if it >= a.warmup:
+                            samples.append(kc.last_stats())
+                    st, lp = samples[-1], kc.last_part()
+                    med = lambda f: statistics.median(s[f] for s in samples)
+                    rows.append({"part": part, "pack_ms": med("pack_ms"), "count_ms": med("count_ms"), "reduce_ms": med("reduce_ms"),
+                                 "total_ms": med("total_ms"), "total_ms_min": min(s["total_ms"] for s in samples),
+                                 "total_ms_max": max(s["total_ms"] for s in samples), "distinct": res["distinct"],
+                                 "probes": st["probes"], "merged": st["merged"], "table_slots": lp["table_slots"],
+                                 "retried": lp["retried"]})
+                slowest = max(r["total_ms"] for r in rows)
+                per_k[str(k)] = {"partitions": rows, "positions": res["positions"], "distinct_sum": sum(r["distinct"] for r in rows),
+                                 "merged_sum": sum(r["merged"] for r in rows), "probes_sum": sum(r["probes"] for r in rows),
+                                 "slowest_total_ms": slowest, "slowest_count_ms": max(r["count_ms"] for r in rows),
+                                 "forecast_positions_per_s": res["positions"] / (slowest * 1e-3)}
+            out["parts"][str(nparts)] = per_k
     kc.close()
     line = json.dumps(out, sort_keys=True)
     print(line)
