@@ -407,6 +407,11 @@ __device__ __forceinline__ uint32_t shr16(uint32_t a) {
 __device__ __forceinline__ uint32_t add_u32_v(uint32_t a, uint32_t b) {
     uint32_t r; asm("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
 }
+typedef __attribute__((address_space(3))) uint32_t bsw_lds_u32;       // 32-bit LDS pointers: one VGPR, so that inline assembly can bump them
+typedef __attribute__((address_space(3))) const uint8_t bsw_lds_u8;
+__device__ __forceinline__ uint32_t max_i16_hi_lo(uint32_t a, uint32_t b) {      // max(upper half of a, low half of b) -> low half, upper half zero
+    uint32_t r; asm("v_max_i16_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0" : "=v"(r) : "v"(a), "v"(b)); return r;
+}
 struct BswCellOut { int h, en, f; };
 __device__ __forceinline__ BswCellOut bsw_cell(int diag, int e, int f, uint32_t qc, uint32_t rlo, uint32_t rhi, int oe_del,
                                                int e_del, int oe_ins, int e_ins) {
@@ -518,8 +523,8 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             if (j + 1 < end) {
                 // Two columns per step, the column-independent part in packed 16-bit lanes (lo = column j, hi = j+1):
                 // M, E' and the F-source of both cells come from v_pk_* instructions; only the H / F carry chain
-                // between the two cells is scalar.  The loop is unrolled by two pairs so that the software pipeline
-                // (next pair's LDS words in flight while this pair is computed) needs no register copies.
+                // between the two cells is scalar.  The loop is unrolled by two pairs for the software pipeline (next pair's
+                // LDS words in flight while this pair is computed); what keeps register copies out of it is said at the loop.
                 const uint32_t k_oe_del = as_u32(pk_splat(oe_del)), k_e_del = as_u32(pk_splat(e_del));
                 const uint32_t k_oe_ins = as_u32(pk_splat(oe_ins));
                 const uint32_t k_bias = 0x00800080u, k_nib = 0x000f000fu;
@@ -533,10 +538,11 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 // M is clamped at 0 (unsigned saturating subtract): H, E' and F all take a max with a non-negative
                 // value, so the clamp changes none of them and lets E' / F-source use saturating subtracts too.
                 // The column-to-column carry chain (H[j] -> F -> H[j+1] -> F) uses one half per instruction anyway: it runs in
-                // the NON-packed 16-bit instructions (v_max_i16 / v_sub_u16 on the low halves, two shifts to bring the upper
-                // halves of ME and T down), which issue every 2.6 cycles at this occupancy instead of 4.2 (profiles/r02_valu_issue.md);
+                // the NON-packed 16-bit instructions (v_max_i16 / v_sub_u16 on the low halves), which issue every 2.6 cycles at
+                // this occupancy instead of 4.2 (profiles/r02_valu_issue.md); the upper halves of ME and T are read through
+                // src0_sel:WORD_1 of an SDWA v_max_i16 -- a 4-cycle op, but one instead of a shift and a max (profiles/bsw_row_sweep.md);
                 // so do the plain 32-bit add of the two packed halves (no carry: both < 256) and the byte mask.
-#define BSW_PAIR(V, QB, JJ, OUT)                                                                                \
+#define BSW_PAIR(V, QB, OUT, HJ)                                                                                \
     {                                                                                                             \
         const uint32_t d2 = (V) & k_lo8;                                         /* diag of both columns */      \
         const uint32_t e2 = __builtin_amdgcn_perm(0u, (V), 0x0c030c01u);         /* E of both columns */         \
@@ -551,22 +557,44 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         const uint32_t HA = max_i16_lo(ME, FV);                                  /* H[j] */                      \
         const uint32_t FA = max_i16_lo(T, sub_u16_lo(FV, v_e_ins));              /* F leaving column j */        \
         const uint32_t hprev = HB;                                                                               \
-        HB = max_i16_lo(shr16(ME), FA);                                          /* H[j+1] */                    \
-        FV = max_i16_lo(shr16(T), sub_u16_lo(FA, v_e_ins));                      /* F leaving column j+1 */      \
+        HB = max_i16_hi_lo(ME, FA);                                           /* H[j+1] */                    \
+        FV = max_i16_hi_lo(T, sub_u16_lo(FA, v_e_ins));                     /* F leaving column j+1 */      \
         /* byte 0 = H[j-1] (hprev), byte 1 = E'[j], byte 2 = H[j] (HA byte 0), byte 3 = E'[j+1] */               \
         (OUT) = (EN << 8) | __builtin_amdgcn_perm(HA, hprev, 0x0c040c00u);                                       \
-        const uint32_t pa = (HA << 16) | (uint32_t)(JJ), pb = (HB << 16) | (uint32_t)((JJ) + 1);                 \
-        rowpk = max(max(rowpk, pa), pb);                                                                         \
+        (HJ) = HA;                                                                                               \
     }
-                for (; j + 3 < end; j += 4, cw += 128, qp += 128) {
-                    const uint32_t v1 = cw[64], q1 = qp[64];
-                    BSW_PAIR(v0, q0, j, cw[0])
-                    v0 = cw[128]; q0 = qp[128];                      // pair index <= end / 2: inside the row allocation
-                    BSW_PAIR(v1, q1, j + 2, cw[64])
+                // Row maximum: ONE key per loop trip, (largest H of the trip's four columns << 16) | first column, the max taken
+                // in the 2-cycle v_max_i16.  Trips cover disjoint, increasing column ranges, so the key that wins names the
+                // LAST group that holds the row maximum; which of its columns is the last one that holds it is read back from
+                // the stored row after the sweep (behind CELL16(end) below).  The cells outside the loop keep exact keys.
+                // No register copies in the loop (the compiler put three into the plain form of it): the pointers and the
+                // column are bumped in place at the end of a trip by 2-cycle adds on VGPR constants, behind every LDS access
+                // of the trip, and the loads of the two halves stay two ds_read_b32 (one LDS instruction more per trip):
+                // merged into one two-word read they land in a register pair that the next trip's read overwrites.
+                bsw_lds_u32 *cl = (bsw_lds_u32 *)cw;
+                bsw_lds_u8 *ql = (bsw_lds_u8 *)qp;
+                uint32_t k_cstep = 512u, k_qstep = 128u, k_jstep = 4u;
+                asm volatile("" : "+v"(k_cstep), "+v"(k_qstep), "+v"(k_jstep));
+                const int jlast = end - 3;
+                while (j < jlast) {
+                    const uint32_t v1 = cl[64], q1 = ql[64];
+                    uint32_t h0j, h2j;
+                    BSW_PAIR(v0, q0, cl[0], h0j)
+                    const uint32_t m01 = max_i16_lo(h0j, HB);
+                    asm volatile("" ::: "memory");                   // keeps the next load from merging with v1's above
+                    v0 = cl[128]; q0 = ql[128];                      // pair index <= end / 2: inside the row allocation
+                    BSW_PAIR(v1, q1, cl[64], h2j)
+                    const uint32_t m4 = max_i16_lo(m01, max_i16_lo(h2j, HB));
+                    rowpk = max(rowpk, (m4 << 16) | (uint32_t)j);
+                    asm volatile("v_add_u32 %0, %0, %3\n\tv_add_u32 %1, %1, %4\n\tv_add_u32 %2, %2, %5"
+                                 : "+v"(cl), "+v"(ql), "+v"(j) : "v"(k_cstep), "v"(k_qstep), "v"(k_jstep) : "memory");
                 }
                 if (j + 1 < end) {
-                    const uint32_t v1 = cw[64], q1 = qp[64];         // the word a trailing single column lives in
-                    BSW_PAIR(v0, q0, j, cw[0])
+                    const uint32_t v1 = cl[64], q1 = ql[64];         // the word a trailing single column lives in
+                    uint32_t hj;
+                    BSW_PAIR(v0, q0, cl[0], hj)
+                    const uint32_t pa = (hj << 16) | (uint32_t)j, pb = (HB << 16) | (uint32_t)(j + 1);
+                    rowpk = max(max(rowpk, pa), pb);
                     j += 2; v0 = v1; q0 = q1;
                 }
                 hleft = (int)HB; f = (int)FV;
@@ -583,13 +611,38 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             }
             cells += (unsigned)(end > beg ? end - beg : 0);
             const int rowmax = (int)(rowpk >> 16);
-            const int rowmax_j = end > beg ? (int)(rowpk & 0xffffu) : -1;
             CELL16(end) = (uint16_t)hleft;        // eh[end].h = h1, eh[end].e = 0
             if (j == qlen) {
                 if (!(gscore > hleft)) g_i = i;
                 gscore = hleft > gscore ? hleft : gscore;
             }
             if (rowmax == 0) break;
+            // One LDS round trip for what the rest of the row needs: the three pair words that hold the row maximum's
+            // candidate columns and the six of the band trimming.  H(i, c) is the low byte of stored cell c + 1 and cell
+            // `end` holds H(i, end - 1), so the candidates kj .. kj + 3 are cells kj + 1 .. kj + 4: pair words
+            // (kj + 1) / 2 .. + 2, the last one at most qlen / 2 + 2 -- behind the cell rows come the query nibbles and
+            // one spare row, so it is inside the launch's LDS (see lds8 at the launch), and a word past cell `end` is masked.
+            const int kj = (int)(rowpk & 0xffffu);
+            const int pb = beg >> 1, pe = end >> 1;
+            const uint32_t *const rw = CW + ((kj + 1) >> 1) * 64;
+            const uint32_t r0 = rw[0], r1 = rw[64], r2 = rw[128];
+            const uint32_t b0 = CW[pb * 64], b1 = CW[(pb + 1) * 64], b2 = CW[(pb + 2) * 64];
+            const uint32_t e2 = CW[pe * 64], e1 = CW[(pe > 0 ? pe - 1 : 0) * 64], e0 = CW[(pe > 1 ? pe - 2 : 0) * 64];
+            // rowmax_j = the LAST column c of [kj, min(kj + 3, end - 1)] with H(i, c) == rowmax.  For a loop trip's key that
+            // is the reference's tie rule inside the group (a later group that reached the maximum would have won the key);
+            // for an exact key column kj itself matches and no later column can: it would have made a larger key.
+            int rowmax_j;
+            {
+                const uint32_t sh = (uint32_t)((kj + 1) & 1) << 4;
+                const uint32_t c01 = __builtin_amdgcn_alignbit(r1, r0, sh), c23 = __builtin_amdgcn_alignbit(r2, r1, sh);
+                const uint32_t rm2 = (uint32_t)rowmax * 0x00010001u;
+                // 1 per 16-bit half whose H differs from the row maximum, gathered into bytes 0..3 = candidates 0..3
+                const uint32_t ne = __builtin_amdgcn_perm(pk_min_u16_1((c23 ^ rm2) & 0x00ff00ffu), pk_min_u16_1((c01 ^ rm2) & 0x00ff00ffu),
+                                                          0x06040200u);
+                const int nv = end - kj < 4 ? end - kj : 4;                       // >= 1: rowmax > 0 comes from a cell of the band
+                const uint32_t eq = (ne ^ 0x01010101u) & (0x01010101u >> (8 * (4 - nv)));
+                rowmax_j = kj + ((31 - __builtin_clz(eq)) >> 3);
+            }
             const int rows_left = tlen - 1 - i;
             bool try_exit = false;
             if (rowmax > best) {
@@ -609,9 +662,6 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             // trip (whole pair words; cells outside [beg, end] only ever shorten the count and the clamps below undo
             // that); the cell-by-cell loops of the reference run only when all four are zero.
             {
-                const int pb = beg >> 1, pe = end >> 1;
-                const uint32_t b0 = CW[pb * 64], b1 = CW[(pb + 1) * 64], b2 = CW[(pb + 2) * 64];
-                const uint32_t e2 = CW[pe * 64], e1 = CW[(pe > 0 ? pe - 1 : 0) * 64], e0 = CW[(pe > 1 ? pe - 2 : 0) * 64];
                 uint64_t x = (uint64_t)b1 << 32 | b0;                      // cells 2pb .. 2pb+3, low half first
                 if (beg & 1) x = (x >> 16) | (uint64_t)(b2 & 0xffffu) << 48;
                 const int lz = x ? __builtin_ctzll(x) >> 4 : 4;
@@ -855,6 +905,8 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
             fprintf(stderr, "[gab_bsw_dp %p] class %d qcap %d pairs %lld bits %d sym %d ms1 %d\n", (void *)h, cls, qcap,
                     (long long)(ke - kb), hmax <= 255 ? 8 : wide ? 32 : 16, (int)sym, (int)ms1);
         if (hmax <= 255 && h->cst.max_sc >= 0) {
+            // qcap / 2 + 1 rows of cells, the nibble rows (at least one) and one spare row: the kernel reads up to pair word
+            // qlen / 2 + 2 (row start, band trimming, the row maximum's candidates), which this layout holds for every qcap >= qlen
             const size_t lds8 = sizeof(uint32_t) * 64 * ((size_t)(qcap + 2) / 2 + ((size_t)(qcap + 1) / 2 + 3) / 4 + 1);
             auto kern = sym ? (ms1 ? bsw_dp8<true, true> : bsw_dp8<true, false>) : (ms1 ? bsw_dp8<false, true> : bsw_dp8<false, false>);
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds8, s, io, h->cst, d_recs, kb, ke, qcap,

@@ -115,6 +115,18 @@ def bsw_exit_model(batch, params, early_exit=True):
     return score, rows, cells, pass_cells
 
 
+def bsw_rowmax_model(batch, params, resolve=True):
+    """CPU model of the 8-bit bsw kernel's row maximum (tools/gen/bsw_rowmax_model.c): one key per group of four columns, exact keys
+    for the edge cells, the column resolved after the row -> (int32 [n, 6] (score, qle, tle, gtle, gscore, max_off), the oracle's
+    layout; int32 [n] bits saying where a row maximum was tied: 1 inside a group, 2 in neighbouring groups, 4 head cell, 8 remainder
+    pair, 16 tail cell); params as for bsw_exit_model.  resolve=False leaves the column at the winning key's (a group's first column)"""
+    n = batch.n
+    result = np.zeros((n, 6), np.int32); ties = np.zeros(n, np.int32)
+    lib().gab_bsw_rowmax_model(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
+                               _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if resolve else 0), _p(result), _p(ties))
+    return result, ties
+
+
 def write_text(bench, path, seed, n, mode=0, *extra):
     build()
     subprocess.check_call([os.path.join(_GEN_DIR, "gabgen"), bench, path, str(seed), str(n), str(mode)]

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""VALU / DS count of the bsw_dp8 row sweep from a gfx950 assembly listing, priced by the two issue classes of
+profiles/r02_valu_issue.md.
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S genarchbench_amd/csrc/bsw.hip -o bsw.s
+    tools/profiling/bsw_isa_count.py bsw.s [SYM MS1]          (default 1 1: the flagship instantiation)
+
+Prints, for bsw_dp8<SYM, MS1>: the innermost column loop (the depth-2 loop with the most VALU instructions) -- VALU, slow / fast
+split, DS, v_mov_b32 count and the weighted cost slow x 4.22 + fast x 2.56 -- and the VALU count of the row loop's blocks outside
+every depth-2 loop (the per-row code).
+
+Slow class (one instruction every ~4.2 cycles at two waves per SIMD): packed 16-bit, VOP3-only integer ops (v_perm, v_lshl_or,
+v_and_or, v_max3, v_bfi, v_bfe, v_alignbit, v_add3, v_lshl_add, v_mad), 32-bit max / min, 24-bit and 32-bit multiplies, left
+shifts, compares and v_cndmask, SDWA / DPP forms, and any instruction with an SGPR or literal operand.  Everything else that is a
+VOP1 / VOP2 instruction on VGPRs and inline constants is fast class (2.56)."""
+import re
+import sys
+
+SLOW = 4.22
+FAST = 2.56
+SLOW_OPS = re.compile(r"^v_(pk_|perm_|lshl_or|and_or|or3|max3|min3|med3|bfi|bfe|alignb|add3|lshl_add|add_lshl|mad_|mul_|"
+                      r"max_[iu]32|min_[iu]32|lshlrev_b32|lshlrev_b64|lshrrev_b64|cmp|cndmask|add_co|sub_co|subrev_co|addc|subb|readfirstlane|readlane|"
+                      r"mbcnt|xnor|cvt_|ffb|sad_|dot)")
+INLINE = re.compile(r"^(-?\d+|0x[0-9a-f]+)$")
+
+
+def is_inline(tok):
+    if not INLINE.match(tok):
+        return True
+    v = int(tok, 0)
+    return -16 <= v <= 64
+
+
+def classify(line):
+    """-> 'slow' / 'fast' for a VALU instruction line"""
+    op, _, rest = line.partition(" ")
+    if SLOW_OPS.match(op) or "_sdwa" in op or "_dpp" in op or "sdwa" in rest or "row_" in rest:
+        return "slow"
+    for tok in [t.strip() for t in rest.split(",")][1:]:
+        tok = tok.split()[0] if tok else tok
+        if re.match(r"^(s\d+|s\[|vcc|exec|m0|ttmp)", tok):
+            return "slow"
+        if INLINE.match(tok) and not is_inline(tok):
+            return "slow"
+    return "fast"
+
+
+def main():
+    path = sys.argv[1]
+    sym, ms1 = (sys.argv[2], sys.argv[3]) if len(sys.argv) > 3 else ("1", "1")
+    want = f"bsw_dp8ILb{sym}ELb{ms1}EE"
+    lines = open(path).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + want + r"\w*:", l))
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    blocks = []                    # (label, depth, [instructions])
+    depth = 0
+    for l in lines[start:end]:
+        s = l.strip()
+        m = re.match(r"^(\.LBB\d+_\d+):|^; %bb\.(\d+):", s)
+        if m:
+            depth = 2 if ("Parent Loop" in l or "Depth=2" in l) else 1 if "Depth=1" in l else 0
+            blocks.append([m.group(1) or "%bb." + m.group(2), depth, [], "Inner Loop Header" in l and "Depth=2" in l])
+            continue
+        if not blocks or not s or s.startswith((";", ".")):
+            if blocks and "Parent Loop" in l:                     # continuation lines of a block's loop annotation
+                blocks[-1][1] = 2
+            if blocks and "Inner Loop Header: Depth=2" in l:
+                blocks[-1][1] = 2
+                blocks[-1][3] = True
+            continue
+        blocks[-1][2].append(s.split(";")[0].strip())
+    # depth-2 loops: a header block and the depth-2 blocks behind it up to the branch back to the header
+    loops = []
+    for k, b in enumerate(blocks):
+        if b[3]:
+            body = list(b[2])
+            j = k + 1
+            while not any(i.startswith("s_cbranch") and i.endswith(b[0]) for i in body) and j < len(blocks) and blocks[j][1] == 2 and not blocks[j][3]:
+                body += blocks[j][2]
+                j += 1
+            loops.append((b[0], body))
+    label, body = max(loops, key=lambda lb: sum(i.startswith("v_") for i in lb[1]))
+    valu = [i for i in body if i.startswith("v_")]
+    slow = sum(classify(i) == "slow" for i in valu)
+    fast = len(valu) - slow
+    ds = sum(i.startswith("ds_") for i in body)
+    mov = sum(i.startswith("v_mov_b32") for i in valu)
+    row = sum(i.startswith("v_") for b in blocks if b[1] == 1 for i in b[2])
+    print(f"bsw_dp8<{sym},{ms1}> column loop {label}: VALU {len(valu)} (slow {slow}, fast {fast}), DS {ds}, v_mov_b32 {mov}, "
+          f"weighted {slow * SLOW + fast * FAST:.1f} cycles; per-row blocks outside depth-2 loops: VALU {row}")
+    if "-v" in sys.argv:
+        for i in valu:
+            print(f"  {classify(i):4s} {i}")
+
+
+if __name__ == "__main__":
+    main()
