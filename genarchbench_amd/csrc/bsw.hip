@@ -42,6 +42,63 @@
 // On the read-like generator input it removes 23 % of the DP cells and 36 % of the rows (profiles/bsw_early_exit.md);
 // tools/gen/bsw_exit_model.c is the CPU model of the rule that the tests pin the cell counter to.
 //
+// Left prune of score-only calls (same condition as the exit; tools/gen/bsw_exit_model.c is the CPU model of it, and the tests pin
+// every kernel's cell counter to that model).  After row i, once both zero trims have run, with R rows left, `best` already updated
+// for the row and m(j) = max(Hd[j], Ev[j]) of stored cell j, the left edge moves over cell beg while beg < end and
+//     m(beg) == 0                                      (the reference's own trim), or
+//     m(beg) + max_sc * min(R, qlen - beg) <= best,    and -- while beg == 0 -- hb <= 0 or hb + max_sc * min(R, qlen) <= best
+//                                                      for the next row's left edge hb = h0 - o_del - e_del * (i + 2).
+// The exit's bound pass then runs over the narrowed band.  On the read-like input the pruned run evaluates 0.788 of the cells that
+// the exit alone leaves (profiles/bsw_left_prune.md).
+// The rule is RESTRICTED to pairs with
+//   (a) qlen <= w + 1 or h0 - oe_ins - (w + 1) * e_ins <= 0: row -1 is zero from column w + 2 on, so the band clamp of row 0 cuts
+//       only zeros.  A later clamp hides no computed cell (the row before wrote cells up to i + w only), and the zero trim leaves only
+//       zeros behind, so EVERY cell right of `end` that a later row reads again is zero, in both runs (step 5 needs this: with a live
+//       row -1 cell out there the pruned run could read it in a later row than the reference did, against another reference base);
+//   (b) zdrop == 0 or zdrop >= 8 * max_sc: economy, not correctness -- under a smaller z-drop the guard below sends so many pairs
+//       through a second pass that the cell count rises above the reference's (measured on the adversarial generator input).
+// z-drop guard: a pair that has dropped a live cell knows its row maxima only as lower bounds of the reference's.  Either z-drop
+// test needs rowmax < best - zdrop to fire, so such a pair, in a row with zdrop > 0, rowmax <= best and rowmax < best - zdrop, abandons
+// the pass and runs again from row -1 with the prune off and the exit on; the cell counter keeps the abandoned pass.  Step 5 of the
+// proof adds a second, much rarer reason to abandon the pass.
+// Proof.  Call a cell of the REFERENCE's run dead when value + max_sc * min(rows left, columns left) <= best (a zero is dead: it
+// yields M = 0), P the pruned run's value of a cell.  Invariant after every row: the two runs have the same best, best_i, best_j; for
+// every stored cell j >= beg of the pruned run P <= reference, and P == reference or the reference's cell is dead; every cell of the
+// reference that the pruned run does not hold (left of its beg, or right of its end) is dead.
+//   1. Potential never grows along a move (the exit's proof above: M uses a row and a column for at most max_sc, E a row, F a
+//      column, both at a loss; M is taken as max(M, 0), which changes no H, E' or F), `best` never falls and R only shrinks: what is
+//      dead stays dead, and a cell whose largest source is dead is dead.  The DP is monotone in its inputs, so P <= reference
+//      carries over, and a cell that is not dead has a largest source that is not dead, which by the invariant the pruned run holds
+//      at the same value: P == reference there.
+//   2. A dropped cell is zero or, by the invariant, stands for a dead cell of the reference (equal value and the rule's test, or
+//      dead already).  Hd[beg] leads to cell (i + 1, beg) with qlen - beg columns left, Ev[beg] to the same cell with fewer: the test
+//      bounds both.  `beg` never decreases, so the cell is not read again; the next row starts right of it with F = 0 and hleft = 0
+//      where the reference carries values that come from dead cells only -- by induction over the columns from its own beg, whose
+//      sources are dropped cells, dead F and, at column 0, the left edge.  Column 0 is left only when the edge of the next row is
+//      dead; later edges are smaller with fewer rows.  (Stored cell 0 holds this row's edge, which is larger than hb, so its own
+//      test implies the edge's; the term is kept as the rule states it.)
+//   3. best: a cell above `best` is not dead, so the pruned run holds it at the same value, in the same row, and every column that
+//      ties with it too: best, best_i and best_j (last column of the row's maximum) are the reference's.
+//   4. rowmax == 0 in the pruned run: its band holds zeros only, so by the invariant every cell of the reference's row is dead, the
+//      cells right of `end` are zero by (a) and column 0 was left behind a dead edge (a pair that still holds column 0 has dropped
+//      nothing and IS the reference).  No later row of the reference exceeds best: ending here returns its score.
+//   5. Right edge: P <= reference, so the pruned run's last non-zero cell and with it its `end` never lie right of the reference's,
+//      and they fall short of it only over cells that are zero in the pruned run, hence dead in the reference.  A cell (i, c) that the
+//      reference computes right of the pruned band takes M and E from such dead cells (or, by (a), from zeros) and F from the band's
+//      last column, which is at most hleft - e_ins for hleft = H(i, end - 1).  Right-edge guard: a pair that has dropped a live cell
+//      abandons the pass, as under the z-drop guard, in a row with end < qlen, end != i + w + 1 (at the clamp both bands end alike),
+//      hleft > e_ins and hleft - e_ins + max_sc * min(R, qlen - end - 1) > best.  In every row that is kept that F is dead, and so
+//      is every cell the reference has beyond the pruned band; none of them exceeds hleft, so the row's maximum and its column
+//      stand.  When the pruned band grows again it reads a zero where the reference may hold a dead value: P <= reference,
+//      reference dead.  stale_pot is the same number in both runs (best and the clamp are the same) and stays in the bound.
+//      (On the generator's inputs this guard has not fired once; it is there because the proof needs it.)
+//   6. The exit's bound on P: a later cell of the reference above best is not dead, so its chain of largest sources runs through
+//      cells that are not dead, which the pruned run holds at equal values inside [beg, end], at the left edge or among the cells
+//      stale_pot stands for: exactly what the bound covers, by the exit's own proof applied to the pruned run.
+//   7. z-drop: while nothing live has been dropped the run is the reference.  Afterwards rowmax <= the reference's rowmax, and the
+//      reference's test fires only if its rowmax < best - zdrop, hence only if ours is; the guard abandons exactly those rows, before
+//      our own test reads a column that may not be the reference's.  In every row that is kept neither run's test can fire.
+//
 // Roofline: integer-VALU / LDS bound (~20 VALU + 1 LDS read + 1 LDS write per DP cell,
 // ~7.4 k cells per ~210 input bytes); HBM traffic is the algorithmic minimum
 // len1 + len2 + 12 B per pair plus the 4-byte permutation entry.
@@ -220,6 +277,19 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
         for (int w4 = 0; w4 * 4 < qlen; w4++)
             *reinterpret_cast<uint32_t *>(QC + w4 * 256) = load_u32_unaligned(q + w4 * 4);
 
+        // band clamp (bandedSWA.cpp:164-172)
+        int w = c.w;
+        {
+            int lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_ins) / e_ins + 1.);
+            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
+            lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
+            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
+        }
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the left prune of the header comment apply
+        // the left prune needs every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
+        bool prune = score_only && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
+        int best, best_i, best_j, g_i, gscore, max_off;
+      for (;;) {                                            // second trip: a pair the z-drop guard sent back, prune off
         // row -1 (bandedSWA.cpp:159-161); E starts at 0 everywhere
         {
             int prev = h0;
@@ -233,19 +303,10 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 if (WIDE) E[j * 64] = 0u;
             }
         }
-        // band clamp (bandedSWA.cpp:164-172)
-        int w = c.w;
-        {
-            int lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_ins) / e_ins + 1.);
-            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
-            lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
-            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
-        }
-
-        int best = h0, best_i = -1, best_j = -1, g_i = -1, gscore = -1, max_off = 0;
+        best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
         int beg = 0, end = qlen;
-        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit of the header comment applies
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
+        bool dropped = false, abandon = false;              // the prune has dropped a live cell; the z-drop guard fired
         uint32_t tw = load_u32_unaligned(t);       // 4 reference bases, refreshed every 4 rows
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -309,6 +370,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 max_off = off > max_off ? off : max_off;
             } else {
                 if (c.zdrop > 0) {
+                    if (dropped && rowmax < best - c.zdrop) { abandon = true; break; }     // the reference's row maximum may differ here
                     int di = i - best_i, dj = rowmax_j - best_j;
                     if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
                     else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
@@ -316,6 +378,9 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
                 try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
+            // right-edge guard of the left prune (header comment, step 5)
+            if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
+                hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best) { abandon = true; break; }
             // trim all-zero cells from both band edges (bandedSWA.cpp:234-237)
             if (WIDE) {
                 for (j = beg; j < end && H[j * 64] == 0u && E[j * 64] == 0u; j++) {}
@@ -327,6 +392,21 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 for (j = end; j >= beg && H[j * 64] == 0u; j--) {}
             }
             end = j + 2 < qlen ? j + 2 : qlen;
+            if (prune && beg < end) {                       // left prune: cell beg is live here, the zero trim stopped at it
+                bool go = true;
+                if (beg == 0) {
+                    const int hb = h0 - c.o_del - e_del * (i + 2);
+                    go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
+                }
+                if (go) {
+                    for (j = beg; j < end; j++) {
+                        const int m = WIDE ? max((int)H[j * 64], (int)E[j * 64]) : max((int)(H[j * 64] & 0xffffu), (int)(H[j * 64] >> 16));
+                        if (m && m + c.max_sc * min(rows_left, qlen - j) > best) break;
+                    }
+                    dropped = dropped || j > beg;
+                    beg = j;
+                }
+            }
             if (try_exit) {
                 int bound = stale_pot;
                 if (beg == 0) {
@@ -340,6 +420,9 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 if (bound <= best) break;
             }
         }
+        if (!abandon) break;
+        prune = false;
+      }
         score_out[id] = best;
         if (result_out) {
             gab_bsw_result r;
@@ -380,6 +463,9 @@ __device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
 }
 __device__ __forceinline__ uint32_t pk_subsat_u16_k(uint32_t a, uint32_t k) {    // max(half - k, 0), unsigned halves
     uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(k)); return r;
+}
+__device__ __forceinline__ uint32_t pk_subsat_u16_v(uint32_t a, uint32_t b) {    // max(half of a - half of b, 0), unsigned halves
+    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r;
 }
 __device__ __forceinline__ uint32_t and_or_b32(uint32_t a, uint32_t mask, uint32_t k) {   // (a & mask) | k, mask uniform
     uint32_t r; asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(k)); return r;
@@ -465,6 +551,18 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 QPAIR(p0 + b) = (uint8_t)(lo | hi << 4);
             }
         }
+        int w = c.w;
+        {
+            int lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_ins) / e_ins + 1.);
+            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
+            lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
+            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
+        }
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the left prune of the header comment apply
+        // the left prune needs every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
+        bool prune = score_only && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
+        int best, best_i, best_j, g_i, gscore, max_off;
+      for (;;) {                                            // second trip: a pair the z-drop guard sent back, prune off
         // row -1 (bandedSWA.cpp:159-161); E = 0
         {
             int prev = h0;
@@ -477,17 +575,10 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 CELL16(j) = (uint16_t)v;
             }
         }
-        int w = c.w;
-        {
-            int lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_ins) / e_ins + 1.);
-            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
-            lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
-            lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
-        }
-        int best = h0, best_i = -1, best_j = -1, g_i = -1, gscore = -1, max_off = 0;
+        best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
         int beg = 0, end = qlen;
-        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit of the header comment applies
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
+        bool dropped = false, abandon = false;              // the prune has dropped a live cell; the z-drop guard fired
         uint32_t tw = load_u32_unaligned(t);
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -651,6 +742,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 max_off = off > max_off ? off : max_off;
             } else {
                 if (c.zdrop > 0) {
+                    if (dropped && rowmax < best - c.zdrop) { abandon = true; break; }     // the reference's row maximum may differ here
                     int di = i - best_i, dj = rowmax_j - best_j;
                     if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
                     else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
@@ -658,6 +750,9 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
                 try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
+            // right-edge guard of the left prune (header comment, step 5)
+            if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
+                hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best) { abandon = true; break; }
             // Band trimming (bandedSWA.cpp:234-237).  The four cells next to either edge are fetched in ONE LDS round
             // trip (whole pair words; cells outside [beg, end] only ever shorten the count and the clamps below undo
             // that); the cell-by-cell loops of the reference run only when all four are zero.
@@ -665,6 +760,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 uint64_t x = (uint64_t)b1 << 32 | b0;                      // cells 2pb .. 2pb+3, low half first
                 if (beg & 1) x = (x >> 16) | (uint64_t)(b2 & 0xffffu) << 48;
                 const int lz = x ? __builtin_ctzll(x) >> 4 : 4;
+                const int beg0 = beg;
                 j = beg + lz;
                 if (lz == 4) for (; j < end && CELL16(j) == 0; j++) {}
                 beg = j < end ? j : end;
@@ -674,8 +770,48 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 j = end - tz;
                 if (tz == 4) for (; j >= beg && CELL16(j) == 0; j--) {}
                 j = j > beg - 1 ? j : beg - 1;
+                end = j + 2 < qlen ? j + 2 : qlen;
+                // Left prune (header comment): cell beg is live here, the zero trim stopped at it.  The four cells of x are
+                // judged in packed 16-bit halves -- m = max(H, E) <= 255 and max_sc * columns left <= 255, and a half right of
+                // the band or the query may hold anything: the clamp to `end` below undoes what it adds -- and the cell-by-cell
+                // loop runs only when all four go or the zero trim has left them behind.
+                if (prune && beg < end) {
+                    bool go = true;
+                    if (beg == 0) {
+                        const int hb = h0 - c.o_del - e_del * (i + 2);
+                        go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
+                    }
+                    if (go) {
+                        j = beg;
+                        if (lz < 4) {
+                            const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+                            const uint32_t r2 = as_u32(pk_splat(min(rows_left, qlen))), m2 = as_u32(pk_splat(c.max_sc));
+                            const uint32_t best2 = (uint32_t)best * 0x00010001u;
+                            const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
+                            const uint32_t ml = pk_max_i16(xl & 0x00ff00ffu, (xl >> 8) & 0x00ff00ffu);
+                            const uint32_t mh = pk_max_i16(xh & 0x00ff00ffu, (xh >> 8) & 0x00ff00ffu);
+                            // per half: non-zero where the cell is live and its potential exceeds best
+                            const uint32_t sl = pk_mul_lo(pk_subsat_u16_v(add_u32_v(ml, pk_mul_lo(pk_min_u16(cl01, r2), m2)), best2),
+                                                          pk_min_u16_1(ml));
+                            const uint32_t sh = pk_mul_lo(pk_subsat_u16_v(add_u32_v(mh, pk_mul_lo(pk_min_u16(cl01 - 0x00020002u, r2), m2)), best2),
+                                                          pk_min_u16_1(mh));
+                            const uint64_t stay = (uint64_t)sh << 32 | sl;
+                            const int lp = stay ? __builtin_ctzll(stay) >> 4 : 4;
+                            j = beg0 + lp;
+                            if (lp < 4) go = false;
+                        }
+                        if (go)
+                            for (; j < end; j++) {
+                                const uint32_t cv = CELL16(j);
+                                const int m = max((int)(cv & 0xffu), (int)(cv >> 8));
+                                if (m && m + c.max_sc * min(rows_left, qlen - j) > best) break;
+                            }
+                        j = j < end ? j : end;
+                        dropped = dropped || j > beg;
+                        beg = j;
+                    }
+                }
             }
-            end = j + 2 < qlen ? j + 2 : qlen;
             if (try_exit) {
                 int bound = stale_pot;
                 if (beg == 0) {
@@ -702,6 +838,9 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 if (bound <= best) break;
             }
         }
+        if (!abandon) break;
+        prune = false;
+      }
         score_out[id] = best;
         if (result_out) {
             gab_bsw_result r;

@@ -103,16 +103,20 @@ def bsw_from_arrays(refs, qrys, h0s):
     return BswBatch(ref, ref_off, qry, qry_off, len1, len2, np.array(h0s, np.int32))
 
 
-def bsw_exit_model(batch, params, early_exit=True):
-    """CPU model of the bsw kernels' score-only early exit (tools/gen/bsw_exit_model.c) -> per-pair (score, rows swept, DP cells
-    evaluated, cells read by the bound passes); params is a ctypes struct laid out like gab_bsw_params (include/gab.h).
-    early_exit=False: the reference's full sweep"""
+def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, wrong_potential=False):
+    """CPU model of the bsw kernels' score-only early exit and left-edge prune (tools/gen/bsw_exit_model.c) -> per-pair (score, rows
+    swept, DP cells evaluated, cells read by the bound passes); params is a ctypes struct laid out like gab_bsw_params
+    (include/gab.h).  early_exit=False: the reference's full sweep.  prune=False: the exit alone.  restarts=True appends a fifth
+    array: 1 where the pair abandoned its pruned pass for the z-drop guard and ran again without the prune.  wrong_potential=True
+    is the tests' negative control (the prune's potential counts two columns too few)"""
     n = batch.n
     score = np.zeros(n, np.int32); rows = np.zeros(n, np.int32); cells = np.zeros(n, np.int64); pass_cells = np.zeros(n, np.int64)
+    redo = np.zeros(n, np.int32)
     lib().gab_bsw_exit_model(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
-                             _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if early_exit else 0), _p(score), _p(rows),
-                             _p(cells), _p(pass_cells))
-    return score, rows, cells, pass_cells
+                             _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if early_exit else 0),
+                             C.c_int((2 if wrong_potential else 1) if prune else 0), _p(score), _p(rows), _p(cells), _p(pass_cells),
+                             _p(redo))
+    return (score, rows, cells, pass_cells, redo) if restarts else (score, rows, cells, pass_cells)
 
 
 def bsw_rowmax_model(batch, params, resolve=True):

@@ -1,4 +1,5 @@
-/* CPU model of the score-only early exit of the bsw DP kernels (genarchbench_amd/csrc/bsw.hip) -- TEST INFRASTRUCTURE ONLY.
+/* CPU model of the score-only early exit and left-edge prune of the bsw DP kernels (genarchbench_amd/csrc/bsw.hip) -- TEST
+ * INFRASTRUCTURE ONLY.  The prune is described at model_one below.
  *
  * The scalar banded Smith-Waterman (BandedPairWiseSW::scalarBandedSWA of the reference), restated with the upper-bound exit
  * exactly as the kernels apply it, so
@@ -13,7 +14,7 @@
  * fires (it cuts live cells, each at most `best`, which a later, wider row reads again).
  * The bound is evaluated only in rows that did not raise `best` and whose maximum cell alone passes it:
  *     rowmax + max_sc * min(R, qlen - 1 - rowmax_j) <= best.
- * With early_exit == 0 these are the score, rows and cells of the reference's full sweep. */
+ * With early_exit == 0 these are the score, rows and cells of the reference's full sweep (the prune needs the exit on). */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,17 +24,27 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
     int8_t mat[25];
 } gab_bsw_model_params;
 
+/* Left-edge prune (prune != 0, score-only rule like the exit): after row i and both zero trims, with m(j) = max(Hd[j], Ev[j]),
+ * the band's left edge moves right over cell beg while beg < end and
+ *     m(beg) == 0                                                      (the reference's own trim), or
+ *     m(beg) + max_sc * min(R, qlen - beg) <= best, and -- while beg == 0 -- the next row's left boundary
+ *     hb = h0 - o_del - e_del * (i + 2) is <= 0 or has hb + max_sc * min(R, qlen) <= best.
+ * It applies only to pairs whose row -1 leaves no non-zero cell behind the first row's band clamp (qlen <= w + 1 or
+ * h0 - oe_ins - (w + 1) * e_ins <= 0): then every cell right of `end` that a later row reads again is zero (bsw.hip's header has
+ * the proof), and -- economy, not correctness -- only with zdrop == 0 or zdrop >= 8 * max_sc: under a z-drop worth fewer than eight
+ * matches the guard below sends so many pairs back that the second passes cost more cells than the prune saves.
+ * A pair that has dropped a live cell knows its row maxima only as lower bounds, so a row of it in which a z-drop could
+ * fire (zdrop > 0, rowmax <= best, rowmax < best - zdrop) abandons the pass: the pair restarts from row -1 with the prune off and
+ * the exit on, and the abandoned pass stays in the cell count.  So does a row of such a pair whose band ends inside the query and
+ * short of the clamp (end < qlen, end != i + w + 1) on a cell hleft = H(i, end - 1) with hleft > e_ins and
+ * hleft - e_ins + max_sc * min(R, qlen - end - 1) > best: the reference's band may be wider there and carry that F on.
+ * prune == 2 is a TEST-ONLY wrong rule (columns left short by two), the negative control of tests/test_bsw_left_prune.py. */
 static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0,
-                      int early_exit, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells) {
+                      int early_exit, int prune, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells,
+                      int64_t *pass_cells, int32_t *restarted) {
     const int oe_del = p->o_del + p->e_del, oe_ins = p->o_ins + p->e_ins;
     const int e_del = p->e_del, e_ins = p->e_ins;
     int64_t ncell = 0, npass = 0;
-
-    memset(Hd, 0, sizeof(int32_t) * (size_t)(qlen + 1));
-    memset(Ev, 0, sizeof(int32_t) * (size_t)(qlen + 1));
-    Hd[0] = h0;
-    if (qlen >= 1) Hd[1] = h0 > oe_ins ? h0 - oe_ins : 0;
-    for (int j = 2; j <= qlen && Hd[j - 1] > e_ins; j++) Hd[j] = Hd[j - 1] - e_ins;
 
     int max_sc = 0;
     for (int k = 0; k < 25; k++) if (p->mat[k] > max_sc) max_sc = p->mat[k];
@@ -44,84 +55,127 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
     lim = (int)((double)(qlen * max_sc + p->end_bonus - p->o_del) / e_del + 1.);
     if (lim < 1) lim = 1;
     if (w > lim) w = lim;
+    const int prune_ok = early_exit && prune && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) &&
+                         (p->zdrop == 0 || p->zdrop >= 8 * max_sc);
+    const int short_by = prune == 2 ? 2 : 0;
 
-    int best = h0, best_i = -1, best_j = -1, stale_pot = 0;
-    int beg = 0, end = qlen, i;
-    for (i = 0; i < tlen; i++) {
-        const int8_t *srow = p->mat + 5 * (target[i] > 4 ? 4 : target[i]);
-        const int R = tlen - 1 - i;
-        if (beg < i - w) beg = i - w;
-        if (end > i + w + 1) {
-            end = i + w + 1;
-            int sp = best + max_sc * (qlen - end);
-            if (sp > stale_pot) stale_pot = sp;
-        }
-        if (end > qlen) end = qlen;
-        int hleft = 0;
-        if (beg == 0) {
-            hleft = h0 - (p->o_del + e_del * (i + 1));
-            if (hleft < 0) hleft = 0;
-        }
-        int f = 0, rowmax = 0, rowmax_j = -1, j;
-        for (j = beg; j < end; j++) {
-            int diag = Hd[j], e = Ev[j];
-            Hd[j] = hleft;
-            int M = diag ? diag + srow[query[j] > 4 ? 4 : query[j]] : 0;
-            int h = M > e ? M : e;
-            if (f > h) h = f;
-            hleft = h;
-            if (!(rowmax > h)) rowmax_j = j;
-            if (h > rowmax) rowmax = h;
-            int t = M - oe_del; if (t < 0) t = 0;
-            e -= e_del; if (t > e) e = t;
-            Ev[j] = e;
-            t = M - oe_ins; if (t < 0) t = 0;
-            f -= e_ins; if (t > f) f = t;
-        }
-        ncell += (end > beg) ? end - beg : 0;
-        Hd[end] = hleft; Ev[end] = 0;
-        if (rowmax == 0) { i++; break; }
-        int try_exit = 0;
-        if (rowmax > best) {
-            best = rowmax; best_i = i; best_j = rowmax_j;
-        } else {
-            if (p->zdrop > 0) {
-                int di = i - best_i, dj = rowmax_j - best_j;
-                if (di > dj) {
-                    if (best - rowmax - (di - dj) * e_del > p->zdrop) { i++; break; }
-                } else {
-                    if (best - rowmax - (dj - di) * e_ins > p->zdrop) { i++; break; }
+    int best = h0, i = 0, redo = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        const int do_prune = prune_ok && pass == 0;
+        int abandon = 0, dropped = 0;
+        memset(Hd, 0, sizeof(int32_t) * (size_t)(qlen + 1));
+        memset(Ev, 0, sizeof(int32_t) * (size_t)(qlen + 1));
+        Hd[0] = h0;
+        if (qlen >= 1) Hd[1] = h0 > oe_ins ? h0 - oe_ins : 0;
+        for (int j = 2; j <= qlen && Hd[j - 1] > e_ins; j++) Hd[j] = Hd[j - 1] - e_ins;
+
+        int best_i = -1, best_j = -1, stale_pot = 0;
+        int beg = 0, end = qlen;
+        best = h0;
+        for (i = 0; i < tlen; i++) {
+            const int8_t *srow = p->mat + 5 * (target[i] > 4 ? 4 : target[i]);
+            const int R = tlen - 1 - i;
+            if (beg < i - w) beg = i - w;
+            if (end > i + w + 1) {
+                end = i + w + 1;
+                int sp = best + max_sc * (qlen - end);
+                if (sp > stale_pot) stale_pot = sp;
+            }
+            if (end > qlen) end = qlen;
+            int hleft = 0;
+            if (beg == 0) {
+                hleft = h0 - (p->o_del + e_del * (i + 1));
+                if (hleft < 0) hleft = 0;
+            }
+            int f = 0, rowmax = 0, rowmax_j = -1, j;
+            for (j = beg; j < end; j++) {
+                int diag = Hd[j], e = Ev[j];
+                Hd[j] = hleft;
+                int M = diag ? diag + srow[query[j] > 4 ? 4 : query[j]] : 0;
+                int h = M > e ? M : e;
+                if (f > h) h = f;
+                hleft = h;
+                if (!(rowmax > h)) rowmax_j = j;
+                if (h > rowmax) rowmax = h;
+                int t = M - oe_del; if (t < 0) t = 0;
+                e -= e_del; if (t > e) e = t;
+                Ev[j] = e;
+                t = M - oe_ins; if (t < 0) t = 0;
+                f -= e_ins; if (t > f) f = t;
+            }
+            ncell += (end > beg) ? end - beg : 0;
+            Hd[end] = hleft; Ev[end] = 0;
+            if (rowmax == 0) { i++; break; }
+            int try_exit = 0;
+            if (rowmax > best) {
+                best = rowmax; best_i = i; best_j = rowmax_j;
+            } else {
+                if (p->zdrop > 0) {
+                    if (dropped && rowmax < best - p->zdrop) { abandon = 1; i++; break; }
+                    int di = i - best_i, dj = rowmax_j - best_j;
+                    if (di > dj) {
+                        if (best - rowmax - (di - dj) * e_del > p->zdrop) { i++; break; }
+                    } else {
+                        if (best - rowmax - (dj - di) * e_ins > p->zdrop) { i++; break; }
+                    }
+                }
+                int cl = qlen - 1 - rowmax_j;
+                try_exit = early_exit && rowmax + max_sc * (R < cl ? R : cl) <= best;
+            }
+            /* right-edge guard: the F that leaves the band's last column is at most hleft - e_ins; the reference, whose band may
+             * reach further right than a pruned pair's, carries it on */
+            if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins) {
+                int cl = qlen - end - 1;
+                if (hleft - e_ins + max_sc * (R < cl ? R : cl) > best) { abandon = 1; i++; break; }
+            }
+            for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
+            beg = j;
+            for (j = end; j >= beg && Hd[j] == 0 && Ev[j] == 0; j--) {}
+            end = j + 2 < qlen ? j + 2 : qlen;
+            if (do_prune && beg < end) {
+                int go = 1;
+                if (beg == 0) {                    /* (cell 0 is live here: the zero trim stopped at it) */
+                    int hb = h0 - p->o_del - e_del * (i + 2);
+                    go = hb <= 0 || hb + max_sc * (R < qlen ? R : qlen) <= best;
+                }
+                if (go) {
+                    const int from = beg;
+                    for (; beg < end; beg++) {
+                        int m = Hd[beg] > Ev[beg] ? Hd[beg] : Ev[beg];
+                        int cl = qlen - beg - short_by;
+                        if (m && m + max_sc * (R < cl ? R : cl) > best) break;
+                    }
+                    if (beg > from) dropped = 1;   /* (cell `from` is live) */
                 }
             }
-            int cl = qlen - 1 - rowmax_j;
-            try_exit = early_exit && rowmax + max_sc * (R < cl ? R : cl) <= best;
-        }
-        for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
-        beg = j;
-        for (j = end; j >= beg && Hd[j] == 0 && Ev[j] == 0; j--) {}
-        end = j + 2 < qlen ? j + 2 : qlen;
-        if (try_exit) {
-            int bound = stale_pot;
-            if (beg == 0) {
-                int hb = h0 - p->o_del - e_del * (i + 2);
-                if (hb > 0) { hb += max_sc * (R < qlen ? R : qlen); if (hb > bound) bound = hb; }
+            if (try_exit) {
+                int bound = stale_pot;
+                if (beg == 0) {
+                    int hb = h0 - p->o_del - e_del * (i + 2);
+                    if (hb > 0) { hb += max_sc * (R < qlen ? R : qlen); if (hb > bound) bound = hb; }
+                }
+                for (j = beg; j <= end; j++) {
+                    int cl = qlen - j;
+                    int pot = Hd[j] ? Hd[j] + max_sc * (R < cl ? R : cl) : 0;
+                    if (pot > bound) bound = pot;
+                }
+                npass += end >= beg ? end - beg + 1 : 0;
+                if (bound <= best) { i++; break; }
             }
-            for (j = beg; j <= end; j++) {
-                int cl = qlen - j;
-                int pot = Hd[j] ? Hd[j] + max_sc * (R < cl ? R : cl) : 0;
-                if (pot > bound) bound = pot;
-            }
-            npass += end >= beg ? end - beg + 1 : 0;
-            if (bound <= best) { i++; break; }
         }
+        if (!abandon) break;
+        redo = 1;
     }
     *score = best; *rows = i; *cells = ncell; *pass_cells = npass;
+    if (restarted) *restarted = redo;
 }
 
-/* per pair: score, rows swept, DP cells evaluated, cells read by the bound passes */
+/* per pair: score, rows swept (of the pass that finished), DP cells evaluated (an abandoned pass included), cells read by the bound
+ * passes, and -- restarted may be NULL -- whether the pair abandoned its pruned pass */
 void gab_bsw_exit_model(const gab_bsw_model_params *p, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry,
                         const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n,
-                        int early_exit, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells) {
+                        int early_exit, int prune, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells,
+                        int32_t *restarted) {
 #pragma omp parallel
     {
         int cap = 512;
@@ -134,8 +188,8 @@ void gab_bsw_exit_model(const gab_bsw_model_params *p, const uint8_t *ref, const
                 free(buf);
                 buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
             }
-            model_one(p, ql, qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], early_exit, buf, buf + ql + 1, &score[k],
-                      &rows[k], &cells[k], &pass_cells[k]);
+            model_one(p, ql, qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], early_exit, prune, buf, buf + ql + 1, &score[k],
+                      &rows[k], &cells[k], &pass_cells[k], restarted ? &restarted[k] : NULL);
         }
         free(buf);
     }

@@ -5,9 +5,9 @@ profiles/r02_valu_issue.md.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S genarchbench_amd/csrc/bsw.hip -o bsw.s
     tools/profiling/bsw_isa_count.py bsw.s [SYM MS1]          (default 1 1: the flagship instantiation)
 
-Prints, for bsw_dp8<SYM, MS1>: the innermost column loop (the depth-2 loop with the most VALU instructions) -- VALU, slow / fast
-split, DS, v_mov_b32 count and the weighted cost slow x 4.22 + fast x 2.56 -- and the VALU count of the row loop's blocks outside
-every depth-2 loop (the per-row code).
+Prints, for bsw_dp8<SYM, MS1>: the innermost column loop (the innermost loop with the most VALU instructions) -- VALU, slow / fast
+split, DS, v_mov_b32 count and the weighted cost slow x 4.22 + fast x 2.56 -- and the VALU count of the blocks of the loop around it that lie outside
+every inner loop (the per-row code).
 
 Slow class (one instruction every ~4.2 cycles at two waves per SIMD): packed 16-bit, VOP3-only integer ops (v_perm, v_lshl_or,
 v_and_or, v_max3, v_bfi, v_bfe, v_alignbit, v_add3, v_lshl_add, v_mad), 32-bit max / min, 24-bit and 32-bit multiplies, left
@@ -52,42 +52,45 @@ def main():
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + want + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    blocks = []                    # (label, depth, [instructions])
-    depth = 0
+    # (label, depth, [instructions], inner loop header): the depth is the one the block's own annotation names ("This [Inner] Loop
+    # Header: Depth=N" or "in Loop: Header=... Depth=N"; its "Parent Loop" lines name the loops around it).  The row loop is the
+    # column loop's parent, whatever lies around it (the score-only kernels wrap it in the loop of the prune's second pass).
+    blocks = []
+    own = re.compile(r"(?:Loop Header: Depth=|in Loop: Header=\S+ Depth=)(\d+)")
     for l in lines[start:end]:
         s = l.strip()
         m = re.match(r"^(\.LBB\d+_\d+):|^; %bb\.(\d+):", s)
         if m:
-            depth = 2 if ("Parent Loop" in l or "Depth=2" in l) else 1 if "Depth=1" in l else 0
-            blocks.append([m.group(1) or "%bb." + m.group(2), depth, [], "Inner Loop Header" in l and "Depth=2" in l])
+            d = own.search(l)
+            blocks.append([m.group(1) or "%bb." + m.group(2), int(d.group(1)) if d else 0, [], "Inner Loop Header" in l])
             continue
         if not blocks or not s or s.startswith((";", ".")):
-            if blocks and "Parent Loop" in l:                     # continuation lines of a block's loop annotation
-                blocks[-1][1] = 2
-            if blocks and "Inner Loop Header: Depth=2" in l:
-                blocks[-1][1] = 2
-                blocks[-1][3] = True
+            if blocks and not blocks[-1][2]:                      # continuation lines of a block's loop annotation
+                d = own.search(l)
+                if d:
+                    blocks[-1][1] = int(d.group(1))
+                    blocks[-1][3] = blocks[-1][3] or "Inner Loop Header" in l
             continue
         blocks[-1][2].append(s.split(";")[0].strip())
-    # depth-2 loops: a header block and the depth-2 blocks behind it up to the branch back to the header
+    # innermost loops: a header block and the blocks of its depth behind it up to the branch back to the header
     loops = []
     for k, b in enumerate(blocks):
         if b[3]:
             body = list(b[2])
             j = k + 1
-            while not any(i.startswith("s_cbranch") and i.endswith(b[0]) for i in body) and j < len(blocks) and blocks[j][1] == 2 and not blocks[j][3]:
+            while not any(i.startswith("s_cbranch") and i.endswith(b[0]) for i in body) and j < len(blocks) and blocks[j][1] == b[1] and not blocks[j][3]:
                 body += blocks[j][2]
                 j += 1
-            loops.append((b[0], body))
-    label, body = max(loops, key=lambda lb: sum(i.startswith("v_") for i in lb[1]))
+            loops.append((b[0], body, b[1]))
+    label, body, cdepth = max(loops, key=lambda lb: sum(i.startswith("v_") for i in lb[1]))
     valu = [i for i in body if i.startswith("v_")]
     slow = sum(classify(i) == "slow" for i in valu)
     fast = len(valu) - slow
     ds = sum(i.startswith("ds_") for i in body)
     mov = sum(i.startswith("v_mov_b32") for i in valu)
-    row = sum(i.startswith("v_") for b in blocks if b[1] == 1 for i in b[2])
+    row = sum(i.startswith("v_") for b in blocks if b[1] == cdepth - 1 for i in b[2])
     print(f"bsw_dp8<{sym},{ms1}> column loop {label}: VALU {len(valu)} (slow {slow}, fast {fast}), DS {ds}, v_mov_b32 {mov}, "
-          f"weighted {slow * SLOW + fast * FAST:.1f} cycles; per-row blocks outside depth-2 loops: VALU {row}")
+          f"weighted {slow * SLOW + fast * FAST:.1f} cycles; per-row blocks outside the inner loops: VALU {row}")
     if "-v" in sys.argv:
         for i in valu:
             print(f"  {classify(i):4s} {i}")
