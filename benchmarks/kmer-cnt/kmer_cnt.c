@@ -11,7 +11,7 @@
  * another.
  *
  * Outside the region of interest, as in the reference: the config file (key = value lines, '#' comments, "%include other.cfg"
- * relative to the including file, kmer-cnt/config.h:36-72; only kmer_size and use_minimizers are read), then every reads file
+ * relative to the including file, kmer-cnt/config.h:36-72; five keys are read, see kc_key_names), then every reads file
  * in the order given, FASTA (multi-line) or FASTQ by its suffix, plain or gzip (kmer-cnt/sequence_container.cpp:22-46, 159-308).
  * A byte that is not one of ACGTacgt: the reference means to replace it by "ACGT"[rand() % 4] (validateSequence,
  * kmer-cnt/sequence_container.cpp:318-328), but its test compares a size_t table entry of -1 with -1U, which never holds where
@@ -21,6 +21,8 @@
  * the same to the record's text (positions counted from the start of the record, its lines joined), which is what makes its
  * numbers equal the reference's on reads with N.  Reads LONGER than max(--min-read, --min-ovlp) are kept
  * (kmer-cnt/kmer_cnt.cpp:205, kmer-cnt/sequence_container.cpp:100-106).
+ * use_minimizers = 1 in the config file selects the minimizer index instead of the count (build_minimizer_index below); it also needs
+ * minimizer_window, repeat_kmer_rate and assemble_kmer_sample there, and runs on the first GPU whatever -g says.
  * Inside it: ONE gab_kmer_count_part per GPU over the kept reads, all at once (that GPU's copy of the reads included), where the
  * reference runs vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).  -g 1 is one gab_kmer_count_part(0 of 1) = gab_kmer_count.
  */
@@ -56,7 +58,10 @@ static void die(const char *fmt, ...) {
 }
 
 /* ---- config ---------------------------------------------------------------------------------------------------------------------- */
-typedef struct { int have_kmer_size, have_use_minimizers; double kmer_size, use_minimizers; } kc_config;
+/* the keys this driver reads; values are floats, as the reference's Config keeps them (kmer-cnt/config.h:69, 100) */
+enum { KC_KMER_SIZE, KC_USE_MINIMIZERS, KC_MINIMIZER_WINDOW, KC_REPEAT_KMER_RATE, KC_ASSEMBLE_KMER_SAMPLE, KC_NKEYS };
+static const char *const kc_key_names[KC_NKEYS] = {"kmer_size", "use_minimizers", "minimizer_window", "repeat_kmer_rate", "assemble_kmer_sample"};
+typedef struct { int have[KC_NKEYS]; float value[KC_NKEYS]; } kc_config;
 static char *trim(char *s) {
     while (*s == ' ' || *s == '\t' || *s == '\r' || *s == '\n') s++;
     char *e = s + strlen(s);
@@ -90,8 +95,8 @@ static void config_load(const char *path, kc_config *cfg, int depth) {
         *eq = 0;
         const char *key = trim(s), *val = trim(eq + 1);
         log_debug("\t%s=%s", key, val);
-        if (strcmp(key, "kmer_size") == 0) { cfg->kmer_size = atof(val); cfg->have_kmer_size = 1; }
-        else if (strcmp(key, "use_minimizers") == 0) { cfg->use_minimizers = atof(val); cfg->have_use_minimizers = 1; }
+        for (int i = 0; i < KC_NKEYS; i++)
+            if (strcmp(key, kc_key_names[i]) == 0) { cfg->value[i] = (float)atof(val); cfg->have[i] = 1; }
     }
     fclose(f);
 }
@@ -238,6 +243,46 @@ static void count_part(int g, void *arg) {
     if (P->rc[g]) snprintf(P->err[g], sizeof P->err[g], "%s", gab_last_error());      /* (the message is the calling thread's) */
 }
 
+/* use_minimizers = 1: ONE gab_kmer_index_minimizers over the kept reads where the reference runs
+ * vertexIndex.buildIndexMinimizers(1, minimizer_window) (kmer-cnt/kmer_cnt.cpp:282-287), and its debug lines in its order
+ * (kmer-cnt/vertex_index.cpp:190-216, 481, 494-500): the floats are computed with the reference's float expressions and written as
+ * its ostream writes them (%g).  The index stays on the first GPU: its filter needs the number of minimizers and of distinct
+ * k-mers of the WHOLE input before any list is laid out, so key-space partitions would have to meet in the middle of the call. */
+static int build_minimizer_index(const kc_reads *R, int kmer, int window, float rate, int32_t min_len, int ngpus) {
+    if (ngpus > 1) log_debug("The minimizer index is built on the first of the %d GPUs (it is not partitioned)", ngpus);
+    gab_kmer *h = NULL;
+    GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(0), &h), "gab_kmer_create");
+    GAB_DIE_IF(gab_kmer_reserve(h, R->n, (int64_t)R->bytes), "gab_kmer_reserve");
+    if (R->bytes) gab_pin(R->seq, R->bytes);
+    gab_kmer_index_result x;
+    memset(&x, 0, sizeof x);
+
+    const double t0 = gab_now();
+    gab_roi_begin_n(1);
+    GAB_DIE_IF(gab_kmer_index_minimizers(h, R->seq, R->off, R->len, R->n, kmer, window, min_len, rate, &x), "gab_kmer_index_minimizers");
+    const float mean = (float)(size_t)x.minimizers / ((size_t)x.distinct + 1);
+    const float filtered_rate = (float)(size_t)x.filtered_entries / (size_t)x.minimizers;
+    log_debug("Mean k-mer frequency: %g", (double)mean);
+    log_debug("Repetitive k-mer frequency: %lld", (long long)x.repetitive_frequency);
+    log_debug("Filtered %lld repetitive k-mers (%g)", (long long)x.filtered_entries, (double)filtered_rate);
+    log_debug("Sorting k-mer index");
+    log_debug("Selected k-mers: %lld", (long long)x.selected_kmers);
+    log_debug("K-mer index size: %lld", (long long)x.index_entries);
+    log_debug("Mean k-mer frequency: %g", (double)((float)(size_t)x.index_entries / (size_t)x.selected_kmers));
+    log_debug("Minimizer rate: %g", (double)((float)(size_t)x.total_len / (size_t)x.index_entries));
+    gab_roi_end();
+    const double t1 = gab_now();
+
+    float ms[4] = {0, 0, 0, 0};
+    (void)gab_kmer_index_last_phases(h, &ms[0], &ms[1], &ms[2], &ms[3]);
+    log_debug("Minimizers: %lld of %lld reads, %lld distinct k-mers, %lld removed; device: sketch %.3f ms, count %.3f ms, fill %.3f ms, sort %.3f ms",
+              (long long)x.minimizers, (long long)x.reads_kept, (long long)x.distinct, (long long)x.filtered_kmers, ms[0], ms[1], ms[2], ms[3]);
+    fprintf(stderr, "Kernel time: %.3f sec\n", t1 - t0);
+    if (R->bytes) gab_unpin(R->seq);
+    gab_kmer_destroy(h);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, c, idx = 0;
     const char *reads = NULL, *config = NULL, *logfile = NULL;
@@ -267,11 +312,20 @@ int main(int argc, char **argv) {
     memset(&cfg, 0, sizeof cfg);
     config_load(config, &cfg, 0);
     if (kmer == -1) {
-        if (!cfg.have_kmer_size) die("No such parameter: kmer_size (give --kmer or set it in %s)", config);
-        kmer = (int)cfg.kmer_size;
+        if (!cfg.have[KC_KMER_SIZE]) die("No such parameter: kmer_size (give --kmer or set it in %s)", config);
+        kmer = (int)cfg.value[KC_KMER_SIZE];
     }
-    if (cfg.have_use_minimizers && cfg.use_minimizers != 0.0)
-        die("use_minimizers = 1 selects the minimizer index (buildIndexMinimizers), which this driver does not build; set use_minimizers = 0");
+    /* use_minimizers != 0: the minimizer index.  The reference then reads assemble_kmer_sample before the region of interest,
+     * minimizer_window and repeat_kmer_rate inside it (kmer-cnt/kmer_cnt.cpp:216-217, 282-286, kmer-cnt/vertex_index.cpp:433) and
+     * throws "No such parameter: KEY" for a missing one (kmer-cnt/config.h:74-82); here all three are asked for before any work. */
+    const int use_minimizers = cfg.have[KC_USE_MINIMIZERS] && cfg.value[KC_USE_MINIMIZERS] != 0.0f;
+    int window = 0;
+    if (use_minimizers) {
+        for (int i = KC_MINIMIZER_WINDOW; i <= KC_ASSEMBLE_KMER_SAMPLE; i++)
+            if (!cfg.have[i]) die("No such parameter: %s (use_minimizers = 1 needs it; set it in %s)", kc_key_names[i], config);
+        window = (int)cfg.value[KC_MINIMIZER_WINDOW];                                  /* const int minWnd = Config::get(...) */
+        if (window < 1 || window > GAB_KMER_MAX_WINDOW) die("wrong minimizer length (minimizer_window = %d; supported 1..%d)", window, GAB_KMER_MAX_WINDOW);
+    }
     if (kmer < 1 || kmer > GAB_KMER_MAX_K) die("Can't use flat counter for k-mer size > %d (k = %d; supported 1..%d)", GAB_KMER_MAX_K, kmer, GAB_KMER_MAX_K);
     log_debug("Running with k-mer size: %d", kmer);
 
@@ -290,6 +344,12 @@ int main(int argc, char **argv) {
 
     int ngpus = gab_pick_gpus(gpus_flag);
     if (ngpus > GAB_KMER_MAX_PARTS) ngpus = GAB_KMER_MAX_PARTS;
+    if (use_minimizers) {
+        const int rc = build_minimizer_index(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len), ngpus);
+        free(R.seq); free(R.off); free(R.len);
+        if (g_log) fclose(g_log);
+        return rc;
+    }
     log_debug("Counting on %d GPU(s), one key-space partition each", ngpus);
     gab_kmer **hs = (gab_kmer **)calloc((size_t)ngpus, sizeof *hs);
     gab_kmer_result *part_res = (gab_kmer_result *)calloc((size_t)ngpus, sizeof *part_res);

@@ -54,6 +54,8 @@ struct KmerCounters {
     unsigned long long bad_query;          // lowest index of a query >= 4^k (~0 = none)
     uint32_t dump_n;
     uint32_t overflow;                     // a bounded insert gave up: the partition's table is full (the host repeats the call)
+    unsigned long long ix_kmers, ix_entries;       // minimizer index: kept k-mers and their entries
+    unsigned long long ix_minimizers;      // ... and the emitted minimizers of the call (the low word is copied in from the scan)
 };
 GAB_STATIC_ATOMIC64(KmerCounters, bad_read);
 GAB_STATIC_ATOMIC64(KmerCounters, bad_query);
@@ -328,6 +330,346 @@ __global__ __launch_bounds__(kBlock) void kmer_compact(const KmerLine *__restric
     }
 }
 
+// ===================================================================================================================== minimizer index
+// buildIndexMinimizers(1, w) (kmer-cnt/vertex_index.cpp:394-502) on the same packed reads, tiles and table.
+//
+// The sketch of a read (yieldMinimizers, kmer-cnt/kmer.h:206-262) keeps a monotone queue of (position, order key); the order key of a
+// position is kmer_order_key of its canonical k-mer.  All that a step needs of that queue is its front f(p), and the front obeys
+//     f(0) = 0
+//     f(p) = p                                        if key[p] < key[f(p - 1)]            (everything before p is popped)
+//          = the LAST position of (p - w, p] that
+//            holds the minimum key of that window     else if f(p - 1) <= p - w            (expired; then the run of equals is skipped)
+//          = f(p - 1)                                 otherwise,
+// and position q is a minimizer iff f(p) = q for some p.  key[f(p)] is always the minimum of the window (p - w, p], so where that
+// minimum is unique f(p) is its position whatever came before; where it is not, which of the equal positions is the front depends
+// on the history (in a homopolymer the minimizers fall at 0, w, 2w, ... from the start of the run).  A lane that owns positions
+// [p0, p1) therefore finds f(p0 - 1) like this: the window of p0 - 1 reaches the start of the read -> the first of its minima (no
+// front has expired yet); its minimum m is unique -> that position; otherwise it walks back, one k-mer per step, to the first
+// step s0 of the stretch of steps whose window minimum is m -- there the front is the last m of the window, because the step
+// before either brought the first m in or saw a smaller key expire -- and plays the recurrence forward from s0.
+// Nothing is kept per window position: when a front expires the lane re-rolls the w k-mers of the window from the packed words
+// (about once per w steps in random sequence and in homopolymers alike; an adversarial read whose keys rise for a long stretch
+// costs w k-mers per step).  Window state is a handful of scalars: no LDS, no private array.
+// The walk back is serial and NOT bounded: inside a stretch of tied window minima -- a homopolymer, a tandem repeat of period <= w --
+// every lane walks back to the stretch's start and replays forward to its p0, so a stretch of T positions costs its lanes
+// T / 64 walks of up to T steps each: about T^2 / 64 k-mers in all, T of them on the slowest lane.  Measured
+// (profiles/kmer_minimizers.md): about 0.65 us per position of the stretch -- a stretch of 1 kb holds one wave for 0.7 ms, which
+// a call over many reads hides behind its other waves; a 16 kb read of one base takes 11 ms, one low-complexity stretch of 1 Mbp
+// 0.68 s, random sequence of that length 0.5 ms.  Handing the front on from lane to lane through a wave scan would bound it and
+// is not done here.
+//
+// A minimizer found at step p may lie up to w - 1 positions back, in another lane's run or another wave's tile, so the lanes mark
+// minimizers in a bitmap (one 64-bit word per run of GAB_KMER_RUN positions, all tiles of a read back to back) with atomicOr.
+__host__ __device__ __forceinline__ uint64_t kmer_order_key(uint64_t x) {      // kmer-cnt/kmer.h:91-98
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the rolling forward / reverse-complement words of kmer_count as an object: seek(p), then every step() gives the k-mer at p, p + 1, ...
+struct KmerRoller {
+    const uint32_t *words;
+    uint64_t mask, fw, rc;
+    int top, k;
+    int32_t b;                             // next base to take in
+    uint32_t w;
+    __device__ __forceinline__ KmerRoller(const uint32_t *words_, int k_)
+        : words(words_), mask((1ull << (2 * k_)) - 1ull), fw(0), rc(0), top(2 * (k_ - 1)), k(k_), b(0), w(0) {}
+    __device__ __forceinline__ uint64_t take() {
+        const uint64_t c = w & 3u;
+        b++;
+        w >>= 2;
+        if ((b & 15) == 0) w = words[b >> 4];      // (the last base taken belongs to position L - k - 1 and is base L - 2, so b <= L - 1: a word of the read)
+        return c;
+    }
+    __device__ __forceinline__ void seek(int32_t p) {
+        fw = 0; rc = 0; b = p;
+        w = words[b >> 4] >> (2 * (b & 15));
+        for (int j = 0; j < k - 1; j++) {
+            const uint64_t c = take();
+            fw = (fw << 2) | c;
+            rc = (rc >> 2) | ((3ull - c) << top);
+        }
+    }
+    __device__ __forceinline__ void step() {
+        const uint64_t c = take();
+        fw = ((fw << 2) | c) & mask;
+        rc = (rc >> 2) | ((3ull - c) << top);
+    }
+    // from the k-mer at q + 1 to the k-mer at q (the cursor of take() stays where it is)
+    __device__ __forceinline__ void back(int32_t q) {
+        const uint64_t c = (words[q >> 4] >> (2 * (q & 15))) & 3u;
+        fw = (fw >> 2) | (c << top);
+        rc = ((rc << 2) | (3ull - c)) & mask;
+    }
+    __device__ __forceinline__ uint64_t canonical() const { return fw < rc ? fw : rc; }
+    __device__ __forceinline__ bool forward() const { return fw <= rc; }      // palindromes are not flipped (kmer-cnt/kmer.h:54-63)
+};
+
+struct KmerWindowMin { uint64_t m; int32_t first, last; };      // the minimum order key of a window, its first and last position
+// re-rolls positions lo .. hi; fw_lo / rc_lo: the two words of the k-mer at lo
+__device__ __forceinline__ KmerWindowMin kmer_window_min(KmerRoller &S, int32_t lo, int32_t hi, uint64_t *fw_lo = nullptr, uint64_t *rc_lo = nullptr) {
+    KmerWindowMin x = {0, lo, lo};
+    S.seek(lo);
+    for (int32_t q = lo; q <= hi; q++) {
+        S.step();
+        const uint64_t h = kmer_order_key(S.canonical());
+        if (q == lo) {
+            x.m = h;
+            if (fw_lo) { *fw_lo = S.fw; *rc_lo = S.rc; }
+        } else if (h < x.m) { x.m = h; x.first = q; x.last = q; }
+        else if (h == x.m) x.last = q;
+    }
+    return x;
+}
+
+// One wave per tile, one lane per run, as kmer_count.  masks: zeroed; word (first run of the read + q / 64), bit q % 64 <- position q
+// of the read is a minimizer.
+__global__ __launch_bounds__(kBlock) void kmer_sketch(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
+                                                      const KmerTile *__restrict__ tiles, int64_t n_tiles, int k, int w, unsigned long long *masks) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (t >= n_tiles) return;
+    const KmerTile tile = tiles[t];
+    const int32_t npos = len[tile.read] - k;
+    const int32_t p0 = tile.start + lane * kRun;
+    const int32_t p1 = min(p0 + kRun, npos);
+    if (p0 >= p1) return;
+    unsigned long long *rmask = masks + (t - tile.start / kTile) * 64;      // the read's first run (its tiles are consecutive)
+    if (w == 1) {                                                          // every position, no queue (kmer-cnt/kmer.h:222-229)
+        rmask[p0 >> 6] = p1 - p0 == 64 ? ~0ull : (1ull << (p1 - p0)) - 1ull;
+        return;
+    }
+    const uint32_t *words = packed + woff[tile.read];
+    KmerRoller R(words, k), S(words, k);
+    int32_t f = 0, last = -1;              // p0 = 0: step 0 makes position 0 the front (any key is <= ~0) and emits it
+    uint64_t hf = ~0ull;
+    auto advance = [&](int32_t p) {        // R.step() gives position p
+        R.step();
+        const uint64_t h = kmer_order_key(R.canonical());
+        if (h < hf) { f = p; hf = h; }
+        else if (f <= p - w) {
+            const KmerWindowMin x = kmer_window_min(S, p - w + 1, p);
+            f = x.last; hf = x.m;
+        }
+    };
+    if (p0 > 0) {
+        const int32_t s = p0 - 1, lo = max(0, s - w + 1);
+        uint64_t fw_lo, rc_lo;
+        const KmerWindowMin x = kmer_window_min(S, lo, s, &fw_lo, &rc_lo);
+        hf = x.m;
+        int32_t from = p0;                 // the recurrence is played forward from here
+        if (lo == 0) f = x.first;
+        else if (x.first == x.last) f = x.last;
+        else {
+            int32_t t2 = s, first = x.first;       // the window of step t2 is [t2 - w + 1, t2], its minimum x.m, the first of them at `first`
+            bool at_start = false;
+            S.fw = fw_lo; S.rc = rc_lo;
+            for (;;) {
+                const int32_t q = t2 - w;          // >= 0: the position the window of step t2 - 1 has and this one has not
+                S.back(q);
+                const uint64_t hq = kmer_order_key(S.canonical());
+                if (hq < x.m) break;
+                if (hq == x.m) first = q;
+                else if (first == t2) break;       // (step t2 - 1 sees no m at all)
+                t2--;
+                if (t2 - w + 1 == 0) { at_start = true; break; }
+            }
+            f = at_start ? first : kmer_window_min(S, t2 - w + 1, t2).last;
+            from = t2 + 1;
+        }
+        R.seek(from);
+        for (int32_t p = from; p < p0; p++) advance(p);
+        last = f;
+    } else R.seek(0);
+    unsigned long long own = 0;
+    for (int32_t p = p0; p < p1; p++) {
+        advance(p);
+        if (f != last) {
+            last = f;
+            if (f >= p0) own |= 1ull << (f - p0);
+            else atomicOr(&rmask[f >> 6], 1ull << (f & 63));
+        }
+    }
+    if (own) atomicOr(&rmask[p0 >> 6], own);
+}
+
+struct KmerPopc {
+    __host__ __device__ __forceinline__ uint32_t operator()(unsigned long long m) const {
+#ifdef __HIP_DEVICE_COMPILE__
+        return (uint32_t)__popcll(m);
+#else
+        return (uint32_t)__builtin_popcountll(m);
+#endif
+    }
+};
+
+// the slot of a key that is in the table (nullptr if it is not: the walk ends at an empty slot, the table is at most half full)
+__device__ __forceinline__ KmerLine *kmer_find(KmerLine *table, uint64_t nlines, uint64_t key, int *slot) {
+    const unsigned long long stored = key + 1;
+    uint64_t line = kmer_line_of(key, nlines);
+    for (uint64_t visited = 0; visited < nlines; visited++) {
+        KmerLine *L = table + line;
+        int match = -1;
+        bool end = false;
+#pragma unroll
+        for (int s = kSlots - 1; s >= 0; s--) {
+            const unsigned long long v = L->key[s];
+            if (v == stored) match = s;
+            if (v == 0) end = true;
+        }
+        if (match >= 0) { *slot = match; return L; }
+        if (end) return nullptr;
+        line = line + 1 == nlines ? 0 : line + 1;
+    }
+    return nullptr;
+}
+
+// The second walk over the reads: a lane re-rolls its run from its first marked position to its last and does one of three things
+// with every minimizer.  offs: exclusive scan of the popcounts of masks.
+enum { kWalkSketch = 0, kWalkCount = 1, kWalkFill = 2 };
+//   kWalkSketch  pos[offs + i] = position in the read
+//   kWalkCount   canonical k-mer into the table (kmer_insert): cnt = capacity of the key
+//   kWalkFill    keys with cnt <= thr: gpos[pad++] = global position (pad was set to the start of the key's list)
+template <int kMode>
+__global__ __launch_bounds__(kBlock) void kmer_mini_walk(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
+                                                         const KmerTile *__restrict__ tiles, int64_t n_tiles, int k,
+                                                         const unsigned long long *__restrict__ masks, const uint32_t *__restrict__ offs,
+                                                         int32_t *__restrict__ pos, KmerLine *table, uint64_t nlines, KmerCounters *ct,
+                                                         const int64_t *__restrict__ rbase, uint32_t thr, int64_t *__restrict__ gpos) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (t >= n_tiles) return;
+    const KmerTile tile = tiles[t];
+    const int32_t L = len[tile.read];
+    const int32_t p0 = tile.start + lane * kRun;
+    if (p0 >= L - k) return;
+    const int64_t run = (t - tile.start / kTile) * 64 + (p0 >> 6);
+    unsigned long long m = masks[run];
+    if (!m) return;
+    const int lead = __builtin_ctzll(m);
+    m >>= lead;
+    KmerRoller R(packed + woff[tile.read], k);
+    R.seek(p0 + lead);
+    uint32_t o = offs[run], probes = 0;
+    const int64_t base = kMode == kWalkFill ? rbase[tile.read] : 0;
+    for (int32_t p = p0 + lead; m; p++, m >>= 1) {
+        R.step();
+        if (!(m & 1)) continue;
+        if constexpr (kMode == kWalkSketch) pos[o++] = p;
+        else if constexpr (kMode == kWalkCount) {
+            const uint64_t key = R.canonical();
+            kmer_insert<false>(table, nlines, kmer_line_of(key, nlines), key, 1u, probes, 0, ct);
+        } else {
+            int slot = 0;
+            KmerLine *line = kmer_find(table, nlines, R.canonical(), &slot);
+            if (line && line->cnt[slot] <= thr) {
+                const uint32_t at = atomicAdd(&line->pad[slot], 1u);
+                gpos[at] = R.forward() ? base + p : base + L + (L - p - k);
+            }
+        }
+    }
+}
+
+// read_start[r] = minimizers before read r (first_run[r] = the runs before it; first_run[n_reads] = all runs)
+__global__ __launch_bounds__(kBlock) void kmer_read_starts(const uint32_t *__restrict__ offs, const int64_t *__restrict__ first_run, int64_t n,
+                                                           int64_t *__restrict__ read_start) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) read_start[i] = (int64_t)offs[first_run[i]];
+}
+
+// every taken slot as (key, slot index), unordered.  A thread takes a whole line (its taken slots are a prefix), the block adds its
+// lines up in LDS and draws ONE range from the counter per round: the table has two slots per k-mer POSITION of the call and few
+// of them are taken, so a draw per wave would be millions of atomics on one address.
+__global__ __launch_bounds__(kBlock) void kmer_index_compact(const KmerLine *__restrict__ table, uint64_t nlines, uint64_t *__restrict__ keys,
+                                                             uint64_t *__restrict__ slots, uint32_t capacity, KmerCounters *ct) {
+    __shared__ uint32_t wave_sum[kBlock / 64], wave_base[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t rounds = (nlines + stride - 1) / stride;
+    for (uint64_t r = 0; r < rounds; r++) {
+        const uint64_t i = r * stride + (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+        unsigned long long key[kSlots] = {0, 0, 0, 0, 0, 0, 0, 0};      // (a thread past the last line takes part in the sums with nothing)
+        uint32_t c = 0;
+        if (i < nlines) {
+            const kmer_ull2 *src = reinterpret_cast<const kmer_ull2 *>(table[i].key);
+#pragma unroll
+            for (int j = 0; j < kSlots / 2; j++) { const kmer_ull2 v = src[j]; key[2 * j] = v.x; key[2 * j + 1] = v.y; }
+#pragma unroll
+            for (int j = 0; j < kSlots; j++) c += key[j] != 0;
+        }
+        uint32_t incl = c;                         // inclusive sum over the lanes of the wave
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t total = 0;
+            for (int w = 0; w < kBlock / 64; w++) total += wave_sum[w];
+            uint32_t at = total ? atomicAdd(&ct->dump_n, total) : 0;
+            for (int w = 0; w < kBlock / 64; w++) { wave_base[w] = at; at += wave_sum[w]; }
+        }
+        __syncthreads();
+        uint32_t at = wave_base[wave] + incl - c;
+#pragma unroll
+        for (int j = 0; j < kSlots; j++)
+            if (key[j] != 0 && at < capacity) { keys[at] = key[j] - 1; slots[at] = i * kSlots + j; at++; }
+        __syncthreads();                           // (the next round writes wave_sum again)
+    }
+}
+
+// keys in ascending order: weight[i] = (1 << 32 | capacity) of a kept key, 0 of a removed one; weight[n] = 0 (the scan's total lands there)
+__global__ __launch_bounds__(kBlock) void kmer_index_weigh(const KmerLine *__restrict__ table, const uint64_t *__restrict__ slots, int64_t n, uint32_t thr,
+                                                           uint64_t *__restrict__ weight) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i > n) return;
+    uint64_t v = 0;
+    if (i < n) {
+        const uint32_t c = table[slots[i] / kSlots].cnt[slots[i] % kSlots];
+        if (c <= thr) v = (1ull << 32) | c;
+    }
+    weight[i] = v;
+}
+
+// scan = exclusive scan of weight: high word = kept keys before i, low word = entries before i.  Writes the kept keys and the start
+// of their lists in order, the start of every key's list (kept or not: a removed key's list is empty) for the segmented sort, and
+// the start of the list into the key's own slot, where the fill pass counts it up.
+__global__ __launch_bounds__(kBlock) void kmer_index_assign(KmerLine *table, const uint64_t *__restrict__ keys, const uint64_t *__restrict__ slots,
+                                                            const uint64_t *__restrict__ weight, const uint64_t *__restrict__ scan, int64_t n,
+                                                            uint64_t *__restrict__ kmers, int64_t *__restrict__ start, uint32_t *__restrict__ seg,
+                                                            KmerCounters *ct) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i > n) return;
+    const uint64_t rank = scan[i] >> 32, off = scan[i] & 0xFFFFFFFFull;
+    seg[i] = (uint32_t)off;
+    if (i == n) { start[rank] = (int64_t)off; ct->ix_kmers = rank; ct->ix_entries = off; return; }
+    if (weight[i]) {
+        kmers[rank] = keys[i];
+        start[rank] = (int64_t)off;
+        table[slots[i] / kSlots].pad[slots[i] % kSlots] = (uint32_t)off;
+    }
+}
+
+// first[i] = start of the list of the canonical form of kmers[i] in the dump's order, count[i] its length; an absent or removed
+// k-mer: -1 and 0; repetitive[i] = 1 for a removed one.  After the fill pass pad = END of the key's list.
+__global__ __launch_bounds__(kBlock) void kmer_index_lookup(KmerLine *table, uint64_t nlines, int k, uint32_t thr, const uint64_t *__restrict__ kmers,
+                                                            int64_t n, int64_t *__restrict__ first, int32_t *__restrict__ count,
+                                                            uint8_t *__restrict__ repetitive, KmerCounters *ct) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t x = kmers[i];
+    first[i] = -1; count[i] = 0; repetitive[i] = 0;
+    if (x >> (2 * k)) { atomicMin(&ct->bad_query, (unsigned long long)i); return; }
+    const uint64_t r = kmer_revcomp(x, k);
+    int slot = 0;
+    const KmerLine *L = kmer_find(table, nlines, x < r ? x : r, &slot);
+    if (!L) return;
+    const uint32_t c = L->cnt[slot];
+    if (c > thr) { repetitive[i] = 1; return; }
+    first[i] = (int64_t)(L->pad[slot] - c);
+    count[i] = (int32_t)c;
+}
+
 }  // namespace
 
 // =============================================================================== host side
@@ -352,6 +694,14 @@ struct gab_kmer {
     int part = 0, nparts = 1;          // what the last count ran as (gab_kmer_last_part)
     bool retried = false;              // ... and whether its first table filled up and the call was repeated
     gab_tuning tun = gab_tuning_loaded();      // experiment knobs, read when the handle is made
+    // minimizer index (gab_kmer_index_minimizers): it takes the table over, so `counted` and `indexed` are never both set
+    gab_devbuf mini;        // sketch: bitmap of the minimizers | its scan | per-read bases
+    gab_devbuf idx;         // the index of the last build: k-mers | starts | global positions
+    hipEvent_t ev_ix[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // start | sketched | counted | resumed | filled | sorted
+    bool indexed = false;
+    gab_kmer_index_result ix = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t ix_thr = 0;               // min(repetitive_frequency, 2^32 - 1): what the kernels compare the 32-bit capacities with
+    float ix_ms[4] = {0, 0, 0, 0};     // sketch | count | fill | sort
 };
 
 static uint64_t table_lines(int64_t positions, int k) {
@@ -391,6 +741,8 @@ extern "C" int gab_kmer_create(int device, gab_kmer **out) {
     h->device = device;
     for (int i = 0; i < 5; i++)
         if (hipEventCreate(&h->ev[i]) != hipSuccess) { gab_set_error("hipEventCreate failed"); gab_kmer_destroy(h); return GAB_EDEVICE; }
+    for (int i = 0; i < 6; i++)
+        if (hipEventCreate(&h->ev_ix[i]) != hipSuccess) { gab_set_error("hipEventCreate failed"); gab_kmer_destroy(h); return GAB_EDEVICE; }
     if (hipHostMalloc((void **)&h->h_ct, sizeof(KmerCounters)) != hipSuccess) {
         h->h_ct = nullptr; gab_set_error("hipHostMalloc failed"); gab_kmer_destroy(h); return GAB_ENOMEM;
     }
@@ -404,8 +756,10 @@ extern "C" int gab_kmer_create(int device, gab_kmer **out) {
 extern "C" void gab_kmer_destroy(gab_kmer *h) {
     if (!h) return;
     gab_device_guard g(h->device);
-    h->io.release(); h->packed.release(); h->plan.release(); h->table.release(); h->ct.release(); h->aux.release(); h->hs.release();
+    h->io.release(); h->packed.release(); h->plan.release(); h->table.release(); h->ct.release(); h->aux.release(); h->mini.release(); h->idx.release();
+    h->hs.release();
     for (int i = 0; i < 5; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
+    for (int i = 0; i < 6; i++) if (h->ev_ix[i]) (void)hipEventDestroy(h->ev_ix[i]);
     if (h->h_ct) (void)hipHostFree(h->h_ct);
     delete h;
 }
@@ -455,7 +809,7 @@ extern "C" int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max
 static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
                            const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res,
                            hipStream_t s) {
-    h->counted = false;
+    h->counted = false; h->indexed = false;
     gab_tuning_refresh(&h->tun);
     // plan on the host: word offset of every read, tiles of the kept ones
     std::vector<int64_t> woff((size_t)n_reads + 1);
@@ -578,6 +932,42 @@ extern "C" int gab_kmer_count_part_device(gab_kmer *h, const char *seq, int64_t 
     return kmer_count_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, min_len_exclusive, part, nparts, res, s);
 }
 
+// The host-pointer entry points: the window of the slab that the reads span, their offsets relative to it and their lengths go
+// into the handle's staging buffer.  st->rel: those offsets on the host.
+struct kmer_staged { char *d_seq; int64_t *d_off; int32_t *d_len; size_t span; std::vector<int64_t> rel; };
+static int kmer_stage_host(gab_kmer *h, const char *fn, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, hipStream_t s,
+                           kmer_staged *st) {
+    int rc;
+    int64_t lo = INT64_MAX, hi = 0;                                // the window of the slab the reads span
+    for (int64_t r = 0; r < n_reads; r++) {
+        GAB_CHECK(len[r] >= 0 && off[r] >= 0, "%s: read %lld has a negative offset or length", fn, (long long)r);
+        if (len[r] == 0) continue;
+        lo = std::min(lo, off[r]); hi = std::max(hi, off[r] + len[r]);
+    }
+    if (hi == 0) lo = 0;
+    GAB_CHECK(seq || hi == 0, "%s: NULL sequence slab", fn);
+    const size_t span = (size_t)(hi - lo);
+    const size_t off_at = align256(span + 64), len_at = off_at + align256((size_t)n_reads * 8);
+    if ((rc = h->io.reserve(len_at + align256((size_t)n_reads * 4)))) return rc;
+    st->d_seq = h->io.as<char>();
+    st->d_off = reinterpret_cast<int64_t *>(st->d_seq + off_at);
+    st->d_len = reinterpret_cast<int32_t *>(st->d_seq + len_at);
+    st->span = span;
+    std::vector<int64_t> &rel = st->rel;
+    rel.assign((size_t)n_reads, 0);
+    for (int64_t r = 0; r < n_reads; r++) rel[(size_t)r] = len[r] ? off[r] - lo : 0;
+    {
+        std::lock_guard<std::mutex> lk(gab_h2d_mutex(h->device));
+        if (span) GAB_HIP(hipMemcpyAsync(st->d_seq, seq + lo, span, hipMemcpyHostToDevice, s));
+        if (n_reads) {
+            GAB_HIP(hipMemcpyAsync(st->d_off, rel.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, s));
+            GAB_HIP(hipMemcpyAsync(st->d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
+        }
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    return GAB_OK;
+}
+
 extern "C" int gab_kmer_count(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
                               gab_kmer_result *res) {
     return gab_kmer_count_part(h, seq, off, len, n_reads, k, min_len_exclusive, 0, 1, res);
@@ -590,32 +980,9 @@ extern "C" int gab_kmer_count_part(gab_kmer *h, const char *seq, const int64_t *
     gab_device_guard g(h->device);
     hipStream_t s;
     if ((rc = h->hs.get(&s))) return rc;
-    int64_t lo = INT64_MAX, hi = 0;                                // the window of the slab the reads span
-    for (int64_t r = 0; r < n_reads; r++) {
-        GAB_CHECK(len[r] >= 0 && off[r] >= 0, "gab_kmer_count: read %lld has a negative offset or length", (long long)r);
-        if (len[r] == 0) continue;
-        lo = std::min(lo, off[r]); hi = std::max(hi, off[r] + len[r]);
-    }
-    if (hi == 0) lo = 0;
-    GAB_CHECK(seq || hi == 0, "gab_kmer_count: NULL sequence slab");
-    const size_t span = (size_t)(hi - lo);
-    const size_t off_at = align256(span + 64), len_at = off_at + align256((size_t)n_reads * 8);
-    if ((rc = h->io.reserve(len_at + align256((size_t)n_reads * 4)))) return rc;
-    char *d_seq = h->io.as<char>();
-    int64_t *d_off = reinterpret_cast<int64_t *>(d_seq + off_at);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d_seq + len_at);
-    std::vector<int64_t> rel((size_t)n_reads);
-    for (int64_t r = 0; r < n_reads; r++) rel[(size_t)r] = len[r] ? off[r] - lo : 0;
-    {
-        std::lock_guard<std::mutex> lk(gab_h2d_mutex(h->device));
-        if (span) GAB_HIP(hipMemcpyAsync(d_seq, seq + lo, span, hipMemcpyHostToDevice, s));
-        if (n_reads) {
-            GAB_HIP(hipMemcpyAsync(d_off, rel.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, s));
-            GAB_HIP(hipMemcpyAsync(d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
-        }
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    return kmer_count_impl(h, d_seq, (int64_t)span, d_off, d_len, rel.data(), len, n_reads, k, min_len_exclusive, part, nparts, res, s);
+    kmer_staged st;
+    if ((rc = kmer_stage_host(h, "gab_kmer_count", seq, off, len, n_reads, s, &st))) return rc;
+    return kmer_count_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, min_len_exclusive, part, nparts, res, s);
 }
 
 #define KMER_NEED_COUNT(fn) GAB_CHECK(h && h->counted, fn ": no finished gab_kmer_count on this handle")
@@ -715,5 +1082,377 @@ extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *
     if (nparts) *nparts = h->nparts;
     if (table_slots) *table_slots = (int64_t)(h->nlines * kSlots);
     if (retried) *retried = h->retried ? 1 : 0;
+    return GAB_OK;
+}
+
+// =============================================================================== minimizer index, host side
+// Stages of gab_kmer_index_minimizers (all on the caller's stream):
+//   kmer_pack, kmer_sketch, a scan of the bitmap's popcounts                                              "sketch"
+//   table clear, kmer_mini_walk<kWalkCount> (capacity of every key), kmer_reduce (distinct)               "count"
+//   -- the one synchronisation in the middle: the host needs the two integers for repetitive_frequency --
+//   every key with its slot, sorted by key; (kept, capacity) scanned in that order: the rank of a kept key and the start of its
+//   list; both written out and the start put into the key's slot; kmer_mini_walk<kWalkFill> counts it up                  "fill"
+//   one segmented sort over the lists (a removed key has an empty one)                                     "sort"
+// and one synchronisation at the end for the two sizes.  The k-mers, the starts and the sorted lists stay in h->idx, the table
+// with the END of every list in its slots stays for gab_kmer_index_lookup.
+namespace {
+
+struct KmerMiniPlan {
+    std::vector<int64_t> woff, rbase, first_run;   // word offset | 2 S_i of a kept read | runs before the read (n_reads + 1)
+    std::vector<KmerTile> tiles;
+    int64_t words = 0, positions = 0, kept = 0, total_len = 0;
+};
+struct KmerMiniDev {       // where the stage put things
+    int64_t *woff; KmerTile *tiles; uint32_t *packed; unsigned long long *masks; uint32_t *offs; int64_t *rbase, *first_run;
+    int64_t n_tiles, n_runs;
+};
+
+int kmer_mini_check(const char *fn, gab_kmer *h, const void *off, const void *len, int64_t n_reads, int k, int window) {
+    GAB_CHECK(h && n_reads >= 0 && (n_reads == 0 || (off && len)), "%s: NULL or negative argument", fn);
+    GAB_CHECK(k >= 1 && k <= GAB_KMER_MAX_K, "%s: k = %d, supported 1..%d", fn, k, GAB_KMER_MAX_K);
+    GAB_CHECK(window >= 1 && window <= GAB_KMER_MAX_WINDOW, "%s: window = %d, supported 1..%d (yieldMinimizers takes any window >= 1, kmer-cnt/kmer.h:208)", fn,
+              window, GAB_KMER_MAX_WINDOW);
+    return GAB_OK;
+}
+
+int kmer_mini_plan(const char *fn, const int64_t *off, const int32_t *len, int64_t n_reads, int64_t seq_bytes, int k, int32_t min_len_exclusive,
+                   KmerMiniPlan *P) {
+    GAB_CHECK(n_reads < (1ll << 31), "%s: %lld reads in one call (limit 2^31)", fn, (long long)n_reads);
+    P->woff.resize((size_t)n_reads + 1); P->rbase.assign((size_t)n_reads + 1, 0); P->first_run.resize((size_t)n_reads + 1);
+    for (int64_t r = 0; r < n_reads; r++) {
+        GAB_CHECK(len[r] >= 0 && off[r] >= 0 && off[r] + len[r] <= seq_bytes, "%s: read %lld (offset %lld, length %d) lies outside the %lld sequence bytes", fn,
+                  (long long)r, (long long)off[r], (int)len[r], (long long)seq_bytes);
+        P->woff[(size_t)r] = P->words;
+        P->words += ((int64_t)len[r] + 15) / 16;
+        P->first_run[(size_t)r] = (int64_t)P->tiles.size() * 64;
+        if (len[r] > min_len_exclusive) {
+            P->kept++;
+            P->rbase[(size_t)r] = 2 * P->total_len;
+            P->total_len += len[r];
+            const int32_t npos = len[r] - k;
+            for (int32_t p = 0; p < npos; p += kTile) P->tiles.push_back(KmerTile{(int32_t)r, p});
+            if (npos > 0) P->positions += npos;
+        }
+    }
+    P->woff[(size_t)n_reads] = P->words;
+    P->first_run[(size_t)n_reads] = (int64_t)P->tiles.size() * 64;
+    GAB_CHECK(P->positions < (1ll << 32), "%s: %lld k-mer positions in one call (limit 2^32)", fn, (long long)P->positions);
+    GAB_CHECK(2 * P->total_len < (1ll << 40), "%s: %lld bases in the kept reads (global positions have 40 bits, kmer-cnt/sequence_container.h:266)", fn,
+              (long long)P->total_len);
+    return GAB_OK;
+}
+
+// plan to the device, pack, sketch, scan; leaves the zeroed counters in h->ct
+int kmer_mini_stage(gab_kmer *h, const char *d_seq, const int64_t *d_off, const int32_t *d_len, const KmerMiniPlan &P, int64_t n_reads, int k, int window,
+                    hipStream_t s, KmerMiniDev *D) {
+    int rc;
+    const int64_t n_tiles = (int64_t)P.tiles.size(), n_runs = n_tiles * 64;
+    const size_t tiles_at = align256(((size_t)n_reads + 1) * 8);
+    if ((rc = h->packed.reserve((size_t)P.words * 4 + 4))) return rc;
+    if ((rc = h->plan.reserve(tiles_at + (size_t)n_tiles * sizeof(KmerTile) + 8))) return rc;
+    size_t tmp_bytes = 0;
+    GAB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)nullptr, KmerPopc()), (uint32_t *)nullptr, 0u,
+                                    (size_t)n_runs + 1, rocprim::plus<uint32_t>(), s));
+    const size_t offs_at = align256(((size_t)n_runs + 1) * 8), rbase_at = offs_at + align256(((size_t)n_runs + 1) * 4);
+    const size_t first_at = rbase_at + align256(((size_t)n_reads + 1) * 8), tmp_at = first_at + align256(((size_t)n_reads + 1) * 8);
+    if ((rc = h->mini.reserve(tmp_at + tmp_bytes + 256))) return rc;
+    char *mb = h->mini.as<char>();
+    D->woff = h->plan.as<int64_t>();
+    D->tiles = reinterpret_cast<KmerTile *>(h->plan.as<char>() + tiles_at);
+    D->packed = h->packed.as<uint32_t>();
+    D->masks = reinterpret_cast<unsigned long long *>(mb);
+    D->offs = reinterpret_cast<uint32_t *>(mb + offs_at);
+    D->rbase = reinterpret_cast<int64_t *>(mb + rbase_at);
+    D->first_run = reinterpret_cast<int64_t *>(mb + first_at);
+    D->n_tiles = n_tiles; D->n_runs = n_runs;
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    KmerCounters zero = {};
+    zero.bad_read = ~0ull; zero.bad_query = ~0ull;
+    *h->h_ct = zero;
+    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
+    GAB_HIP(hipMemcpyAsync(D->woff, P.woff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+    GAB_HIP(hipMemcpyAsync(D->rbase, P.rbase.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+    GAB_HIP(hipMemcpyAsync(D->first_run, P.first_run.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_tiles) GAB_HIP(hipMemcpyAsync(D->tiles, P.tiles.data(), (size_t)n_tiles * sizeof(KmerTile), hipMemcpyHostToDevice, s));
+    if (P.words)
+        hipLaunchKernelGGL(kmer_pack, dim3((unsigned)gab_ceil_div(P.words, kBlock)), dim3(kBlock), 0, s, d_seq, d_off, d_len, D->woff, n_reads, P.words, D->packed,
+                           d_ct);
+    GAB_HIP(hipMemsetAsync(D->masks, 0, ((size_t)n_runs + 1) * 8, s));
+    if (n_tiles)
+        hipLaunchKernelGGL(kmer_sketch, dim3((unsigned)gab_ceil_div(n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D->packed, D->woff, d_len, D->tiles, n_tiles, k, window,
+                           D->masks);
+    GAB_HIP(rocprim::exclusive_scan(mb + tmp_at, tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)D->masks, KmerPopc()), D->offs, 0u,
+                                    (size_t)n_runs + 1, rocprim::plus<uint32_t>(), s));
+    return GAB_OK;
+}
+
+// the counters and the number of minimizers (the scan's last element) to the host; synchronises
+int kmer_mini_fetch(gab_kmer *h, const char *fn, const KmerMiniDev &D, hipStream_t s) {
+    GAB_HIP(hipMemcpyAsync(h->h_ct, h->ct.as<KmerCounters>(), sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(&h->h_ct->ix_minimizers, D.offs + D.n_runs, 4, hipMemcpyDeviceToHost, s));     // (little-endian: the low word)
+    GAB_HIP(hipStreamSynchronize(s));
+    GAB_HIP(hipGetLastError());
+    GAB_CHECK(h->h_ct->bad_read == ~0ull, "%s: read %lld holds a byte outside ACGTacgt (a driver replaces such bytes before the call)", fn,
+              (long long)h->h_ct->bad_read);
+    return GAB_OK;
+}
+
+template <int kMode>
+void kmer_mini_launch_walk(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int32_t *pos, uint32_t thr, int64_t *gpos, hipStream_t s) {
+    if (!D.n_tiles) return;
+    hipLaunchKernelGGL(kmer_mini_walk<kMode>, dim3((unsigned)gab_ceil_div(D.n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D.packed, D.woff, d_len, D.tiles, D.n_tiles, k,
+                       D.masks, D.offs, pos, h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos);
+}
+
+// d_*: device; off / len: the same two arrays on the host.  out_on_device: read_start / pos are device pointers
+int kmer_sketch_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
+                     int64_t n_reads, int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout,
+                     bool out_on_device, hipStream_t s) {
+    KmerMiniPlan P;
+    KmerMiniDev D;
+    int rc;
+    if ((rc = kmer_mini_plan("gab_kmer_sketch", off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
+    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    if ((rc = kmer_mini_fetch(h, "gab_kmer_sketch", D, s))) return rc;
+    const int64_t m = (int64_t)h->h_ct->ix_minimizers;
+    *nout = m;
+    if (capacity < m) { gab_set_error("gab_kmer_sketch: %lld minimizers, room for %lld", (long long)m, (long long)capacity); return GAB_ERANGE; }
+    GAB_CHECK(read_start && (pos || m == 0), "gab_kmer_sketch: NULL output");
+    int64_t *d_start = read_start;
+    int32_t *d_pos = pos;
+    const size_t pos_at = align256(((size_t)n_reads + 1) * 8);
+    if (!out_on_device) {
+        if ((rc = h->aux.reserve(pos_at + (size_t)m * 4 + 4))) return rc;
+        d_start = h->aux.as<int64_t>();
+        d_pos = reinterpret_cast<int32_t *>(h->aux.as<char>() + pos_at);
+    }
+    hipLaunchKernelGGL(kmer_read_starts, dim3((unsigned)gab_ceil_div(n_reads + 1, kBlock)), dim3(kBlock), 0, s, D.offs, D.first_run, n_reads + 1, d_start);
+    kmer_mini_launch_walk<kWalkSketch>(h, D, d_len, k, d_pos, 0u, nullptr, s);
+    if (!out_on_device) {
+        GAB_HIP(hipMemcpyAsync(read_start, d_start, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (m) GAB_HIP(hipMemcpyAsync(pos, d_pos, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    }
+    GAB_HIP(hipStreamSynchronize(s));
+    GAB_HIP(hipGetLastError());
+    return GAB_OK;
+}
+
+int kmer_index_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
+                    int64_t n_reads, int k, int window, int32_t min_len_exclusive, float rate, gab_kmer_index_result *res, hipStream_t s) {
+    const char *fn = "gab_kmer_index_minimizers";
+    h->counted = false; h->indexed = false;
+    KmerMiniPlan P;
+    KmerMiniDev D;
+    int rc;
+    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
+    // a minimizer per position at most, so the table of a count over the same reads is never more than half full
+    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
+    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    KmerLine *table = h->table.as<KmerLine>();
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    h->nlines = nlines; h->k = k; h->part = 0; h->nparts = 1;
+
+    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
+    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
+    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+    kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s);
+    hipLaunchKernelGGL(kmer_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+    GAB_HIP(hipEventRecord(h->ev_ix[2], s));
+    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
+
+    // filterFrequentKmers (kmer-cnt/vertex_index.cpp:190-191) with its float operations
+    const uint64_t total = h->h_ct->ix_minimizers, unique = h->h_ct->distinct;
+    const float mean = (float)total / (float)(unique + 1);
+    const float cut = rate * mean;
+    const uint64_t rep = cut >= 18446744073709551615.0f ? ~0ull : (uint64_t)cut;
+    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
+    const int64_t n = (int64_t)unique, m = (int64_t)total;
+    gab_kmer_index_result R = {P.kept, P.total_len, m, n, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
+
+    GAB_HIP(hipEventRecord(h->ev_ix[3], s));
+    if (n) {
+        size_t sort_bytes = 0, scan_bytes = 0, seg_bytes = 0;
+        GAB_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, 0u,
+                                          (unsigned)(2 * k), s));
+        GAB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
+        GAB_HIP(rocprim::segmented_radix_sort_keys(nullptr, seg_bytes, (int64_t *)nullptr, (int64_t *)nullptr, (unsigned)m, (unsigned)n, (uint32_t *)nullptr,
+                                                   (uint32_t *)nullptr, 0u, 40u, s));
+        const size_t nb = align256(((size_t)n + 1) * 8), mb = align256((size_t)m * 8);
+        const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, seg_bytes));
+        if ((rc = h->aux.reserve(6 * nb + align256(((size_t)n + 1) * 4) + mb + tmp_bytes + 256))) return rc;
+        if ((rc = h->idx.reserve(2 * nb + mb + 256))) return rc;
+        char *ab = h->aux.as<char>(), *ib = h->idx.as<char>();
+        uint64_t *k_in = reinterpret_cast<uint64_t *>(ab), *k_out = reinterpret_cast<uint64_t *>(ab + nb);
+        uint64_t *s_in = reinterpret_cast<uint64_t *>(ab + 2 * nb), *s_out = reinterpret_cast<uint64_t *>(ab + 3 * nb);
+        uint64_t *weight = reinterpret_cast<uint64_t *>(ab + 4 * nb), *scan = reinterpret_cast<uint64_t *>(ab + 5 * nb);
+        uint32_t *seg = reinterpret_cast<uint32_t *>(ab + 6 * nb);
+        int64_t *g_in = reinterpret_cast<int64_t *>(ab + 6 * nb + align256(((size_t)n + 1) * 4));
+        void *tmp = ab + 6 * nb + align256(((size_t)n + 1) * 4) + mb;
+        uint64_t *kmers = reinterpret_cast<uint64_t *>(ib);
+        int64_t *start = reinterpret_cast<int64_t *>(ib + nb), *g_out = reinterpret_cast<int64_t *>(ib + 2 * nb);
+        const dim3 per_key((unsigned)gab_ceil_div(n + 1, kBlock));
+        hipLaunchKernelGGL(kmer_index_compact, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines, k_in, s_in, (uint32_t)n, d_ct);
+        GAB_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, k_in, k_out, s_in, s_out, (size_t)n, 0u, (unsigned)(2 * k), s));
+        hipLaunchKernelGGL(kmer_index_weigh, per_key, dim3(kBlock), 0, s, table, s_out, n, thr, weight);
+        GAB_HIP(rocprim::exclusive_scan(tmp, scan_bytes, weight, scan, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
+        hipLaunchKernelGGL(kmer_index_assign, per_key, dim3(kBlock), 0, s, table, k_out, s_out, weight, scan, n, kmers, start, seg, d_ct);
+        kmer_mini_launch_walk<kWalkFill>(h, D, d_len, k, nullptr, thr, g_in, s);
+        GAB_HIP(hipEventRecord(h->ev_ix[4], s));
+        GAB_HIP(rocprim::segmented_radix_sort_keys(tmp, seg_bytes, g_in, g_out, (unsigned)m, (unsigned)n, seg, seg + 1, 0u, 40u, s));
+        GAB_HIP(hipEventRecord(h->ev_ix[5], s));
+        GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+        GAB_HIP(hipGetLastError());
+        R.selected_kmers = (int64_t)h->h_ct->ix_kmers; R.index_entries = (int64_t)h->h_ct->ix_entries;
+        R.filtered_kmers = n - R.selected_kmers; R.filtered_entries = m - R.index_entries;
+    } else {
+        GAB_HIP(hipEventRecord(h->ev_ix[4], s));
+        GAB_HIP(hipEventRecord(h->ev_ix[5], s));
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
+    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);
+    (void)hipEventElapsedTime(&h->ix_ms[2], h->ev_ix[3], h->ev_ix[4]);
+    (void)hipEventElapsedTime(&h->ix_ms[3], h->ev_ix[4], h->ev_ix[5]);
+    h->ix = R; h->ix_thr = thr; h->indexed = true;
+    if (res) *res = R;
+    return GAB_OK;
+}
+
+int kmer_fetch_off_len(const int64_t *off, const int32_t *len, int64_t n_reads, std::vector<int64_t> *h_off, std::vector<int32_t> *h_len, hipStream_t s) {
+    h_off->resize((size_t)n_reads); h_len->resize((size_t)n_reads);
+    if (n_reads) {
+        GAB_HIP(hipMemcpyAsync(h_off->data(), off, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipMemcpyAsync(h_len->data(), len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    return GAB_OK;
+}
+
+}  // namespace
+
+extern "C" int gab_kmer_sketch(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                               int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout) {
+    int rc = kmer_mini_check("gab_kmer_sketch", h, off, len, n_reads, k, window);
+    if (rc) return rc;
+    GAB_CHECK(nout && capacity >= 0, "gab_kmer_sketch: NULL or negative argument");
+    gab_device_guard g(h->device);
+    hipStream_t s;
+    if ((rc = h->hs.get(&s))) return rc;
+    kmer_staged st;
+    if ((rc = kmer_stage_host(h, "gab_kmer_sketch", seq, off, len, n_reads, s, &st))) return rc;
+    return kmer_sketch_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, read_start, pos, capacity,
+                            nout, false, s);
+}
+
+extern "C" int gab_kmer_sketch_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                                      int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout, void *stream) {
+    int rc = kmer_mini_check("gab_kmer_sketch_device", h, off, len, n_reads, k, window);
+    if (rc) return rc;
+    GAB_CHECK(nout && capacity >= 0 && seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_sketch_device: bad argument");
+    gab_device_guard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_len;
+    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
+    return kmer_sketch_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, read_start, pos, capacity, nout, true, s);
+}
+
+static int kmer_check_rate(float rate) {
+    GAB_CHECK(rate >= 0.0f && rate <= 3.0e38f, "gab_kmer_index_minimizers: repeat_kmer_rate = %g (a finite number >= 0)", (double)rate);
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_index_minimizers(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                                         int32_t min_len_exclusive, float repeat_kmer_rate, gab_kmer_index_result *res) {
+    int rc = kmer_mini_check("gab_kmer_index_minimizers", h, off, len, n_reads, k, window);
+    if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
+    gab_device_guard g(h->device);
+    hipStream_t s;
+    if ((rc = h->hs.get(&s))) return rc;
+    kmer_staged st;
+    if ((rc = kmer_stage_host(h, "gab_kmer_index_minimizers", seq, off, len, n_reads, s, &st))) return rc;
+    return kmer_index_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, repeat_kmer_rate, res, s);
+}
+
+extern "C" int gab_kmer_index_minimizers_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                                                int window, int32_t min_len_exclusive, float repeat_kmer_rate, gab_kmer_index_result *res, void *stream) {
+    int rc = kmer_mini_check("gab_kmer_index_minimizers_device", h, off, len, n_reads, k, window);
+    if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
+    GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_index_minimizers_device: bad sequence slab");
+    gab_device_guard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_len;
+    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
+    return kmer_index_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, repeat_kmer_rate, res, s);
+}
+
+#define KMER_NEED_INDEX(fn) GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers on this handle")
+
+extern "C" int gab_kmer_index_dump(gab_kmer *h, uint64_t *kmers, int64_t *start, int64_t *gpos, int64_t cap_kmers, int64_t cap_entries, int64_t *nk,
+                                   int64_t *ne) {
+    KMER_NEED_INDEX("gab_kmer_index_dump");
+    GAB_CHECK(nk && ne && cap_kmers >= 0 && cap_entries >= 0, "gab_kmer_index_dump: NULL or negative argument");
+    const int64_t n = h->ix.selected_kmers, m = h->ix.index_entries;
+    *nk = n; *ne = m;
+    if (cap_kmers < n || cap_entries < m) {
+        gab_set_error("gab_kmer_index_dump: %lld k-mers and %lld entries, room for %lld and %lld", (long long)n, (long long)m, (long long)cap_kmers,
+                      (long long)cap_entries);
+        return GAB_ERANGE;
+    }
+    GAB_CHECK(start, "gab_kmer_index_dump: NULL output");
+    if (n == 0) { start[0] = 0; return GAB_OK; }
+    GAB_CHECK(kmers && gpos, "gab_kmer_index_dump: NULL output");
+    gab_device_guard g(h->device);
+    hipStream_t s;
+    int rc;
+    if ((rc = h->hs.get(&s))) return rc;
+    const size_t nb = align256(((size_t)h->ix.distinct + 1) * 8);      // (the layout of the build)
+    const char *ib = h->idx.as<char>();
+    GAB_HIP(hipMemcpyAsync(kmers, ib, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(start, ib + nb, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(gpos, ib + 2 * nb, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipStreamSynchronize(s));
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_index_lookup(gab_kmer *h, const uint64_t *kmers, int64_t n, int64_t *first, int32_t *count, uint8_t *repetitive) {
+    KMER_NEED_INDEX("gab_kmer_index_lookup");
+    GAB_CHECK(n >= 0 && (n == 0 || (kmers && first && count && repetitive)), "gab_kmer_index_lookup: NULL or negative argument");
+    if (n == 0) return GAB_OK;
+    gab_device_guard g(h->device);
+    hipStream_t s;
+    int rc;
+    if ((rc = h->hs.get(&s))) return rc;
+    const size_t nb = align256((size_t)n * 8), cb = align256((size_t)n * 4);
+    if ((rc = h->aux.reserve(2 * nb + cb + align256((size_t)n)))) return rc;
+    char *ab = h->aux.as<char>();
+    uint64_t *d_k = reinterpret_cast<uint64_t *>(ab);
+    int64_t *d_first = reinterpret_cast<int64_t *>(ab + nb);
+    int32_t *d_count = reinterpret_cast<int32_t *>(ab + 2 * nb);
+    uint8_t *d_rep = reinterpret_cast<uint8_t *>(ab + 2 * nb + cb);
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    h->h_ct->bad_query = ~0ull;
+    GAB_HIP(hipMemcpyAsync(&d_ct->bad_query, &h->h_ct->bad_query, 8, hipMemcpyHostToDevice, s));
+    GAB_HIP(hipMemcpyAsync(d_k, kmers, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(kmer_index_lookup, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, h->ix_thr, d_k, n,
+                       d_first, d_count, d_rep, d_ct);
+    GAB_HIP(hipMemcpyAsync(&h->h_ct->bad_query, &d_ct->bad_query, 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(first, d_first, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(repetitive, d_rep, (size_t)n, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipStreamSynchronize(s));
+    GAB_CHECK(h->h_ct->bad_query == ~0ull, "gab_kmer_index_lookup: k-mer %lld has bits above 2k = %d", (long long)h->h_ct->bad_query, 2 * h->k);
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *count_ms, float *fill_ms, float *sort_ms) {
+    KMER_NEED_INDEX("gab_kmer_index_last_phases");
+    if (sketch_ms) *sketch_ms = h->ix_ms[0];
+    if (count_ms) *count_ms = h->ix_ms[1];
+    if (fill_ms) *fill_ms = h->ix_ms[2];
+    if (sort_ms) *sort_ms = h->ix_ms[3];
     return GAB_OK;
 }

@@ -1,5 +1,6 @@
 """Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI, whole or in key-space partitions
-(include/gab.h: gab_kmer_count_part)."""
+(include/gab.h: gab_kmer_count_part), and of the minimizer index, VertexIndex::buildIndexMinimizers (kmer-cnt/vertex_index.cpp:394-502;
+include/gab.h: gab_kmer_sketch, gab_kmer_index_minimizers)."""
 import ctypes as C
 import threading
 
@@ -10,10 +11,17 @@ from ._lib import GabError, check, lib
 RUN = 64        # GAB_KMER_RUN: positions per GPU lane (what last_stats()["merged"] is defined by)
 MAX_K = 17      # GAB_KMER_MAX_K
 MAX_PARTS = 64  # GAB_KMER_MAX_PARTS
+MAX_WINDOW = 255    # GAB_KMER_MAX_WINDOW
+ERANGE = -34    # GAB_ERANGE
 
 
 class _Result(C.Structure):
     _fields_ = [(f, C.c_int64) for f in ("reads_kept", "positions", "distinct", "total_kmers", "hash_size", "max_count")]
+
+
+class _IndexResult(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("reads_kept", "total_len", "minimizers", "distinct", "repetitive_frequency", "filtered_kmers",
+                                         "filtered_entries", "selected_kmers", "index_entries")]
 
 
 def _p(a):
@@ -149,6 +157,99 @@ class KmerCounter:
         return {"probes": pr.value, "merged": mg.value, "kernel_ms": kms.value, "total_ms": tms.value,
                 "pack_ms": a.value, "count_ms": b.value, "reduce_ms": c.value}
 
+    # ---- minimizer mode -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _packed(reads):
+        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
+        return np.ascontiguousarray(seq, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(ln, np.int32)
+
+    def sketch_into(self, reads, k, window, read_start, pos, min_len=5000):
+        """one raw gab_kmer_sketch into the caller's arrays: (return code, needed size)"""
+        seq, off, ln = self._packed(reads)
+        n = C.c_int64(-1)
+        rc = lib().gab_kmer_sketch(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int(window), C.c_int32(min_len), _p(read_start),
+                                   _p(pos), C.c_int64(pos.size), C.byref(n))
+        return rc, n.value
+
+    def sketch(self, reads, k, window, min_len=5000, capacity=None):
+        """-> (read_start int64 [n + 1], pos int32): the minimizer positions of read i are pos[read_start[i]:read_start[i + 1]], ascending;
+        a filtered or too-short read has an empty range.  capacity: room offered on the first try (grown once when it is too little);
+        by default twice the 2 / (window + 1) of the k-mer positions that random sequence gives, and never more than all of them"""
+        packed = self._packed(reads)
+        positions = int(np.maximum(packed[2].astype(np.int64) - k, 0).sum())
+        cap = min(positions, 4 * positions // (max(window, 1) + 1)) + 64 if capacity is None else int(capacity)
+        while True:
+            start = np.full(packed[2].size + 1, -12345, np.int64); pos = np.full(cap, -12345, np.int32)
+            rc, n = self.sketch_into(packed, k, window, start, pos, min_len)
+            if rc == ERANGE and n > cap:
+                cap = n
+                continue
+            check(rc)
+            return start, pos[:n]
+
+    def sketch_device(self, seq, off, ln, k, window, read_start, pos, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: seq uint8, off int64, ln int32; outputs read_start int64 [n + 1] and pos int32 [capacity]
+        -> (return code, needed size); ERANGE when pos is too small (nothing written)"""
+        n = C.c_int64(-1)
+        rc = lib().gab_kmer_sketch_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()), C.c_void_p(ln.data_ptr()),
+                                          C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len), C.c_void_p(read_start.data_ptr()),
+                                          C.c_void_p(pos.data_ptr()), C.c_int64(pos.numel()), C.byref(n), C.c_void_p(stream))
+        if rc != ERANGE:
+            check(rc)
+        return rc, n.value
+
+    @staticmethod
+    def _index_dict(res):
+        return {f: getattr(res, f) for f, _ in _IndexResult._fields_}
+
+    def index_minimizers(self, reads, k, window, rate=100.0, min_len=5000):
+        """builds the minimizer index into the handle (it replaces the count table) -> the nine fields of gab_kmer_index_result"""
+        seq, off, ln = self._packed(reads)
+        res = _IndexResult(*([-12345] * 9))
+        check(lib().gab_kmer_index_minimizers(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int(window), C.c_int32(min_len),
+                                              C.c_float(rate), C.byref(res)))
+        return self._index_dict(res)
+
+    def index_minimizers_device(self, seq, off, ln, k, window, rate=100.0, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: uint8 / int64 / int32"""
+        res = _IndexResult(*([-12345] * 9))
+        check(lib().gab_kmer_index_minimizers_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
+                                                     C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len),
+                                                     C.c_float(rate), C.byref(res), C.c_void_p(stream)))
+        return self._index_dict(res)
+
+    def index_dump_into(self, kmers, start, gpos):
+        """one raw gab_kmer_index_dump: (return code, needed k-mers, needed entries); start needs kmers.size + 1 of room"""
+        nk = C.c_int64(-1); ne = C.c_int64(-1)
+        assert start.size >= kmers.size + 1
+        rc = lib().gab_kmer_index_dump(self._h, _p(kmers), _p(start), _p(gpos), C.c_int64(kmers.size), C.c_int64(gpos.size), C.byref(nk), C.byref(ne))
+        return rc, nk.value, ne.value
+
+    def index_dump(self):
+        """-> (k-mers uint64 ascending, start int64 [nk + 1], gpos int64): the list of kmers[i] is gpos[start[i]:start[i + 1]], ascending"""
+        nk, ne = 0, 0
+        while True:
+            kmers = np.full(nk, 0xDEADBEEFDEADBEEF, np.uint64); start = np.full(nk + 1, -12345, np.int64); gpos = np.full(ne, -12345, np.int64)
+            rc, need_k, need_e = self.index_dump_into(kmers, start, gpos)
+            if rc == ERANGE and (need_k > nk or need_e > ne):
+                nk, ne = need_k, need_e
+                continue
+            check(rc)
+            return kmers[:need_k], start[:need_k + 1], gpos[:need_e]
+
+    def index_lookup(self, kmers):
+        """-> (first int64, count int32, repetitive uint8) per k-mer (canonicalised first): its list is index_dump()'s
+        gpos[first:first + count]; absent: count 0, first -1; removed as repetitive: count 0, first -1, repetitive 1"""
+        kmers = np.ascontiguousarray(kmers, np.uint64)
+        first = np.full(kmers.size, -12345, np.int64); count = np.full(kmers.size, -12345, np.int32); rep = np.full(kmers.size, 77, np.uint8)
+        check(lib().gab_kmer_index_lookup(self._h, _p(kmers), C.c_int64(kmers.size), _p(first), _p(count), _p(rep)))
+        return first, count, rep
+
+    def index_last_phases(self):
+        a = C.c_float(0); b = C.c_float(0); c = C.c_float(0); d = C.c_float(0)
+        check(lib().gab_kmer_index_last_phases(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"sketch_ms": a.value, "count_ms": b.value, "fill_ms": c.value, "sort_ms": d.value}
+
 
 class KmerCounterSet:
     """One count over several GPUs without a merge: handle i, on devices[i], counts partition i of len(devices) of the key space.
@@ -224,4 +325,4 @@ class KmerCounterSet:
         return [dict(kc.last_stats(), **kc.last_part()) for kc in self.parts]
 
 
-__all__ = ["KmerCounter", "KmerCounterSet", "GabError", "pack_reads", "part_of", "table_slots", "RUN", "MAX_K", "MAX_PARTS"]
+__all__ = ["KmerCounter", "KmerCounterSet", "GabError", "pack_reads", "part_of", "table_slots", "RUN", "MAX_K", "MAX_PARTS", "MAX_WINDOW"]

@@ -457,6 +457,71 @@ int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max_seq_bytes,
 /* what the last count ran as: its partition, the slots of the table it ended in, and whether it was repeated (0 / 1) */
 int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried);
 
+/* ---- kmer-cnt, minimizer mode: the sketch of every read and the k-mer -> positions index (use_minimizers = 1) -------------
+ * Replaces  vertexIndex.buildIndexMinimizers(1, minimizer_window)   kmer-cnt/kmer_cnt.cpp:282-287
+ *           -> VertexIndex::buildIndexMinimizers                    kmer-cnt/vertex_index.cpp:394-502
+ *           (the sketch: yieldMinimizers, kmer-cnt/kmer.h:206-262; the filter: filterFrequentKmers, kmer-cnt/vertex_index.cpp:178-217).
+ * Reads, the length filter, the strand and the k-mer positions 0 .. L - k - 1 are those of gab_kmer_count above.
+ * Sketch of one read, window w: w = 1 -> every position.  Otherwise the order key of a position is the splitmix64 finaliser
+ * (kmer-cnt/kmer.h:91-98) of its canonical k-mer, and a monotone queue is walked over the positions: entries with a strictly greater
+ * key leave from the back (equal ones stay); when the front's position is <= p - w the expired fronts leave and, on such a step only,
+ * the front moves on to the last of a leading run of equal keys; after every step the front is emitted unless it was the last
+ * position emitted.  Position 0 is always emitted and emission starts before the first full window.  The tie rule is stateful: in a
+ * homopolymer the minimizers fall at 0, w, 2w, ... from the start of the run.  The result equals that sequential definition on
+ * every input.
+ * Index: capacity(x) = emitted minimizers, over all kept reads, with canonical k-mer x; minimizers = their sum, distinct = their
+ * number; repetitive_frequency = (size_t)(repeat_kmer_rate * ((float)minimizers / (distinct + 1))) in C float arithmetic; every x
+ * with capacity(x) > repetitive_frequency is removed (filtered_kmers of them, filtered_entries minimizers); every other x keeps the
+ * ascending list of the global positions of its minimizers (selected_kmers lists, index_entries positions).
+ * Global positions (kmer-cnt/sequence_container.cpp:48-79, 359-370): kept read i of length L_i, S_i = the lengths of the kept reads
+ * before it, owns [2 S_i, 2 S_i + L_i) forward and [2 S_i + L_i, 2 S_i + 2 L_i) reverse complement; a minimizer at forward position p
+ * is entered at 2 S_i + p if its forward k-mer is the canonical one (palindromes are not flipped, kmer-cnt/kmer.h:54-63), at
+ * 2 S_i + L_i + (L_i - p - k) otherwise.  2 * total_len < 2^40 as in the reference, fewer than 2^32 k-mer positions per call.
+ * 1 <= k <= GAB_KMER_MAX_K, 1 <= window <= GAB_KMER_MAX_WINDOW, repeat_kmer_rate >= 0 and finite; anything else -> GAB_EINVAL.
+ * An index call takes the handle's table over: afterwards gab_kmer_spectrum / query / dump (and last_stats / last_phases /
+ * last_part) return GAB_EINVAL until the next count, and the gab_kmer_index_* accessors return GAB_EINVAL before the first index
+ * call and after any later count.  gab_kmer_sketch touches neither.  Empty input, no kept read, no read longer than k, or a rate
+ * that removes every k-mer give zeros and an empty index, not an error.  Two calls on one handle are independent.
+ */
+#define GAB_KMER_MAX_WINDOW 255
+typedef struct {
+    int64_t reads_kept;             /* reads with len > min_len_exclusive */
+    int64_t total_len;              /* their bases (the reference's totalLen of the forward strands) */
+    int64_t minimizers, distinct;   /* the reference's totalKmers and uniqueKmers of the filter */
+    int64_t repetitive_frequency;
+    int64_t filtered_kmers, filtered_entries;
+    int64_t selected_kmers, index_entries;
+} gab_kmer_index_result;
+/* The minimizer positions of every read: pos[read_start[i] .. read_start[i + 1]) ascending, read_start has n_reads + 1 entries;
+ * a filtered or too-short read has an empty range.  *nout = their number; when that exceeds `capacity` neither array is written
+ * and the call returns GAB_ERANGE: call again with *nout of room.  Host pointers; a byte outside ACGTacgt -> GAB_EINVAL naming
+ * the read. */
+int gab_kmer_sketch(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                    int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout);
+/* seq / off / len / read_start / pos: device pointers (see gab_kmer_count_device); nout: host pointer.  Synchronises `stream`. */
+int gab_kmer_sketch_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads,
+                           int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity,
+                           int64_t *nout, void *stream);
+/* Builds the index into the handle.  Host pointers / device pointers as gab_kmer_count / gab_kmer_count_device; res: host. */
+int gab_kmer_index_minimizers(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                              int32_t min_len_exclusive, float repeat_kmer_rate, gab_kmer_index_result *res);
+int gab_kmer_index_minimizers_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len,
+                                     int64_t n_reads, int k, int window, int32_t min_len_exclusive, float repeat_kmer_rate,
+                                     gab_kmer_index_result *res, void *stream);
+/* The index of the last build: kmers[0 .. *nk) ascending, the list of kmers[i] is gpos[start[i] .. start[i + 1]) ascending
+ * (start has *nk + 1 entries, so it needs cap_kmers + 1 of room).  *nk = selected_kmers, *ne = index_entries; when either exceeds
+ * its capacity nothing is written and the call returns GAB_ERANGE with both needed sizes.  Host pointers. */
+int gab_kmer_index_dump(gab_kmer *h, uint64_t *kmers, int64_t *start, int64_t *gpos, int64_t cap_kmers, int64_t cap_entries,
+                        int64_t *nk, int64_t *ne);
+/* kmers[i] is canonicalised as by gab_kmer_query (a value >= 4^k -> GAB_EINVAL).  count[i] = length of its list and first[i] = where
+ * the list starts in gab_kmer_index_dump's gpos; an absent k-mer: count 0, first -1; a removed (repetitive) one: count 0, first -1,
+ * repetitive[i] = 1 (0 for every other).  Host pointers. */
+int gab_kmer_index_lookup(gab_kmer *h, const uint64_t *kmers, int64_t n, int64_t *first, int32_t *count, uint8_t *repetitive);
+/* last index build, per stage (HIP events, ms): 2-bit packing + sketch + scan; table clear + capacity pass + reduction; ordering
+ * the keys, list offsets and the fill pass; the segmented sort of the lists.  The host computes repetitive_frequency between
+ * the second and the third: that wait is in none of them. */
+int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *count_ms, float *fill_ms, float *sort_ms);
+
 /* ---- input parsers ---------------------------------------------------------
  * The reference drivers parse their text inputs on the host, line by line, outside the region of interest
  * (bsw: loadPairs, bsw/src/main_banded.cpp:164-206 -- fgets + sscanf per pair; bpm / wfa: getline per line,

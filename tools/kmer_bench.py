@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the k-mer counter (gab_kmer_*) on a generated E. coli-like read set.  Standalone; needs a GPU.
 
-    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--parts 1,2,4,8] [--out kmer_bench.json]
+    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--parts 1,2,4,8] [--minimizers W] [--out kmer_bench.json]
 
 The read set: a 4.6 Mbp random genome, reads of 5 .. 20 kb at 50x, both strands, 10 % errors (substitutions, seeded).
 For k = 17 and 15 it reports, warm, as the median of the repeats:
@@ -16,6 +16,11 @@ the same warm-up and repeats: what one GPU of N would do, every GPU walking all 
 partition the stage times, and per N the slowest partition's call time with the positions per second it would give -- a ONE-GPU
 FORECAST of an N-GPU run, not a measurement of one (no second card, no shared host link).  As N grows the count stage tends to
 what extraction alone costs: the floor no number of GPUs gets under.
+
+--minimizers W: INSTEAD of the count, the minimizer index (gab_kmer_index_minimizers_device, window W, repeat_kmer_rate --rate) on
+the same reads, resident, for k = 17 and 15: the nine result fields, k-mer positions per second over the wall time of the call
+(median of the warm repeats; the call synchronises twice, once for the filter's two integers) and the device time of its four
+stages -- sketch, capacity count, fill, segmented sort.
 """
 import argparse
 import json
@@ -64,6 +69,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--coverage", type=int, default=50)
     ap.add_argument("--parts", default="", help="comma-separated partition counts to forecast, e.g. 1,2,4,8")
+    ap.add_argument("--minimizers", type=int, default=0, metavar="W", help="measure the minimizer index with window W instead of the count")
+    ap.add_argument("--rate", type=float, default=100.0, help="repeat_kmer_rate of --minimizers")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -79,36 +86,65 @@ def main():
     kc = KmerCounter()
     kc.reserve(len(reads), seq.size)
     out = {"reads": len(reads), "bases": int(seq.size), "repeats": a.repeats, "warmup": a.warmup, "k": {}}
-    for k in (17, 15):
-        row = {}
-        res = None
-        for mode in ("resident", "host"):
+    if a.minimizers:
+        out["minimizers"] = {"window": a.minimizers, "rate": a.rate, "k": {}}
+        for k in (17, 15):
             samples = []
             for it in range(a.warmup + a.repeats):
                 t0 = time.perf_counter()
-                res = kc.count_device(d_seq, d_off, d_len, k) if mode == "resident" else kc.count((seq, off, ln), k)
+                res = kc.index_minimizers_device(d_seq, d_off, d_len, k, a.minimizers, a.rate)
                 wall = time.perf_counter() - t0
-                st = kc.last_stats()
                 if it >= a.warmup:
-                    samples.append((st["total_ms"] * 1e-3 if mode == "resident" else wall, wall, st))
-            pos = res["positions"]
+                    samples.append((wall, kc.index_last_phases()))
+            positions = int(np.maximum(ln[ln > 5000].astype(np.int64) - k, 0).sum())
             t = statistics.median(s[0] for s in samples)
-            row[mode] = {"positions_per_s": pos / t, "seconds_median": t, "seconds_min": min(s[0] for s in samples), "seconds_max": max(s[0] for s in samples),
-                         "wall_seconds_median": statistics.median(s[1] for s in samples),
-                         "pack_ms": statistics.median(s[2]["pack_ms"] for s in samples),
-                         "count_ms": statistics.median(s[2]["count_ms"] for s in samples),
-                         "reduce_ms": statistics.median(s[2]["reduce_ms"] for s in samples)}
-        st = kc.last_stats()
-        inserts = res["positions"] - st["merged"]
-        row["result"] = res
-        row["inserts"] = inserts
-        row["lines_per_insert"] = st["probes"] / max(inserts, 1)
-        row["inserts_per_s_in_count_stage"] = inserts / (row["resident"]["count_ms"] * 1e-3)
-        if a.check:
-            from tests import kmer_model
-            m = kmer_model.model(reads, k)
-            row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
-        out["k"][str(k)] = row
+            row = {"result": res, "positions": positions, "positions_per_s": positions / t, "seconds_median": t,
+                   "seconds_min": min(s[0] for s in samples), "seconds_max": max(s[0] for s in samples)}
+            for f in ("sketch_ms", "count_ms", "fill_ms", "sort_ms"):
+                row[f] = statistics.median(s[1][f] for s in samples)
+            # the reference's own numbers for this very set, where they were recorded (tests/golden/make_minimizer_golden.py --time)
+            rec_path = os.path.join(ROOT, "tests", "golden", "kmer_minimizer_expected.json")
+            if os.path.exists(rec_path) and (a.coverage, a.minimizers, a.rate) == (50, 10, 100.0):
+                rec = json.load(open(rec_path)).get("reference_cpu_time", {}).get("k", {}).get(str(k))
+                if rec:
+                    row["matches_reference_record"] = all(res[f] == rec[f] for f in ("repetitive_frequency", "filtered_entries", "selected_kmers",
+                                                                                     "index_entries"))
+            if a.check:
+                from tests import minimizer_model
+                m = minimizer_model.build_index(reads, k, a.minimizers, a.rate)
+                row["matches_model"] = all(res[f] == m[f] for f in minimizer_model.FIELDS)
+            out["minimizers"]["k"][str(k)] = row
+    else:
+        for k in (17, 15):
+            row = {}
+            res = None
+            for mode in ("resident", "host"):
+                samples = []
+                for it in range(a.warmup + a.repeats):
+                    t0 = time.perf_counter()
+                    res = kc.count_device(d_seq, d_off, d_len, k) if mode == "resident" else kc.count((seq, off, ln), k)
+                    wall = time.perf_counter() - t0
+                    st = kc.last_stats()
+                    if it >= a.warmup:
+                        samples.append((st["total_ms"] * 1e-3 if mode == "resident" else wall, wall, st))
+                pos = res["positions"]
+                t = statistics.median(s[0] for s in samples)
+                row[mode] = {"positions_per_s": pos / t, "seconds_median": t, "seconds_min": min(s[0] for s in samples), "seconds_max": max(s[0] for s in samples),
+                             "wall_seconds_median": statistics.median(s[1] for s in samples),
+                             "pack_ms": statistics.median(s[2]["pack_ms"] for s in samples),
+                             "count_ms": statistics.median(s[2]["count_ms"] for s in samples),
+                             "reduce_ms": statistics.median(s[2]["reduce_ms"] for s in samples)}
+            st = kc.last_stats()
+            inserts = res["positions"] - st["merged"]
+            row["result"] = res
+            row["inserts"] = inserts
+            row["lines_per_insert"] = st["probes"] / max(inserts, 1)
+            row["inserts_per_s_in_count_stage"] = inserts / (row["resident"]["count_ms"] * 1e-3)
+            if a.check:
+                from tests import kmer_model
+                m = kmer_model.model(reads, k)
+                row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
+            out["k"][str(k)] = row
     if a.parts:
         out["parts"] = {}
         for nparts in [int(x) for x in a.parts.split(",")]:
