@@ -1,7 +1,7 @@
 /* kmer-cnt -- drop-in driver of the kmer-cnt benchmark (Flye's solid k-mer counter) on MI355X.
  *
  *     kmer-cnt --reads a.fasta[,b.fastq.gz,...] --config F [--kmer K] [--min-read N] [--min-ovlp N] [--threads T] [--log F] [--debug]
- *              [-g N | --gpus N]
+ *              [-g N | --gpus N] [--index-gpus N]
  *
  * Options, the "Hash size: N" / "Total k-mers N" debug lines and the "Kernel time: %.3f sec" line on stderr are those of the
  * reference's driver (kmer-cnt/kmer_cnt.cpp:47-125, 155-337; the two counts: kmer-cnt/vertex_index.cpp:858-859).  --threads only
@@ -22,7 +22,10 @@
  * numbers equal the reference's on reads with N.  Reads LONGER than max(--min-read, --min-ovlp) are kept
  * (kmer-cnt/kmer_cnt.cpp:205, kmer-cnt/sequence_container.cpp:100-106).
  * use_minimizers = 1 in the config file selects the minimizer index instead of the count (build_minimizer_index below); it also needs
- * minimizer_window, repeat_kmer_rate and assemble_kmer_sample there, and runs on the first GPU whatever -g says.
+ * minimizer_window, repeat_kmer_rate and assemble_kmer_sample there, and runs on the first GPU whatever -g says -- unless
+ * --index-gpus N (1..GAB_KMER_MAX_PARTS) asks for the index in N key-space partitions, one per GPU, built in two phases
+ * (build_minimizer_index_parts below; include/gab.h: gab_kmer_index_part_begin / _finish).  In counting mode --index-gpus is accepted
+ * and ignored.
  * Inside it: ONE gab_kmer_count_part per GPU over the kept reads, all at once (that GPU's copy of the reads included), where the
  * reference runs vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).  -g 1 is one gab_kmer_count_part(0 of 1) = gab_kmer_count.
  */
@@ -218,7 +221,7 @@ static void load_file(const char *name, kc_reads *R, int64_t min_len) {
 
 static void usage(void) {
     fprintf(stderr, "Usage: kmer-cnt  --reads path --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
-                    "\t\t[--threads num] [--log path] [--debug] [-g num | --gpus num] [-h]\n\n"
+                    "\t\t[--threads num] [--log path] [--debug] [-g num | --gpus num] [--index-gpus num] [-h]\n\n"
                     "Required arguments:\n"
                     "  --reads path\tcomma-separated list of read files (FASTA / FASTQ, plain or gzip)\n"
                     "  --config path\tpath to the config file\n\n"
@@ -229,7 +232,9 @@ static void usage(void) {
                     "  --debug \t\tenable debug output [default = false]\n"
                     "  --log log_file\toutput log to file [default = not set]\n"
                     "  --threads num_threads\taccepted and ignored (the count runs on the GPUs)\n"
-                    "  -g, --gpus num\tGPUs to count on, each one partition of the k-mers [default = $GAB_GPUS, else 1]\n", GAB_KMER_MAX_K);
+                    "  -g, --gpus num\tGPUs to count on, each one partition of the k-mers [default = $GAB_GPUS, else 1]\n"
+                    "  --index-gpus num\tuse_minimizers = 1: GPUs to build the index on, each one partition of the k-mers, 1..%d\n"
+                    "\t\t\t[default = not set: the index is built on the first GPU, not partitioned]\n", GAB_KMER_MAX_K, GAB_KMER_MAX_PARTS);
 }
 
 /* one partition per logical GPU, run by gab_run_parts */
@@ -246,8 +251,9 @@ static void count_part(int g, void *arg) {
 /* use_minimizers = 1: ONE gab_kmer_index_minimizers over the kept reads where the reference runs
  * vertexIndex.buildIndexMinimizers(1, minimizer_window) (kmer-cnt/kmer_cnt.cpp:282-287), and its debug lines in its order
  * (kmer-cnt/vertex_index.cpp:190-216, 481, 494-500): the floats are computed with the reference's float expressions and written as
- * its ostream writes them (%g).  The index stays on the first GPU: its filter needs the number of minimizers and of distinct
- * k-mers of the WHOLE input before any list is laid out, so key-space partitions would have to meet in the middle of the call. */
+ * its ostream writes them (%g).  Without --index-gpus the index stays on the first GPU: its filter needs the number of minimizers
+ * and of distinct k-mers of the WHOLE input before any list is laid out, so key-space partitions have to meet in the middle of the
+ * build (build_minimizer_index_parts below does that). */
 static int build_minimizer_index(const kc_reads *R, int kmer, int window, float rate, int32_t min_len, int ngpus) {
     if (ngpus > 1) log_debug("The minimizer index is built on the first of the %d GPUs (it is not partitioned)", ngpus);
     gab_kmer *h = NULL;
@@ -283,13 +289,99 @@ static int build_minimizer_index(const kc_reads *R, int kmer, int window, float 
     return 0;
 }
 
+/* use_minimizers = 1 with --index-gpus N: the same index in N key-space partitions, one per logical GPU.  The filter's threshold
+ * needs the minimizers and the distinct k-mers of the WHOLE input, so the partitions meet in the middle: one round of
+ * gab_kmer_index_part_begin on every GPU (each sketches all reads and counts the capacities of its own k-mers), the two sums on the
+ * host, one round of gab_kmer_index_part_finish with them.  Every count of the partitions adds up to the unpartitioned build's, so
+ * the reference's lines are printed from the sums with the float expressions of build_minimizer_index above. */
+typedef struct {
+    gab_kmer **h; gab_kmer_index_result *res; int *rc; char (*err)[512];
+    const kc_reads *R; int kmer, window, nparts; int32_t min_len;
+    int64_t minimizers, distinct; float rate;        /* phase 2: the sums over all partitions */
+} kc_index_parts;
+static void index_part_begin(int g, void *arg) {
+    kc_index_parts *P = (kc_index_parts *)arg;
+    P->rc[g] = gab_kmer_index_part_begin(P->h[g], P->R->seq, P->R->off, P->R->len, P->R->n, P->kmer, P->window, P->min_len, g, P->nparts, &P->res[g]);
+    if (P->rc[g]) snprintf(P->err[g], sizeof P->err[g], "%s", gab_last_error());      /* (the message is the calling thread's) */
+}
+static void index_part_finish(int g, void *arg) {
+    kc_index_parts *P = (kc_index_parts *)arg;
+    P->rc[g] = gab_kmer_index_part_finish(P->h[g], P->minimizers, P->distinct, P->rate, &P->res[g]);
+    if (P->rc[g]) snprintf(P->err[g], sizeof P->err[g], "%s", gab_last_error());
+}
+static void index_parts_check(const kc_index_parts *P, const char *what) {
+    for (int g = 0; g < P->nparts; g++)
+        if (P->rc[g]) { fprintf(stderr, "ERROR: %s failed on partition %d (%d): %s\n", what, g, P->rc[g], P->err[g]); exit(EXIT_FAILURE); }
+}
+static int build_minimizer_index_parts(const kc_reads *R, int kmer, int window, float rate, int32_t min_len, int ngpus) {
+    log_debug("Building the minimizer index on %d GPU(s), one key-space partition each", ngpus);
+    gab_kmer **hs = (gab_kmer **)calloc((size_t)ngpus, sizeof *hs);
+    gab_kmer_index_result *part_res = (gab_kmer_index_result *)calloc((size_t)ngpus, sizeof *part_res);
+    int *part_rc = (int *)calloc((size_t)ngpus, sizeof *part_rc);
+    char (*part_err)[512] = (char (*)[512])calloc((size_t)ngpus, 512);
+    if (!hs || !part_res || !part_rc || !part_err) die("out of memory");
+    for (int g = 0; g < ngpus; g++) {                                                  /* buffers before the region of interest */
+        GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(g), &hs[g]), "gab_kmer_create");
+        GAB_DIE_IF(gab_kmer_reserve_part(hs[g], R->n, (int64_t)R->bytes, ngpus), "gab_kmer_reserve_part");
+    }
+    if (R->bytes) gab_pin(R->seq, R->bytes);
+    kc_index_parts P = {hs, part_res, part_rc, part_err, R, kmer, window, ngpus, min_len, 0, 0, rate};
+    gab_kmer_index_result x;
+    memset(&x, 0, sizeof x);
+
+    const double t0 = gab_now();
+    gab_roi_begin_n(ngpus);
+    if (ngpus == 1) index_part_begin(0, &P);
+    else gab_run_parts(ngpus, index_part_begin, &P);
+    index_parts_check(&P, "gab_kmer_index_part_begin");
+    for (int g = 0; g < ngpus; g++) { P.minimizers += part_res[g].minimizers; P.distinct += part_res[g].distinct; }
+    if (ngpus == 1) index_part_finish(0, &P);
+    else gab_run_parts(ngpus, index_part_finish, &P);
+    index_parts_check(&P, "gab_kmer_index_part_finish");
+    x.reads_kept = part_res[0].reads_kept; x.total_len = part_res[0].total_len; x.repetitive_frequency = part_res[0].repetitive_frequency;
+    for (int g = 0; g < ngpus; g++) {                                                  /* disjoint partitions of the keys: the counts add */
+        x.minimizers += part_res[g].minimizers; x.distinct += part_res[g].distinct;
+        x.filtered_kmers += part_res[g].filtered_kmers; x.filtered_entries += part_res[g].filtered_entries;
+        x.selected_kmers += part_res[g].selected_kmers; x.index_entries += part_res[g].index_entries;
+    }
+    const float mean = (float)(size_t)x.minimizers / ((size_t)x.distinct + 1);
+    const float filtered_rate = (float)(size_t)x.filtered_entries / (size_t)x.minimizers;
+    log_debug("Mean k-mer frequency: %g", (double)mean);
+    log_debug("Repetitive k-mer frequency: %lld", (long long)x.repetitive_frequency);
+    log_debug("Filtered %lld repetitive k-mers (%g)", (long long)x.filtered_entries, (double)filtered_rate);
+    log_debug("Sorting k-mer index");
+    log_debug("Selected k-mers: %lld", (long long)x.selected_kmers);
+    log_debug("K-mer index size: %lld", (long long)x.index_entries);
+    log_debug("Mean k-mer frequency: %g", (double)((float)(size_t)x.index_entries / (size_t)x.selected_kmers));
+    log_debug("Minimizer rate: %g", (double)((float)(size_t)x.total_len / (size_t)x.index_entries));
+    gab_roi_end();
+    const double t1 = gab_now();
+
+    log_debug("Minimizers: %lld of %lld reads, %lld distinct k-mers, %lld removed", (long long)x.minimizers, (long long)x.reads_kept, (long long)x.distinct,
+              (long long)x.filtered_kmers);
+    for (int g = 0; g < ngpus; g++) {
+        float ms[4] = {0, 0, 0, 0};
+        int retried = 0;
+        (void)gab_kmer_index_last_phases(hs[g], &ms[0], &ms[1], &ms[2], &ms[3]);
+        (void)gab_kmer_index_last_part(hs[g], NULL, NULL, NULL, &retried);
+        log_debug("Partition %d of %d: %lld minimizers of %lld distinct k-mers, %lld removed; device: sketch %.3f ms, count %.3f ms, fill %.3f ms, sort %.3f ms%s",
+                  g, ngpus, (long long)part_res[g].minimizers, (long long)part_res[g].distinct, (long long)part_res[g].filtered_kmers, ms[0], ms[1], ms[2], ms[3],
+                  retried ? "; its first table filled and the capacities were counted again in a larger one" : "");
+    }
+    fprintf(stderr, "Kernel time: %.3f sec\n", t1 - t0);
+    if (R->bytes) gab_unpin(R->seq);
+    for (int g = 0; g < ngpus; g++) gab_kmer_destroy(hs[g]);
+    free(hs); free(part_res); free(part_rc); free(part_err);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, c, idx = 0;
+    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, index_gpus = 0, c, idx = 0;
     const char *reads = NULL, *config = NULL, *logfile = NULL;
     static struct option lo[] = {{"reads", required_argument, 0, 0}, {"config", required_argument, 0, 0}, {"min-read", required_argument, 0, 0},
                                  {"log", required_argument, 0, 0}, {"threads", required_argument, 0, 0}, {"kmer", required_argument, 0, 0},
                                  {"min-ovlp", required_argument, 0, 0}, {"debug", no_argument, 0, 0}, {"gpus", required_argument, 0, 'g'},
-                                 {0, 0, 0, 0}};
+                                 {"index-gpus", required_argument, 0, 0}, {0, 0, 0, 0}};
     while ((c = getopt_long(argc, argv, "hg:", lo, &idx)) != -1) {
         if (c == 'h') { usage(); return 0; }
         if (c == 'g') { gpus_flag = atoi(optarg); if (gpus_flag < 1) { usage(); return 1; } continue; }
@@ -303,6 +395,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(name, "debug")) g_debug = 1;
         else if (!strcmp(name, "reads")) reads = optarg;
         else if (!strcmp(name, "config")) config = optarg;
+        else if (!strcmp(name, "index-gpus")) { index_gpus = atoi(optarg); if (index_gpus < 1 || index_gpus > GAB_KMER_MAX_PARTS) { usage(); return 1; } }
     }
     (void)threads;
     if (!reads || !*reads || !config || !*config) { usage(); return 1; }
@@ -345,11 +438,18 @@ int main(int argc, char **argv) {
     int ngpus = gab_pick_gpus(gpus_flag);
     if (ngpus > GAB_KMER_MAX_PARTS) ngpus = GAB_KMER_MAX_PARTS;
     if (use_minimizers) {
-        const int rc = build_minimizer_index(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len), ngpus);
+        const int32_t min_len32 = (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len);
+        int rc;
+        if (index_gpus) {                                   /* (clamped to the cards there are, as -g is, unless GAB_GPU_OVERSUBSCRIBE) */
+            int n = gab_pick_gpus(index_gpus);
+            if (n > GAB_KMER_MAX_PARTS) n = GAB_KMER_MAX_PARTS;
+            rc = build_minimizer_index_parts(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], min_len32, n);
+        } else rc = build_minimizer_index(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], min_len32, ngpus);
         free(R.seq); free(R.off); free(R.len);
         if (g_log) fclose(g_log);
         return rc;
     }
+    if (index_gpus) log_debug("--index-gpus %d is ignored: use_minimizers is not set, there is no index to build", index_gpus);
     log_debug("Counting on %d GPU(s), one key-space partition each", ngpus);
     gab_kmer **hs = (gab_kmer **)calloc((size_t)ngpus, sizeof *hs);
     gab_kmer_result *part_res = (gab_kmer_result *)calloc((size_t)ngpus, sizeof *part_res);

@@ -24,6 +24,8 @@
 // Several GPUs split the KEYS, not the reads (gab_kmer_count_part): every GPU walks all reads and inserts only the canonical k-mers
 // whose hash falls into its partition, into a table sized for that share.  The partial results are disjoint, so nothing is merged
 // and no GPU talks to another; what N GPUs add is atomic throughput, what each of them repeats is the extraction.
+// The minimizer index splits the same way (gab_kmer_index_part_begin / _finish), but its filter needs two integers of the whole
+// input, so its partitions meet once, on the host, in the middle of the build: see "minimizer index, host side" below.
 #include "gab_internal.h"
 #include <string.h>
 #include <rocprim/rocprim.hpp>
@@ -219,6 +221,8 @@ __global__ __launch_bounds__(kBlock) void kmer_count(const uint32_t *__restrict_
 }
 
 // ---- reduce ------------------------------------------------------------------------------------------------------------------------
+// kCaps (a partition of the minimizer index): total_kmers <- the sum of the counts themselves, the minimizers of the partition's keys
+template <bool kCaps = false>
 __global__ __launch_bounds__(kBlock) void kmer_reduce(const KmerLine *__restrict__ table, uint64_t nslots, KmerCounters *ct) {
     unsigned long long distinct = 0, total = 0, hashed = 0, mx = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * kBlock) {
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void kmer_reduce(const KmerLine *__restrict
         if (L->key[s]) {
             const unsigned long long c = L->cnt[s];
             distinct++;
-            total += (c + 255) >> 8;
+            total += kCaps ? c : (c + 255) >> 8;
             hashed += c >= 256;
             mx = c > mx ? c : mx;
         }
@@ -506,9 +510,9 @@ struct KmerPopc {
 };
 
 // the slot of a key that is in the table (nullptr if it is not: the walk ends at an empty slot, the table is at most half full)
-__device__ __forceinline__ KmerLine *kmer_find(KmerLine *table, uint64_t nlines, uint64_t key, int *slot) {
+// (line: the key's home line, kmer_line_of in the whole table, kmer_line_of_hash in a partition's)
+__device__ __forceinline__ KmerLine *kmer_find_from(KmerLine *table, uint64_t nlines, uint64_t line, uint64_t key, int *slot) {
     const unsigned long long stored = key + 1;
-    uint64_t line = kmer_line_of(key, nlines);
     for (uint64_t visited = 0; visited < nlines; visited++) {
         KmerLine *L = table + line;
         int match = -1;
@@ -525,6 +529,9 @@ __device__ __forceinline__ KmerLine *kmer_find(KmerLine *table, uint64_t nlines,
     }
     return nullptr;
 }
+__device__ __forceinline__ KmerLine *kmer_find(KmerLine *table, uint64_t nlines, uint64_t key, int *slot) {
+    return kmer_find_from(table, nlines, kmer_line_of(key, nlines), key, slot);
+}
 
 // The second walk over the reads: a lane re-rolls its run from its first marked position to its last and does one of three things
 // with every minimizer.  offs: exclusive scan of the popcounts of masks.
@@ -532,12 +539,18 @@ enum { kWalkSketch = 0, kWalkCount = 1, kWalkFill = 2 };
 //   kWalkSketch  pos[offs + i] = position in the read
 //   kWalkCount   canonical k-mer into the table (kmer_insert): cnt = capacity of the key
 //   kWalkFill    keys with cnt <= thr: gpos[pad++] = global position (pad was set to the start of the key's list)
-template <int kMode>
+// kPart = false: the whole key space in one table (part, nparts and limit are not read).  kPart = true (kWalkCount, kWalkFill): the
+// lane hashes the canonical k-mer of a minimizer once, skips it BEFORE it touches the table when the hash falls into another
+// partition -- (nparts - 1) / nparts of them, each of which would otherwise pay a random 128-byte line that must miss -- and takes the
+// home line from the same hash; the capacity inserts are bounded as those of kmer_count<true> (limit, ct->overflow).  Lanes that
+// skip idle while their wave's owners probe.
+template <int kMode, bool kPart = false>
 __global__ __launch_bounds__(kBlock) void kmer_mini_walk(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
                                                          const KmerTile *__restrict__ tiles, int64_t n_tiles, int k,
                                                          const unsigned long long *__restrict__ masks, const uint32_t *__restrict__ offs,
                                                          int32_t *__restrict__ pos, KmerLine *table, uint64_t nlines, KmerCounters *ct,
-                                                         const int64_t *__restrict__ rbase, uint32_t thr, int64_t *__restrict__ gpos) {
+                                                         const int64_t *__restrict__ rbase, uint32_t thr, int64_t *__restrict__ gpos,
+                                                         uint32_t part, uint32_t nparts, uint64_t limit) {
     const int lane = threadIdx.x & 63;
     const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (t >= n_tiles) return;
@@ -560,10 +573,20 @@ __global__ __launch_bounds__(kBlock) void kmer_mini_walk(const uint32_t *__restr
         if constexpr (kMode == kWalkSketch) pos[o++] = p;
         else if constexpr (kMode == kWalkCount) {
             const uint64_t key = R.canonical();
-            kmer_insert<false>(table, nlines, kmer_line_of(key, nlines), key, 1u, probes, 0, ct);
+            if constexpr (!kPart) kmer_insert<false>(table, nlines, kmer_line_of(key, nlines), key, 1u, probes, 0, ct);
+            else {
+                const uint64_t hk = kmer_hash(key);
+                if (kmer_part_of_hash(hk, nparts) == part)
+                    kmer_insert<true>(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, 1u, probes, limit, ct);
+            }
         } else {
             int slot = 0;
-            KmerLine *line = kmer_find(table, nlines, R.canonical(), &slot);
+            KmerLine *line = nullptr;
+            if constexpr (!kPart) line = kmer_find(table, nlines, R.canonical(), &slot);
+            else {
+                const uint64_t key = R.canonical(), hk = kmer_hash(key);
+                if (kmer_part_of_hash(hk, nparts) == part) line = kmer_find_from(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, &slot);
+            }
             if (line && line->cnt[slot] <= thr) {
                 const uint32_t at = atomicAdd(&line->pad[slot], 1u);
                 gpos[at] = R.forward() ? base + p : base + L + (L - p - k);
@@ -652,9 +675,11 @@ __global__ __launch_bounds__(kBlock) void kmer_index_assign(KmerLine *table, con
 
 // first[i] = start of the list of the canonical form of kmers[i] in the dump's order, count[i] its length; an absent or removed
 // k-mer: -1 and 0; repetitive[i] = 1 for a removed one.  After the fill pass pad = END of the key's list.
+// kPart: the index of one partition; a key of another partition is absent, and is answered without a probe.
+template <bool kPart>
 __global__ __launch_bounds__(kBlock) void kmer_index_lookup(KmerLine *table, uint64_t nlines, int k, uint32_t thr, const uint64_t *__restrict__ kmers,
                                                             int64_t n, int64_t *__restrict__ first, int32_t *__restrict__ count,
-                                                            uint8_t *__restrict__ repetitive, KmerCounters *ct) {
+                                                            uint8_t *__restrict__ repetitive, KmerCounters *ct, uint32_t part, uint32_t nparts) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const uint64_t x = kmers[i];
@@ -662,7 +687,14 @@ __global__ __launch_bounds__(kBlock) void kmer_index_lookup(KmerLine *table, uin
     if (x >> (2 * k)) { atomicMin(&ct->bad_query, (unsigned long long)i); return; }
     const uint64_t r = kmer_revcomp(x, k);
     int slot = 0;
-    const KmerLine *L = kmer_find(table, nlines, x < r ? x : r, &slot);
+    const uint64_t key = x < r ? x : r;
+    const KmerLine *L = nullptr;
+    if constexpr (!kPart) L = kmer_find(table, nlines, key, &slot);
+    else {
+        const uint64_t hk = kmer_hash(key);
+        if (kmer_part_of_hash(hk, nparts) != part) return;
+        L = kmer_find_from(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, &slot);
+    }
     if (!L) return;
     const uint32_t c = L->cnt[slot];
     if (c > thr) { repetitive[i] = 1; return; }
@@ -702,6 +734,17 @@ struct gab_kmer {
     gab_kmer_index_result ix = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t ix_thr = 0;               // min(repetitive_frequency, 2^32 - 1): what the kernels compare the 32-bit capacities with
     float ix_ms[4] = {0, 0, 0, 0};     // sketch | count | fill | sort
+    // between gab_kmer_index_part_begin and _finish: packed, plan, mini and table (and io for the host form) hold what the stage and
+    // the capacity walk left there, and these say where; neither `counted` nor `indexed` is set meanwhile
+    struct Pending {
+        bool on = false;
+        int64_t *woff = nullptr; void *tiles = nullptr; uint32_t *packed = nullptr; unsigned long long *masks = nullptr; uint32_t *offs = nullptr;
+        int64_t *rbase = nullptr, *first_run = nullptr;
+        int64_t n_tiles = 0, n_runs = 0;
+        const int32_t *d_len = nullptr;    // the handle's staging buffer (host form) or the caller's array (device form)
+        hipStream_t stream = nullptr;
+        int64_t kept = 0, total_len = 0, minimizers = 0, distinct = 0;     // the whole call's | the partition's own
+    } pend;
 };
 
 static uint64_t table_lines(int64_t positions, int k) {
@@ -809,7 +852,7 @@ extern "C" int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max
 static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
                            const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res,
                            hipStream_t s) {
-    h->counted = false; h->indexed = false;
+    h->counted = false; h->indexed = false; h->pend.on = false;
     gab_tuning_refresh(&h->tun);
     // plan on the host: word offset of every read, tiles of the kept ones
     std::vector<int64_t> woff((size_t)n_reads + 1);
@@ -874,7 +917,7 @@ static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, co
         }
         GAB_HIP(hipEventRecord(h->ev[2], s));
         h->nlines = nlines;
-        hipLaunchKernelGGL(kmer_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+        hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
         GAB_HIP(hipEventRecord(h->ev[3], s));
         GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
         GAB_HIP(hipEventRecord(h->ev[4], s));
@@ -938,6 +981,7 @@ struct kmer_staged { char *d_seq; int64_t *d_off; int32_t *d_len; size_t span; s
 static int kmer_stage_host(gab_kmer *h, const char *fn, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, hipStream_t s,
                            kmer_staged *st) {
     int rc;
+    h->pend.on = false;                                            // (a pending partitioned index build keeps its lengths in `io`)
     int64_t lo = INT64_MAX, hi = 0;                                // the window of the slab the reads span
     for (int64_t r = 0; r < n_reads; r++) {
         GAB_CHECK(len[r] >= 0 && off[r] >= 0, "%s: read %lld has a negative offset or length", fn, (long long)r);
@@ -1095,6 +1139,10 @@ extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *
 //   one segmented sort over the lists (a removed key has an empty one)                                     "sort"
 // and one synchronisation at the end for the two sizes.  The k-mers, the starts and the sorted lists stay in h->idx, the table
 // with the END of every list in its slots stays for gab_kmer_index_lookup.
+// In key-space partitions the build is cut at the synchronisation in the middle: gab_kmer_index_part_begin is everything before it,
+// with the capacity walk and the table restricted to the keys of one partition (kmer_index_begin_impl), the caller adds up the two
+// integers of all partitions, and gab_kmer_index_part_finish is everything after it (kmer_index_layout, shared with the
+// unpartitioned build) over the partition's own keys and entries, with the threshold of the whole input.
 namespace {
 
 struct KmerMiniPlan {
@@ -1197,11 +1245,18 @@ int kmer_mini_fetch(gab_kmer *h, const char *fn, const KmerMiniDev &D, hipStream
     return GAB_OK;
 }
 
+// h->part of h->nparts (1: the unpartitioned kernel); limit: the lines a bounded capacity insert may leave
 template <int kMode>
-void kmer_mini_launch_walk(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int32_t *pos, uint32_t thr, int64_t *gpos, hipStream_t s) {
+void kmer_mini_launch_walk(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int32_t *pos, uint32_t thr, int64_t *gpos, hipStream_t s,
+                           uint64_t limit = 0) {
     if (!D.n_tiles) return;
-    hipLaunchKernelGGL(kmer_mini_walk<kMode>, dim3((unsigned)gab_ceil_div(D.n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D.packed, D.woff, d_len, D.tiles, D.n_tiles, k,
-                       D.masks, D.offs, pos, h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos);
+    const dim3 grid((unsigned)gab_ceil_div(D.n_tiles, kBlock / 64));
+    if (h->nparts == 1)
+        hipLaunchKernelGGL((kmer_mini_walk<kMode, false>), grid, dim3(kBlock), 0, s, D.packed, D.woff, d_len, D.tiles, D.n_tiles, k, D.masks, D.offs, pos,
+                           h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos, 0u, 1u, (uint64_t)0);
+    else
+        hipLaunchKernelGGL((kmer_mini_walk<kMode, kMode != kWalkSketch>), grid, dim3(kBlock), 0, s, D.packed, D.woff, d_len, D.tiles, D.n_tiles, k, D.masks, D.offs,
+                           pos, h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos, (uint32_t)h->part, (uint32_t)h->nparts, limit);
 }
 
 // d_*: device; off / len: the same two arrays on the host.  out_on_device: read_start / pos are device pointers
@@ -1211,6 +1266,7 @@ int kmer_sketch_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const in
     KmerMiniPlan P;
     KmerMiniDev D;
     int rc;
+    h->pend.on = false;                    // (the stage below overwrites what a pending partitioned index build keeps)
     if ((rc = kmer_mini_plan("gab_kmer_sketch", off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
     if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
     if ((rc = kmer_mini_fetch(h, "gab_kmer_sketch", D, s))) return rc;
@@ -1237,39 +1293,24 @@ int kmer_sketch_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const in
     return GAB_OK;
 }
 
-int kmer_index_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
-                    int64_t n_reads, int k, int window, int32_t min_len_exclusive, float rate, gab_kmer_index_result *res, hipStream_t s) {
-    const char *fn = "gab_kmer_index_minimizers";
-    h->counted = false; h->indexed = false;
-    KmerMiniPlan P;
-    KmerMiniDev D;
-    int rc;
-    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
-    // a minimizer per position at most, so the table of a count over the same reads is never more than half full
-    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
-    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
-    KmerLine *table = h->table.as<KmerLine>();
-    KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    h->nlines = nlines; h->k = k; h->part = 0; h->nparts = 1;
-
-    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
-    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
-    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
-    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
-    kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s);
-    hipLaunchKernelGGL(kmer_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
-    GAB_HIP(hipEventRecord(h->ev_ix[2], s));
-    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
-
-    // filterFrequentKmers (kmer-cnt/vertex_index.cpp:190-191) with its float operations
-    const uint64_t total = h->h_ct->ix_minimizers, unique = h->h_ct->distinct;
+// filterFrequentKmers (kmer-cnt/vertex_index.cpp:190-191) with its float operations: (size_t)(rate * mean), saturated where the float
+// has no size_t
+uint64_t kmer_repetitive(uint64_t total, uint64_t unique, float rate) {
     const float mean = (float)total / (float)(unique + 1);
     const float cut = rate * mean;
-    const uint64_t rep = cut >= 18446744073709551615.0f ? ~0ull : (uint64_t)cut;
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
-    const int64_t n = (int64_t)unique, m = (int64_t)total;
-    gab_kmer_index_result R = {P.kept, P.total_len, m, n, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
+    return cut >= 18446744073709551615.0f ? ~0ull : (uint64_t)cut;
+}
 
+// The second half of an index build, after the synchronisation that gave the host the filter's two integers: orders the n keys of
+// the table, lays out their lists (m entries before the filter), fills and sorts them.  The table holds the keys of h->part of
+// h->nparts, n and m are that partition's own, thr comes from the totals of the whole input.  Fills the last four fields of R.
+int kmer_index_layout(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int64_t n, int64_t m, uint32_t thr, gab_kmer_index_result *Rp,
+                      hipStream_t s) {
+    gab_kmer_index_result &R = *Rp;
+    KmerLine *table = h->table.as<KmerLine>();
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    const uint64_t nlines = h->nlines;
+    int rc;
     GAB_HIP(hipEventRecord(h->ev_ix[3], s));
     if (n) {
         size_t sort_bytes = 0, scan_bytes = 0, seg_bytes = 0;
@@ -1311,12 +1352,97 @@ int kmer_index_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int
         GAB_HIP(hipEventRecord(h->ev_ix[5], s));
         GAB_HIP(hipStreamSynchronize(s));
     }
-    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
-    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);
     (void)hipEventElapsedTime(&h->ix_ms[2], h->ev_ix[3], h->ev_ix[4]);
     (void)hipEventElapsedTime(&h->ix_ms[3], h->ev_ix[4], h->ev_ix[5]);
+    return GAB_OK;
+}
+
+int kmer_index_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
+                    int64_t n_reads, int k, int window, int32_t min_len_exclusive, float rate, gab_kmer_index_result *res, hipStream_t s) {
+    const char *fn = "gab_kmer_index_minimizers";
+    h->counted = false; h->indexed = false; h->pend.on = false;
+    KmerMiniPlan P;
+    KmerMiniDev D;
+    int rc;
+    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
+    // a minimizer per position at most, so the table of a count over the same reads is never more than half full
+    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
+    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    KmerLine *table = h->table.as<KmerLine>();
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    h->nlines = nlines; h->k = k; h->part = 0; h->nparts = 1; h->retried = false;
+
+    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
+    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
+    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+    kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s);
+    hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+    GAB_HIP(hipEventRecord(h->ev_ix[2], s));
+    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
+
+    const uint64_t total = h->h_ct->ix_minimizers, unique = h->h_ct->distinct;
+    const uint64_t rep = kmer_repetitive(total, unique, rate);
+    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
+    const int64_t n = (int64_t)unique, m = (int64_t)total;
+    gab_kmer_index_result R = {P.kept, P.total_len, m, n, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
+
+    if ((rc = kmer_index_layout(h, D, d_len, k, n, m, thr, &R, s))) return rc;
+    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
+    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);
     h->ix = R; h->ix_thr = thr; h->indexed = true;
     if (res) *res = R;
+    return GAB_OK;
+}
+
+// Phase 1 of a partitioned index build: stage and sketch as kmer_index_impl, then the capacities of the keys of `part` alone, in a
+// table sized for that share (the first table and its repeat: see kmer_count_impl).  Ends with the synchronisation that every
+// index build has in its middle; what it leaves in the handle is described at gab_kmer::pend.
+int kmer_index_begin_impl(gab_kmer *h, const char *fn, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
+                          const int32_t *len, int64_t n_reads, int k, int window, int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res,
+                          hipStream_t s) {
+    h->counted = false; h->indexed = false; h->pend.on = false;
+    gab_tuning_refresh(&h->tun);
+    KmerMiniPlan P;
+    KmerMiniDev D;
+    int rc;
+    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
+    uint64_t nlines = nparts > 1 && h->tun.kmer_part_floor ? 16 : part_table_lines(std::max<int64_t>(P.positions, 1), k, nparts);
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    h->k = k; h->part = part; h->nparts = nparts; h->retried = false;
+
+    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
+    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
+    for (int attempt = 0;; attempt++) {
+        if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+        KmerLine *table = h->table.as<KmerLine>();
+        h->nlines = nlines;
+        GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+        kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s, attempt ? nlines : std::min<uint64_t>(nlines, kProbeCap));
+        hipLaunchKernelGGL(kmer_reduce<true>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+        GAB_HIP(hipEventRecord(h->ev_ix[2], s));
+        if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
+        if (!h->h_ct->overflow) break;
+        GAB_CHECK(attempt == 0, "%s: internal error: a table of %llu lines for %lld positions filled up", fn, (unsigned long long)nlines, (long long)P.positions);
+        h->retried = true;
+        nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
+        KmerCounters zero = {};
+        zero.bad_read = ~0ull; zero.bad_query = ~0ull;
+        *h->h_ct = zero;
+        GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
+    }
+    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
+    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);       // (after a repeat: both attempts)
+    h->ix_ms[2] = 0; h->ix_ms[3] = 0;
+    gab_kmer::Pending &Q = h->pend;
+    Q.woff = D.woff; Q.tiles = D.tiles; Q.packed = D.packed; Q.masks = D.masks; Q.offs = D.offs; Q.rbase = D.rbase; Q.first_run = D.first_run;
+    Q.n_tiles = D.n_tiles; Q.n_runs = D.n_runs; Q.d_len = d_len; Q.stream = s;
+    Q.kept = P.kept; Q.total_len = P.total_len;
+    Q.minimizers = (int64_t)h->h_ct->total_kmers;                  // (kmer_reduce<true>: the sum of the capacities in this table)
+    Q.distinct = (int64_t)h->h_ct->distinct;
+    Q.on = true;
+    if (res) *res = gab_kmer_index_result{Q.kept, Q.total_len, Q.minimizers, Q.distinct, 0, 0, 0, 0, 0};
     return GAB_OK;
 }
 
@@ -1389,7 +1515,74 @@ extern "C" int gab_kmer_index_minimizers_device(gab_kmer *h, const char *seq, in
     return kmer_index_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, repeat_kmer_rate, res, s);
 }
 
-#define KMER_NEED_INDEX(fn) GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers on this handle")
+extern "C" int64_t gab_kmer_repetitive_frequency(int64_t minimizers, int64_t distinct, float repeat_kmer_rate) {
+    GAB_CHECK(minimizers >= 0 && distinct >= 0, "gab_kmer_repetitive_frequency: minimizers = %lld, distinct = %lld (both >= 0)", (long long)minimizers,
+              (long long)distinct);
+    int rc = kmer_check_rate(repeat_kmer_rate);
+    if (rc) return rc;
+    return (int64_t)std::min<uint64_t>(kmer_repetitive((uint64_t)minimizers, (uint64_t)distinct, repeat_kmer_rate), (uint64_t)INT64_MAX);
+}
+
+static int kmer_check_index_part(const char *fn, int part, int nparts) {
+    int rc = kmer_check_parts(fn, nparts);
+    if (rc) return rc;
+    GAB_CHECK(part >= 0 && part < nparts, "%s: part = %d, nparts = %d (0 <= part < nparts)", fn, part, nparts);
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_index_part_begin(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                                         int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res) {
+    const char *fn = "gab_kmer_index_part_begin";
+    int rc = kmer_mini_check(fn, h, off, len, n_reads, k, window);
+    if (rc || (rc = kmer_check_index_part(fn, part, nparts))) return rc;
+    gab_device_guard g(h->device);
+    hipStream_t s;
+    if ((rc = h->hs.get(&s))) return rc;
+    kmer_staged st;
+    if ((rc = kmer_stage_host(h, fn, seq, off, len, n_reads, s, &st))) return rc;
+    return kmer_index_begin_impl(h, fn, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, part, nparts,
+                                 res, s);
+}
+
+extern "C" int gab_kmer_index_part_begin_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                                                int window, int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res, void *stream) {
+    const char *fn = "gab_kmer_index_part_begin_device";
+    int rc = kmer_mini_check(fn, h, off, len, n_reads, k, window);
+    if (rc || (rc = kmer_check_index_part(fn, part, nparts))) return rc;
+    GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "%s: bad sequence slab", fn);
+    gab_device_guard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_len;
+    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
+    return kmer_index_begin_impl(h, fn, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, part, nparts, res, s);
+}
+
+// (an argument that is refused leaves the pending state as it is: the caller may call again with the right totals)
+extern "C" int gab_kmer_index_part_finish(gab_kmer *h, int64_t minimizers, int64_t distinct, float repeat_kmer_rate, gab_kmer_index_result *res) {
+    GAB_CHECK(h, "gab_kmer_index_part_finish: NULL handle");
+    GAB_CHECK(h->pend.on, "gab_kmer_index_part_finish: no pending gab_kmer_index_part_begin on this handle (each begin is finished once; any other "
+                          "count, sketch or index call in between drops it)");
+    int rc = kmer_check_rate(repeat_kmer_rate);
+    if (rc) return rc;
+    const gab_kmer::Pending &Q = h->pend;
+    GAB_CHECK(minimizers >= Q.minimizers && distinct >= Q.distinct,
+              "gab_kmer_index_part_finish: totals of %lld minimizers and %lld distinct k-mers, but this partition alone has %lld and %lld (pass the sums over ALL "
+              "partitions)", (long long)minimizers, (long long)distinct, (long long)Q.minimizers, (long long)Q.distinct);
+    GAB_CHECK(minimizers >= distinct, "gab_kmer_index_part_finish: %lld minimizers < %lld distinct k-mers", (long long)minimizers, (long long)distinct);
+    gab_device_guard g(h->device);
+    const uint64_t rep = kmer_repetitive((uint64_t)minimizers, (uint64_t)distinct, repeat_kmer_rate);
+    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
+    gab_kmer_index_result R = {Q.kept, Q.total_len, Q.minimizers, Q.distinct, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
+    KmerMiniDev D = {Q.woff, static_cast<KmerTile *>(Q.tiles), Q.packed, Q.masks, Q.offs, Q.rbase, Q.first_run, Q.n_tiles, Q.n_runs};
+    h->pend.on = false;                    // (the fill consumes the list starts: there is no second finish, and none after a failure)
+    if ((rc = kmer_index_layout(h, D, Q.d_len, h->k, Q.distinct, Q.minimizers, thr, &R, Q.stream))) return rc;
+    h->ix = R; h->ix_thr = thr; h->indexed = true;
+    if (res) *res = R;
+    return GAB_OK;
+}
+
+#define KMER_NEED_INDEX(fn) GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers (or gab_kmer_index_part_finish) on this handle")
 
 extern "C" int gab_kmer_index_dump(gab_kmer *h, uint64_t *kmers, int64_t *start, int64_t *gpos, int64_t cap_kmers, int64_t cap_entries, int64_t *nk,
                                    int64_t *ne) {
@@ -1437,8 +1630,12 @@ extern "C" int gab_kmer_index_lookup(gab_kmer *h, const uint64_t *kmers, int64_t
     h->h_ct->bad_query = ~0ull;
     GAB_HIP(hipMemcpyAsync(&d_ct->bad_query, &h->h_ct->bad_query, 8, hipMemcpyHostToDevice, s));
     GAB_HIP(hipMemcpyAsync(d_k, kmers, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kmer_index_lookup, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, h->ix_thr, d_k, n,
-                       d_first, d_count, d_rep, d_ct);
+    if (h->nparts == 1)
+        hipLaunchKernelGGL(kmer_index_lookup<false>, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, h->ix_thr,
+                           d_k, n, d_first, d_count, d_rep, d_ct, 0u, 1u);
+    else
+        hipLaunchKernelGGL(kmer_index_lookup<true>, dim3((unsigned)gab_ceil_div(n, kBlock)), dim3(kBlock), 0, s, h->table.as<KmerLine>(), h->nlines, h->k, h->ix_thr,
+                           d_k, n, d_first, d_count, d_rep, d_ct, (uint32_t)h->part, (uint32_t)h->nparts);
     GAB_HIP(hipMemcpyAsync(&h->h_ct->bad_query, &d_ct->bad_query, 8, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipMemcpyAsync(first, d_first, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1454,5 +1651,14 @@ extern "C" int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *
     if (count_ms) *count_ms = h->ix_ms[1];
     if (fill_ms) *fill_ms = h->ix_ms[2];
     if (sort_ms) *sort_ms = h->ix_ms[3];
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_index_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
+    KMER_NEED_INDEX("gab_kmer_index_last_part");
+    if (part) *part = h->part;
+    if (nparts) *nparts = h->nparts;
+    if (table_slots) *table_slots = (int64_t)(h->nlines * kSlots);
+    if (retried) *retried = h->retried ? 1 : 0;
     return GAB_OK;
 }

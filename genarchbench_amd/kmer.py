@@ -1,6 +1,7 @@
 """Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI, whole or in key-space partitions
 (include/gab.h: gab_kmer_count_part), and of the minimizer index, VertexIndex::buildIndexMinimizers (kmer-cnt/vertex_index.cpp:394-502;
-include/gab.h: gab_kmer_sketch, gab_kmer_index_minimizers)."""
+include/gab.h: gab_kmer_sketch, gab_kmer_index_minimizers), whole or in key-space partitions built in two phases
+(gab_kmer_index_part_begin / gab_kmer_index_part_finish)."""
 import ctypes as C
 import threading
 
@@ -51,6 +52,16 @@ def table_slots(positions, k, nparts):
     fn = lib().gab_kmer_table_slots
     fn.restype = C.c_int64
     n = fn(C.c_int64(positions), C.c_int(k), C.c_int(nparts))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def repetitive_frequency(minimizers, distinct, rate):
+    """the filter's threshold, (size_t)(rate * ((float)minimizers / (distinct + 1))), as the library computes it; no GPU"""
+    fn = lib().gab_kmer_repetitive_frequency
+    fn.restype = C.c_int64
+    n = fn(C.c_int64(minimizers), C.c_int64(distinct), C.c_float(rate))
     if n < 0:
         check(int(n))
     return int(n)
@@ -218,6 +229,38 @@ class KmerCounter:
                                                      C.c_float(rate), C.byref(res), C.c_void_p(stream)))
         return self._index_dict(res)
 
+    def index_part_begin(self, reads, k, window, part, nparts, min_len=5000):
+        """phase 1 of partition `part` of `nparts` of the minimizer index: sketches all reads, counts the capacities of the k-mers the
+        partition owns -> the nine fields, of which reads_kept and total_len are the whole call's, minimizers and distinct the
+        partition's own and the rest 0.  The handle is then pending until index_part_finish"""
+        seq, off, ln = self._packed(reads)
+        res = _IndexResult(*([-12345] * 9))
+        check(lib().gab_kmer_index_part_begin(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int(window), C.c_int32(min_len),
+                                              C.c_int(part), C.c_int(nparts), C.byref(res)))
+        return self._index_dict(res)
+
+    def index_part_begin_device(self, seq, off, ln, k, window, part, nparts, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: uint8 / int64 / int32; `ln` must stay alive and unchanged until index_part_finish"""
+        res = _IndexResult(*([-12345] * 9))
+        check(lib().gab_kmer_index_part_begin_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
+                                                     C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len),
+                                                     C.c_int(part), C.c_int(nparts), C.byref(res), C.c_void_p(stream)))
+        return self._index_dict(res)
+
+    def index_part_finish(self, minimizers, distinct, rate=100.0):
+        """phase 2: minimizers / distinct are the sums of phase 1 over ALL partitions -> the nine fields: repetitive_frequency is the
+        global threshold, every other count the partition's own.  The handle then holds the partition's index (index_dump,
+        index_lookup, index_last_phases, index_last_part)"""
+        res = _IndexResult(*([-12345] * 9))
+        check(lib().gab_kmer_index_part_finish(self._h, C.c_int64(minimizers), C.c_int64(distinct), C.c_float(rate), C.byref(res)))
+        return self._index_dict(res)
+
+    def index_last_part(self):
+        """what the last index build ran as: its partition, the slots of the capacity table it ended in, whether the first one filled up"""
+        part = C.c_int(-1); nparts = C.c_int(-1); slots = C.c_int64(-1); retried = C.c_int(-1)
+        check(lib().gab_kmer_index_last_part(self._h, C.byref(part), C.byref(nparts), C.byref(slots), C.byref(retried)))
+        return {"part": part.value, "nparts": nparts.value, "table_slots": slots.value, "retried": retried.value}
+
     def index_dump_into(self, kmers, start, gpos):
         """one raw gab_kmer_index_dump: (return code, needed k-mers, needed entries); start needs kmers.size + 1 of room"""
         nk = C.c_int64(-1); ne = C.c_int64(-1)
@@ -254,7 +297,8 @@ class KmerCounter:
 class KmerCounterSet:
     """One count over several GPUs without a merge: handle i, on devices[i], counts partition i of len(devices) of the key space.
     Every handle walks all reads; no handle needs anything from another.  A device may appear more than once (several partitions on
-    one card, one after the other or side by side)."""
+    one card, one after the other or side by side).  index_minimizers builds the minimizer index the same way, in two rounds around
+    the sum of the partitions' minimizers and distinct k-mers."""
 
     def __init__(self, devices):
         devices = list(devices)
@@ -324,5 +368,78 @@ class KmerCounterSet:
         """one row per partition: last_stats() and last_part() of its handle"""
         return [dict(kc.last_stats(), **kc.last_part()) for kc in self.parts]
 
+    # ---- minimizer mode: the index in key-space partitions, built in two phases ------------------------------------------------------
+    def _each(self, call):
+        """call(i) for every handle at once, one host thread per handle -> the list of results; the first exception is raised here"""
+        n = len(self.parts)
+        out = [None] * n
 
-__all__ = ["KmerCounter", "KmerCounterSet", "GabError", "pack_reads", "part_of", "table_slots", "RUN", "MAX_K", "MAX_PARTS", "MAX_WINDOW"]
+        def run(i):
+            try:
+                out[i] = call(i)
+            except Exception as e:      # (handed to the caller's thread below)
+                out[i] = e
+        threads = [threading.Thread(target=run, args=(i,)) for i in range(1, n)]
+        for t in threads:
+            t.start()
+        run(0)
+        for t in threads:
+            t.join()
+        for r in out:
+            if isinstance(r, Exception):
+                raise r
+        return out
+
+    def index_minimizers(self, reads, k, window, rate=100.0, min_len=5000):
+        """two rounds of one host thread per handle: every partition sketches all reads and counts its own capacities; the sums of
+        their minimizers and distinct k-mers give the one threshold every partition then filters with -> the nine fields of the whole
+        input"""
+        packed = KmerCounter._packed(reads)
+        n = len(self.parts)
+        begun = self._each(lambda i: self.parts[i].index_part_begin(packed, k, window, i, n, min_len))
+        minimizers = sum(r["minimizers"] for r in begun); distinct = sum(r["distinct"] for r in begun)
+        out = self._each(lambda i: self.parts[i].index_part_finish(minimizers, distinct, rate))
+        both = {f: out[0][f] for f in ("reads_kept", "total_len", "repetitive_frequency")}
+        both.update({f: sum(r[f] for r in out) for f in ("minimizers", "distinct", "filtered_kmers", "filtered_entries", "selected_kmers", "index_entries")})
+        return {f: both[f] for f, _ in _IndexResult._fields_}
+
+    def index_dump(self):
+        """-> (k-mers uint64 ascending, start int64 [nk + 1], gpos int64): the partitions' dumps merged by k-mer, start recomputed"""
+        dumps = [kc.index_dump() for kc in self.parts]
+        kmers = np.concatenate([d[0] for d in dumps])
+        lens = np.concatenate([np.diff(d[1]) for d in dumps])
+        base = np.cumsum([0] + [d[2].size for d in dumps])[:-1]
+        first = np.concatenate([d[1][:-1] + b for d, b in zip(dumps, base)])      # where every list starts in the concatenated gpos
+        gpos = np.concatenate([d[2] for d in dumps])
+        order = np.argsort(kmers, kind="stable")      # (disjoint sorted lists: a merge)
+        kmers, lens, first = kmers[order], lens[order], first[order]
+        start = np.zeros(kmers.size + 1, np.int64)
+        start[1:] = np.cumsum(lens)
+        take = np.repeat(first - start[:-1], lens) + np.arange(int(start[-1]), dtype=np.int64)
+        return kmers, start, gpos[take]
+
+    def index_lookup(self, kmers):
+        """-> (first, count, repetitive) as KmerCounter.index_lookup: count and repetitive come from the partition that owns the k-mer,
+        first is the start of its list in index_dump()'s merged gpos"""
+        kmers = np.ascontiguousarray(kmers, np.uint64)
+        first = np.full(kmers.size, -1, np.int64); count = np.zeros(kmers.size, np.int32); rep = np.zeros(kmers.size, np.uint8)
+        keys = []
+        for kc in self.parts:
+            f, c, r = kc.index_lookup(kmers)      # (another partition's k-mer: -1, 0, 0)
+            count += c; rep |= r
+            hit = np.flatnonzero(f >= 0)
+            if hit.size:      # (the canonical k-mer of every hit: list starts are strictly ascending, a kept k-mer has an entry)
+                own_kmers, own_start, _ = kc.index_dump()
+                keys.append((hit, own_kmers[np.searchsorted(own_start, f[hit])]))
+        if keys:
+            merged, start, _ = self.index_dump()
+            for hit, canon in keys:
+                first[hit] = start[np.searchsorted(merged, canon)]
+        return first, count, rep
+
+    def index_last_phases(self):
+        """one row per partition: index_last_phases() and index_last_part() of its handle"""
+        return [dict(kc.index_last_phases(), **kc.index_last_part()) for kc in self.parts]
+
+
+__all__ = ["KmerCounter", "KmerCounterSet", "GabError", "pack_reads", "part_of", "table_slots", "repetitive_frequency", "RUN", "MAX_K", "MAX_PARTS", "MAX_WINDOW"]

@@ -522,6 +522,50 @@ int gab_kmer_index_lookup(gab_kmer *h, const uint64_t *kmers, int64_t n, int64_t
  * the second and the third: that wait is in none of them. */
 int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *count_ms, float *fill_ms, float *sort_ms);
 
+/* The minimizer index in key-space partitions, one per GPU (or per call), in two phases.  The filter's threshold needs the number of
+ * minimizers and of distinct k-mers of the WHOLE input (filterFrequentKmers, kmer-cnt/vertex_index.cpp:178-217) before any list is
+ * laid out, so the partitions meet in the middle of the build -- on the host, through two integers each:
+ *   1. gab_kmer_index_part_begin on every partition: it sketches ALL reads (the sketch is replicated: a split by reads would need
+ *      minimizers exchanged between GPUs, and this library has no collective) and counts the capacities of the k-mers it owns
+ *      (ownership: gab_kmer_part_of, the same split as gab_kmer_count_part), in a table sized for that share;
+ *   2. the caller adds up `minimizers` and `distinct` of all partitions;
+ *   3. gab_kmer_index_part_finish on every partition with those sums: it filters with the GLOBAL threshold, then lays out, fills and
+ *      sorts the lists of its own k-mers.
+ * The partitions are disjoint: their dumps, merged by k-mer, are gab_kmer_index_minimizers' index of the same input bit for bit, and
+ * minimizers, distinct, filtered_kmers, filtered_entries, selected_kmers and index_entries add up to its fields.  No call needs
+ * anything from another but the two sums.  nparts = 1: begin(0 of 1) and finish with its own two numbers are
+ * gab_kmer_index_minimizers. */
+/* (size_t)(rate * ((float)minimizers / (distinct + 1))) in the reference's C float arithmetic (kmer-cnt/vertex_index.cpp:190-191),
+ * saturated as gab_kmer_index_minimizers saturates it (at INT64_MAX): the ONE place the threshold is computed, for library, driver and
+ * mirror.  Plain host arithmetic, no GPU needed.  A negative count or a rate that is negative or not finite -> GAB_EINVAL. */
+int64_t gab_kmer_repetitive_frequency(int64_t minimizers, int64_t distinct, float repeat_kmer_rate);
+/* Phase 1 of partition `part` of `nparts`.  Arguments as gab_kmer_index_minimizers / _device and gab_kmer_count_part; synchronises.
+ * res: reads_kept and total_len of the whole call, the same on every partition; minimizers and distinct of the partition's OWN
+ * k-mers (over the partitions minimizers adds up to what gab_kmer_sketch emits); the other five fields are 0.  The handle is then
+ * PENDING: it keeps the packed reads, the sketch and the partition's capacity table for phase 2; it is neither counted nor
+ * indexed, so every gab_kmer_* accessor of a count or an index returns GAB_EINVAL, and any gab_kmer_count*, gab_kmer_sketch*,
+ * gab_kmer_index_minimizers* or another begin drops the pending state.  Device form: the caller's `len` array and `stream` must
+ * stay valid and unchanged until gab_kmer_index_part_finish, which runs on that stream.  The first table is a forecast of the
+ * partition's share, as for gab_kmer_count_part: should it fill up, the capacity pass runs once more in the unpartitioned table
+ * size (gab_kmer_index_last_part). */
+int gab_kmer_index_part_begin(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
+                              int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res);
+int gab_kmer_index_part_begin_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads,
+                                     int k, int window, int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res, void *stream);
+/* Phase 2: minimizers / distinct = the sums of phase 1 over ALL partitions; the threshold is
+ * gab_kmer_repetitive_frequency(minimizers, distinct, repeat_kmer_rate).  res: reads_kept and total_len of the whole call,
+ * minimizers and distinct of the partition's own k-mers, repetitive_frequency the global value (the same on every partition),
+ * filtered_kmers, filtered_entries, selected_kmers and index_entries of the partition's own k-mers.  Afterwards the handle holds the
+ * partition's index: gab_kmer_index_dump returns its k-mers ascending with their ascending lists, gab_kmer_index_lookup answers for a
+ * k-mer it owns and returns first -1, count 0, repetitive 0 for any k-mer of another partition, gab_kmer_index_last_phases returns
+ * sketch | count of phase 1 and fill | sort of phase 2.  GAB_EINVAL: no pending begin on the handle (also a second finish: the fill
+ * consumed the list starts), a bad rate, totals smaller than the partition's own numbers, minimizers < distinct; a refused argument
+ * leaves the handle pending. */
+int gab_kmer_index_part_finish(gab_kmer *h, int64_t minimizers, int64_t distinct, float repeat_kmer_rate, gab_kmer_index_result *res);
+/* what the last index build ran as (cf. gab_kmer_last_part): its partition (0 of 1 after gab_kmer_index_minimizers), the slots of the
+ * capacity table it ended in, and whether the capacity pass was repeated (0 / 1) */
+int gab_kmer_index_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried);
+
 /* ---- input parsers ---------------------------------------------------------
  * The reference drivers parse their text inputs on the host, line by line, outside the region of interest
  * (bsw: loadPairs, bsw/src/main_banded.cpp:164-206 -- fgets + sscanf per pair; bpm / wfa: getline per line,

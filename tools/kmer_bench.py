@@ -21,6 +21,13 @@ what extraction alone costs: the floor no number of GPUs gets under.
 the same reads, resident, for k = 17 and 15: the nine result fields, k-mer positions per second over the wall time of the call
 (median of the warm repeats; the call synchronises twice, once for the filter's two integers) and the device time of its four
 stages -- sketch, capacity count, fill, segmented sort.
+
+--minimizers W --parts N[,N...]: for every N, the index in N key-space partitions (gab_kmer_index_part_begin_device /
+gab_kmer_index_part_finish), every partition's two phases run in turn on the one GPU, each on a handle of its own: per partition the
+wall time of its begin and of its finish (medians of the warm repeats) and the device time of its stages.  The two phases of N
+GPUs are two rounds with the host's sum in between, so the ONE-GPU FORECAST of the N-GPU wall time is the slowest begin plus the
+slowest finish -- not a measurement of one (no second card, no shared host link).  --check compares the merged dumps with the
+unpartitioned index.
 """
 import argparse
 import json
@@ -61,6 +68,56 @@ def write_fasta(path, reads):
     with open(path, "wb") as f:
         for i, r in enumerate(reads):
             f.write(b">r%d\n%s\n" % (i, r))
+
+
+def index_parts(a, reads, d_seq, d_off, d_len):
+    """--minimizers W --parts ...: see the head of this file"""
+    from genarchbench_amd.kmer import KmerCounter, KmerCounterSet
+    out = {}
+    whole = KmerCounter() if a.check else None
+    for nparts in [int(x) for x in a.parts.split(",")]:
+        ks = KmerCounterSet([0] * nparts)
+        ks.reserve(len(reads), int(d_seq.numel()))
+        per_k = {}
+        for k in (17, 15):
+            begin_s = [[] for _ in range(nparts)]; finish_s = [[] for _ in range(nparts)]; phases = [[] for _ in range(nparts)]
+            for it in range(a.warmup + a.repeats):
+                begun = []
+                for p, kc in enumerate(ks.parts):
+                    t0 = time.perf_counter()
+                    begun.append(kc.index_part_begin_device(d_seq, d_off, d_len, k, a.minimizers, p, nparts))
+                    if it >= a.warmup:
+                        begin_s[p].append(time.perf_counter() - t0)
+                m = sum(b["minimizers"] for b in begun); n = sum(b["distinct"] for b in begun)
+                done = []
+                for p, kc in enumerate(ks.parts):
+                    t0 = time.perf_counter()
+                    done.append(kc.index_part_finish(m, n, a.rate))
+                    if it >= a.warmup:
+                        finish_s[p].append(time.perf_counter() - t0)
+                        phases[p].append(kc.index_last_phases())
+            rows = []
+            for p, kc in enumerate(ks.parts):
+                row = {"part": p, "begin_seconds": statistics.median(begin_s[p]), "finish_seconds": statistics.median(finish_s[p]),
+                       "minimizers": done[p]["minimizers"], "distinct": done[p]["distinct"], "index_entries": done[p]["index_entries"]}
+                for f in ("sketch_ms", "count_ms", "fill_ms", "sort_ms"):
+                    row[f] = statistics.median(s[f] for s in phases[p])
+                row.update({f: v for f, v in kc.index_last_part().items() if f in ("table_slots", "retried")})
+                rows.append(row)
+            forecast = max(r["begin_seconds"] for r in rows) + max(r["finish_seconds"] for r in rows)
+            sums = {f: sum(d[f] for d in done) for f in ("minimizers", "distinct", "filtered_kmers", "filtered_entries", "selected_kmers", "index_entries")}
+            per_k[str(k)] = {"partitions": rows, "sums": dict(sums, repetitive_frequency=done[0]["repetitive_frequency"]),
+                             "slowest_begin_seconds": max(r["begin_seconds"] for r in rows), "slowest_finish_seconds": max(r["finish_seconds"] for r in rows),
+                             "forecast_seconds": forecast}
+            if a.check:
+                want = whole.index_minimizers_device(d_seq, d_off, d_len, k, a.minimizers, a.rate)
+                got = dict(sums, reads_kept=done[0]["reads_kept"], total_len=done[0]["total_len"], repetitive_frequency=done[0]["repetitive_frequency"])
+                per_k[str(k)]["matches_unpartitioned"] = bool(got == want and all(np.array_equal(x, y) for x, y in zip(ks.index_dump(), whole.index_dump())))
+        ks.close()
+        out[str(nparts)] = per_k
+    if whole:
+        whole.close()
+    return out
 
 
 def main():
@@ -109,7 +166,7 @@ def main():
                 if rec:
                     row["matches_reference_record"] = all(res[f] == rec[f] for f in ("repetitive_frequency", "filtered_entries", "selected_kmers",
                                                                                      "index_entries"))
-            if a.check:
+            if a.check and not a.parts:      # (with --parts, --check compares the merged partitions with this build instead)
                 from tests import minimizer_model
                 m = minimizer_model.build_index(reads, k, a.minimizers, a.rate)
                 row["matches_model"] = all(res[f] == m[f] for f in minimizer_model.FIELDS)
@@ -145,7 +202,9 @@ def main():
                 m = kmer_model.model(reads, k)
                 row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
             out["k"][str(k)] = row
-    if a.parts:
+    if a.parts and a.minimizers:
+        out["index_parts"] = index_parts(a, reads, d_seq, d_off, d_len)
+    elif a.parts:
         out["parts"] = {}
         for nparts in [int(x) for x in a.parts.split(",")]:
             kc.reserve_part(len(reads), seq.size, nparts)
