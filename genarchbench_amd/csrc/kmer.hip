@@ -85,6 +85,62 @@ __host__ __device__ __forceinline__ uint32_t kmer_part_of_hash(uint64_t h, uint3
 __host__ __device__ __forceinline__ uint64_t kmer_line_of_hash(uint64_t h, uint32_t nparts, uint64_t nlines) { return kmer_mulhi(h * nparts, nlines); }
 __device__ __forceinline__ uint64_t kmer_line_of(uint64_t key, uint64_t nlines) { return __umul64hi(kmer_hash(key), nlines); }
 
+// The one partition rule: does the table of `part` of `nparts` own the canonical k-mer `key`, and which of its nlines lines is the
+// key's home?  One hash answers both.  kPart = false: the whole key space in one table; part and nparts are not read.
+// (No early return for another partition's key: the compiler sinks the line's product below the caller's test either way, and in
+// this shape the callers keep the registers they had.)
+template <bool kPart>
+__device__ __forceinline__ bool kmer_home(uint64_t key, uint32_t part, uint32_t nparts, uint64_t nlines, uint64_t *line) {
+    if constexpr (!kPart) *line = kmer_line_of(key, nlines);
+    else {
+        const uint64_t h = kmer_hash(key);
+        *line = kmer_line_of_hash(h, nparts, nlines);
+        return kmer_part_of_hash(h, nparts) == part;
+    }
+    return true;
+}
+
+// ---- the rolling forward / reverse-complement words of a read (one shift-or each per base): seek(p), then every step() gives the
+// k-mer at p, p + 1, ...
+struct KmerRoller {
+    const uint32_t *words;
+    uint64_t mask, fw, rc;
+    int top, k;
+    int32_t b;                             // next base to take in
+    uint32_t w;
+    __device__ __forceinline__ KmerRoller(const uint32_t *words_, int k_)
+        : words(words_), mask((1ull << (2 * k_)) - 1ull), fw(0), rc(0), top(2 * (k_ - 1)), k(k_), b(0), w(0) {}
+    __device__ __forceinline__ uint64_t take() {
+        const uint64_t c = w & 3u;
+        b++;
+        w >>= 2;
+        if ((b & 15) == 0) w = words[b >> 4];      // (the last base taken belongs to position L - k - 1 and is base L - 2, so b <= L - 1: a word of the read)
+        return c;
+    }
+    __device__ __forceinline__ void seek(int32_t p) {
+        fw = 0; rc = 0; b = p;
+        w = words[b >> 4] >> (2 * (b & 15));
+        for (int j = 0; j < k - 1; j++) {
+            const uint64_t c = take();
+            fw = (fw << 2) | c;
+            rc = (rc >> 2) | ((3ull - c) << top);
+        }
+    }
+    __device__ __forceinline__ void step() {
+        const uint64_t c = take();
+        fw = ((fw << 2) | c) & mask;
+        rc = (rc >> 2) | ((3ull - c) << top);
+    }
+    // from the k-mer at q + 1 to the k-mer at q (the cursor of take() stays where it is)
+    __device__ __forceinline__ void back(int32_t q) {
+        const uint64_t c = (words[q >> 4] >> (2 * (q & 15))) & 3u;
+        fw = (fw >> 2) | (c << top);
+        rc = ((rc << 2) | (3ull - c)) & mask;
+    }
+    __device__ __forceinline__ uint64_t canonical() const { return fw < rc ? fw : rc; }
+    __device__ __forceinline__ bool forward() const { return fw <= rc; }      // palindromes are not flipped (kmer-cnt/kmer.h:54-63)
+};
+
 // ---- pack: thread = one output word of one read ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void kmer_pack(const char *__restrict__ seq, const int64_t *__restrict__ off, const int32_t *__restrict__ len,
                                                     const int64_t *__restrict__ woff, int64_t n_reads, int64_t n_words,
@@ -168,41 +224,19 @@ __global__ __launch_bounds__(kBlock) void kmer_count(const uint32_t *__restrict_
         const int32_t p0 = tile.start + lane * kRun;
         const int32_t p1 = min(p0 + kRun, npos);
         if (p0 < p1) {
-            const uint32_t *words = packed + woff[tile.read];
-            const uint64_t mask = (1ull << (2 * k)) - 1ull;
-            const int top = 2 * (k - 1);
-            uint64_t fw = 0, rc = 0;
-            int32_t b = p0;                                        // next base to take in
-            uint32_t w = words[b >> 4] >> (2 * (b & 15));
-            auto next_base = [&]() -> uint64_t {
-                const uint64_t c = w & 3u;
-                b++;
-                w >>= 2;
-                if ((b & 15) == 0) w = words[b >> 4];              // (the last base taken is p1 + k - 2 <= L - 2, so b <= L - 1: a word of the read)
-                return c;
-            };
-            for (int j = 0; j < k - 1; j++) {
-                const uint64_t c = next_base();
-                fw = (fw << 2) | c;
-                rc = (rc >> 2) | ((3ull - c) << top);
-            }
+            KmerRoller R(packed + woff[tile.read], k);
+            R.seek(p0);
             uint64_t cur = ~0ull;
             uint32_t n = 0;
             auto flush = [&]() {
-                if constexpr (!kPart) kmer_insert<false>(table, nlines, kmer_line_of(cur, nlines), cur, n, probes, 0, ct);
-                else {
-                    const uint64_t h = kmer_hash(cur);
-                    if (kmer_part_of_hash(h, nparts) == part) {
-                        merged += n - 1;
-                        kmer_insert<true>(table, nlines, kmer_line_of_hash(h, nparts, nlines), cur, n, probes, limit, ct);
-                    }
-                }
+                uint64_t line;
+                if (!kmer_home<kPart>(cur, part, nparts, nlines, &line)) return;
+                if constexpr (kPart) merged += n - 1;
+                kmer_insert<kPart>(table, nlines, line, cur, n, probes, limit, ct);
             };
             for (int32_t p = p0; p < p1; p++) {
-                const uint64_t c = next_base();
-                fw = ((fw << 2) | c) & mask;
-                rc = (rc >> 2) | ((3ull - c) << top);
-                const uint64_t key = fw < rc ? fw : rc;
+                R.step();
+                const uint64_t key = R.canonical();
                 if (key == cur) { n++; if constexpr (!kPart) merged++; }
                 else {
                     if (n) flush();
@@ -278,6 +312,29 @@ __global__ __launch_bounds__(kBlock) void kmer_spectrum(const KmerLine *__restri
         if (lds[j]) atomicAdd(&hist[j], (unsigned long long)lds[j]);      // (lds[j] != 0 only for j < nbins)
 }
 
+// the slot of a key that is in the table, const or not (nullptr if it is not: the walk ends at an empty slot -- a line's taken slots
+// are a prefix -- and the table is at most half full; a partition's table may hold no empty slot near this line, or none at all, so
+// nlines lines at most).  line: the key's home line (kmer_home)
+template <class Line>
+__device__ __forceinline__ Line *kmer_find(Line *table, uint64_t nlines, uint64_t line, uint64_t key, int *slot) {
+    const unsigned long long stored = key + 1;
+    for (uint64_t visited = 0; visited < nlines; visited++) {
+        Line *L = table + line;
+        int match = -1;
+        bool end = false;
+#pragma unroll
+        for (int s = kSlots - 1; s >= 0; s--) {
+            const unsigned long long v = L->key[s];
+            if (v == stored) match = s;
+            if (v == 0) end = true;
+        }
+        if (match >= 0) { *slot = match; return L; }
+        if (end) return nullptr;
+        line = line + 1 == nlines ? 0 : line + 1;
+    }
+    return nullptr;
+}
+
 // ---- query -------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t kmer_revcomp(uint64_t x, int k) {
     x = ~x;
@@ -294,25 +351,12 @@ __global__ __launch_bounds__(kBlock) void kmer_query(const KmerLine *__restrict_
     const uint64_t x = kmers[i];
     if (x >> (2 * k)) { counts[i] = 0; atomicMin(&ct->bad_query, (unsigned long long)i); return; }
     const uint64_t r = kmer_revcomp(x, k);
-    const unsigned long long stored = (x < r ? x : r) + 1;
-    const uint64_t h = kmer_hash(stored - 1);
-    if (kmer_part_of_hash(h, nparts) != part) { counts[i] = 0; return; }       // another partition's key
-    uint64_t line = kmer_line_of_hash(h, nparts, nlines);
-    uint32_t c = 0;
-    // (the walk ends at an empty slot; a partition's table may hold no empty slot near this line, or none at all: nlines lines at most)
-    for (uint64_t visited = 0; visited < nlines; visited++) {
-        const KmerLine *L = table + line;
-        bool done = false;
-#pragma unroll
-        for (int s = 0; s < kSlots; s++) {
-            const unsigned long long v = L->key[s];
-            if (!done && v == stored) { c = L->cnt[s]; done = true; }
-            if (v == 0) done = true;
-        }
-        if (done) break;
-        line = line + 1 == nlines ? 0 : line + 1;
-    }
-    counts[i] = c;
+    const uint64_t key = x < r ? x : r;
+    uint64_t line;
+    int slot = 0;
+    const KmerLine *L = nullptr;               // (another partition's key is answered without a probe)
+    if (kmer_home<true>(key, part, nparts, nlines, &line)) L = kmer_find(table, nlines, line, key, &slot);
+    counts[i] = L ? L->cnt[slot] : 0;
 }
 
 // ---- dump: the taken slots, unordered; sorted afterwards ---------------------------------------------------------------------------------
@@ -370,46 +414,6 @@ __host__ __device__ __forceinline__ uint64_t kmer_order_key(uint64_t x) {      /
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-
-// the rolling forward / reverse-complement words of kmer_count as an object: seek(p), then every step() gives the k-mer at p, p + 1, ...
-struct KmerRoller {
-    const uint32_t *words;
-    uint64_t mask, fw, rc;
-    int top, k;
-    int32_t b;                             // next base to take in
-    uint32_t w;
-    __device__ __forceinline__ KmerRoller(const uint32_t *words_, int k_)
-        : words(words_), mask((1ull << (2 * k_)) - 1ull), fw(0), rc(0), top(2 * (k_ - 1)), k(k_), b(0), w(0) {}
-    __device__ __forceinline__ uint64_t take() {
-        const uint64_t c = w & 3u;
-        b++;
-        w >>= 2;
-        if ((b & 15) == 0) w = words[b >> 4];      // (the last base taken belongs to position L - k - 1 and is base L - 2, so b <= L - 1: a word of the read)
-        return c;
-    }
-    __device__ __forceinline__ void seek(int32_t p) {
-        fw = 0; rc = 0; b = p;
-        w = words[b >> 4] >> (2 * (b & 15));
-        for (int j = 0; j < k - 1; j++) {
-            const uint64_t c = take();
-            fw = (fw << 2) | c;
-            rc = (rc >> 2) | ((3ull - c) << top);
-        }
-    }
-    __device__ __forceinline__ void step() {
-        const uint64_t c = take();
-        fw = ((fw << 2) | c) & mask;
-        rc = (rc >> 2) | ((3ull - c) << top);
-    }
-    // from the k-mer at q + 1 to the k-mer at q (the cursor of take() stays where it is)
-    __device__ __forceinline__ void back(int32_t q) {
-        const uint64_t c = (words[q >> 4] >> (2 * (q & 15))) & 3u;
-        fw = (fw >> 2) | (c << top);
-        rc = ((rc << 2) | (3ull - c)) & mask;
-    }
-    __device__ __forceinline__ uint64_t canonical() const { return fw < rc ? fw : rc; }
-    __device__ __forceinline__ bool forward() const { return fw <= rc; }      // palindromes are not flipped (kmer-cnt/kmer.h:54-63)
-};
 
 struct KmerWindowMin { uint64_t m; int32_t first, last; };      // the minimum order key of a window, its first and last position
 // re-rolls positions lo .. hi; fw_lo / rc_lo: the two words of the k-mer at lo
@@ -509,30 +513,6 @@ struct KmerPopc {
     }
 };
 
-// the slot of a key that is in the table (nullptr if it is not: the walk ends at an empty slot, the table is at most half full)
-// (line: the key's home line, kmer_line_of in the whole table, kmer_line_of_hash in a partition's)
-__device__ __forceinline__ KmerLine *kmer_find_from(KmerLine *table, uint64_t nlines, uint64_t line, uint64_t key, int *slot) {
-    const unsigned long long stored = key + 1;
-    for (uint64_t visited = 0; visited < nlines; visited++) {
-        KmerLine *L = table + line;
-        int match = -1;
-        bool end = false;
-#pragma unroll
-        for (int s = kSlots - 1; s >= 0; s--) {
-            const unsigned long long v = L->key[s];
-            if (v == stored) match = s;
-            if (v == 0) end = true;
-        }
-        if (match >= 0) { *slot = match; return L; }
-        if (end) return nullptr;
-        line = line + 1 == nlines ? 0 : line + 1;
-    }
-    return nullptr;
-}
-__device__ __forceinline__ KmerLine *kmer_find(KmerLine *table, uint64_t nlines, uint64_t key, int *slot) {
-    return kmer_find_from(table, nlines, kmer_line_of(key, nlines), key, slot);
-}
-
 // The second walk over the reads: a lane re-rolls its run from its first marked position to its last and does one of three things
 // with every minimizer.  offs: exclusive scan of the popcounts of masks.
 enum { kWalkSketch = 0, kWalkCount = 1, kWalkFill = 2 };
@@ -573,20 +553,14 @@ __global__ __launch_bounds__(kBlock) void kmer_mini_walk(const uint32_t *__restr
         if constexpr (kMode == kWalkSketch) pos[o++] = p;
         else if constexpr (kMode == kWalkCount) {
             const uint64_t key = R.canonical();
-            if constexpr (!kPart) kmer_insert<false>(table, nlines, kmer_line_of(key, nlines), key, 1u, probes, 0, ct);
-            else {
-                const uint64_t hk = kmer_hash(key);
-                if (kmer_part_of_hash(hk, nparts) == part)
-                    kmer_insert<true>(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, 1u, probes, limit, ct);
-            }
+            uint64_t home;
+            if (kmer_home<kPart>(key, part, nparts, nlines, &home)) kmer_insert<kPart>(table, nlines, home, key, 1u, probes, limit, ct);
         } else {
+            const uint64_t key = R.canonical();
+            uint64_t home;
             int slot = 0;
             KmerLine *line = nullptr;
-            if constexpr (!kPart) line = kmer_find(table, nlines, R.canonical(), &slot);
-            else {
-                const uint64_t key = R.canonical(), hk = kmer_hash(key);
-                if (kmer_part_of_hash(hk, nparts) == part) line = kmer_find_from(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, &slot);
-            }
+            if (kmer_home<kPart>(key, part, nparts, nlines, &home)) line = kmer_find(table, nlines, home, key, &slot);
             if (line && line->cnt[slot] <= thr) {
                 const uint32_t at = atomicAdd(&line->pad[slot], 1u);
                 gpos[at] = R.forward() ? base + p : base + L + (L - p - k);
@@ -688,19 +662,20 @@ __global__ __launch_bounds__(kBlock) void kmer_index_lookup(KmerLine *table, uin
     const uint64_t r = kmer_revcomp(x, k);
     int slot = 0;
     const uint64_t key = x < r ? x : r;
-    const KmerLine *L = nullptr;
-    if constexpr (!kPart) L = kmer_find(table, nlines, key, &slot);
-    else {
-        const uint64_t hk = kmer_hash(key);
-        if (kmer_part_of_hash(hk, nparts) != part) return;
-        L = kmer_find_from(table, nlines, kmer_line_of_hash(hk, nparts, nlines), key, &slot);
-    }
+    uint64_t line;
+    if (!kmer_home<kPart>(key, part, nparts, nlines, &line)) return;
+    const KmerLine *L = kmer_find(table, nlines, line, key, &slot);
     if (!L) return;
     const uint32_t c = L->cnt[slot];
     if (c > thr) { repetitive[i] = 1; return; }
     first[i] = (int64_t)(L->pad[slot] - c);
     count[i] = (int32_t)c;
 }
+
+struct KmerDev {           // where the stage put things (kmer_stage: the first line; kmer_mini_stage: all of it)
+    int64_t *woff; KmerTile *tiles; uint32_t *packed; int64_t n_tiles, n_runs;
+    unsigned long long *masks; uint32_t *offs; int64_t *rbase, *first_run;
+};
 
 }  // namespace
 
@@ -714,7 +689,7 @@ struct gab_kmer {
     gab_devbuf table;
     gab_devbuf ct;          // KmerCounters
     gab_devbuf aux;         // spectrum bins, query staging, dump keys / counts and the sort's scratch
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // start | packed | counted | reduced | end
+    hipEvent_t ev[11] = {};            // count: start | packed | counted | reduced | end; then the six of the index (ev_ix)
     KmerCounters *h_ct = nullptr;      // pinned
     bool counted = false;              // the table of a finished count is in the handle
     int k = 0;
@@ -729,7 +704,7 @@ struct gab_kmer {
     // minimizer index (gab_kmer_index_minimizers): it takes the table over, so `counted` and `indexed` are never both set
     gab_devbuf mini;        // sketch: bitmap of the minimizers | its scan | per-read bases
     gab_devbuf idx;         // the index of the last build: k-mers | starts | global positions
-    hipEvent_t ev_ix[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // start | sketched | counted | resumed | filled | sorted
+    hipEvent_t *const ev_ix = ev + 5;  // start | sketched | counted | resumed | filled | sorted
     bool indexed = false;
     gab_kmer_index_result ix = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t ix_thr = 0;               // min(repetitive_frequency, 2^32 - 1): what the kernels compare the 32-bit capacities with
@@ -738,9 +713,7 @@ struct gab_kmer {
     // the capacity walk left there, and these say where; neither `counted` nor `indexed` is set meanwhile
     struct Pending {
         bool on = false;
-        int64_t *woff = nullptr; void *tiles = nullptr; uint32_t *packed = nullptr; unsigned long long *masks = nullptr; uint32_t *offs = nullptr;
-        int64_t *rbase = nullptr, *first_run = nullptr;
-        int64_t n_tiles = 0, n_runs = 0;
+        KmerDev dev = {};
         const int32_t *d_len = nullptr;    // the handle's staging buffer (host form) or the caller's array (device form)
         hipStream_t stream = nullptr;
         int64_t kept = 0, total_len = 0, minimizers = 0, distinct = 0;     // the whole call's | the partition's own
@@ -782,10 +755,8 @@ extern "C" int gab_kmer_create(int device, gab_kmer **out) {
     gab_kmer *h = new (std::nothrow) gab_kmer();
     if (!h) { gab_set_error("out of host memory"); return GAB_ENOMEM; }
     h->device = device;
-    for (int i = 0; i < 5; i++)
-        if (hipEventCreate(&h->ev[i]) != hipSuccess) { gab_set_error("hipEventCreate failed"); gab_kmer_destroy(h); return GAB_EDEVICE; }
-    for (int i = 0; i < 6; i++)
-        if (hipEventCreate(&h->ev_ix[i]) != hipSuccess) { gab_set_error("hipEventCreate failed"); gab_kmer_destroy(h); return GAB_EDEVICE; }
+    for (hipEvent_t &e : h->ev)
+        if (hipEventCreate(&e) != hipSuccess) { gab_set_error("hipEventCreate failed"); gab_kmer_destroy(h); return GAB_EDEVICE; }
     if (hipHostMalloc((void **)&h->h_ct, sizeof(KmerCounters)) != hipSuccess) {
         h->h_ct = nullptr; gab_set_error("hipHostMalloc failed"); gab_kmer_destroy(h); return GAB_ENOMEM;
     }
@@ -801,8 +772,7 @@ extern "C" void gab_kmer_destroy(gab_kmer *h) {
     gab_device_guard g(h->device);
     h->io.release(); h->packed.release(); h->plan.release(); h->table.release(); h->ct.release(); h->aux.release(); h->mini.release(); h->idx.release();
     h->hs.release();
-    for (int i = 0; i < 5; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    for (int i = 0; i < 6; i++) if (h->ev_ix[i]) (void)hipEventDestroy(h->ev_ix[i]);
+    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->h_ct) (void)hipHostFree(h->h_ct);
     delete h;
 }
@@ -847,77 +817,191 @@ extern "C" int gab_kmer_reserve_part(gab_kmer *h, int64_t max_reads, int64_t max
     return gab_warm_copy_engines(s, h->io.p, h->io.cap);
 }
 
-// d_*: device; off / len: the same two arrays on the host
-// part / nparts: the partition of the key space this call counts (0 / 1: all of it, in the unpartitioned kernel)
-static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
-                           const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res,
-                           hipStream_t s) {
-    h->counted = false; h->indexed = false; h->pend.on = false;
-    gab_tuning_refresh(&h->tun);
-    // plan on the host: word offset of every read, tiles of the kept ones
-    std::vector<int64_t> woff((size_t)n_reads + 1);
-    std::vector<KmerTile> tiles;
-    int64_t words = 0, positions = 0, kept = 0;
-    GAB_CHECK(n_reads < (1ll << 31), "gab_kmer_count: %lld reads in one call (limit 2^31)", (long long)n_reads);
+// ---- the front half of every call: input, plan, stage, first table ---------------------------------------------------------------------
+namespace {
+
+// The reads of one call.  d_*: device; off / len: the same two arrays on the host.
+struct KmerInput {
+    const char *d_seq = nullptr; int64_t seq_bytes = 0;
+    const int64_t *d_off = nullptr; const int32_t *d_len = nullptr;
+    const int64_t *off = nullptr; const int32_t *len = nullptr;
+    int64_t n_reads = 0;
+    hipStream_t stream = nullptr;
+    std::vector<int64_t> h_off;            // owner of `off` (host form: the offsets relative to the staged window) ...
+    std::vector<int32_t> h_len;            // ... and, in the device form, of `len`
+};
+
+// The host-pointer entry points: on the handle's stream, the window of the slab that the reads span, their offsets relative to it
+// and their lengths go into the handle's staging buffer.
+int kmer_input_host(gab_kmer *h, const char *fn, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, KmerInput *in) {
+    int rc;
+    hipStream_t s;
+    if ((rc = h->hs.get(&s))) return rc;
+    h->pend.on = false;                                            // (a pending partitioned index build keeps its lengths in `io`)
+    int64_t lo = INT64_MAX, hi = 0;                                // the window of the slab the reads span
     for (int64_t r = 0; r < n_reads; r++) {
-        GAB_CHECK(len[r] >= 0 && off[r] >= 0 && off[r] + len[r] <= seq_bytes,
-                  "gab_kmer_count: read %lld (offset %lld, length %d) lies outside the %lld sequence bytes", (long long)r, (long long)off[r], (int)len[r],
-                  (long long)seq_bytes);
-        woff[(size_t)r] = words;
-        words += ((int64_t)len[r] + 15) / 16;
+        GAB_CHECK(len[r] >= 0 && off[r] >= 0, "%s: read %lld has a negative offset or length", fn, (long long)r);
+        if (len[r] == 0) continue;
+        lo = std::min(lo, off[r]); hi = std::max(hi, off[r] + len[r]);
+    }
+    if (hi == 0) lo = 0;
+    GAB_CHECK(seq || hi == 0, "%s: NULL sequence slab", fn);
+    const size_t span = (size_t)(hi - lo);
+    const size_t off_at = align256(span + 64), len_at = off_at + align256((size_t)n_reads * 8);
+    if ((rc = h->io.reserve(len_at + align256((size_t)n_reads * 4)))) return rc;
+    char *d_seq = h->io.as<char>();
+    int64_t *d_off = reinterpret_cast<int64_t *>(d_seq + off_at);
+    int32_t *d_len = reinterpret_cast<int32_t *>(d_seq + len_at);
+    std::vector<int64_t> &rel = in->h_off;
+    rel.assign((size_t)n_reads, 0);
+    for (int64_t r = 0; r < n_reads; r++) rel[(size_t)r] = len[r] ? off[r] - lo : 0;
+    {
+        std::lock_guard<std::mutex> lk(gab_h2d_mutex(h->device));
+        if (span) GAB_HIP(hipMemcpyAsync(d_seq, seq + lo, span, hipMemcpyHostToDevice, s));
+        if (n_reads) {
+            GAB_HIP(hipMemcpyAsync(d_off, rel.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, s));
+            GAB_HIP(hipMemcpyAsync(d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
+        }
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    in->d_seq = d_seq; in->seq_bytes = (int64_t)span; in->d_off = d_off; in->d_len = d_len;
+    in->off = rel.data(); in->len = len; in->n_reads = n_reads; in->stream = s;
+    return GAB_OK;
+}
+
+// The device-pointer entry points: everything stays where it is, on the caller's stream; the plan needs off and len on the host.
+int kmer_input_device(const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, void *stream, KmerInput *in) {
+    hipStream_t s = (hipStream_t)stream;
+    in->h_off.resize((size_t)n_reads); in->h_len.resize((size_t)n_reads);
+    if (n_reads) {
+        GAB_HIP(hipMemcpyAsync(in->h_off.data(), off, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipMemcpyAsync(in->h_len.data(), len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    in->d_seq = seq; in->seq_bytes = seq_bytes; in->d_off = off; in->d_len = len;
+    in->off = in->h_off.data(); in->len = in->h_len.data(); in->n_reads = n_reads; in->stream = s;
+    return GAB_OK;
+}
+
+// The plan of a call, made on the host: the word offset of every read, the tiles of the kept ones, and what the minimizer paths
+// need on top of that.
+struct KmerPlan {
+    std::vector<int64_t> woff, rbase, first_run;   // word offset | 2 S_i of a kept read | runs before the read (n_reads + 1)
+    std::vector<KmerTile> tiles;
+    int64_t words = 0, positions = 0, kept = 0, total_len = 0;
+};
+
+// global_positions (the sketch and the index): the kept reads must fit the 40 bits of a global position
+int kmer_plan(const char *fn, const KmerInput &in, int k, int32_t min_len_exclusive, bool global_positions, KmerPlan *P) {
+    const int64_t n_reads = in.n_reads;
+    const int64_t *off = in.off;
+    const int32_t *len = in.len;
+    GAB_CHECK(n_reads < (1ll << 31), "%s: %lld reads in one call (limit 2^31)", fn, (long long)n_reads);
+    P->woff.resize((size_t)n_reads + 1); P->rbase.assign((size_t)n_reads + 1, 0); P->first_run.resize((size_t)n_reads + 1);
+    for (int64_t r = 0; r < n_reads; r++) {
+        GAB_CHECK(len[r] >= 0 && off[r] >= 0 && off[r] + len[r] <= in.seq_bytes, "%s: read %lld (offset %lld, length %d) lies outside the %lld sequence bytes",
+                  fn, (long long)r, (long long)off[r], (int)len[r], (long long)in.seq_bytes);
+        P->woff[(size_t)r] = P->words;
+        P->words += ((int64_t)len[r] + 15) / 16;
+        P->first_run[(size_t)r] = (int64_t)P->tiles.size() * 64;
         if (len[r] > min_len_exclusive) {
-            kept++;
+            P->kept++;
+            P->rbase[(size_t)r] = 2 * P->total_len;
+            P->total_len += len[r];
             const int32_t npos = len[r] - k;
-            for (int32_t p = 0; p < npos; p += kTile) tiles.push_back(KmerTile{(int32_t)r, p});
-            if (npos > 0) positions += npos;
+            for (int32_t p = 0; p < npos; p += kTile) P->tiles.push_back(KmerTile{(int32_t)r, p});
+            if (npos > 0) P->positions += npos;
         }
     }
-    woff[(size_t)n_reads] = words;
-    GAB_CHECK(positions < (1ll << 32), "gab_kmer_count: %lld k-mer positions in one call (limit 2^32: the counts are 32-bit)", (long long)positions);
-    const int64_t n_tiles = (int64_t)tiles.size();
-    // GAB_KMER_PART_FLOOR: the first table of a partitioned call is the 16-line floor (test hook of the repeat below)
-    uint64_t nlines = nparts > 1 && h->tun.kmer_part_floor ? 16 : part_table_lines(std::max<int64_t>(positions, 1), k, nparts);
-    int rc;
-    const size_t tiles_at = align256(((size_t)n_reads + 1) * 8);
-    if ((rc = h->packed.reserve((size_t)words * 4 + 4))) return rc;
-    if ((rc = h->plan.reserve(tiles_at + (size_t)n_tiles * sizeof(KmerTile) + 8))) return rc;
-    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
-    int64_t *d_woff = h->plan.as<int64_t>();
-    KmerTile *d_tiles = reinterpret_cast<KmerTile *>(h->plan.as<char>() + tiles_at);
-    KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    uint32_t *packed = h->packed.as<uint32_t>();
+    P->woff[(size_t)n_reads] = P->words;
+    P->first_run[(size_t)n_reads] = (int64_t)P->tiles.size() * 64;
+    GAB_CHECK(P->positions < (1ll << 32), "%s: %lld k-mer positions in one call (limit 2^32%s)", fn, (long long)P->positions,
+              global_positions ? "" : ": the counts are 32-bit");
+    GAB_CHECK(!global_positions || 2 * P->total_len < (1ll << 40),
+              "%s: %lld bases in the kept reads (global positions have 40 bits, kmer-cnt/sequence_container.h:266)", fn, (long long)P->total_len);
+    return GAB_OK;
+}
 
-    GAB_HIP(hipEventRecord(h->ev[0], s));
+int kmer_zero_counters(gab_kmer *h, hipStream_t s) {
     KmerCounters zero = {};
     zero.bad_read = ~0ull; zero.bad_query = ~0ull;
     *h->h_ct = zero;
-    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
-    GAB_HIP(hipMemcpyAsync(d_woff, woff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_tiles) GAB_HIP(hipMemcpyAsync(d_tiles, tiles.data(), (size_t)n_tiles * sizeof(KmerTile), hipMemcpyHostToDevice, s));
-    if (words)
-        hipLaunchKernelGGL(kmer_pack, dim3((unsigned)gab_ceil_div(words, kBlock)), dim3(kBlock), 0, s, d_seq, d_off, d_len, d_woff, n_reads, words, packed, d_ct);
-    GAB_HIP(hipEventRecord(h->ev[1], s));
-    // (a bad byte packs as some base: the count below runs on it harmlessly and the call fails after the one synchronisation)
-    // A partition's first table is a forecast (part_table_lines) and its inserts are bounded: when one gave up, the host sees
-    // ct->overflow after the call's one synchronisation and runs clear, count and reduce once more in a table of table_lines lines,
-    // which is at most half full whatever the hash does.  (After such a repeat pack_ms includes the first attempt.)
+    GAB_HIP(hipMemcpyAsync(h->ct.as<KmerCounters>(), h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
+    return GAB_OK;
+}
+
+// plan to the device and pack; leaves the zeroed counters in h->ct
+// (a bad byte packs as some base: what follows runs on it harmlessly and the call fails after its next synchronisation)
+int kmer_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, KmerDev *D) {
+    int rc;
+    const int64_t n_tiles = (int64_t)P.tiles.size();
+    const size_t tiles_at = align256(((size_t)in.n_reads + 1) * 8);
+    if ((rc = h->packed.reserve((size_t)P.words * 4 + 4))) return rc;
+    if ((rc = h->plan.reserve(tiles_at + (size_t)n_tiles * sizeof(KmerTile) + 8))) return rc;
+    D->woff = h->plan.as<int64_t>();
+    D->tiles = reinterpret_cast<KmerTile *>(h->plan.as<char>() + tiles_at);
+    D->packed = h->packed.as<uint32_t>();
+    D->n_tiles = n_tiles; D->n_runs = n_tiles * 64;
+    if ((rc = kmer_zero_counters(h, in.stream))) return rc;
+    GAB_HIP(hipMemcpyAsync(D->woff, P.woff.data(), ((size_t)in.n_reads + 1) * 8, hipMemcpyHostToDevice, in.stream));
+    if (n_tiles) GAB_HIP(hipMemcpyAsync(D->tiles, P.tiles.data(), (size_t)n_tiles * sizeof(KmerTile), hipMemcpyHostToDevice, in.stream));
+    if (P.words)
+        hipLaunchKernelGGL(kmer_pack, dim3((unsigned)gab_ceil_div(P.words, kBlock)), dim3(kBlock), 0, in.stream, in.d_seq, in.d_off, in.d_len, D->woff, in.n_reads,
+                           P.words, D->packed, h->ct.as<KmerCounters>());
+    return GAB_OK;
+}
+
+// The table of a call that may be partitioned.  A partition's first table is a forecast (part_table_lines; GAB_KMER_PART_FLOOR: the
+// 16-line floor, test hook of the repeat) and its inserts are bounded: when one gave up, the host sees ct->overflow after the
+// attempt's synchronisation and runs the attempt once more, with fresh counters, in a table of table_lines lines, which is at most
+// half full whatever the hash does.  attempt(n, limit): clear, walk, reduce and fetch for the table h->table of h->nlines lines;
+// n: 0, or 1 for the repeat; limit: the lines a bounded insert may leave.  It synchronises and leaves the counters in h->h_ct.
+template <class Attempt>
+int kmer_first_table(gab_kmer *h, const char *fn, int64_t positions, int k, int nparts, hipStream_t s, Attempt attempt) {
+    int rc;
+    gab_tuning_refresh(&h->tun);
+    h->nlines = nparts > 1 && h->tun.kmer_part_floor ? 16 : part_table_lines(std::max<int64_t>(positions, 1), k, nparts);
     h->retried = false;
-    for (int attempt = 0;; attempt++) {
-        if (attempt && (rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    for (int n = 0;; n++) {
+        if ((rc = h->table.reserve((size_t)h->nlines * sizeof(KmerLine)))) return rc;
+        if ((rc = attempt(n, n ? h->nlines : std::min<uint64_t>(h->nlines, kProbeCap)))) return rc;
+        if (!h->h_ct->overflow) return GAB_OK;
+        GAB_CHECK(n == 0, "%s: internal error: a table of %llu lines for %lld positions filled up", fn, (unsigned long long)h->nlines, (long long)positions);
+        h->retried = true;
+        h->nlines = table_lines(std::max<int64_t>(positions, 1), k);
+        if ((rc = kmer_zero_counters(h, s))) return rc;
+    }
+}
+
+}  // namespace
+
+// part / nparts: the partition of the key space this call counts (0 / 1: all of it, in the unpartitioned kernel)
+static int kmer_count_impl(gab_kmer *h, const KmerInput &in, int k, int32_t min_len_exclusive, int part, int nparts, gab_kmer_result *res) {
+    h->counted = false; h->indexed = false; h->pend.on = false;
+    hipStream_t s = in.stream;
+    KmerPlan P;
+    KmerDev D = {};
+    int rc;
+    if ((rc = kmer_plan("gab_kmer_count", in, k, min_len_exclusive, false, &P))) return rc;
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    GAB_HIP(hipEventRecord(h->ev[0], s));
+    if ((rc = kmer_stage(h, in, P, &D))) return rc;
+    GAB_HIP(hipEventRecord(h->ev[1], s));
+    rc = kmer_first_table(h, "gab_kmer_count", P.positions, k, nparts, s, [&](int attempt, uint64_t limit) -> int {
         KmerLine *table = h->table.as<KmerLine>();
-        GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
-        if (n_tiles) {
-            const dim3 grid((unsigned)gab_ceil_div(n_tiles, kBlock / 64));
+        if (attempt) GAB_HIP(hipEventRecord(h->ev[1], s));        // (after a repeat pack_ms includes the first attempt)
+        GAB_HIP(hipMemsetAsync(table, 0, (size_t)h->nlines * sizeof(KmerLine), s));
+        if (D.n_tiles) {
+            const dim3 grid((unsigned)gab_ceil_div(D.n_tiles, kBlock / 64));
             if (nparts == 1)
-                hipLaunchKernelGGL(kmer_count<false>, grid, dim3(kBlock), 0, s, packed, d_woff, d_len, d_tiles, n_tiles, k, table, nlines, d_ct, 0u, 1u,
+                hipLaunchKernelGGL(kmer_count<false>, grid, dim3(kBlock), 0, s, D.packed, D.woff, in.d_len, D.tiles, D.n_tiles, k, table, h->nlines, d_ct, 0u, 1u,
                                    (uint64_t)0);
             else
-                hipLaunchKernelGGL(kmer_count<true>, grid, dim3(kBlock), 0, s, packed, d_woff, d_len, d_tiles, n_tiles, k, table, nlines, d_ct, (uint32_t)part,
-                                   (uint32_t)nparts, attempt ? nlines : std::min<uint64_t>(nlines, kProbeCap));
+                hipLaunchKernelGGL(kmer_count<true>, grid, dim3(kBlock), 0, s, D.packed, D.woff, in.d_len, D.tiles, D.n_tiles, k, table, h->nlines, d_ct,
+                                   (uint32_t)part, (uint32_t)nparts, limit);
         }
         GAB_HIP(hipEventRecord(h->ev[2], s));
-        h->nlines = nlines;
-        hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+        hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, h->nlines * kSlots, d_ct);
         GAB_HIP(hipEventRecord(h->ev[3], s));
         GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
         GAB_HIP(hipEventRecord(h->ev[4], s));
@@ -925,17 +1009,11 @@ static int kmer_count_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, co
         GAB_HIP(hipGetLastError());
         GAB_CHECK(h->h_ct->bad_read == ~0ull, "gab_kmer_count: read %lld holds a byte outside ACGTacgt (a driver replaces such bytes before the call)",
                   (long long)h->h_ct->bad_read);
-        if (!h->h_ct->overflow) break;
-        GAB_CHECK(attempt == 0, "gab_kmer_count: internal error: a table of %llu lines for %lld positions filled up", (unsigned long long)nlines,
-                  (long long)positions);
-        h->retried = true;
-        nlines = table_lines(std::max<int64_t>(positions, 1), k);
-        *h->h_ct = zero;
-        GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
-        GAB_HIP(hipEventRecord(h->ev[1], s));
-    }
+        return GAB_OK;
+    });
+    if (rc) return rc;
     const KmerCounters &c = *h->h_ct;
-    h->last = gab_kmer_result{kept, positions, (int64_t)c.distinct, (int64_t)c.total_kmers, (int64_t)c.hash_size, (int64_t)c.max_count};
+    h->last = gab_kmer_result{P.kept, P.positions, (int64_t)c.distinct, (int64_t)c.total_kmers, (int64_t)c.hash_size, (int64_t)c.max_count};
     h->probes = (int64_t)c.probes; h->merged = (int64_t)c.merged;
     for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&h->phase_ms[i], h->ev[i], h->ev[i + 1]);
     (void)hipEventElapsedTime(&h->total_ms, h->ev[0], h->ev[4]);
@@ -964,52 +1042,9 @@ extern "C" int gab_kmer_count_part_device(gab_kmer *h, const char *seq, int64_t 
     if (rc) return rc;
     GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_count_device: bad sequence slab");
     gab_device_guard g(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int64_t> h_off((size_t)n_reads);
-    std::vector<int32_t> h_len((size_t)n_reads);
-    if (n_reads) {
-        GAB_HIP(hipMemcpyAsync(h_off.data(), off, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipMemcpyAsync(h_len.data(), len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    return kmer_count_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, min_len_exclusive, part, nparts, res, s);
-}
-
-// The host-pointer entry points: the window of the slab that the reads span, their offsets relative to it and their lengths go
-// into the handle's staging buffer.  st->rel: those offsets on the host.
-struct kmer_staged { char *d_seq; int64_t *d_off; int32_t *d_len; size_t span; std::vector<int64_t> rel; };
-static int kmer_stage_host(gab_kmer *h, const char *fn, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, hipStream_t s,
-                           kmer_staged *st) {
-    int rc;
-    h->pend.on = false;                                            // (a pending partitioned index build keeps its lengths in `io`)
-    int64_t lo = INT64_MAX, hi = 0;                                // the window of the slab the reads span
-    for (int64_t r = 0; r < n_reads; r++) {
-        GAB_CHECK(len[r] >= 0 && off[r] >= 0, "%s: read %lld has a negative offset or length", fn, (long long)r);
-        if (len[r] == 0) continue;
-        lo = std::min(lo, off[r]); hi = std::max(hi, off[r] + len[r]);
-    }
-    if (hi == 0) lo = 0;
-    GAB_CHECK(seq || hi == 0, "%s: NULL sequence slab", fn);
-    const size_t span = (size_t)(hi - lo);
-    const size_t off_at = align256(span + 64), len_at = off_at + align256((size_t)n_reads * 8);
-    if ((rc = h->io.reserve(len_at + align256((size_t)n_reads * 4)))) return rc;
-    st->d_seq = h->io.as<char>();
-    st->d_off = reinterpret_cast<int64_t *>(st->d_seq + off_at);
-    st->d_len = reinterpret_cast<int32_t *>(st->d_seq + len_at);
-    st->span = span;
-    std::vector<int64_t> &rel = st->rel;
-    rel.assign((size_t)n_reads, 0);
-    for (int64_t r = 0; r < n_reads; r++) rel[(size_t)r] = len[r] ? off[r] - lo : 0;
-    {
-        std::lock_guard<std::mutex> lk(gab_h2d_mutex(h->device));
-        if (span) GAB_HIP(hipMemcpyAsync(st->d_seq, seq + lo, span, hipMemcpyHostToDevice, s));
-        if (n_reads) {
-            GAB_HIP(hipMemcpyAsync(st->d_off, rel.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, s));
-            GAB_HIP(hipMemcpyAsync(st->d_len, len, (size_t)n_reads * 4, hipMemcpyHostToDevice, s));
-        }
-        GAB_HIP(hipStreamSynchronize(s));
-    }
-    return GAB_OK;
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_count_impl(h, in, k, min_len_exclusive, part, nparts, res);
 }
 
 extern "C" int gab_kmer_count(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
@@ -1022,11 +1057,9 @@ extern "C" int gab_kmer_count_part(gab_kmer *h, const char *seq, const int64_t *
     int rc = kmer_check_args(h, off, len, n_reads, k, part, nparts);
     if (rc) return rc;
     gab_device_guard g(h->device);
-    hipStream_t s;
-    if ((rc = h->hs.get(&s))) return rc;
-    kmer_staged st;
-    if ((rc = kmer_stage_host(h, "gab_kmer_count", seq, off, len, n_reads, s, &st))) return rc;
-    return kmer_count_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, min_len_exclusive, part, nparts, res, s);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, "gab_kmer_count", seq, off, len, n_reads, &in))) return rc;
+    return kmer_count_impl(h, in, k, min_len_exclusive, part, nparts, res);
 }
 
 #define KMER_NEED_COUNT(fn) GAB_CHECK(h && h->counted, fn ": no finished gab_kmer_count on this handle")
@@ -1120,13 +1153,17 @@ extern "C" int gab_kmer_last_phases(gab_kmer *h, float *pack_ms, float *count_ms
     return GAB_OK;
 }
 
-extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
-    KMER_NEED_COUNT("gab_kmer_last_part");
+static int kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
     if (part) *part = h->part;
     if (nparts) *nparts = h->nparts;
     if (table_slots) *table_slots = (int64_t)(h->nlines * kSlots);
     if (retried) *retried = h->retried ? 1 : 0;
     return GAB_OK;
+}
+
+extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
+    KMER_NEED_COUNT("gab_kmer_last_part");
+    return kmer_last_part(h, part, nparts, table_slots, retried);
 }
 
 // =============================================================================== minimizer index, host side
@@ -1145,16 +1182,6 @@ extern "C" int gab_kmer_last_part(gab_kmer *h, int *part, int *nparts, int64_t *
 // unpartitioned build) over the partition's own keys and entries, with the threshold of the whole input.
 namespace {
 
-struct KmerMiniPlan {
-    std::vector<int64_t> woff, rbase, first_run;   // word offset | 2 S_i of a kept read | runs before the read (n_reads + 1)
-    std::vector<KmerTile> tiles;
-    int64_t words = 0, positions = 0, kept = 0, total_len = 0;
-};
-struct KmerMiniDev {       // where the stage put things
-    int64_t *woff; KmerTile *tiles; uint32_t *packed; unsigned long long *masks; uint32_t *offs; int64_t *rbase, *first_run;
-    int64_t n_tiles, n_runs;
-};
-
 int kmer_mini_check(const char *fn, gab_kmer *h, const void *off, const void *len, int64_t n_reads, int k, int window) {
     GAB_CHECK(h && n_reads >= 0 && (n_reads == 0 || (off && len)), "%s: NULL or negative argument", fn);
     GAB_CHECK(k >= 1 && k <= GAB_KMER_MAX_K, "%s: k = %d, supported 1..%d", fn, k, GAB_KMER_MAX_K);
@@ -1163,41 +1190,11 @@ int kmer_mini_check(const char *fn, gab_kmer *h, const void *off, const void *le
     return GAB_OK;
 }
 
-int kmer_mini_plan(const char *fn, const int64_t *off, const int32_t *len, int64_t n_reads, int64_t seq_bytes, int k, int32_t min_len_exclusive,
-                   KmerMiniPlan *P) {
-    GAB_CHECK(n_reads < (1ll << 31), "%s: %lld reads in one call (limit 2^31)", fn, (long long)n_reads);
-    P->woff.resize((size_t)n_reads + 1); P->rbase.assign((size_t)n_reads + 1, 0); P->first_run.resize((size_t)n_reads + 1);
-    for (int64_t r = 0; r < n_reads; r++) {
-        GAB_CHECK(len[r] >= 0 && off[r] >= 0 && off[r] + len[r] <= seq_bytes, "%s: read %lld (offset %lld, length %d) lies outside the %lld sequence bytes", fn,
-                  (long long)r, (long long)off[r], (int)len[r], (long long)seq_bytes);
-        P->woff[(size_t)r] = P->words;
-        P->words += ((int64_t)len[r] + 15) / 16;
-        P->first_run[(size_t)r] = (int64_t)P->tiles.size() * 64;
-        if (len[r] > min_len_exclusive) {
-            P->kept++;
-            P->rbase[(size_t)r] = 2 * P->total_len;
-            P->total_len += len[r];
-            const int32_t npos = len[r] - k;
-            for (int32_t p = 0; p < npos; p += kTile) P->tiles.push_back(KmerTile{(int32_t)r, p});
-            if (npos > 0) P->positions += npos;
-        }
-    }
-    P->woff[(size_t)n_reads] = P->words;
-    P->first_run[(size_t)n_reads] = (int64_t)P->tiles.size() * 64;
-    GAB_CHECK(P->positions < (1ll << 32), "%s: %lld k-mer positions in one call (limit 2^32)", fn, (long long)P->positions);
-    GAB_CHECK(2 * P->total_len < (1ll << 40), "%s: %lld bases in the kept reads (global positions have 40 bits, kmer-cnt/sequence_container.h:266)", fn,
-              (long long)P->total_len);
-    return GAB_OK;
-}
-
-// plan to the device, pack, sketch, scan; leaves the zeroed counters in h->ct
-int kmer_mini_stage(gab_kmer *h, const char *d_seq, const int64_t *d_off, const int32_t *d_len, const KmerMiniPlan &P, int64_t n_reads, int k, int window,
-                    hipStream_t s, KmerMiniDev *D) {
+// kmer_stage, then sketch and scan (rbase and first_run go up first: a copy behind the pack kernel would hold the sketch back)
+int kmer_mini_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, int k, int window, KmerDev *D) {
     int rc;
-    const int64_t n_tiles = (int64_t)P.tiles.size(), n_runs = n_tiles * 64;
-    const size_t tiles_at = align256(((size_t)n_reads + 1) * 8);
-    if ((rc = h->packed.reserve((size_t)P.words * 4 + 4))) return rc;
-    if ((rc = h->plan.reserve(tiles_at + (size_t)n_tiles * sizeof(KmerTile) + 8))) return rc;
+    hipStream_t s = in.stream;
+    const int64_t n_reads = in.n_reads, n_tiles = (int64_t)P.tiles.size(), n_runs = n_tiles * 64;
     size_t tmp_bytes = 0;
     GAB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)nullptr, KmerPopc()), (uint32_t *)nullptr, 0u,
                                     (size_t)n_runs + 1, rocprim::plus<uint32_t>(), s));
@@ -1205,37 +1202,24 @@ int kmer_mini_stage(gab_kmer *h, const char *d_seq, const int64_t *d_off, const 
     const size_t first_at = rbase_at + align256(((size_t)n_reads + 1) * 8), tmp_at = first_at + align256(((size_t)n_reads + 1) * 8);
     if ((rc = h->mini.reserve(tmp_at + tmp_bytes + 256))) return rc;
     char *mb = h->mini.as<char>();
-    D->woff = h->plan.as<int64_t>();
-    D->tiles = reinterpret_cast<KmerTile *>(h->plan.as<char>() + tiles_at);
-    D->packed = h->packed.as<uint32_t>();
     D->masks = reinterpret_cast<unsigned long long *>(mb);
     D->offs = reinterpret_cast<uint32_t *>(mb + offs_at);
     D->rbase = reinterpret_cast<int64_t *>(mb + rbase_at);
     D->first_run = reinterpret_cast<int64_t *>(mb + first_at);
-    D->n_tiles = n_tiles; D->n_runs = n_runs;
-    KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    KmerCounters zero = {};
-    zero.bad_read = ~0ull; zero.bad_query = ~0ull;
-    *h->h_ct = zero;
-    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
-    GAB_HIP(hipMemcpyAsync(D->woff, P.woff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
     GAB_HIP(hipMemcpyAsync(D->rbase, P.rbase.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
     GAB_HIP(hipMemcpyAsync(D->first_run, P.first_run.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_tiles) GAB_HIP(hipMemcpyAsync(D->tiles, P.tiles.data(), (size_t)n_tiles * sizeof(KmerTile), hipMemcpyHostToDevice, s));
-    if (P.words)
-        hipLaunchKernelGGL(kmer_pack, dim3((unsigned)gab_ceil_div(P.words, kBlock)), dim3(kBlock), 0, s, d_seq, d_off, d_len, D->woff, n_reads, P.words, D->packed,
-                           d_ct);
+    if ((rc = kmer_stage(h, in, P, D))) return rc;
     GAB_HIP(hipMemsetAsync(D->masks, 0, ((size_t)n_runs + 1) * 8, s));
     if (n_tiles)
-        hipLaunchKernelGGL(kmer_sketch, dim3((unsigned)gab_ceil_div(n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D->packed, D->woff, d_len, D->tiles, n_tiles, k, window,
-                           D->masks);
+        hipLaunchKernelGGL(kmer_sketch, dim3((unsigned)gab_ceil_div(n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D->packed, D->woff, in.d_len, D->tiles, n_tiles, k,
+                           window, D->masks);
     GAB_HIP(rocprim::exclusive_scan(mb + tmp_at, tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)D->masks, KmerPopc()), D->offs, 0u,
                                     (size_t)n_runs + 1, rocprim::plus<uint32_t>(), s));
     return GAB_OK;
 }
 
 // the counters and the number of minimizers (the scan's last element) to the host; synchronises
-int kmer_mini_fetch(gab_kmer *h, const char *fn, const KmerMiniDev &D, hipStream_t s) {
+int kmer_mini_fetch(gab_kmer *h, const char *fn, const KmerDev &D, hipStream_t s) {
     GAB_HIP(hipMemcpyAsync(h->h_ct, h->ct.as<KmerCounters>(), sizeof(KmerCounters), hipMemcpyDeviceToHost, s));
     GAB_HIP(hipMemcpyAsync(&h->h_ct->ix_minimizers, D.offs + D.n_runs, 4, hipMemcpyDeviceToHost, s));     // (little-endian: the low word)
     GAB_HIP(hipStreamSynchronize(s));
@@ -1247,7 +1231,7 @@ int kmer_mini_fetch(gab_kmer *h, const char *fn, const KmerMiniDev &D, hipStream
 
 // h->part of h->nparts (1: the unpartitioned kernel); limit: the lines a bounded capacity insert may leave
 template <int kMode>
-void kmer_mini_launch_walk(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int32_t *pos, uint32_t thr, int64_t *gpos, hipStream_t s,
+void kmer_mini_launch_walk(gab_kmer *h, const KmerDev &D, const int32_t *d_len, int k, int32_t *pos, uint32_t thr, int64_t *gpos, hipStream_t s,
                            uint64_t limit = 0) {
     if (!D.n_tiles) return;
     const dim3 grid((unsigned)gab_ceil_div(D.n_tiles, kBlock / 64));
@@ -1259,16 +1243,17 @@ void kmer_mini_launch_walk(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_l
                            pos, h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos, (uint32_t)h->part, (uint32_t)h->nparts, limit);
 }
 
-// d_*: device; off / len: the same two arrays on the host.  out_on_device: read_start / pos are device pointers
-int kmer_sketch_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
-                     int64_t n_reads, int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout,
-                     bool out_on_device, hipStream_t s) {
-    KmerMiniPlan P;
-    KmerMiniDev D;
+// out_on_device: read_start / pos are device pointers
+int kmer_sketch_impl(gab_kmer *h, const KmerInput &in, int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity,
+                     int64_t *nout, bool out_on_device) {
+    hipStream_t s = in.stream;
+    const int64_t n_reads = in.n_reads;
+    KmerPlan P;
+    KmerDev D;
     int rc;
     h->pend.on = false;                    // (the stage below overwrites what a pending partitioned index build keeps)
-    if ((rc = kmer_mini_plan("gab_kmer_sketch", off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
-    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    if ((rc = kmer_plan("gab_kmer_sketch", in, k, min_len_exclusive, true, &P))) return rc;
+    if ((rc = kmer_mini_stage(h, in, P, k, window, &D))) return rc;
     if ((rc = kmer_mini_fetch(h, "gab_kmer_sketch", D, s))) return rc;
     const int64_t m = (int64_t)h->h_ct->ix_minimizers;
     *nout = m;
@@ -1283,7 +1268,7 @@ int kmer_sketch_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const in
         d_pos = reinterpret_cast<int32_t *>(h->aux.as<char>() + pos_at);
     }
     hipLaunchKernelGGL(kmer_read_starts, dim3((unsigned)gab_ceil_div(n_reads + 1, kBlock)), dim3(kBlock), 0, s, D.offs, D.first_run, n_reads + 1, d_start);
-    kmer_mini_launch_walk<kWalkSketch>(h, D, d_len, k, d_pos, 0u, nullptr, s);
+    kmer_mini_launch_walk<kWalkSketch>(h, D, in.d_len, k, d_pos, 0u, nullptr, s);
     if (!out_on_device) {
         GAB_HIP(hipMemcpyAsync(read_start, d_start, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
         if (m) GAB_HIP(hipMemcpyAsync(pos, d_pos, (size_t)m * 4, hipMemcpyDeviceToHost, s));
@@ -1301,12 +1286,22 @@ uint64_t kmer_repetitive(uint64_t total, uint64_t unique, float rate) {
     return cut >= 18446744073709551615.0f ? ~0ull : (uint64_t)cut;
 }
 
+// The filter's threshold from the totals of the whole input: thr is min(repetitive_frequency, 2^32 - 1), what the kernels compare the
+// 32-bit capacities with.  -> the result so far; minimizers and distinct are this table's own.
+gab_kmer_index_result kmer_index_threshold(int64_t kept, int64_t total_len, int64_t minimizers, int64_t distinct, uint64_t total, uint64_t unique, float rate,
+                                           uint32_t *thr) {
+    const uint64_t rep = kmer_repetitive(total, unique, rate);
+    *thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
+    return gab_kmer_index_result{kept, total_len, minimizers, distinct, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
+}
+
 // The second half of an index build, after the synchronisation that gave the host the filter's two integers: orders the n keys of
 // the table, lays out their lists (m entries before the filter), fills and sorts them.  The table holds the keys of h->part of
-// h->nparts, n and m are that partition's own, thr comes from the totals of the whole input.  Fills the last four fields of R.
-int kmer_index_layout(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, int k, int64_t n, int64_t m, uint32_t thr, gab_kmer_index_result *Rp,
+// h->nparts, n = R.distinct and m = R.minimizers are that partition's own, thr comes from the totals of the whole input
+// (kmer_index_threshold).  Fills the last four fields of R; the handle then holds the index.
+int kmer_index_layout(gab_kmer *h, const KmerDev &D, const int32_t *d_len, int k, gab_kmer_index_result R, uint32_t thr, gab_kmer_index_result *res,
                       hipStream_t s) {
-    gab_kmer_index_result &R = *Rp;
+    const int64_t n = R.distinct, m = R.minimizers;
     KmerLine *table = h->table.as<KmerLine>();
     KmerCounters *d_ct = h->ct.as<KmerCounters>();
     const uint64_t nlines = h->nlines;
@@ -1354,105 +1349,77 @@ int kmer_index_layout(gab_kmer *h, const KmerMiniDev &D, const int32_t *d_len, i
     }
     (void)hipEventElapsedTime(&h->ix_ms[2], h->ev_ix[3], h->ev_ix[4]);
     (void)hipEventElapsedTime(&h->ix_ms[3], h->ev_ix[4], h->ev_ix[5]);
-    return GAB_OK;
-}
-
-int kmer_index_impl(gab_kmer *h, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off, const int32_t *len,
-                    int64_t n_reads, int k, int window, int32_t min_len_exclusive, float rate, gab_kmer_index_result *res, hipStream_t s) {
-    const char *fn = "gab_kmer_index_minimizers";
-    h->counted = false; h->indexed = false; h->pend.on = false;
-    KmerMiniPlan P;
-    KmerMiniDev D;
-    int rc;
-    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
-    // a minimizer per position at most, so the table of a count over the same reads is never more than half full
-    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
-    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
-    KmerLine *table = h->table.as<KmerLine>();
-    KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    h->nlines = nlines; h->k = k; h->part = 0; h->nparts = 1; h->retried = false;
-
-    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
-    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
-    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
-    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
-    kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s);
-    hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
-    GAB_HIP(hipEventRecord(h->ev_ix[2], s));
-    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
-
-    const uint64_t total = h->h_ct->ix_minimizers, unique = h->h_ct->distinct;
-    const uint64_t rep = kmer_repetitive(total, unique, rate);
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
-    const int64_t n = (int64_t)unique, m = (int64_t)total;
-    gab_kmer_index_result R = {P.kept, P.total_len, m, n, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
-
-    if ((rc = kmer_index_layout(h, D, d_len, k, n, m, thr, &R, s))) return rc;
-    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
-    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);
     h->ix = R; h->ix_thr = thr; h->indexed = true;
     if (res) *res = R;
     return GAB_OK;
 }
 
-// Phase 1 of a partitioned index build: stage and sketch as kmer_index_impl, then the capacities of the keys of `part` alone, in a
-// table sized for that share (the first table and its repeat: see kmer_count_impl).  Ends with the synchronisation that every
-// index build has in its middle; what it leaves in the handle is described at gab_kmer::pend.
-int kmer_index_begin_impl(gab_kmer *h, const char *fn, const char *d_seq, int64_t seq_bytes, const int64_t *d_off, const int32_t *d_len, const int64_t *off,
-                          const int32_t *len, int64_t n_reads, int k, int window, int32_t min_len_exclusive, int part, int nparts, gab_kmer_index_result *res,
-                          hipStream_t s) {
+int kmer_index_impl(gab_kmer *h, const KmerInput &in, int k, int window, int32_t min_len_exclusive, float rate, gab_kmer_index_result *res) {
+    const char *fn = "gab_kmer_index_minimizers";
     h->counted = false; h->indexed = false; h->pend.on = false;
-    gab_tuning_refresh(&h->tun);
-    KmerMiniPlan P;
-    KmerMiniDev D;
+    hipStream_t s = in.stream;
+    KmerPlan P;
+    KmerDev D;
     int rc;
-    if ((rc = kmer_mini_plan(fn, off, len, n_reads, seq_bytes, k, min_len_exclusive, &P))) return rc;
-    uint64_t nlines = nparts > 1 && h->tun.kmer_part_floor ? 16 : part_table_lines(std::max<int64_t>(P.positions, 1), k, nparts);
-    KmerCounters *d_ct = h->ct.as<KmerCounters>();
-    h->k = k; h->part = part; h->nparts = nparts; h->retried = false;
+    if ((rc = kmer_plan(fn, in, k, min_len_exclusive, true, &P))) return rc;
+    // a minimizer per position at most, so the table of a count over the same reads is never more than half full
+    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
+    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    KmerLine *table = h->table.as<KmerLine>();
+    h->nlines = nlines; h->k = k; h->part = 0; h->nparts = 1; h->retried = false;
 
     GAB_HIP(hipEventRecord(h->ev_ix[0], s));
-    if ((rc = kmer_mini_stage(h, d_seq, d_off, d_len, P, n_reads, k, window, s, &D))) return rc;
+    if ((rc = kmer_mini_stage(h, in, P, k, window, &D))) return rc;
     GAB_HIP(hipEventRecord(h->ev_ix[1], s));
-    for (int attempt = 0;; attempt++) {
-        if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+    kmer_mini_launch_walk<kWalkCount>(h, D, in.d_len, k, nullptr, 0u, nullptr, s);
+    hipLaunchKernelGGL(kmer_reduce<false>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, h->ct.as<KmerCounters>());
+    GAB_HIP(hipEventRecord(h->ev_ix[2], s));
+    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
+    (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
+    (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);
+
+    const uint64_t total = h->h_ct->ix_minimizers, unique = h->h_ct->distinct;
+    uint32_t thr;
+    const gab_kmer_index_result R = kmer_index_threshold(P.kept, P.total_len, (int64_t)total, (int64_t)unique, total, unique, rate, &thr);
+    return kmer_index_layout(h, D, in.d_len, k, R, thr, res, s);
+}
+
+// Phase 1 of a partitioned index build: stage and sketch as kmer_index_impl, then the capacities of the keys of `part` alone, in a
+// table sized for that share (the first table and its repeat: kmer_first_table).  Ends with the synchronisation that every
+// index build has in its middle; what it leaves in the handle is described at gab_kmer::pend.
+int kmer_index_begin_impl(gab_kmer *h, const char *fn, const KmerInput &in, int k, int window, int32_t min_len_exclusive, int part, int nparts,
+                          gab_kmer_index_result *res) {
+    h->counted = false; h->indexed = false; h->pend.on = false;
+    hipStream_t s = in.stream;
+    KmerPlan P;
+    KmerDev D;
+    int rc;
+    if ((rc = kmer_plan(fn, in, k, min_len_exclusive, true, &P))) return rc;
+    h->k = k; h->part = part; h->nparts = nparts;
+
+    GAB_HIP(hipEventRecord(h->ev_ix[0], s));
+    if ((rc = kmer_mini_stage(h, in, P, k, window, &D))) return rc;
+    GAB_HIP(hipEventRecord(h->ev_ix[1], s));
+    rc = kmer_first_table(h, fn, P.positions, k, nparts, s, [&](int, uint64_t limit) -> int {
         KmerLine *table = h->table.as<KmerLine>();
-        h->nlines = nlines;
-        GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
-        kmer_mini_launch_walk<kWalkCount>(h, D, d_len, k, nullptr, 0u, nullptr, s, attempt ? nlines : std::min<uint64_t>(nlines, kProbeCap));
-        hipLaunchKernelGGL(kmer_reduce<true>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, d_ct);
+        GAB_HIP(hipMemsetAsync(table, 0, (size_t)h->nlines * sizeof(KmerLine), s));
+        kmer_mini_launch_walk<kWalkCount>(h, D, in.d_len, k, nullptr, 0u, nullptr, s, limit);
+        hipLaunchKernelGGL(kmer_reduce<true>, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, h->nlines * kSlots, h->ct.as<KmerCounters>());
         GAB_HIP(hipEventRecord(h->ev_ix[2], s));
-        if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
-        if (!h->h_ct->overflow) break;
-        GAB_CHECK(attempt == 0, "%s: internal error: a table of %llu lines for %lld positions filled up", fn, (unsigned long long)nlines, (long long)P.positions);
-        h->retried = true;
-        nlines = table_lines(std::max<int64_t>(P.positions, 1), k);
-        KmerCounters zero = {};
-        zero.bad_read = ~0ull; zero.bad_query = ~0ull;
-        *h->h_ct = zero;
-        GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(KmerCounters), hipMemcpyHostToDevice, s));
-    }
+        return kmer_mini_fetch(h, fn, D, s);
+    });
+    if (rc) return rc;
     (void)hipEventElapsedTime(&h->ix_ms[0], h->ev_ix[0], h->ev_ix[1]);
     (void)hipEventElapsedTime(&h->ix_ms[1], h->ev_ix[1], h->ev_ix[2]);       // (after a repeat: both attempts)
     h->ix_ms[2] = 0; h->ix_ms[3] = 0;
     gab_kmer::Pending &Q = h->pend;
-    Q.woff = D.woff; Q.tiles = D.tiles; Q.packed = D.packed; Q.masks = D.masks; Q.offs = D.offs; Q.rbase = D.rbase; Q.first_run = D.first_run;
-    Q.n_tiles = D.n_tiles; Q.n_runs = D.n_runs; Q.d_len = d_len; Q.stream = s;
+    Q.dev = D; Q.d_len = in.d_len; Q.stream = s;
     Q.kept = P.kept; Q.total_len = P.total_len;
     Q.minimizers = (int64_t)h->h_ct->total_kmers;                  // (kmer_reduce<true>: the sum of the capacities in this table)
     Q.distinct = (int64_t)h->h_ct->distinct;
     Q.on = true;
     if (res) *res = gab_kmer_index_result{Q.kept, Q.total_len, Q.minimizers, Q.distinct, 0, 0, 0, 0, 0};
-    return GAB_OK;
-}
-
-int kmer_fetch_off_len(const int64_t *off, const int32_t *len, int64_t n_reads, std::vector<int64_t> *h_off, std::vector<int32_t> *h_len, hipStream_t s) {
-    h_off->resize((size_t)n_reads); h_len->resize((size_t)n_reads);
-    if (n_reads) {
-        GAB_HIP(hipMemcpyAsync(h_off->data(), off, (size_t)n_reads * 8, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipMemcpyAsync(h_len->data(), len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
     return GAB_OK;
 }
 
@@ -1464,12 +1431,9 @@ extern "C" int gab_kmer_sketch(gab_kmer *h, const char *seq, const int64_t *off,
     if (rc) return rc;
     GAB_CHECK(nout && capacity >= 0, "gab_kmer_sketch: NULL or negative argument");
     gab_device_guard g(h->device);
-    hipStream_t s;
-    if ((rc = h->hs.get(&s))) return rc;
-    kmer_staged st;
-    if ((rc = kmer_stage_host(h, "gab_kmer_sketch", seq, off, len, n_reads, s, &st))) return rc;
-    return kmer_sketch_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, read_start, pos, capacity,
-                            nout, false, s);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, "gab_kmer_sketch", seq, off, len, n_reads, &in))) return rc;
+    return kmer_sketch_impl(h, in, k, window, min_len_exclusive, read_start, pos, capacity, nout, false);
 }
 
 extern "C" int gab_kmer_sketch_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int window,
@@ -1478,11 +1442,9 @@ extern "C" int gab_kmer_sketch_device(gab_kmer *h, const char *seq, int64_t seq_
     if (rc) return rc;
     GAB_CHECK(nout && capacity >= 0 && seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_sketch_device: bad argument");
     gab_device_guard g(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int64_t> h_off;
-    std::vector<int32_t> h_len;
-    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
-    return kmer_sketch_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, read_start, pos, capacity, nout, true, s);
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_sketch_impl(h, in, k, window, min_len_exclusive, read_start, pos, capacity, nout, true);
 }
 
 static int kmer_check_rate(float rate) {
@@ -1495,11 +1457,9 @@ extern "C" int gab_kmer_index_minimizers(gab_kmer *h, const char *seq, const int
     int rc = kmer_mini_check("gab_kmer_index_minimizers", h, off, len, n_reads, k, window);
     if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
     gab_device_guard g(h->device);
-    hipStream_t s;
-    if ((rc = h->hs.get(&s))) return rc;
-    kmer_staged st;
-    if ((rc = kmer_stage_host(h, "gab_kmer_index_minimizers", seq, off, len, n_reads, s, &st))) return rc;
-    return kmer_index_impl(h, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, repeat_kmer_rate, res, s);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, "gab_kmer_index_minimizers", seq, off, len, n_reads, &in))) return rc;
+    return kmer_index_impl(h, in, k, window, min_len_exclusive, repeat_kmer_rate, res);
 }
 
 extern "C" int gab_kmer_index_minimizers_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
@@ -1508,11 +1468,9 @@ extern "C" int gab_kmer_index_minimizers_device(gab_kmer *h, const char *seq, in
     if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
     GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "gab_kmer_index_minimizers_device: bad sequence slab");
     gab_device_guard g(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int64_t> h_off;
-    std::vector<int32_t> h_len;
-    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
-    return kmer_index_impl(h, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, repeat_kmer_rate, res, s);
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_index_impl(h, in, k, window, min_len_exclusive, repeat_kmer_rate, res);
 }
 
 extern "C" int64_t gab_kmer_repetitive_frequency(int64_t minimizers, int64_t distinct, float repeat_kmer_rate) {
@@ -1536,12 +1494,9 @@ extern "C" int gab_kmer_index_part_begin(gab_kmer *h, const char *seq, const int
     int rc = kmer_mini_check(fn, h, off, len, n_reads, k, window);
     if (rc || (rc = kmer_check_index_part(fn, part, nparts))) return rc;
     gab_device_guard g(h->device);
-    hipStream_t s;
-    if ((rc = h->hs.get(&s))) return rc;
-    kmer_staged st;
-    if ((rc = kmer_stage_host(h, fn, seq, off, len, n_reads, s, &st))) return rc;
-    return kmer_index_begin_impl(h, fn, st.d_seq, (int64_t)st.span, st.d_off, st.d_len, st.rel.data(), len, n_reads, k, window, min_len_exclusive, part, nparts,
-                                 res, s);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, fn, seq, off, len, n_reads, &in))) return rc;
+    return kmer_index_begin_impl(h, fn, in, k, window, min_len_exclusive, part, nparts, res);
 }
 
 extern "C" int gab_kmer_index_part_begin_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
@@ -1551,11 +1506,9 @@ extern "C" int gab_kmer_index_part_begin_device(gab_kmer *h, const char *seq, in
     if (rc || (rc = kmer_check_index_part(fn, part, nparts))) return rc;
     GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "%s: bad sequence slab", fn);
     gab_device_guard g(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<int64_t> h_off;
-    std::vector<int32_t> h_len;
-    if ((rc = kmer_fetch_off_len(off, len, n_reads, &h_off, &h_len, s))) return rc;
-    return kmer_index_begin_impl(h, fn, seq, seq_bytes, off, len, h_off.data(), h_len.data(), n_reads, k, window, min_len_exclusive, part, nparts, res, s);
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_index_begin_impl(h, fn, in, k, window, min_len_exclusive, part, nparts, res);
 }
 
 // (an argument that is refused leaves the pending state as it is: the caller may call again with the right totals)
@@ -1571,15 +1524,10 @@ extern "C" int gab_kmer_index_part_finish(gab_kmer *h, int64_t minimizers, int64
               "partitions)", (long long)minimizers, (long long)distinct, (long long)Q.minimizers, (long long)Q.distinct);
     GAB_CHECK(minimizers >= distinct, "gab_kmer_index_part_finish: %lld minimizers < %lld distinct k-mers", (long long)minimizers, (long long)distinct);
     gab_device_guard g(h->device);
-    const uint64_t rep = kmer_repetitive((uint64_t)minimizers, (uint64_t)distinct, repeat_kmer_rate);
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(rep, 0xFFFFFFFFull);
-    gab_kmer_index_result R = {Q.kept, Q.total_len, Q.minimizers, Q.distinct, (int64_t)std::min<uint64_t>(rep, (uint64_t)INT64_MAX), 0, 0, 0, 0};
-    KmerMiniDev D = {Q.woff, static_cast<KmerTile *>(Q.tiles), Q.packed, Q.masks, Q.offs, Q.rbase, Q.first_run, Q.n_tiles, Q.n_runs};
+    uint32_t thr;
+    const gab_kmer_index_result R = kmer_index_threshold(Q.kept, Q.total_len, Q.minimizers, Q.distinct, (uint64_t)minimizers, (uint64_t)distinct, repeat_kmer_rate, &thr);
     h->pend.on = false;                    // (the fill consumes the list starts: there is no second finish, and none after a failure)
-    if ((rc = kmer_index_layout(h, D, Q.d_len, h->k, Q.distinct, Q.minimizers, thr, &R, Q.stream))) return rc;
-    h->ix = R; h->ix_thr = thr; h->indexed = true;
-    if (res) *res = R;
-    return GAB_OK;
+    return kmer_index_layout(h, Q.dev, Q.d_len, h->k, R, thr, res, Q.stream);
 }
 
 #define KMER_NEED_INDEX(fn) GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers (or gab_kmer_index_part_finish) on this handle")
@@ -1656,9 +1604,5 @@ extern "C" int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *
 
 extern "C" int gab_kmer_index_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried) {
     KMER_NEED_INDEX("gab_kmer_index_last_part");
-    if (part) *part = h->part;
-    if (nparts) *nparts = h->nparts;
-    if (table_slots) *table_slots = (int64_t)(h->nlines * kSlots);
-    if (retried) *retried = h->retried ? 1 : 0;
-    return GAB_OK;
+    return kmer_last_part(h, part, nparts, table_slots, retried);
 }

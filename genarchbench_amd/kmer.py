@@ -29,6 +29,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _dev(seq, off, ln):
+    """the five leading arguments of every *_device call, from torch tensors on the handle's GPU"""
+    return (C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()), C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()))
+
+
 def pack_reads(reads):
     """list of bytes -> (seq uint8, off int64, len int32), reads back to back"""
     ln = np.array([len(r) for r in reads], np.int32)
@@ -86,22 +91,19 @@ class KmerCounter:
     def _dict(res):
         return {f: getattr(res, f) for f, _ in _Result._fields_}
 
+    @staticmethod
+    def _packed(reads):
+        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
+        return np.ascontiguousarray(seq, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(ln, np.int32)
+
     def count(self, reads, k, min_len=5000):
         """reads: list of bytes, or a packed (seq, off, len) triple of numpy arrays -> the six result fields; only reads LONGER than
         min_len are counted"""
-        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
-        seq = np.ascontiguousarray(seq, np.uint8); off = np.ascontiguousarray(off, np.int64); ln = np.ascontiguousarray(ln, np.int32)
-        res = _Result(*([-12345] * 6))
-        check(lib().gab_kmer_count(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int32(min_len), C.byref(res)))
-        return self._dict(res)
+        return self.count_part(reads, k, 0, 1, min_len)
 
     def count_device(self, seq, off, ln, k, min_len=5000, stream=0):
         """torch tensors on the handle's GPU: uint8 / int64 / int32"""
-        res = _Result(*([-12345] * 6))
-        check(lib().gab_kmer_count_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
-                                          C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int32(min_len), C.byref(res),
-                                          C.c_void_p(stream)))
-        return self._dict(res)
+        return self.count_part_device(seq, off, ln, k, 0, 1, min_len, stream)
 
     def reserve_part(self, max_reads, max_seq_bytes, nparts):
         check(lib().gab_kmer_reserve_part(self._h, C.c_int64(max_reads), C.c_int64(max_seq_bytes), C.c_int(nparts)))
@@ -109,8 +111,7 @@ class KmerCounter:
     def count_part(self, reads, k, part, nparts, min_len=5000):
         """count() for partition `part` of `nparts` of the key space: reads_kept and positions are the whole call's, the other four
         fields the partition's, and the handle then holds the partition (spectrum, query, dump, last_stats)"""
-        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
-        seq = np.ascontiguousarray(seq, np.uint8); off = np.ascontiguousarray(off, np.int64); ln = np.ascontiguousarray(ln, np.int32)
+        seq, off, ln = self._packed(reads)
         res = _Result(*([-12345] * 6))
         check(lib().gab_kmer_count_part(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), C.c_int(k), C.c_int32(min_len), C.c_int(part),
                                         C.c_int(nparts), C.byref(res)))
@@ -119,16 +120,18 @@ class KmerCounter:
     def count_part_device(self, seq, off, ln, k, part, nparts, min_len=5000, stream=0):
         """torch tensors on the handle's GPU: uint8 / int64 / int32"""
         res = _Result(*([-12345] * 6))
-        check(lib().gab_kmer_count_part_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
-                                               C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int32(min_len), C.c_int(part),
-                                               C.c_int(nparts), C.byref(res), C.c_void_p(stream)))
+        check(lib().gab_kmer_count_part_device(self._h, *_dev(seq, off, ln), C.c_int(k), C.c_int32(min_len), C.c_int(part), C.c_int(nparts), C.byref(res),
+                                               C.c_void_p(stream)))
         return self._dict(res)
+
+    def _last_part(self, fn):
+        part = C.c_int(-1); nparts = C.c_int(-1); slots = C.c_int64(-1); retried = C.c_int(-1)
+        check(fn(self._h, C.byref(part), C.byref(nparts), C.byref(slots), C.byref(retried)))
+        return {"part": part.value, "nparts": nparts.value, "table_slots": slots.value, "retried": retried.value}
 
     def last_part(self):
         """what the last count ran as: its partition, the slots of the table it ended in, whether its first table filled up and it ran again"""
-        part = C.c_int(-1); nparts = C.c_int(-1); slots = C.c_int64(-1); retried = C.c_int(-1)
-        check(lib().gab_kmer_last_part(self._h, C.byref(part), C.byref(nparts), C.byref(slots), C.byref(retried)))
-        return {"part": part.value, "nparts": nparts.value, "table_slots": slots.value, "retried": retried.value}
+        return self._last_part(lib().gab_kmer_last_part)
 
     def spectrum(self, nbins):
         hist = np.full(nbins, -12345, np.int64)
@@ -169,11 +172,6 @@ class KmerCounter:
                 "pack_ms": a.value, "count_ms": b.value, "reduce_ms": c.value}
 
     # ---- minimizer mode -------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _packed(reads):
-        seq, off, ln = reads if isinstance(reads, tuple) else pack_reads(reads)
-        return np.ascontiguousarray(seq, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(ln, np.int32)
-
     def sketch_into(self, reads, k, window, read_start, pos, min_len=5000):
         """one raw gab_kmer_sketch into the caller's arrays: (return code, needed size)"""
         seq, off, ln = self._packed(reads)
@@ -202,8 +200,7 @@ class KmerCounter:
         """torch tensors on the handle's GPU: seq uint8, off int64, ln int32; outputs read_start int64 [n + 1] and pos int32 [capacity]
         -> (return code, needed size); ERANGE when pos is too small (nothing written)"""
         n = C.c_int64(-1)
-        rc = lib().gab_kmer_sketch_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()), C.c_void_p(ln.data_ptr()),
-                                          C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len), C.c_void_p(read_start.data_ptr()),
+        rc = lib().gab_kmer_sketch_device(self._h, *_dev(seq, off, ln), C.c_int(k), C.c_int(window), C.c_int32(min_len), C.c_void_p(read_start.data_ptr()),
                                           C.c_void_p(pos.data_ptr()), C.c_int64(pos.numel()), C.byref(n), C.c_void_p(stream))
         if rc != ERANGE:
             check(rc)
@@ -224,9 +221,8 @@ class KmerCounter:
     def index_minimizers_device(self, seq, off, ln, k, window, rate=100.0, min_len=5000, stream=0):
         """torch tensors on the handle's GPU: uint8 / int64 / int32"""
         res = _IndexResult(*([-12345] * 9))
-        check(lib().gab_kmer_index_minimizers_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
-                                                     C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len),
-                                                     C.c_float(rate), C.byref(res), C.c_void_p(stream)))
+        check(lib().gab_kmer_index_minimizers_device(self._h, *_dev(seq, off, ln), C.c_int(k), C.c_int(window), C.c_int32(min_len), C.c_float(rate),
+                                                     C.byref(res), C.c_void_p(stream)))
         return self._index_dict(res)
 
     def index_part_begin(self, reads, k, window, part, nparts, min_len=5000):
@@ -242,9 +238,8 @@ class KmerCounter:
     def index_part_begin_device(self, seq, off, ln, k, window, part, nparts, min_len=5000, stream=0):
         """torch tensors on the handle's GPU: uint8 / int64 / int32; `ln` must stay alive and unchanged until index_part_finish"""
         res = _IndexResult(*([-12345] * 9))
-        check(lib().gab_kmer_index_part_begin_device(self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(off.data_ptr()),
-                                                     C.c_void_p(ln.data_ptr()), C.c_int64(ln.numel()), C.c_int(k), C.c_int(window), C.c_int32(min_len),
-                                                     C.c_int(part), C.c_int(nparts), C.byref(res), C.c_void_p(stream)))
+        check(lib().gab_kmer_index_part_begin_device(self._h, *_dev(seq, off, ln), C.c_int(k), C.c_int(window), C.c_int32(min_len), C.c_int(part),
+                                                     C.c_int(nparts), C.byref(res), C.c_void_p(stream)))
         return self._index_dict(res)
 
     def index_part_finish(self, minimizers, distinct, rate=100.0):
@@ -257,9 +252,7 @@ class KmerCounter:
 
     def index_last_part(self):
         """what the last index build ran as: its partition, the slots of the capacity table it ended in, whether the first one filled up"""
-        part = C.c_int(-1); nparts = C.c_int(-1); slots = C.c_int64(-1); retried = C.c_int(-1)
-        check(lib().gab_kmer_index_last_part(self._h, C.byref(part), C.byref(nparts), C.byref(slots), C.byref(retried)))
-        return {"part": part.value, "nparts": nparts.value, "table_slots": slots.value, "retried": retried.value}
+        return self._last_part(lib().gab_kmer_index_last_part)
 
     def index_dump_into(self, kmers, start, gpos):
         """one raw gab_kmer_index_dump: (return code, needed k-mers, needed entries); start needs kmers.size + 1 of room"""
@@ -323,24 +316,9 @@ class KmerCounterSet:
 
     def count(self, reads, k, min_len=5000):
         """every partition at once, one host thread per handle -> the six fields of the whole input"""
-        packed = reads if isinstance(reads, tuple) else pack_reads(reads)
+        packed = KmerCounter._packed(reads)
         n = len(self.parts)
-        out = [None] * n
-
-        def run(i):
-            try:
-                out[i] = self.parts[i].count_part(packed, k, i, n, min_len)
-            except Exception as e:      # (handed to the caller's thread below)
-                out[i] = e
-        threads = [threading.Thread(target=run, args=(i,)) for i in range(1, n)]
-        for t in threads:
-            t.start()
-        run(0)
-        for t in threads:
-            t.join()
-        for r in out:
-            if isinstance(r, Exception):
-                raise r
+        out = self._each(lambda i: self.parts[i].count_part(packed, k, i, n, min_len))
         both = {f: out[0][f] for f in ("reads_kept", "positions")}
         both.update({f: sum(r[f] for r in out) for f in ("distinct", "total_kmers", "hash_size")})
         both["max_count"] = max(r["max_count"] for r in out)
@@ -368,7 +346,6 @@ class KmerCounterSet:
         """one row per partition: last_stats() and last_part() of its handle"""
         return [dict(kc.last_stats(), **kc.last_part()) for kc in self.parts]
 
-    # ---- minimizer mode: the index in key-space partitions, built in two phases ------------------------------------------------------
     def _each(self, call):
         """call(i) for every handle at once, one host thread per handle -> the list of results; the first exception is raised here"""
         n = len(self.parts)
@@ -390,6 +367,7 @@ class KmerCounterSet:
                 raise r
         return out
 
+    # ---- minimizer mode: the index in key-space partitions, built in two phases ------------------------------------------------------
     def index_minimizers(self, reads, k, window, rate=100.0, min_len=5000):
         """two rounds of one host thread per handle: every partition sketches all reads and counts its own capacities; the sums of
         their minimizers and distinct k-mers give the one threshold every partition then filters with -> the nine fields of the whole

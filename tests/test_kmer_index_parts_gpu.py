@@ -327,6 +327,69 @@ def test_device_form_equals_the_host_form(handles):
         np.testing.assert_array_equal(a, b)
 
 
+def test_every_operation_reads_one_input_the_same_way(handles):
+    """count, sketch, index and the two-phase index take their reads through one descriptor, filled from host pointers or from
+    device pointers: on one tiny input both forms of every operation give equal fields and equal dumps, and the three partitions
+    add up to the unpartitioned call.  The reads: a second tile of a single position | min_len + 1 bases, kept | min_len bases,
+    filtered | k bases, kept without a position"""
+    import torch
+    from genarchbench_amd.kmer import pack_reads
+    k, w, min_len, nparts = 5, 4, 3, 3
+    reads = [rand(80, TILE + 1 + k), rand(81, min_len + 1), rand(82, min_len), rand(83, k)]
+    seq, off, ln = pack_reads(reads)
+    t_seq, t_off, t_ln = (torch.from_numpy(a).to("cuda:0") for a in (seq, off, ln))
+    hs, one = handles[:nparts], handles[3]
+
+    def same(a, b):
+        for x, y in zip(a, b):
+            np.testing.assert_array_equal(x, y)
+
+    # count_part
+    host = [hs[p].count_part(reads, k, p, nparts, min_len) for p in range(nparts)]
+    host_dumps = [hs[p].dump() for p in range(nparts)]
+    assert [hs[p].count_part_device(t_seq, t_off, t_ln, k, p, nparts, min_len) for p in range(nparts)] == host
+    for p in range(nparts):
+        same(hs[p].dump(), host_dumps[p])
+    whole = one.count(reads, k, min_len)
+    assert (whole["reads_kept"], whole["positions"]) == (3, TILE + 1)
+    assert all((r["reads_kept"], r["positions"]) == (3, TILE + 1) for r in host)
+    assert {f: sum(r[f] for r in host) for f in ("distinct", "total_kmers", "hash_size")} == {f: whole[f] for f in ("distinct", "total_kmers", "hash_size")}
+    assert max(r["max_count"] for r in host) == whole["max_count"]
+    kmers = np.concatenate([d[0] for d in host_dumps]); counts = np.concatenate([d[1] for d in host_dumps])
+    order = np.argsort(kmers, kind="stable")
+    same((kmers[order], counts[order]), one.dump())
+    assert one.count_device(t_seq, t_off, t_ln, k, min_len) == whole
+    same(one.dump(), (kmers[order], counts[order]))
+
+    # sketch
+    start, pos = one.sketch(reads, k, w, min_len)
+    assert start[0] == 0 and (np.diff(start)[1:] == 0).all() and pos.size == start[-1] > 0
+    t_start = torch.full((len(reads) + 1,), -12345, dtype=torch.int64, device="cuda:0")
+    t_pos = torch.full((pos.size,), -12345, dtype=torch.int32, device="cuda:0")
+    assert one.sketch_device(t_seq, t_off, t_ln, k, w, t_start, t_pos, min_len) == (0, pos.size)
+    same((t_start.cpu().numpy(), t_pos.cpu().numpy()), (start, pos))
+
+    # index_minimizers
+    whole = one.index_minimizers(reads, k, w, 3, min_len)
+    whole_dump = one.index_dump()
+    assert (whole["reads_kept"], whole["total_len"], whole["minimizers"]) == (3, TILE + 1 + k + min_len + 1 + k, pos.size)
+    assert one.index_minimizers_device(t_seq, t_off, t_ln, k, w, 3, min_len) == whole
+    same(one.index_dump(), whole_dump)
+
+    # index_part_begin -> index_part_finish
+    begun = [hs[p].index_part_begin(reads, k, w, p, nparts, min_len) for p in range(nparts)]
+    M, U = sum(b["minimizers"] for b in begun), sum(b["distinct"] for b in begun)
+    assert (M, U) == (whole["minimizers"], whole["distinct"])
+    done = [hs[p].index_part_finish(M, U, 3) for p in range(nparts)]
+    dumps = [hs[p].index_dump() for p in range(nparts)]
+    assert [hs[p].index_part_begin_device(t_seq, t_off, t_ln, k, w, p, nparts, min_len) for p in range(nparts)] == begun
+    assert [hs[p].index_part_finish(M, U, 3) for p in range(nparts)] == done
+    for p in range(nparts):
+        same(hs[p].index_dump(), dumps[p])
+    assert pu.sum_fields(done) == whole
+    same(pu.merge(dumps), whole_dump)
+
+
 # ---- 10. the set ---------------------------------------------------------------------------------------------------------------------------
 def test_the_set_equals_one_counter(kc):
     from genarchbench_amd.kmer import KmerCounterSet
