@@ -73,3 +73,11 @@ class ChainEngine:
         ev = C.c_int64(0); ms = C.c_float(0)
         check(lib().gab_chain_last_stats(self._h, C.byref(ev), C.byref(ms)))
         return {"evals": ev.value, "kernel_ms": ms.value}
+
+    def last_split(self, ncalls):
+        """which kernel form took each call of the last run_device / run_device_through call (gab_chain_last_split; host_chain_kernel too
+        below its big-batch paths): (form, counters) -- form[c] 0 empty, 1 throughput, 2 latency, 3 table, 4 table: not eligible,
+        5 table: handed back, 6 legacy-only launch; counters {no_room, rescans, helpers, groups_needed}"""
+        form = np.full(ncalls, 255, np.uint8); ct = (C.c_int64 * 4)()
+        check(lib().gab_chain_last_split(self._h, C.c_int64(ncalls), _p(form), ct))
+        return form, dict(zip(("no_room", "rescans", "helpers", "groups_needed"), (int(v) for v in ct)))

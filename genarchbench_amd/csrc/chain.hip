@@ -1785,6 +1785,14 @@ struct gab_chain {
     uint8_t *h_started = nullptr;            // pinned: one byte per workgroup of chain_gather_kernel
     hipEvent_t xe_fed = nullptr;
     bool have_stats = false;
+    // gab_chain_last_split: the host-side facts of the last gab_chain_run_device[_through] call (what the device knows -- eligibility,
+    // bail words, counters -- stays in `tab`'s buffers until it is asked for)
+    struct Split {
+        bool valid = false, legacy_only = false;
+        size_t ntab = 0, nfast = 0;          // the sorted list: [0, ntab) table form, [ntab, ntab + nfast) latency form
+        int helpers = 0;                     // helper waves of the single launch when neither form took a call (chain_launch)
+        std::vector<int32_t> n;              // anchors of every call in the caller's order: the sorted order is rebuilt from it
+    } split;
     ChainTab tab;                            // the table form's buffers (chain_tab.hip)
     hipStream_t ts = nullptr;                // ... and its stream: it runs beside the other two forms
     hipEvent_t te[2] = {nullptr, nullptr};
@@ -1925,7 +1933,8 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     GAB_CHECK(mode == GAB_CHAIN || mode == GAB_FASTCHAIN, "gab_chain_run_device: unknown mode %d", mode);
     GAB_CHECK(ncalls >= 0 && ncalls < (1ll << 31), "gab_chain_run_device: ncalls out of range");
     h->have_stats = false;
-    if (ncalls == 0) return GAB_OK;
+    h->split.valid = false;
+    if (ncalls == 0) { h->split = gab_chain::Split(); h->split.valid = true; return GAB_OK; }
     GAB_CHECK(call_off && hdr, "gab_chain_run_device: NULL call table");
     int64_t total = 0;
     int rc = chain_check_hdrs(hdr, call_off, ncalls, &total);
@@ -1938,7 +1947,9 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     // longest call first: the sequential walk of the biggest call is the critical path
     std::vector<ChainWork> wk;
     wk.reserve((size_t)ncalls);
+    h->split.n.resize((size_t)ncalls);
     for (int64_t c = 0; c < ncalls; c++) {
+        h->split.n[(size_t)c] = (int32_t)hdr[c].n;
         if (hdr[c].n == 0) continue;
         ChainWork w;
         w.off = w.hoff = call_off[c]; w.n = hdr[c].n; w.avg_qspan = hdr[c].avg_qspan;
@@ -1951,7 +1962,7 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     const size_t o_ev = (sizeof(ChainWork) * nw + 15) & ~(size_t)15;
     rc = h->work.reserve(o_ev + 16);
     if (rc) return rc;
-    if (nw == 0) return GAB_OK;
+    if (nw == 0) { h->split.legacy_only = false; h->split.ntab = h->split.nfast = 0; h->split.helpers = 0; h->split.valid = true; return GAB_OK; }
     GAB_CHECK_ATOMIC64(o_ev);
     ChainWork *d_work = h->work.as<ChainWork>();
     unsigned long long *d_ev = (unsigned long long *)(h->work.as<char>() + o_ev);
@@ -2105,6 +2116,9 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     }
     if (ntab && h->tun.chain_trace) chain_tab_report(&h->tab, ntab);
     h->have_stats = true;
+    h->split.legacy_only = legacy_only; h->split.ntab = ntab; h->split.nfast = nfast;
+    h->split.helpers = (ntab || nfast) ? 0 : (mode == GAB_CHAIN && h->tun.chain_walk) ? kChHelpers : chain_helpers_for(h->tun, total, wk[0].n);
+    h->split.valid = true;
     return GAB_OK;
 }
 
@@ -2122,6 +2136,7 @@ static int chain_run_overlapped(gab_chain *h, int mode, const uint64_t *x, const
                                 const gab_chain_hdr *hdr, int64_t ncalls, int64_t total, int32_t *score_out, int32_t *parent_out,
                                 hipStream_t sA) {
     h->have_stats = false;
+    h->split.valid = false;
     const size_t t = (size_t)total;
     char *b = h->io.as<char>();
     uint64_t *dx = (uint64_t *)b, *dy = (uint64_t *)(b + 8 * t);
@@ -2295,6 +2310,7 @@ static int chain_run_fed(gab_chain *h, int mode, const uint64_t *x, const uint64
         return 1;
     }
     h->have_stats = false;
+    h->split.valid = false;
     int gather_blocks = 256;
     {
         const int rc0 = chain_fed_setup(h, &gather_blocks);
@@ -2550,6 +2566,7 @@ extern "C" int gab_chain_reserve_mode(gab_chain *h, int mode, int64_t max_anchor
     const bool had = h->have_stats;
     rc = gab_chain_run_device(h, mode, d_x, d_y, &off, &hd, 1, d_s, d_p, s);
     h->have_stats = had;
+    h->split.valid = false;      // (the warm-up call is not a run of the caller's, and it has used the table form's call list)
     if (rc) return rc;
     if (h->tun.chain_tab != 0) rc = chain_tab_prealloc(&h->tab, max_anchors, max_calls);
     return rc;
@@ -2562,5 +2579,36 @@ extern "C" int gab_chain_last_stats(gab_chain *h, int64_t *evals, float *kernel_
     GAB_HIP(hipEventSynchronize(h->ev[1]));
     if (evals) *evals = (int64_t)*h->h_evals;
     if (kernel_ms) GAB_HIP(hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]));
+    return GAB_OK;
+}
+
+// Which kernel form took each call of the last gab_chain_run_device[_through] call (include/gab.h).  Nothing of this is gathered
+// while a run is under way: the split of the sorted list is three host-side numbers, the sorted order follows from the calls'
+// lengths (the stable sort of the run, done again here), and what the table form decided on the device -- TabCall.ok, the bail
+// words, its counters -- is read from the handle's buffers now, where it lives until the handle's next run.
+extern "C" int gab_chain_last_split(gab_chain *h, int64_t ncalls, uint8_t *form, int64_t counters[4]) {
+    GAB_CHECK(h, "gab_chain_last_split: NULL handle");
+    GAB_CHECK(h->split.valid, "gab_chain_last_split: no completed gab_chain_run_device call on this handle");
+    const gab_chain::Split &sp = h->split;
+    GAB_CHECK(ncalls == (int64_t)sp.n.size(), "gab_chain_last_split: ncalls = %lld, the last run had %lld calls", (long long)ncalls, (long long)sp.n.size());
+    std::vector<uint8_t> tabform(sp.ntab, 0);
+    int64_t ct[4] = {0, 0, 0, 0};
+    if (sp.ntab) {
+        gab_device_guard g(h->device);
+        const int rc = chain_tab_split(&h->tab, sp.ntab, tabform.data(), ct);
+        if (rc) return rc;
+    }
+    ct[2] = sp.legacy_only ? sp.helpers : 0;
+    if (counters) for (int k = 0; k < 4; k++) counters[k] = ct[k];
+    if (!form) return GAB_OK;
+    std::vector<int64_t> order;
+    order.reserve(sp.n.size());
+    for (int64_t c = 0; c < ncalls; c++) {
+        form[c] = 0;
+        if (sp.n[(size_t)c] > 0) order.push_back(c);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return sp.n[(size_t)a] > sp.n[(size_t)b]; });
+    for (size_t k = 0; k < order.size(); k++)
+        form[order[k]] = sp.legacy_only ? 6 : k < sp.ntab ? tabform[k] : k < sp.ntab + sp.nfast ? 2 : 1;
     return GAB_OK;
 }

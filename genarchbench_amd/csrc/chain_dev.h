@@ -208,5 +208,6 @@ int chain_tab_run(ChainTab *t, const gab_tuning &tun, int mode, hipStream_t s, c
                   const uint64_t *d_x, const uint64_t *d_y, int32_t *d_score, int32_t *d_parent, int32_t *d_gm, unsigned long long *d_evals, uint32_t **d_bail,
                   int32_t *host_score = nullptr, int32_t *host_parent = nullptr);      // (device-visible addresses of page-locked host arrays: results written through)
 void chain_tab_report(ChainTab *t, size_t nsplit);      // GAB_CHAIN_TRACE: what the last run did with its calls (after a synchronisation)
+int chain_tab_split(ChainTab *t, size_t nsplit, uint8_t *form, int64_t counters[4]);      // gab_chain_last_split: after a synchronisation, like the report
 int chain_tab_setup();      // function attributes (dynamic LDS), once
 int chain_tab_prealloc(ChainTab *t, int64_t max_anchors, int64_t max_calls);

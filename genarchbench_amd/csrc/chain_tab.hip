@@ -1005,6 +1005,23 @@ void chain_tab_report(ChainTab *t, size_t nsplit) {
     }
 }
 
+// gab_chain_last_split: what the last run's table form did with its `nsplit` calls (sorted order) -- 3 folded here, 4 not eligible
+// (ctab_prep), 5 eligible but handed back (no room: ctab_place; certificate / patches: the fold) -- and its counters
+int chain_tab_split(ChainTab *t, size_t nsplit, uint8_t *form, int64_t counters[4]) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_bail = up(sizeof(TabCall) * nsplit), o_ct = o_bail + up(4 * nsplit);
+    GAB_CHECK(t->calls.p && t->calls.cap >= o_ct + sizeof(TabCounters), "gab_chain_last_split: the table form's call list is gone");
+    std::vector<TabCall> hc(nsplit);
+    std::vector<uint32_t> hb(nsplit);
+    TabCounters ct;
+    GAB_HIP(hipMemcpy(hc.data(), t->calls.p, sizeof(TabCall) * nsplit, hipMemcpyDeviceToHost));
+    GAB_HIP(hipMemcpy(hb.data(), t->calls.as<char>() + o_bail, 4 * nsplit, hipMemcpyDeviceToHost));
+    GAB_HIP(hipMemcpy(&ct, t->calls.as<char>() + o_ct, sizeof ct, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nsplit; k++) form[k] = !hc[k].ok ? 4 : hb[k] ? 5 : 3;
+    counters[0] = ct.no_room; counters[1] = ct.rescans; counters[2] = 0; counters[3] = (int64_t)ct.groups_needed;
+    return GAB_OK;
+}
+
 int chain_tab_run(ChainTab *t, const gab_tuning &tun, int mode, hipStream_t s, const ChainWork *d_work, const ChainWork *h_work, size_t nsplit, int64_t total_anchors,
                   const uint64_t *d_x, const uint64_t *d_y, int32_t *d_score, int32_t *d_parent, int32_t *d_gm, unsigned long long *d_evals, uint32_t **d_bail,
                   int32_t *host_score, int32_t *host_parent) {

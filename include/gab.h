@@ -166,6 +166,22 @@ int gab_chain_run_device_through(gab_chain *h, int mode, const uint64_t *d_x, co
  * reference's own visits for the anchors that needed its max_skip scan; fast-chain: the windows) and kernel time (HIP
  * events) of the last run */
 int gab_chain_last_stats(gab_chain *h, int64_t *evals, float *kernel_ms);
+/* which kernel form took each call of the last gab_chain_run_device / _through call on this handle (gab_chain_run too, where it
+ * goes through gab_chain_run_device: batches below its big-batch paths).  ncalls must be that call's.  form[c], in the caller's call order:
+ *   0 empty call
+ *   1 throughput form
+ *   2 latency form
+ *   3 table form, folded there
+ *   4 table form, not eligible
+ *   5 table form, eligible but handed back (no room in the table, or by the fold)
+ *   6 the legacy-only launch (GAB_CHAIN_KERNEL=walk for GAB_CHAIN, or GAB_CHAIN_HELPERS set)
+ * (4 and 5: the call was then computed by the latency-form kernel behind the table form.)
+ * counters: {calls that found no room in the table, exact re-scans that confirmed the fold's result, helper waves of the legacy-only
+ * launch or 0, 16-row groups of table the eligible calls needed}.  form and counters may be NULL.
+ * A run records nothing for this on the device and copies nothing: the call list of the table form is read here, from the
+ * handle's buffers, where it stays until the handle's next run (or gab_chain_reserve_mode call, whose warm-up run uses them).
+ * GAB_EINVAL: no such run since, or another ncalls. */
+int gab_chain_last_split(gab_chain *h, int64_t ncalls, uint8_t *form, int64_t counters[4]);
 
 /* ---- bpm: bit-parallel Myers edit distance (+ backtrace-derived score) -----------------
  * Replaces  it->score = benchmark_edit_bpm(&align_input)   bpm/tools/align_benchmark.c:243-257

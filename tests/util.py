@@ -906,3 +906,79 @@ def wfa_expected_resumed(name):
     maybe = left & ~wfa_pad_bytes(batch) & (model["max_m"] > WFA_OFFB_SAFE) & (r_pool < launches[0][2])
     n_left, n_sure, n_maybe, slots = int(left.sum()), int(sure.sum()), int(maybe.sum()), plan["slots"]
     return max(0, min(slots, n_left) - (n_left - n_sure)), min(slots, n_sure + n_maybe)
+
+
+# ---- chain: which kernel form a call of a batch is sent to (genarchbench_amd/csrc/chain.hip, the batch-shape rule of gab_chain_run_device)
+CHAIN_FORM_THROUGHPUT, CHAIN_FORM_LATENCY, CHAIN_FORM_TABLE, CHAIN_FORM_LEGACY = 1, 2, 3, 6
+CHAIN_DISPATCH = {                      # the four settings tests/test_chain_gpu.py runs under
+    "default-split": {},
+    "latency-form-for-all": {"GAB_CHAIN_FAST_MIN": "1", "GAB_CHAIN_FAST_CALLS": "1000000000", "GAB_CHAIN_TAB": "0"},
+    "throughput-form-for-all": {"GAB_CHAIN_FAST_CALLS": "0", "GAB_CHAIN_TAB": "0"},
+    "table-form-for-all": {"GAB_CHAIN_TAB_MIN": "1"},
+}
+CHAIN_SPLIT_KNOBS = ("GAB_CHAIN_TAB", "GAB_CHAIN_TAB_MIN", "GAB_CHAIN_FAST_MIN", "GAB_CHAIN_FAST_CALLS", "GAB_CHAIN_KERNEL", "GAB_CHAIN_HELPERS")
+
+
+def chain_split_model(n_per_call, mode, env=None):
+    """the form gab_chain_run_device sends every call of a batch to, BEFORE the forms' own eligibility tests: 0 empty call,
+    1 throughput form, 2 latency form, 3 table form, 6 the legacy-only launch -- per call, in the caller's order.  n_per_call: anchors of
+    the calls (back to back: the batch's anchors are their sum); mode 0 chain, 1 fast-chain; env: the GAB_CHAIN_* pins that are set.
+
+    The rule, as chain.hip words it.  The calls are sorted longest first (stable).  The throughput form takes ~0.30 us per anchor of a
+    call and does ~2.85 G anchors/s over all calls; a batch whose longest call needs at least 0.75 of the batch's throughput time WAITS
+    for it.  Such a batch hands to the table form every call that would take a quarter of that time, 2 048 anchors at least; whatever
+    the batch, fast-chain sends calls of >= 4 096 anchors there and chain those of >= 8 192 (not modelled: the written-through entry
+    point has no such floors).  GAB_CHAIN_TAB_MIN pins the table form's smallest call, GAB_CHAIN_TAB=0 turns the form off.  The same test on what is left
+    (its anchors, its longest call) hands every remaining call of >= 512 anchors to the latency form; GAB_CHAIN_FAST_MIN pins that
+    length and GAB_CHAIN_FAST_CALLS the number of calls (FAST_MIN alone: as many as there are).  The rest is the throughput form's.
+    GAB_CHAIN_HELPERS, and GAB_CHAIN_KERNEL=walk for chain, send everything through one launch of the older kernels instead."""
+    env = env or {}
+    pin = lambda k: int(env[k]) if k in env else -1
+    n = np.asarray(n_per_call, np.int64)
+    form = np.zeros(len(n), np.uint8)
+    order = [int(c) for c in np.argsort(-n, kind="stable") if n[c] > 0]
+    if not order:
+        return form
+    if "GAB_CHAIN_HELPERS" in env or (mode == 0 and env.get("GAB_CHAIN_KERNEL") == "walk"):
+        form[order] = CHAIN_FORM_LEGACY
+        return form
+    srt = [int(n[c]) for c in order]
+    total, per_anchor, rate, wait = sum(srt), 0.30e-6, 2.85e9, 0.75
+    ntab = 0
+    if pin("GAB_CHAIN_TAB") != 0:
+        tp = total / rate
+        least = max(2048, int(0.25 * tp / per_anchor)) if per_anchor * srt[0] >= wait * tp else None
+        floor = 4096 if mode == 1 else 8192
+        least = floor if least is None else min(least, floor)
+        if pin("GAB_CHAIN_TAB_MIN") >= 0:
+            least = pin("GAB_CHAIN_TAB_MIN")
+        while ntab < len(srt) and srt[ntab] >= least:
+            ntab += 1
+    rest = srt[ntab:]
+    nfast = 0
+    if rest:
+        tp = sum(rest) / rate
+        least, most = (512, len(rest)) if per_anchor * rest[0] >= wait * tp else (0, 0)
+        if pin("GAB_CHAIN_FAST_MIN") >= 0:
+            least = pin("GAB_CHAIN_FAST_MIN")
+            most = len(rest)
+        if pin("GAB_CHAIN_FAST_CALLS") >= 0:
+            most = pin("GAB_CHAIN_FAST_CALLS")
+        while nfast < min(len(rest), most) and rest[nfast] >= least:
+            nfast += 1
+    form[order[:ntab]] = CHAIN_FORM_TABLE
+    form[order[ntab:ntab + nfast]] = CHAIN_FORM_LATENCY
+    form[order[ntab + nfast:]] = CHAIN_FORM_THROUGHPUT
+    return form
+
+
+def chain_split_margins(n_per_call, mode):
+    """how far the floating-point comparisons of the default rule are from flipping on this batch: the ratios (longest call's time) /
+    (0.75 of the throughput time) of the two stages, for the table form and for what it leaves -- a test batch keeps both 10 %
+    away from 1 (the lengths themselves are compared as integers)"""
+    n = sorted((int(v) for v in n_per_call if v > 0), reverse=True)
+    ntab = int((chain_split_model(n, mode) == CHAIN_FORM_TABLE).sum())
+    out = [0.30e-6 * n[0] / (0.75 * sum(n) / 2.85e9)]
+    if n[ntab:]:
+        out.append(0.30e-6 * n[ntab] / (0.75 * sum(n[ntab:]) / 2.85e9))
+    return out
