@@ -1,26 +1,31 @@
 // chain / fast-chain -- minimap2 seed-chaining DP on gfx950.
 //
 // Semantics
-//   mode CHAIN     : chain_dp of /root/reference/benchmarks/chain/src/host_kernel.cpp:30-94
+//   mode CHAIN     : chain_dp of the reference, benchmarks/chain/src/host_kernel.cpp:30-94
 //                    (64-bit anchors, segment ids, max_iter = 5000, max_skip = 25 via targets[]).
-//   mode FASTCHAIN : chain_dp of /root/reference/benchmarks/fast-chain/src/host_kernel.cpp as its
+//   mode FASTCHAIN : chain_dp of the reference, benchmarks/fast-chain/src/host_kernel.cpp, as its
 //                    AVX2 (:408-683) and AVX-512 (:175-407) builds compute it: 32-bit truncated
 //                    coordinates, no max_skip, fp32 floor gap cost when the window holds more
 //                    than six predecessors, double otherwise.
 //
-// Mapping.  The scores along i are a true recurrence (score[i] needs score[i-1]) and a batch takes as long as the walk
-// of its slowest call, so everything is arranged around the latency of one anchor step:
-//   * CHAIN (chain_hw_kernel): one main wave per call carries the dependence; the last 512 anchors (x, y, score,
-//     parent, segment id) live in an LDS ring; each lane owns an aligned group of four predecessors, a super-chunk is
-//     256 predecessors.  Two helper waves compute everything that does not depend on earlier results -- window start,
-//     filters, min(dq, dr, q_span) and the gap cost of the 256 newest predecessors -- eight anchors ahead into LDS.
-//     The sequential max_skip logic is reproduced exactly in three parallel steps: unfiltered
-//     items scatter their marks targets[parent[j]] = i into a tagged 16-bit LDS ring (a global array for windows
-//     deeper than the ring), the improvement flags come from an exclusive prefix-max (DPP scan), and the saturating
-//     n_skip counter has a closed form over the prefix sums of (+1 hit, -1 improvement).  Marks scattered by items
-//     past the break point are harmless because a mark value i is only ever compared with the current i.
-//   * FASTCHAIN (fastchain_kernel): block formulation, see below.
-//   * thousands of independent calls run concurrently, longest call first.
+// The scores along i are a true recurrence (score[i] needs score[i-1]) and a batch takes as long as its slowest call, so every
+// form below is arranged around the latency of one anchor step; thousands of independent calls run concurrently, longest first.
+//
+// Map of this file (chain_dev.h: what it shares with chain_tab.hip -- the DPP scans, chain_geometry and the gap costs, the window
+// test and the one-pointer window search, the per-call "plain" fact and its reduction, the exact max_skip scan chain_exact_global)
+//   the fed path's device side   ChainFeed, chain_feed_wait, chain_gather_kernel: the anchors come in by a kernel, longest call first
+//   chain_hw_kernel              chain only, GAB_CHAIN_KERNEL=walk: the per-anchor walk, kept as the A/B variant it is
+//   throughput form              fastchain_kernel* / chain_block_kernel* (fastchain_body, chain_block_body): blocks of 64 anchors, one
+//                                main wave and 3 / 5 / 7 helper waves per call, several calls per CU; chain_facts_kernel in front of it
+//   latency form                 chain_fast_kernel<mode>: one call per CU, sixteen waves with one job each
+//   table form                   chain_tab.hip (chain_tab_run): the geometry of every block by any CU, the call's workgroup only folds;
+//                                calls it hands back run in the latency form behind it
+//   host side                    chain_split decides which calls of a sorted work list take which form, chain_launch / chain_launch_fast
+//                                are the only places that name a kernel instantiation.  Entry points:
+//       gab_chain_run_device[_through]  ->  chain_run_device_impl: split, up to three streams (table | latency | throughput form)
+//       gab_chain_run                   ->  small batches: copy in, gab_chain_run_device, copy out
+//                                           big batches, page-locked arrays: chain_run_fed (gather kernel + one fed throughput launch)
+//                                           big batches otherwise, or a fed run that gave up: chain_run_overlapped (three copy streams)
 //
 // Roofline: 24 B of HBM traffic per anchor (16 B in, 8 B out) against ~130-200 predecessor
 // evaluations per anchor: latency/VALU bound by construction; the window re-reads are served by
@@ -41,16 +46,16 @@ namespace {
 // ---- the host-pointer path of big batches: the anchors come in by a KERNEL, longest call first -----------------------
 // (see chain_run_fed).  A call's workgroup waits until its anchors are there and writes its results through to the caller's
 // page-locked arrays block by block; all members null = the plain device path.
+constexpr long kFeedSpinLimit = 600000;       // x ~7 us of s_sleep: a wait gives up after seconds, so the grid always drains
 struct ChainFeed {
-    uint32_t *facts;                          // per work item: 0 = anchors not here yet; 2 | (plain ? 1 : 0) once they are
-    int32_t *host_score, *host_parent;        // device addresses of the caller's result arrays
-    uint32_t *abort;                          // set by a wait that gave up; every other wait then gives up too
-    unsigned long long *dbg;                  // diagnosis (GAB_CHAIN_TRACE): per work item wall-clock ticks at start / ready / done
-    long spin_limit;                          // spins of a wait before it gives up (kFeedSpinLimit; tests: a few thousand)
+    uint32_t *facts = nullptr;                                // per work item: 0 = anchors not here yet; 2 | (plain ? 1 : 0) once they are
+    int32_t *host_score = nullptr, *host_parent = nullptr;    // device addresses of the caller's result arrays
+    uint32_t *abort = nullptr;                                // set by a wait that gave up; every other wait then gives up too
+    unsigned long long *dbg = nullptr;                        // diagnosis (GAB_CHAIN_TRACE): per work item wall-clock ticks at start / ready / done
+    long spin_limit = kFeedSpinLimit;                         // spins of a wait before it gives up (tests: a few thousand)
 };
 struct ChainChunk { int64_t hoff, doff; int32_t n, item; };   // up to kFeedChunk anchors of work item `item`: where they are, where they go
 constexpr int kFeedChunk = 2048;
-constexpr long kFeedSpinLimit = 600000;       // x ~7 us of s_sleep: a wait gives up after seconds, so the grid always drains
 
 // wait (thread 0, sleeping) until the anchors of this workgroup's call are in device memory; returns the facts word (0: gave up)
 __device__ __forceinline__ uint32_t gab_xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xfu; }   // HW_REG_XCC_ID
@@ -89,8 +94,6 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(const ChainChunk *__r
                                                            uint32_t *done, unsigned long long *xlo, unsigned long long *xhi,
                                                            uint32_t *mixed, uint32_t *facts, volatile uint8_t *started, int gap_tab_max,
                                                            uint32_t *next_chunk, unsigned long long *pub_dbg, uint32_t never_publish) {
-    __shared__ unsigned long long s_lo[4], s_hi[4];
-    __shared__ uint32_t s_mx[4];
     __shared__ uint32_t s_chunk;
     if (threadIdx.x == 0) started[blockIdx.x] = (uint8_t)(1u + gab_xcc_id());   // (host memory: the host launches the DP once every workgroup is resident, and learns where they are)
     // The chunks are handed out from ONE counter, in table order: workgroups read the bus at very different rates (a static
@@ -126,15 +129,9 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(const ChainChunk *__r
                 mx |= ((uint32_t)(y >> 48 & 0xff) != sid0) ? 1u : 0u;
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-            lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; mx |= __shfl_xor(mx, o);
-        }
-        if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_mx[threadIdx.x >> 6] = mx; }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's stores have completed (at the device's coherence point) ...
-        __syncthreads();                                         // ... and so have everybody's, before thread 0 counts the chunk
+        chain_block_range(lo, hi, mx);                           // ... and, behind its barrier, so have everybody's, before thread 0 counts the chunk
         if (threadIdx.x == 0) {
-            for (int k = 1; k < 4; k++) { lo = s_lo[k] < lo ? s_lo[k] : lo; hi = s_hi[k] > hi ? s_hi[k] : hi; mx |= s_mx[k]; }
             atomicMin(&xlo[ch.item], lo); atomicMax(&xhi[ch.item], hi);
             if (mx) atomicOr(&mixed[ch.item], 1u);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // the three have been performed before the chunk is counted
@@ -142,9 +139,7 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(const ChainChunk *__r
                 const unsigned long long L = __hip_atomic_load(&xlo[ch.item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                                          H = __hip_atomic_load(&xhi[ch.item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t M = __hip_atomic_load(&mixed[ch.item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int32_t mq = w.max_dist_y < w.max_dist_x ? w.max_dist_y : w.max_dist_x;
-                const unsigned long long lim = mq < 0 ? 0ull : (unsigned long long)mq;
-                const bool plain = w.n > 0 && !M && H - L + lim < 0x7fffffffull && w.bw >= 0 && w.bw <= gap_tab_max;   // = chain_facts_kernel
+                const bool plain = chain_call_plain(w, L, H, M != 0, gap_tab_max);
                 // (never_publish: GAB_CHAIN_FEED_GIVEUP, a test hook -- one call's word stays 0, so that its workgroup's wait gives up)
                 if ((uint32_t)ch.item != never_publish) __hip_atomic_store(&facts[ch.item], 2u | (plain ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (pub_dbg) pub_dbg[ch.item] = wall_clock64();
@@ -157,37 +152,25 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(const ChainChunk *__r
 constexpr int kRing = 1024;               // anchors whose score / parent are kept in the LDS ring
 constexpr int kRingSafe = kRing - 8;      // entries younger than this are read from the ring
 
-// ---- chain: the sequential walk (main wave) -----------------------------------------------------------------------
-// A call is walked by ONE wave (an earlier four-wave version spent most of its time on workgroup barriers and on
-// instructions all four waves executed for a window one wave can hold).  Each lane owns an ALIGNED group of four ring
-// entries (one ds_read_b128 per field), so a super-chunk is 256 predecessors and needs no barrier at all -- LDS
-// operations of one wave complete in program order.  Visiting order (descending j)
-// is lane order, and inside a lane item k = 0..3 <-> j = 4g+3-k.  The max_skip logic is the same three steps as
-// before with a 4-item sequential part inside the lane and wave scans across the lanes:
-//   marks     targets[parent[j]] = i for every unfiltered item (tagged 16-bit LDS ring / global array for deep windows)
+// ---- chain: the per-anchor walk, one main wave + helper waves (GAB_CHAIN_KERNEL=walk: A/B runs only) ------------------------------
+// The walk of one call is a chain of dependent anchors (~1.9 us per anchor here), carried by ONE wave: the newest kRing anchors
+// (score, parent) live in an LDS ring, each lane owns an ALIGNED group of four ring entries (one ds_read_b128 per field), so a
+// super-chunk is 256 predecessors and needs no barrier at all -- LDS operations of one wave complete in program order.  Visiting
+// order (descending j) is lane order, and inside a lane item k = 0..3 <-> j = 4g+3-k.
+// Most of an anchor's instructions do not depend on earlier results at all: the filters, min(dq, dr, q_span) and the gap cost are
+// pure geometry of (anchor, predecessor).  Helper waves compute that geometry one block of kChBlock anchors AHEAD (window start,
+// the kGeoDepth newest predecessors per anchor, coalesced reads of x / y) and leave it in LDS; the main wave only adds score[j].
+// Windows deeper than kGeoDepth continue in the main wave, which then evaluates the geometry itself.
+// The sequential max_skip logic is reproduced exactly in three parallel steps, a 4-item sequential part
+// inside the lane and wave scans across the lanes:
+//   marks     targets[parent[j]] = i for every unfiltered item (tagged 16-bit LDS ring / global array for deep windows); marks
+//             scattered by items past the break point are harmless: a mark value i is only ever compared with the current i
 //   improve   sc > max(prefix max over earlier items, best so far)
 //   n_skip    counter reflected at 0: c = P - min(-c_in, running min of P), P = prefix sums of (+1 hit, -1 improvement)
-// ---- chain: main wave + helper waves ------------------------------------------------------------------------------
-// The walk of one call is a chain of dependent anchors, and the time of the whole batch is the walk of its longest
-// call (~1.9 us per anchor with either kernel above).  Most of an anchor's instructions do not depend on earlier
-// results at all: the filters, min(dq, dr, q_span) and the gap cost are pure geometry of (anchor, predecessor).
-// Here helper waves compute that geometry one block of kChBlock anchors AHEAD (window start, 256 newest predecessors
-// per anchor, coalesced reads of x / y) and leave it in LDS; the main wave, which alone carries the dependence, only
-// adds score[j], and runs the marks / prefix-max / n_skip steps described above.  Windows deeper than 256
-// predecessors continue in the main wave, which then evaluates the geometry itself.
 constexpr int kChPriorityCalls = 128;         // the longest calls (= first workgroups) run at raised wave priority
-#ifndef GAB_CH_HELPERS                        // tuning builds only (-DGAB_CH_HELPERS=.. -DGAB_CH_BLOCK=.. -DGAB_CH_GEODEPTH=..)
-#define GAB_CH_HELPERS 3
-#endif
-#ifndef GAB_CH_BLOCK
-#define GAB_CH_BLOCK GAB_CH_HELPERS
-#endif
-#ifndef GAB_CH_GEODEPTH
-#define GAB_CH_GEODEPTH 1024
-#endif
-constexpr int kChHelpers = GAB_CH_HELPERS;
-constexpr int kChBlock = GAB_CH_BLOCK;
-constexpr int kGeoDepth = GAB_CH_GEODEPTH;   // predecessors per anchor the helpers prepare (kGeoDepth / 256 super-chunks)
+constexpr int kChHelpers = 3;
+constexpr int kChBlock = kChHelpers;          // anchors per block the helpers prepare: one each
+constexpr int kGeoDepth = 1024;               // predecessors per anchor the helpers prepare (kGeoDepth / 256 super-chunks)
 constexpr int kGeoNone = (int)0x80000000;      // predecessor filtered out (or outside the window)
 
 __global__ __launch_bounds__(64 * (1 + kChHelpers)) void chain_hw_kernel(const ChainWork *__restrict__ work,
@@ -230,21 +213,7 @@ __global__ __launch_bounds__(64 * (1 + kChHelpers)) void chain_hw_kernel(const C
                 const uint64_t xi = X[i], yi = Y[i];       // wave-uniform
                 // window start with the reference's sequential-pointer semantics (host_kernel.cpp:56-57); every helper
                 // tracks it for every anchor (a ballot per anchor), so the helpers need no exchange among themselves
-                for (;;) {
-                    const int cand = sb + lane;
-                    const bool far = xi > XS + mdx64;
-                    const bool pass = cand < st || (cand < i && far);
-                    const unsigned long long m = __ballot(pass);
-                    if (m == ~0ull) {
-                        sb += 64; st = sb;
-                        XS = (sb + lane < n) ? X[sb + lane] : 0;
-                        continue;
-                    }
-                    st = sb + __builtin_ctzll(~m);
-                    break;
-                }
-                if (i - st > kMaxIter) st = i - kMaxIter;
-                if (st - sb >= 64) { sb = st & ~63; XS = (sb + lane < n) ? X[sb + lane] : 0; }
+                chain_window_advance<false>(X, n, i, xi, mdx64, lane, st, sb, XS);
                 if ((b % kChHelpers) != wave - 1) continue;             // anchors are dealt round-robin to the helpers
                 if (lane == 0) { meta_st[buf][b] = st; meta_x[buf][b] = xi; meta_y[buf][b] = yi; }
                 const int32_t qi = (int32_t)yi, q_span = (int32_t)(yi >> 32 & 0xff), sidi = (int32_t)(yi >> 48 & 0xff);
@@ -543,9 +512,7 @@ template <> struct AnchorPtr<true> { using type = const uint64_t *; };
 template <bool FED> struct AnchorView {
     const uint64_t *p;
     __device__ __forceinline__ uint64_t operator[](int64_t i) const {
-#ifndef GAB_KO_FEDPLAIN
         if (FED) return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
         return p[i];
     }
 };
@@ -602,10 +569,7 @@ __device__ __forceinline__ void fastchain_body(const ChainWork *__restrict__ wor
     // (blocks in which some lane has a narrow window, and calls whose bw does not fit the table, take the arithmetic variant)
     const bool use_tab = bw >= 0 && bw <= kGapTab - 2;
     if (use_tab) {
-        for (int d = threadIdx.x; d <= bw + 1; d += 64 * (1 + H)) {
-            const int32_t dv = d <= bw ? d : (int32_t)0x80000000;
-            gap_tab[d] = (int32_t)floorf(__fmul_rn((float)dv, k32)) + (15 - (__clz((int)((uint32_t)dv | 1u)) >> 1));
-        }
+        for (int d = threadIdx.x; d <= bw + 1; d += 64 * (1 + H)) gap_tab[d] = fastchain_gap32(d <= bw ? d : (int32_t)0x80000000, k32);
         __syncthreads();
     }
 
@@ -633,16 +597,7 @@ __device__ __forceinline__ void fastchain_body(const ChainWork *__restrict__ wor
                     const int64_t i = i0 + a;
                     const uint64_t xi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(xa64 >> 32), a) << 32) |
                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)xa64, a);
-                    for (;;) {
-                        const int64_t cand = sb + lane;
-                        const bool pass = cand < st || (cand < i && (xi - XS) > mdx64);
-                        const unsigned long long m = __ballot(pass);
-                        if (m == ~0ull) { sb += 64; st = sb; XS = (sb + lane < n) ? X[sb + lane] : 0; continue; }
-                        st = sb + __builtin_ctzll(~m);
-                        break;
-                    }
-                    if (i - st > kMaxIter) st = i - kMaxIter;
-                    if (st - sb >= 64) { sb = st & ~63ll; XS = (sb + lane < n) ? X[sb + lane] : 0; }
+                    chain_window_advance<true>(X, n, i, xi, mdx64, lane, st, sb, XS);
                     if (lane == a) st_a = st;
                 }
                 const int64_t ia = i0 + lane;
@@ -680,13 +635,7 @@ __device__ __forceinline__ void fastchain_body(const ChainWork *__restrict__ wor
                     auto far_chunk_tab = [&]() {
                         auto pre = [&](int l, uint32_t &idx, bool &ok) -> int32_t {
                             const int32_t xj = __builtin_amdgcn_readlane(vx, l), yj = __builtin_amdgcn_readlane(vy, l);
-                            const int32_t ddr = (int32_t)((uint32_t)xa - (uint32_t)xj);
-                            const int32_t ddq = (int32_t)((uint32_t)ya - (uint32_t)yj);
-                            const int32_t diff = (int32_t)((uint32_t)ddr - (uint32_t)ddq);
-                            const int32_t dd = max(diff, (int32_t)(0u - (uint32_t)diff));
-                            ok = !(dd > bw || ddr == 0 || (uint32_t)ddq - 1u >= mq_u);
-                            idx = min((uint32_t)dd, (uint32_t)bw + 1u);
-                            return min(min(ddr, ddq), qsa);
+                            return fastchain_pair_pre((uint32_t)xa, (uint32_t)ya, qsa, (uint32_t)xj, (uint32_t)yj, bw, mq_u, idx, ok);
                         };
                         auto fold = [&](int32_t oc, int32_t gc, bool ok, int l) {
                             const int32_t sc = (int32_t)((uint32_t)__builtin_amdgcn_readlane(vs, l) + (uint32_t)oc - (uint32_t)gc);
@@ -809,41 +758,25 @@ void fastchain_kernel_lat(const ChainWork *__restrict__ work, typename AnchorPtr
 // score is broadcast to the younger anchors of the block.  On the suite's inputs that is ~1 % of the anchors.
 constexpr int kCbHelpers = 3;
 
-// Per-call facts the block kernel specialises on (one workgroup per call, before the DP; ChainWork.pad bit 0):
-//   plain = every anchor of the call carries the same segment id (then "sidi == sidj" is always true and the cross-segment
-//           gap rule never applies) AND max(x) - min(x) < 2^31 (then every x[i] - x[j] of the call is exact in 32 bits).
-// Both hold for every call of the suite's inputs (one reference strand per call); calls that miss either use the generic
-// arithmetic.  Reads x and y once: 16 B per seed at HBM speed.
+// Per-call facts the block kernel specialises on (one workgroup per call, before the DP; ChainWork.pad bit 0): plain, see
+// chain_call_plain (chain_dev.h).  It holds for every call of the suite's inputs (one reference strand per call); calls that miss it
+// use the generic arithmetic.  Reads x and y once: 16 B per seed at HBM speed.
 __global__ __launch_bounds__(256) void chain_facts_kernel(ChainWork *work, const uint64_t *__restrict__ xs, const uint64_t *__restrict__ ys,
                                                           const uint32_t *gate = nullptr) {
     if (gate && gate[blockIdx.x] == 0) return;      // (the launch behind the table form: only the calls it handed back)
-    __shared__ unsigned long long s_lo[4], s_hi[4];
-    __shared__ int s_mixed[4];
     ChainWork &w = work[blockIdx.x];
     const uint64_t *X = xs + w.off, *Y = ys + w.off;
     const int64_t n = w.n;
     unsigned long long lo = ~0ull, hi = 0;
     const uint32_t sid0 = n > 0 ? (uint32_t)(Y[0] >> 48 & 0xff) : 0;
-    int mixed = 0;
+    uint32_t mixed = 0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const unsigned long long x = X[i];
         lo = x < lo ? x : lo; hi = x > hi ? x : hi;
-        mixed |= ((uint32_t)(Y[i] >> 48 & 0xff) != sid0) ? 1 : 0;
+        mixed |= ((uint32_t)(Y[i] >> 48 & 0xff) != sid0) ? 1u : 0u;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-        lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; mixed |= __shfl_xor(mixed, o);
-    }
-    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_mixed[threadIdx.x >> 6] = mixed; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) { lo = s_lo[k] < lo ? s_lo[k] : lo; hi = s_hi[k] > hi ? s_hi[k] : hi; mixed |= s_mixed[k]; }
-        // ... and, for the gap-cost table of the block kernel: 0 <= bw <= kGapTab - 2, and dq - dr cannot wrap for a pair that
-        // passes the dq filter (dq in [1, min(max_dist_x, max_dist_y)]): then dd = |dr - dq| is an exact value in [0, 2^31)
-        const int32_t mq = w.max_dist_y < w.max_dist_x ? w.max_dist_y : w.max_dist_x;
-        const unsigned long long lim = mq < 0 ? 0ull : (unsigned long long)mq;
-        w.pad = (n > 0 && !mixed && hi - lo + lim < 0x7fffffffull && w.bw >= 0 && w.bw <= kGapTab - 2) ? 1 : 0;
-    }
+    chain_block_range(lo, hi, mixed);
+    if (threadIdx.x == 0) w.pad = chain_call_plain(w, lo, hi, mixed != 0, kGapTab - 2) ? 1 : 0;
 }
 
 // chain_geometry for a call with the facts above: one segment id, 32-bit-exact x differences.  `xa_lo` / `xj_lo` are the low
@@ -855,30 +788,26 @@ __global__ __launch_bounds__(256) void chain_facts_kernel(ChainWork *work, const
 // (chain_gap_cost: chain_dev.h)
 // the part of chain_geometry_plain before the table: the overlap term and the table index.  Callers that evaluate several
 // pairs in a row take the indices of all of them first and read the table afterwards, so that the LDS reads are in flight
-// together (left to the compiler every step waits for its own ds_read_b32).  MSEG: the call has n_segs > 1 (dr > max_dist_y rule)
-template <bool MSEG>
+// together (left to the compiler every step waits for its own ds_read_b32).  mseg: the call has n_segs > 1 (dr > max_dist_y rule);
+// a compile-time constant at every caller but chain_geometry_plain
 __device__ __forceinline__ int32_t chain_geometry_plain_pre(uint32_t xa_lo, int32_t qa, int32_t q_span, uint32_t xj_lo, uint32_t yj, int32_t mdy,
-                                                            uint32_t dq_lim, int32_t bw, uint32_t &idx, bool &ok) {
+                                                            uint32_t dq_lim, int32_t bw, bool mseg, uint32_t &idx, bool &ok) {
     const int32_t dr = (int32_t)(xa_lo - xj_lo);
     const int32_t dq = qa - (int32_t)yj;
     const int32_t diff = (int32_t)((uint32_t)dr - (uint32_t)dq);
+    // |dr - dq|: exact for every pair that passes the dq filter (chain_call_plain: dq - dr cannot wrap then); a pair that
+    // fails it is filtered whatever dd says, so the reference's `dr > dq ? dr - dq : dq - dr` on wrapped values is not needed
     const int32_t dd = max(diff, (int32_t)(0u - (uint32_t)diff));
-    ok = !(dr == 0 || (uint32_t)dq - 1u >= dq_lim || dd > bw || (MSEG && dr > mdy));
+    // dq <= 0 || dq > max_dist_y || dq > max_dist_x  ==  (unsigned)(dq - 1) >= min(max_dist_y, max_dist_x)
+    ok = !(dr == 0 || (uint32_t)dq - 1u >= dq_lim || dd > bw || (mseg && dr > mdy));
     idx = min((uint32_t)dd, (uint32_t)bw + 1u);
     return min(min(dq, dr), q_span);
 }
 __device__ __forceinline__ int32_t chain_geometry_plain(uint32_t xa_lo, int32_t qa, int32_t q_span, uint32_t xj_lo, uint32_t yj, int32_t mdy,
                                                         uint32_t dq_lim, int32_t bw, bool multi_seg, const int32_t *gap_tab, bool &ok) {
-    const int32_t dr = (int32_t)(xa_lo - xj_lo);
-    const int32_t dq = qa - (int32_t)yj;
-    const int32_t diff = (int32_t)((uint32_t)dr - (uint32_t)dq);
-    // |dr - dq|: exact for every pair that passes the dq filter (chain_facts_kernel: dq - dr cannot wrap then); a pair that
-    // fails it is filtered whatever dd says, so the reference's `dr > dq ? dr - dq : dq - dr` on wrapped values is not needed
-    const int32_t dd = max(diff, (int32_t)(0u - (uint32_t)diff));
-    // dq <= 0 || dq > max_dist_y || dq > max_dist_x  ==  (unsigned)(dq - 1) >= min(max_dist_y, max_dist_x)
-    ok = !(dr == 0 || (uint32_t)dq - 1u >= dq_lim || dd > bw || (multi_seg && dr > mdy));
-    const int32_t v = min(min(dq, dr), q_span);
-    return v - gap_tab[min((uint32_t)dd, (uint32_t)bw + 1u)];
+    uint32_t idx;
+    const int32_t v = chain_geometry_plain_pre(xa_lo, qa, q_span, xj_lo, yj, mdy, dq_lim, bw, multi_seg, idx, ok);
+    return v - gap_tab[idx];
 }
 
 
@@ -953,16 +882,7 @@ __device__ __forceinline__ void chain_block_body(const ChainWork *__restrict__ w
                     const int i = i0 + a;
                     const uint64_t xi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(xa >> 32), a) << 32) |
                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)xa, a);
-                    for (;;) {
-                        const int cand = sb + lane;
-                        const bool pass = cand < st || (cand < i && xi > XS + mdx64);
-                        const unsigned long long m = __ballot(pass);
-                        if (m == ~0ull) { sb += 64; st = sb; XS = (sb + lane < n) ? X[sb + lane] : 0; continue; }
-                        st = sb + __builtin_ctzll(~m);
-                        break;
-                    }
-                    if (i - st > kMaxIter) st = i - kMaxIter;
-                    if (st - sb >= 64) { sb = st & ~63; XS = (sb + lane < n) ? X[sb + lane] : 0; }
+                    chain_window_advance<false>(X, n, i, xi, mdx64, lane, st, sb, XS);
                     if (lane == a) st_a = st;
                 }
                 const int st_rel = st_a - i0;
@@ -1018,7 +938,7 @@ __device__ __forceinline__ void chain_block_body(const ChainWork *__restrict__ w
                         auto pre = [&](int l, uint32_t &idx, bool &ok) -> int32_t {
                             const uint32_t xj_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pv.x, l);
                             const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)pv.y, l);
-                            return chain_geometry_plain_pre<MSEG>((uint32_t)xa, qa, qsa, xj_lo, yj, mdy, dq_lim, bw, idx, ok);
+                            return chain_geometry_plain_pre((uint32_t)xa, qa, qsa, xj_lo, yj, mdy, dq_lim, bw, MSEG, idx, ok);
                         };
                         int l = 0;
                         if (inside) {
@@ -1100,7 +1020,7 @@ __device__ __forceinline__ void chain_block_body(const ChainWork *__restrict__ w
                 constexpr bool MSEG = decltype(mseg_tag)::value;
                 const uint32_t xj_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pv.x, src);
                 const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)pv.y, src);
-                return chain_geometry_plain_pre<MSEG>((uint32_t)xa, qa, qsa, xj_lo, yj, mdy, dq_lim, bw, idx, ok);
+                return chain_geometry_plain_pre((uint32_t)xa, qa, qsa, xj_lo, yj, mdy, dq_lim, bw, MSEG, idx, ok);
             };
             // the near / in-block predecessors lie inside every anchor's window when the LAST anchor's does (the pointer never moves
             // back): then the per-pair window tests go (most blocks: windows hold ~200 predecessors)
@@ -1315,10 +1235,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
     const int NEG = (int)0x80000000;
     if (use_tab) {
         for (int d = threadIdx.x; d <= bw + 1; d += 64 * (2 + NW)) {
-            if (FC) {
-                const int32_t dv = d <= bw ? d : NEG;
-                gap_tab[d] = (int32_t)floorf(__fmul_rn((float)dv, k32)) + (15 - (__clz((int)((uint32_t)dv | 1u)) >> 1));
-            } else gap_tab[d] = chain_gap_cost(d, avg_d);
+            gap_tab[d] = FC ? fastchain_gap32(d <= bw ? d : NEG, k32) : chain_gap_cost(d, avg_d);
         }
     }
     if (threadIdx.x < 2) weird[threadIdx.x] = 0;
@@ -1361,16 +1278,8 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
         const uint32_t xj_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pv.x, src);
         const uint32_t yj = (uint32_t)__builtin_amdgcn_readlane((int)pv.y, src);
         wrapped = false;
-        if constexpr (FC) {
-            const int32_t ddr = (int32_t)((uint32_t)A.x - xj_lo);
-            const int32_t ddq = (int32_t)((uint32_t)A.q - yj);
-            const int32_t diff = (int32_t)((uint32_t)ddr - (uint32_t)ddq);
-            const int32_t dd = max(diff, (int32_t)(0u - (uint32_t)diff));
-            ok = !(dd > bw || ddr == 0 || (uint32_t)ddq - 1u >= dq_lim);
-            wrapped = dd < 0;
-            idx = min((uint32_t)dd, (uint32_t)bw + 1u);
-            return min(min(ddr, ddq), A.qs);
-        } else return chain_geometry_plain_pre<MSEG>((uint32_t)A.x, A.q, A.qs, xj_lo, yj, mdy, dq_lim, bw, idx, ok);
+        if constexpr (FC) return fastchain_pair_pre((uint32_t)A.x, (uint32_t)A.q, A.qs, xj_lo, yj, bw, dq_lim, idx, ok, wrapped);
+        else return chain_geometry_plain_pre((uint32_t)A.x, A.q, A.qs, xj_lo, yj, mdy, dq_lim, bw, MSEG, idx, ok);
     };
     auto load_pred = [&](int i, bool valid) {
         Pred pv = {0, 0, 0};
@@ -1378,8 +1287,6 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
         return pv;
     };
     auto anchor_of = [&](uint64_t xa, uint64_t ya, bool wide) { return Anchor{xa, (int32_t)ya, (int32_t)(ya >> 32 & 0xff), (int32_t)(ya >> 48 & 0xff), wide}; };
-    // the window test of the start search: chain host_kernel.cpp:56-57, fast-chain host_kernel.cpp:200-207 (unsigned difference)
-    auto beyond = [&](uint64_t xi, uint64_t xj) { return FC ? (xi - xj) > mdx64 : xi > xj + mdx64; };
 
     // ---- the search wave's state: st = the pointer after the last anchor searched; XS = x[sb + lane], sb a multiple of 64
     int st = 0, sb = 0;
@@ -1395,16 +1302,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
             const int i = i0 + a;
             const uint64_t xi = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(xa >> 32), a) << 32) |
                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)xa, a);
-            for (;;) {
-                const int cand = sb + lane;
-                const bool pass = cand < st || (cand < i && beyond(xi, XS));
-                const unsigned long long m = __ballot(pass);
-                if (m == ~0ull) { sb += 64; st = sb; XS = (sb + lane < n) ? X[sb + lane] : 0; continue; }
-                st = sb + __builtin_ctzll(~m);
-                break;
-            }
-            if (i - st > kMaxIter) st = i - kMaxIter;
-            if (st - sb >= 64) { sb = st & ~63; XS = (sb + lane < n) ? X[sb + lane] : 0; }
+            chain_window_advance<FC>(X, n, i, xi, mdx64, lane, st, sb, XS);
             if (lane == a) st_a = st;
         }
         return st_a;
@@ -1416,9 +1314,6 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
         const int ia = i0 + lane;
         const uint64_t xa = mine ? sxa : 0;
         sxa = ia + 64 < n ? X[ia + 64] : 0;
-#ifdef GAB_KO_SEARCH
-        { part_st[kb % 3][lane] = ia > 200 ? ia - 200 : 0; return; }
-#endif
         const int S0 = st, sb0 = sb;
         const uint64_t XS0 = XS;
         // leading passes of every anchor over the candidates S0, S0 + 1, ... (all of an anchor's candidates are below its own index)
@@ -1437,7 +1332,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
             const uint32_t xlo = (uint32_t)XS, xhi = (uint32_t)(XS >> 32);
             auto step = [&](int jj) {
                 const uint64_t xj = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)xhi, jj - sb) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)xlo, jj - sb);
-                const bool pass = (jj < ia) & beyond(xa, xj);
+                const bool pass = (jj < ia) & chain_beyond<FC>(xa, xj, mdx64);
                 alive = alive & pass;
                 cnt += alive ? 1 : 0;
             };
@@ -1450,7 +1345,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
         const int Mprev = lane == 0 ? S0 : wave_shr1(M, S0);
         // an anchor that would stop BEFORE the pointer it inherits must stop AT it (true when x ascends)
         bool bad = false;
-        if (mine && g < Mprev) bad = Mprev < ia && beyond(xa, X[Mprev]);
+        if (mine && g < Mprev) bad = Mprev < ia && chain_beyond<FC>(xa, X[Mprev], mdx64);
         int st_a = M;
         if (__ballot(bad)) {                                  // unsorted x: the reference's own loop from the block's entry state
             st = S0; sb = sb0; XS = XS0;
@@ -1507,11 +1402,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
                 };
                 Pred fpv; int32_t fvs;
                 far_load(fu, fpv, fvs);
-#ifdef GAB_KO_G
-                if (false) {
-#else
                 if (fast && !arith && wk < 8) {
-#endif
                     // G of 16 predecessors: units 0..3 the previous block's anchors, 4..7 the block's own
                     const bool nearu = wk < 4;
                     const int p0 = (wk & 3) * 16;
@@ -1555,11 +1446,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
                 int32_t best = NEG, best_j = -1, nok = 0;
                 // far predecessors j <= i0 - 65 (final since block t - 1) in units of 16, dealt round-robin starting with the
                 // workers that have no G unit
-#ifdef GAB_KO_FAR
-                for (; false; fu += NW) {
-#else
                 for (; i0 - 65 - 16 * fu >= st_lo; fu += NW) {
-#endif
                     const int jb = i0 - 65 - 16 * fu;
                     const Pred pv = fpv;
                     const int32_t vs = fvs;
@@ -1656,11 +1543,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
             sane = sane && __ballot(mine && ((uint32_t)pbest >= (uint32_t)kFastSane || (j0 != kNoJ && (uint32_t)thr0 >= (uint32_t)kFastSane))) == 0;
             int32_t best = 0, best_jrel = kNoJ;
             bool redo = !fast || arith || !sane || (FC && weird[par ^ 1] != 0);
-#ifdef GAB_KO_MAIN
-            if (false) {
-#else
             if (!redo) {
-#endif
                 const int32_t initkey = (qsa << 7) | 127;
                 int32_t key = j0 != kNoJ ? max(initkey, thr0 << 7) : initkey;
                 const int4 *gn = G4 + ((size_t)((par ^ 1) * 2 + 0) * 16) * 64 + lane;
@@ -1698,9 +1581,6 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
                     }
                     redo = __ballot(mine && !none && risk > kMaxSkip) != 0;
                 }
-#ifdef GAB_KO_G
-                redo = false;                                  // (timing experiment: the G tables are garbage)
-#endif
             }
             if (redo) {
                 // the legacy block: geometry in this wave; chain: the certificate per anchor, the reference's own scan on a miss
@@ -1749,9 +1629,7 @@ void chain_fast_kernel(const ChainWork *__restrict__ work, const uint64_t *__res
                 best = thr - (best_j == kNoJ ? 1 : 0);
                 best_jrel = best_j;
             }
-#ifndef GAB_KO_STORE
             if (mine) { S[i0 + lane] = best; P[i0 + lane] = best_jrel == kNoJ ? -1 : i0 + best_jrel; }
-#endif
             pbest = best;
             mpx = xa64; mpy = ya64;
             if (FC && lane == 0) weird[par ^ 1] = 0;          // (the workers set the other slot in this phase)
@@ -1856,10 +1734,11 @@ static int chain_helpers_for(const gab_tuning &tun, int64_t total_anchors, int64
     return total_anchors <= 326 * longest_call ? 7 : 3;
 }
 
-// the kernels of one work list (already on the device) on `s`; nothing else (no memset, no synchronisation)
+// The throughput kernels of one work list (already on the device) on `s`; nothing else (no memset, no synchronisation).  The only
+// place that names an instantiation of fastchain_kernel* / chain_block_kernel*.  feed.facts: the fed path; feed.host_score: results
+// written through.  facts = false: the caller has run chain_facts_kernel over these calls already.
 static void chain_launch(const gab_tuning &tun, int mode, int helpers, hipStream_t s, ChainWork *d_work, unsigned nw, const uint64_t *d_x, const uint64_t *d_y,
-                         int32_t *d_score, int32_t *d_parent, int32_t *d_gm, unsigned long long *d_ev, const ChainFeed *feed_in = nullptr) {
-    const ChainFeed feed = feed_in ? *feed_in : ChainFeed{nullptr, nullptr, nullptr, nullptr, nullptr, kFeedSpinLimit};
+                         int32_t *d_score, int32_t *d_parent, int32_t *d_gm, unsigned long long *d_ev, const ChainFeed &feed = ChainFeed(), bool facts = true) {
     if (nw == 0) return;
     if (mode == GAB_FASTCHAIN) {
         if (feed.facts) hipLaunchKernelGGL((fastchain_kernel<kFcHelpers, true>), dim3(nw), dim3(64 * (1 + kFcHelpers)), 0, s, d_work, d_x, d_y, d_score, d_parent, d_ev, feed);
@@ -1874,12 +1753,18 @@ static void chain_launch(const gab_tuning &tun, int mode, int helpers, hipStream
             hipLaunchKernelGGL((chain_block_kernel<kCbHelpers, true>), dim3(nw), dim3(64 * (1 + kCbHelpers)), 0, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, feed);
             return;
         }
-        hipLaunchKernelGGL(chain_facts_kernel, dim3(nw), dim3(256), 0, s, d_work, d_x, d_y, (const uint32_t *)nullptr);
+        if (facts) hipLaunchKernelGGL(chain_facts_kernel, dim3(nw), dim3(256), 0, s, d_work, d_x, d_y, (const uint32_t *)nullptr);
         if (helpers == 7) hipLaunchKernelGGL((chain_block_kernel_lat<7, false>), dim3(nw), dim3(64 * 8), 0, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, feed);
         else if (helpers == 5) hipLaunchKernelGGL((chain_block_kernel_lat<5, false>), dim3(nw), dim3(64 * 6), 0, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, feed);
         else if (feed.host_score) hipLaunchKernelGGL((chain_block_kernel<kCbHelpers, false, true>), dim3(nw), dim3(64 * (1 + kCbHelpers)), 0, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, feed);
         else hipLaunchKernelGGL((chain_block_kernel<kCbHelpers, false>), dim3(nw), dim3(64 * (1 + kCbHelpers)), 0, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, feed);
     }
+}
+// ... and the latency form; the only place that names chain_fast_kernel<>.  gate: the launch behind the table form (see the kernel)
+static auto chain_fast_fn(int mode) { return mode == GAB_CHAIN ? chain_fast_kernel<GAB_CHAIN> : chain_fast_kernel<GAB_FASTCHAIN>; }
+static void chain_launch_fast(int mode, hipStream_t s, ChainWork *d_work, unsigned nw, const uint64_t *d_x, const uint64_t *d_y, int32_t *d_score, int32_t *d_parent,
+                              int32_t *d_gm, unsigned long long *d_ev, const uint32_t *gate) {
+    hipLaunchKernelGGL(chain_fast_fn(mode), dim3(nw), dim3(64 * (2 + kFastW)), kFastDynLds, s, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, gate);
 }
 
 static ChainWork chain_work_of(const gab_chain_hdr &hd, int64_t off) {
@@ -1887,6 +1772,27 @@ static ChainWork chain_work_of(const gab_chain_hdr &hd, int64_t off) {
     w.off = w.hoff = off; w.n = hd.n; w.avg_qspan = hd.avg_qspan;
     w.max_dist_x = hd.max_dist_x; w.max_dist_y = hd.max_dist_y; w.bw = hd.bw; w.n_segs = hd.n_segs; w.pad = 0;
     return w;
+}
+// the non-empty calls, longest first (stable): the sequential walk of the biggest call is the critical path, and workgroups are
+// dispatched in list order
+static std::vector<ChainWork> chain_sorted_work(const gab_chain_hdr *hdr, const int64_t *call_off, int64_t ncalls) {
+    std::vector<ChainWork> wk;
+    wk.reserve((size_t)ncalls);
+    for (int64_t c = 0; c < ncalls; c++) if (hdr[c].n) wk.push_back(chain_work_of(hdr[c], call_off[c]));
+    std::stable_sort(wk.begin(), wk.end(), [](const ChainWork &a, const ChainWork &b) { return a.n > b.n; });
+    return wk;
+}
+
+// the staging buffer of the host-pointer entry points (h->io, 24 bytes per anchor) for t anchors: x | y | score | parent
+struct ChainIo { uint64_t *x, *y; int32_t *score, *parent; };
+static ChainIo chain_io(gab_chain *h, size_t t) {
+    char *b = h->io.as<char>();
+    return ChainIo{(uint64_t *)b, (uint64_t *)(b + 8 * t), (int32_t *)(b + 16 * t), (int32_t *)(b + 20 * t)};
+}
+static int chain_copy_results(int32_t *host_score, int32_t *host_parent, const int32_t *d_score, const int32_t *d_parent, size_t total, hipStream_t s) {
+    GAB_HIP(hipMemcpyAsync(host_score, d_score, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s));
+    GAB_HIP(hipMemcpyAsync(host_parent, d_parent, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s));
+    return GAB_OK;
 }
 
 // stream, events and LDS attribute of the latency form (chain_fast_kernel); also made by gab_chain_reserve: a stream costs
@@ -1901,11 +1807,75 @@ static int chain_fast_setup(gab_chain *h) {
     if (h->fs) return GAB_OK;
     if (hipStreamCreateWithFlags(&h->fs, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->fe[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->fe[1], hipEventDisableTiming) != hipSuccess ||
-        hipFuncSetAttribute((const void *)chain_fast_kernel<GAB_CHAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFastDynLds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)chain_fast_kernel<GAB_FASTCHAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFastDynLds) != hipSuccess) {
+        hipFuncSetAttribute((const void *)chain_fast_fn(GAB_CHAIN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFastDynLds) != hipSuccess ||
+        hipFuncSetAttribute((const void *)chain_fast_fn(GAB_FASTCHAIN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFastDynLds) != hipSuccess) {
         gab_set_error("gab_chain: stream / event / LDS attribute of the latency-form kernel failed"); return GAB_EDEVICE;
     }
     return GAB_OK;
+}
+
+// Which calls of a sorted work list go where: [0, ntab) table form, [ntab, ntab + nfast) latency form, the rest throughput form.
+// Host arithmetic only.  through: the results are also written through to page-locked host arrays (gab_chain_run_device_through).
+struct ChainSplit {
+    bool legacy_only;      // GAB_CHAIN_KERNEL=walk / GAB_CHAIN_HELPERS: one launch of the chosen kernel
+    size_t ntab; int64_t tab_anchors; size_t nfast;
+    int helpers;           // helper waves of the single launch when neither form took a call, else 0
+};
+static ChainSplit chain_split(const gab_tuning &tun, int mode, const std::vector<ChainWork> &wk, int64_t total, bool through) {
+    const size_t nw = wk.size();
+    // The longest calls (the list is sorted) go to the latency form (chain_fast_kernel: one call per CU, sixteen waves), the
+    // rest to the throughput form, side by side on two streams -- when the batch would otherwise wait for its longest call:
+    // the throughput form takes ~0.30 us per anchor of a call however empty the chip is and does ~2.85 G anchors/s over all
+    // calls; a batch whose longest call needs more than 0.75 of the batch's throughput time hands every call of 512 anchors or
+    // more to the latency form (chain-large on one GPU: none; an eighth of it and the 1 000-call input: 99 % of their anchors --
+    // leaving the mid-size calls in the throughput form beside it cost the slowest call 1-2 %: its CU's SIMDs are shared).
+    // GAB_CHAIN_FAST_MIN / GAB_CHAIN_FAST_CALLS pin the choice (tests, A/B runs).
+    // r04 -- and the calls a batch would WAIT for go to the table form (chain_tab.hip: the geometry of every block on any CU,
+    // the call's own workgroup only folds): a 60 000-anchor call takes ~1 ms there instead of 5-10, at 2 bytes of HBM traffic per
+    // pair.  The list is sorted longest first: [0, ntab) table form, [ntab, ntab + nfast) latency form, the rest throughput
+    // form, side by side on three streams.  GAB_CHAIN_TAB_MIN pins the table form's smallest call, GAB_CHAIN_TAB=0 turns it off.
+    ChainSplit sp{(mode == GAB_CHAIN && tun.chain_walk) || tun.chain_helpers_set, 0, 0, 0, 0};
+    if (!sp.legacy_only && tun.chain_tab != 0) {
+        // A batch whose longest call would outlast 0.75 of the batch's throughput time in the throughput form (0.30 us per anchor of
+        // a call, 2.85 G anchors/s over all calls: the latency-form rule below) hands its long calls to the table form: every call
+        // that would take a quarter of that time there, 2048 anchors at least.  Measured (r04, one rank's share of chain-large
+        // under 2 / 4 / 8-GPU strong scaling, smallest table call 2048 .. 35 000 anchors): the more calls in the table form the
+        // better down to ~2048 anchors -- 8 GPUs 4.97-5.12 ms, 4 GPUs 7.80-8.29 ms, 2 GPUs 15.2-15.6 ms (17.0 without) -- while
+        // chain-large on ONE GPU loses (27.8 -> 29.4 ms with the calls above 45 000 anchors there): the table form costs 2 bytes of
+        // HBM traffic per pair and ~25 % more instructions, and only pays where calls are waited for.
+        int64_t min_n = INT64_MAX;
+        const double est_tp = (double)total / 2.85e9, lat_max = 0.30e-6 * (double)wk[0].n;
+        if (lat_max >= 0.75 * est_tp) min_n = std::max<int64_t>(2048, (int64_t)(0.25 * est_tp / 0.30e-6));
+        // fast-chain (no certificate, no exact re-scans; its geometry rows are batched): since the end of r04 the table form is also
+        // the FASTER form for calls of a few thousand anchors and more, whatever the batch -- all of fast-chain-large on one GPU with
+        // the calls of >= 40 000 / 25 000 / 12 500 / 4 096 / 2 048 / 512 / 1 anchors there: 27.87 / 27.09 / 26.15 / 25.88-25.95 / 26.16 / 26.48 /
+        // 26.65 ms against 27.65 without.  chain: 29.2 / 28.4 / 27.9 / 28.2 against 27.8 -- it keeps the rule above.
+        // (not when the results are also written through to host memory, gab_chain_run_device_through: the fold then produces 0.6 GB
+        // of results in its 10 ms and is held to the link's ~40 GB/s -- 16.5 ms -- while the throughput form spreads the same bytes
+        // over its 27 ms: the fast-chain driver's region of interest 32.3 ms against 29.8)
+        if (mode == GAB_FASTCHAIN && !through) min_n = std::min<int64_t>(min_n, 4096);
+        // chain: with the fold of the end of the round (far maxima merged by LDS atomics, fourteen workers) its longest calls gain too, less:
+        // all of chain-large on one GPU with the calls of >= 30 000 / 20 000 / 16 000 / 12 500 / 8 192 / 6 000 anchors there: 27.86 / 26.99 /
+        // 26.83 / 27.01 / 27.23 / 27.13 ms against 27.82 without; and once the fold's loop existed per role: 16 000 / 10 000 / 6 000 / 4 096 /
+        // 2 048 anchors 25.04 / 24.89 / 24.85 / 24.90 / 25.00 ms
+        // (written through, the same holds as for fast-chain: the chain driver's region of interest 31.8 ms with the 8 192 rule, 31.2-32.2 ms
+        // with a 16 000 rule -- the faster fold of the end of the round makes the burst of results shorter still --, 29.0-29.1 ms without)
+        else if (mode == GAB_CHAIN && !through) min_n = std::min<int64_t>(min_n, 8192);
+        if (tun.chain_tab_min >= 0) min_n = tun.chain_tab_min;      // GAB_CHAIN_TAB_MIN
+        while (sp.ntab < nw && wk[sp.ntab].n >= min_n) { sp.tab_anchors += wk[sp.ntab].n; sp.ntab++; }
+    }
+    const size_t nrest = nw - sp.ntab;
+    if (!sp.legacy_only && nrest) {
+        int64_t min_n = 0, max_calls = 0;
+        const double est_tp = (double)(total - sp.tab_anchors) / 2.85e9, lat_max = 0.30e-6 * (double)wk[sp.ntab].n;
+        if (lat_max >= 0.75 * est_tp) { min_n = 512; max_calls = (int64_t)nrest; }
+        if (tun.chain_fast_min >= 0) min_n = tun.chain_fast_min;              // GAB_CHAIN_FAST_MIN
+        if (tun.chain_fast_calls >= 0) max_calls = tun.chain_fast_calls;      // GAB_CHAIN_FAST_CALLS
+        if (tun.chain_fast_min >= 0 && tun.chain_fast_calls < 0) max_calls = (int64_t)nrest;
+        while (sp.nfast < nrest && (int64_t)sp.nfast < max_calls && wk[sp.ntab + sp.nfast].n >= min_n) sp.nfast++;
+    }
+    if (!sp.ntab && !sp.nfast) sp.helpers = (mode == GAB_CHAIN && tun.chain_walk) ? kChHelpers : chain_helpers_for(tun, total, wk[0].n);
+    return sp;
 }
 
 static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, const uint64_t *d_y, const int64_t *call_off, const gab_chain_hdr *hdr,
@@ -1944,20 +1914,9 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     gab_tuning_refresh(&h->tun);
     hipStream_t s = (hipStream_t)stream_;
 
-    // longest call first: the sequential walk of the biggest call is the critical path
-    std::vector<ChainWork> wk;
-    wk.reserve((size_t)ncalls);
     h->split.n.resize((size_t)ncalls);
-    for (int64_t c = 0; c < ncalls; c++) {
-        h->split.n[(size_t)c] = (int32_t)hdr[c].n;
-        if (hdr[c].n == 0) continue;
-        ChainWork w;
-        w.off = w.hoff = call_off[c]; w.n = hdr[c].n; w.avg_qspan = hdr[c].avg_qspan;
-        w.max_dist_x = hdr[c].max_dist_x; w.max_dist_y = hdr[c].max_dist_y; w.bw = hdr[c].bw;
-        w.n_segs = hdr[c].n_segs; w.pad = 0;
-        wk.push_back(w);
-    }
-    std::stable_sort(wk.begin(), wk.end(), [](const ChainWork &a, const ChainWork &b) { return a.n > b.n; });
+    for (int64_t c = 0; c < ncalls; c++) h->split.n[(size_t)c] = (int32_t)hdr[c].n;
+    const std::vector<ChainWork> wk = chain_sorted_work(hdr, call_off, ncalls);
     const size_t nw = wk.size();
     const size_t o_ev = (sizeof(ChainWork) * nw + 15) & ~(size_t)15;
     rc = h->work.reserve(o_ev + 16);
@@ -1978,146 +1937,64 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
         GAB_HIP(hipMemsetAsync(d_gm, 0, sizeof(int32_t) * (size_t)total, s));      // vector::resize zero-fills targets
     }
     GAB_HIP(hipEventRecord(h->ev[0], s));
-    // The longest calls (the list is sorted) go to the latency form (chain_fast_kernel: one call per CU, sixteen waves), the
-    // rest to the throughput form, side by side on two streams -- when the batch would otherwise wait for its longest call:
-    // the throughput form takes ~0.30 us per anchor of a call however empty the chip is and does ~2.85 G anchors/s over all
-    // calls; a batch whose longest call needs more than 0.75 of the batch's throughput time hands every call of 512 anchors or
-    // more to the latency form (chain-large on one GPU: none; an eighth of it and the 1 000-call input: 99 % of their anchors --
-    // leaving the mid-size calls in the throughput form beside it cost the slowest call 1-2 %: its CU's SIMDs are shared).
-    // GAB_CHAIN_FAST_MIN / GAB_CHAIN_FAST_CALLS pin the choice (tests, A/B runs).
-    // r04 -- and the calls a batch would WAIT for go to the table form (chain_tab.hip: the geometry of every block on any CU,
-    // the call's own workgroup only folds): a 60 000-anchor call takes ~1 ms there instead of 5-10, at 2 bytes of HBM traffic per
-    // pair.  The list is sorted longest first: [0, ntab) table form, [ntab, ntab + nfast) latency form, the rest throughput
-    // form, side by side on three streams.  GAB_CHAIN_TAB_MIN pins the table form's smallest call, GAB_CHAIN_TAB=0 turns it off.
-    const bool legacy_only = (mode == GAB_CHAIN && h->tun.chain_walk) || h->tun.chain_helpers_set;
-    size_t ntab = 0, nfast = 0;
-    int64_t tab_anchors = 0;
     bool written_through = false;          // gab_chain_run_device_through: the DP kernels themselves fill the host arrays
-    int32_t *hs = nullptr, *hp = nullptr;  // ... device-visible addresses of the caller's page-locked arrays (nullptr: pageable, or not asked for)
+    ChainFeed through;                     // ... at the device-visible addresses of the caller's page-locked arrays (null: pageable, or not asked for)
     if (host_score) {
         void *a = nullptr, *b = nullptr;
-        if (hipHostGetDevicePointer(&a, host_score, 0) == hipSuccess && hipHostGetDevicePointer(&b, host_parent, 0) == hipSuccess) { hs = (int32_t *)a; hp = (int32_t *)b; }
+        if (hipHostGetDevicePointer(&a, host_score, 0) == hipSuccess && hipHostGetDevicePointer(&b, host_parent, 0) == hipSuccess) { through.host_score = (int32_t *)a; through.host_parent = (int32_t *)b; }
         else (void)hipGetLastError();
     }
+    const bool can_through = through.host_score != nullptr;
+    const ChainSplit sp = chain_split(h->tun, mode, wk, total, can_through);
+    const size_t ntab = sp.ntab, nfast = sp.nfast, nrest = nw - ntab;
     uint32_t *d_bail = nullptr;
-    if (!legacy_only && h->tun.chain_tab != 0) {
-        // A batch whose longest call would outlast 0.75 of the batch's throughput time in the throughput form (0.30 us per anchor of
-        // a call, 2.85 G anchors/s over all calls: the latency-form rule below) hands its long calls to the table form: every call
-        // that would take a quarter of that time there, 2048 anchors at least.  Measured (r04, one rank's share of chain-large
-        // under 2 / 4 / 8-GPU strong scaling, smallest table call 2048 .. 35 000 anchors): the more calls in the table form the
-        // better down to ~2048 anchors -- 8 GPUs 4.97-5.12 ms, 4 GPUs 7.80-8.29 ms, 2 GPUs 15.2-15.6 ms (17.0 without) -- while
-        // chain-large on ONE GPU loses (27.8 -> 29.4 ms with the calls above 45 000 anchors there): the table form costs 2 bytes of
-        // HBM traffic per pair and ~25 % more instructions, and only pays where calls are waited for.
-        int64_t min_n = INT64_MAX;
-        const double est_tp = (double)total / 2.85e9, lat_max = 0.30e-6 * (double)wk[0].n;
-        if (lat_max >= 0.75 * est_tp) min_n = std::max<int64_t>(2048, (int64_t)(0.25 * est_tp / 0.30e-6));
-        // fast-chain (no certificate, no exact re-scans; its geometry rows are batched): since the end of r04 the table form is also
-        // the FASTER form for calls of a few thousand anchors and more, whatever the batch -- all of fast-chain-large on one GPU with
-        // the calls of >= 40 000 / 25 000 / 12 500 / 4 096 / 2 048 / 512 / 1 anchors there: 27.87 / 27.09 / 26.15 / 25.88-25.95 / 26.16 / 26.48 /
-        // 26.65 ms against 27.65 without.  chain: 29.2 / 28.4 / 27.9 / 28.2 against 27.8 -- it keeps the rule above.
-        // (not when the results are also written through to host memory, gab_chain_run_device_through: the fold then produces 0.6 GB
-        // of results in its 10 ms and is held to the link's ~40 GB/s -- 16.5 ms -- while the throughput form spreads the same bytes
-        // over its 27 ms: the fast-chain driver's region of interest 32.3 ms against 29.8)
-        if (mode == GAB_FASTCHAIN && !hs) min_n = std::min<int64_t>(min_n, 4096);
-        // chain: with the fold of the end of the round (far maxima merged by LDS atomics, fourteen workers) its longest calls gain too, less:
-        // all of chain-large on one GPU with the calls of >= 30 000 / 20 000 / 16 000 / 12 500 / 8 192 / 6 000 anchors there: 27.86 / 26.99 /
-        // 26.83 / 27.01 / 27.23 / 27.13 ms against 27.82 without; and once the fold's loop existed per role: 16 000 / 10 000 / 6 000 / 4 096 /
-        // 2 048 anchors 25.04 / 24.89 / 24.85 / 24.90 / 25.00 ms
-        // (written through, the same holds as for fast-chain: the chain driver's region of interest 31.8 ms with the 8 192 rule, 31.2-32.2 ms
-        // with a 16 000 rule -- the faster fold of the end of the round makes the burst of results shorter still --, 29.0-29.1 ms without)
-        else if (mode == GAB_CHAIN && !hs) min_n = std::min<int64_t>(min_n, 8192);
-        if (h->tun.chain_tab_min >= 0) min_n = h->tun.chain_tab_min;      // GAB_CHAIN_TAB_MIN
-        while (ntab < nw && wk[ntab].n >= min_n) { tab_anchors += wk[ntab].n; ntab++; }
-    }
-    const size_t nrest = nw - ntab;
-    if (!legacy_only && nrest) {
-        int64_t min_n = 0, max_calls = 0;
-        const double est_tp = (double)(total - tab_anchors) / 2.85e9, lat_max = 0.30e-6 * (double)wk[ntab].n;
-        if (lat_max >= 0.75 * est_tp) { min_n = 512; max_calls = (int64_t)nrest; }
-        if (h->tun.chain_fast_min >= 0) min_n = h->tun.chain_fast_min;              // GAB_CHAIN_FAST_MIN
-        if (h->tun.chain_fast_calls >= 0) max_calls = h->tun.chain_fast_calls;      // GAB_CHAIN_FAST_CALLS
-        if (h->tun.chain_fast_min >= 0 && h->tun.chain_fast_calls < 0) max_calls = (int64_t)nrest;
-        while (nfast < nrest && (int64_t)nfast < max_calls && wk[ntab + nfast].n >= min_n) nfast++;
-    }
     if (ntab || nfast) {
         if ((rc = chain_fast_setup(h)) != GAB_OK) return rc;
-        const ChainFeed nofeed{nullptr, nullptr, nullptr, nullptr, nullptr, kFeedSpinLimit};
         // (the facts of the calls in the table form are only needed by the few it hands back: taken behind it, gated)
         if (mode == GAB_CHAIN && nrest) hipLaunchKernelGGL(chain_facts_kernel, dim3((unsigned)nrest), dim3(256), 0, s, d_work + ntab, d_x, d_y, (const uint32_t *)nullptr);
         GAB_HIP(hipEventRecord(h->fe[0], s));
         if (ntab) {
             // the table form and, behind it on the same stream, the latency form for the calls it hands back (bail word set)
             GAB_HIP(hipStreamWaitEvent(h->ts, h->fe[0], 0));
-            if ((rc = chain_tab_run(&h->tab, h->tun, mode, h->ts, d_work, wk.data(), ntab, total, d_x, d_y, d_score, d_parent, d_gm, d_ev, &d_bail, nfast == 0 ? hs : nullptr, nfast == 0 ? hp : nullptr)) != GAB_OK) return rc;
+            if ((rc = chain_tab_run(&h->tab, h->tun, mode, h->ts, d_work, wk.data(), ntab, total, d_x, d_y, d_score, d_parent, d_gm, d_ev, &d_bail,
+                                    nfast == 0 ? through.host_score : nullptr, nfast == 0 ? through.host_parent : nullptr)) != GAB_OK) return rc;
             if (mode == GAB_CHAIN) hipLaunchKernelGGL(chain_facts_kernel, dim3((unsigned)ntab), dim3(256), 0, h->ts, d_work, d_x, d_y, (const uint32_t *)d_bail);
-            if (mode == GAB_CHAIN)
-                hipLaunchKernelGGL(chain_fast_kernel<GAB_CHAIN>, dim3((unsigned)ntab), dim3(64 * (2 + kFastW)), kFastDynLds, h->ts, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, (const uint32_t *)d_bail);
-            else
-                hipLaunchKernelGGL(chain_fast_kernel<GAB_FASTCHAIN>, dim3((unsigned)ntab), dim3(64 * (2 + kFastW)), kFastDynLds, h->ts, d_work, d_x, d_y, d_score, d_parent, d_gm, d_ev, (const uint32_t *)d_bail);
+            chain_launch_fast(mode, h->ts, d_work, (unsigned)ntab, d_x, d_y, d_score, d_parent, d_gm, d_ev, d_bail);
             GAB_HIP(hipGetLastError());
             GAB_HIP(hipEventRecord(h->te[1], h->ts));
         }
         if (nfast) {
             GAB_HIP(hipStreamWaitEvent(h->fs, h->fe[0], 0));
-            if (mode == GAB_CHAIN)
-                hipLaunchKernelGGL(chain_fast_kernel<GAB_CHAIN>, dim3((unsigned)nfast), dim3(64 * (2 + kFastW)), kFastDynLds, h->fs, d_work + ntab, d_x, d_y, d_score, d_parent, d_gm, d_ev, (const uint32_t *)nullptr);
-            else
-                hipLaunchKernelGGL(chain_fast_kernel<GAB_FASTCHAIN>, dim3((unsigned)nfast), dim3(64 * (2 + kFastW)), kFastDynLds, h->fs, d_work + ntab, d_x, d_y, d_score, d_parent, d_gm, d_ev, (const uint32_t *)nullptr);
+            chain_launch_fast(mode, h->fs, d_work + ntab, (unsigned)nfast, d_x, d_y, d_score, d_parent, d_gm, d_ev, nullptr);
             GAB_HIP(hipGetLastError());
             GAB_HIP(hipEventRecord(h->fe[1], h->fs));
         }
         // (gab_chain_run_device_through: the table form and the throughput form write their results through; the latency form does
         // not, and neither do the calls the table form hands back -- then the arrays are copied at the end)
-        written_through = hs != nullptr && nfast == 0;
-        if (nrest > nfast) {
-            const ChainFeed through{nullptr, hs, hp, nullptr, nullptr, kFeedSpinLimit};
-            if (mode == GAB_CHAIN) {
-                if (written_through)
-                    hipLaunchKernelGGL((chain_block_kernel<kCbHelpers, false, true>), dim3((unsigned)(nrest - nfast)), dim3(64 * (1 + kCbHelpers)), 0, s, d_work + ntab + nfast, d_x, d_y,
-                                       d_score, d_parent, d_gm, d_ev, through);
-                else
-                    hipLaunchKernelGGL((chain_block_kernel<kCbHelpers, false>), dim3((unsigned)(nrest - nfast)), dim3(64 * (1 + kCbHelpers)), 0, s, d_work + ntab + nfast, d_x, d_y,
-                                       d_score, d_parent, d_gm, d_ev, nofeed);
-            } else {
-                if (written_through)
-                    hipLaunchKernelGGL((fastchain_kernel<kFcHelpers, false, true>), dim3((unsigned)(nrest - nfast)), dim3(64 * (1 + kFcHelpers)), 0, s, d_work + ntab + nfast, d_x, d_y,
-                                       d_score, d_parent, d_ev, through);
-                else
-                    hipLaunchKernelGGL((fastchain_kernel<kFcHelpers, false>), dim3((unsigned)(nrest - nfast)), dim3(64 * (1 + kFcHelpers)), 0, s, d_work + ntab + nfast, d_x, d_y,
-                                       d_score, d_parent, d_ev, nofeed);
-            }
-        }
+        written_through = can_through && nfast == 0;
+        chain_launch(h->tun, mode, 3, s, d_work + ntab + nfast, (unsigned)(nrest - nfast), d_x, d_y, d_score, d_parent, d_gm, d_ev, written_through ? through : ChainFeed(), false);
         if (nfast) GAB_HIP(hipStreamWaitEvent(s, h->fe[1], 0));
         if (ntab) GAB_HIP(hipStreamWaitEvent(s, h->te[1], 0));
     } else {
-        const int helpers = chain_helpers_for(h->tun, total, wk.empty() ? 0 : wk[0].n);
-        ChainFeed through{nullptr, nullptr, nullptr, nullptr, nullptr, kFeedSpinLimit};
-        if (hs && helpers == 3 && !(mode == GAB_CHAIN && h->tun.chain_walk)) {
-            through.host_score = hs; through.host_parent = hp;      // page-locked: the DP writes its results through
-            written_through = true;
-        }
-        chain_launch(h->tun, mode, helpers, s, d_work, (unsigned)nw, d_x, d_y, d_score, d_parent, d_gm, d_ev, written_through ? &through : nullptr);
+        // page-locked: the DP writes its results through
+        written_through = can_through && sp.helpers == 3 && !(mode == GAB_CHAIN && h->tun.chain_walk);
+        chain_launch(h->tun, mode, sp.helpers, s, d_work, (unsigned)nw, d_x, d_y, d_score, d_parent, d_gm, d_ev, written_through ? through : ChainFeed());
     }
     GAB_HIP(hipGetLastError());
     GAB_HIP(hipEventRecord(h->ev[1], s));
     GAB_HIP(hipMemcpyAsync(h->h_evals, d_ev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     std::vector<uint32_t> h_bail;
     if (written_through && ntab) { h_bail.resize(ntab); GAB_HIP(hipMemcpyAsync(h_bail.data(), d_bail, 4 * ntab, hipMemcpyDeviceToHost, s)); }
-    if (host_score && !written_through) {
-        GAB_HIP(hipMemcpyAsync(host_score, d_score, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipMemcpyAsync(host_parent, d_parent, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
-    }
+    if (host_score && !written_through && (rc = chain_copy_results(host_score, host_parent, d_score, d_parent, (size_t)total, s)) != GAB_OK) return rc;
     GAB_HIP(hipStreamSynchronize(s));    // wk (host vector) must outlive the H2D copy
     if (written_through && ntab && std::any_of(h_bail.begin(), h_bail.end(), [](uint32_t b) { return b != 0; })) {
         // a call the table form handed back ran in the latency form, which writes to the device arrays only: copy after all
-        GAB_HIP(hipMemcpyAsync(host_score, d_score, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
-        GAB_HIP(hipMemcpyAsync(host_parent, d_parent, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+        if ((rc = chain_copy_results(host_score, host_parent, d_score, d_parent, (size_t)total, s)) != GAB_OK) return rc;
         GAB_HIP(hipStreamSynchronize(s));
     }
     if (ntab && h->tun.chain_trace) chain_tab_report(&h->tab, ntab);
     h->have_stats = true;
-    h->split.legacy_only = legacy_only; h->split.ntab = ntab; h->split.nfast = nfast;
-    h->split.helpers = (ntab || nfast) ? 0 : (mode == GAB_CHAIN && h->tun.chain_walk) ? kChHelpers : chain_helpers_for(h->tun, total, wk[0].n);
+    h->split.legacy_only = sp.legacy_only; h->split.ntab = ntab; h->split.nfast = nfast; h->split.helpers = sp.helpers;
     h->split.valid = true;
     return GAB_OK;
 }
@@ -2138,9 +2015,7 @@ static int chain_run_overlapped(gab_chain *h, int mode, const uint64_t *x, const
     h->have_stats = false;
     h->split.valid = false;
     const size_t t = (size_t)total;
-    char *b = h->io.as<char>();
-    uint64_t *dx = (uint64_t *)b, *dy = (uint64_t *)(b + 8 * t);
-    int32_t *ds = (int32_t *)(b + 16 * t), *dp = (int32_t *)(b + 20 * t);
+    const auto [dx, dy, ds, dp] = chain_io(h, t);
     for (int k = 0; k < 2; k++)
         if (!h->xs[k] && hipStreamCreateWithFlags(&h->xs[k], hipStreamNonBlocking) != hipSuccess) { gab_set_error("gab_chain_run: stream creation failed"); return GAB_EDEVICE; }
     for (int k = 0; k < 5; k++)
@@ -2300,6 +2175,47 @@ static int chain_fed_setup(gab_chain *h, int *gather_blocks) {
     return GAB_OK;
 }
 
+// GAB_CHAIN_TRACE: what the fed path's last run did, on stderr (after both streams are idle); frees the two diagnosis buffers
+static void chain_fed_report(gab_chain *h, const std::vector<ChainWork> &wk, size_t nchunks, hipEvent_t (&tv)[4], unsigned long long *d_dbg,
+                             unsigned long long *d_pub, int gather_blocks) {
+    const size_t nw = wk.size();
+    float a = 0, c = 0;
+    float d = 0;
+    (void)hipEventElapsedTime(&a, tv[0], tv[1]); (void)hipEventElapsedTime(&c, tv[0], tv[3]); (void)hipEventElapsedTime(&d, tv[2], tv[3]);
+    fprintf(stderr, "[gab_chain_run] fed: %zu calls in %zu chunks; all anchors on the device after %.1f ms, DP done after %.1f ms (the DP launch itself: %.1f ms)\n", nw, nchunks, a, c, d);
+    for (auto &e : tv) (void)hipEventDestroy(e);
+    if (d_dbg) {
+        std::vector<unsigned long long> dbg(3 * nw), pub(nw);
+        (void)hipMemcpy(dbg.data(), d_dbg, 24 * nw, hipMemcpyDeviceToHost);
+        if (d_pub) (void)hipMemcpy(pub.data(), d_pub, 8 * nw, hipMemcpyDeviceToHost);
+        unsigned long long t0 = ~0ull;
+        std::vector<int> xcc(nw);
+        for (size_t k = 0; k < nw; k++) { xcc[k] = (int)(dbg[3 * k] & 15); dbg[3 * k] >>= 4; }
+        for (size_t k = 0; k < nw; k++) t0 = std::min(t0, dbg[3 * k]);
+        for (size_t k : {(size_t)0, (size_t)50, (size_t)300, (size_t)900, (size_t)1100, (size_t)1300, (size_t)1600, (size_t)2500, (size_t)5000, nw - 1})
+            if (k < nw) fprintf(stderr, "   item %zu (n = %lld): dispatched %.2f ms, published by the gather %.2f ms, anchors there %.2f ms, done %.2f ms\n", k, (long long)wk[k].n,
+                                (dbg[3 * k] - t0) * 1e-5, ((double)pub[k] - (double)t0) * 1e-5, (dbg[3 * k + 1] - t0) * 1e-5, (dbg[3 * k + 2] - t0) * 1e-5);
+        {
+            int hist[16] = {};
+            for (int k = 0; k < gather_blocks; k++) { const int v = ((volatile uint8_t *)h->h_started)[k]; if (v) hist[(v - 1) & 15]++; }
+            fprintf(stderr, "   gather workgroups per XCD: %d %d %d %d %d %d %d %d\n",
+                    hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7]);
+        }
+        for (int r = 0; r < 8; r++) {
+            double lat = 0, disp = 0; int nl = 0, nd = 0;
+            for (size_t k = 0; k < nw; k++) {
+                if (xcc[k] != r) continue;
+                if (k < 1000) { lat += (double)(dbg[3 * k + 2] - dbg[3 * k + 1]) * 1e-5 / ((double)wk[k].n * 1e-3); nl++; }
+                else if (k >= 3000) { disp += (double)(dbg[3 * k] - t0) * 1e-5; nd++; }
+            }
+            fprintf(stderr, "   XCD %d: %.3f ms per 1000 anchors for its calls among the 1000 longest; items 3000.. dispatched after %.1f ms on average\n",
+                    r, nl ? lat / nl : 0., nd ? disp / nd : 0.);
+        }
+        (void)hipFree(d_dbg);
+        if (d_pub) (void)hipFree(d_pub);
+    }
+}
+
 static int chain_run_fed(gab_chain *h, int mode, const uint64_t *x, const uint64_t *y, const int64_t *call_off,
                          const gab_chain_hdr *hdr, int64_t ncalls, int64_t total, int32_t *score_out, int32_t *parent_out,
                          hipStream_t sA) {
@@ -2319,10 +2235,7 @@ static int chain_run_fed(gab_chain *h, int mode, const uint64_t *x, const uint64
     hipStream_t sG = h->gs ? h->gs : h->xs[0];
     // work list, longest call first; on the device every call starts on a 128-byte line (16 anchors), so that no cache line is
     // shared between calls (see chain_feed_wait); and the chunk table
-    std::vector<ChainWork> wk;
-    wk.reserve((size_t)ncalls);
-    for (int64_t c = 0; c < ncalls; c++) if (hdr[c].n) wk.push_back(chain_work_of(hdr[c], call_off[c]));
-    std::stable_sort(wk.begin(), wk.end(), [](const ChainWork &a, const ChainWork &c) { return a.n > c.n; });
+    std::vector<ChainWork> wk = chain_sorted_work(hdr, call_off, ncalls);
     const size_t nw = wk.size();
     std::vector<ChainChunk> chunks;
     std::vector<uint32_t> need(nw);
@@ -2338,9 +2251,7 @@ static int chain_run_fed(gab_chain *h, int mode, const uint64_t *x, const uint64
     const size_t t = (size_t)dtotal;
     int rc = h->io.reserve(24 * t + 64);
     if (rc) return rc;
-    char *b = h->io.as<char>();
-    uint64_t *dx = (uint64_t *)b, *dy = (uint64_t *)(b + 8 * t);
-    int32_t *ds = (int32_t *)(b + 16 * t), *dp = (int32_t *)(b + 20 * t);
+    const auto [dx, dy, ds, dp] = chain_io(h, t);
     GAB_CHECK(chunks.size() < (1ull << 32), "gab_chain_run: too many chunks");
     // device scratch: work | evals, abort | facts | done | need | mixed | xlo | xhi | chunks
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -2405,56 +2316,19 @@ static int chain_run_fed(gab_chain *h, int mode, const uint64_t *x, const uint64
     if (h->tun.chain_fed_serial) GAB_HIP(hipStreamSynchronize(sG));        // experiments: the DP only after the last anchor
     // ---- the DP: one launch, its workgroups wait for their call
     GAB_HIP(hipStreamWaitEvent(sA, h->xe_fed, 0));
-    const bool write_through = true;              // (measured: results by two copies at the end instead cost their 12 ms in full)
     unsigned long long *d_dbg = nullptr;
     if (trace && mode == GAB_CHAIN) { (void)hipMalloc((void **)&d_dbg, 24 * nw); (void)hipMemsetAsync(d_dbg, 0, 24 * nw, sA); }
-    ChainFeed feed{(uint32_t *)(wb + o_facts), write_through ? (int32_t *)hs : nullptr, write_through ? (int32_t *)hp : nullptr, d_abort, d_dbg,
-                   giveup_test ? 3000 : kFeedSpinLimit};
+    // (results written through -- measured: by two copies at the end instead they cost their 12 ms in full)
+    const ChainFeed feed{(uint32_t *)(wb + o_facts), (int32_t *)hs, (int32_t *)hp, d_abort, d_dbg, giveup_test ? 3000 : kFeedSpinLimit};
     if (trace) (void)hipEventRecord(tv[2], sA);
-    chain_launch(h->tun, mode, 3, sA, d_work, (unsigned)nw, dx, dy, ds, dp, d_gm, d_ev, &feed);
+    chain_launch(h->tun, mode, 3, sA, d_work, (unsigned)nw, dx, dy, ds, dp, d_gm, d_ev, feed);
     GAB_HIP(hipGetLastError());
     if (trace) (void)hipEventRecord(tv[3], sA);
     GAB_HIP(hipEventRecord(h->ev[1], sA));
     GAB_HIP(hipMemcpyAsync(h->h_evals, d_ev, 2 * sizeof(unsigned long long) + 8, hipMemcpyDeviceToHost, sA));
     GAB_HIP(hipStreamSynchronize(sG));
     GAB_HIP(hipStreamSynchronize(sA));            // (the host vectors must outlive their copies)
-    if (trace) {
-        float a = 0, c = 0;
-        float d = 0;
-        (void)hipEventElapsedTime(&a, tv[0], tv[1]); (void)hipEventElapsedTime(&c, tv[0], tv[3]); (void)hipEventElapsedTime(&d, tv[2], tv[3]);
-        fprintf(stderr, "[gab_chain_run] fed: %zu calls in %zu chunks; all anchors on the device after %.1f ms, DP done after %.1f ms (the DP launch itself: %.1f ms)\n", nw, chunks.size(), a, c, d);
-        for (auto &e : tv) (void)hipEventDestroy(e);
-        if (d_dbg) {
-            std::vector<unsigned long long> dbg(3 * nw), pub(nw);
-            (void)hipMemcpy(dbg.data(), d_dbg, 24 * nw, hipMemcpyDeviceToHost);
-            if (d_pub) (void)hipMemcpy(pub.data(), d_pub, 8 * nw, hipMemcpyDeviceToHost);
-            unsigned long long t0 = ~0ull;
-            std::vector<int> xcc(nw);
-            for (size_t k = 0; k < nw; k++) { xcc[k] = (int)(dbg[3 * k] & 15); dbg[3 * k] >>= 4; }
-            for (size_t k = 0; k < nw; k++) t0 = std::min(t0, dbg[3 * k]);
-            for (size_t k : {(size_t)0, (size_t)50, (size_t)300, (size_t)900, (size_t)1100, (size_t)1300, (size_t)1600, (size_t)2500, (size_t)5000, nw - 1})
-                if (k < nw) fprintf(stderr, "   item %zu (n = %lld): dispatched %.2f ms, published by the gather %.2f ms, anchors there %.2f ms, done %.2f ms\n", k, (long long)wk[k].n,
-                                    (dbg[3 * k] - t0) * 1e-5, ((double)pub[k] - (double)t0) * 1e-5, (dbg[3 * k + 1] - t0) * 1e-5, (dbg[3 * k + 2] - t0) * 1e-5);
-            {
-                int hist[16] = {};
-                for (int k = 0; k < gather_blocks; k++) { const int v = ((volatile uint8_t *)h->h_started)[k]; if (v) hist[(v - 1) & 15]++; }
-                fprintf(stderr, "   gather workgroups per XCD: %d %d %d %d %d %d %d %d\n",
-                        hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7]);
-            }
-            for (int r = 0; r < 8; r++) {
-                double lat = 0, disp = 0; int nl = 0, nd = 0;
-                for (size_t k = 0; k < nw; k++) {
-                    if (xcc[k] != r) continue;
-                    if (k < 1000) { lat += (double)(dbg[3 * k + 2] - dbg[3 * k + 1]) * 1e-5 / ((double)wk[k].n * 1e-3); nl++; }
-                    else if (k >= 3000) { disp += (double)(dbg[3 * k] - t0) * 1e-5; nd++; }
-                }
-                fprintf(stderr, "   XCD %d: %.3f ms per 1000 anchors for its calls among the 1000 longest; items 3000.. dispatched after %.1f ms on average\n",
-                        r, nl ? lat / nl : 0., nd ? disp / nd : 0.);
-            }
-            (void)hipFree(d_dbg);
-            if (d_pub) (void)hipFree(d_pub);
-        }
-    }
+    if (trace) chain_fed_report(h, wk, chunks.size(), tv, d_dbg, d_pub, gather_blocks);
     if (((uint32_t *)h->h_evals)[4] != 0) {
         // a wait gave up (seconds without its anchors: a stalled bus, a pre-empted gather kernel).  Every waiting workgroup
         // has left, the grid has drained, nothing was lost but time: the caller takes the copy-engine path instead.
@@ -2481,9 +2355,7 @@ extern "C" int gab_chain_run(gab_chain *h, int mode, const uint64_t *x, const ui
     const size_t t = (size_t)total;
     rc = h->io.reserve(24 * t + 64);
     if (rc) return rc;
-    char *b = h->io.as<char>();
-    uint64_t *dx = (uint64_t *)b, *dy = (uint64_t *)(b + 8 * t);
-    int32_t *ds = (int32_t *)(b + 16 * t), *dp = (int32_t *)(b + 20 * t);
+    const auto [dx, dy, ds, dp] = chain_io(h, t);
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
     // (GAB_CHAIN_FEED_MIN: tests push small batches through the big-batch paths)
@@ -2500,8 +2372,7 @@ extern "C" int gab_chain_run(gab_chain *h, int mode, const uint64_t *x, const ui
     GAB_HIP(hipMemcpyAsync(dy, y, 8 * t, hipMemcpyHostToDevice, s));
     rc = gab_chain_run_device(h, mode, dx, dy, call_off, hdr, ncalls, ds, dp, s);
     if (rc) return rc;
-    GAB_HIP(hipMemcpyAsync(score_out, ds, 4 * t, hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(parent_out, dp, 4 * t, hipMemcpyDeviceToHost, s));
+    if ((rc = chain_copy_results(score_out, parent_out, ds, dp, t, s)) != GAB_OK) return rc;
     GAB_HIP(hipStreamSynchronize(s));
     return GAB_OK;
 }

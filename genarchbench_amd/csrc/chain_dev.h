@@ -66,6 +66,79 @@ __device__ __forceinline__ int32_t chain_gap_cost(int32_t dd, double avg_d) {
     return gap - (gap >> 31);
 }
 
+// the fp32-floor gap cost of fast-chain's AVX code for one dd (the entries of a call's gap table; k32 = (float)(.01 * avg_qspan))
+__device__ __forceinline__ int32_t fastchain_gap32(int32_t dv, float k32) {
+    // ilog2(dv) >> 1 with ilog2(0) = 0:  (31 - clz(dv | 1)) >> 1 = 15 - (clz(dv | 1) >> 1)
+    return (int32_t)floorf(__fmul_rn((float)dv, k32)) + (15 - (__clz((int)((uint32_t)dv | 1u)) >> 1));
+}
+
+// fast-chain, the score-independent part of a pair (anchor a, predecessor j) in the AVX code's wrapped 32-bit arithmetic, for the
+// callers that read the gap cost from the call's table -- the counterpart of chain's chain_geometry_plain_pre (chain.hip).  Returns
+// the overlap term; idx = the table entry (dd = |ddr - ddq| for 0 .. bw, and bw + 1 where every dd > bw lands and the wrapped
+// INT_MIN, which `dd > bw` lets through like the AVX code does); ok = the pair passes the filters; wrapped = dd is that INT_MIN.
+// mq_u = min(max_dist_y, max_dist_x) clamped at 0 (negative limits reject every predecessor):
+// ddq <= 0 || ddq > max_dist_y || ddq > max_dist_x  ==  (unsigned)(ddq - 1) >= mq_u
+__device__ __forceinline__ int32_t fastchain_pair_pre(uint32_t xa, uint32_t ya, int32_t qsa, uint32_t xj, uint32_t yj, int32_t bw, uint32_t mq_u,
+                                                      uint32_t &idx, bool &ok, bool &wrapped) {
+    const int32_t ddr = (int32_t)(xa - xj);
+    const int32_t ddq = (int32_t)(ya - yj);
+    const int32_t diff = (int32_t)((uint32_t)ddr - (uint32_t)ddq);
+    const int32_t dd = max(diff, (int32_t)(0u - (uint32_t)diff));          // |diff| with the AVX wrap-around for INT_MIN
+    ok = !(dd > bw || ddr == 0 || (uint32_t)ddq - 1u >= mq_u);
+    wrapped = dd < 0;
+    idx = min((uint32_t)dd, (uint32_t)bw + 1u);
+    return min(min(ddr, ddq), qsa);
+}
+__device__ __forceinline__ int32_t fastchain_pair_pre(uint32_t xa, uint32_t ya, int32_t qsa, uint32_t xj, uint32_t yj, int32_t bw, uint32_t mq_u,
+                                                      uint32_t &idx, bool &ok) {
+    bool wrapped;
+    return fastchain_pair_pre(xa, ya, qsa, xj, yj, bw, mq_u, idx, ok, wrapped);
+}
+
+// the window test of the start search: chain host_kernel.cpp:56-57, fast-chain host_kernel.cpp:200-207 (unsigned difference)
+template <bool FC> __device__ __forceinline__ bool chain_beyond(uint64_t xi, uint64_t xj, uint64_t mdx64) { return FC ? (xi - xj) > mdx64 : xi > xj + mdx64; }
+
+// The reference's one-pointer window start for anchor i (x = xi, wave-uniform), by one whole wave:
+//     while (st < i && beyond(x[i], x[st])) ++st;   if (i - st > max_iter) st = i - max_iter;
+// 64 candidates per ballot.  XS = x[sb + lane] is the wave's view of the candidates, sb <= st its base; both move with the pointer.
+// X: the call's anchors (a pointer or an AnchorView), I: the index type of the caller (int, or int64_t in fastchain_body).
+template <bool FC, class Anchors, class I>
+__device__ __forceinline__ void chain_window_advance(const Anchors &X, I n, I i, uint64_t xi, uint64_t mdx64, int lane, I &st, I &sb, uint64_t &XS) {
+    for (;;) {
+        const I cand = sb + lane;
+        const bool pass = cand < st || (cand < i && chain_beyond<FC>(xi, XS, mdx64));
+        const unsigned long long m = __ballot(pass);
+        if (m == ~0ull) { sb += 64; st = sb; XS = (sb + lane < n) ? X[sb + lane] : 0; continue; }
+        st = sb + __builtin_ctzll(~m);
+        break;
+    }
+    if (i - st > kMaxIter) st = i - kMaxIter;
+    if (st - sb >= 64) { sb = st & ~(I)63; XS = (sb + lane < n) ? X[sb + lane] : 0; }
+}
+
+// Per-call facts.  plain = every anchor of the call carries the same segment id (then "sidi == sidj" is always true and the
+// cross-segment gap rule never applies), max(x) - min(x) + min(max_dist) < 2^31 - 1 (then every x[i] - x[j] of the call is exact in
+// 32 bits and dq - dr cannot wrap for a pair that passes the dq filter, dq in [1, min(max_dist_x, max_dist_y)]: dd = |dr - dq| is an
+// exact value in [0, 2^31)), and 0 <= bw <= gap_tab_max (the call's gap costs fit the table of kGapTab entries).
+__device__ __forceinline__ bool chain_call_plain(const ChainWork &w, unsigned long long lo, unsigned long long hi, bool mixed, int gap_tab_max) {
+    const int32_t mq = w.max_dist_y < w.max_dist_x ? w.max_dist_y : w.max_dist_x;
+    const unsigned long long lim = mq < 0 ? 0ull : (unsigned long long)mq;
+    return w.n > 0 && !mixed && hi - lo + lim < 0x7fffffffull && w.bw >= 0 && w.bw <= gap_tab_max;
+}
+// ... and what it is decided on: every thread's (min x, max x, flag bits) -> the block's, in ALL 256 threads.  One barrier; the caller
+// puts another between two uses.
+__device__ __forceinline__ void chain_block_range(unsigned long long &lo, unsigned long long &hi, uint32_t &flags) {
+    __shared__ unsigned long long s_lo[4], s_hi[4];
+    __shared__ uint32_t s_flags[4];
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; flags |= __shfl_xor(flags, o);
+    }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_flags[threadIdx.x >> 6] = flags; }
+    __syncthreads();
+    for (int k = 0; k < 4; k++) { lo = s_lo[k] < lo ? s_lo[k] : lo; hi = s_hi[k] > hi ? s_hi[k] : hi; flags |= s_flags[k]; }
+}
+
 __device__ __forceinline__ int32_t chain_geometry(uint64_t xi, int32_t qi, int32_t q_span, int32_t sidi, uint64_t xj, uint32_t yj,
                                                   int32_t sidj, int32_t mdx, int32_t mdy, int32_t bw, bool multi_seg, double avg_d,
                                                   bool &ok) {

@@ -74,14 +74,14 @@ template <int MODE>
 __global__ __launch_bounds__(256) void ctab_prep(const ChainWork *__restrict__ work, TabCall *calls, uint32_t *bail,
                                                  const uint64_t *__restrict__ xs, const uint64_t *__restrict__ ys, int32_t *gtab) {
     constexpr bool FC = MODE == GAB_FASTCHAIN;
-    __shared__ unsigned long long s_lo[4], s_hi[4];
-    __shared__ int s_flag[4], s_qmin[4], s_qmax[4], s_gmax[4];
+    __shared__ int s_qmin[4], s_qmax[4], s_gmax[4];
     const ChainWork w = work[blockIdx.x];
     TabCall &tc = calls[blockIdx.x];
     const uint64_t *X = xs + w.off, *Y = ys + w.off;
     const int64_t n = w.n;
     unsigned long long lo = ~0ull, hi = 0;
-    int flag = 0, qmin = 255, qmax = 0;                        // flag bit 0: segment ids differ, bit 1: x does not ascend
+    uint32_t flag = 0;
+    int qmin = 255, qmax = 0;                                  // flag bit 0: segment ids differ, bit 1: x does not ascend
     const uint32_t sid0 = n > 0 ? (uint32_t)(Y[0] >> 48 & 0xff) : 0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const unsigned long long x = X[i], y = Y[i];
@@ -101,41 +101,29 @@ __global__ __launch_bounds__(256) void ctab_prep(const ChainWork *__restrict__ w
         for (int d = threadIdx.x; d <= w.bw; d += 256) {
             int gc;
             if (FC) {
-                const int lgh = 15 - (__clz((int)((uint32_t)d | 1u)) >> 1);
-                gc = (int32_t)floorf(__fmul_rn((float)d, k32)) + lgh;
-                const int gd = (int32_t)__dmul_rn(__dmul_rn((double)d, .01), avg_d) + lgh;     // the scalar tail's cost (narrow windows)
+                gc = fastchain_gap32(d, k32);
+                const int gd = (int32_t)__dmul_rn(__dmul_rn((double)d, .01), avg_d) + (15 - (__clz((int)((uint32_t)d | 1u)) >> 1));     // the scalar tail's cost (narrow windows)
                 gmax = gd > gmax ? gd : gmax;
             } else gc = chain_gap_cost(d, avg_d);
             gmax = gc > gmax ? gc : gmax;
         }
     for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
-        lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; flag |= __shfl_xor(flag, o);
         const int a = __shfl_xor(qmin, o), b = __shfl_xor(qmax, o), g = __shfl_xor(gmax, o);
         qmin = a < qmin ? a : qmin; qmax = b > qmax ? b : qmax; gmax = g > gmax ? g : gmax;
     }
     const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_lo[wv] = lo; s_hi[wv] = hi; s_flag[wv] = flag; s_qmin[wv] = qmin; s_qmax[wv] = qmax; s_gmax[wv] = gmax; }
-    __syncthreads();
-    for (int k = 0; k < 4; k++) {
-        lo = s_lo[k] < lo ? s_lo[k] : lo; hi = s_hi[k] > hi ? s_hi[k] : hi; flag |= s_flag[k];
-        qmin = s_qmin[k] < qmin ? s_qmin[k] : qmin; qmax = s_qmax[k] > qmax ? s_qmax[k] : qmax; gmax = s_gmax[k] > gmax ? s_gmax[k] : gmax;
-    }
+    if ((threadIdx.x & 63) == 0) { s_qmin[wv] = qmin; s_qmax[wv] = qmax; s_gmax[wv] = gmax; }
+    chain_block_range(lo, hi, flag);       // (its barrier also covers the three arrays above)
+    for (int k = 0; k < 4; k++) { qmin = s_qmin[k] < qmin ? s_qmin[k] : qmin; qmax = s_qmax[k] > qmax ? s_qmax[k] : qmax; gmax = s_gmax[k] > gmax ? s_gmax[k] : gmax; }
     const int32_t mq = w.max_dist_y < w.max_dist_x ? w.max_dist_y : w.max_dist_x;
-    const unsigned long long lim = mq < 0 ? 0ull : (unsigned long long)mq;
     bool ok = n >= 1 && n < (1 << 24) && !(flag & 2) && qmin >= 1 && avg_ok && bw_ok && w.max_dist_x >= 0 && w.max_dist_x < (1 << 30) &&
               (long long)n * qmax < (1 << 24) - (1 << 15);                     // (a score fits the 24 bits above the key's code)
-    if (FC) ok = ok && lim <= (1u << 20);
-    else ok = ok && !(flag & 1) && hi - lo + lim < 0x7fffffffull && hi <= ~0ull - (unsigned long long)w.max_dist_x;   // chain_facts_kernel's "plain", and x + max_dist_x cannot wrap
+    if (FC) ok = ok && mq <= (1 << 20);
+    else ok = ok && chain_call_plain(w, lo, hi, (flag & 1) != 0, kGapTab - 2) && hi <= ~0ull - (unsigned long long)w.max_dist_x;   // plain, and x + max_dist_x cannot wrap
     const int bias = gmax + 1;
     ok = ok && qmax + bias <= 255;
     if (ok) {
-        for (int d = threadIdx.x; d <= w.bw; d += 256) {
-            int gc;
-            if (FC) gc = (int32_t)floorf(__fmul_rn((float)d, k32)) + (15 - (__clz((int)((uint32_t)d | 1u)) >> 1));
-            else gc = chain_gap_cost(d, avg_d);
-            gtab[tc.gt_off + d] = gc - bias;
-        }
+        for (int d = threadIdx.x; d <= w.bw; d += 256) gtab[tc.gt_off + d] = (FC ? fastchain_gap32(d, k32) : chain_gap_cost(d, avg_d)) - bias;
         if (threadIdx.x == 0) gtab[tc.gt_off + w.bw + 1] = 1 << 20;           // dd > bw: the byte comes out as 0
     }
     if (threadIdx.x == 0) { tc.bias = bias; tc.ok = ok ? 1 : 0; tc.ngrp = 0; bail[blockIdx.x] = ok ? 0u : 1u; }
@@ -150,9 +138,6 @@ __global__ __launch_bounds__(256) void ctab_blocks_init(const TabCall *__restric
         blocks[tc.blk0 + k] = b;
     }
 }
-
-// the window test of the start search: chain host_kernel.cpp:56-57, fast-chain host_kernel.cpp:200-207 (unsigned difference)
-template <bool FC> __device__ __forceinline__ bool ctab_beyond(uint64_t xi, uint64_t xj, uint64_t mdx64) { return FC ? (xi - xj) > mdx64 : xi > xj + mdx64; }
 
 // ---- 3. window starts (one wave per block) ----------------------------------------------------------------------------------------
 // The reference advances ONE pointer: while (st < i && beyond(x[i], x[st])) ++st; then st = max(st, i - max_iter).  With x
@@ -180,7 +165,7 @@ __global__ __launch_bounds__(256) void ctab_st(const ChainWork *__restrict__ wor
         int lo = 0, hi = ia;                                   // beyond(x[i], x[i]) is false: the bound is at most i
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (ctab_beyond<FC>(xi, X[mid], mdx64)) lo = mid + 1; else hi = mid;
+            if (chain_beyond<FC>(xi, X[mid], mdx64)) lo = mid + 1; else hi = mid;
         }
         st = lo > ia - kMaxIter ? lo : ia - kMaxIter;
         st_all[w.off + ia] = st;
@@ -406,24 +391,6 @@ constexpr int kTabMaxPatch = 8;            // anchors of a call whose result max
 #ifndef GAB_TAB_NEAR_LDS
 #define GAB_TAB_NEAR_LDS 1
 #endif
-#ifndef GAB_KO_CERT_FAR          // timing experiments (wrong results for calls whose certificate misses)
-#define GAB_KO_CERT_FAR 0
-#endif
-#ifndef GAB_KO_CERT_NEAR
-#define GAB_KO_CERT_NEAR 0
-#endif
-#ifndef GAB_KO_OKH
-#define GAB_KO_OKH 0
-#endif
-#ifndef GAB_KO_MAIN_NEAR      // (with GAB_KO_CERT_FAR = GAB_KO_CERT_NEAR = 1: the keys are garbage, nothing may act on them)
-#define GAB_KO_MAIN_NEAR 0
-#endif
-#ifndef GAB_KO_MAIN_BLOCK
-#define GAB_KO_MAIN_BLOCK 0
-#endif
-#ifndef GAB_KO_MAIN_MERGE
-#define GAB_KO_MAIN_MERGE 0
-#endif
 struct TabDesc { long long grp; int jrow0, ng; };       // what ctab_fold needs of a TabBlock
 struct TabLds {
     int4 G4[2][2][16][64];                // [slot][previous block | block itself][row / 4][anchor]: keys of 4 rows
@@ -594,7 +561,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                 }
 #else
 #pragma unroll
-                for (int hh = 0; hh < (GAB_KO_MAIN_MERGE ? 1 : NF); hh++) {
+                for (int hh = 0; hh < NF; hh++) {
                     const int32_t b2 = L.part_best[par ^ 1][hh][lane], g2 = L.part_g[par ^ 1][hh][lane];
                     if (b2 > fbest || (b2 == fbest && g2 > fg)) { fbest = b2; fg = g2; }
                 }
@@ -614,7 +581,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                 }
                 if (!kHelpM && t > 0) {
 #else
-                if (t > 0 && !GAB_KO_MAIN_NEAR) {
+                if (t > 0) {
 #endif
 #if GAB_TAB_NEAR_LDS
                     // (the previous block's scores come back from LDS as broadcasts, four per 16-byte read, instead of 64 v_readlane:
@@ -642,7 +609,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                 // the block itself, in units of four anchors closed by the workers (see there): the kernel's only chain of dependent
                 // steps is four readlanes (the unit's scores before the unit), four adds, two three-way maxima -- per FOUR anchors
 #pragma unroll
-                for (int g4 = 0; g4 < (GAB_KO_MAIN_BLOCK ? 0 : 16); g4++) {
+                for (int g4 = 0; g4 < 16; g4++) {
                     const int4 g = gb[(size_t)g4 * 64];
                     const int32_t x0 = __builtin_amdgcn_readlane(key, 4 * g4) & ~127, x1 = __builtin_amdgcn_readlane(key, 4 * g4 + 1) & ~127,
                                   x2 = __builtin_amdgcn_readlane(key, 4 * g4 + 2) & ~127, x3 = __builtin_amdgcn_readlane(key, 4 * g4 + 3) & ~127;
@@ -665,11 +632,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
             }
         } else if constexpr (ROLE == 1) {
             // ------------------------------------------------ resolver: parents (chain: and the certificate), two blocks behind
-#ifdef GAB_KO_TAB_RES
-            if (false) {
-#else
             if (t - 2 >= min_blk) {
-#endif
                 const int r = t - 2;
                 const int i0 = r * 64;
                 const int nb = n - i0 < 64 ? n - i0 : 64;
@@ -698,7 +661,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                         if (far && bb != 0 && v == best && kstar < 0) kstar = k;
                     }
                     if (far) parent = j0 + kstar;            // (kstar >= 0: the group's maximum is attained in it)
-                    if (!FC && !GAB_KO_CERT_FAR) {
+                    if (!FC) {
                         // unfiltered predecessors newer than the argmax among the far ones: the rest of its group, then every later group
                         if (far) {
 #pragma unroll
@@ -725,7 +688,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                         }
                     }
                 }
-                if (!FC && !GAB_KO_CERT_NEAR) {
+                if (!FC) {
                     // ... and among the near / in-block pairs: pair numbers code .. 127 (pair code - 1 is the argmax; all of them for a far one)
 #pragma unroll
                     for (int wd2 = 0; wd2 < 4; wd2++) {
@@ -736,7 +699,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                 }
                 if (pl) for (int q = 0; q < L.patch_n; q++) if (L.patch_blk[q] == r && L.patch_lane[q] == lane) parent = L.patch_parent[q];
                 if (mine) { P[i0 + lane] = parent; if (host_parent) host_parent[w.hoff + i0 + lane] = parent; }
-                if (!FC && !GAB_KO_CERT_NEAR) {
+                if (!FC) {
                     unsigned long long miss = __ballot(mine && !none && !pl && risk > kMaxSkip);
                     if (miss) {
                         // max_skip may have cut these anchors' scans short (the certificate of chain_hw_kernel does not hold): the
@@ -806,11 +769,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
 #pragma unroll
             for (int q = 0; q < 2; q++) {
                 const int u = unit_of(q);
-#ifdef GAB_KO_TAB_G
-                if (false) {
-#else
                 if (u < 8) {
-#endif
                     const bool nearu = u < 4;
                     const bool pl = !FC && L.patch_n && patched(kb);       // nothing is folded into a patched anchor
                     const uint32_t wd[4] = {pl ? 0u : cg[q].x, pl ? 0u : cg[q].y, pl ? 0u : cg[q].z, pl ? 0u : cg[q].w};
@@ -848,7 +807,7 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                         }
                         dst[(size_t)q4 * 64] = make_int4(gv[0], gv[1], gv[2], gv[3]);
                     }
-                    if (!FC && !GAB_KO_OKH) L.okh[kb & 3][u][lane] = (uint16_t)bits;
+                    if (!FC) L.okh[kb & 3][u][lane] = (uint16_t)bits;
                 }
             }
             // the far groups (scores final since block t - 1), dealt round-robin
@@ -872,11 +831,9 @@ void ctab_fold(const ChainWork *__restrict__ work, const TabCall *__restrict__ c
                 const bool up = gmax >= best && gmax > kTabNegH;      // groups ascend: the newer group wins a tie
                 best = up ? gmax : best; bg = up ? fgi : bg;
             };
-#ifndef GAB_KO_TAB_FAR
 #pragma unroll
             for (int q = 0; q < kTabF; q++) { const int fgi = fw + NF * q; if (fw >= 0 && fgi < nfar) far_group(cf[q], fgi); }
             if (fw >= 0) for (int fgi = fw + NF * kTabF; fgi < nfar; fgi += NF) far_group(T8[(d.grp + fgi) * 64 + lane], fgi);      // deep windows
-#endif
 #if GAB_TAB_MERGE_ATOMIC
             if (fw >= 0 && bg >= 0) atomicMax(&L.part64[par][lane], (long long)(((unsigned long long)(uint32_t)best << 32) | (uint32_t)bg));
 #else

@@ -213,6 +213,30 @@ def test_fed_path_two_handles_on_one_gpu(mode, monkeypatch, kernel_choice):
 
 
 @pytest.mark.parametrize("mode", [0, 1])
+def test_fed_path_facts_at_their_limits(eng, mode, monkeypatch, kernel_choice):
+    """the fed path decides a call's "plain" fact in its gather kernel (one segment id, x span + min(max_dist) < 2^31 - 1,
+    0 <= bw <= 2046), chunk by chunk: calls on either side of each of those limits, through gab_chain_run on page-locked arrays"""
+    if kernel_choice != "default-split":
+        pytest.skip("one kernel choice is enough for the host path")
+    from tests import chain_form_cases as cfc
+    monkeypatch.setenv("GAB_CHAIN_FEED_MIN", "1000")
+    cases = cfc.limit_cases()
+    batches = [(name,) + tuple(cases[name][k] for k in (0, 2)) for name in ("x_span_2p31", "n_segs_header_against_data", "bw_neg1", "x_top_of_64_bits")]
+    rng = np.random.default_rng(67)
+    batches.append(("bw_2046_and_2047", [cfc.call(*cfc.diagonal(rng), bw=bw) for bw in (2046, 2047)], [True, True]))
+    for name, calls, chains in batches:
+        batch = gabgen.chain_from_calls(calls)
+        assert 4000 <= batch.x.size <= 8000
+        ws, wp = pyoracle.chain(batch, mode)
+        for c, chained in enumerate(chains):       # a filter that rejects everything cannot pass
+            o, n = int(batch.call_off[c]), int(batch.hdr["n"][c])
+            assert not chained or (wp[o:o + n] >= 0).sum() > 500, (name, c)
+        s, p = eng.host_chain_kernel(batch, mode, pinned=True)
+        np.testing.assert_array_equal(s, ws, err_msg=name)
+        np.testing.assert_array_equal(p, wp, err_msg=name)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
 def test_gap_cost_table_limits(eng, mode):
     """the block kernels read the gap cost of a pair from a per-call table of bw + 2 entries when 0 <= bw <= 2046 and
     compute it otherwise: band widths on both sides of the limit, 0 and 1, with diagonal differences from 0 to beyond bw,

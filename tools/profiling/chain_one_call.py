@@ -2,8 +2,9 @@
 """Latency of chain / fast-chain calls through gab_chain_run_device (profiles/r03_chain_latency.md): batches of 1 .. 512 generated
 calls of exactly N anchors, kernel time from the library's HIP events (best of three after a warm-up).
     python tools/profiling/chain_one_call.py [label] [mode 0|1] [anchors per call] [call counts ...]
-GAB_CHAIN_FAST_MIN=1 puts every call into the latency form, GAB_CHAIN_FAST_CALLS=0 none; GAB_LIB_PATH selects a knock-out build
-(-DGAB_KO_SEARCH / _FAR / _G / _MAIN in chain.hip: parts of chain_fast_kernel removed -- wrong results, only the time counts)."""
+GAB_CHAIN_FAST_MIN=1 puts every call into the latency form, GAB_CHAIN_FAST_CALLS=0 none; GAB_LIB_PATH selects a knock-out build:
+apply tools/experiments/chain_knockouts.patch (it lists the -DGAB_KO_* flags: parts of chain_fast_kernel / ctab_fold removed -- wrong
+results, only the time counts), then build the variant with tools/profiling/build_variant.sh."""
 import os
 import sys
 
