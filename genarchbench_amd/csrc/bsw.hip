@@ -99,6 +99,35 @@
 //      reference's test fires only if its rowmax < best - zdrop, hence only if ours is; the guard abandons exactly those rows, before
 //      our own test reads a column that may not be the reference's.  In every row that is kept neither run's test can fire.
 //
+// Right prune of score-only calls (same calls, same pairs: restrictions (a) and (b)).  After the left prune, with jl the last live
+// stored cell -- where the reference's right trim stopped; the next end is min(jl + 2, qlen) -- the right edge moves over cell jl
+// while jl >= beg and
+//     m(jl) == 0   or   m(jl) + max_sc * min(R, qlen - jl) <= best:
+// the cell is SET TO ZERO (Hd = Ev = 0), jl moves one cell left, and end = min(jl + 2, qlen) afterwards.  A drop of a live cell
+// sets `dropped`.  On the read-like input the run evaluates 0.725 of the cells that the left prune alone leaves
+// (profiles/bsw_right_prune.md).
+// Cap, both sides: per row an edge moves over at most the four cells next to the edge the row was swept with -- beg0 .. beg0 + 3 on
+// the left, end0 - 3 .. end0 on the right, the windows the zero trim fetches anyway -- and a row whose zero trim has run past its
+// window prunes nothing on that side.  Any subset of the drops is safe (each drop is justified by its own cell), so the cap needs
+// no argument of its own; it costs 0.7 % more cells than the uncapped left rule and removes its cell-by-cell loop.
+// Proof, continued.
+//   8. The test is step 2's: Hd[jl] leads to cell (i + 1, jl) with qlen - jl columns left, Ev[jl] to the same cell with fewer, so a
+//      dropped cell is zero or stands for a dead cell of the reference; writing zero keeps P <= reference with the reference's cell
+//      dead.  Unlike a cell left of beg, a cell right of end IS read again when the band grows, and (a) rests on all of those being
+//      zero: the zeroing is what keeps (a) true, and with it steps 4 and 5 as they stand.  The rest is the reference's own
+//      zero-trim bookkeeping on a row whose last cells are zero: end = jl + 2, the exit's bound pass over [beg, end].
+//   9. The guards are unchanged because a right drop sets `dropped` like a left one.  Step 5's F: stored cell jl holds
+//      H(i, jl - 1), which has one column more left than the F that leaves column jl - 1 and is at least that F + e_ins, so the
+//      cell's test implies the F test for every dropped cell; for the F that leaves the narrowed band in a LATER row the
+//      right-edge guard stands as it is.  Step 7 holds for any pair with rowmax <= the reference's.
+//  10. Zero-row guard.  Step 4 used "a pair that still holds column 0 has dropped nothing"; the right prune drops cells of such
+//      pairs.  With rowmax == 0 every cell of the reference's row is still dead, but dead cells may keep the reference's row maximum
+//      above zero and its row loop alive until the left edge raises the score, where the pruned run would stop.  So a row with
+//      rowmax == 0 of a pair that has dropped a live cell, has beg == 0 and a left edge hb = h0 - o_del - e_del * (i + 1) > 0
+//      (stored cell 0, the diagonal of cell (i + 1, 0)) with hb + max_sc * min(R, qlen) > best abandons the pass like the other
+//      two guards.  With a dead or zero edge nothing the reference still holds can exceed best, and ending returns its score.
+//      (9 of the 10 M read-like pairs at the defaults; found by the model at a mismatch score of -128, where rows of zeros are common.)
+//
 // Roofline: integer-VALU / LDS bound (~20 VALU + 1 LDS read + 1 LDS write per DP cell,
 // ~7.4 k cells per ~210 input bytes); HBM traffic is the algorithmic minimum
 // len1 + len2 + 12 B per pair plus the 4-byte permutation entry.
@@ -285,11 +314,11 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
             lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
             lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
         }
-        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the left prune of the header comment apply
-        // the left prune needs every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the two prunes of the header comment apply
+        // the prunes need every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
         bool prune = score_only && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
         int best, best_i, best_j, g_i, gscore, max_off;
-      for (;;) {                                            // second trip: a pair the z-drop guard sent back, prune off
+      for (;;) {                                            // second trip: a pair one of the guards sent back, prunes off
         // row -1 (bandedSWA.cpp:159-161); E starts at 0 everywhere
         {
             int prev = h0;
@@ -306,7 +335,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
         best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
         int beg = 0, end = qlen;
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
-        bool dropped = false, abandon = false;              // the prune has dropped a live cell; the z-drop guard fired
+        bool dropped = false, abandon = false;              // a prune has dropped a live cell; one of the three guards fired
         uint32_t tw = load_u32_unaligned(t);       // 4 reference bases, refreshed every 4 rows
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -321,6 +350,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
             if (beg < i - w) beg = i - w;
             if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + c.max_sc * (qlen - end)); }
             if (end > qlen) end = qlen;
+            const int beg0 = beg, end0 = end;               // the band this row is swept with: either prune moves its edge by at most four cells
             int hleft = 0;
             if (beg == 0) { hleft = h0 - (c.o_del + e_del * (i + 1)); hleft = hleft > 0 ? hleft : 0; }
             int f = 0;
@@ -361,7 +391,13 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 if (!(gscore > hleft)) g_i = i;
                 gscore = hleft > gscore ? hleft : gscore;
             }
-            if (rowmax == 0) break;
+            if (rowmax == 0) {                              // zero-row guard of the right prune (header comment, step 10)
+                if (dropped && beg == 0) {
+                    const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
+                    abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                }
+                break;
+            }
             const int rows_left = tlen - 1 - i;
             bool try_exit = false;
             if (rowmax > best) {
@@ -391,6 +427,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 beg = j;
                 for (j = end; j >= beg && H[j * 64] == 0u; j--) {}
             }
+            int jl = j;                                     // the last live stored cell (beg - 1: none)
             end = j + 2 < qlen ? j + 2 : qlen;
             if (prune && beg < end) {                       // left prune: cell beg is live here, the zero trim stopped at it
                 bool go = true;
@@ -399,13 +436,24 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                     go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
                 }
                 if (go) {
-                    for (j = beg; j < end; j++) {
+                    const int lcap = min(end, beg0 + 4);
+                    for (j = beg; j < lcap; j++) {
                         const int m = WIDE ? max((int)H[j * 64], (int)E[j * 64]) : max((int)(H[j * 64] & 0xffffu), (int)(H[j * 64] >> 16));
                         if (m && m + c.max_sc * min(rows_left, qlen - j) > best) break;
                     }
                     dropped = dropped || j > beg;
                     beg = j;
                 }
+            }
+            if (prune && jl >= beg) {                       // right prune: cell jl is live here; dropped cells are zeroed (header comment)
+                const int from = jl;
+                for (; jl >= beg && jl > end0 - 4; jl--) {
+                    const int m = WIDE ? max((int)H[jl * 64], (int)E[jl * 64]) : max((int)(H[jl * 64] & 0xffffu), (int)(H[jl * 64] >> 16));
+                    if (m && m + c.max_sc * min(rows_left, qlen - jl) > best) break;
+                    H[jl * 64] = 0u;
+                    if (WIDE) E[jl * 64] = 0u;
+                }
+                if (jl < from) { dropped = true; end = jl + 2 < qlen ? jl + 2 : qlen; }
             }
             if (try_exit) {
                 int bound = stale_pot;
@@ -558,11 +606,11 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
             lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
         }
-        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the left prune of the header comment apply
-        // the left prune needs every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
+        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the two prunes of the header comment apply
+        // the prunes need every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
         bool prune = score_only && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
         int best, best_i, best_j, g_i, gscore, max_off;
-      for (;;) {                                            // second trip: a pair the z-drop guard sent back, prune off
+      for (;;) {                                            // second trip: a pair one of the guards sent back, prunes off
         // row -1 (bandedSWA.cpp:159-161); E = 0
         {
             int prev = h0;
@@ -578,7 +626,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
         int beg = 0, end = qlen;
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
-        bool dropped = false, abandon = false;              // the prune has dropped a live cell; the z-drop guard fired
+        bool dropped = false, abandon = false;              // a prune has dropped a live cell; one of the three guards fired
         uint32_t tw = load_u32_unaligned(t);
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -707,7 +755,13 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 if (!(gscore > hleft)) g_i = i;
                 gscore = hleft > gscore ? hleft : gscore;
             }
-            if (rowmax == 0) break;
+            if (rowmax == 0) {                              // zero-row guard of the right prune (header comment, step 10)
+                if (dropped && beg == 0) {
+                    const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
+                    abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                }
+                break;
+            }
             // One LDS round trip for what the rest of the row needs: the three pair words that hold the row maximum's
             // candidate columns and the six of the band trimming.  H(i, c) is the low byte of stored cell c + 1 and cell
             // `end` holds H(i, end - 1), so the candidates kj .. kj + 3 are cells kj + 1 .. kj + 4: pair words
@@ -767,26 +821,27 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 uint64_t y = (uint64_t)e2 << 32 | e1;                      // cells 2pe-2 .. 2pe+1; cell `end` goes on top
                 if (!(end & 1)) y = (y << 16) | (e0 >> 16);
                 const int tz = y ? __builtin_clzll(y) >> 4 : 4;
+                const int end0 = end;
                 j = end - tz;
                 if (tz == 4) for (; j >= beg && CELL16(j) == 0; j--) {}
                 j = j > beg - 1 ? j : beg - 1;
+                const int jl = j;                                          // the last live stored cell (beg - 1: none)
                 end = j + 2 < qlen ? j + 2 : qlen;
                 // Left prune (header comment): cell beg is live here, the zero trim stopped at it.  The four cells of x are
                 // judged in packed 16-bit halves -- m = max(H, E) <= 255 and max_sc * columns left <= 255, and a half right of
-                // the band or the query may hold anything: the clamp to `end` below undoes what it adds -- and the cell-by-cell
-                // loop runs only when all four go or the zero trim has left them behind.
-                if (prune && beg < end) {
-                    bool go = true;
-                    if (beg == 0) {
-                        const int hb = h0 - c.o_del - e_del * (i + 2);
-                        go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
-                    }
-                    if (go) {
-                        j = beg;
-                        if (lz < 4) {
+                // the band or the query may hold anything: the clamp to `end` below undoes what it adds.  The edge moves over
+                // these four cells at most; a row whose zero trim has left them behind (lz == 4) prunes nothing.
+                if (prune) {
+                    const uint32_t r2 = as_u32(pk_splat(min(rows_left, qlen))), m2 = as_u32(pk_splat(c.max_sc));
+                    const uint32_t best2 = (uint32_t)best * 0x00010001u;
+                    if (beg < end && lz < 4) {
+                        bool go = true;
+                        if (beg == 0) {
+                            const int hb = h0 - c.o_del - e_del * (i + 2);
+                            go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
+                        }
+                        if (go) {
                             const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
-                            const uint32_t r2 = as_u32(pk_splat(min(rows_left, qlen))), m2 = as_u32(pk_splat(c.max_sc));
-                            const uint32_t best2 = (uint32_t)best * 0x00010001u;
                             const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
                             const uint32_t ml = pk_max_i16(xl & 0x00ff00ffu, (xl >> 8) & 0x00ff00ffu);
                             const uint32_t mh = pk_max_i16(xh & 0x00ff00ffu, (xh >> 8) & 0x00ff00ffu);
@@ -798,17 +853,33 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                             const uint64_t stay = (uint64_t)sh << 32 | sl;
                             const int lp = stay ? __builtin_ctzll(stay) >> 4 : 4;
                             j = beg0 + lp;
-                            if (lp < 4) go = false;
+                            j = j < end ? j : end;
+                            dropped = dropped || j > beg;
+                            beg = j;
                         }
-                        if (go)
-                            for (; j < end; j++) {
-                                const uint32_t cv = CELL16(j);
-                                const int m = max((int)(cv & 0xffu), (int)(cv >> 8));
-                                if (m && m + c.max_sc * min(rows_left, qlen - j) > best) break;
-                            }
-                        j = j < end ? j : end;
-                        dropped = dropped || j > beg;
-                        beg = j;
+                    }
+                    // Right prune (header comment): the four cells of y, end0 - 3 .. end0, judged the same way from the top; a half
+                    // left of `beg` or of the query may hold anything: the clamp to beg - 1 undoes what it adds.  A row whose zero
+                    // trim has left the four behind (tz == 4) has jl <= end0 - 4 and prunes nothing.  The dropped cells are set
+                    // to zero with 16-bit stores (nothing waits for them), only in lanes and rows that drop a live cell.
+                    if (jl >= beg) {
+                        const uint32_t yl = (uint32_t)y, yh = (uint32_t)(y >> 32);
+                        const uint32_t cr01 = ((uint32_t)(qlen - end0 + 3) & 0xffffu) | (uint32_t)(qlen - end0 + 2) << 16;
+                        const uint32_t ml = pk_max_i16(yl & 0x00ff00ffu, (yl >> 8) & 0x00ff00ffu);
+                        const uint32_t mh = pk_max_i16(yh & 0x00ff00ffu, (yh >> 8) & 0x00ff00ffu);
+                        const uint32_t sl = pk_mul_lo(pk_subsat_u16_v(add_u32_v(ml, pk_mul_lo(pk_min_u16(cr01, r2), m2)), best2),
+                                                      pk_min_u16_1(ml));
+                        const uint32_t sh = pk_mul_lo(pk_subsat_u16_v(add_u32_v(mh, pk_mul_lo(pk_min_u16(cr01 - 0x00020002u, r2), m2)), best2),
+                                                      pk_min_u16_1(mh));
+                        const uint64_t stay = (uint64_t)sh << 32 | sl;
+                        const int tp = stay ? __builtin_clzll(stay) >> 4 : 4;
+                        int jn = end0 - tp;
+                        jn = jn > beg - 1 ? jn : beg - 1;
+                        if (jn < jl) {
+                            for (j = jn + 1; j <= jl; j++) CELL16(j) = 0;
+                            dropped = true;
+                            end = jn + 2 < qlen ? jn + 2 : qlen;
+                        }
                     }
                 }
             }

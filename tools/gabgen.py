@@ -103,18 +103,25 @@ def bsw_from_arrays(refs, qrys, h0s):
     return BswBatch(ref, ref_off, qry, qry_off, len1, len2, np.array(h0s, np.int32))
 
 
-def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, wrong_potential=False):
-    """CPU model of the bsw kernels' score-only early exit and left-edge prune (tools/gen/bsw_exit_model.c) -> per-pair (score, rows
+BSW_PRUNE_RULES = {"default": 1, "wrong_left": 2, "parent": 3, "wrong_right": 4, "left_cap_only": 5, "right_only": 6}
+
+
+def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, wrong_potential=False, rule="default"):
+    """CPU model of the bsw kernels' score-only early exit and edge prunes (tools/gen/bsw_exit_model.c) -> per-pair (score, rows
     swept, DP cells evaluated, cells read by the bound passes); params is a ctypes struct laid out like gab_bsw_params
     (include/gab.h).  early_exit=False: the reference's full sweep.  prune=False: the exit alone.  restarts=True appends a fifth
     array: 1 where the pair abandoned its pruned pass for the z-drop guard and ran again without the prune.  wrong_potential=True
-    is the tests' negative control (the prune's potential counts two columns too few)"""
+    is the tests' negative control (the left prune's potential counts two columns too few).  rule picks among the model's prune
+    rules: "default" is what the kernels do (left prune capped at four cells per row, right prune); "parent" the rule before the
+    right prune (left uncapped, no right prune); "left_cap_only", "right_only" its two halves; "wrong_right" the right side's
+    negative control (its potential counts two columns too few)"""
     n = batch.n
+    sel = BSW_PRUNE_RULES["wrong_left" if wrong_potential else rule] if prune else 0
     score = np.zeros(n, np.int32); rows = np.zeros(n, np.int32); cells = np.zeros(n, np.int64); pass_cells = np.zeros(n, np.int64)
     redo = np.zeros(n, np.int32)
     lib().gab_bsw_exit_model(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
                              _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if early_exit else 0),
-                             C.c_int((2 if wrong_potential else 1) if prune else 0), _p(score), _p(rows), _p(cells), _p(pass_cells),
+                             C.c_int(sel), _p(score), _p(rows), _p(cells), _p(pass_cells),
                              _p(redo))
     return (score, rows, cells, pass_cells, redo) if restarts else (score, rows, cells, pass_cells)
 

@@ -1,5 +1,5 @@
-/* CPU model of the score-only early exit and left-edge prune of the bsw DP kernels (genarchbench_amd/csrc/bsw.hip) -- TEST
- * INFRASTRUCTURE ONLY.  The prune is described at model_one below.
+/* CPU model of the score-only early exit and the left- and right-edge prune of the bsw DP kernels (genarchbench_amd/csrc/bsw.hip) -- TEST
+ * INFRASTRUCTURE ONLY.  The prunes are described at model_one below.
  *
  * The scalar banded Smith-Waterman (BandedPairWiseSW::scalarBandedSWA of the reference), restated with the upper-bound exit
  * exactly as the kernels apply it, so
@@ -38,7 +38,24 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
  * the exit on, and the abandoned pass stays in the cell count.  So does a row of such a pair whose band ends inside the query and
  * short of the clamp (end < qlen, end != i + w + 1) on a cell hleft = H(i, end - 1) with hleft > e_ins and
  * hleft - e_ins + max_sc * min(R, qlen - end - 1) > best: the reference's band may be wider there and carry that F on.
- * prune == 2 is a TEST-ONLY wrong rule (columns left short by two), the negative control of tests/test_bsw_left_prune.py. */
+ * Per row the left edge advances over at most the four cells beg0 .. beg0 + 3 next to the `beg` the row was swept with (the window
+ * the kernels' zero trim has fetched anyway); a row whose zero trim has run past them prunes nothing on the left.
+ *
+ * Right-edge prune (same scope, same pairs): after the left prune, with jl the last live stored cell (where the reference's right
+ * trim stopped; the next end is min(jl + 2, qlen)) and end0 the `end` the row was swept with, while jl >= beg, jl > end0 - 4 and
+ *     m(jl) == 0  or  m(jl) + max_sc * min(R, qlen - jl) <= best
+ * cell jl is SET TO ZERO (Hd = Ev = 0) and jl moves one cell left; end = min(jl + 2, qlen) afterwards.  The zeroing keeps every
+ * cell right of `end` zero, which a later, wider row reads again.  A drop sets `dropped`: the two guards above cover these pairs
+ * unchanged.  Again at most the four cells end0 - 3 .. end0 per row.
+ * The right prune drops cells of pairs that still hold column 0, so a third guard joins the two: a row with rowmax == 0 of a pair
+ * that has dropped a live cell, has beg == 0 and a left edge hb = h0 - o_del - e_del * (i + 1) > 0 (stored cell 0) with
+ * hb + max_sc * min(R, qlen) > best abandons the pass too (the reference's row may hold dead cells that keep it going until that
+ * edge raises the score).
+ *
+ * `prune` selects the rule:  0 off;  1 what the kernels do (left prune capped, right prune);  3 the rule before the right prune
+ * (left prune uncapped, no right prune);  5 left prune capped, no right prune;  6 left prune uncapped, right prune.
+ * TEST-ONLY wrong rules, the negative controls of tests/test_bsw_left_prune.py and tests/test_bsw_right_prune.py:
+ * 2 is rule 1 with the left potential's columns short by two, 4 is rule 1 with the right potential's columns short by two. */
 static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0,
                       int early_exit, int prune, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells,
                       int64_t *pass_cells, int32_t *restarted) {
@@ -57,7 +74,8 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
     if (w > lim) w = lim;
     const int prune_ok = early_exit && prune && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) &&
                          (p->zdrop == 0 || p->zdrop >= 8 * max_sc);
-    const int short_by = prune == 2 ? 2 : 0;
+    const int short_by = prune == 2 ? 2 : 0, short_r = prune == 4 ? 2 : 0;
+    const int left_cap = !(prune == 3 || prune == 6), right_prune = prune != 3 && prune != 5;
 
     int best = h0, i = 0, redo = 0;
     for (int pass = 0; pass < 2; pass++) {
@@ -82,6 +100,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 if (sp > stale_pot) stale_pot = sp;
             }
             if (end > qlen) end = qlen;
+            const int beg0 = beg, end0 = end;
             int hleft = 0;
             if (beg == 0) {
                 hleft = h0 - (p->o_del + e_del * (i + 1));
@@ -105,7 +124,16 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
             }
             ncell += (end > beg) ? end - beg : 0;
             Hd[end] = hleft; Ev[end] = 0;
-            if (rowmax == 0) { i++; break; }
+            if (rowmax == 0) {
+                /* zero-row guard: a pair that has dropped a live cell cannot tell whether the reference's row is zero too; while it
+                 * still holds column 0 and this row's left edge (stored cell 0, the diagonal of cell (i + 1, 0)) can reach `best`,
+                 * the reference may go on from that edge */
+                if (dropped && beg == 0) {
+                    int hb = h0 - p->o_del - e_del * (i + 1);
+                    if (hb > 0 && hb + max_sc * (R < qlen ? R : qlen) > best) abandon = 1;
+                }
+                i++; break;
+            }
             int try_exit = 0;
             if (rowmax > best) {
                 best = rowmax; best_i = i; best_j = rowmax_j;
@@ -131,6 +159,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
             for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
             beg = j;
             for (j = end; j >= beg && Hd[j] == 0 && Ev[j] == 0; j--) {}
+            int jl = j;
             end = j + 2 < qlen ? j + 2 : qlen;
             if (do_prune && beg < end) {
                 int go = 1;
@@ -140,13 +169,23 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 }
                 if (go) {
                     const int from = beg;
-                    for (; beg < end; beg++) {
+                    for (; beg < end && !(left_cap && beg >= beg0 + 4); beg++) {
                         int m = Hd[beg] > Ev[beg] ? Hd[beg] : Ev[beg];
                         int cl = qlen - beg - short_by;
                         if (m && m + max_sc * (R < cl ? R : cl) > best) break;
                     }
                     if (beg > from) dropped = 1;   /* (cell `from` is live) */
                 }
+            }
+            if (do_prune && right_prune && jl >= beg && jl > end0 - 4) {     /* (cell jl is live: the zero trim stopped at it) */
+                const int from = jl;
+                for (; jl >= beg && jl > end0 - 4; jl--) {
+                    int m = Hd[jl] > Ev[jl] ? Hd[jl] : Ev[jl];
+                    int cl = qlen - jl - short_r;
+                    if (m && m + max_sc * (R < cl ? R : cl) > best) break;
+                    Hd[jl] = 0; Ev[jl] = 0;
+                }
+                if (jl < from) { dropped = 1; end = jl + 2 < qlen ? jl + 2 : qlen; }
             }
             if (try_exit) {
                 int bound = stale_pot;
