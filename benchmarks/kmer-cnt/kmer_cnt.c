@@ -1,7 +1,7 @@
 /* kmer-cnt -- drop-in driver of the kmer-cnt benchmark (Flye's solid k-mer counter) on MI355X.
  *
  *     kmer-cnt --reads a.fasta[,b.fastq.gz,...] --config F [--kmer K] [--min-read N] [--min-ovlp N] [--threads T] [--log F] [--debug]
- *              [-g N | --gpus N] [--index-gpus N]
+ *              [-g N | --gpus N] [--index-gpus N] [--solid-index]
  *
  * Options, the "Hash size: N" / "Total k-mers N" debug lines and the "Kernel time: %.3f sec" line on stderr are those of the
  * reference's driver (kmer-cnt/kmer_cnt.cpp:47-125, 155-337; the two counts: kmer-cnt/vertex_index.cpp:858-859).  --threads only
@@ -11,7 +11,7 @@
  * another.
  *
  * Outside the region of interest, as in the reference: the config file (key = value lines, '#' comments, "%include other.cfg"
- * relative to the including file, kmer-cnt/config.h:36-72; five keys are read, see kc_key_names), then every reads file
+ * relative to the including file, kmer-cnt/config.h:36-72; seven keys are read, see kc_key_names), then every reads file
  * in the order given, FASTA (multi-line) or FASTQ by its suffix, plain or gzip (kmer-cnt/sequence_container.cpp:22-46, 159-308).
  * A byte that is not one of ACGTacgt: the reference means to replace it by "ACGT"[rand() % 4] (validateSequence,
  * kmer-cnt/sequence_container.cpp:318-328), but its test compares a size_t table entry of -1 with -1U, which never holds where
@@ -26,6 +26,9 @@
  * --index-gpus N (1..GAB_KMER_MAX_PARTS) asks for the index in N key-space partitions, one per GPU, built in two phases
  * (build_minimizer_index_parts below; include/gab.h: gab_kmer_index_part_begin / _finish).  In counting mode --index-gpus is accepted
  * and ignored.
+ * --solid-index (not an option of the reference; counting mode only): after the count, the solid k-mer index the reference's driver
+ * carries commented out right behind countKmers() (kmer-cnt/kmer_cnt.cpp:228-230, 290-292), with its MIN_FREQ = 2 and
+ * meta_read_top_kmer_rate, meta_read_filter_kmer_freq and repeat_kmer_rate from the config file (build_solid_index below).
  * Inside it: ONE gab_kmer_count_part per GPU over the kept reads, all at once (that GPU's copy of the reads included), where the
  * reference runs vertexIndex.countKmers() (kmer-cnt/kmer_cnt.cpp:282-294).  -g 1 is one gab_kmer_count_part(0 of 1) = gab_kmer_count.
  */
@@ -62,8 +65,10 @@ static void die(const char *fmt, ...) {
 
 /* ---- config ---------------------------------------------------------------------------------------------------------------------- */
 /* the keys this driver reads; values are floats, as the reference's Config keeps them (kmer-cnt/config.h:69, 100) */
-enum { KC_KMER_SIZE, KC_USE_MINIMIZERS, KC_MINIMIZER_WINDOW, KC_REPEAT_KMER_RATE, KC_ASSEMBLE_KMER_SAMPLE, KC_NKEYS };
-static const char *const kc_key_names[KC_NKEYS] = {"kmer_size", "use_minimizers", "minimizer_window", "repeat_kmer_rate", "assemble_kmer_sample"};
+enum { KC_KMER_SIZE, KC_USE_MINIMIZERS, KC_MINIMIZER_WINDOW, KC_REPEAT_KMER_RATE, KC_ASSEMBLE_KMER_SAMPLE, KC_META_TOP_KMER_RATE, KC_META_FILTER_KMER_FREQ,
+       KC_NKEYS };
+static const char *const kc_key_names[KC_NKEYS] = {"kmer_size", "use_minimizers", "minimizer_window", "repeat_kmer_rate", "assemble_kmer_sample",
+                                                   "meta_read_top_kmer_rate", "meta_read_filter_kmer_freq"};
 typedef struct { int have[KC_NKEYS]; float value[KC_NKEYS]; } kc_config;
 static char *trim(char *s) {
     while (*s == ' ' || *s == '\t' || *s == '\r' || *s == '\n') s++;
@@ -221,7 +226,7 @@ static void load_file(const char *name, kc_reads *R, int64_t min_len) {
 
 static void usage(void) {
     fprintf(stderr, "Usage: kmer-cnt  --reads path --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
-                    "\t\t[--threads num] [--log path] [--debug] [-g num | --gpus num] [--index-gpus num] [-h]\n\n"
+                    "\t\t[--threads num] [--log path] [--debug] [-g num | --gpus num] [--index-gpus num] [--solid-index] [-h]\n\n"
                     "Required arguments:\n"
                     "  --reads path\tcomma-separated list of read files (FASTA / FASTQ, plain or gzip)\n"
                     "  --config path\tpath to the config file\n\n"
@@ -234,7 +239,9 @@ static void usage(void) {
                     "  --threads num_threads\taccepted and ignored (the count runs on the GPUs)\n"
                     "  -g, --gpus num\tGPUs to count on, each one partition of the k-mers [default = $GAB_GPUS, else 1]\n"
                     "  --index-gpus num\tuse_minimizers = 1: GPUs to build the index on, each one partition of the k-mers, 1..%d\n"
-                    "\t\t\t[default = not set: the index is built on the first GPU, not partitioned]\n", GAB_KMER_MAX_K, GAB_KMER_MAX_PARTS);
+                    "\t\t\t[default = not set: the index is built on the first GPU, not partitioned]\n"
+                    "  --solid-index\tafter the count, build the solid k-mer index (meta_read_top_kmer_rate,\n"
+                    "\t\t\tmeta_read_filter_kmer_freq and repeat_kmer_rate of the config file) [default = false]\n", GAB_KMER_MAX_K, GAB_KMER_MAX_PARTS);
 }
 
 /* one partition per logical GPU, run by gab_run_parts */
@@ -375,13 +382,39 @@ static int build_minimizer_index_parts(const kc_reads *R, int kmer, int window, 
     return 0;
 }
 
+/* --solid-index: ONE gab_kmer_index_solid over the kept reads, on a handle of its own on the first GPU, where the reference's driver
+ * has vertexIndex.buildIndexUnevenCoverage(MIN_FREQ, SELECT_RATE, TANDEM_FREQ) commented out (kmer-cnt/kmer_cnt.cpp:290-292), and
+ * that function's debug lines in its order (kmer-cnt/vertex_index.cpp:209-216, 113, 126-129), the floats with its float expressions.
+ * The call counts for itself: the rank of a read needs every count, so it does not use the partitions of the count before it. */
+static void build_solid_index(gab_kmer *h, const kc_reads *R, int kmer, int32_t min_len, float select_rate, int tandem_freq, float rate) {
+    const int MIN_FREQ = 2;                                                              /* kmer-cnt/kmer_cnt.cpp:228 */
+    gab_kmer_solid_result x;
+    memset(&x, 0, sizeof x);
+    GAB_DIE_IF(gab_kmer_index_solid(h, R->seq, R->off, R->len, R->n, kmer, min_len, MIN_FREQ, select_rate, tandem_freq, rate, &x), "gab_kmer_index_solid");
+    log_debug("Mean k-mer frequency: %g", (double)((float)(size_t)x.mean_total / ((size_t)x.mean_unique + 1)));
+    log_debug("Repetitive k-mer frequency: %lld", (long long)x.repetitive_frequency);
+    log_debug("Filtered %lld repetitive k-mers (%g)", (long long)x.filtered_entries, (double)((float)(size_t)x.filtered_entries / (size_t)x.mean_total));
+    log_debug("Sorting k-mer index");
+    log_debug("Selected k-mers: %lld", (long long)x.selected_kmers);
+    log_debug("Index size: %lld", (long long)x.index_entries);
+    log_debug("Mean k-mer index frequency: %g", (double)((float)(size_t)x.index_entries / (size_t)x.selected_kmers));
+    float ms[5] = {0, 0, 0, 0, 0};
+    int64_t tested = 0, fallback = 0;
+    (void)gab_kmer_solid_last_phases(h, &ms[0], &ms[1], &ms[2], &ms[3], &ms[4]);
+    (void)gab_kmer_solid_last_stats(h, &tested, &fallback);
+    log_debug("Solid index: %lld of %lld positions selected, %lld candidate k-mers, %lld removed, %lld lists not empty; %lld positions took the tandem test "
+              "(%lld reads in hash classes); device: count %.3f ms, select %.3f ms, capacity %.3f ms, fill %.3f ms, sort %.3f ms",
+              (long long)x.selected_positions, (long long)x.positions, (long long)x.candidates, (long long)x.filtered_kmers, (long long)x.indexed_kmers,
+              (long long)tested, (long long)fallback, ms[0], ms[1], ms[2], ms[3], ms[4]);
+}
+
 int main(int argc, char **argv) {
-    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, index_gpus = 0, c, idx = 0;
+    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1, gpus_flag = 0, index_gpus = 0, solid_index = 0, c, idx = 0;
     const char *reads = NULL, *config = NULL, *logfile = NULL;
     static struct option lo[] = {{"reads", required_argument, 0, 0}, {"config", required_argument, 0, 0}, {"min-read", required_argument, 0, 0},
                                  {"log", required_argument, 0, 0}, {"threads", required_argument, 0, 0}, {"kmer", required_argument, 0, 0},
                                  {"min-ovlp", required_argument, 0, 0}, {"debug", no_argument, 0, 0}, {"gpus", required_argument, 0, 'g'},
-                                 {"index-gpus", required_argument, 0, 0}, {0, 0, 0, 0}};
+                                 {"index-gpus", required_argument, 0, 0}, {"solid-index", no_argument, 0, 0}, {0, 0, 0, 0}};
     while ((c = getopt_long(argc, argv, "hg:", lo, &idx)) != -1) {
         if (c == 'h') { usage(); return 0; }
         if (c == 'g') { gpus_flag = atoi(optarg); if (gpus_flag < 1) { usage(); return 1; } continue; }
@@ -395,6 +428,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(name, "debug")) g_debug = 1;
         else if (!strcmp(name, "reads")) reads = optarg;
         else if (!strcmp(name, "config")) config = optarg;
+        else if (!strcmp(name, "solid-index")) solid_index = 1;
         else if (!strcmp(name, "index-gpus")) { index_gpus = atoi(optarg); if (index_gpus < 1 || index_gpus > GAB_KMER_MAX_PARTS) { usage(); return 1; } }
     }
     (void)threads;
@@ -418,6 +452,13 @@ int main(int argc, char **argv) {
             if (!cfg.have[i]) die("No such parameter: %s (use_minimizers = 1 needs it; set it in %s)", kc_key_names[i], config);
         window = (int)cfg.value[KC_MINIMIZER_WINDOW];                                  /* const int minWnd = Config::get(...) */
         if (window < 1 || window > GAB_KMER_MAX_WINDOW) die("wrong minimizer length (minimizer_window = %d; supported 1..%d)", window, GAB_KMER_MAX_WINDOW);
+    }
+    if (solid_index && !use_minimizers) {                                              /* (the reference's Config::get throws for a missing key) */
+        const int need[3] = {KC_META_TOP_KMER_RATE, KC_META_FILTER_KMER_FREQ, KC_REPEAT_KMER_RATE};
+        for (int i = 0; i < 3; i++)
+            if (!cfg.have[need[i]]) die("No such parameter: %s (--solid-index needs it; set it in %s)", kc_key_names[need[i]], config);
+        const float top = cfg.value[KC_META_TOP_KMER_RATE];
+        if (!(top >= 0.0f && top < 1.0f)) die("meta_read_top_kmer_rate = %g: --solid-index takes 0 <= rate < 1", (double)top);
     }
     if (kmer < 1 || kmer > GAB_KMER_MAX_K) die("Can't use flat counter for k-mer size > %d (k = %d; supported 1..%d)", GAB_KMER_MAX_K, kmer, GAB_KMER_MAX_K);
     log_debug("Running with k-mer size: %d", kmer);
@@ -446,6 +487,7 @@ int main(int argc, char **argv) {
             rc = build_minimizer_index_parts(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], min_len32, n);
         } else rc = build_minimizer_index(&R, kmer, window, cfg.value[KC_REPEAT_KMER_RATE], min_len32, ngpus);
         free(R.seq); free(R.off); free(R.len);
+        if (solid_index) log_debug("--solid-index is ignored: use_minimizers is set, the index built is the minimizer index");
         if (g_log) fclose(g_log);
         return rc;
     }
@@ -460,6 +502,8 @@ int main(int argc, char **argv) {
         GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(g), &hs[g]), "gab_kmer_create");
         GAB_DIE_IF(gab_kmer_reserve_part(hs[g], R.n, (int64_t)R.bytes, ngpus), "gab_kmer_reserve_part");
     }
+    gab_kmer *solid = NULL;
+    if (solid_index) GAB_DIE_IF(gab_kmer_create(gab_phys_gpu(0), &solid), "gab_kmer_create");
     if (R.bytes) gab_pin(R.seq, R.bytes);
     kc_parts P = {hs, part_res, part_rc, part_err, &R, kmer, ngpus, (int32_t)(min_len > INT32_MAX ? INT32_MAX : min_len)};
     gab_kmer_result res;
@@ -478,6 +522,8 @@ int main(int argc, char **argv) {
     }
     log_debug("Hash size: %lld", (long long)res.hash_size);
     log_debug("Total k-mers %lld", (long long)res.total_kmers);
+    if (solid)
+        build_solid_index(solid, &R, kmer, P.min_len, cfg.value[KC_META_TOP_KMER_RATE], (int)cfg.value[KC_META_FILTER_KMER_FREQ], cfg.value[KC_REPEAT_KMER_RATE]);
     gab_roi_end();
     const double t1 = gab_now();
 
@@ -498,6 +544,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Kernel time: %.3f sec\n", t1 - t0);
     if (R.bytes) gab_unpin(R.seq);
     for (int g = 0; g < ngpus; g++) gab_kmer_destroy(hs[g]);
+    gab_kmer_destroy(solid);
     free(hs); free(part_res); free(part_rc); free(part_err);
     free(R.seq); free(R.off); free(R.len);
     if (g_log) fclose(g_log);

@@ -58,6 +58,9 @@ struct KmerCounters {
     uint32_t overflow;                     // a bounded insert gave up: the partition's table is full (the host repeats the call)
     unsigned long long ix_kmers, ix_entries;       // minimizer index: kept k-mers and their entries
     unsigned long long ix_minimizers;      // ... and the emitted minimizers of the call (the low word is copied in from the scan)
+    unsigned long long sx_total, sx_unique;        // solid index: capacities >= min_freq, their sum and their number (the filter's totals)
+    unsigned long long sx_empty, sx_empty_cap;     // ... kept keys whose list stays empty (c(x) > thr), and the sum of their capacities
+    unsigned long long sx_need, sx_fallback;       // ... positions that took the multiplicity test; reads that left the LDS table for the partitioned passes
 };
 GAB_STATIC_ATOMIC64(KmerCounters, bad_read);
 GAB_STATIC_ATOMIC64(KmerCounters, bad_query);
@@ -672,6 +675,246 @@ __global__ __launch_bounds__(kBlock) void kmer_index_lookup(KmerLine *table, uin
     count[i] = (int32_t)c;
 }
 
+// =========================================================================================================================== solid index
+// buildIndexUnevenCoverage(globalMinFreq, selectRate, tandemFreq) (kmer-cnt/vertex_index.cpp:30-130) with its selector
+// yieldFrequentKmers (kmer-cnt/vertex_index.cpp:321-363), on the same packed reads, tiles, bitmap and table.  What is new is the
+// producer of the bitmap: per read, the positions whose canonical k-mer has a global count of at least the read's cut -- the count
+// of rank (size_t)(selectRate * n) among the read's n counts in descending order -- and of at least min_freq, minus the positions
+// whose k-mer occurs more than tandem_freq times in the read itself.
+//   kmer_solid_freq     one wave per tile, one lane per run, as kmer_count: freq[first position of the read + p] = c(k-mer at p); a
+//                       lane probes the count table once per stretch of equal keys of its run
+//   kmer_solid_select   one block per read.  The cut is an exact order statistic: four passes over the read's counts, most
+//                       significant byte first, each a 256-bin histogram in LDS of the counts that share the bytes found so far,
+//                       so the digit boundaries lie at 2^8, 2^16 and 2^24.  Then one ballot per run writes the bitmap word of the
+//                       positions that pass on their count alone.  A position with c(x) <= tandem_freq cannot occur more often
+//                       than that in its read, so only the others ("need") take the multiplicity test: their keys are counted in an LDS table of
+//                       kSolidSlots entries and looked up again.  When the read has more such distinct keys than kSolidFill the
+//                       block splits them by hash into P = 2, 4, ... classes and runs one count-and-mark pass per class, doubling P until
+//                       every class fits: exact at any size, at P times the rolling (ct->sx_fallback counts those reads).
+constexpr int kSolidSlots = 2048;
+constexpr int kSolidFill = kSolidSlots * 3 / 4;        // claims allowed: kSolidFill + kBlock racing lanes still leave empty slots
+constexpr uint32_t kSolidMaxClasses = 1u << 20;
+struct KmerSolidRule { float select_rate; uint32_t min_freq, tandem; int32_t min_len; };      // tandem = 0: no multiplicity test
+
+__global__ __launch_bounds__(kBlock) void kmer_solid_freq(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
+                                                          const KmerTile *__restrict__ tiles, int64_t n_tiles, int k, const KmerLine *__restrict__ table,
+                                                          uint64_t nlines, uint32_t *__restrict__ freq) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (t >= n_tiles) return;
+    const KmerTile tile = tiles[t];
+    const int32_t npos = len[tile.read] - k;
+    const int32_t p0 = tile.start + lane * kRun;
+    const int32_t p1 = min(p0 + kRun, npos);
+    if (p0 >= p1) return;
+    uint32_t *out = freq + (t - tile.start / kTile) * kTile;       // the read's first position (its tiles are consecutive)
+    KmerRoller R(packed + woff[tile.read], k);
+    R.seek(p0);
+    uint64_t cur = ~0ull;
+    uint32_t c = 0;
+    for (int32_t p = p0; p < p1; p++) {
+        R.step();
+        const uint64_t key = R.canonical();
+        if (key != cur) {
+            cur = key;
+            int slot = 0;
+            const KmerLine *L = kmer_find(table, nlines, kmer_line_of(key, nlines), key, &slot);
+            c = L ? L->cnt[slot] : 0;
+        }
+        out[p] = c;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void kmer_solid_select(const uint32_t *__restrict__ packed, const int64_t *__restrict__ woff, const int32_t *__restrict__ len,
+                                                            const int64_t *__restrict__ first_run, int k, KmerSolidRule rule, const uint32_t *__restrict__ freq,
+                                                            unsigned long long *masks, KmerCounters *ct) {
+    __shared__ uint32_t hist[256];
+    __shared__ unsigned long long tkey[kSolidSlots];
+    __shared__ uint32_t tcnt[kSolidSlots];
+    __shared__ uint32_t sh_prefix, sh_rank, sh_used, sh_over, sh_need;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r = blockIdx.x;
+    const int32_t L = len[r], n = L - k;
+    if (L <= rule.min_len || n <= 0) return;
+    const uint32_t *f = freq + first_run[r] * kRun;
+    unsigned long long *rmask = masks + first_run[r];
+    if (tid == 0) sh_need = 0;
+
+    // ---- the cut: rank maxKmers of the counts in descending order = rank n - 1 - maxKmers in ascending order
+    uint32_t maxk = (uint32_t)__fmul_rn(rule.select_rate, (float)n);      // (size_t)(selectRate * topKmers.size()): one float product, truncated
+    if (maxk >= (uint32_t)n) maxk = (uint32_t)n - 1;                      // (there the reference reads past its array)
+    uint32_t prefix = 0, rank = (uint32_t)n - 1 - maxk;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = tid; j < 256; j += kBlock) hist[j] = 0;
+        __syncthreads();
+        const uint32_t above = shift == 24 ? 0u : ~0u << (shift + 8);
+        for (int32_t base = 0; base < n; base += kBlock) {                 // (whole waves take every round: ballots)
+            const int32_t p = base + tid;
+            const uint32_t v = p < n ? f[p] : 0u;
+            const bool in = p < n && (v & above) == prefix;
+            const uint32_t d = (v >> shift) & 255u;
+            const unsigned long long act = __ballot(in);
+            if (act) {                                                     // the lanes of a wave mostly share a digit: one add for them
+                const int lead = __builtin_ctzll(act);
+                const uint32_t d0 = __shfl(d, lead);
+                const unsigned long long same = __ballot(in && d == d0);
+                if (lane == lead) atomicAdd(&hist[d0], (uint32_t)__popcll(same));
+                if (in && d != d0) atomicAdd(&hist[d], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t cum = 0;
+            int b = 0;
+            for (; b < 255 && cum + hist[b] <= rank; b++) cum += hist[b];
+            sh_prefix = prefix | ((uint32_t)b << shift); sh_rank = rank - cum;
+        }
+        __syncthreads();
+        prefix = sh_prefix; rank = sh_rank;
+    }
+    const uint32_t cut = max(prefix, rule.min_freq);
+
+    // ---- the positions that pass on their count alone; the others of the read's top counts need the multiplicity test
+    const int32_t nruns = (n + kRun - 1) / kRun;
+    uint32_t need = 0;
+    for (int32_t run = wave; run < nruns; run += kBlock / 64) {
+        const int32_t p = run * kRun + lane;
+        const uint32_t v = p < n ? f[p] : 0u;
+        const bool top = p < n && v >= cut;
+        const bool test = top && rule.tandem && v > rule.tandem;
+        const unsigned long long m = __ballot(top && !test);
+        need += (uint32_t)__popcll(__ballot(test));
+        if (lane == 0) rmask[run] = m;
+    }
+    if (lane == 0 && need) atomicAdd(&sh_need, need);
+    __syncthreads();
+    if (!sh_need) return;
+    if (tid == 0) atomicAdd(&ct->sx_need, (unsigned long long)sh_need);
+
+    // ---- the multiplicity test.  Runs go to the waves in chunks of 64: one ballot per run, lane i keeps the word of the chunk's run i
+    // and rolls that run.  Every occurrence of a key in the read has the key's global count, so either all of them are here or none.
+    const int32_t nchunks = (nruns + 63) / 64;
+    auto chunk_word = [&](int32_t chunk) {
+        unsigned long long mine = 0;
+        for (int i = 0; i < 64 && chunk * 64 + i < nruns; i++) {
+            const int32_t p = (chunk * 64 + i) * kRun + lane;
+            const uint32_t v = p < n ? f[p] : 0u;
+            const unsigned long long b = __ballot(p < n && v >= cut && v > rule.tandem);
+            if (lane == i) mine = b;
+        }
+        return mine;
+    };
+    const uint32_t *words = packed + woff[r];
+    uint32_t classes = 1, cls = 0;
+    while (cls < classes) {
+        for (int j = tid; j < kSolidSlots; j += kBlock) { tkey[j] = 0; tcnt[j] = 0; }
+        if (tid == 0) { sh_used = 0; sh_over = 0; }
+        __syncthreads();
+        for (int32_t chunk = wave; chunk < nchunks; chunk += kBlock / 64) {
+            unsigned long long m = chunk_word(chunk);
+            const int lead = m ? __builtin_ctzll(m) : 0;
+            m >>= lead;
+            KmerRoller R(words, k);
+            if (m) R.seek((chunk * 64 + lane) * kRun + lead);
+            for (; m; m >>= 1) {
+                R.step();
+                if (!(m & 1)) continue;
+                const uint64_t key = R.canonical(), h = kmer_hash(key);
+                if (((uint32_t)(h >> 40) & (classes - 1)) != cls) continue;
+                if (*(volatile uint32_t *)&sh_over) break;
+                const unsigned long long stored = key + 1;
+                for (uint32_t s = (uint32_t)h & (kSolidSlots - 1);; s = (s + 1) & (kSolidSlots - 1)) {
+                    const unsigned long long seen = atomicCAS(&tkey[s], 0ull, stored);
+                    if (seen == 0 && atomicAdd(&sh_used, 1u) >= (uint32_t)kSolidFill) sh_over = 1;
+                    if (seen == 0 || seen == stored) { atomicAdd(&tcnt[s], 1u); break; }
+                }
+            }
+        }
+        __syncthreads();
+        if (sh_over) {                                 // more distinct keys than the table takes: twice the classes, from the first one
+            __syncthreads();                           // (everyone has read sh_over before it is cleared)
+            classes *= 2; cls = 0;
+            if (classes > kSolidMaxClasses) { if (tid == 0) atomicOr(&ct->overflow, 1u); return; }
+            continue;
+        }
+        for (int32_t chunk = wave; chunk < nchunks; chunk += kBlock / 64) {
+            unsigned long long m = chunk_word(chunk), keep = 0;
+            const int lead = m ? __builtin_ctzll(m) : 0;
+            m >>= lead;
+            KmerRoller R(words, k);
+            if (m) R.seek((chunk * 64 + lane) * kRun + lead);
+            for (int bit = lead; m; m >>= 1, bit++) {
+                R.step();
+                if (!(m & 1)) continue;
+                const uint64_t key = R.canonical(), h = kmer_hash(key);
+                if (((uint32_t)(h >> 40) & (classes - 1)) != cls) continue;
+                uint32_t s = (uint32_t)h & (kSolidSlots - 1);
+                while (tkey[s] != key + 1) s = (s + 1) & (kSolidSlots - 1);       // (the pass above put it there)
+                if (tcnt[s] <= rule.tandem) keep |= 1ull << bit;
+            }
+            if (keep) rmask[chunk * 64 + lane] |= keep;          // (this lane owns the run's word in every pass)
+        }
+        __syncthreads();
+        cls++;
+    }
+    if (tid == 0 && classes > 1) atomicAdd(&ct->sx_fallback, 1ull);
+}
+
+// the filter's totals over the capacity table (filterFrequentKmers, kmer-cnt/vertex_index.cpp:180-189): every key counts as a
+// candidate, only capacities >= min_freq enter the mean
+__global__ __launch_bounds__(kBlock) void kmer_solid_reduce(const KmerLine *__restrict__ table, uint64_t nslots, uint32_t min_freq, KmerCounters *ct) {
+    unsigned long long distinct = 0, total = 0, unique = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * kBlock) {
+        const KmerLine *L = table + i / kSlots;
+        const int s = (int)(i % kSlots);
+        if (L->key[s]) {
+            const unsigned long long c = L->cnt[s];
+            distinct++;
+            if (c >= min_freq) { total += c; unique++; }
+        }
+    }
+    for (int d = 32; d; d >>= 1) { distinct += __shfl_xor(distinct, d); total += __shfl_xor(total, d); unique += __shfl_xor(unique, d); }
+    if ((threadIdx.x & 63) == 0 && distinct) {
+        atomicAdd(&ct->distinct, distinct);
+        if (unique) { atomicAdd(&ct->sx_total, total); atomicAdd(&ct->sx_unique, unique); }
+    }
+}
+
+// kmer_index_weigh for the solid index: a key that stays (capacity <= thr) gets its capacity in slots only if its global count is
+// <= thr too -- the second pass of the reference skips by global count (kmer-cnt/vertex_index.cpp:78-79) -- and an empty list
+// otherwise.  counts: the table of the call's count, still alive.  n is rounded up to whole waves by the launch.
+__global__ __launch_bounds__(kBlock) void kmer_solid_weigh(const KmerLine *__restrict__ table, const uint64_t *__restrict__ keys, const uint64_t *__restrict__ slots,
+                                                           int64_t n, uint32_t thr, const KmerLine *__restrict__ counts, uint64_t count_lines,
+                                                           uint64_t *__restrict__ weight, KmerCounters *ct) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint64_t v = 0;
+    unsigned long long empty = 0, empty_cap = 0;
+    if (i < n) {
+        const uint32_t c = table[slots[i] / kSlots].cnt[slots[i] % kSlots];
+        if (c <= thr) {
+            int slot = 0;
+            const KmerLine *L = kmer_find(counts, count_lines, kmer_line_of(keys[i], count_lines), keys[i], &slot);
+            const bool full = L && L->cnt[slot] <= thr;
+            v = full ? (1ull << 32) | c : 0;
+            empty = full ? 0 : 1;
+            empty_cap = full ? 0 : c;
+        }
+    }
+    if (i <= n) weight[i] = v;
+    for (int d = 32; d; d >>= 1) { empty += __shfl_xor(empty, d); empty_cap += __shfl_xor(empty_cap, d); }
+    if ((threadIdx.x & 63) == 0 && empty) { atomicAdd(&ct->sx_empty, empty); atomicAdd(&ct->sx_empty_cap, empty_cap); }
+}
+
+// after kmer_index_assign: the keys with an empty list leave the table -- a look-up then reads them as absent and the fill pass
+// passes them by.  Their slots stay taken (by a value no key + 1 equals), so the taken slots of a line are still a prefix.
+__global__ __launch_bounds__(kBlock) void kmer_solid_retire(KmerLine *table, const uint64_t *__restrict__ slots, const uint64_t *__restrict__ weight, int64_t n,
+                                                            uint32_t thr) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || weight[i]) return;
+    KmerLine *L = table + slots[i] / kSlots;
+    if (L->cnt[slots[i] % kSlots] <= thr) L->key[slots[i] % kSlots] = ~0ull;
+}
+
 struct KmerDev {           // where the stage put things (kmer_stage: the first line; kmer_mini_stage: all of it)
     int64_t *woff; KmerTile *tiles; uint32_t *packed; int64_t n_tiles, n_runs;
     unsigned long long *masks; uint32_t *offs; int64_t *rbase, *first_run;
@@ -689,7 +932,7 @@ struct gab_kmer {
     gab_devbuf table;
     gab_devbuf ct;          // KmerCounters
     gab_devbuf aux;         // spectrum bins, query staging, dump keys / counts and the sort's scratch
-    hipEvent_t ev[11] = {};            // count: start | packed | counted | reduced | end; then the six of the index (ev_ix)
+    hipEvent_t ev[17] = {};            // count: start | packed | counted | reduced | end; then the six of the index (ev_ix) and of the solid front (ev_sx)
     KmerCounters *h_ct = nullptr;      // pinned
     bool counted = false;              // the table of a finished count is in the handle
     int k = 0;
@@ -709,6 +952,15 @@ struct gab_kmer {
     gab_kmer_index_result ix = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t ix_thr = 0;               // min(repetitive_frequency, 2^32 - 1): what the kernels compare the 32-bit capacities with
     float ix_ms[4] = {0, 0, 0, 0};     // sketch | count | fill | sort
+    // solid index (gab_kmer_index_solid): the count table and the capacity table are alive together; the build ends with the capacity
+    // table in `table` (it is the index's) and the counts dropped, so afterwards `indexed` is set as after a minimizer build
+    gab_devbuf cap;         // the second table: the capacities during a solid build, the counts of gab_kmer_solid_positions
+    gab_devbuf freq;        // c(x) of every position, read by read
+    hipEvent_t *const ev_sx = ev + 11; // start | counted | selected | capacities (the later stages: ev_ix[3..5])
+    bool solid = false;                // the index in the handle came from gab_kmer_index_solid
+    gab_kmer_solid_result sx = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float sx_ms[3] = {0, 0, 0};        // count | look-up + selection | capacity
+    int64_t sx_need = 0, sx_fallback = 0;
     // between gab_kmer_index_part_begin and _finish: packed, plan, mini and table (and io for the host form) hold what the stage and
     // the capacity walk left there, and these say where; neither `counted` nor `indexed` is set meanwhile
     struct Pending {
@@ -770,7 +1022,7 @@ extern "C" int gab_kmer_create(int device, gab_kmer **out) {
 extern "C" void gab_kmer_destroy(gab_kmer *h) {
     if (!h) return;
     gab_device_guard g(h->device);
-    h->io.release(); h->packed.release(); h->plan.release(); h->table.release(); h->ct.release(); h->aux.release(); h->mini.release(); h->idx.release();
+    h->io.release(); h->packed.release(); h->plan.release(); h->table.release(); h->ct.release(); h->aux.release(); h->mini.release(); h->idx.release(); h->cap.release(); h->freq.release();
     h->hs.release();
     for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
     if (h->h_ct) (void)hipHostFree(h->h_ct);
@@ -1190,8 +1442,10 @@ int kmer_mini_check(const char *fn, gab_kmer *h, const void *off, const void *le
     return GAB_OK;
 }
 
-// kmer_stage, then sketch and scan (rbase and first_run go up first: a copy behind the pack kernel would hold the sketch back)
-int kmer_mini_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, int k, int window, KmerDev *D) {
+// The bitmap of chosen positions of a call, one 64-bit word per run: kmer_stage plus the zeroed bitmap, the room of its scan and the
+// per-read bases (rbase and first_run go up first: a copy behind the pack kernel would hold the marking kernel back) ...
+struct KmerBitmapScan { void *tmp; size_t tmp_bytes; };
+int kmer_bitmap_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, KmerDev *D, KmerBitmapScan *B) {
     int rc;
     hipStream_t s = in.stream;
     const int64_t n_reads = in.n_reads, n_tiles = (int64_t)P.tiles.size(), n_runs = n_tiles * 64;
@@ -1210,12 +1464,25 @@ int kmer_mini_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, int k, 
     GAB_HIP(hipMemcpyAsync(D->first_run, P.first_run.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, s));
     if ((rc = kmer_stage(h, in, P, D))) return rc;
     GAB_HIP(hipMemsetAsync(D->masks, 0, ((size_t)n_runs + 1) * 8, s));
-    if (n_tiles)
-        hipLaunchKernelGGL(kmer_sketch, dim3((unsigned)gab_ceil_div(n_tiles, kBlock / 64)), dim3(kBlock), 0, s, D->packed, D->woff, in.d_len, D->tiles, n_tiles, k,
-                           window, D->masks);
-    GAB_HIP(rocprim::exclusive_scan(mb + tmp_at, tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)D->masks, KmerPopc()), D->offs, 0u,
-                                    (size_t)n_runs + 1, rocprim::plus<uint32_t>(), s));
+    B->tmp = mb + tmp_at; B->tmp_bytes = tmp_bytes;
     return GAB_OK;
+}
+// ... and, once a kernel has marked the positions, offs = the exclusive scan of the words' popcounts
+int kmer_bitmap_scan(const KmerDev &D, KmerBitmapScan B, hipStream_t s) {
+    GAB_HIP(rocprim::exclusive_scan(B.tmp, B.tmp_bytes, rocprim::make_transform_iterator((const unsigned long long *)D.masks, KmerPopc()), D.offs, 0u,
+                                    (size_t)D.n_runs + 1, rocprim::plus<uint32_t>(), s));
+    return GAB_OK;
+}
+
+// kmer_bitmap_stage, sketch, scan
+int kmer_mini_stage(gab_kmer *h, const KmerInput &in, const KmerPlan &P, int k, int window, KmerDev *D) {
+    int rc;
+    KmerBitmapScan B;
+    if ((rc = kmer_bitmap_stage(h, in, P, D, &B))) return rc;
+    if (D->n_tiles)
+        hipLaunchKernelGGL(kmer_sketch, dim3((unsigned)gab_ceil_div(D->n_tiles, kBlock / 64)), dim3(kBlock), 0, in.stream, D->packed, D->woff, in.d_len, D->tiles,
+                           D->n_tiles, k, window, D->masks);
+    return kmer_bitmap_scan(*D, B, in.stream);
 }
 
 // the counters and the number of minimizers (the scan's last element) to the host; synchronises
@@ -1243,22 +1510,18 @@ void kmer_mini_launch_walk(gab_kmer *h, const KmerDev &D, const int32_t *d_len, 
                            pos, h->table.as<KmerLine>(), h->nlines, h->ct.as<KmerCounters>(), D.rbase, thr, gpos, (uint32_t)h->part, (uint32_t)h->nparts, limit);
 }
 
-// out_on_device: read_start / pos are device pointers
-int kmer_sketch_impl(gab_kmer *h, const KmerInput &in, int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity,
+// The marked positions of every read, out of the scanned bitmap: synchronises for their number, then writes read_start and pos
+// (out_on_device: they are device pointers) or returns GAB_ERANGE with nothing written.
+int kmer_bitmap_emit(gab_kmer *h, const char *fn, const KmerInput &in, const KmerDev &D, int k, int64_t *read_start, int32_t *pos, int64_t capacity,
                      int64_t *nout, bool out_on_device) {
     hipStream_t s = in.stream;
     const int64_t n_reads = in.n_reads;
-    KmerPlan P;
-    KmerDev D;
     int rc;
-    h->pend.on = false;                    // (the stage below overwrites what a pending partitioned index build keeps)
-    if ((rc = kmer_plan("gab_kmer_sketch", in, k, min_len_exclusive, true, &P))) return rc;
-    if ((rc = kmer_mini_stage(h, in, P, k, window, &D))) return rc;
-    if ((rc = kmer_mini_fetch(h, "gab_kmer_sketch", D, s))) return rc;
+    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
     const int64_t m = (int64_t)h->h_ct->ix_minimizers;
     *nout = m;
-    if (capacity < m) { gab_set_error("gab_kmer_sketch: %lld minimizers, room for %lld", (long long)m, (long long)capacity); return GAB_ERANGE; }
-    GAB_CHECK(read_start && (pos || m == 0), "gab_kmer_sketch: NULL output");
+    if (capacity < m) { gab_set_error("%s: %lld positions, room for %lld", fn, (long long)m, (long long)capacity); return GAB_ERANGE; }
+    GAB_CHECK(read_start && (pos || m == 0), "%s: NULL output", fn);
     int64_t *d_start = read_start;
     int32_t *d_pos = pos;
     const size_t pos_at = align256(((size_t)n_reads + 1) * 8);
@@ -1276,6 +1539,18 @@ int kmer_sketch_impl(gab_kmer *h, const KmerInput &in, int k, int window, int32_
     GAB_HIP(hipStreamSynchronize(s));
     GAB_HIP(hipGetLastError());
     return GAB_OK;
+}
+
+// out_on_device: read_start / pos are device pointers
+int kmer_sketch_impl(gab_kmer *h, const KmerInput &in, int k, int window, int32_t min_len_exclusive, int64_t *read_start, int32_t *pos, int64_t capacity,
+                     int64_t *nout, bool out_on_device) {
+    KmerPlan P;
+    KmerDev D;
+    int rc;
+    h->pend.on = false;                    // (the stage below overwrites what a pending partitioned index build keeps)
+    if ((rc = kmer_plan("gab_kmer_sketch", in, k, min_len_exclusive, true, &P))) return rc;
+    if ((rc = kmer_mini_stage(h, in, P, k, window, &D))) return rc;
+    return kmer_bitmap_emit(h, "gab_kmer_sketch", in, D, k, read_start, pos, capacity, nout, out_on_device);
 }
 
 // filterFrequentKmers (kmer-cnt/vertex_index.cpp:190-191) with its float operations: (size_t)(rate * mean), saturated where the float
@@ -1299,8 +1574,11 @@ gab_kmer_index_result kmer_index_threshold(int64_t kept, int64_t total_len, int6
 // the table, lays out their lists (m entries before the filter), fills and sorts them.  The table holds the keys of h->part of
 // h->nparts, n = R.distinct and m = R.minimizers are that partition's own, thr comes from the totals of the whole input
 // (kmer_index_threshold).  Fills the last four fields of R; the handle then holds the index.
+// counts (the solid index): the count table of the call, count_lines lines.  A key that stays but whose global count is above thr
+// keeps an empty list and leaves the table (kmer_solid_weigh, kmer_solid_retire); selected_kmers and index_entries are then those of
+// the lists that are not empty, filtered_* include the empty ones, and the caller takes them apart again with ct->sx_empty*.
 int kmer_index_layout(gab_kmer *h, const KmerDev &D, const int32_t *d_len, int k, gab_kmer_index_result R, uint32_t thr, gab_kmer_index_result *res,
-                      hipStream_t s) {
+                      hipStream_t s, const KmerLine *counts = nullptr, uint64_t count_lines = 0) {
     const int64_t n = R.distinct, m = R.minimizers;
     KmerLine *table = h->table.as<KmerLine>();
     KmerCounters *d_ct = h->ct.as<KmerCounters>();
@@ -1330,9 +1608,11 @@ int kmer_index_layout(gab_kmer *h, const KmerDev &D, const int32_t *d_len, int k
         const dim3 per_key((unsigned)gab_ceil_div(n + 1, kBlock));
         hipLaunchKernelGGL(kmer_index_compact, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines, k_in, s_in, (uint32_t)n, d_ct);
         GAB_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, k_in, k_out, s_in, s_out, (size_t)n, 0u, (unsigned)(2 * k), s));
-        hipLaunchKernelGGL(kmer_index_weigh, per_key, dim3(kBlock), 0, s, table, s_out, n, thr, weight);
+        if (counts) hipLaunchKernelGGL(kmer_solid_weigh, per_key, dim3(kBlock), 0, s, table, k_out, s_out, n, thr, counts, count_lines, weight, d_ct);
+        else hipLaunchKernelGGL(kmer_index_weigh, per_key, dim3(kBlock), 0, s, table, s_out, n, thr, weight);
         GAB_HIP(rocprim::exclusive_scan(tmp, scan_bytes, weight, scan, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
         hipLaunchKernelGGL(kmer_index_assign, per_key, dim3(kBlock), 0, s, table, k_out, s_out, weight, scan, n, kmers, start, seg, d_ct);
+        if (counts) hipLaunchKernelGGL(kmer_solid_retire, per_key, dim3(kBlock), 0, s, table, s_out, weight, n, thr);
         kmer_mini_launch_walk<kWalkFill>(h, D, d_len, k, nullptr, thr, g_in, s);
         GAB_HIP(hipEventRecord(h->ev_ix[4], s));
         GAB_HIP(rocprim::segmented_radix_sort_keys(tmp, seg_bytes, g_in, g_out, (unsigned)m, (unsigned)n, seg, seg + 1, 0u, 40u, s));
@@ -1349,7 +1629,7 @@ int kmer_index_layout(gab_kmer *h, const KmerDev &D, const int32_t *d_len, int k
     }
     (void)hipEventElapsedTime(&h->ix_ms[2], h->ev_ix[3], h->ev_ix[4]);
     (void)hipEventElapsedTime(&h->ix_ms[3], h->ev_ix[4], h->ev_ix[5]);
-    h->ix = R; h->ix_thr = thr; h->indexed = true;
+    h->ix = R; h->ix_thr = thr; h->indexed = true; h->solid = counts != nullptr;
     if (res) *res = R;
     return GAB_OK;
 }
@@ -1420,6 +1700,115 @@ int kmer_index_begin_impl(gab_kmer *h, const char *fn, const KmerInput &in, int 
     Q.distinct = (int64_t)h->h_ct->distinct;
     Q.on = true;
     if (res) *res = gab_kmer_index_result{Q.kept, Q.total_len, Q.minimizers, Q.distinct, 0, 0, 0, 0, 0};
+    return GAB_OK;
+}
+
+
+// ---- solid index, host side ------------------------------------------------------------------------------------------------------------
+// Stages of gab_kmer_index_solid (all on the caller's stream):
+//   kmer_pack, table clear, kmer_count<false>                                                              "count"
+//   kmer_solid_freq, kmer_solid_select, the scan of the bitmap                                             "select"
+//   second table clear, kmer_mini_walk<kWalkCount> into it, kmer_solid_reduce                              "capacity"
+//   -- the synchronisation in the middle, as in the minimizer build --
+//   kmer_index_layout with the count table at hand                                                         "fill", "sort"
+// The two tables trade places on the host before the capacity walk: `table` is whatever the index's kernels work on.
+struct KmerSolidArgs { int k; int32_t min_len; int min_freq; float select_rate; int tandem; };
+
+int kmer_solid_check(const char *fn, gab_kmer *h, const void *off, const void *len, int64_t n_reads, int k, int min_freq, float select_rate) {
+    GAB_CHECK(h && n_reads >= 0 && (n_reads == 0 || (off && len)), "%s: NULL or negative argument", fn);
+    GAB_CHECK(k >= 1 && k <= GAB_KMER_MAX_K, "%s: k = %d, supported 1..%d", fn, k, GAB_KMER_MAX_K);
+    GAB_CHECK(min_freq >= 0, "%s: min_freq = %d (>= 0)", fn, min_freq);
+    GAB_CHECK(select_rate >= 0.0f && select_rate < 1.0f, "%s: select_rate = %g (0 <= select_rate < 1: the rank select_rate * n must be a position of the read)", fn,
+              (double)select_rate);
+    return GAB_OK;
+}
+
+// stage, count into `counts` (count_lines lines, reserved by the caller), look-up, selection and scan: the bitmap then holds the
+// selected positions.  ev: start | counted | selected
+int kmer_solid_front(gab_kmer *h, const KmerInput &in, const KmerPlan &P, const KmerSolidArgs &a, KmerLine *counts, uint64_t count_lines, KmerDev *D,
+                     hipEvent_t *ev) {
+    int rc;
+    hipStream_t s = in.stream;
+    KmerBitmapScan B;
+    KmerCounters *d_ct = h->ct.as<KmerCounters>();
+    GAB_HIP(hipEventRecord(ev[0], s));
+    if ((rc = kmer_bitmap_stage(h, in, P, D, &B))) return rc;
+    if ((rc = h->freq.reserve((size_t)D->n_runs * kRun * 4 + 256))) return rc;
+    GAB_HIP(hipMemsetAsync(counts, 0, (size_t)count_lines * sizeof(KmerLine), s));
+    if (D->n_tiles) {
+        const dim3 grid((unsigned)gab_ceil_div(D->n_tiles, kBlock / 64));
+        hipLaunchKernelGGL(kmer_count<false>, grid, dim3(kBlock), 0, s, D->packed, D->woff, in.d_len, D->tiles, D->n_tiles, a.k, counts, count_lines, d_ct, 0u, 1u,
+                           (uint64_t)0);
+        GAB_HIP(hipEventRecord(ev[1], s));
+        const KmerSolidRule rule = {a.select_rate, (uint32_t)a.min_freq, a.tandem > 0 ? (uint32_t)a.tandem : 0u, a.min_len};
+        hipLaunchKernelGGL(kmer_solid_freq, grid, dim3(kBlock), 0, s, D->packed, D->woff, in.d_len, D->tiles, D->n_tiles, a.k, counts, count_lines,
+                           h->freq.as<uint32_t>());
+        hipLaunchKernelGGL(kmer_solid_select, dim3((unsigned)in.n_reads), dim3(kBlock), 0, s, D->packed, D->woff, in.d_len, D->first_run, a.k, rule,
+                           h->freq.as<uint32_t>(), D->masks, d_ct);
+    } else GAB_HIP(hipEventRecord(ev[1], s));
+    if ((rc = kmer_bitmap_scan(*D, B, s))) return rc;
+    GAB_HIP(hipEventRecord(ev[2], s));
+    return GAB_OK;
+}
+
+int kmer_solid_fetch(gab_kmer *h, const char *fn, const KmerDev &D, hipStream_t s) {
+    int rc;
+    if ((rc = kmer_mini_fetch(h, fn, D, s))) return rc;
+    GAB_CHECK(!h->h_ct->overflow, "%s: internal error: the multiplicity test of a read did not fit after %u classes", fn, kSolidMaxClasses);
+    return GAB_OK;
+}
+
+int kmer_solid_impl(gab_kmer *h, const KmerInput &in, const KmerSolidArgs &a, float rate, gab_kmer_solid_result *res) {
+    const char *fn = "gab_kmer_index_solid";
+    h->counted = false; h->indexed = false; h->pend.on = false;
+    hipStream_t s = in.stream;
+    KmerPlan P;
+    KmerDev D;
+    int rc;
+    if ((rc = kmer_plan(fn, in, a.k, a.min_len, true, &P))) return rc;
+    // both tables: at most one key per position, so never more than half full
+    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), a.k);
+    if ((rc = h->table.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    if ((rc = h->cap.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;
+    h->nlines = nlines; h->k = a.k; h->part = 0; h->nparts = 1; h->retried = false;
+    if ((rc = kmer_solid_front(h, in, P, a, h->table.as<KmerLine>(), nlines, &D, h->ev_sx))) return rc;
+    std::swap(h->table, h->cap);           // from here on `table` is the capacity table and `cap` holds the counts
+    KmerLine *table = h->table.as<KmerLine>();
+    const KmerLine *counts = h->cap.as<KmerLine>();
+    GAB_HIP(hipMemsetAsync(table, 0, (size_t)nlines * sizeof(KmerLine), s));
+    kmer_mini_launch_walk<kWalkCount>(h, D, in.d_len, a.k, nullptr, 0u, nullptr, s);
+    hipLaunchKernelGGL(kmer_solid_reduce, dim3(sweep_grid(h)), dim3(kBlock), 0, s, table, nlines * kSlots, (uint32_t)a.min_freq, h->ct.as<KmerCounters>());
+    GAB_HIP(hipEventRecord(h->ev_sx[3], s));
+    if ((rc = kmer_solid_fetch(h, fn, D, s))) return rc;
+    for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&h->sx_ms[i], h->ev_sx[i], h->ev_sx[i + 1]);
+    h->ix_ms[0] = h->sx_ms[0] + h->sx_ms[1]; h->ix_ms[1] = h->sx_ms[2];      // (gab_kmer_index_last_phases: everything before the capacities | the capacities)
+    h->sx_need = (int64_t)h->h_ct->sx_need; h->sx_fallback = (int64_t)h->h_ct->sx_fallback;
+
+    const uint64_t selected = h->h_ct->ix_minimizers, candidates = h->h_ct->distinct, total = h->h_ct->sx_total, unique = h->h_ct->sx_unique;
+    uint32_t thr;
+    gab_kmer_index_result R = kmer_index_threshold(P.kept, P.total_len, (int64_t)selected, (int64_t)candidates, total, unique, rate, &thr);
+    if ((rc = kmer_index_layout(h, D, in.d_len, a.k, R, thr, &R, s, counts, nlines))) return rc;
+    const int64_t empty = (int64_t)h->h_ct->sx_empty, empty_cap = (int64_t)h->h_ct->sx_empty_cap;
+    h->sx = gab_kmer_solid_result{P.kept, P.total_len, P.positions, (int64_t)selected, (int64_t)candidates, (int64_t)total, (int64_t)unique,
+                                  R.repetitive_frequency, R.filtered_kmers - empty, R.filtered_entries - empty_cap, R.selected_kmers + empty,
+                                  R.selected_kmers, R.index_entries};
+    if (res) *res = h->sx;
+    return GAB_OK;
+}
+
+int kmer_solid_positions_impl(gab_kmer *h, const KmerInput &in, const KmerSolidArgs &a, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout,
+                              bool out_on_device) {
+    const char *fn = "gab_kmer_solid_positions";
+    KmerPlan P;
+    KmerDev D;
+    int rc;
+    h->pend.on = false;                    // (the stage below overwrites what a pending partitioned index build keeps)
+    if ((rc = kmer_plan(fn, in, a.k, a.min_len, true, &P))) return rc;
+    const uint64_t nlines = table_lines(std::max<int64_t>(P.positions, 1), a.k);
+    if ((rc = h->cap.reserve((size_t)nlines * sizeof(KmerLine)))) return rc;      // (the counts go where a count or an index in the handle is not)
+    if ((rc = kmer_solid_front(h, in, P, a, h->cap.as<KmerLine>(), nlines, &D, h->ev_sx))) return rc;
+    if ((rc = kmer_bitmap_emit(h, fn, in, D, a.k, read_start, pos, capacity, nout, out_on_device))) return rc;
+    GAB_CHECK(!h->h_ct->overflow, "%s: internal error: the multiplicity test of a read did not fit after %u classes", fn, kSolidMaxClasses);
     return GAB_OK;
 }
 
@@ -1530,7 +1919,8 @@ extern "C" int gab_kmer_index_part_finish(gab_kmer *h, int64_t minimizers, int64
     return kmer_index_layout(h, Q.dev, Q.d_len, h->k, R, thr, res, Q.stream);
 }
 
-#define KMER_NEED_INDEX(fn) GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers (or gab_kmer_index_part_finish) on this handle")
+#define KMER_NEED_INDEX(fn) \
+    GAB_CHECK(h && h->indexed, fn ": no finished gab_kmer_index_minimizers (or gab_kmer_index_part_finish, or gab_kmer_index_solid) on this handle")
 
 extern "C" int gab_kmer_index_dump(gab_kmer *h, uint64_t *kmers, int64_t *start, int64_t *gpos, int64_t cap_kmers, int64_t cap_entries, int64_t *nk,
                                    int64_t *ne) {
@@ -1599,6 +1989,75 @@ extern "C" int gab_kmer_index_last_phases(gab_kmer *h, float *sketch_ms, float *
     if (count_ms) *count_ms = h->ix_ms[1];
     if (fill_ms) *fill_ms = h->ix_ms[2];
     if (sort_ms) *sort_ms = h->ix_ms[3];
+    return GAB_OK;
+}
+
+
+extern "C" int gab_kmer_index_solid(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
+                                    int min_freq, float select_rate, int tandem_freq, float repeat_kmer_rate, gab_kmer_solid_result *res) {
+    const char *fn = "gab_kmer_index_solid";
+    int rc = kmer_solid_check(fn, h, off, len, n_reads, k, min_freq, select_rate);
+    if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
+    gab_device_guard g(h->device);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, fn, seq, off, len, n_reads, &in))) return rc;
+    return kmer_solid_impl(h, in, KmerSolidArgs{k, min_len_exclusive, min_freq, select_rate, tandem_freq}, repeat_kmer_rate, res);
+}
+
+extern "C" int gab_kmer_index_solid_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                                           int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, float repeat_kmer_rate,
+                                           gab_kmer_solid_result *res, void *stream) {
+    const char *fn = "gab_kmer_index_solid_device";
+    int rc = kmer_solid_check(fn, h, off, len, n_reads, k, min_freq, select_rate);
+    if (rc || (rc = kmer_check_rate(repeat_kmer_rate))) return rc;
+    GAB_CHECK(seq_bytes >= 0 && (seq || seq_bytes == 0), "%s: bad sequence slab", fn);
+    gab_device_guard g(h->device);
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_solid_impl(h, in, KmerSolidArgs{k, min_len_exclusive, min_freq, select_rate, tandem_freq}, repeat_kmer_rate, res);
+}
+
+extern "C" int gab_kmer_solid_positions(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k, int32_t min_len_exclusive,
+                                        int min_freq, float select_rate, int tandem_freq, int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout) {
+    const char *fn = "gab_kmer_solid_positions";
+    int rc = kmer_solid_check(fn, h, off, len, n_reads, k, min_freq, select_rate);
+    if (rc) return rc;
+    GAB_CHECK(nout && capacity >= 0, "%s: NULL or negative argument", fn);
+    gab_device_guard g(h->device);
+    KmerInput in;
+    if ((rc = kmer_input_host(h, fn, seq, off, len, n_reads, &in))) return rc;
+    return kmer_solid_positions_impl(h, in, KmerSolidArgs{k, min_len_exclusive, min_freq, select_rate, tandem_freq}, read_start, pos, capacity, nout, false);
+}
+
+extern "C" int gab_kmer_solid_positions_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                                               int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, int64_t *read_start, int32_t *pos,
+                                               int64_t capacity, int64_t *nout, void *stream) {
+    const char *fn = "gab_kmer_solid_positions_device";
+    int rc = kmer_solid_check(fn, h, off, len, n_reads, k, min_freq, select_rate);
+    if (rc) return rc;
+    GAB_CHECK(nout && capacity >= 0 && seq_bytes >= 0 && (seq || seq_bytes == 0), "%s: bad argument", fn);
+    gab_device_guard g(h->device);
+    KmerInput in;
+    if ((rc = kmer_input_device(seq, seq_bytes, off, len, n_reads, stream, &in))) return rc;
+    return kmer_solid_positions_impl(h, in, KmerSolidArgs{k, min_len_exclusive, min_freq, select_rate, tandem_freq}, read_start, pos, capacity, nout, true);
+}
+
+#define KMER_NEED_SOLID(fn) GAB_CHECK(h && h->indexed && h->solid, fn ": no finished gab_kmer_index_solid on this handle")
+
+extern "C" int gab_kmer_solid_last_phases(gab_kmer *h, float *count_ms, float *select_ms, float *capacity_ms, float *fill_ms, float *sort_ms) {
+    KMER_NEED_SOLID("gab_kmer_solid_last_phases");
+    if (count_ms) *count_ms = h->sx_ms[0];
+    if (select_ms) *select_ms = h->sx_ms[1];
+    if (capacity_ms) *capacity_ms = h->sx_ms[2];
+    if (fill_ms) *fill_ms = h->ix_ms[2];
+    if (sort_ms) *sort_ms = h->ix_ms[3];
+    return GAB_OK;
+}
+
+extern "C" int gab_kmer_solid_last_stats(gab_kmer *h, int64_t *tested_positions, int64_t *fallback_reads) {
+    KMER_NEED_SOLID("gab_kmer_solid_last_stats");
+    if (tested_positions) *tested_positions = h->sx_need;
+    if (fallback_reads) *fallback_reads = h->sx_fallback;
     return GAB_OK;
 }
 

@@ -1,7 +1,8 @@
 """Host-side mirror of KmerCounter::count (kmer-cnt/vertex_index.cpp:787-860) over the C ABI, whole or in key-space partitions
 (include/gab.h: gab_kmer_count_part), and of the minimizer index, VertexIndex::buildIndexMinimizers (kmer-cnt/vertex_index.cpp:394-502;
 include/gab.h: gab_kmer_sketch, gab_kmer_index_minimizers), whole or in key-space partitions built in two phases
-(gab_kmer_index_part_begin / gab_kmer_index_part_finish)."""
+(gab_kmer_index_part_begin / gab_kmer_index_part_finish), and of the solid k-mer index, VertexIndex::buildIndexUnevenCoverage
+(kmer-cnt/vertex_index.cpp:30-130; include/gab.h: gab_kmer_index_solid, gab_kmer_solid_positions)."""
 import ctypes as C
 import threading
 
@@ -23,6 +24,11 @@ class _Result(C.Structure):
 class _IndexResult(C.Structure):
     _fields_ = [(f, C.c_int64) for f in ("reads_kept", "total_len", "minimizers", "distinct", "repetitive_frequency", "filtered_kmers",
                                          "filtered_entries", "selected_kmers", "index_entries")]
+
+
+class _SolidResult(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in ("reads_kept", "total_len", "positions", "selected_positions", "candidates", "mean_total", "mean_unique",
+                                         "repetitive_frequency", "filtered_kmers", "filtered_entries", "selected_kmers", "indexed_kmers", "index_entries")]
 
 
 def _p(a):
@@ -285,6 +291,75 @@ class KmerCounter:
         a = C.c_float(0); b = C.c_float(0); c = C.c_float(0); d = C.c_float(0)
         check(lib().gab_kmer_index_last_phases(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"sketch_ms": a.value, "count_ms": b.value, "fill_ms": c.value, "sort_ms": d.value}
+
+    # ---- solid k-mer index ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _solid_dict(res):
+        return {f: getattr(res, f) for f, _ in _SolidResult._fields_}
+
+    @staticmethod
+    def _solid_rule(k, min_len, min_freq, select_rate, tandem_freq):
+        return C.c_int(k), C.c_int32(min_len), C.c_int(min_freq), C.c_float(select_rate), C.c_int(tandem_freq)
+
+    def index_solid(self, reads, k, min_freq=2, select_rate=0.4, tandem_freq=100, rate=100.0, min_len=5000):
+        """counts, then builds the solid k-mer index into the handle (it replaces a count or an index there) -> the thirteen fields of
+        gab_kmer_solid_result; index_dump / index_lookup then read it"""
+        seq, off, ln = self._packed(reads)
+        res = _SolidResult(*([-12345] * 13))
+        check(lib().gab_kmer_index_solid(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), *self._solid_rule(k, min_len, min_freq, select_rate, tandem_freq),
+                                         C.c_float(rate), C.byref(res)))
+        return self._solid_dict(res)
+
+    def index_solid_device(self, seq, off, ln, k, min_freq=2, select_rate=0.4, tandem_freq=100, rate=100.0, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU: uint8 / int64 / int32"""
+        res = _SolidResult(*([-12345] * 13))
+        check(lib().gab_kmer_index_solid_device(self._h, *_dev(seq, off, ln), *self._solid_rule(k, min_len, min_freq, select_rate, tandem_freq), C.c_float(rate),
+                                                C.byref(res), C.c_void_p(stream)))
+        return self._solid_dict(res)
+
+    def solid_positions_into(self, reads, k, read_start, pos, min_freq=2, select_rate=0.4, tandem_freq=100, min_len=5000):
+        """one raw gab_kmer_solid_positions into the caller's arrays: (return code, needed size)"""
+        seq, off, ln = self._packed(reads)
+        n = C.c_int64(-1)
+        rc = lib().gab_kmer_solid_positions(self._h, _p(seq), _p(off), _p(ln), C.c_int64(ln.size), *self._solid_rule(k, min_len, min_freq, select_rate, tandem_freq),
+                                            _p(read_start), _p(pos), C.c_int64(pos.size), C.byref(n))
+        return rc, n.value
+
+    def solid_positions(self, reads, k, min_freq=2, select_rate=0.4, tandem_freq=100, min_len=5000, capacity=None):
+        """-> (read_start int64 [n + 1], pos int32): the selected positions of read i are pos[read_start[i]:read_start[i + 1]], ascending.
+        capacity: room offered on the first try (grown once when it is too little); by default the select_rate share of the positions"""
+        packed = self._packed(reads)
+        positions = int(np.maximum(packed[2].astype(np.int64) - k, 0).sum())
+        cap = int(positions * min(1.0, select_rate + 0.1)) + 64 if capacity is None else int(capacity)
+        while True:
+            start = np.full(packed[2].size + 1, -12345, np.int64); pos = np.full(cap, -12345, np.int32)
+            rc, n = self.solid_positions_into(packed, k, start, pos, min_freq, select_rate, tandem_freq, min_len)
+            if rc == ERANGE and n > cap:
+                cap = n
+                continue
+            check(rc)
+            return start, pos[:n]
+
+    def solid_positions_device(self, seq, off, ln, k, read_start, pos, min_freq=2, select_rate=0.4, tandem_freq=100, min_len=5000, stream=0):
+        """torch tensors on the handle's GPU; outputs read_start int64 [n + 1] and pos int32 [capacity] -> (return code, needed size)"""
+        n = C.c_int64(-1)
+        rc = lib().gab_kmer_solid_positions_device(self._h, *_dev(seq, off, ln), *self._solid_rule(k, min_len, min_freq, select_rate, tandem_freq),
+                                                   C.c_void_p(read_start.data_ptr()), C.c_void_p(pos.data_ptr()), C.c_int64(pos.numel()), C.byref(n),
+                                                   C.c_void_p(stream))
+        if rc != ERANGE:
+            check(rc)
+        return rc, n.value
+
+    def solid_last_phases(self):
+        v = [C.c_float(0) for _ in range(5)]
+        check(lib().gab_kmer_solid_last_phases(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("count_ms", "select_ms", "capacity_ms", "fill_ms", "sort_ms"), (x.value for x in v)))
+
+    def solid_last_stats(self):
+        """tested_positions: positions that took the multiplicity test; fallback_reads: reads whose test outgrew the on-chip table"""
+        a = C.c_int64(-1); b = C.c_int64(-1)
+        check(lib().gab_kmer_solid_last_stats(self._h, C.byref(a), C.byref(b)))
+        return {"tested_positions": a.value, "fallback_reads": b.value}
 
 
 class KmerCounterSet:

@@ -582,6 +582,62 @@ int gab_kmer_index_part_finish(gab_kmer *h, int64_t minimizers, int64_t distinct
  * capacity table it ended in, and whether the capacity pass was repeated (0 / 1) */
 int gab_kmer_index_last_part(gab_kmer *h, int *part, int *nparts, int64_t *table_slots, int *retried);
 
+/* ---- kmer-cnt, solid k-mer index: per read, the k-mers of the highest global count (buildIndexUnevenCoverage) ---------------
+ * Replaces  vertexIndex.buildIndexUnevenCoverage(MIN_FREQ, rate, tandem)   kmer-cnt/kmer_cnt.cpp:228-230, 290-292 (commented out there)
+ *           -> VertexIndex::buildIndexUnevenCoverage                       kmer-cnt/vertex_index.cpp:30-130
+ *           (the selector: yieldFrequentKmers, kmer-cnt/vertex_index.cpp:321-363; the filter: filterFrequentKmers,
+ *            kmer-cnt/vertex_index.cpp:178-217; getFreq as the exact count, which is what COUNT_VERSION 0 makes of it).
+ * Reads, the length filter, the strand, the positions 0 .. L - k - 1, the canonical form and the global positions are those of
+ * gab_kmer_index_minimizers; c(x) is gab_kmer_count's exact count over the kept reads.  The call counts and builds in one go.
+ * Selection, per kept read with n = L - k > 0 positions and f[p] = c(canonical k-mer at p):
+ *   1. cut = the element of rank (size_t)(select_rate * (float)n) (a float product, truncated; 0-based) of f in descending order;
+ *      where the product reaches n the reference reads past its array and this library takes rank n - 1;
+ *   2. every position with f[p] >= cut stays (ties included, so these can be far more than the rank);
+ *   3. tandem_freq > 0: positions whose canonical k-mer occurs more than tandem_freq times among ALL n positions of the read go;
+ *   4. positions with f[p] < min_freq go.
+ * Index: capacity(x) = selected positions with canonical k-mer x (`candidates` keys, `selected_positions` in all).  The filter's
+ * mean runs over the keys with capacity >= min_freq (mean_total their sum, mean_unique their number): repetitive_frequency =
+ * gab_kmer_repetitive_frequency(mean_total, mean_unique, repeat_kmer_rate).  Keys with capacity > repetitive_frequency are removed
+ * (filtered_kmers, filtered_entries).  Every other key stays (selected_kmers, the reference's "Selected k-mers"), with the ascending
+ * global positions of its selected positions if c(x) <= repetitive_frequency and with an EMPTY list otherwise (the reference's
+ * second pass skips by global count, kmer-cnt/vertex_index.cpp:78-79); indexed_kmers lists are not empty, index_entries positions.
+ * Afterwards the handle holds an index: gab_kmer_index_dump returns the indexed_kmers non-empty lists, gab_kmer_index_lookup reads a
+ * key with an empty list as absent and a removed one as repetitive, the count accessors return GAB_EINVAL (the reference clears its
+ * counter, kmer-cnt/vertex_index.cpp:111) and a pending gab_kmer_index_part_begin is dropped.
+ * Limits: those of gab_kmer_index_minimizers, min_freq >= 0, 0 <= select_rate < 1 (NaN is refused); tandem_freq <= 0 switches rule 3 off.
+ * Key-space partitions are not offered: the rank of a read needs every count. */
+typedef struct {
+    int64_t reads_kept, total_len, positions;      /* as gab_kmer_index_result / gab_kmer_result */
+    int64_t selected_positions, candidates;        /* the sum of the capacities; the keys with capacity >= 1 */
+    int64_t mean_total, mean_unique;               /* the filter's totals: over capacities >= min_freq */
+    int64_t repetitive_frequency;
+    int64_t filtered_kmers, filtered_entries;
+    int64_t selected_kmers;                        /* kept keys, empty lists included (what the reference prints) */
+    int64_t indexed_kmers, index_entries;          /* the non-empty lists and their positions */
+} gab_kmer_solid_result;
+int gab_kmer_index_solid(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                         int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, float repeat_kmer_rate,
+                         gab_kmer_solid_result *res);
+int gab_kmer_index_solid_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads,
+                                int k, int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq,
+                                float repeat_kmer_rate, gab_kmer_solid_result *res, void *stream);
+/* The selection alone (rules 1-4), as gab_kmer_sketch returns the minimizers: pos[read_start[i] .. read_start[i + 1]) ascending;
+ * GAB_ERANGE with *nout and nothing written when `capacity` is too small.  It counts into memory of its own: a count or an index
+ * in the handle stays as it is (a pending gab_kmer_index_part_begin is dropped, as by gab_kmer_sketch). */
+int gab_kmer_solid_positions(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
+                             int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, int64_t *read_start,
+                             int32_t *pos, int64_t capacity, int64_t *nout);
+int gab_kmer_solid_positions_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len,
+                                    int64_t n_reads, int k, int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq,
+                                    int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout, void *stream);
+/* last solid build, per stage (HIP events, ms): 2-bit packing + table clear + count; frequency look-up + selection + scan; second
+ * table clear + capacity pass + reduction; ordering the keys, list offsets and the fill pass; the segmented sort. */
+int gab_kmer_solid_last_phases(gab_kmer *h, float *count_ms, float *select_ms, float *capacity_ms, float *fill_ms, float *sort_ms);
+/* last solid build: the positions that took the multiplicity test of rule 3 (those with c(x) > tandem_freq among a read's top
+ * counts; a k-mer cannot occur more often in one read than in all), and the reads whose tested k-mers outgrew the on-chip table
+ * of the test and were taken in several hash classes instead (exact either way). */
+int gab_kmer_solid_last_stats(gab_kmer *h, int64_t *tested_positions, int64_t *fallback_reads);
+
 /* ---- input parsers ---------------------------------------------------------
  * The reference drivers parse their text inputs on the host, line by line, outside the region of interest
  * (bsw: loadPairs, bsw/src/main_banded.cpp:164-206 -- fgets + sscanf per pair; bpm / wfa: getline per line,

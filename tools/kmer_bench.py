@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the k-mer counter (gab_kmer_*) on a generated E. coli-like read set.  Standalone; needs a GPU.
 
-    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--parts 1,2,4,8] [--minimizers W] [--out kmer_bench.json]
+    python tools/kmer_bench.py [--repeats 7] [--warmup 2] [--coverage 50] [--parts 1,2,4,8] [--minimizers W] [--solid] [--out kmer_bench.json]
 
 The read set: a 4.6 Mbp random genome, reads of 5 .. 20 kb at 50x, both strands, 10 % errors (substitutions, seeded).
 For k = 17 and 15 it reports, warm, as the median of the repeats:
@@ -28,6 +28,12 @@ wall time of its begin and of its finish (medians of the warm repeats) and the d
 GPUs are two rounds with the host's sum in between, so the ONE-GPU FORECAST of the N-GPU wall time is the slowest begin plus the
 slowest finish -- not a measurement of one (no second card, no shared host link).  --check compares the merged dumps with the
 unpartitioned index.
+
+--solid: INSTEAD of the count, the solid k-mer index (gab_kmer_index_solid_device with --min-freq, --select-rate, --tandem and
+--rate) on the same reads, resident, for k = 17 and 15: the thirteen result fields, k-mer positions per second over the wall time of
+the call (median of the warm repeats; the call counts for itself and synchronises twice), the device time of its five stages --
+count, frequency look-up + selection, capacity, fill, sort -- and the positions that took the tandem test with the reads that left
+the on-chip table.  --check compares the fields with the numpy model of tests/solid_model.py (minutes of CPU time at this size).
 """
 import argparse
 import json
@@ -127,7 +133,11 @@ def main():
     ap.add_argument("--coverage", type=int, default=50)
     ap.add_argument("--parts", default="", help="comma-separated partition counts to forecast, e.g. 1,2,4,8")
     ap.add_argument("--minimizers", type=int, default=0, metavar="W", help="measure the minimizer index with window W instead of the count")
-    ap.add_argument("--rate", type=float, default=100.0, help="repeat_kmer_rate of --minimizers")
+    ap.add_argument("--rate", type=float, default=100.0, help="repeat_kmer_rate of --minimizers and --solid")
+    ap.add_argument("--solid", action="store_true", help="measure the solid k-mer index instead of the count")
+    ap.add_argument("--min-freq", type=int, default=2)
+    ap.add_argument("--select-rate", type=float, default=0.4)
+    ap.add_argument("--tandem", type=int, default=100)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -143,7 +153,28 @@ def main():
     kc = KmerCounter()
     kc.reserve(len(reads), seq.size)
     out = {"reads": len(reads), "bases": int(seq.size), "repeats": a.repeats, "warmup": a.warmup, "k": {}}
-    if a.minimizers:
+    if a.solid:
+        out["solid"] = {"min_freq": a.min_freq, "select_rate": a.select_rate, "tandem_freq": a.tandem, "rate": a.rate, "k": {}}
+        for k in (17, 15):
+            samples = []
+            for it in range(a.warmup + a.repeats):
+                t0 = time.perf_counter()
+                res = kc.index_solid_device(d_seq, d_off, d_len, k, a.min_freq, a.select_rate, a.tandem, a.rate)
+                wall = time.perf_counter() - t0
+                if it >= a.warmup:
+                    samples.append((wall, kc.solid_last_phases()))
+            t = statistics.median(s[0] for s in samples)
+            row = {"result": res, "positions_per_s": res["positions"] / t, "seconds_median": t, "seconds_min": min(s[0] for s in samples),
+                   "seconds_max": max(s[0] for s in samples)}
+            for f in ("count_ms", "select_ms", "capacity_ms", "fill_ms", "sort_ms"):
+                row[f] = statistics.median(s[1][f] for s in samples)
+            row.update(kc.solid_last_stats())
+            if a.check:
+                from tests import solid_model
+                m = solid_model.build_index(reads, k, a.min_freq, a.select_rate, a.tandem, a.rate)
+                row["matches_model"] = all(res[f] == m[f] for f in solid_model.FIELDS)
+            out["solid"]["k"][str(k)] = row
+    elif a.minimizers:
         out["minimizers"] = {"window": a.minimizers, "rate": a.rate, "k": {}}
         for k in (17, 15):
             samples = []
@@ -202,7 +233,9 @@ def main():
                 m = kmer_model.model(reads, k)
                 row["matches_model"] = all(res[f] == m[f] for f in kmer_model.FIELDS)
             out["k"][str(k)] = row
-    if a.parts and a.minimizers:
+    if a.solid:
+        pass                                    # (key-space partitions of the solid index are not offered: the rank of a read needs every count)
+    elif a.parts and a.minimizers:
         out["index_parts"] = index_parts(a, reads, d_seq, d_off, d_len)
     elif a.parts:
         out["parts"] = {}
