@@ -128,6 +128,13 @@
 //      two guards.  With a dead or zero edge nothing the reference still holds can exceed best, and ending returns its score.
 //      (9 of the 10 M read-like pairs at the defaults; found by the model at a mismatch score of -128, where rows of zeros are common.)
 //
+// Where the rule lives in bsw_dp8 (the 8-bit kernel; profiles/bsw_row_tail.md): score-only is a template argument, so the six-field
+// form holds none of the above and the score-only form none of the six-field bookkeeping.  Behind a row's sweep the zero trim and
+// both prunes are ONE evaluation of the two four-cell windows -- a zero cell is a dropped cell, so with `best` taken as 0 the
+// prune's test is the reference's trim, and a lane whose prune is off (or whose left edge may not move) differs by an operand, not
+// by a branch; whatever ends the pair in this row (z-drop, a guard, the exit's bound) is gathered in one flag and acted on once.
+// bsw_dp<WIDE> keeps the rule in the order this comment states it.
+//
 // Roofline: integer-VALU / LDS bound (~20 VALU + 1 LDS read + 1 LDS write per DP cell,
 // ~7.4 k cells per ~210 input bytes); HBM traffic is the algorithmic minimum
 // len1 + len2 + 12 B per pair plus the 4-byte permutation entry.
@@ -560,7 +567,14 @@ __device__ __forceinline__ BswCellOut bsw_cell(int diag, int e, int f, uint32_t 
 
 // SYM: o_del + e_del == o_ins + e_ins (BWA-MEM's defaults): M - (o + e) is the same value for the E and the F source.
 // MS1: no score above 1 (BWA-MEM's a = 1): for diag >= 1, M <= diag + 1 <= 2 diag, so "diag == 0 -> M = 0" is min(M, 2 diag).
-template <bool SYM, bool MS1>
+// SO : score-only call (result_out == nullptr, known at the launch).  The score-only form carries no gscore / gtle / max_off and
+//      writes no six-field record; the six-field form has no exit, no prune, no guard and no second pass.
+// Per-row code behind the column sweep (both forms): the row maximum's column, z-drop, then ONE straight block for the band
+// trimming -- the zero trim and, in the score-only form, both prunes are the same evaluation of the four-cell windows next to the
+// two edges (a zero cell is a dropped cell; with `best` taken as 0 the prune's test IS the zero trim), so a lane whose prune is off
+// or whose left edge may not move gets a zero operand instead of a branch.  Only the cell-by-cell loops of a zero trim that has
+// run past its window, the zeroing of dropped cells and the exit's bound pass are divergent regions.
+template <bool SYM, bool MS1, bool SO>
 __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec *__restrict__ recs, int64_t kbeg,
                                               int64_t kend, int qcap, int32_t *__restrict__ score_out,
                                               gab_bsw_result *__restrict__ result_out, BswStats *st) {
@@ -590,14 +604,17 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         const int oe_del = c.o_del + c.e_del, oe_ins = c.o_ins + c.e_ins;
         const int e_del = c.e_del, e_ins = c.e_ins;
 
-        // query -> nibbles (codes above 4 count as N)
-        for (int p0 = 0; p0 * 2 < qlen; p0 += 2) {             // 4 bases -> 2 nibble bytes
-            const uint32_t src = load_u32_unaligned(q + p0 * 2);
-            for (int b = 0; b < 2; b++) {
-                uint32_t lo = (src >> (b * 16)) & 0xff, hi = (src >> (b * 16 + 8)) & 0xff;
-                lo = lo > 4u ? 4u : lo; hi = hi > 4u ? 4u : hi;
-                QPAIR(p0 + b) = (uint8_t)(lo | hi << 4);
-            }
+        // query -> nibbles (codes above 4 count as N), 8 bases -> 4 nibble bytes per trip.  The second dword is read only when
+        // it holds a base (a sequence has three readable bytes behind it, not seven); the four stores stay inside the nibble
+        // rows: pair 4 * ((qlen - 1) / 8) + 3 <= qcap / 2 - 1, qcap being a multiple of 16.
+        for (int p0 = 0; p0 * 2 < qlen; p0 += 4) {
+            const uint32_t s0 = load_u32_unaligned(q + p0 * 2);
+            const uint32_t s1 = p0 * 2 + 4 < qlen ? load_u32_unaligned(q + p0 * 2 + 4) : 0u;
+            // even bases in the low byte of each half, odd bases on top of them: a half is one nibble pair
+            const uint32_t n0 = pk_min_u16(s0 & 0x00ff00ffu, 0x00040004u) | pk_min_u16((s0 >> 8) & 0x00ff00ffu, 0x00040004u) << 4;
+            const uint32_t n1 = pk_min_u16(s1 & 0x00ff00ffu, 0x00040004u) | pk_min_u16((s1 >> 8) & 0x00ff00ffu, 0x00040004u) << 4;
+            QPAIR(p0) = (uint8_t)n0; QPAIR(p0 + 1) = (uint8_t)(n0 >> 16);
+            QPAIR(p0 + 2) = (uint8_t)n1; QPAIR(p0 + 3) = (uint8_t)(n1 >> 16);
         }
         int w = c.w;
         {
@@ -606,21 +623,20 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             lim = (int)((double)(qlen * c.max_sc + c.end_bonus - c.o_del) / e_del + 1.);
             lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
         }
-        const bool score_only = result_out == nullptr;      // wave-uniform: the early exit and the two prunes of the header comment apply
         // the prunes need every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
-        bool prune = score_only && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
+        bool prune = SO && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
         int best, best_i, best_j, g_i, gscore, max_off;
       for (;;) {                                            // second trip: a pair one of the guards sent back, prunes off
-        // row -1 (bandedSWA.cpp:159-161); E = 0
+        // row -1 (bandedSWA.cpp:159-161); E = 0.  Cell 0 is h0 and cell j >= 1 is max(h0 - oe_ins - (j - 1) * e_ins, 0): two cells
+        // per dword store.  Pair word qlen / 2 ends on cell qlen + 1 when qlen is even -- inside the cell rows (qcap is even), and a
+        // cell the sweep never reads as part of a band.
         {
-            int prev = h0;
-            for (int j = 0; j <= qlen; j++) {
-                int v;
-                if (j == 0) v = h0;
-                else if (j == 1) v = h0 > oe_ins ? h0 - oe_ins : 0;
-                else v = prev > e_ins ? prev - e_ins : 0;
-                prev = v;
-                CELL16(j) = (uint16_t)v;
+            int v = h0 - oe_ins;                            // cell 2p - 1
+            CW[0] = (uint32_t)h0 | (uint32_t)max(v, 0) << 16;
+            for (int p = 1; p <= (qlen >> 1); p++) {
+                const int lo = v - e_ins;
+                v = lo - e_ins;
+                CW[p * 64] = (uint32_t)max(lo, 0) | (uint32_t)max(v, 0) << 16;
             }
         }
         best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
@@ -751,14 +767,18 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             cells += (unsigned)(end > beg ? end - beg : 0);
             const int rowmax = (int)(rowpk >> 16);
             CELL16(end) = (uint16_t)hleft;        // eh[end].h = h1, eh[end].e = 0
-            if (j == qlen) {
-                if (!(gscore > hleft)) g_i = i;
-                gscore = hleft > gscore ? hleft : gscore;
+            if constexpr (!SO) {
+                if (j == qlen) {
+                    if (!(gscore > hleft)) g_i = i;
+                    gscore = hleft > gscore ? hleft : gscore;
+                }
             }
             if (rowmax == 0) {                              // zero-row guard of the right prune (header comment, step 10)
-                if (dropped && beg == 0) {
-                    const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
-                    abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                if constexpr (SO) {
+                    if (dropped && beg == 0) {
+                        const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
+                        abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                    }
                 }
                 break;
             }
@@ -788,107 +808,128 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 const uint32_t eq = (ne ^ 0x01010101u) & (0x01010101u >> (8 * (4 - nv)));
                 rowmax_j = kj + ((31 - __builtin_clz(eq)) >> 3);
             }
+            // What ends the pair's row loop in this row is gathered in `stop` and acted on once, behind the trimming (a lane that
+            // stops trims its own band for nothing: the other lanes of the wave run that code anyway, and every access of it is
+            // one that a row that goes on makes too).  Order as in the reference: the z-drop guard, the z-drop test, the right-edge
+            // guard, and the exit's bound last.
             const int rows_left = tlen - 1 - i;
-            bool try_exit = false;
-            if (rowmax > best) {
+            const bool raised = rowmax > best;
+            bool stop = false;
+            if (c.zdrop > 0) {                              // (wave-uniform)
+                const int di = i - best_i, dj = rowmax_j - best_j;
+                const int gap = di > dj ? (di - dj) * e_del : (dj - di) * e_ins;
+                stop = !raised && best - rowmax - gap > c.zdrop;
+                if constexpr (SO) {                         // z-drop guard: the reference's row maximum may differ here
+                    abandon = !raised && dropped && rowmax < best - c.zdrop;
+                    stop = stop || abandon;
+                }
+            }
+            // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
+            const bool try_exit = SO && !raised && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
+            if (raised) {
                 best = rowmax; best_i = i; best_j = rowmax_j;
-                int off = rowmax_j - i; off = off < 0 ? -off : off;
-                max_off = off > max_off ? off : max_off;
-            } else {
-                if (c.zdrop > 0) {
-                    if (dropped && rowmax < best - c.zdrop) { abandon = true; break; }     // the reference's row maximum may differ here
-                    int di = i - best_i, dj = rowmax_j - best_j;
-                    if (di > dj) { if (best - rowmax - (di - dj) * e_del > c.zdrop) break; }
-                    else { if (best - rowmax - (dj - di) * e_ins > c.zdrop) break; }
+                if constexpr (!SO) {
+                    int off = rowmax_j - i; off = off < 0 ? -off : off;
+                    max_off = off > max_off ? off : max_off;
                 }
-                // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
-                try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
-            // right-edge guard of the left prune (header comment, step 5)
-            if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
-                hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best) { abandon = true; break; }
-            // Band trimming (bandedSWA.cpp:234-237).  The four cells next to either edge are fetched in ONE LDS round
-            // trip (whole pair words; cells outside [beg, end] only ever shorten the count and the clamps below undo
-            // that); the cell-by-cell loops of the reference run only when all four are zero.
+            if constexpr (SO) {
+                // right-edge guard of the left prune (header comment, step 5); a row that the z-drop test ends does not reach it
+                const bool guard = !stop && dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
+                                   hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best;
+                abandon = abandon || guard;
+                stop = stop || guard;
+            }
+            // Band trimming (bandedSWA.cpp:234-237) and, in the score-only form, both prunes (header comment).  The four cells
+            // next to either edge are fetched in ONE LDS round trip (whole pair words): x = cells beg0 .. beg0 + 3, y = cells
+            // end0 - 3 .. end0.  A half outside [beg0, end0] or the query may hold anything: it can only shorten a count, and the
+            // clamps below undo that.  rowmax > 0 puts a live cell into [beg0 + 1, end0], so both trims stop inside the band.
+            // The next row's left edge, which the left prune and the exit's bound both test:
+            int edge_pot = 0;
             {
+                const int beg0 = beg, end0 = end;
                 uint64_t x = (uint64_t)b1 << 32 | b0;                      // cells 2pb .. 2pb+3, low half first
-                if (beg & 1) x = (x >> 16) | (uint64_t)(b2 & 0xffffu) << 48;
-                const int lz = x ? __builtin_ctzll(x) >> 4 : 4;
-                const int beg0 = beg;
-                j = beg + lz;
-                if (lz == 4) for (; j < end && CELL16(j) == 0; j++) {}
-                beg = j < end ? j : end;
+                if (beg0 & 1) x = (x >> 16) | (uint64_t)(b2 & 0xffffu) << 48;
                 uint64_t y = (uint64_t)e2 << 32 | e1;                      // cells 2pe-2 .. 2pe+1; cell `end` goes on top
-                if (!(end & 1)) y = (y << 16) | (e0 >> 16);
-                const int tz = y ? __builtin_clzll(y) >> 4 : 4;
-                const int end0 = end;
-                j = end - tz;
-                if (tz == 4) for (; j >= beg && CELL16(j) == 0; j--) {}
-                j = j > beg - 1 ? j : beg - 1;
-                const int jl = j;                                          // the last live stored cell (beg - 1: none)
-                end = j + 2 < qlen ? j + 2 : qlen;
-                // Left prune (header comment): cell beg is live here, the zero trim stopped at it.  The four cells of x are
-                // judged in packed 16-bit halves -- m = max(H, E) <= 255 and max_sc * columns left <= 255, and a half right of
-                // the band or the query may hold anything: the clamp to `end` below undoes what it adds.  The edge moves over
-                // these four cells at most; a row whose zero trim has left them behind (lz == 4) prunes nothing.
-                if (prune) {
-                    const uint32_t r2 = as_u32(pk_splat(min(rows_left, qlen))), m2 = as_u32(pk_splat(c.max_sc));
-                    const uint32_t best2 = (uint32_t)best * 0x00010001u;
-                    if (beg < end && lz < 4) {
-                        bool go = true;
-                        if (beg == 0) {
-                            const int hb = h0 - c.o_del - e_del * (i + 2);
-                            go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
-                        }
-                        if (go) {
-                            const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
-                            const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
-                            const uint32_t ml = pk_max_i16(xl & 0x00ff00ffu, (xl >> 8) & 0x00ff00ffu);
-                            const uint32_t mh = pk_max_i16(xh & 0x00ff00ffu, (xh >> 8) & 0x00ff00ffu);
-                            // per half: non-zero where the cell is live and its potential exceeds best
-                            const uint32_t sl = pk_mul_lo(pk_subsat_u16_v(add_u32_v(ml, pk_mul_lo(pk_min_u16(cl01, r2), m2)), best2),
-                                                          pk_min_u16_1(ml));
-                            const uint32_t sh = pk_mul_lo(pk_subsat_u16_v(add_u32_v(mh, pk_mul_lo(pk_min_u16(cl01 - 0x00020002u, r2), m2)), best2),
-                                                          pk_min_u16_1(mh));
-                            const uint64_t stay = (uint64_t)sh << 32 | sl;
-                            const int lp = stay ? __builtin_ctzll(stay) >> 4 : 4;
-                            j = beg0 + lp;
-                            j = j < end ? j : end;
-                            dropped = dropped || j > beg;
-                            beg = j;
-                        }
-                    }
-                    // Right prune (header comment): the four cells of y, end0 - 3 .. end0, judged the same way from the top; a half
-                    // left of `beg` or of the query may hold anything: the clamp to beg - 1 undoes what it adds.  A row whose zero
-                    // trim has left the four behind (tz == 4) has jl <= end0 - 4 and prunes nothing.  The dropped cells are set
-                    // to zero with 16-bit stores (nothing waits for them), only in lanes and rows that drop a live cell.
-                    if (jl >= beg) {
-                        const uint32_t yl = (uint32_t)y, yh = (uint32_t)(y >> 32);
-                        const uint32_t cr01 = ((uint32_t)(qlen - end0 + 3) & 0xffffu) | (uint32_t)(qlen - end0 + 2) << 16;
-                        const uint32_t ml = pk_max_i16(yl & 0x00ff00ffu, (yl >> 8) & 0x00ff00ffu);
-                        const uint32_t mh = pk_max_i16(yh & 0x00ff00ffu, (yh >> 8) & 0x00ff00ffu);
-                        const uint32_t sl = pk_mul_lo(pk_subsat_u16_v(add_u32_v(ml, pk_mul_lo(pk_min_u16(cr01, r2), m2)), best2),
-                                                      pk_min_u16_1(ml));
-                        const uint32_t sh = pk_mul_lo(pk_subsat_u16_v(add_u32_v(mh, pk_mul_lo(pk_min_u16(cr01 - 0x00020002u, r2), m2)), best2),
-                                                      pk_min_u16_1(mh));
-                        const uint64_t stay = (uint64_t)sh << 32 | sl;
-                        const int tp = stay ? __builtin_clzll(stay) >> 4 : 4;
-                        int jn = end0 - tp;
-                        jn = jn > beg - 1 ? jn : beg - 1;
-                        if (jn < jl) {
-                            for (j = jn + 1; j <= jl; j++) CELL16(j) = 0;
-                            dropped = true;
-                            end = jn + 2 < qlen ? jn + 2 : qlen;
-                        }
-                    }
-                }
-            }
-            if (try_exit) {
-                int bound = stale_pot;
-                if (beg == 0) {
+                if (!(end0 & 1)) y = (y << 16) | (e0 >> 16);
+                const int lz = x ? __builtin_ctzll(x) >> 4 : 4, tz = y ? __builtin_clzll(y) >> 4 : 4;
+                int base = min(beg0 + lz, end0);                           // the zero trim's left edge: the first live cell
+                int lp = lz, tp = tz;                                      // cells either edge moves over, of its window
+                if constexpr (SO) {
+                    // The windows judged in packed 16-bit halves: m = max(H, E) <= 255 and max_sc * columns left <= 255.  A half is
+                    // non-zero where its cell is live and its potential exceeds the lane's operand -- `best` where the edge
+                    // may be pruned; 0 where it may only be trimmed (prune off; or the left edge at column 0 in front of a live
+                    // next-row edge, or at qlen), which leaves exactly the non-zero cells: lp == lz, tp == tz there.  A row
+                    // whose zero trim runs past a window (lz == 4, tz == 4) has all four halves zero under either operand
+                    // and prunes nothing on that side.
+                    const int rq = min(rows_left, qlen);
                     const int hb = h0 - c.o_del - e_del * (i + 2);
-                    if (hb > 0) bound = max(bound, hb + c.max_sc * min(rows_left, qlen));
+                    edge_pot = hb > 0 ? hb + c.max_sc * rq : 0;
+                    const bool go = prune && base < qlen && (base != 0 || edge_pot <= best);
+                    const uint32_t r2 = as_u32(pk_splat(rq)), m2 = as_u32(pk_splat(c.max_sc));
+                    const uint32_t bestL = (uint32_t)(go ? best : 0) * 0x00010001u, bestR = (uint32_t)(prune ? best : 0) * 0x00010001u;
+                    const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
+                    const uint32_t cr01 = ((uint32_t)(qlen - end0 + 3) & 0xffffu) | (uint32_t)(qlen - end0 + 2) << 16;
+#define BSW_STAY(W, CL, B2, OUT)                                                                                   \
+    {                                                                                                             \
+        const uint32_t m = pk_max_i16((W) & 0x00ff00ffu, ((W) >> 8) & 0x00ff00ffu);                              \
+        (OUT) = pk_mul_lo(pk_subsat_u16_v(add_u32_v(m, pk_mul_lo(pk_min_u16((CL), r2), m2)), (B2)), pk_min_u16_1(m)); \
+    }
+                    uint32_t sll, slh, srl, srh;
+                    BSW_STAY((uint32_t)x, cl01, bestL, sll)
+                    BSW_STAY((uint32_t)(x >> 32), cl01 - 0x00020002u, bestL, slh)
+                    BSW_STAY((uint32_t)y, cr01, bestR, srl)
+                    BSW_STAY((uint32_t)(y >> 32), cr01 - 0x00020002u, bestR, srh)
+#undef BSW_STAY
+                    const uint64_t stl = (uint64_t)slh << 32 | sll, str = (uint64_t)srh << 32 | srl;
+                    lp = stl ? __builtin_ctzll(stl) >> 4 : 4;
+                    tp = str ? __builtin_clzll(str) >> 4 : 4;
                 }
+                int bl = beg0 + lp;
+                if (__builtin_expect(lz == 4, 0)) {                        // the reference's cell-by-cell trim, behind the window
+                    for (j = beg0 + 4; j < end0 && CELL16(j) == 0; j++) {}
+                    base = bl = j < end0 ? j : end0;
+                }
+                j = end0 - tz;
+                if (__builtin_expect(tz == 4, 0)) for (; j >= base && CELL16(j) == 0; j--) {}
+                const int jlz = j > base - 1 ? j : base - 1;               // the zero trim's last live stored cell (base - 1: none)
+                const int endz = jlz + 2 < qlen ? jlz + 2 : qlen;
+                beg = bl < endz ? bl : endz;
+                int jl = jlz;
+                if constexpr (SO) {
+                    dropped = dropped || beg > base;                       // (cell `base` is live)
+                    // Right edge: jn = where the prune stops, never left of beg - 1 and, with tz == 4, never left of jlz.  The
+                    // dropped cells jn + 1 .. jlz lie in y's window and are set to zero with 16-bit stores (nothing waits for
+                    // them; no word write-back: with end0 <= 3 the edge words are clamped duplicates).  With end0 >= 3 all four
+                    // cells of the window are the lane's own, and the four stores are unconditional: every cell right of the new
+                    // jl gets zero -- the dropped ones, and those the zero trim found zero already -- and the others get the value
+                    // they hold.  Only a band that ends left of column 3 takes the predicated form.
+                    int jn = end0 - tp;
+                    jn = jn > beg - 1 ? jn : beg - 1;
+                    dropped = dropped || jn < jlz;
+                    jl = jn < jlz ? jn : jlz;
+                    if (__builtin_expect(end0 >= 3, 1)) {
+                        const int nz = end0 - jl;                          // >= 0; cells of the window to clear, from the top
+                        const uint64_t yz = nz >= 4 ? 0ull : y & (~0ull >> (16 * nz));
+                        uint8_t *const a0 = CB + (end0 >> 1) * 256 + (end0 & 1) * 2;          // cell end0; cell end0 - 2 is 256 bytes below
+                        const int d1 = (end0 & 1) ? 2 : 254;                                  // cell end0 - 1 (and end0 - 3 below end0 - 2)
+                        *reinterpret_cast<uint16_t *>(a0) = (uint16_t)(yz >> 48);
+                        *reinterpret_cast<uint16_t *>(a0 - d1) = (uint16_t)(yz >> 32);
+                        *reinterpret_cast<uint16_t *>(a0 - 256) = (uint16_t)(yz >> 16);
+                        *reinterpret_cast<uint16_t *>(a0 - 256 - d1) = (uint16_t)yz;
+                    } else if (jn < jlz) {
+#pragma unroll
+                        for (int k = 0; k < 3; k++) {                      // (end0 <= 2)
+                            const int cj = end0 - k;                       // > jn >= -1
+                            if (cj > jn && cj <= jlz) CELL16(cj) = 0;
+                        }
+                    }
+                }
+                end = jl + 2 < qlen ? jl + 2 : qlen;
+            }
+            if (try_exit && !stop) {
+                int bound = stale_pot;
+                if (beg == 0) bound = max(bound, edge_pot);
                 if (bound <= best) {
                     // pot() of columns 2p (low half) and 2p + 1 (high half) of every pair word that holds a cell of [beg, end];
                     // the halves outside the band are masked to Hd = 0.  All halves stay below 2^15: Hd <= 255,
@@ -906,14 +947,15 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     }
                     bound = max(bound, max((int)(acc & 0xffffu), (int)(acc >> 16)));
                 }
-                if (bound <= best) break;
+                stop = bound <= best;
             }
+            if (stop) break;
         }
-        if (!abandon) break;
+        if (!SO || !abandon) break;
         prune = false;
       }
         score_out[id] = best;
-        if (result_out) {
+        if constexpr (!SO) {
             gab_bsw_result r;
             r.score = best; r.qle = best_j + 1; r.tle = best_i + 1;
             r.gtle = g_i + 1; r.gscore = gscore; r.max_off = max_off;
@@ -924,6 +966,14 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
 #undef QPAIR
     for (int o = 32; o > 0; o >>= 1) cells += __shfl_xor(cells, o);
     if (lane == 0 && cells) atomicAdd(&st->cells, cells);
+}
+
+// the eight instantiations of bsw_dp8
+using BswDp8Fn = void (*)(BswIO, BswConst, const BswRec *, int64_t, int64_t, int, int32_t *, gab_bsw_result *, BswStats *);
+template <bool SYM, bool MS1> BswDp8Fn bsw_dp8_pick(bool so) { return so ? bsw_dp8<SYM, MS1, true> : bsw_dp8<SYM, MS1, false>; }
+BswDp8Fn bsw_dp8_kernel(bool sym, bool ms1, bool so) {
+    return sym ? (ms1 ? bsw_dp8_pick<true, true>(so) : bsw_dp8_pick<true, false>(so))
+               : (ms1 ? bsw_dp8_pick<false, true>(so) : bsw_dp8_pick<false, false>(so));
 }
 
 }  // namespace
@@ -986,13 +1036,13 @@ extern "C" int gab_bsw_create(const gab_bsw_params *p, int device, gab_bsw **out
     if (!aux_ok) { gab_set_error("gab_bsw_create: stream / event creation failed"); delete h; return GAB_EDEVICE; }
     // the 256-base class needs more than the default 64 KiB of dynamic LDS
     if (hipFuncSetAttribute((const void *)bsw_dp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bsw_dp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bsw_dp8<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bsw_dp8<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bsw_dp8<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bsw_dp8<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess) {
+        hipFuncSetAttribute((const void *)bsw_dp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
         gab_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); delete h; return GAB_EDEVICE;
     }
+    for (int k = 0; k < 8; k++)
+        if (hipFuncSetAttribute((const void *)bsw_dp8_kernel(k & 4, k & 2, k & 1), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess) {
+            gab_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); delete h; return GAB_EDEVICE;
+        }
     if (hipHostMalloc((void **)&h->h_qstart, sizeof(uint32_t) * (kQBuckets + 1)) != hipSuccess ||
         hipHostMalloc((void **)&h->h_stats, sizeof(BswStats)) != hipSuccess) {
         gab_set_error("hipHostMalloc failed"); delete h; return GAB_ENOMEM;
@@ -1118,7 +1168,7 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
             // qcap / 2 + 1 rows of cells, the nibble rows (at least one) and one spare row: the kernel reads up to pair word
             // qlen / 2 + 2 (row start, band trimming, the row maximum's candidates), which this layout holds for every qcap >= qlen
             const size_t lds8 = sizeof(uint32_t) * 64 * ((size_t)(qcap + 2) / 2 + ((size_t)(qcap + 1) / 2 + 3) / 4 + 1);
-            auto kern = sym ? (ms1 ? bsw_dp8<true, true> : bsw_dp8<true, false>) : (ms1 ? bsw_dp8<false, true> : bsw_dp8<false, false>);
+            auto kern = bsw_dp8_kernel(sym, ms1, result_out == nullptr);      // (score-only is a template argument of bsw_dp8)
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds8, s, io, h->cst, d_recs, kb, ke, qcap,
                                score_out, result_out, d_stats);
             continue;

@@ -126,6 +126,38 @@ def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, w
     return (score, rows, cells, pass_cells, redo) if restarts else (score, rows, cells, pass_cells)
 
 
+BSW_TRACE_FLAGS = {"lz4": 1, "tz4": 2, "left_drop": 4, "right_drop": 8, "bound_pass": 16, "zdrop_guard": 32, "right_edge_guard": 64,
+                   "zero_row_guard": 128}
+
+
+def bsw_exit_trace(batch, params, early_exit=True, prune=True, rule="default"):
+    """bsw_exit_model with the per-row trace of tools/gen/bsw_exit_model.c's gab_bsw_exit_trace -> (score, rows, cells, pass_cells,
+    restarted, off, beg, end, flags, drops): pair k's swept rows, an abandoned pass first, are beg / end / flags / drops[off[k]:off[k + 1]]
+    -- the band [beg, end) the row's cells were computed over (int16), the BSW_TRACE_FLAGS bits of the per-row paths it takes (uint8;
+    a guard's bit is set on the row that abandons the pass) and the cells the left prune moved over | the right prune zeroed << 4"""
+    n = batch.n
+    sel = BSW_PRUNE_RULES[rule] if prune else 0
+    room = batch.len1.astype(np.int64)
+    for _ in range(2):                                  # a pair that restarts needs up to 2 * len1 rows: second round
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(room, out=off[1:])
+        score = np.zeros(n, np.int32); rows = np.zeros(n, np.int32); cells = np.zeros(n, np.int64); pass_cells = np.zeros(n, np.int64)
+        redo = np.zeros(n, np.int32); nrows = np.zeros(n, np.int32)
+        beg = np.zeros(int(off[-1]), np.int16); end = np.zeros(int(off[-1]), np.int16); flags = np.zeros(int(off[-1]), np.uint8)
+        drops = np.zeros(int(off[-1]), np.uint8)
+        lib().gab_bsw_exit_trace(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
+                                 _p(batch.len2), _p(batch.h0), C.c_int64(n), C.c_int(1 if early_exit else 0), C.c_int(sel),
+                                 _p(score), _p(rows), _p(cells), _p(pass_cells), _p(redo), _p(off), _p(nrows), _p(beg), _p(end), _p(flags), _p(drops))
+        if (nrows <= room).all():
+            break
+        room = np.where(nrows > room, 2 * batch.len1.astype(np.int64), room)
+    # compact: keep the rows that were swept
+    keep = (np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], room)) < np.repeat(nrows.astype(np.int64), room)
+    noff = np.zeros(n + 1, np.int64)
+    np.cumsum(nrows, out=noff[1:])
+    return score, rows, cells, pass_cells, redo, noff, beg[keep], end[keep], flags[keep], drops[keep]
+
+
 def bsw_rowmax_model(batch, params, resolve=True):
     """CPU model of the 8-bit bsw kernel's row maximum (tools/gen/bsw_rowmax_model.c): one key per group of four columns, exact keys
     for the edge cells, the column resolved after the row -> (int32 [n, 6] (score, qle, tle, gtle, gscore, max_off), the oracle's

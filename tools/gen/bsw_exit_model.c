@@ -56,9 +56,22 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
  * (left prune uncapped, no right prune);  5 left prune capped, no right prune;  6 left prune uncapped, right prune.
  * TEST-ONLY wrong rules, the negative controls of tests/test_bsw_left_prune.py and tests/test_bsw_right_prune.py:
  * 2 is rule 1 with the left potential's columns short by two, 4 is rule 1 with the right potential's columns short by two. */
+/* Row trace (gab_bsw_exit_trace below; NULL for the other entry points): per swept row of every pass, the abandoned one included,
+ * the [beg, end) the row was swept with and which of the kernels' per-row paths the row takes. */
+enum { TR_LZ4 = 1,        /* the left zero trim ran past its four-cell window */
+       TR_TZ4 = 2,        /* the right one did */
+       TR_LDROP = 4,      /* the left prune dropped a live cell */
+       TR_RDROP = 8,      /* the right prune did */
+       TR_BOUND = 16,     /* the exit's bound pass ran */
+       TR_ZGUARD = 32,    /* the row abandoned the pass: z-drop guard */
+       TR_RGUARD = 64,    /*                             right-edge guard */
+       TR_ZROW = 128 };   /*                             zero-row guard */
+typedef struct { int16_t *beg, *end; uint8_t *flags, *drops; int64_t cap, n; } row_trace;   /* drops: live and zero cells the left prune
+                                                                                             * moved over beyond the zero trim | the right one's << 4 */
+
 static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0,
                       int early_exit, int prune, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells,
-                      int64_t *pass_cells, int32_t *restarted) {
+                      int64_t *pass_cells, int32_t *restarted, row_trace *tr) {
     const int oe_del = p->o_del + p->e_del, oe_ins = p->o_ins + p->e_ins;
     const int e_del = p->e_del, e_ins = p->e_ins;
     int64_t ncell = 0, npass = 0;
@@ -124,6 +137,11 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
             }
             ncell += (end > beg) ? end - beg : 0;
             Hd[end] = hleft; Ev[end] = 0;
+            uint8_t *trf = NULL;
+            if (tr) {
+                if (tr->n < tr->cap) { tr->beg[tr->n] = (int16_t)beg; tr->end[tr->n] = (int16_t)end; tr->flags[tr->n] = 0; tr->drops[tr->n] = 0; trf = &tr->flags[tr->n]; }
+                tr->n++;
+            }
             if (rowmax == 0) {
                 /* zero-row guard: a pair that has dropped a live cell cannot tell whether the reference's row is zero too; while it
                  * still holds column 0 and this row's left edge (stored cell 0, the diagonal of cell (i + 1, 0)) can reach `best`,
@@ -132,6 +150,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                     int hb = h0 - p->o_del - e_del * (i + 1);
                     if (hb > 0 && hb + max_sc * (R < qlen ? R : qlen) > best) abandon = 1;
                 }
+                if (trf && abandon) *trf |= TR_ZROW;
                 i++; break;
             }
             int try_exit = 0;
@@ -139,7 +158,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 best = rowmax; best_i = i; best_j = rowmax_j;
             } else {
                 if (p->zdrop > 0) {
-                    if (dropped && rowmax < best - p->zdrop) { abandon = 1; i++; break; }
+                    if (dropped && rowmax < best - p->zdrop) { abandon = 1; if (trf) *trf |= TR_ZGUARD; i++; break; }
                     int di = i - best_i, dj = rowmax_j - best_j;
                     if (di > dj) {
                         if (best - rowmax - (di - dj) * e_del > p->zdrop) { i++; break; }
@@ -154,13 +173,14 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
              * reach further right than a pruned pair's, carries it on */
             if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins) {
                 int cl = qlen - end - 1;
-                if (hleft - e_ins + max_sc * (R < cl ? R : cl) > best) { abandon = 1; i++; break; }
+                if (hleft - e_ins + max_sc * (R < cl ? R : cl) > best) { abandon = 1; if (trf) *trf |= TR_RGUARD; i++; break; }
             }
             for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
             beg = j;
             for (j = end; j >= beg && Hd[j] == 0 && Ev[j] == 0; j--) {}
             int jl = j;
             end = j + 2 < qlen ? j + 2 : qlen;
+            if (trf) *trf |= (beg - beg0 >= 4 ? TR_LZ4 : 0) | (end0 - jl >= 4 ? TR_TZ4 : 0);
             if (do_prune && beg < end) {
                 int go = 1;
                 if (beg == 0) {                    /* (cell 0 is live here: the zero trim stopped at it) */
@@ -175,6 +195,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                         if (m && m + max_sc * (R < cl ? R : cl) > best) break;
                     }
                     if (beg > from) dropped = 1;   /* (cell `from` is live) */
+                    if (trf && beg > from) { *trf |= TR_LDROP; tr->drops[tr->n - 1] |= (uint8_t)(beg - from > 15 ? 15 : beg - from); }
                 }
             }
             if (do_prune && right_prune && jl >= beg && jl > end0 - 4) {     /* (cell jl is live: the zero trim stopped at it) */
@@ -186,6 +207,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                     Hd[jl] = 0; Ev[jl] = 0;
                 }
                 if (jl < from) { dropped = 1; end = jl + 2 < qlen ? jl + 2 : qlen; }
+                if (trf && jl < from) { *trf |= TR_RDROP; tr->drops[tr->n - 1] |= (uint8_t)((from - jl) << 4); }
             }
             if (try_exit) {
                 int bound = stale_pot;
@@ -199,6 +221,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                     if (pot > bound) bound = pot;
                 }
                 npass += end >= beg ? end - beg + 1 : 0;
+                if (trf) *trf |= TR_BOUND;
                 if (bound <= best) { i++; break; }
             }
         }
@@ -228,7 +251,38 @@ void gab_bsw_exit_model(const gab_bsw_model_params *p, const uint8_t *ref, const
                 buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
             }
             model_one(p, ql, qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], early_exit, prune, buf, buf + ql + 1, &score[k],
-                      &rows[k], &cells[k], &pass_cells[k], restarted ? &restarted[k] : NULL);
+                      &rows[k], &cells[k], &pass_cells[k], restarted ? &restarted[k] : NULL, NULL);
+        }
+        free(buf);
+    }
+}
+
+/* gab_bsw_exit_model plus the row trace: pair k's rows go to tr_beg / tr_end / tr_flags [trace_off[k], trace_off[k + 1]) in the order
+ * they were swept (an abandoned pass first), trace_rows[k] says how many there were -- rows beyond the pair's room are counted but not
+ * stored, so a caller that sees trace_rows[k] > trace_off[k + 1] - trace_off[k] calls again with more room (2 * len1[k] always holds).
+ * tr_beg / tr_end are the band [beg, end) the row's cells were computed over; tr_flags the TR_* bits above; tr_drops the cells the
+ * left prune moved the edge over (low nibble, at most 15 is recorded) and the cells the right prune zeroed (high nibble). */
+void gab_bsw_exit_trace(const gab_bsw_model_params *p, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry,
+                        const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n,
+                        int early_exit, int prune, int32_t *score, int32_t *rows, int64_t *cells, int64_t *pass_cells,
+                        int32_t *restarted, const int64_t *trace_off, int32_t *trace_rows, int16_t *tr_beg, int16_t *tr_end,
+                        uint8_t *tr_flags, uint8_t *tr_drops) {
+#pragma omp parallel
+    {
+        int cap = 512;
+        int32_t *buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
+#pragma omp for schedule(dynamic, 256)
+        for (int64_t k = 0; k < n; k++) {
+            int ql = len2[k];
+            if (ql > cap) {
+                cap = ql;
+                free(buf);
+                buf = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)(cap + 1));
+            }
+            row_trace tr = {tr_beg + trace_off[k], tr_end + trace_off[k], tr_flags + trace_off[k], tr_drops + trace_off[k], trace_off[k + 1] - trace_off[k], 0};
+            model_one(p, ql, qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], early_exit, prune, buf, buf + ql + 1, &score[k],
+                      &rows[k], &cells[k], &pass_cells[k], restarted ? &restarted[k] : NULL, &tr);
+            trace_rows[k] = (int32_t)tr.n;
         }
         free(buf);
     }
