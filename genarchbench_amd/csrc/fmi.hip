@@ -59,14 +59,15 @@ struct FmiCounters {
     int32_t max_per_read;
     int32_t bad, first_bad;
     int32_t next_read;             // work queue of the seeding kernel
-    int32_t n_ovf, pad;            // reads whose SMEMs overflowed the first-round slot
+    int32_t n_ovf, n_defer;        // reads whose SMEMs overflowed the first-round slot; those of them whose pass 1 alone did (their pass 2 waits)
     int32_t wide_items, wide_cands, wide_queue, wide_pad;   // wide backward phases handed over (fmi_wide_kernel), the re-seeding candidates they find, its work queue
     uint32_t wide_top, wide_pad2;  // entries used of the hand-over list area
     unsigned long long wave_steps; // sum over waves of the steps of their longest-running lane (GAB_FMI_DEBUG)
     unsigned long long positions, spills, list_sum;   // seeding positions, those whose list outgrew LDS, sum of list lengths
+    unsigned long long ovf_sum;    // SMEMs the first round counted for the reads of n_ovf
 };
 GAB_STATIC_ATOMIC64(FmiCounters, ext_calls); GAB_STATIC_ATOMIC64(FmiCounters, rec_reads); GAB_STATIC_ATOMIC64(FmiCounters, tab_reads); GAB_STATIC_ATOMIC64(FmiCounters, total);
-GAB_STATIC_ATOMIC64(FmiCounters, wave_steps); GAB_STATIC_ATOMIC64(FmiCounters, positions); GAB_STATIC_ATOMIC64(FmiCounters, spills); GAB_STATIC_ATOMIC64(FmiCounters, list_sum);
+GAB_STATIC_ATOMIC64(FmiCounters, wave_steps); GAB_STATIC_ATOMIC64(FmiCounters, positions); GAB_STATIC_ATOMIC64(FmiCounters, spills); GAB_STATIC_ATOMIC64(FmiCounters, list_sum); GAB_STATIC_ATOMIC64(FmiCounters, ovf_sum);
 
 __device__ __forceinline__ void load_rec(const CpOcc *p, int64_t (&cnt)[4], uint64_t (&bits)[4]) {
     const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(p);
@@ -219,12 +220,16 @@ enum FmiState : int {
 // LDSQ: the lane's current read sits in LDS as 4-bit codes ([word of 8 bases][lane], conflict-free), so stepping
 // along the read costs no global round trip; used whenever the read length bound fits (stride <= kLdsQMax).
 constexpr int kLdsQMax = 256;
-template <bool LDSQ>
+// SECOND: a round over the reads that overflowed their first-round slot (ids), with slots that hold all of pass 1.  The first round
+// has counted everything it ran; what it did not run is pass 2 of a read whose pass-1 records alone exceeded the slot (pass 2 reads
+// them back from there): the first round marks those reads in defer[], and a SECOND launch keeps the counts of exactly that --
+// pass 2 of the marked reads -- by snapshot and restore at the pass transitions, so the extension site itself is the same code.
+template <bool LDSQ, bool SECOND>
 __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *__restrict__ enc, int32_t stride,
                                                       const int32_t *__restrict__ len_arr, int64_t first, int32_t nbatch,
                                                       int min_seed_len, PrevRec *prev, int prev_cap, OutRec *out_all, int cap,
                                                       int32_t *counts, FmiCounters *ct, int lds_entries, int64_t enc_bytes, int passes,
-                                                      int narrow_lists, const int32_t *__restrict__ ids, FmiWide wide) {
+                                                      int narrow_lists, const int32_t *__restrict__ ids, FmiWide wide, uint8_t *defer) {
     // dynamic LDS (LDSQ only): [ (stride + 7) / 8 words of read codes ][ lds_entries list entries ]  x 64 lanes; a list entry
     // is 16 bytes (k, l, s < 2^40, n < 256 packed), or -- narrow_lists, for indexes below 2^32 rows -- three dword planes
     // and a byte plane = 13 bytes, which is two more waves per CU at 12 entries
@@ -353,6 +358,10 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
     // in that state instead of once per sub-transition.
     unsigned long long steps = 0;
     unsigned dbg_pos = 0, dbg_spill = 0, dbg_list = 0;
+    uint32_t k_calls = 0, k_recs = 0, k_tabs = 0, k_pos = 0, k_spill = 0, k_list = 0;      // SECOND: what this lane keeps of its counts
+    bool deferred = false;
+    auto keep_counts = [&]() { k_calls = calls; k_recs = recs; k_tabs = tabs; k_pos = dbg_pos; k_spill = dbg_spill; k_list = dbg_list; };
+    auto drop_counts = [&]() { calls = k_calls; recs = k_recs; tabs = k_tabs; dbg_pos = k_pos; dbg_spill = k_spill; dbg_list = k_list; };
     while (state != ST_DONE) {
         steps++;
         bool need = false;
@@ -383,6 +392,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
             if (pass == 1) { x = next_x; state = ST_P1_NEXT; } else state = ST_P2_NEXT;
         }
         if (state == ST_READ_DONE) {
+            if (SECOND) drop_counts();                       // (pass 3 ran in the first round)
             counts[t] = nout;
             tot += (unsigned long long)(nout - nout0); mx = nout > mx ? nout : mx;
             state = ST_NEW_READ;
@@ -411,6 +421,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                 q = enc + r * (int64_t)stride; len = len_arr[r];
                 out = out_all + (int64_t)idx * cap;
                 x = 0; min_intv = 1; p2q0 = 0; p2q1 = 0; p2n = 0;
+                if (SECOND) deferred = defer[t] != 0;
                 if (passes & 1) { nout = 0; pass = 1; state = ST_P1_NEXT; }
                 else { nout = counts[t]; pass = 3; state = ST_P3_START; }        // appends to what passes 1 and 2 found
                 nout0 = nout;
@@ -445,7 +456,14 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
         }
         if (state == ST_P1_NEXT) {                           // getSMEMsAllPosOneThread loop, FMI_search.cpp:672-724
             if (x < len) state = ST_START_POS;
-            else { pass = 2; n1 = nout; jrec = 0; state = ST_P2_NEXT; }
+            else {
+                pass = 2; n1 = nout; jrec = 0; state = ST_P2_NEXT;
+                if (SECOND) drop_counts();                   // (pass 1 ran in the first round)
+                else {                                       // pass 2 needs all of pass 1 in the slot: else it waits for the second round
+                    defer[t] = n1 > cap ? 1 : 0;
+                    if (n1 > cap) atomicAdd(&ct->n_defer, 1);
+                }
+            }
         }
         if (state == ST_P2_NEXT) {                           // re-seeding, fmi.cpp:300-324
             bool started = false;
@@ -468,6 +486,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                     }
                 }
             }
+            if (SECOND && !started) { if (deferred) keep_counts(); else drop_counts(); }      // pass 2 of a marked read is counted here
             if (started) state = ST_START_POS;
             else if (passes & 2) { pass = 3; x = 0; state = ST_P3_START; }
             else state = ST_READ_DONE;                       // pass 3 runs as its own launch (next step)
@@ -640,7 +659,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
                                                       int64_t first, const FmiWideItem *__restrict__ items, const int32_t *__restrict__ n_items_dev,
                                                       int32_t items_cap, const uint4 *__restrict__ lists_in, FmiWideItem *__restrict__ cands,
                                                       int32_t *n_cands_dev, int32_t cands_cap, OutRec *__restrict__ out_all, int cap, int32_t *counts,
-                                                      FmiCounters *ct, int min_seed_len) {
+                                                      FmiCounters *ct, int min_seed_len, const uint8_t *__restrict__ defer) {
     // per group ONE list of LL entries: a step reads sixteen entries and then writes its survivors at ranks that are not above
     // the first of them, so the column's list is compacted in place
     extern __shared__ uint4 lst_all[];
@@ -653,7 +672,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
     int mx = 0;
     // group-uniform state (every lane of the group holds the same values)
     int st = W_NEW, t = 0, len = 0, j = 0, a = 4, a_next = 4, nprev = 0, ncur = 0, p0 = 0;
-    bool pass1 = false, first_phase = true, have_k = false;
+    bool pass1 = false, first_phase = true, have_k = false, deferred = false;
     uint32_t cur_m = 0;
     int64_t min_intv = 1, last_so = 0;
     const uint8_t *rbase = enc;
@@ -665,7 +684,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
         const int slot = atomicAdd(&counts[t], 1);
         if (slot < cap) { OutRec o; o.m = m; o.n = n; o.k = k; o.l = l; o.s = sv; out_all[(int64_t)t * cap + slot] = o; }
         tot++; mx = slot + 1 > mx ? slot + 1 : mx;
-        if (pass1 && cands && (int)(n + 1 - m) >= split_len && sv <= 10) {
+        if (pass1 && cands && !deferred && (int)(n + 1 - m) >= split_len && sv <= 10) {      // (deferred: the read's whole pass 2 runs in the second round)
             const int ci = atomicAdd(n_cands_dev, 1);
             if (ci < cands_cap) {
                 FmiWideItem c; c.t = (uint32_t)t; c.jm = ((n + 1 + m) >> 1) | (uint32_t)(sv + 1) << 16; c.off = c.n = c.cur_m = 0; c.kind = 1; c.pad[0] = c.pad[1] = 0;
@@ -691,6 +710,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
                     a_next = 4;
                     if (w.kind == 0) {
                         pass1 = (w.jm >> 31) != 0;
+                        deferred = pass1 && cands && defer[t] != 0;
                         j = (int)(w.jm & 0xffffu) - 1; cur_m = w.cur_m; nprev = (int)w.n;
                         for (int v = gl; v < nprev; v += 16) lst_all[g * LL + (v)] = lists_in[w.off + (uint32_t)v];
                         a = j >= 0 ? (int)rbase[j] : 4;
@@ -885,9 +905,10 @@ __global__ __launch_bounds__(256) void fmi_compact(const int32_t *counts, int32_
 }
 // The reads of a batch whose SMEMs did not fit the first-round slot (a handful of low-complexity reads among millions):
 // their numbers in batch order, for a second round of the seeding kernel over them alone with slots of the exact size.
-__global__ __launch_bounds__(256) void fmi_list_overflowed(const int32_t *counts, int32_t n, int cap, int32_t *ids, int32_t *n_ids) {
+__global__ __launch_bounds__(256) void fmi_list_overflowed(const int32_t *counts, int32_t n, int cap, int32_t *ids, int32_t *n_ids,
+                                                           unsigned long long *sum) {
     const int32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t < n && counts[t] > cap) ids[atomicAdd(n_ids, 1)] = t;
+    if (t < n && counts[t] > cap) { ids[atomicAdd(n_ids, 1)] = t; atomicAdd(sum, (unsigned long long)counts[t]); }
 }
 __global__ __launch_bounds__(256) void fmi_compact_overflowed(const int32_t *counts, const int32_t *ids, int32_t n_ids, const OutRec *slots,
                                                               int cap, int64_t first, const int64_t *read_off, gab_smem *out) {
@@ -1052,6 +1073,7 @@ struct gab_fmi {
     bool have_stats = false;
     int64_t ext_calls = 0, rec_reads = 0, nsmem = 0;
     float kernel_ms = 0;
+    int64_t paths[GAB_FMI_PATHS] = {0};        // gab_fmi_last_paths: summed over the batches of the last call
 };
 
 static int fmi_new_handle(int device, gab_fmi **out) {
@@ -1227,12 +1249,13 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
         GAB_HIP(hipGetDeviceProperties(&prop, h->device));
         n_cu = prop.multiProcessorCount;
         if (ldsq) {
-            GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<true>, 64, lds_bytes));
-            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu_p3, fmi_seed_kernel<true>, 64, lds_bytes_p3));
+            GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<true, false>, 64, lds_bytes));
+            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu_p3, fmi_seed_kernel<true, false>, 64, lds_bytes_p3));
             GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wide_occ, fmi_wide_kernel, 64, wide_lds));
             if (wide_occ < 1) wide_occ = 1;
-        } else GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<false>, 64, 0));
+        } else GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<false, false>, 64, 0));
         GAB_CHECK(waves_per_cu > 0, "gab_fmi_seed_device: the seeding kernel does not fit a CU (stride %d)", stride);
         // the per-lane spill area is stride x 32 B x 64 lanes per resident wave: long reads (no LDS lists: every list entry
         // lives there) run on fewer waves rather than on tens of GB of scratch
@@ -1247,7 +1270,8 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     B = gab_ceil_div(nreads, gab_ceil_div(nreads, B));       // equal batches: no short last one
     const int64_t nb_blocks = gab_ceil_div(B, 256);
     const size_t o_counts = 256, o_bs = o_counts + 4 * (size_t)B + 64;
-    rc = h->ws.reserve(o_bs + 8 * (size_t)nb_blocks + 64);
+    const size_t o_defer = ((o_bs + 7) & ~(size_t)7) + 8 * (size_t)nb_blocks + 64;      // one byte per read of the batch: pass 2 waits for the second round
+    rc = h->ws.reserve(o_defer + (size_t)B + 64);
     if (rc) return rc;
     rc = h->prev.reserve(sizeof(PrevRec) * (size_t)stride * (size_t)grid_waves * 64);
     if (rc) return rc;
@@ -1255,6 +1279,7 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     FmiCounters *d_ct = (FmiCounters *)wb;
     int32_t *d_counts = (int32_t *)(wb + o_counts);
     int64_t *d_bs = (int64_t *)(wb + ((o_bs + 7) & ~(size_t)7));
+    uint8_t *d_defer = (uint8_t *)(wb + o_defer);
 
     memset(h->h_ct, 0, sizeof(FmiCounters));
     h->h_ct->first_bad = 0x7fffffff;
@@ -1276,6 +1301,7 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     int64_t total = 0;
     unsigned long long ext_total = 0, rec_total = 0;
     float kms = 0;
+    int64_t pt[GAB_FMI_PATHS] = {0};                         // which route took what, summed over the batches (gab_fmi_last_paths)
     // one launch of the seeding kernel(s) over `count` reads of the batch at `first`: all of them (ids == nullptr, slot t for
     // read t) or the listed ones (slot i for read ids[i])
     bool handover = h->handover_env != 0;                   // wide backward phases go to fmi_wide_kernel (off for the rest of a call whose candidates outgrew their queue)
@@ -1298,29 +1324,32 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
                 if (rcw) return rcw;
                 wide = FmiWide{h->witems.as<FmiWideItem>(), h->wlists.as<uint4>(), wcap, lcap, h->handover_env > 1 ? h->handover_env : kWideMin};
             }
-            hipLaunchKernelGGL(fmi_seed_kernel<true>, dim3(seed_blocks), dim3(64), lds_bytes, s, h->ix, d_enc, stride, d_len, first,
+            const auto k12 = ids ? fmi_seed_kernel<true, true> : fmi_seed_kernel<true, false>;
+            hipLaunchKernelGGL(k12, dim3(seed_blocks), dim3(64), lds_bytes, s, h->ix, d_enc, stride, d_len, first,
                                count, min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct,
-                               lds_entries, (int64_t)nreads * stride, 1, narrow_lists, ids, wide);
+                               lds_entries, (int64_t)nreads * stride, 1, narrow_lists, ids, wide, d_defer);
             if (wide.items) {
                 // ... and are walked by groups of 16 lanes: the items, then the re-seeding candidates their pass-1 phases found
                 const int wblocks = n_cu * wide_occ;
                 hipLaunchKernelGGL(fmi_wide_kernel, dim3(wblocks), dim3(64), wide_lds, s, h->ix, d_enc, stride, d_len, first, (const FmiWideItem *)wide.items,
                                    (const int32_t *)&d_ct->wide_items, wcap, (const uint4 *)wide.lists, h->wcands.as<FmiWideItem>(), &d_ct->wide_cands, wcap,
-                                   slots, slot_cap, d_counts, d_ct, min_seed_len);
+                                   slots, slot_cap, d_counts, d_ct, min_seed_len, (const uint8_t *)d_defer);
                 GAB_HIP(hipMemsetAsync(&d_ct->wide_queue, 0, sizeof(int32_t), s));
                 hipLaunchKernelGGL(fmi_wide_kernel, dim3(wblocks), dim3(64), wide_lds, s, h->ix, d_enc, stride, d_len, first, (const FmiWideItem *)h->wcands.as<FmiWideItem>(),
                                    (const int32_t *)&d_ct->wide_cands, wcap, (const uint4 *)wide.lists, (FmiWideItem *)nullptr, (int32_t *)nullptr, 0,
-                                   slots, slot_cap, d_counts, d_ct, min_seed_len);
+                                   slots, slot_cap, d_counts, d_ct, min_seed_len, (const uint8_t *)nullptr);
             }
             GAB_HIP(hipMemsetAsync(&d_ct->next_read, 0, sizeof(int32_t), s));
             const int p3_blocks = (int)std::min<int64_t>((int64_t)n_cu * waves_per_cu_p3, gab_ceil_div((int64_t)count, 64));
-            hipLaunchKernelGGL(fmi_seed_kernel<true>, dim3(p3_blocks), dim3(64), lds_bytes_p3, s, h->ix, d_enc, stride, d_len, first,
+            hipLaunchKernelGGL(k12, dim3(p3_blocks), dim3(64), lds_bytes_p3, s, h->ix, d_enc, stride, d_len, first,
                                count, min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct,
-                               0, (int64_t)nreads * stride, 2, narrow_lists, ids, FmiWide{nullptr, nullptr, 0, 0, 0});
-        } else
-            hipLaunchKernelGGL(fmi_seed_kernel<false>, dim3(seed_blocks), dim3(64), 0, s, h->ix, d_enc, stride, d_len, first, count,
+                               0, (int64_t)nreads * stride, 2, narrow_lists, ids, FmiWide{nullptr, nullptr, 0, 0, 0}, d_defer);
+        } else {
+            const auto k123 = ids ? fmi_seed_kernel<false, true> : fmi_seed_kernel<false, false>;
+            hipLaunchKernelGGL(k123, dim3(seed_blocks), dim3(64), 0, s, h->ix, d_enc, stride, d_len, first, count,
                                min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct, 0,
-                               (int64_t)nreads * stride, 3, 0, ids, FmiWide{nullptr, nullptr, 0, 0, 0});
+                               (int64_t)nreads * stride, 3, 0, ids, FmiWide{nullptr, nullptr, 0, 0, 0}, d_defer);
+        }
         hipLaunchKernelGGL(fmi_sort_slots, dim3((unsigned)gab_ceil_div((int64_t)count, 256)), dim3(256), 0, s, slots, slot_cap, d_counts, count, ids);
         GAB_HIP(hipGetLastError());
         (void)nb;
@@ -1333,7 +1362,7 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
         rc = h->slots.reserve(sizeof(OutRec) * (size_t)cap * (size_t)nb);
         if (rc) return rc;
         for (;;) {                                            // twice only when the handed-over phases found more candidates than their queue holds
-            h->h_ct->ext_calls = 0; h->h_ct->rec_reads = 0; h->h_ct->tab_reads = 0; h->h_ct->total = 0; h->h_ct->max_per_read = 0; h->h_ct->next_read = 0; h->h_ct->n_ovf = 0; h->h_ct->wide_items = h->h_ct->wide_cands = h->h_ct->wide_queue = 0; h->h_ct->wide_top = 0; h->h_ct->wave_steps = 0; h->h_ct->positions = h->h_ct->spills = h->h_ct->list_sum = 0;
+            h->h_ct->ext_calls = 0; h->h_ct->rec_reads = 0; h->h_ct->tab_reads = 0; h->h_ct->total = 0; h->h_ct->max_per_read = 0; h->h_ct->next_read = 0; h->h_ct->n_ovf = 0; h->h_ct->n_defer = 0; h->h_ct->ovf_sum = 0; h->h_ct->wide_items = h->h_ct->wide_cands = h->h_ct->wide_queue = 0; h->h_ct->wide_top = 0; h->h_ct->wave_steps = 0; h->h_ct->positions = h->h_ct->spills = h->h_ct->list_sum = 0;
             GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(FmiCounters), hipMemcpyHostToDevice, s));
             GAB_HIP(hipEventRecord(h->ev[0], s));
             rc = seed(first, nb, nb, nullptr, h->slots.as<OutRec>(), cap, &seed_blocks_dbg);
@@ -1347,21 +1376,83 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
             GAB_HIP(hipEventElapsedTime(&lost, h->ev[0], h->ev[1]));
             kms += lost;
             handover = false;
+            pt[GAB_FMI_PATH_RERUNS]++;
         }
-        const int over_cap = h->h_ct->max_per_read > cap ? h->h_ct->max_per_read : 0;   // the counters of THIS round are the batch's
+        int over_cap = h->h_ct->max_per_read > cap ? h->h_ct->max_per_read : 0;   // the counters of THIS round are the batch's
         float ms = 0;
         GAB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
         kms += ms;
-        ext_total += h->h_ct->ext_calls + h->h_ct->tab_reads; rec_total += h->h_ct->rec_reads;
+        FmiCounters c = *h->h_ct;                             // (a copy: the pinned one is read into again below)
+        int32_t n_ovf = 0;
+        int32_t *d_ids = nullptr;
+        int64_t round = 0;
+        if (over_cap) {
+            // Some reads found more SMEMs than a first-round slot holds (low-complexity reads; a handful among millions of
+            // real ones): they alone run again with slots of the size the worst of them needs, in as many parts as the
+            // scratch budget asks for, and their records go to the places fmi_compact leaves open.
+            rc = h->ovf.reserve(4 * (size_t)nb + 64);
+            if (rc) return rc;
+            d_ids = h->ovf.as<int32_t>();
+            hipLaunchKernelGGL(fmi_list_overflowed, dim3(blocks), dim3(256), 0, s, d_counts, nb, cap, d_ids, &d_ct->n_ovf, &d_ct->ovf_sum);
+            GAB_HIP(hipGetLastError());
+            GAB_HIP(hipMemcpyAsync(&n_ovf, &d_ct->n_ovf, 4, hipMemcpyDeviceToHost, s));
+            GAB_HIP(hipStreamSynchronize(s));
+            auto plan = [&]() -> int {
+                const int64_t per_round = std::max<int64_t>(1, (int64_t)(budget / (sizeof(OutRec) * (size_t)over_cap)));
+                round = std::min<int64_t>(n_ovf, per_round);
+                return h->slots2.reserve(sizeof(OutRec) * (size_t)over_cap * (size_t)round);
+            };
+            if (c.n_defer && n_ovf) {
+                // Pass 1 alone overflowed the slot of some of them, and pass 2 -- which reads the records of pass 1 back from the
+                // slot -- did not run for those (defer[]): their counts, and so the batch's total, its largest count and the offsets
+                // fmi_compact derives from the counts, are not final yet.  A launch of the second round's kernel over the overflowed
+                // reads, with slots that hold the largest count so far (all of any read's pass 1), settles the counts; it keeps the
+                // counts of what the first round left out and drops the rest, and what it writes into the slots is not used.
+                rc = plan();
+                if (rc) return rc;
+                GAB_HIP(hipMemsetAsync(&d_ct->total, 0, sizeof(d_ct->total), s));
+                GAB_HIP(hipMemsetAsync(&d_ct->max_per_read, 0, sizeof(d_ct->max_per_read), s));
+                GAB_HIP(hipEventRecord(h->ev[0], s));
+                for (int64_t i0 = 0; i0 < n_ovf; i0 += round) {
+                    rc = seed(first, nb, (int32_t)std::min<int64_t>(round, n_ovf - i0), d_ids + i0, h->slots2.as<OutRec>(), over_cap, nullptr);
+                    if (rc) return rc;
+                }
+                GAB_HIP(hipEventRecord(h->ev[1], s));
+                GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, s));
+                GAB_HIP(hipStreamSynchronize(s));
+                GAB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+                kms += ms;
+                const FmiCounters &r = *h->h_ct;              // extensions, records, positions: the first round's and what this launch kept
+                c.ext_calls = r.ext_calls; c.rec_reads = r.rec_reads; c.tab_reads = r.tab_reads;
+                c.positions = r.positions; c.spills = r.spills; c.list_sum = r.list_sum;
+                c.total = c.total - r.ovf_sum + r.total;      // the overflowed reads' SMEMs, counted again
+                c.max_per_read = std::max(c.max_per_read, r.max_per_read);
+                over_cap = c.max_per_read;
+            }
+            rc = plan();
+            if (rc) return rc;
+        }
+        ext_total += c.ext_calls + c.tab_reads; rec_total += c.rec_reads;
+        {   // the counters of the round that is kept
+            pt[GAB_FMI_PATH_BATCHES]++;
+            pt[GAB_FMI_PATH_POSITIONS] += (int64_t)c.positions; pt[GAB_FMI_PATH_LIST_SUM] += (int64_t)c.list_sum; pt[GAB_FMI_PATH_SPILLS] += (int64_t)c.spills;
+            pt[GAB_FMI_PATH_INDEX_EXT] += (int64_t)c.ext_calls; pt[GAB_FMI_PATH_TABLE_EXT] += (int64_t)c.tab_reads;
+            if (handover && ldsq) {
+                pt[GAB_FMI_PATH_WIDE_ITEMS] += std::min<int64_t>(std::max(c.wide_items, 0), wide_cap(nb));
+                pt[GAB_FMI_PATH_WIDE_ENTRIES] += (int64_t)c.wide_top; pt[GAB_FMI_PATH_WIDE_CANDS] += c.wide_cands;
+            }
+            pt[GAB_FMI_PATH_MAX_PER_READ] = std::max<int64_t>(pt[GAB_FMI_PATH_MAX_PER_READ], c.max_per_read);
+            pt[GAB_FMI_PATH_OVERFLOW_READS] += n_ovf; pt[GAB_FMI_PATH_SECOND_ROUND_PARTS] += n_ovf ? gab_ceil_div((int64_t)n_ovf, round) : 0;
+        }
         if (h->tun.fmi_debug)
             fprintf(stderr, "[gab_fmi] batch of %d reads: %d waves (%d per CU), %.3f ms, %llu index extensions + %llu table look-ups, %llu wave steps -> %.1f extensions per step; %llu positions, %llu spilled, mean list %.2f\n",
-                    nb, seed_blocks_dbg, waves_per_cu, ms, h->h_ct->ext_calls, h->h_ct->tab_reads, h->h_ct->wave_steps,
-                    (double)(h->h_ct->ext_calls + h->h_ct->tab_reads) / (double)(h->h_ct->wave_steps ? h->h_ct->wave_steps : 1), h->h_ct->positions,
-                    h->h_ct->spills, (double)h->h_ct->list_sum / (double)(h->h_ct->positions ? h->h_ct->positions : 1));
-        if (h->tun.fmi_debug && h->h_ct->wide_items)
+                    nb, seed_blocks_dbg, waves_per_cu, ms, c.ext_calls, c.tab_reads, c.wave_steps,
+                    (double)(c.ext_calls + c.tab_reads) / (double)(c.wave_steps ? c.wave_steps : 1), c.positions,
+                    c.spills, (double)c.list_sum / (double)(c.positions ? c.positions : 1));
+        if (h->tun.fmi_debug && c.wide_items)
             fprintf(stderr, "[gab_fmi]   %d wide backward phases handed over (%u list entries), %d re-seeding candidates from them\n",
-                    h->h_ct->wide_items, h->h_ct->wide_top, h->h_ct->wide_cands);
-        const int64_t add = (int64_t)h->h_ct->total;
+                    c.wide_items, c.wide_top, c.wide_cands);
+        const int64_t add = (int64_t)c.total;
         if ((size_t)(total + add) > out_cap) {
             // grow, keeping what earlier batches wrote
             size_t ncap = std::max<size_t>(out_cap * 2, (size_t)(total + add));
@@ -1373,29 +1464,15 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
             h->out.release();
             h->out = bigger;
             out_cap = ncap;
+            pt[GAB_FMI_PATH_OUT_GROWTHS]++;
         }
         hipLaunchKernelGGL(fmi_block_sums, dim3(blocks), dim3(256), 0, s, d_counts, nb, d_bs);
         hipLaunchKernelGGL(fmi_scan_blocks, dim3(1), dim3(1024), 0, s, d_bs, blocks, total);
         hipLaunchKernelGGL(fmi_compact, dim3(blocks), dim3(256), 0, s, d_counts, nb, d_bs, h->slots.as<OutRec>(), cap, first,
                            h->roff.as<int64_t>(), h->out.as<gab_smem>());
         GAB_HIP(hipGetLastError());
-        if (over_cap) {
-            // Some reads found more SMEMs than a first-round slot holds (low-complexity reads; a handful among millions of
-            // real ones): they alone run again with slots of the size the worst of them needs, in as many rounds as the
-            // scratch budget asks for, and their records go to the places fmi_compact left open.  Everything the kernel
-            // counts (extensions, records) was complete after the first round; the second round's counts are dropped.
-            rc = h->ovf.reserve(4 * (size_t)nb + 64);
-            if (rc) return rc;
-            int32_t *d_ids = h->ovf.as<int32_t>();
-            hipLaunchKernelGGL(fmi_list_overflowed, dim3(blocks), dim3(256), 0, s, d_counts, nb, cap, d_ids, &d_ct->n_ovf);
-            GAB_HIP(hipGetLastError());
-            int32_t n_ovf = 0;
-            GAB_HIP(hipMemcpyAsync(&n_ovf, &d_ct->n_ovf, 4, hipMemcpyDeviceToHost, s));
-            GAB_HIP(hipStreamSynchronize(s));
-            const int64_t per_round = std::max<int64_t>(1, (int64_t)(budget / (sizeof(OutRec) * (size_t)over_cap)));
-            const int64_t round = std::min<int64_t>(n_ovf, per_round);
-            rc = h->slots2.reserve(sizeof(OutRec) * (size_t)over_cap * (size_t)round);
-            if (rc) return rc;
+        if (n_ovf) {
+            // the second round: every count is final, and so is what the kernels counted; this round's counts are dropped
             if (h->tun.fmi_debug)
                 fprintf(stderr, "[gab_fmi] %d read(s) overflowed their %d-record slot (worst: %d records): second round in %lld part(s)\n",
                         n_ovf, cap, over_cap, (long long)gab_ceil_div((int64_t)n_ovf, round));
@@ -1421,6 +1498,10 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     *nout = total;
     if (d_out) *d_out = h->out.as<gab_smem>();
     h->ext_calls = (int64_t)ext_total; h->rec_reads = (int64_t)rec_total; h->nsmem = total; h->kernel_ms = kms;
+    pt[GAB_FMI_PATH_FORM] = ldsq ? 1 : 0; pt[GAB_FMI_PATH_LDS_ENTRIES] = lds_entries; pt[GAB_FMI_PATH_LIST_ENTRY_BYTES] = ldsq ? (narrow_lists ? 13 : 16) : 0;
+    pt[GAB_FMI_PATH_KMER_DEPTH] = ldsq ? h->ix.kmer_depth : 0;
+    pt[GAB_FMI_PATH_WIDE_MIN] = ldsq && handover ? (h->handover_env > 1 ? h->handover_env : kWideMin) : 0;   // (0 too once a batch had to run again without)
+    memcpy(h->paths, pt, sizeof pt);
     h->have_stats = true;
     return GAB_OK;
 }
@@ -1523,9 +1604,15 @@ extern "C" int gab_fmi_reserve(gab_fmi *h, int64_t max_reads, int32_t stride) {
     GAB_HIP(hipMemsetAsync(h->io.p, 0, o_len + 4 * (size_t)max_reads, s));
     const gab_smem *d_out = nullptr;
     int64_t n = 0;
-    const bool had = h->have_stats;
+    const bool had = h->have_stats;                          // the answers of gab_fmi_last_* stay those of the last real run
+    const int64_t ext_was = h->ext_calls, rec_was = h->rec_reads, nsmem_was = h->nsmem;
+    const float ms_was = h->kernel_ms;
+    int64_t paths_were[GAB_FMI_PATHS];
+    memcpy(paths_were, h->paths, sizeof paths_were);
     rc = gab_fmi_seed_device(h, h->io.as<uint8_t>(), stride, (const int32_t *)(h->io.as<char>() + o_len), max_reads, 19, &d_out, nullptr, &n, s);
     h->have_stats = had;
+    h->ext_calls = ext_was; h->rec_reads = rec_was; h->nsmem = nsmem_was; h->kernel_ms = ms_was;
+    memcpy(h->paths, paths_were, sizeof paths_were);
     if (rc) return rc;
     // the output of a real batch: ~8 records per read of 151 bases (the device array grows by doubling from 16 per read)
     return gab_warm_copy_engines(s, h->io.p, h->io.cap);
@@ -1537,6 +1624,14 @@ extern "C" int gab_fmi_last_stats(gab_fmi *h, int64_t *ext_calls, int64_t *nsmem
     if (ext_calls) *ext_calls = h->ext_calls;
     if (nsmem) *nsmem = h->nsmem;
     if (kernel_ms) *kernel_ms = h->kernel_ms;
+    return GAB_OK;
+}
+
+extern "C" int gab_fmi_last_paths(gab_fmi *h, int64_t paths[GAB_FMI_PATHS]) {
+    GAB_CHECK(h, "gab_fmi_last_paths: NULL handle");
+    GAB_CHECK(paths, "gab_fmi_last_paths: NULL argument");
+    GAB_CHECK(h->have_stats, "gab_fmi_last_paths: no completed run on this handle");
+    memcpy(paths, h->paths, sizeof h->paths);
     return GAB_OK;
 }
 

@@ -80,6 +80,16 @@ class FMI_search:
         check(lib().gab_fmi_last_records(self._h, C.byref(r)))
         return {"ext_calls": e.value, "smems": n.value, "kernel_ms": k.value, "cp_occ_records": r.value}
 
+    PATH_KEYS = ("batches", "form", "lds_entries", "list_entry_bytes", "kmer_depth", "wide_min", "positions", "list_sum", "spills",
+                 "index_ext", "table_ext", "wide_items", "wide_entries", "wide_cands", "reruns", "overflow_reads",
+                 "second_round_parts", "max_per_read", "out_growths")
+
+    def last_paths(self):
+        """which route of the seeding path took what in the last run (gab_fmi_last_paths, keys in the order of GAB_FMI_PATH_*)"""
+        v = (C.c_int64 * len(self.PATH_KEYS))()
+        check(lib().gab_fmi_last_paths(self._h, v))
+        return dict(zip(self.PATH_KEYS, (int(x) for x in v)))
+
     # ---- suffix-array look-up (FMI_search::get_sa_entries, FMI_search.cpp:1177-1196)
     def set_sa(self, sa_ms_byte, sa_ls_word):
         ms = np.ascontiguousarray(sa_ms_byte, np.int8); ls = np.ascontiguousarray(sa_ls_word, np.uint32)

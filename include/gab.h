@@ -366,6 +366,32 @@ int gab_fmi_last_stats(gab_fmi *h, int64_t *ext_calls, int64_t *nsmem, float *ke
 /* last run: 64-byte CP_OCC records the extensions fetched (GET_OCC, FMI_search.h:66-73: one when both interval
  * ends share a record, else two) -- the random index traffic of the run is 64 B x this number */
 int gab_fmi_last_records(gab_fmi *h, int64_t *cp_occ_records);
+/* last run: which route of the seeding path took what, summed over the batches of the call (of a batch that ran twice, the
+ * round that was kept).  Read from the counters the kernels keep anyway; the call allocates and copies nothing on the device.
+ * GAB_EINVAL without a completed run; gab_fmi_reserve leaves the answer as it was. */
+enum {
+    GAB_FMI_PATH_BATCHES,            /* launches of the seeding kernel over a slice of the reads */
+    GAB_FMI_PATH_FORM,               /* 1: read and interval lists in LDS (stride <= 256), 0: lists in global scratch */
+    GAB_FMI_PATH_LDS_ENTRIES,        /* entries of the LDS ring per lane (0 in the global form) */
+    GAB_FMI_PATH_LIST_ENTRY_BYTES,   /* 13 or 16 (0 in the global form) */
+    GAB_FMI_PATH_KMER_DEPTH,         /* depth of the short-pattern table the kernel used (0: none) */
+    GAB_FMI_PATH_WIDE_MIN,           /* survivors that make a backward phase wide; 0 when phases are not handed over */
+    GAB_FMI_PATH_POSITIONS,          /* seeding positions whose backward phase the seeding kernel started */
+    GAB_FMI_PATH_LIST_SUM,           /* sum of their forward list lengths */
+    GAB_FMI_PATH_SPILLS,             /* those whose list outgrew the ring */
+    GAB_FMI_PATH_INDEX_EXT,          /* extensions answered by the index; + TABLE_EXT = ext_calls of gab_fmi_last_stats */
+    GAB_FMI_PATH_TABLE_EXT,          /* extensions answered by the short-pattern table */
+    GAB_FMI_PATH_WIDE_ITEMS,         /* wide backward phases handed to the wide kernel (those that got a place) */
+    GAB_FMI_PATH_WIDE_ENTRIES,       /* list entries handed over with them */
+    GAB_FMI_PATH_WIDE_CANDS,         /* re-seeding candidates the handed-over phases found */
+    GAB_FMI_PATH_RERUNS,             /* batches run again without hand-over (candidates outgrew their queue) */
+    GAB_FMI_PATH_OVERFLOW_READS,     /* reads whose SMEMs did not fit the first-round slot */
+    GAB_FMI_PATH_SECOND_ROUND_PARTS, /* launches of the second round over them */
+    GAB_FMI_PATH_MAX_PER_READ,       /* most SMEMs of one read */
+    GAB_FMI_PATH_OUT_GROWTHS,        /* times the output array was re-allocated */
+    GAB_FMI_PATHS
+};
+int gab_fmi_last_paths(gab_fmi *h, int64_t paths[GAB_FMI_PATHS]);
 
 /* ---- fmi: suffix-array look-up -- the step BWA-MEM2 takes right after seeding:
  *     FMI_search::get_sa_entries(SMEM *smemArray, int64_t *coordArray, int32_t *coordCountArray, uint32_t count,

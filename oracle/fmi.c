@@ -232,6 +232,185 @@ int64_t oracle_fmi_batch(const oracle_fmindex *idx, const uint8_t *enc, int32_t 
 
 void oracle_fmi_release(oracle_smem *p) { free(p); }
 
+/* ---- route model: which part of genarchbench_amd/csrc/fmi.hip runs each extension ------------------------------
+ * The same three passes as oracle_fmi_read, with every seeding position, list and extension booked to the route the
+ * library takes for it (gab_fmi_last_paths).  The model describes a run whose hand-over queues and list area never
+ * fill.  Rules, read off fmi.hip:
+ *   - a pass-1 / pass-2 seeding position with a clean first base is a `position` of the seeding kernel; its list is
+ *     what the forward walk leaves (nprev after the final push); it `spills` when the list is longer than the ring
+ *     (global form: ring 0)
+ *   - LDS form with wide_min > 0: the backward phase leaves the seeding kernel after the first column that keeps
+ *     >= wide_min survivors (one item, ncur entries); a pass-1 SMEM it emits afterwards that qualifies for re-seeding
+ *     is a candidate: that position runs in the wide kernel, is no `position` and never an item
+ *   - a read whose pass-1 SMEMs written by the seeding kernel itself exceed slot_cap has its WHOLE pass 2 put off to
+ *     the second round: every re-seeding position of it is a `position` there, without hand-over, no candidates
+ *   - table extension: LDS form, seeding kernel, result pattern of at most `depth` bases (forward and pass 3:
+ *     j - x < depth; backward: n - j < depth).  The pass-3 jump answers depth - 1 such steps with one look-up and books
+ *     depth - 1: the same steps the per-step rule books, so the model needs no rule for it.
+ *   - an index extension fetches one CP_OCC record when both ends of the interval handed to backwardExt share one */
+enum { OP_POSITIONS, OP_LIST_SUM, OP_SPILLS, OP_INDEX_EXT, OP_TABLE_EXT, OP_RECORDS, OP_WIDE_ITEMS, OP_WIDE_ENTRIES,
+       OP_WIDE_CANDS, OP_SMEMS, OP_P1_OVER, OP_DEFERRED, OP_WIDEST, OP_ITEM_READS, OP_RERUN_SURE, OP_N };
+typedef struct {
+    const oracle_fmindex *x;
+    int ring, depth, wide_min, lds_form;
+    int read_items, first_p1, first_cands;   /* this read: items so far; its first item is a pass-1 phase; candidates that phase finds */
+    int64_t c[OP_N];
+} pctx;
+
+static oracle_smem p_ext(pctx *pc, oracle_smem sm, int a, int table) {
+    int64_t dummy = 0;
+    fctx fc; fc.calls = &dummy; fc.x = pc->x;
+    if (table) pc->c[OP_TABLE_EXT]++;
+    else { pc->c[OP_INDEX_EXT]++; pc->c[OP_RECORDS] += (sm.k >> 6) == ((sm.k + sm.s) >> 6) ? 1 : 2; }
+    return backward_ext(&fc, sm, a);
+}
+static oracle_smem p_fwd(pctx *pc, oracle_smem sm, int a, int table) {
+    oracle_smem t = sm;
+    t.k = sm.l; t.l = sm.k;
+    oracle_smem r = p_ext(pc, t, 3 - a, table);
+    oracle_smem o = r;
+    o.k = r.l; o.l = r.k;
+    return o;
+}
+
+/* getSMEMsOnePosOneThread at x.  in_wide: a re-seeding candidate (the wide kernel runs all of it); handover: the phase may
+ * leave the seeding kernel.  wide_flag[i] (optional) = SMEM out[i] was emitted after the hand-over point. */
+static int p_one_pos(pctx *pc, const uint8_t *q, int len, uint32_t rid, int x, int min_intv, int min_seed_len, int in_wide,
+                     int handover, oracle_smem *prev, oracle_smem *out, uint8_t *wide_flag, int64_t *nout) {
+    const oracle_fmindex *ix = pc->x;
+    const int D = (pc->lds_form && !in_wide) ? pc->depth : 0;
+    int next_x = x + 1;
+    int a = q[x];
+    if (a >= 4) return next_x;
+    oracle_smem sm;
+    sm.rid = rid; sm.m = (uint32_t)x; sm.n = (uint32_t)x; sm.pad = 0;
+    sm.k = ix->count[a]; sm.l = ix->count[3 - a]; sm.s = ix->count[a + 1] - ix->count[a];
+    int nprev = 0, j;
+    for (j = x + 1; j < len; j++) {
+        a = q[j];
+        next_x = j + 1;
+        if (a >= 4) break;
+        oracle_smem nw = p_fwd(pc, sm, a, j - x < D);
+        nw.n = (uint32_t)j;
+        prev[nprev] = sm;
+        nprev += nw.s != sm.s;
+        if (nw.s < min_intv) { next_x = j; break; }
+        sm = nw;
+    }
+    if (sm.s >= min_intv) prev[nprev++] = sm;
+    if (!in_wide) {
+        pc->c[OP_POSITIONS]++; pc->c[OP_LIST_SUM] += nprev;
+        pc->c[OP_SPILLS] += nprev > (pc->lds_form ? pc->ring : 0);
+    }
+    for (int p = 0; p < nprev / 2; p++) { oracle_smem t = prev[p]; prev[p] = prev[nprev - 1 - p]; prev[nprev - 1 - p] = t; }
+    int handed = 0, is_first = 0;                                     /* the rest of the phase runs in the wide kernel */
+    const int split_len = (int)(min_seed_len * 1.5 + .499);
+    for (j = x - 1; j >= 0; j--) {
+        int ncur = 0;
+        int curr_s = -1;
+        a = q[j];
+        if (a > 3) break;
+        int first = 1;
+        for (int p = 0; p < nprev; p++) {
+            const oracle_smem s0 = prev[p];
+            oracle_smem nw = p_ext(pc, s0, a, !handed && (int)s0.n - j < D);
+            nw.m = (uint32_t)j;
+            if (first && nw.s < min_intv && (int)(s0.n - s0.m + 1) >= min_seed_len) {
+                if (wide_flag) wide_flag[*nout] = (uint8_t)handed;
+                if (is_first && wide_flag && (int)(s0.n - s0.m + 1) >= split_len && s0.s <= 10) pc->first_cands++;
+                out[(*nout)++] = s0; first = 0;
+            } else if (nw.s >= min_intv && nw.s != curr_s) { curr_s = (int)nw.s; prev[ncur++] = nw; first = 0; }
+        }
+        nprev = ncur;
+        if (ncur == 0) break;
+        if (ncur > pc->c[OP_WIDEST]) pc->c[OP_WIDEST] = ncur;
+        if (handover && !in_wide && !handed && pc->lds_form && pc->wide_min > 0 && ncur >= pc->wide_min) {
+            handed = 1; pc->c[OP_WIDE_ITEMS]++; pc->c[OP_WIDE_ENTRIES] += ncur;
+            if (pc->read_items++ == 0) { is_first = 1; pc->first_p1 = wide_flag != NULL; }
+        }
+    }
+    if (nprev != 0) {
+        const oracle_smem s0 = prev[0];
+        if ((int)(s0.n - s0.m + 1) >= min_seed_len) {
+            if (wide_flag) wide_flag[*nout] = (uint8_t)handed;
+            if (is_first && wide_flag && (int)(s0.n - s0.m + 1) >= split_len && s0.s <= 10) pc->first_cands++;
+            out[(*nout)++] = s0;
+        }
+    }
+    return next_x;
+}
+
+static int64_t p_read(pctx *pc, const uint8_t *q, int len, uint32_t rid, int min_seed_len, int slot_cap, oracle_smem *out) {
+    oracle_smem *prev = (oracle_smem *)malloc(sizeof(oracle_smem) * (size_t)(len + 2));
+    uint8_t *wf = (uint8_t *)calloc((size_t)(3 * len + 8), 1);
+    int64_t n1 = 0, n1_seed = 0;
+    pc->read_items = pc->first_p1 = pc->first_cands = 0;
+    for (int x = 0; x < len;) x = p_one_pos(pc, q, len, rid, x, 1, min_seed_len, 0, 1, prev, out, wf, &n1);
+    for (int64_t j = 0; j < n1; j++) n1_seed += !wf[j];
+    const int deferred = n1_seed > slot_cap;
+    pc->c[OP_P1_OVER] += n1 > slot_cap; pc->c[OP_DEFERRED] += deferred;
+    const int split_len = (int)(min_seed_len * 1.5 + .499);
+    int64_t n2 = n1;
+    for (int64_t j = 0; j < n1; j++) {
+        const int start = (int)out[j].m, end = (int)out[j].n + 1;
+        if (end - start < split_len || out[j].s > 10) continue;
+        const int cand = wf[j] && !deferred;
+        pc->c[OP_WIDE_CANDS] += cand;
+        p_one_pos(pc, q, len, rid, (end + start) >> 1, (int)(out[j].s + 1), min_seed_len, cand, !deferred, prev, out, NULL, &n2);
+    }
+    /* with ONE place in the item queue the read that takes it is the first to reach an eligible phase, and that phase is the read's
+     * first: if it is a pass-1 phase that finds two candidates, they outgrow a queue of one place whichever read it was */
+    pc->c[OP_ITEM_READS] += pc->read_items > 0;
+    pc->c[OP_RERUN_SURE] += pc->read_items > 0 && pc->first_p1 && pc->first_cands >= 2 && !deferred;
+    int64_t n3 = n2;
+    const int max_intv = 20, msl = min_seed_len + 1, D = pc->lds_form ? pc->depth : 0;
+    for (int x = 0; x < len;) {
+        int next_x = x + 1;
+        int a = q[x];
+        if (a < 4) {
+            oracle_smem sm;
+            sm.rid = rid; sm.m = (uint32_t)x; sm.n = (uint32_t)x; sm.pad = 0;
+            sm.k = pc->x->count[a]; sm.l = pc->x->count[3 - a]; sm.s = pc->x->count[a + 1] - pc->x->count[a];
+            for (int j = x + 1; j < len; j++) {
+                next_x = j + 1;
+                a = q[j];
+                if (a >= 4) break;
+                sm = p_fwd(pc, sm, a, j - x < D);
+                sm.n = (uint32_t)j;
+                if (sm.s < max_intv && (int)(sm.n - sm.m + 1) >= msl) {
+                    if (sm.s > 0) out[n3++] = sm;
+                    break;
+                }
+            }
+        }
+        x = next_x;
+    }
+    free(prev); free(wf);
+    return n3;
+}
+
+/* counters[15] in the order of the enum above (OP_WIDEST: the widest backward column any phase kept; OP_ITEM_READS: reads with an
+ * item; OP_RERUN_SURE: those whose first item is a pass-1 phase that finds two candidates or more); per_read[nreads]
+ * (optional) receives every read's SMEM count.  Returns the SMEM total. */
+int64_t oracle_fmi_paths(const oracle_fmindex *idx, const uint8_t *enc, int32_t stride, const int32_t *len, int64_t nreads,
+                         int min_seed_len, int ring, int depth, int wide_min, int lds_form, int slot_cap, int64_t *counters,
+                         int32_t *per_read) {
+    pctx pc;
+    memset(&pc, 0, sizeof pc);
+    pc.x = idx; pc.ring = ring; pc.depth = depth; pc.wide_min = wide_min; pc.lds_form = lds_form;
+    int64_t total = 0;
+    for (int64_t r = 0; r < nreads; r++) {
+        oracle_smem *buf = (oracle_smem *)malloc(sizeof(oracle_smem) * (size_t)(3 * len[r] + 8));
+        const int64_t n = p_read(&pc, enc + r * (int64_t)stride, len[r], (uint32_t)r, min_seed_len, slot_cap, buf);
+        if (per_read) per_read[r] = (int32_t)n;
+        total += n;
+        free(buf);
+    }
+    pc.c[OP_SMEMS] = total;
+    memcpy(counters, pc.c, sizeof pc.c);
+    return total;
+}
+
 /* ---- suffix-array look-up ------------------------------------------------------------------ */
 /* get_sa_entry_compressed, FMI_search.cpp:1103-1175: rows that are a multiple of 8 are stored; any other row walks the
  * LF mapping (one CP_OCC record per step) until it reaches a stored row or the sentinel, counting the steps. */

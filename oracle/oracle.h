@@ -98,6 +98,14 @@ int64_t oracle_fmi_batch(const oracle_fmindex *idx, const uint8_t *enc, int32_t 
                          int64_t nreads, int min_seed_len, int threads, oracle_smem **out_p, int64_t *read_off,
                          int64_t *ext_calls);
 void oracle_fmi_release(oracle_smem *p);
+/* route model of genarchbench_amd/csrc/fmi.hip (see fmi.c): the three passes again, every position, list and extension booked
+ * to the kernel route that takes it.  counters[15]: positions, list_sum, spills, index_ext, table_ext, records, wide_items,
+ * wide_entries, wide_cands, smems, reads whose pass-1 SMEMs exceed slot_cap, reads whose pass 2 is put off to the second
+ * round, widest backward column, reads with an item, those whose first item is a pass-1 phase that finds >= 2 candidates.
+ * per_read[nreads] (optional): SMEMs of every read. */
+int64_t oracle_fmi_paths(const oracle_fmindex *idx, const uint8_t *enc, int32_t stride, const int32_t *len, int64_t nreads,
+                         int min_seed_len, int ring, int depth, int wide_min, int lds_form, int slot_cap, int64_t *counters,
+                         int32_t *per_read);
 /* suffix-array look-up of SMEM intervals (FMI_search.cpp:1103-1196): for SMEM i the rows k, k+step, ... (< k+s, at
  * most max_occ of them, step = s > max_occ ? s / max_occ : 1) are resolved with get_sa_entry_compressed; coords are
  * written back to back, coord_off[n+1] delimits them.  Returns the total, or -1 if the index has no SA arrays.

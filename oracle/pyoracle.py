@@ -170,6 +170,55 @@ def fmi(idx, reads, min_seed_len=19, threads=0, want_calls=False):
     return (arr, off, calls.value) if want_calls else (arr, off)
 
 
+FMI_PATH_KEYS = ("batches", "form", "lds_entries", "list_entry_bytes", "kmer_depth", "wide_min", "positions", "list_sum", "spills",
+                 "index_ext", "table_ext", "wide_items", "wide_entries", "wide_cands", "reruns", "overflow_reads",
+                 "second_round_parts", "max_per_read", "out_growths")
+
+
+def fmi_paths(idx, reads, min_seed_len, ring, depth, wide_min, lds_form, slot_cap=48, batch=1 << 24, scratch_bytes=6 << 30,
+              wide_lists=False, detail=False):
+    """CPU model of the routes genarchbench_amd/csrc/fmi.hip takes (oracle_fmi_paths) -> the dict FMI_search.last_paths()
+    returns for a run whose hand-over queues never fill.  ring / depth / wide_min are what the run is configured with
+    ($GAB_FMI_LDS_ENTRIES, $GAB_FMI_KMER_DEPTH, $GAB_FMI_WIDE; the global form ignores all three); batch and scratch_bytes are
+    $GAB_FMI_BATCH and $GAB_FMI_SCRATCH_MB << 20, wide_lists $GAB_FMI_WIDE_LISTS.  detail=True -> (paths, extra): extra holds
+    cp_occ_records, smems, per_read, the reads whose pass-1 SMEMs alone exceed slot_cap (p1_over_reads), those whose pass 2
+    waits for the second round (deferred_reads), the widest backward column (widest_column), the reads with an item (item_reads)
+    and those of them whose first item is a pass-1 phase that finds two candidates or more (rerun_sure_reads)."""
+    L = lib()
+    L.oracle_fmi_paths.restype = C.c_int64
+    if not lds_form:
+        ring = depth = wide_min = 0
+    ct = np.zeros(15, np.int64); per = np.zeros(max(reads.n, 1), np.int32)
+    L.oracle_fmi_paths(C.byref(idx), _p(reads.enc), C.c_int32(reads.stride), _p(reads.len), C.c_int64(reads.n), C.c_int(min_seed_len),
+                       C.c_int(ring), C.c_int(depth), C.c_int(wide_min), C.c_int(1 if lds_form else 0), C.c_int(slot_cap), _p(ct), _p(per))
+    per = per[:reads.n]
+    n = reads.n
+    # the host side of gab_fmi_seed_device: equal batches, the second round's parts, the output array's doubling
+    B = min(n, max(1024, scratch_bytes // (64 * 32)), batch)
+    B = -(-n // -(-n // B)) if n else 0
+    batches = parts = growths = ovf = total = 0
+    out_cap = max(n * 16, 1024)
+    for first in range(0, n, max(B, 1)):
+        c = per[first:first + B]
+        batches += 1
+        if total + int(c.sum()) > out_cap:
+            out_cap = max(out_cap * 2, total + int(c.sum())); growths += 1
+        total += int(c.sum())
+        n_ovf = int((c > slot_cap).sum())
+        if n_ovf:
+            per_round = max(1, scratch_bytes // (32 * int(c.max())))
+            parts += -(-n_ovf // min(n_ovf, per_round)); ovf += n_ovf
+    paths = dict(batches=batches, form=1 if lds_form else 0, lds_entries=ring, list_entry_bytes=(16 if wide_lists or idx.ref_seq_len >= 0xffffffff else 13) if lds_form else 0,
+                 kmer_depth=depth, wide_min=wide_min, positions=int(ct[0]), list_sum=int(ct[1]), spills=int(ct[2]), index_ext=int(ct[3]),
+                 table_ext=int(ct[4]), wide_items=int(ct[6]), wide_entries=int(ct[7]), wide_cands=int(ct[8]), reruns=0, overflow_reads=ovf,
+                 second_round_parts=parts, max_per_read=int(per.max()) if n else 0, out_growths=growths)
+    assert tuple(paths) == FMI_PATH_KEYS
+    if not detail:
+        return paths
+    return paths, dict(cp_occ_records=int(ct[5]), smems=int(ct[9]), per_read=per, p1_over_reads=int(ct[10]), deferred_reads=int(ct[11]),
+                       widest_column=int(ct[12]), item_reads=int(ct[13]), rerun_sure_reads=int(ct[14]))
+
+
 def fmi_sa_lookup(idx, smems, max_occ):
     """suffix-array coordinates of SMEM intervals -> (coords int64[total], coord_off int64[n+1], lf_steps)"""
     L = lib()

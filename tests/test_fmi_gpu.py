@@ -95,18 +95,20 @@ def test_repetitive_reads_overflow_slots(tmp_path):
     reads = gabgen.fmi_reads(9, ref, 3000, 300, 900)
     f = FMI_search(prefix)
     got = f.seed(reads, 10)
-    w, woff = pyoracle.fmi(pyoracle.fmi_load(prefix), reads, 10)
+    w, woff, calls = pyoracle.fmi(pyoracle.fmi_load(prefix), reads, 10, want_calls=True)
     same(got, (w, woff))
     assert np.diff(woff).max() > 48
+    assert f.last_stats()["ext_calls"] == calls
     f.close()
 
 
 @pytest.mark.parametrize("lds_entries", [None, "4", "wide"])
 def test_repetitive_short_reads_spill_lists(tmp_path, monkeypatch, lds_entries):
     """reads that fit the LDS path (<= 256 bases) on a repetitive reference: interval lists longer than the LDS ring
-    (forced with a 4-entry ring in the second variant) spill to the global scratch and are fetched one step ahead;
-    some reads also overflow their first-pass output slot.  Small indexes use the 13-byte list entries; the third variant
-    forces the 16-byte format of indexes with 2^32 rows or more"""
+    (forced with a 4-entry ring in the second variant) spill to the global scratch and are fetched one step ahead.
+    No read of this input overflows its first-pass output slot (the most SMEMs of one read is 34 of 48; slot overflow on the
+    LDS path is in tests/test_fmi_paths_gpu.py).  Small indexes use the 13-byte list entries; the third variant forces the
+    16-byte format of indexes with 2^32 rows or more"""
     from genarchbench_amd.fmi import FMI_search
     rng = np.random.default_rng(6)
     unit = rng.integers(0, 4, 29).astype(np.uint8)
@@ -114,57 +116,49 @@ def test_repetitive_short_reads_spill_lists(tmp_path, monkeypatch, lds_entries):
     idx, prefix = build(ref, tmp_path)
     reads = gabgen.fmi_reads(10, ref, 6000, 120, 250)
     w, woff, calls = pyoracle.fmi(pyoracle.fmi_load(prefix), reads, 10, want_calls=True)
-    if lds_entries is not None:
-        # the ring size is read once per process: exercise it through the C driver-style environment in a child
-        import subprocess, sys, json, os
-        code = ("import sys, numpy as np; sys.path.insert(0, %r); from tools import gabgen; from genarchbench_amd.fmi import FMI_search;"
-                "reads = gabgen.ReadBatch(np.load(%r), np.load(%r)); f = FMI_search(%r); sm, off = f.seed(reads, 10);"
-                "np.save(%r, sm); np.save(%r, off); print(f.last_stats()['ext_calls'])")
-        e, l = str(tmp_path / "enc.npy"), str(tmp_path / "len.npy")
-        np.save(e, reads.enc); np.save(l, reads.len)
-        so, oo = str(tmp_path / "sm.npy"), str(tmp_path / "off.npy")
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        r = subprocess.run([sys.executable, "-c", code % (root, e, l, prefix, so, oo)], capture_output=True, text=True,
-                           env=dict(os.environ, GAB_FMI_WIDE_LISTS="1") if lds_entries == "wide" else
-                           dict(os.environ, GAB_FMI_LDS_ENTRIES=lds_entries))
-        assert r.returncode == 0, r.stderr[-2000:]
-        got = (np.load(so), np.load(oo)); ext = int(r.stdout.split()[-1])
-    else:
-        f = FMI_search(prefix)
-        got = f.seed(reads, 10); ext = f.last_stats()["ext_calls"]
-        f.close()
+    # a handle reads its knobs when it is made: set them, then make a fresh one
+    for k in ("GAB_FMI_LDS_ENTRIES", "GAB_FMI_WIDE_LISTS"):
+        monkeypatch.delenv(k, raising=False)
+    if lds_entries == "wide":
+        monkeypatch.setenv("GAB_FMI_WIDE_LISTS", "1")
+    elif lds_entries is not None:
+        monkeypatch.setenv("GAB_FMI_LDS_ENTRIES", lds_entries)
+    f = FMI_search(prefix)
+    got = f.seed(reads, 10); ext = f.last_stats()["ext_calls"]
+    paths = f.last_paths()
+    f.close()
+    assert paths["lds_entries"] == (4 if lds_entries == "4" else 12) and paths["list_entry_bytes"] == (16 if lds_entries == "wide" else 13)
     same(got, (w, woff))
     assert ext == calls
 
 
 @pytest.mark.parametrize("wide, cap", [("0", None), ("4", None), ("4", "8"), ("2", "3")])
-def test_wide_phases_handed_over(tmp_path, wide, cap):
+def test_wide_phases_handed_over(tmp_path, monkeypatch, wide, cap):
     """backward phases whose lists stay wide leave the seeding kernel for fmi_wide_kernel (16 lanes per phase): on a repetitive
-    reference with the threshold lowered to 4 / 2 survivors nearly every phase goes that way, pass-1 phases with their re-seeding
+    reference with the threshold lowered to 4 / 2 survivors many phases go that way, pass-1 phases with their re-seeding
     candidates included; with room for 8 / 3 items and candidates the queues run full -- items stay with their lanes, a
     candidate without a place makes the library run the batch again without the hand-over; GAB_FMI_WIDE=0 is the kernel alone.
-    Same SMEMs and the same number of extensions in every variant."""
-    import subprocess, sys, os
+    Same SMEMs and the same number of extensions in every variant.  (What each variant really did: tests/test_fmi_paths_gpu.py.)"""
+    from genarchbench_amd.fmi import FMI_search
     rng = np.random.default_rng(31)
     unit = rng.integers(0, 4, 41).astype(np.uint8)
     ref = np.concatenate([np.tile(unit, 120), rng.integers(0, 4, 40000).astype(np.uint8), np.tile(unit, 60), rng.integers(0, 4, 20000).astype(np.uint8)])
     idx, prefix = build(ref, tmp_path)
     reads = gabgen.fmi_reads(32, ref, 5000, 100, 151)
     w, woff, calls = pyoracle.fmi(pyoracle.fmi_load(prefix), reads, 19, want_calls=True)
-    code = ("import sys, numpy as np; sys.path.insert(0, %r); from tools import gabgen; from genarchbench_amd.fmi import FMI_search;"
-            "reads = gabgen.ReadBatch(np.load(%r), np.load(%r)); f = FMI_search(%r); sm, off = f.seed(reads, 19);"
-            "np.save(%r, sm); np.save(%r, off); print(f.last_stats()['ext_calls'])")
-    e, l = str(tmp_path / "enc.npy"), str(tmp_path / "len.npy")
-    np.save(e, reads.enc); np.save(l, reads.len)
-    so, oo = str(tmp_path / "sm.npy"), str(tmp_path / "off.npy")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GAB_FMI_WIDE=wide)
+    # a handle reads its knobs when it is made: set them, then make a fresh one
+    monkeypatch.setenv("GAB_FMI_WIDE", wide)
+    monkeypatch.delenv("GAB_FMI_WIDE_CAP", raising=False)
     if cap:
-        env["GAB_FMI_WIDE_CAP"] = cap
-    r = subprocess.run([sys.executable, "-c", code % (root, e, l, prefix, so, oo)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
-    same((np.load(so), np.load(oo)), (w, woff))
-    assert int(r.stdout.split()[-1]) == calls
+        monkeypatch.setenv("GAB_FMI_WIDE_CAP", cap)
+    f = FMI_search(prefix)
+    got = f.seed(reads, 19)
+    ext = f.last_stats()["ext_calls"]
+    paths = f.last_paths()
+    f.close()
+    same(got, (w, woff))
+    assert ext == calls
+    assert (paths["wide_items"] == 0) == (wide == "0" or paths["reruns"] > 0) and (not cap or paths["wide_items"] <= int(cap))
 
 
 def test_all_n_and_short_reads(tmp_path):
