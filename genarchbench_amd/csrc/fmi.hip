@@ -1,29 +1,35 @@
-// fmi -- FM-index SMEM seeding (three passes per read) on gfx950.
+// fmi -- FM-index SMEM seeding (three passes per read) and the suffix-array look-up on gfx950.
 //
-// Semantics: the per-batch body of the fmi driver, /root/reference/benchmarks/fmi/fmi.cpp:288-348, on
-// BWA-MEM2's FMI_search (/root/reference/benchmarks/fmi/bwa-mem2/x86_64/src/FMI_search.cpp):
+// Semantics: the per-batch body of the fmi driver, benchmarks/fmi/fmi.cpp:288-348, on BWA-MEM2's FMI_search
+// (benchmarks/fmi/bwa-mem2/x86_64/src/FMI_search.cpp):
 //   pass 1  getSMEMsAllPosOneThread(min_intv = 1)                    :672-724 -> :496-670
 //   pass 2  getSMEMsOnePosOneThread at the midpoint of every pass-1 SMEM with length >=
 //           (int)(minSeedLen*1.5+.499) and s <= 10, min_intv = s + 1  fmi.cpp:300-324
 //   pass 3  bwtSeedStrategyAllPosOneThread(max_intv = 20, minSeedLen+1) :726-812
 //   sortSMEMs (rid, m ascending, n descending)                         :986-1022
-// every extension = backwardExt :1025-1052 = two CP_OCC look-ups (GET_OCC, FMI_search.h:66-73).
-// The index is the reference's own ".bwt.2bit.64" file (load_index :384-494), uploaded unchanged:
-// 64-byte CP_OCC records, one per 64 BWT rows.
+// every extension = backwardExt :1025-1052 = two CP_OCC look-ups (GET_OCC, FMI_search.h:66-73).  The index is the reference's
+// own ".bwt.2bit.64" file (load_index :384-494), uploaded unchanged: 64-byte CP_OCC records, one per 64 BWT rows.
+// What bounds the seeding is the rate of random index look-ups (~55 G line fills/s on MI355X whatever the record size,
+// profiles/r01_random_read_ceiling.md).  Roofline: readlen + 40 B per SMEM of streaming traffic + 64 B per CP_OCC record
+// actually fetched (counted by the kernel, gab_fmi_last_records).
 //
-// Mapping.  The reference interleaves reads in lock-step rounds inside a thread to overlap cache
-// misses; every read is nevertheless independent in all three passes.  Here one lane owns one read at a
-// time and walks the three passes as an explicit state machine (see fmi_seed_kernel), so that the whole
-// wave meets at ONE look-up site per step; reads, interval lists and the re-seeding queue stay in LDS /
-// registers, and extensions that produce a pattern of at most eight bases are answered by an L2-resident
-// table of bi-intervals instead of the index.  What bounds the kernel is the rate of random index
-// look-ups (~55 G line fills/s on MI355X whatever the record size, profiles/r01_random_read_ceiling.md).
-// A call is ONE batch of that kernel when memory allows (a batch ends with its slowest chains alone on the chip), and the
-// backward phases whose interval lists stay wide -- those chains -- are handed over to fmi_wide_kernel, a group of 16 lanes
-// per phase (FmiWideItem); pass 3 is a second launch of the state machine without list LDS.
-//
-// Roofline: readlen + 40 B per SMEM of streaming traffic + 64 B per CP_OCC record actually fetched
-// (counted by the kernel, gab_fmi_last_records).
+// Map of this file
+//   shared device pieces   occ_mask / occ_rank, pack_iv / unpack_iv (the 16-byte interval), start_interval, reseed_candidate (the
+//                          pass-2 rule), extend (THE extension: index or short-pattern table through the same loads), FmiLds (the
+//                          dynamic-LDS layout the kernels address by and the host sizes by)
+//   fmi_build_kmer_level   the short-pattern table, level by level (gab_fmi_create)
+//   fmi_seed_kernel<LDSQ, SECOND>   one lane = one read at a time, the three passes as a state machine so that the whole wave meets
+//                          at ONE look-up site per step; read, interval lists and re-seeding queue in LDS / registers (LDSQ) or
+//                          in global memory (stride > kLdsQMax); SECOND: the round over the reads that overflowed their slot
+//   fmi_wide_kernel        backward phases whose lists stay wide, handed over as FmiWideItem: 16 lanes per phase
+//   fmi_sort_slots, fmi_block_sums / fmi_scan_blocks / fmi_compact, fmi_list_overflowed / fmi_compact_overflowed, fmi_validate
+//   fmi_sa_count / fmi_sa_offsets / fmi_sa_kernel   get_sa_entries: one lane = one BWT row at a time
+//   host side              gab_fmi (FmiSharedKnobs: what a clone takes from its source), create / load / clone / destroy
+//       gab_fmi_seed_device  ->  fmi_make_plan (FmiPlan), fmi_validate_lengths, then per batch: fmi_first_round (fmi_launch_round,
+//                                again without hand-over if the candidates outgrew their queue), fmi_find_overflowed and fmi_settle
+//                                (fmi_settle_counts), fmi_append_batch, fmi_run_overflowed (the second round, in parts)
+//       gab_fmi_seed / gab_fmi_seed_into / gab_fmi_reserve  ->  fmi_stage_reads, gab_fmi_seed_device
+//       gab_fmi_sa_lookup[_device], gab_fmi_last_*
 #include "gab_internal.h"
 #include <algorithm>
 #include <new>
@@ -76,34 +82,36 @@ __device__ __forceinline__ void load_rec(const CpOcc *p, int64_t (&cnt)[4], uint
     bits[0] = c.x; bits[1] = c.y; bits[2] = d.x; bits[3] = d.y;
 }
 
-// backwardExt (FMI_search.cpp:1025-1052)
-__device__ __forceinline__ void backward_ext(const FmiIdx &ix, int64_t k, int64_t l, int64_t s, int a, int64_t &ko,
-                                             int64_t &lo, int64_t &so, unsigned long long &calls, unsigned long long &recs) {
-    calls++;
-    const int64_t sp = k, ep = k + s;
-    int64_t c_sp[4], c_ep[4]; uint64_t b_sp[4], b_ep[4];
-    const CpOcc *r_sp = ix.cp_occ + (sp >> 6), *r_ep = ix.cp_occ + (ep >> 6);
-    load_rec(r_sp, c_sp, b_sp);
-    recs += r_sp == r_ep ? 1 : 2;
-    if (r_sp == r_ep) {
-#pragma unroll
-        for (int b = 0; b < 4; b++) { c_ep[b] = c_sp[b]; b_ep[b] = b_sp[b]; }
-    } else load_rec(r_ep, c_ep, b_ep);
-    const int y_sp = (int)(sp & 63), y_ep = (int)(ep & 63);
-    const uint64_t m_sp = y_sp ? ~0ull << (64 - y_sp) : 0ull, m_ep = y_ep ? ~0ull << (64 - y_ep) : 0ull;
-    int64_t kk[4], ss[4];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const int64_t o_sp = c_sp[b] + __popcll(b_sp[b] & m_sp);
-        const int64_t o_ep = c_ep[b] + __popcll(b_ep[b] & m_ep);
-        kk[b] = ix.count[b] + o_sp;
-        ss[b] = o_ep - o_sp;
-    }
-    const int64_t sent = (k <= ix.sentinel && k + s > ix.sentinel) ? 1 : 0;
-    const int64_t l3 = l + sent, l2 = l3 + ss[3], l1 = l2 + ss[2], l0 = l1 + ss[1];
-    ko = a == 0 ? kk[0] : a == 1 ? kk[1] : a == 2 ? kk[2] : kk[3];
-    so = a == 0 ? ss[0] : a == 1 ? ss[1] : a == 2 ? ss[2] : ss[3];
-    lo = a == 0 ? l0 : a == 1 ? l1 : a == 2 ? l2 : l3;
+// Rows [64 i, 64 i + y) of a CP_OCC record as a mask over its bit vectors (first row = highest bit), and the rank of a base below
+// such a row (GET_OCC, FMI_search.h:66-73).
+__device__ __forceinline__ uint64_t occ_mask(int y) { return y ? ~0ull << (64 - y) : 0ull; }
+__device__ __forceinline__ int64_t occ_rank(int64_t cnt, uint64_t bits, uint64_t mask) { return cnt + __popcll(bits & mask); }
+
+// ---- the packed interval: k, l, s < 2^40 and n < 256 in 16 bytes (LDS list entries, the hand-over lists, the table) ----------
+__device__ __forceinline__ uint4 pack_iv(int64_t k, int64_t l, int64_t s, uint32_t n) {
+    uint4 w;
+    w.x = (uint32_t)k; w.y = (uint32_t)l; w.z = (uint32_t)s;
+    w.w = ((uint32_t)(k >> 32) & 0xffu) | ((uint32_t)(l >> 32) & 0xffu) << 8 | ((uint32_t)(s >> 32) & 0xffu) << 16 | n << 24;
+    return w;
+}
+__device__ __forceinline__ uint4 pack_iv(const PrevRec &r) { return pack_iv(r.k, r.l, r.s, (uint32_t)r.n); }
+__device__ __forceinline__ PrevRec unpack_iv(const uint4 w) {
+    PrevRec r;
+    r.k = (int64_t)((uint64_t)(w.w & 0xffu) << 32 | w.x); r.l = (int64_t)((uint64_t)((w.w >> 8) & 0xffu) << 32 | w.y);
+    r.s = (int64_t)((uint64_t)((w.w >> 16) & 0xffu) << 32 | w.z); r.n = (int64_t)(w.w >> 24);
+    return r;
+}
+// The bi-interval of the one-base pattern `a` (FMI_search.cpp:531-533).
+__device__ __forceinline__ void start_interval(const FmiIdx &ix, int a, int64_t &k, int64_t &l, int64_t &s) {
+    k = ix.count[a]; l = ix.count[3 - a]; s = ix.count[a + 1] - ix.count[a];
+}
+// Re-seeding (fmi.cpp:300-324): an SMEM [m, n] of pass 1 that is at least split_len long and has at most 10 occurrences is
+// searched again from its midpoint x with min_intv = s + 1.
+__device__ __forceinline__ int reseed_split_len(int min_seed_len) { return (int)(min_seed_len * 1.5 + .499); }
+__device__ __forceinline__ bool reseed_candidate(uint32_t m, uint32_t n, int64_t s, int split_len, uint32_t &x, int64_t &min_intv) {
+    if ((int)(n + 1 - m) < split_len || s > 10) return false;
+    x = (n + 1 + m) >> 1; min_intv = s + 1;
+    return true;
 }
 // ---- short-pattern table -------------------------------------------------------------------------------------
 // The bi-interval (k, l, s) of a pattern is a function of the pattern alone, however the search reached it, so the
@@ -115,29 +123,9 @@ __device__ __forceinline__ void backward_ext(const FmiIdx &ix, int64_t k, int64_
 // (an empty interval only ever propagates s == 0, FMI_search.cpp:1040-1051).
 constexpr int kDefaultKmerDepth = 8;      // GAB_FMI_KMER_DEPTH: 0 .. 11 (tuning)
 __device__ __forceinline__ uint32_t kmer_level_off(int len) { return (0x55555555u & ((1u << (2 * len)) - 1u)) - 1u; }
-__device__ __forceinline__ uint4 pack_iv(int64_t k, int64_t l, int64_t s, uint32_t n) {
-    uint4 w;
-    w.x = (uint32_t)k; w.y = (uint32_t)l; w.z = (uint32_t)s;
-    w.w = ((uint32_t)(k >> 32) & 0xffu) | ((uint32_t)(l >> 32) & 0xffu) << 8 | ((uint32_t)(s >> 32) & 0xffu) << 16 | n << 24;
-    return w;
-}
-__global__ __launch_bounds__(256) void fmi_build_kmer_level(FmiIdx ix, uint4 *tab, int len) {
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= (1u << (2 * len))) return;
-    int64_t k = 0, l = 0, s = 0;
-    if (len == 1) { const int a = (int)c; k = ix.count[a]; l = ix.count[3 - a]; s = ix.count[a + 1] - ix.count[a]; }
-    else {
-        const uint4 w = tab[kmer_level_off(len - 1) + (c >> 2)];          // the pattern without its first base
-        const int64_t pk = (int64_t)((uint64_t)(w.w & 0xffu) << 32 | w.x), pl = (int64_t)((uint64_t)((w.w >> 8) & 0xffu) << 32 | w.y);
-        const int64_t ps = (int64_t)((uint64_t)((w.w >> 16) & 0xffu) << 32 | w.z);
-        if (ps > 0) { unsigned long long c0 = 0, c1 = 0; backward_ext(ix, pk, pl, ps, (int)(c & 3u), k, l, s, c0, c1); }
-    }
-    if (s <= 0) k = l = s = 0;
-    tab[kmer_level_off(len) + c] = pack_iv(k, l, s, 0);
-}
-// One extension for the seeding kernel: either backwardExt on the index or, for `tlen` > 0, the table entry `tidx`.
-// Both kinds fetch through the same loads (a table entry is a quarter of a 64-byte line), so a wave with lanes of
-// both kinds still waits for memory once.
+// One extension, for every kernel: either backwardExt (FMI_search.cpp:1025-1052) on the index or, for `use_tab`, the table
+// entry `tidx`.  Both kinds fetch through the same loads (a table entry is a quarter of a 64-byte line), so a wave with lanes
+// of both kinds still waits for memory once.
 __device__ __forceinline__ void extend(const FmiIdx &ix, int64_t k, int64_t l, int64_t s, int a, bool use_tab, uint32_t tidx,
                                        bool tab_swap, int64_t &ko, int64_t &lo, int64_t &so, uint32_t &calls, uint32_t &recs,
                                        uint32_t &tabs) {
@@ -155,21 +143,18 @@ __device__ __forceinline__ void extend(const FmiIdx &ix, int64_t k, int64_t l, i
         const uint32_t e = tidx & 3u;
         const uint64_t lo64 = e == 0 ? (uint64_t)c_sp[0] : e == 1 ? (uint64_t)c_sp[2] : e == 2 ? b_sp[0] : b_sp[2];
         const uint64_t hi64 = e == 0 ? (uint64_t)c_sp[1] : e == 1 ? (uint64_t)c_sp[3] : e == 2 ? b_sp[1] : b_sp[3];
-        const uint32_t wx = (uint32_t)lo64, wy = (uint32_t)(lo64 >> 32), wz = (uint32_t)hi64, ww = (uint32_t)(hi64 >> 32);
-        const int64_t tk = (int64_t)((uint64_t)(ww & 0xffu) << 32 | wx), tl = (int64_t)((uint64_t)((ww >> 8) & 0xffu) << 32 | wy);
-        so = (int64_t)((uint64_t)((ww >> 16) & 0xffu) << 32 | wz);
-        ko = tab_swap ? tl : tk; lo = tab_swap ? tk : tl;
+        const PrevRec t = unpack_iv(make_uint4((uint32_t)lo64, (uint32_t)(lo64 >> 32), (uint32_t)hi64, (uint32_t)(hi64 >> 32)));
+        so = t.s;
+        ko = tab_swap ? t.l : t.k; lo = tab_swap ? t.k : t.l;
         return;
     }
     calls++;
     recs += r_sp == r_ep ? 1u : 2u;
-    const int y_sp = (int)(sp & 63), y_ep = (int)(ep & 63);
-    const uint64_t m_sp = y_sp ? ~0ull << (64 - y_sp) : 0ull, m_ep = y_ep ? ~0ull << (64 - y_ep) : 0ull;
+    const uint64_t m_sp = occ_mask((int)(sp & 63)), m_ep = occ_mask((int)(ep & 63));
     int64_t kk[4], ss[4];
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-        const int64_t o_sp = c_sp[b] + __popcll(b_sp[b] & m_sp);
-        const int64_t o_ep = c_ep[b] + __popcll(b_ep[b] & m_ep);
+        const int64_t o_sp = occ_rank(c_sp[b], b_sp[b], m_sp), o_ep = occ_rank(c_ep[b], b_ep[b], m_ep);
         kk[b] = ix.count[b] + o_sp;
         ss[b] = o_ep - o_sp;
     }
@@ -178,6 +163,19 @@ __device__ __forceinline__ void extend(const FmiIdx &ix, int64_t k, int64_t l, i
     ko = a == 0 ? kk[0] : a == 1 ? kk[1] : a == 2 ? kk[2] : kk[3];
     so = a == 0 ? ss[0] : a == 1 ? ss[1] : a == 2 ? ss[2] : ss[3];
     lo = a == 0 ? l0 : a == 1 ? l1 : a == 2 ? l2 : l3;
+}
+__global__ __launch_bounds__(256) void fmi_build_kmer_level(FmiIdx ix, uint4 *tab, int len) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= (1u << (2 * len))) return;
+    int64_t k = 0, l = 0, s = 0;
+    if (len == 1) start_interval(ix, (int)c, k, l, s);
+    else {
+        const PrevRec p = unpack_iv(tab[kmer_level_off(len - 1) + (c >> 2)]);      // the pattern without its first base
+        uint32_t unused = 0;
+        if (p.s > 0) extend(ix, p.k, p.l, p.s, (int)(c & 3u), false, 0u, false, k, l, s, unused, unused, unused);
+    }
+    if (s <= 0) k = l = s = 0;
+    tab[kmer_level_off(len) + c] = pack_iv(k, l, s, 0);
 }
 // ---- wide backward phases: handed over -----------------------------------------------------------------------------
 // The backward phase of a seeding position extends every entry of an interval list, column by column.  Most lists shrink to
@@ -200,6 +198,24 @@ struct FmiWideItem {            // 32 bytes
 static_assert(sizeof(FmiWideItem) == 32, "FmiWideItem must be 32 bytes");
 constexpr int kWideMin = 24;
 struct FmiWide { FmiWideItem *items; uint4 *lists; int32_t items_cap; uint32_t lists_cap; int32_t min_entries; };
+
+// ---- dynamic LDS: ONE description for the kernels that address it and the host that sizes it --------------------------------
+// fmi_seed_kernel<true, *>:  [ (stride + 7) / 8 words of read codes ][ `entries` list entries ]  x 64 lanes.  A list entry is 16
+// bytes (pack_iv), or -- `narrow`, for indexes below 2^32 rows -- three dword planes and a byte plane = 13 bytes, which is two
+// more waves per CU at 12 entries.  The pass-3 launch has no lists, only slack for nibbles_at's reads past the read.
+// fmi_wide_kernel: four groups, a list of wide_ll(stride) entries each.
+struct FmiLds {
+    int stride, entries, narrow;
+    __host__ __device__ int list_base() const { return ((stride + 7) / 8 * 64 + 3) / 4; }             // in uint4: the lists start here
+    __host__ __device__ size_t byte_plane() const { return (size_t)entries * 3 * 64 * 4; }            // narrow: bytes from the list base
+    __host__ __device__ size_t list_bytes() const {
+        return narrow ? (((size_t)entries * 64 * 13 + 15) & ~(size_t)15) : (size_t)entries * 64 * 16;
+    }
+    __host__ __device__ size_t bytes() const { return (size_t)list_base() * 16 + list_bytes(); }       // passes 1 + 2
+    __host__ __device__ size_t bytes_no_lists() const { return ((size_t)list_base() + 64) * 16; }      // pass 3
+    __host__ __device__ static int wide_ll(int stride) { return (stride + 15) & ~15; }
+    __host__ __device__ static size_t wide_bytes(int stride) { return (size_t)4 * (size_t)wide_ll(stride) * sizeof(uint4); }
+};
 
 // ---- the seeding kernel: one lane = one read at a time, as a state machine ------------------------------------
 // A straight transcription (one lane runs the three passes as nested loops) leaves ~13 % of the lanes active
@@ -230,18 +246,16 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                                                       int min_seed_len, PrevRec *prev, int prev_cap, OutRec *out_all, int cap,
                                                       int32_t *counts, FmiCounters *ct, int lds_entries, int64_t enc_bytes, int passes,
                                                       int narrow_lists, const int32_t *__restrict__ ids, FmiWide wide, uint8_t *defer) {
-    // dynamic LDS (LDSQ only): [ (stride + 7) / 8 words of read codes ][ lds_entries list entries ]  x 64 lanes; a list entry
-    // is 16 bytes (k, l, s < 2^40, n < 256 packed), or -- narrow_lists, for indexes below 2^32 rows -- three dword planes
-    // and a byte plane = 13 bytes, which is two more waves per CU at 12 entries
-    extern __shared__ uint4 lds_all[];
+    extern __shared__ uint4 lds_all[];                       // LDSQ only: see FmiLds
     const int lane = threadIdx.x;
-    uint32_t *const lq = reinterpret_cast<uint32_t *>(lds_all) + lane;
-    uint4 *const lp = lds_all + ((stride + 7) / 8 * 64 + 3) / 4 + lane;        // entry slot e at lp[e * 64]
     const int C = LDSQ ? lds_entries : 0;
+    const FmiLds lay{stride, C, narrow_lists};
+    uint32_t *const lq = reinterpret_cast<uint32_t *>(lds_all) + lane;
+    uint4 *const lp = lds_all + lay.list_base() + lane;      // entry slot e at lp[e * 64]
     const int64_t tid = (int64_t)blockIdx.x * 64 + lane;
     const int64_t pstride = (int64_t)gridDim.x * 64;
     PrevRec *const prevp = prev + tid;                       // overflow entry e of this lane at prevp[e * pstride]
-    const int split_len = (int)(min_seed_len * 1.5 + .499);
+    const int split_len = reseed_split_len(min_seed_len);
     const int msl = min_seed_len + 1;
 
     unsigned long long tot = 0;
@@ -298,15 +312,16 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
     int fslot = 0, Rslot = 0, nfwd = 0, nxt_for = -1;
     PrevRec nxt; nxt.n = nxt.k = nxt.l = nxt.s = 0;
     // narrow: field f of slot e of this lane at lw[(3 e + f) * 64], its byte at lb[e * 64] (planes behind the read codes)
-    uint4 *const list_base = lds_all + ((stride + 7) / 8 * 64 + 3) / 4;
-    uint32_t *const lw = reinterpret_cast<uint32_t *>(list_base) + lane;
-    uint8_t *const lb = reinterpret_cast<uint8_t *>(list_base) + (size_t)C * 3 * 64 * 4 + lane;
+    uint32_t *const lw = reinterpret_cast<uint32_t *>(lds_all + lay.list_base()) + lane;
+    uint8_t *const lb = reinterpret_cast<uint8_t *>(lds_all + lay.list_base()) + lay.byte_plane() + lane;
     auto lds_put = [&](int slot, const PrevRec &r) {
         if (narrow_lists) {
             lw[(3 * slot) * 64] = (uint32_t)r.k; lw[(3 * slot + 1) * 64] = (uint32_t)r.l; lw[(3 * slot + 2) * 64] = (uint32_t)r.s;
             lb[slot * 64] = (uint8_t)r.n;
             return;
         }
+        // pack_iv(r), written out: through the shared function the compiler picks another byte permute for this one site, and the
+        // hot launches lose their instruction-for-instruction match with the form they were measured in (profiles/fmi_refactor.md)
         uint4 w;
         w.x = (uint32_t)r.k; w.y = (uint32_t)r.l; w.z = (uint32_t)r.s;
         w.w = ((uint32_t)(r.k >> 32) & 0xffu) | ((uint32_t)(r.l >> 32) & 0xffu) << 8 | ((uint32_t)(r.s >> 32) & 0xffu) << 16 |
@@ -314,16 +329,13 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
         lp[slot * 64] = w;
     };
     auto lds_get = [&](int slot) -> PrevRec {
-        PrevRec r;
         if (narrow_lists) {
+            PrevRec r;
             r.k = (int64_t)lw[(3 * slot) * 64]; r.l = (int64_t)lw[(3 * slot + 1) * 64]; r.s = (int64_t)lw[(3 * slot + 2) * 64];
             r.n = (int64_t)lb[slot * 64];
             return r;
         }
-        const uint4 w = lp[slot * 64];
-        r.k = (int64_t)((uint64_t)(w.w & 0xffu) << 32 | w.x); r.l = (int64_t)((uint64_t)((w.w >> 8) & 0xffu) << 32 | w.y);
-        r.s = (int64_t)((uint64_t)((w.w >> 16) & 0xffu) << 32 | w.z); r.n = (int64_t)(w.w >> 24);
-        return r;
+        return unpack_iv(lp[slot * 64]);
     };
     auto g_fwd = [&](int i) -> PrevRec * { return prevp + (int64_t)(prev_cap - 1 - i) * pstride; };   // forward entry i, spilled
     auto list_slot = [&](int v) -> int { const int s = Rslot - v; return s < 0 ? s + C : s; };
@@ -337,8 +349,9 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
     auto emit = [&](uint32_t m, uint32_t n, int64_t k, int64_t l, int64_t s) {
         if (nout < cap) { OutRec o; o.m = m; o.n = n; o.k = k; o.l = l; o.s = s; out[nout] = o; }
         nout++;
-        if (LDSQ && pass == 1 && (int)(n + 1 - m) >= split_len && s <= 10) {
-            const uint64_t e = (uint64_t)((n + 1 + m) >> 1) | (uint64_t)(s + 1) << 8;
+        uint32_t cx; int64_t cmin;
+        if (LDSQ && pass == 1 && reseed_candidate(m, n, s, split_len, cx, cmin)) {
+            const uint64_t e = (uint64_t)cx | (uint64_t)cmin << 8;
             if (p2n < 5) p2q0 |= e << (12 * p2n); else if (p2n < kP2Max) p2q1 |= e << (12 * (p2n - 5));
             p2n++;
         }
@@ -478,7 +491,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                 } else {
                     while (jrec < n1) {
                         const OutRec o = out[jrec++];
-                        const int start = (int)o.m, end = (int)o.n + 1;
+                        const int start = (int)o.m, end = (int)o.n + 1;      // reseed_candidate(), written out: see profiles/fmi_refactor.md
                         if (end - start < split_len || o.s > 10) continue;
                         x = (end + start) >> 1; min_intv = o.s + 1;
                         started = true;
@@ -496,7 +509,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
             a = base_at(x);
             if (a >= 4) state = ST_POS_DONE;                 // (next step)
             else {
-                sm_n = x; sm_k = ix.count[a]; sm_l = ix.count[3 - a]; sm_s = ix.count[a + 1] - ix.count[a];
+                sm_n = x; start_interval(ix, a, sm_k, sm_l, sm_s);
                 nprev = 0; fslot = 0; j = x + 1;
                 state = ST_FWD_STEP;
             }
@@ -507,7 +520,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                 next_x = x + 1;
                 a = base_at(x);
                 if (a < 4) {
-                    sm_n = x; sm_k = ix.count[a]; sm_l = ix.count[3 - a]; sm_s = ix.count[a + 1] - ix.count[a];
+                    sm_n = x; start_interval(ix, a, sm_k, sm_l, sm_s);
                     j = x + 1;
                     state = ST_P3_STEP;
                     // the first D - 1 steps of the walk cannot emit (D < minSeedLen + 1) and only stop at an N or the
@@ -598,7 +611,7 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
                             if (off + (uint32_t)ncur <= wide.lists_cap && min_intv < 0x7fff) {
                                 for (int v = 0; v < ncur; v++) {
                                     const PrevRec r = v < C ? lds_get(list_slot(v)) : prevp[(int64_t)v * pstride];
-                                    wide.lists[off + (uint32_t)v] = pack_iv(r.k, r.l, r.s, (uint32_t)r.n);
+                                    wide.lists[off + (uint32_t)v] = pack_iv(r);
                                 }
                                 w.kind = 0;
                                 state = ST_POS_DONE;             // (next step) the phase is somebody else's now
@@ -621,7 +634,8 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
             } else j++;
         }
     }
-    // statistics: one atomic per wave
+    // statistics: one atomic per wave (fmi_wide_kernel ends with the same reduction of the counters both have; a shared function
+    // for them changed both kernels' code, profiles/fmi_refactor.md)
     unsigned long long c64 = calls, r64 = recs, t64 = tabs, p64 = dbg_pos, s64 = dbg_spill, l64 = dbg_list;
     for (int o = 32; o > 0; o >>= 1) {
         c64 += __shfl_xor(c64, o); tot += __shfl_xor(tot, o); r64 += __shfl_xor(r64, o); t64 += __shfl_xor(t64, o);
@@ -651,10 +665,6 @@ __global__ __launch_bounds__(64) void fmi_seed_kernel(FmiIdx ix, const uint8_t *
 // from (int64)(int)so of the previous entry with so >= min_intv (kept or not: a skipped one equals the value it was
 // compared with).  Both are ballots and lane shuffles over the sixteen entries of a step, carried from step to step.
 enum WideState : int { W_NEW, W_FWD, W_COL, W_ROUND, W_DONE };
-__device__ __forceinline__ void unpack_iv(const uint4 w, int64_t &k, int64_t &l, int64_t &s, int &n) {
-    k = (int64_t)((uint64_t)(w.w & 0xffu) << 32 | w.x); l = (int64_t)((uint64_t)((w.w >> 8) & 0xffu) << 32 | w.y);
-    s = (int64_t)((uint64_t)((w.w >> 16) & 0xffu) << 32 | w.z); n = (int)(w.w >> 24);
-}
 __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *__restrict__ enc, int32_t stride, const int32_t *__restrict__ len_arr,
                                                       int64_t first, const FmiWideItem *__restrict__ items, const int32_t *__restrict__ n_items_dev,
                                                       int32_t items_cap, const uint4 *__restrict__ lists_in, FmiWideItem *__restrict__ cands,
@@ -663,9 +673,9 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
     // per group ONE list of LL entries: a step reads sixteen entries and then writes its survivors at ranks that are not above
     // the first of them, so the column's list is compacted in place
     extern __shared__ uint4 lst_all[];
-    const int LL = (stride + 15) & ~15;
+    const int LL = FmiLds::wide_ll(stride);
     const int lane = threadIdx.x, g = lane >> 4, gl = lane & 15, lead = g * 16;
-    const int split_len = (int)(min_seed_len * 1.5 + .499);
+    const int split_len = reseed_split_len(min_seed_len);
     const int n_items = (uint32_t)*n_items_dev < (uint32_t)items_cap ? *n_items_dev : items_cap;      // (the counter as unsigned: never a negative count)
     uint32_t calls = 0, recs = 0, tabs = 0, dummy = 0;
     unsigned long long tot = 0;
@@ -684,10 +694,11 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
         const int slot = atomicAdd(&counts[t], 1);
         if (slot < cap) { OutRec o; o.m = m; o.n = n; o.k = k; o.l = l; o.s = sv; out_all[(int64_t)t * cap + slot] = o; }
         tot++; mx = slot + 1 > mx ? slot + 1 : mx;
-        if (pass1 && cands && !deferred && (int)(n + 1 - m) >= split_len && sv <= 10) {      // (deferred: the read's whole pass 2 runs in the second round)
+        uint32_t cx; int64_t cmin;
+        if (pass1 && cands && !deferred && reseed_candidate(m, n, sv, split_len, cx, cmin)) {      // (deferred: the read's whole pass 2 runs in the second round)
             const int ci = atomicAdd(n_cands_dev, 1);
             if (ci < cands_cap) {
-                FmiWideItem c; c.t = (uint32_t)t; c.jm = ((n + 1 + m) >> 1) | (uint32_t)(sv + 1) << 16; c.off = c.n = c.cur_m = 0; c.kind = 1; c.pad[0] = c.pad[1] = 0;
+                FmiWideItem c; c.t = (uint32_t)t; c.jm = cx | (uint32_t)cmin << 16; c.off = c.n = c.cur_m = 0; c.kind = 1; c.pad[0] = c.pad[1] = 0;
                 cands[ci] = c;
             }
         }
@@ -720,7 +731,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
                         x = (int)(w.jm & 0xffffu);
                         const int a0 = x < len ? (int)rbase[x] : 4;
                         if (a0 <= 3) {
-                            sm_n = x; sm_k = ix.count[a0]; sm_l = ix.count[3 - a0]; sm_s = ix.count[a0 + 1] - ix.count[a0];
+                            sm_n = x; start_interval(ix, a0, sm_k, sm_l, sm_s);
                             nprev = 0; jf = x + 1;
                             st = W_FWD;
                         }
@@ -736,9 +747,8 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
                 st = W_ROUND;
             } else {                                         // the read's start or an N: the longest entry is an SMEM
                 if (nprev != 0 && gl == 0) {
-                    int64_t k0, l0, s0; int n0;
-                    unpack_iv(lst_all[g * LL + (0)], k0, l0, s0, n0);
-                    if ((int)((int64_t)n0 - (int64_t)cur_m + 1) >= min_seed_len) emit(cur_m, (uint32_t)n0, k0, l0, s0);
+                    const PrevRec e = unpack_iv(lst_all[g * LL + (0)]);
+                    if ((int)(e.n - (int64_t)cur_m + 1) >= min_seed_len) emit(cur_m, (uint32_t)e.n, e.k, e.l, e.s);
                 }
                 st = W_NEW;
             }
@@ -748,7 +758,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
         int64_t K = 0, L = 0, S = 0; int A = 0, n0 = 0;
         if (st == W_ROUND) {
             const int p = p0 + gl;
-            if (p < nprev) { unpack_iv(lst_all[g * LL + (p)], K, L, S, n0); A = a; need = true; }
+            if (p < nprev) { const PrevRec e = unpack_iv(lst_all[g * LL + (p)]); K = e.k; L = e.l; S = e.s; n0 = (int)e.n; A = a; need = true; }
         } else if (st == W_FWD) {                            // forward loop :531-575
             if (jf >= len) fwd_end = true;
             else {
@@ -806,7 +816,7 @@ __global__ __launch_bounds__(64) void fmi_wide_kernel(FmiIdx ix, const uint8_t *
             }
         }
     }
-    unsigned long long c64 = calls, r64 = recs, t64 = tabs;
+    unsigned long long c64 = calls, r64 = recs, t64 = tabs;      // (as at the end of fmi_seed_kernel)
     for (int o = 32; o > 0; o >>= 1) {
         c64 += __shfl_xor(c64, o); r64 += __shfl_xor(r64, o); t64 += __shfl_xor(t64, o); tot += __shfl_xor(tot, o);
         const int v = __shfl_xor(mx, o); mx = v > mx ? v : mx;
@@ -877,31 +887,40 @@ __global__ __launch_bounds__(1024) void fmi_scan_blocks(int64_t *block_sums, int
         carry += total;
     }
 }
+// exclusive scan of one value per thread over a block of 256 (sh: 256 places)
+template <typename T>
+__device__ __forceinline__ T block_exscan_256(T *sh, T c) {
+    sh[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const T add = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += add;
+        __syncthreads();
+    }
+    return sh[threadIdx.x] - c;
+}
+// the c records of read `rid` from its slot to their place in the output
+__device__ __forceinline__ void store_smems(gab_smem *out, int64_t off, uint32_t rid, const OutRec *src, int c) {
+    for (int j = 0; j < c; j++) {
+        const OutRec o = src[j];
+        gab_smem g;
+        g.rid = rid; g.m = o.m; g.n = o.n; g.pad = 0; g.k = o.k; g.l = o.l; g.s = o.s;
+        out[off + j] = g;
+    }
+}
 __global__ __launch_bounds__(256) void fmi_compact(const int32_t *counts, int32_t n, const int64_t *block_off,
                                                    const OutRec *slots, int cap, int64_t first, int64_t *read_off,
                                                    gab_smem *out) {
     __shared__ int64_t sh[256];
     const int32_t t = blockIdx.x * 256 + threadIdx.x;
     const int c = t < n ? counts[t] : 0;
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int64_t add = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
+    const int64_t before = block_exscan_256<int64_t>(sh, c);
     if (t >= n) return;
-    const int64_t off = block_off[blockIdx.x] + sh[threadIdx.x] - c;
+    const int64_t off = block_off[blockIdx.x] + before;
     read_off[first + t] = off;
     if (c > cap) return;                          // its records come from the second round (fmi_compact_overflowed)
-    const OutRec *src = slots + (int64_t)t * cap;
-    for (int j = 0; j < c; j++) {
-        const OutRec o = src[j];
-        gab_smem g;
-        g.rid = (uint32_t)(first + t); g.m = o.m; g.n = o.n; g.pad = 0; g.k = o.k; g.l = o.l; g.s = o.s;
-        out[off + j] = g;
-    }
+    store_smems(out, off, (uint32_t)(first + t), slots + (int64_t)t * cap, c);
 }
 // The reads of a batch whose SMEMs did not fit the first-round slot (a handful of low-complexity reads among millions):
 // their numbers in batch order, for a second round of the seeding kernel over them alone with slots of the exact size.
@@ -915,15 +934,7 @@ __global__ __launch_bounds__(256) void fmi_compact_overflowed(const int32_t *cou
     const int32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_ids) return;
     const int32_t t = ids[i];
-    const int c = counts[t];
-    const int64_t off = read_off[first + t];
-    const OutRec *src = slots + (int64_t)i * cap;
-    for (int j = 0; j < c; j++) {
-        const OutRec o = src[j];
-        gab_smem g;
-        g.rid = (uint32_t)(first + t); g.m = o.m; g.n = o.n; g.pad = 0; g.k = o.k; g.l = o.l; g.s = o.s;
-        out[off + j] = g;
-    }
+    store_smems(out, read_off[first + t], (uint32_t)(first + t), slots + (int64_t)i * cap, counts[t]);
 }
 
 __global__ __launch_bounds__(256) void fmi_validate(const int32_t *len, int64_t n, int32_t stride, FmiCounters *ct) {
@@ -959,16 +970,8 @@ __global__ __launch_bounds__(256) void fmi_sa_count(const gab_smem *__restrict__
 __global__ __launch_bounds__(256) void fmi_sa_offsets(const int32_t *counts, int64_t n, const int64_t *block_off, int64_t *coord_off) {
     __shared__ int32_t sh[256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c = i < n ? counts[i] : 0;
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int v = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if (i < n) coord_off[i] = block_off[blockIdx.x] + sh[threadIdx.x] - c;
+    const int before = block_exscan_256<int32_t>(sh, i < n ? counts[i] : 0);
+    if (i < n) coord_off[i] = block_off[blockIdx.x] + before;
 }
 // One lane resolves one BWT row at a time and immediately takes the next row (of the same SMEM, else the next SMEM of
 // the wave's chunk) when it is done: LF walks have a geometric length (mean 7 steps, no bound), so lanes that waited
@@ -1022,11 +1025,9 @@ __global__ __launch_bounds__(64) void fmi_sa_kernel(FmiIdx ix, SaIdx sa, const g
                     const int b = (bits[0] >> y) & 1 ? 0 : (bits[1] >> y) & 1 ? 1 : (bits[2] >> y) & 1 ? 2 : (bits[3] >> y) & 1 ? 3 : 4;
                     if (b == 4) { coords[out + t] = offset; t++; have = false; }       // the sentinel row
                     else {
-                        const int ysp = (int)(sp & 63);
-                        const uint64_t m = ysp ? ~0ull << (64 - ysp) : 0ull;
                         const uint64_t bb = b == 0 ? bits[0] : b == 1 ? bits[1] : b == 2 ? bits[2] : bits[3];
                         const int64_t cc = b == 0 ? cnt4[0] : b == 1 ? cnt4[1] : b == 2 ? cnt4[2] : cnt4[3];
-                        sp = ix.count[b] + cc + __popcll(bb & m);
+                        sp = ix.count[b] + occ_rank(cc, bb, occ_mask((int)(sp & 63)));
                         offset++; steps++;
                     }
                 }
@@ -1041,8 +1042,26 @@ __global__ __launch_bounds__(64) void fmi_sa_kernel(FmiIdx ix, SaIdx sa, const g
 }  // namespace
 
 // =============================================================================== host side
+// The experiment knobs of a handle are read from the environment once, when the handle is made (an fmi handle never re-reads
+// them).  gab_fmi_clone gives the clone its SOURCE's FmiSharedKnobs; every other knob -- $GAB_FMI_LDS_ENTRIES, _WIDE_LISTS, _DEBUG
+// (and _KMER_DEPTH, which only gab_fmi_create looks at) -- is read from h->tun: the environment the handle itself was made in.
+struct FmiSharedKnobs {
+    size_t scratch_budget = (size_t)6 << 30;   // bound of the two big scratch areas (per-lane spill lists, per-read output slots)
+    bool scratch_from_env = false;             // $GAB_FMI_SCRATCH_MB set: never look at the free memory for a bigger one
+    int64_t batch_max = 1 << 24;               // $GAB_FMI_BATCH: reads per launch of the seeding kernel
+    int waves = 0;                             // $GAB_FMI_WAVES: cap of the resident waves per CU of passes 1 + 2 (experiments)
+    int handover = 1;                          // $GAB_FMI_WIDE=0: no hand-over (every phase stays with the lane that owns the read); > 1: the survivor count that makes a phase wide
+    int wide_cap = 0;                          // $GAB_FMI_WIDE_CAP: places of the hand-over item / candidate queues (tests: the queues run full)
+};
+struct FmiLast {                               // the answers of gab_fmi_last_stats / _records / _paths
+    bool have = false;
+    int64_t ext_calls = 0, rec_reads = 0, nsmem = 0;
+    float kernel_ms = 0;
+    int64_t paths[GAB_FMI_PATHS] = {0};        // summed over the batches of the last call
+};
 struct gab_fmi {
-    gab_tuning tun = gab_tuning_loaded();      // experiment knobs, read when the handle is made (an fmi handle never re-reads them)
+    gab_tuning tun = gab_tuning_loaded();
+    FmiSharedKnobs shared;
     gab_host_stream hs;     // private stream of the host-pointer entry point(s)
     int device = 0;
     FmiIdx ix;
@@ -1053,8 +1072,6 @@ struct gab_fmi {
     gab_devbuf slots;       // per-read output slots
     gab_devbuf slots2, ovf; // second round: slots of the exact size for the reads that overflowed theirs, and their numbers
     gab_devbuf witems, wlists, wcands;   // wide backward phases handed over to fmi_wide_kernel: items, their lists, the candidates they find
-    int wide_cap_env = 0;   // $GAB_FMI_WIDE_CAP: places of the hand-over item / candidate queues (tests: the queues run full)
-    int handover_env = 1;   // $GAB_FMI_WIDE=0: no hand-over (every phase stays with the lane that owns the read); > 1: the survivor count that makes a phase wide
     gab_devbuf out;         // compacted SMEMs
     gab_devbuf roff;        // read_off (nreads + 1)
     gab_devbuf io;          // staging for the host entry point
@@ -1062,18 +1079,9 @@ struct gab_fmi {
     gab_devbuf sa_ws, sa_off, sa_coords, sa_io;
     SaIdx sa_ix = {nullptr, nullptr};
     int64_t sa_lf_steps = 0; float sa_ms = 0; bool have_sa_stats = false;
-    size_t scratch_budget = (size_t)6 << 30;   // bound of the two big scratch areas (per-lane spill lists, per-read output slots)
-    bool scratch_from_env = false;             // $GAB_FMI_SCRATCH_MB set: never look at the free memory for a bigger one
-    int lds_entries_env = 0;                   // $GAB_FMI_LDS_ENTRIES / $GAB_FMI_WIDE_LISTS as they were when the handle was made
-    int64_t batch_max = 1 << 24;               // $GAB_FMI_BATCH: reads per launch of the seeding kernel
-    int waves_env = 0;                         // $GAB_FMI_WAVES: cap of the resident waves per CU of passes 1 + 2 (experiments)
-    bool wide_env = false;                     // (tests and bench.py: force the list format of indexes with >= 2^32 rows)
     hipEvent_t ev[2] = {nullptr, nullptr};
     FmiCounters *h_ct = nullptr;
-    bool have_stats = false;
-    int64_t ext_calls = 0, rec_reads = 0, nsmem = 0;
-    float kernel_ms = 0;
-    int64_t paths[GAB_FMI_PATHS] = {0};        // gab_fmi_last_paths: summed over the batches of the last call
+    FmiLast last;
 };
 
 static int fmi_new_handle(int device, gab_fmi **out) {
@@ -1083,16 +1091,20 @@ static int fmi_new_handle(int device, gab_fmi **out) {
     if (!h) { gab_set_error("out of host memory"); return GAB_ENOMEM; }
     h->device = device;
     const gab_tuning &t = h->tun;
-    h->lds_entries_env = t.fmi_lds_entries; h->wide_env = t.fmi_wide_lists; h->waves_env = t.fmi_waves;
-    h->handover_env = t.fmi_wide; h->wide_cap_env = t.fmi_wide_cap;
-    if (t.fmi_batch >= 1024) h->batch_max = t.fmi_batch;
-    if (t.fmi_scratch_mb > 0) { h->scratch_budget = (size_t)t.fmi_scratch_mb << 20; h->scratch_from_env = true; }
+    h->shared.waves = t.fmi_waves; h->shared.handover = t.fmi_wide; h->shared.wide_cap = t.fmi_wide_cap;
+    if (t.fmi_batch >= 1024) h->shared.batch_max = t.fmi_batch;
+    if (t.fmi_scratch_mb > 0) { h->shared.scratch_budget = (size_t)t.fmi_scratch_mb << 20; h->shared.scratch_from_env = true; }
     if (hipEventCreate(&h->ev[0]) != hipSuccess || hipEventCreate(&h->ev[1]) != hipSuccess ||
         hipHostMalloc((void **)&h->h_ct, sizeof(FmiCounters)) != hipSuccess) {
         gab_set_error("gab_fmi: event / pinned allocation failed"); delete h; return GAB_EDEVICE;
     }
     *out = h;
     return GAB_OK;
+}
+// the survivor count that makes a backward phase wide, and the places of the item / candidate queues for `count` reads
+static int fmi_wide_min(const gab_fmi *h) { return h->shared.handover > 1 ? h->shared.handover : kWideMin; }
+static int32_t fmi_wide_cap(const gab_fmi *h, int64_t count) {
+    return h->shared.wide_cap > 0 ? (int32_t)h->shared.wide_cap : (int32_t)std::min<int64_t>(count * 3 / 10 + 4096, 1 << 28);
 }
 
 extern "C" int gab_fmi_create(int device, int64_t ref_seq_len, const int64_t count_file[5], const void *cp_occ,
@@ -1181,7 +1193,8 @@ extern "C" int gab_fmi_clone(gab_fmi *src, gab_fmi **out) {
     gab_fmi *h = nullptr;
     int rc = fmi_new_handle(src->device, &h);
     if (rc) return rc;
-    h->ix = src->ix; h->sa_ix = src->sa_ix; h->scratch_budget = src->scratch_budget; h->scratch_from_env = src->scratch_from_env; h->batch_max = src->batch_max; h->waves_env = src->waves_env; h->handover_env = src->handover_env; h->wide_cap_env = src->wide_cap_env;
+    h->ix = src->ix; h->sa_ix = src->sa_ix;
+    h->shared = src->shared;                                 // (h->tun stays the clone's own)
     *out = h;
     return GAB_OK;
 }
@@ -1196,6 +1209,290 @@ extern "C" void gab_fmi_destroy(gab_fmi *h) {
     delete h;
 }
 
+// ---- gab_fmi_seed_device in steps: the plan, one launch round, the overflowed reads in parts, settle, append -----------------
+constexpr int kSlotCap = 48;                   // records of a first-round output slot
+
+// What a call runs with.  The seeding kernel is a persistent grid of one-wave blocks sized to the occupancy; lanes pull reads
+// from a counter.  Scratch: a spill area for interval lists longer than the LDS part (stride entries x 32 B per LANE, touched
+// only by the rare long list) and the output slot per READ (kSlotCap x 32 B).
+// A batch cannot end before its slowest read has (passes 1 + 2 of a read are one chain of dependent look-ups: ~750 wave steps
+// on average, but ONE backward phase of a re-seeded position inside a repeat -- a 76-entry list over 75 columns -- is 5 700,
+// ~25 ms), and while the last reads finish most lanes idle: 10 M reads in four batches spent 4 x ~22 ms of 322 ms there
+// (profiles/r03_fmi_batches.md).  So the whole call is ONE batch whenever its slots fit a third of the memory that is free right
+// now, up to 32 GB; $GAB_FMI_SCRATCH_MB fixes the budget instead.
+struct FmiPlan {
+    size_t budget;                             // of the two scratch areas, for this call
+    bool ldsq;                                 // form: read and lists in LDS (stride <= kLdsQMax), else in global memory
+    int lds_entries, narrow_lists;             // ring entries per lane; list entries of 13 bytes (every interval bound fits 32 bits), else 16
+    size_t lds_bytes, lds_bytes_p3, wide_lds;  // dynamic LDS of passes 1 + 2, of pass 3, of fmi_wide_kernel (FmiLds)
+    int n_cu, waves_per_cu, waves_per_cu_p3, wide_occ;
+    int64_t grid_waves;                        // waves that own a spill area
+    int64_t B, nb_blocks;                      // reads per batch, and their blocks of 256
+    size_t o_counts, o_bs, o_defer, ws_bytes;  // workspace: counters | counts | block sums | one byte per read (pass 2 waits for the second round)
+};
+static int fmi_make_plan(const gab_fmi *h, int32_t stride, int64_t nreads, FmiPlan *plan) {
+    FmiPlan &p = *plan;
+    p.budget = h->shared.scratch_budget;
+    if (!h->shared.scratch_from_env && (size_t)nreads * kSlotCap * sizeof(OutRec) > p.budget) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
+            const size_t avail = (fr + h->slots.cap) / 3;
+            p.budget = std::max(p.budget, std::min<size_t>(avail, (size_t)32 << 30));
+        }
+    }
+    p.ldsq = stride <= kLdsQMax;
+    p.lds_entries = p.ldsq ? (h->tun.fmi_lds_entries > 0 ? h->tun.fmi_lds_entries : 12) : 0;
+    p.narrow_lists = (h->ix.ref_seq_len < 0xffffffffll && !h->tun.fmi_wide_lists) ? 1 : 0;
+    const FmiLds lay{stride, p.lds_entries, p.narrow_lists};
+    p.lds_bytes = p.ldsq ? lay.bytes() : 0; p.lds_bytes_p3 = p.ldsq ? lay.bytes_no_lists() : 0; p.wide_lds = FmiLds::wide_bytes(stride);
+    p.waves_per_cu = p.waves_per_cu_p3 = 0; p.wide_occ = 1;
+    hipDeviceProp_t prop;
+    GAB_HIP(hipGetDeviceProperties(&prop, h->device));
+    p.n_cu = prop.multiProcessorCount;
+    if (p.ldsq) {
+        GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p.waves_per_cu, fmi_seed_kernel<true, false>, 64, p.lds_bytes));
+        GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p.waves_per_cu_p3, fmi_seed_kernel<true, false>, 64, p.lds_bytes_p3));
+        GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p.wide_occ, fmi_wide_kernel, 64, p.wide_lds));
+        if (p.wide_occ < 1) p.wide_occ = 1;
+    } else GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p.waves_per_cu, fmi_seed_kernel<false, false>, 64, 0));
+    GAB_CHECK(p.waves_per_cu > 0, "gab_fmi_seed_device: the seeding kernel does not fit a CU (stride %d)", stride);
+    // the per-lane spill area is stride x 32 B x 64 lanes per resident wave: long reads (no LDS lists: every list entry
+    // lives there) run on fewer waves rather than on tens of GB of scratch
+    const int64_t fit = (int64_t)(p.budget / (sizeof(PrevRec) * (size_t)stride * 64)) / p.n_cu;
+    if (fit < p.waves_per_cu) p.waves_per_cu = (int)std::max<int64_t>(fit, 1);
+    if (h->shared.waves > 0 && h->shared.waves < p.waves_per_cu) p.waves_per_cu = h->shared.waves;
+    if (fit < p.waves_per_cu_p3) p.waves_per_cu_p3 = (int)std::max<int64_t>(fit, 1);
+    p.grid_waves = (int64_t)p.n_cu * std::max(p.waves_per_cu, p.waves_per_cu_p3);
+    p.B = (int64_t)std::min<size_t>((size_t)nreads, std::max<size_t>(1024, p.budget / (64 * sizeof(OutRec))));
+    p.B = std::min<int64_t>(p.B, h->shared.batch_max);
+    p.B = gab_ceil_div(nreads, gab_ceil_div(nreads, p.B));   // equal batches: no short last one
+    p.nb_blocks = gab_ceil_div(p.B, 256);
+    p.o_counts = 256; p.o_bs = (p.o_counts + 4 * (size_t)p.B + 64 + 7) & ~(size_t)7;
+    p.o_defer = p.o_bs + 8 * (size_t)p.nb_blocks + 64; p.ws_bytes = p.o_defer + (size_t)p.B + 64;
+    return GAB_OK;
+}
+
+struct FmiCall {                               // one gab_fmi_seed_device call: its arguments, its plan, its workspace, what its batches add up to
+    gab_fmi *h; hipStream_t s;
+    const uint8_t *d_enc; const int32_t *d_len; int32_t stride; int64_t nreads; int32_t min_seed_len;
+    FmiPlan p;
+    FmiCounters *d_ct; int32_t *d_counts; int64_t *d_bs; uint8_t *d_defer;
+    bool handover;                             // wide backward phases go to fmi_wide_kernel (off for the rest of a call whose candidates outgrew their queue)
+    float kms;                                 // kernel time so far
+    int64_t pt[GAB_FMI_PATHS];                 // which route took what, summed over the batches (gab_fmi_last_paths)
+};
+struct FmiOverflow {                           // the reads of a batch whose SMEMs did not fit their first-round slot
+    int32_t n = 0; int32_t *d_ids = nullptr;   // how many, their numbers in batch order
+    int over_cap = 0;                          // the slot that holds the largest count
+    int64_t round = 0;                         // reads per part of the second round
+};
+
+static int fmi_validate_lengths(const FmiCall &c) {
+    gab_fmi *h = c.h;
+    *h->h_ct = FmiCounters{};
+    h->h_ct->first_bad = 0x7fffffff;
+    GAB_HIP(hipMemcpyAsync(c.d_ct, h->h_ct, sizeof(FmiCounters), hipMemcpyHostToDevice, c.s));
+    hipLaunchKernelGGL(fmi_validate, dim3((unsigned)std::min<int64_t>(gab_ceil_div(c.nreads, 256), 2048)), dim3(256), 0, c.s,
+                       c.d_len, c.nreads, c.stride, c.d_ct);
+    GAB_HIP(hipMemcpyAsync(h->h_ct, c.d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipStreamSynchronize(c.s));
+    if (h->h_ct->bad) {
+        gab_set_error("gab_fmi_seed_device: %d read(s) have a length outside 0..stride (first: read %d)", h->h_ct->bad,
+                      h->h_ct->first_bad - 1);
+        return GAB_EINVAL;
+    }
+    return GAB_OK;
+}
+
+// One launch round of the seeding kernel(s) over `count` reads of the batch at `first`: all of them (ids == nullptr, slot t for
+// read t) or the listed ones (slot i for read ids[i]); their slots sorted.
+static int fmi_launch_round(const FmiCall &c, int64_t first, int32_t count, const int32_t *ids, OutRec *slots, int slot_cap, int *waves_dbg) {
+    gab_fmi *h = c.h; hipStream_t s = c.s; const FmiPlan &p = c.p;
+    const FmiWide no_wide{nullptr, nullptr, 0, 0, 0};
+    auto seed = [&](auto kernel, int64_t waves_per_cu, size_t lds, int entries, int passes, int narrow, const FmiWide &wide) {
+        const int blocks = (int)std::min<int64_t>(p.n_cu * waves_per_cu, gab_ceil_div((int64_t)count, 64));
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, s, h->ix, c.d_enc, c.stride, c.d_len, first, count, c.min_seed_len,
+                           h->prev.as<PrevRec>(), (int)c.stride, slots, slot_cap, c.d_counts, c.d_ct, entries,
+                           (int64_t)c.nreads * c.stride, passes, narrow, ids, wide, c.d_defer);
+        return blocks;
+    };
+    GAB_HIP(hipMemsetAsync(&c.d_ct->next_read, 0, sizeof(int32_t), s));
+    if (p.ldsq) {
+        // passes 1 + 2 need the interval lists in LDS, which caps the occupancy; pass 3 needs only the read, so it
+        // runs as a second launch of the same kernel with no list area and twice the waves
+        // wide backward phases leave the kernel as items (see FmiWideItem): the areas for a batch of `count` reads
+        FmiWide wide = no_wide;
+        const int32_t wcap = fmi_wide_cap(h, count);
+        if (!ids && c.handover) {
+            const uint32_t lcap = (uint32_t)std::min<int64_t>((int64_t)count * 12 + 65536, 0x7fffffffll);
+            int rcw = h->witems.reserve(sizeof(FmiWideItem) * (size_t)wcap);
+            if (!rcw) rcw = h->wcands.reserve(sizeof(FmiWideItem) * (size_t)wcap);
+            if (!rcw) rcw = h->wlists.reserve(sizeof(uint4) * (size_t)lcap);
+            if (rcw) return rcw;
+            wide = FmiWide{h->witems.as<FmiWideItem>(), h->wlists.as<uint4>(), wcap, lcap, fmi_wide_min(h)};
+        }
+        const auto k12 = ids ? fmi_seed_kernel<true, true> : fmi_seed_kernel<true, false>;
+        const int blocks = seed(k12, p.waves_per_cu, p.lds_bytes, p.lds_entries, 1, p.narrow_lists, wide);
+        if (waves_dbg) *waves_dbg = blocks;
+        if (wide.items) {
+            // ... and are walked by groups of 16 lanes: the items, then the re-seeding candidates their pass-1 phases found
+            auto walk = [&](const FmiWideItem *items, const int32_t *n_items, FmiWideItem *cands, int32_t *n_cands, int32_t cands_cap, const uint8_t *defer) {
+                hipLaunchKernelGGL(fmi_wide_kernel, dim3(p.n_cu * p.wide_occ), dim3(64), p.wide_lds, s, h->ix, c.d_enc, c.stride, c.d_len, first, items,
+                                   n_items, wcap, (const uint4 *)wide.lists, cands, n_cands, cands_cap, slots, slot_cap, c.d_counts, c.d_ct,
+                                   c.min_seed_len, defer);
+            };
+            walk(wide.items, &c.d_ct->wide_items, h->wcands.as<FmiWideItem>(), &c.d_ct->wide_cands, wcap, c.d_defer);
+            GAB_HIP(hipMemsetAsync(&c.d_ct->wide_queue, 0, sizeof(int32_t), s));
+            walk(h->wcands.as<FmiWideItem>(), &c.d_ct->wide_cands, nullptr, nullptr, 0, nullptr);
+        }
+        GAB_HIP(hipMemsetAsync(&c.d_ct->next_read, 0, sizeof(int32_t), s));
+        seed(k12, p.waves_per_cu_p3, p.lds_bytes_p3, 0, 2, p.narrow_lists, no_wide);
+    } else {
+        const int blocks = seed(ids ? fmi_seed_kernel<false, true> : fmi_seed_kernel<false, false>, p.waves_per_cu, 0, 0, 3, 0, no_wide);
+        if (waves_dbg) *waves_dbg = blocks;
+    }
+    hipLaunchKernelGGL(fmi_sort_slots, dim3((unsigned)gab_ceil_div((int64_t)count, 256)), dim3(256), 0, s, slots, slot_cap, c.d_counts, count, ids);
+    GAB_HIP(hipGetLastError());
+    return GAB_OK;
+}
+
+// The first round of a batch, timed, its counters in h->h_ct.  Twice only when the handed-over phases found more candidates
+// than their queue holds: a candidate without a place is a re-seeding that did not happen, so the batch runs again, every phase
+// with its own lane.
+static int fmi_first_round(FmiCall &c, int64_t first, int32_t nb, int *waves_dbg, float *ms) {
+    gab_fmi *h = c.h;
+    for (;;) {
+        *h->h_ct = FmiCounters{};              // (bad is 0 after fmi_validate_lengths, first_bad is not read again)
+        GAB_HIP(hipMemcpyAsync(c.d_ct, h->h_ct, sizeof(FmiCounters), hipMemcpyHostToDevice, c.s));
+        GAB_HIP(hipEventRecord(h->ev[0], c.s));
+        const int rc = fmi_launch_round(c, first, nb, nullptr, h->slots.as<OutRec>(), kSlotCap, waves_dbg);
+        if (rc) return rc;
+        GAB_HIP(hipEventRecord(h->ev[1], c.s));
+        GAB_HIP(hipMemcpyAsync(h->h_ct, c.d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, c.s));
+        GAB_HIP(hipStreamSynchronize(c.s));
+        if (!c.handover || h->h_ct->wide_cands <= fmi_wide_cap(h, nb)) break;
+        float lost = 0;
+        GAB_HIP(hipEventElapsedTime(&lost, h->ev[0], h->ev[1]));
+        c.kms += lost;
+        c.handover = false;
+        c.pt[GAB_FMI_PATH_RERUNS]++;
+    }
+    GAB_HIP(hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
+    c.kms += *ms;
+    return GAB_OK;
+}
+
+// Some reads found more SMEMs than a first-round slot holds (low-complexity reads; a handful among millions of real ones): they
+// alone run again with slots of the size the worst of them needs, in as many parts as the scratch budget asks for, and their
+// records go to the places fmi_compact leaves open.  Here: their numbers.
+static int fmi_find_overflowed(const FmiCall &c, int32_t nb, FmiOverflow *ovf) {
+    gab_fmi *h = c.h;
+    const int rc = h->ovf.reserve(4 * (size_t)nb + 64);
+    if (rc) return rc;
+    ovf->d_ids = h->ovf.as<int32_t>();
+    hipLaunchKernelGGL(fmi_list_overflowed, dim3((unsigned)gab_ceil_div(nb, 256)), dim3(256), 0, c.s, c.d_counts, nb, kSlotCap, ovf->d_ids,
+                       &c.d_ct->n_ovf, &c.d_ct->ovf_sum);
+    GAB_HIP(hipGetLastError());
+    GAB_HIP(hipMemcpyAsync(&ovf->n, &c.d_ct->n_ovf, 4, hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipStreamSynchronize(c.s));
+    return GAB_OK;
+}
+// ... the parts the budget allows for slots of ovf->over_cap records, and those slots
+static int fmi_size_parts(const FmiCall &c, FmiOverflow *ovf) {
+    const int64_t per_round = std::max<int64_t>(1, (int64_t)(c.p.budget / (sizeof(OutRec) * (size_t)ovf->over_cap)));
+    ovf->round = std::min<int64_t>(ovf->n, per_round);
+    return c.h->slots2.reserve(sizeof(OutRec) * (size_t)ovf->over_cap * (size_t)ovf->round);
+}
+// ... and the launch rounds over them, part by part, timed.  `compact`: every part's records go to the output, and nothing is
+// read back; else the counters come back to h->h_ct.
+static int fmi_run_overflowed(FmiCall &c, int64_t first, const FmiOverflow &ovf, bool compact, float *ms) {
+    gab_fmi *h = c.h; hipStream_t s = c.s;
+    GAB_HIP(hipEventRecord(h->ev[0], s));
+    for (int64_t i0 = 0; i0 < ovf.n; i0 += ovf.round) {
+        const int32_t cnt = (int32_t)std::min<int64_t>(ovf.round, ovf.n - i0);
+        const int rc = fmi_launch_round(c, first, cnt, ovf.d_ids + i0, h->slots2.as<OutRec>(), ovf.over_cap, nullptr);
+        if (rc) return rc;
+        if (!compact) continue;
+        hipLaunchKernelGGL(fmi_compact_overflowed, dim3((unsigned)gab_ceil_div((int64_t)cnt, 256)), dim3(256), 0, s, c.d_counts, ovf.d_ids + i0,
+                           cnt, h->slots2.as<OutRec>(), ovf.over_cap, first, h->roff.as<int64_t>(), h->out.as<gab_smem>());
+        GAB_HIP(hipGetLastError());
+    }
+    GAB_HIP(hipEventRecord(h->ev[1], s));
+    if (compact) GAB_HIP(hipEventSynchronize(h->ev[1]));
+    else {
+        GAB_HIP(hipMemcpyAsync(h->h_ct, c.d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+    }
+    GAB_HIP(hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
+    c.kms += *ms;
+    return GAB_OK;
+}
+
+// Settle the counts of a batch in which pass 1 alone overflowed the slot of some reads.  Pass 2 -- which reads the records of
+// pass 1 back from the slot -- did not run for those (defer[]): their counts, and so the batch's total, its largest count and the
+// offsets fmi_compact derives from the counts, are not final after the first round.  A launch of the second round's kernel over
+// the overflowed reads, with slots that hold the largest count so far (all of any read's pass 1), settles them; it keeps the
+// counts of what the first round left out and drops the rest, and what it writes into the slots is not used.
+// `c`: the first round's counters; `r`: the device's after the settling launch.
+static void fmi_settle_counts(FmiCounters *c, const FmiCounters &r) {
+    c->ext_calls = r.ext_calls; c->rec_reads = r.rec_reads; c->tab_reads = r.tab_reads;      // extensions, records, positions: the device went on counting
+    c->positions = r.positions; c->spills = r.spills; c->list_sum = r.list_sum;
+    c->total = c->total - r.ovf_sum + r.total;               // total and max_per_read were zeroed: the overflowed reads' SMEMs, counted again
+    c->max_per_read = std::max(c->max_per_read, r.max_per_read);
+}
+static int fmi_settle(FmiCall &c, int64_t first, FmiOverflow *ovf, FmiCounters *cnt, float *ms) {
+    int rc = fmi_size_parts(c, ovf);
+    if (rc) return rc;
+    GAB_HIP(hipMemsetAsync(&c.d_ct->total, 0, sizeof(c.d_ct->total), c.s));
+    GAB_HIP(hipMemsetAsync(&c.d_ct->max_per_read, 0, sizeof(c.d_ct->max_per_read), c.s));
+    rc = fmi_run_overflowed(c, first, *ovf, false, ms);
+    if (rc) return rc;
+    fmi_settle_counts(cnt, *c.h->h_ct);
+    ovf->over_cap = cnt->max_per_read;
+    return GAB_OK;
+}
+
+// Append a batch of `add` SMEMs behind the `total` of the batches before it: the output grows geometrically, keeping what is
+// there; offsets from the counts; the records of every read whose slot held them.
+static int fmi_append_batch(FmiCall &c, int64_t first, int32_t nb, int64_t total, int64_t add, size_t *out_cap) {
+    gab_fmi *h = c.h; hipStream_t s = c.s;
+    if ((size_t)(total + add) > *out_cap) {
+        const size_t ncap = std::max<size_t>(*out_cap * 2, (size_t)(total + add));
+        gab_devbuf bigger;
+        const int rc = bigger.reserve(ncap * sizeof(gab_smem));
+        if (rc) return rc;
+        GAB_HIP(hipMemcpyAsync(bigger.p, h->out.p, (size_t)total * sizeof(gab_smem), hipMemcpyDeviceToDevice, s));
+        GAB_HIP(hipStreamSynchronize(s));
+        h->out.release();
+        h->out = bigger;
+        *out_cap = ncap;
+        c.pt[GAB_FMI_PATH_OUT_GROWTHS]++;
+    }
+    const int blocks = (int)gab_ceil_div(nb, 256);
+    hipLaunchKernelGGL(fmi_block_sums, dim3(blocks), dim3(256), 0, s, c.d_counts, nb, c.d_bs);
+    hipLaunchKernelGGL(fmi_scan_blocks, dim3(1), dim3(1024), 0, s, c.d_bs, blocks, total);
+    hipLaunchKernelGGL(fmi_compact, dim3(blocks), dim3(256), 0, s, c.d_counts, nb, c.d_bs, h->slots.as<OutRec>(), kSlotCap, first,
+                       h->roff.as<int64_t>(), h->out.as<gab_smem>());
+    GAB_HIP(hipGetLastError());
+    return GAB_OK;
+}
+
+// the counters of the round that is kept -> gab_fmi_last_paths
+static void fmi_book_paths(FmiCall &c, const FmiCounters &cnt, const FmiOverflow &ovf, int32_t nb) {
+    int64_t *pt = c.pt;
+    pt[GAB_FMI_PATH_BATCHES]++;
+    pt[GAB_FMI_PATH_POSITIONS] += (int64_t)cnt.positions; pt[GAB_FMI_PATH_LIST_SUM] += (int64_t)cnt.list_sum; pt[GAB_FMI_PATH_SPILLS] += (int64_t)cnt.spills;
+    pt[GAB_FMI_PATH_INDEX_EXT] += (int64_t)cnt.ext_calls; pt[GAB_FMI_PATH_TABLE_EXT] += (int64_t)cnt.tab_reads;
+    if (c.handover && c.p.ldsq) {
+        pt[GAB_FMI_PATH_WIDE_ITEMS] += std::min<int64_t>(std::max(cnt.wide_items, 0), fmi_wide_cap(c.h, nb));
+        pt[GAB_FMI_PATH_WIDE_ENTRIES] += (int64_t)cnt.wide_top; pt[GAB_FMI_PATH_WIDE_CANDS] += cnt.wide_cands;
+    }
+    pt[GAB_FMI_PATH_MAX_PER_READ] = std::max<int64_t>(pt[GAB_FMI_PATH_MAX_PER_READ], cnt.max_per_read);
+    pt[GAB_FMI_PATH_OVERFLOW_READS] += ovf.n; pt[GAB_FMI_PATH_SECOND_ROUND_PARTS] += ovf.n ? gab_ceil_div((int64_t)ovf.n, ovf.round) : 0;
+}
+
 extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t stride, const int32_t *d_len, int64_t nreads,
                                    int32_t min_seed_len, const gab_smem **d_out, const int64_t **d_read_off,
                                    int64_t *nout, void *stream_) {
@@ -1205,7 +1502,7 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
               GAB_FMI_MAX_READLEN - 1);
     GAB_CHECK(min_seed_len >= 1, "gab_fmi_seed_device: minSeedLen must be >= 1");
     GAB_CHECK(nout, "gab_fmi_seed_device: NULL nout");
-    h->have_stats = false;
+    h->last.have = false;
     *nout = 0;
     gab_device_guard g(h->device);
     hipStream_t s = (hipStream_t)stream_;
@@ -1216,279 +1513,56 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     if (nreads == 0) { GAB_HIP(hipMemsetAsync(h->roff.p, 0, 8, s)); return GAB_OK; }
     GAB_CHECK(d_enc && d_len, "gab_fmi_seed_device: NULL buffer");
 
-    // The seeding kernel is a persistent grid of one-wave blocks sized to the occupancy; lanes pull reads from a
-    // counter.  Scratch: a spill area for interval lists longer than the LDS part (stride entries x 32 B per LANE,
-    // touched only by the rare long list) and the output slot per READ (cap x 32 B).
-    // A batch cannot end before its slowest read has (passes 1 + 2 of a read are one chain of dependent look-ups: ~750 wave steps
-    // on average, but ONE backward phase of a re-seeded position inside a repeat -- a 76-entry list over 75 columns -- is 5 700,
-    // ~25 ms), and while the last reads finish most lanes idle: 10 M reads in four batches spent 4 x ~22 ms of 322 ms there
-    // (profiles/r03_fmi_batches.md).  So the whole call is ONE batch whenever its slots (cap x 32 B per read) fit a third of
-    // the memory that is free right now, up to 32 GB; $GAB_FMI_SCRATCH_MB fixes the budget instead.
-    size_t budget = h->scratch_budget;
-    if (!h->scratch_from_env && (size_t)nreads * 48 * sizeof(OutRec) > budget) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-            const size_t avail = (fr + h->slots.cap) / 3;
-            budget = std::max(budget, std::min<size_t>(avail, (size_t)32 << 30));
-        }
-    }
-    const int cap = 48;
-    const int lds_entries_env = h->lds_entries_env;
-    const bool ldsq = stride <= kLdsQMax;
-    const int lds_entries = ldsq ? (lds_entries_env > 0 ? lds_entries_env : 12) : 0;
-    // list entries: 13 bytes (three dword planes + a byte plane) when every interval bound fits 32 bits, else 16 packed
-    const bool wide_env = h->wide_env;
-    const int narrow_lists = (h->ix.ref_seq_len < 0xffffffffll && !wide_env) ? 1 : 0;
-    const size_t list_bytes = narrow_lists ? (((size_t)lds_entries * 64 * 13 + 15) & ~(size_t)15) : (size_t)lds_entries * 64 * 16;
-    const size_t lds_bytes = ldsq ? (((size_t)(stride + 7) / 8 * 64 + 3) / 4) * 16 + list_bytes : 0;
-    const size_t lds_bytes_p3 = ldsq ? (((size_t)(stride + 7) / 8 * 64 + 3) / 4 + 64) * 16 : 0;   // read + slack for nibbles_at
-    int waves_per_cu = 0, waves_per_cu_p3 = 0, n_cu = 0, wide_occ = 1;
-    const size_t wide_lds = (size_t)4 * (size_t)((stride + 15) & ~15) * sizeof(uint4);          // fmi_wide_kernel: four groups, a list each
-    {
-        hipDeviceProp_t prop;
-        GAB_HIP(hipGetDeviceProperties(&prop, h->device));
-        n_cu = prop.multiProcessorCount;
-        if (ldsq) {
-            GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            GAB_HIP(hipFuncSetAttribute((const void *)fmi_seed_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<true, false>, 64, lds_bytes));
-            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu_p3, fmi_seed_kernel<true, false>, 64, lds_bytes_p3));
-            GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wide_occ, fmi_wide_kernel, 64, wide_lds));
-            if (wide_occ < 1) wide_occ = 1;
-        } else GAB_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_per_cu, fmi_seed_kernel<false, false>, 64, 0));
-        GAB_CHECK(waves_per_cu > 0, "gab_fmi_seed_device: the seeding kernel does not fit a CU (stride %d)", stride);
-        // the per-lane spill area is stride x 32 B x 64 lanes per resident wave: long reads (no LDS lists: every list entry
-        // lives there) run on fewer waves rather than on tens of GB of scratch
-        const int64_t fit = (int64_t)(budget / (sizeof(PrevRec) * (size_t)stride * 64)) / n_cu;
-        if (fit < waves_per_cu) waves_per_cu = (int)std::max<int64_t>(fit, 1);
-        if (h->waves_env > 0 && h->waves_env < waves_per_cu) waves_per_cu = h->waves_env;
-        if (fit < waves_per_cu_p3) waves_per_cu_p3 = (int)std::max<int64_t>(fit, 1);
-    }
-    const int64_t grid_waves = (int64_t)n_cu * std::max(waves_per_cu, waves_per_cu_p3);
-    int64_t B = (int64_t)std::min<size_t>((size_t)nreads, std::max<size_t>(1024, budget / (64 * sizeof(OutRec))));
-    B = std::min<int64_t>(B, h->batch_max);
-    B = gab_ceil_div(nreads, gab_ceil_div(nreads, B));       // equal batches: no short last one
-    const int64_t nb_blocks = gab_ceil_div(B, 256);
-    const size_t o_counts = 256, o_bs = o_counts + 4 * (size_t)B + 64;
-    const size_t o_defer = ((o_bs + 7) & ~(size_t)7) + 8 * (size_t)nb_blocks + 64;      // one byte per read of the batch: pass 2 waits for the second round
-    rc = h->ws.reserve(o_defer + (size_t)B + 64);
-    if (rc) return rc;
-    rc = h->prev.reserve(sizeof(PrevRec) * (size_t)stride * (size_t)grid_waves * 64);
-    if (rc) return rc;
+    FmiCall c{};
+    c.h = h; c.s = s; c.d_enc = d_enc; c.d_len = d_len; c.stride = stride; c.nreads = nreads; c.min_seed_len = min_seed_len;
+    c.handover = h->shared.handover != 0;
+    if ((rc = fmi_make_plan(h, stride, nreads, &c.p)) != GAB_OK) return rc;
+    const FmiPlan &p = c.p;
+    if ((rc = h->ws.reserve(p.ws_bytes)) != GAB_OK) return rc;
+    if ((rc = h->prev.reserve(sizeof(PrevRec) * (size_t)stride * (size_t)p.grid_waves * 64)) != GAB_OK) return rc;
     char *wb = h->ws.as<char>();
-    FmiCounters *d_ct = (FmiCounters *)wb;
-    int32_t *d_counts = (int32_t *)(wb + o_counts);
-    int64_t *d_bs = (int64_t *)(wb + ((o_bs + 7) & ~(size_t)7));
-    uint8_t *d_defer = (uint8_t *)(wb + o_defer);
+    c.d_ct = (FmiCounters *)wb; c.d_counts = (int32_t *)(wb + p.o_counts); c.d_bs = (int64_t *)(wb + p.o_bs); c.d_defer = (uint8_t *)(wb + p.o_defer);
+    if ((rc = fmi_validate_lengths(c)) != GAB_OK) return rc;
 
-    memset(h->h_ct, 0, sizeof(FmiCounters));
-    h->h_ct->first_bad = 0x7fffffff;
-    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(FmiCounters), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(fmi_validate, dim3((unsigned)std::min<int64_t>(gab_ceil_div(nreads, 256), 2048)), dim3(256), 0, s,
-                       d_len, nreads, stride, d_ct);
-    GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipStreamSynchronize(s));
-    if (h->h_ct->bad) {
-        gab_set_error("gab_fmi_seed_device: %d read(s) have a length outside 0..stride (first: read %d)", h->h_ct->bad,
-                      h->h_ct->first_bad - 1);
-        return GAB_EINVAL;
-    }
-
-    // output grows geometrically; batches append
-    size_t out_cap = std::max<size_t>((size_t)nreads * 16, 1024);
-    rc = h->out.reserve(out_cap * sizeof(gab_smem));
-    if (rc) return rc;
+    size_t out_cap = std::max<size_t>((size_t)nreads * 16, 1024);      // output grows geometrically; batches append
+    if ((rc = h->out.reserve(out_cap * sizeof(gab_smem))) != GAB_OK) return rc;
     int64_t total = 0;
     unsigned long long ext_total = 0, rec_total = 0;
-    float kms = 0;
-    int64_t pt[GAB_FMI_PATHS] = {0};                         // which route took what, summed over the batches (gab_fmi_last_paths)
-    // one launch of the seeding kernel(s) over `count` reads of the batch at `first`: all of them (ids == nullptr, slot t for
-    // read t) or the listed ones (slot i for read ids[i])
-    bool handover = h->handover_env != 0;                   // wide backward phases go to fmi_wide_kernel (off for the rest of a call whose candidates outgrew their queue)
-    auto wide_cap = [&](int64_t count) { return h->wide_cap_env > 0 ? (int32_t)h->wide_cap_env : (int32_t)std::min<int64_t>(count * 3 / 10 + 4096, 1 << 28); };
-    auto seed = [&](int64_t first, int32_t nb, int32_t count, const int32_t *ids, OutRec *slots, int slot_cap, int *waves_dbg) -> int {
-        const int seed_blocks = (int)std::min<int64_t>((int64_t)n_cu * waves_per_cu, gab_ceil_div((int64_t)count, 64));
-        if (waves_dbg) *waves_dbg = seed_blocks;
-        GAB_HIP(hipMemsetAsync(&d_ct->next_read, 0, sizeof(int32_t), s));
-        if (ldsq) {
-            // passes 1 + 2 need the interval lists in LDS, which caps the occupancy; pass 3 needs only the read, so it
-            // runs as a second launch of the same kernel with no list area and twice the waves
-            // wide backward phases leave the kernel as items (see FmiWideItem): the areas for a batch of `count` reads
-            FmiWide wide{nullptr, nullptr, 0, 0, 0};
-            const int32_t wcap = wide_cap(count);
-            if (!ids && handover) {
-                const uint32_t lcap = (uint32_t)std::min<int64_t>((int64_t)count * 12 + 65536, 0x7fffffffll);
-                int rcw = h->witems.reserve(sizeof(FmiWideItem) * (size_t)wcap);
-                if (!rcw) rcw = h->wcands.reserve(sizeof(FmiWideItem) * (size_t)wcap);
-                if (!rcw) rcw = h->wlists.reserve(sizeof(uint4) * (size_t)lcap);
-                if (rcw) return rcw;
-                wide = FmiWide{h->witems.as<FmiWideItem>(), h->wlists.as<uint4>(), wcap, lcap, h->handover_env > 1 ? h->handover_env : kWideMin};
-            }
-            const auto k12 = ids ? fmi_seed_kernel<true, true> : fmi_seed_kernel<true, false>;
-            hipLaunchKernelGGL(k12, dim3(seed_blocks), dim3(64), lds_bytes, s, h->ix, d_enc, stride, d_len, first,
-                               count, min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct,
-                               lds_entries, (int64_t)nreads * stride, 1, narrow_lists, ids, wide, d_defer);
-            if (wide.items) {
-                // ... and are walked by groups of 16 lanes: the items, then the re-seeding candidates their pass-1 phases found
-                const int wblocks = n_cu * wide_occ;
-                hipLaunchKernelGGL(fmi_wide_kernel, dim3(wblocks), dim3(64), wide_lds, s, h->ix, d_enc, stride, d_len, first, (const FmiWideItem *)wide.items,
-                                   (const int32_t *)&d_ct->wide_items, wcap, (const uint4 *)wide.lists, h->wcands.as<FmiWideItem>(), &d_ct->wide_cands, wcap,
-                                   slots, slot_cap, d_counts, d_ct, min_seed_len, (const uint8_t *)d_defer);
-                GAB_HIP(hipMemsetAsync(&d_ct->wide_queue, 0, sizeof(int32_t), s));
-                hipLaunchKernelGGL(fmi_wide_kernel, dim3(wblocks), dim3(64), wide_lds, s, h->ix, d_enc, stride, d_len, first, (const FmiWideItem *)h->wcands.as<FmiWideItem>(),
-                                   (const int32_t *)&d_ct->wide_cands, wcap, (const uint4 *)wide.lists, (FmiWideItem *)nullptr, (int32_t *)nullptr, 0,
-                                   slots, slot_cap, d_counts, d_ct, min_seed_len, (const uint8_t *)nullptr);
-            }
-            GAB_HIP(hipMemsetAsync(&d_ct->next_read, 0, sizeof(int32_t), s));
-            const int p3_blocks = (int)std::min<int64_t>((int64_t)n_cu * waves_per_cu_p3, gab_ceil_div((int64_t)count, 64));
-            hipLaunchKernelGGL(k12, dim3(p3_blocks), dim3(64), lds_bytes_p3, s, h->ix, d_enc, stride, d_len, first,
-                               count, min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct,
-                               0, (int64_t)nreads * stride, 2, narrow_lists, ids, FmiWide{nullptr, nullptr, 0, 0, 0}, d_defer);
-        } else {
-            const auto k123 = ids ? fmi_seed_kernel<false, true> : fmi_seed_kernel<false, false>;
-            hipLaunchKernelGGL(k123, dim3(seed_blocks), dim3(64), 0, s, h->ix, d_enc, stride, d_len, first, count,
-                               min_seed_len, h->prev.as<PrevRec>(), (int)stride, slots, slot_cap, d_counts, d_ct, 0,
-                               (int64_t)nreads * stride, 3, 0, ids, FmiWide{nullptr, nullptr, 0, 0, 0}, d_defer);
-        }
-        hipLaunchKernelGGL(fmi_sort_slots, dim3((unsigned)gab_ceil_div((int64_t)count, 256)), dim3(256), 0, s, slots, slot_cap, d_counts, count, ids);
-        GAB_HIP(hipGetLastError());
-        (void)nb;
-        return GAB_OK;
-    };
     for (int64_t first = 0; first < nreads;) {
-        const int32_t nb = (int32_t)std::min<int64_t>(B, nreads - first);
-        const int blocks = (int)gab_ceil_div(nb, 256);
+        const int32_t nb = (int32_t)std::min<int64_t>(p.B, nreads - first);
         int seed_blocks_dbg = 0;
-        rc = h->slots.reserve(sizeof(OutRec) * (size_t)cap * (size_t)nb);
-        if (rc) return rc;
-        for (;;) {                                            // twice only when the handed-over phases found more candidates than their queue holds
-            h->h_ct->ext_calls = 0; h->h_ct->rec_reads = 0; h->h_ct->tab_reads = 0; h->h_ct->total = 0; h->h_ct->max_per_read = 0; h->h_ct->next_read = 0; h->h_ct->n_ovf = 0; h->h_ct->n_defer = 0; h->h_ct->ovf_sum = 0; h->h_ct->wide_items = h->h_ct->wide_cands = h->h_ct->wide_queue = 0; h->h_ct->wide_top = 0; h->h_ct->wave_steps = 0; h->h_ct->positions = h->h_ct->spills = h->h_ct->list_sum = 0;
-            GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(FmiCounters), hipMemcpyHostToDevice, s));
-            GAB_HIP(hipEventRecord(h->ev[0], s));
-            rc = seed(first, nb, nb, nullptr, h->slots.as<OutRec>(), cap, &seed_blocks_dbg);
-            if (rc) return rc;
-            GAB_HIP(hipEventRecord(h->ev[1], s));
-            GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, s));
-            GAB_HIP(hipStreamSynchronize(s));
-            if (!handover || h->h_ct->wide_cands <= wide_cap(nb)) break;
-            // a candidate without a place is a re-seeding that did not happen: the batch again, every phase with its own lane
-            float lost = 0;
-            GAB_HIP(hipEventElapsedTime(&lost, h->ev[0], h->ev[1]));
-            kms += lost;
-            handover = false;
-            pt[GAB_FMI_PATH_RERUNS]++;
-        }
-        int over_cap = h->h_ct->max_per_read > cap ? h->h_ct->max_per_read : 0;   // the counters of THIS round are the batch's
         float ms = 0;
-        GAB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        kms += ms;
-        FmiCounters c = *h->h_ct;                             // (a copy: the pinned one is read into again below)
-        int32_t n_ovf = 0;
-        int32_t *d_ids = nullptr;
-        int64_t round = 0;
-        if (over_cap) {
-            // Some reads found more SMEMs than a first-round slot holds (low-complexity reads; a handful among millions of
-            // real ones): they alone run again with slots of the size the worst of them needs, in as many parts as the
-            // scratch budget asks for, and their records go to the places fmi_compact leaves open.
-            rc = h->ovf.reserve(4 * (size_t)nb + 64);
-            if (rc) return rc;
-            d_ids = h->ovf.as<int32_t>();
-            hipLaunchKernelGGL(fmi_list_overflowed, dim3(blocks), dim3(256), 0, s, d_counts, nb, cap, d_ids, &d_ct->n_ovf, &d_ct->ovf_sum);
-            GAB_HIP(hipGetLastError());
-            GAB_HIP(hipMemcpyAsync(&n_ovf, &d_ct->n_ovf, 4, hipMemcpyDeviceToHost, s));
-            GAB_HIP(hipStreamSynchronize(s));
-            auto plan = [&]() -> int {
-                const int64_t per_round = std::max<int64_t>(1, (int64_t)(budget / (sizeof(OutRec) * (size_t)over_cap)));
-                round = std::min<int64_t>(n_ovf, per_round);
-                return h->slots2.reserve(sizeof(OutRec) * (size_t)over_cap * (size_t)round);
-            };
-            if (c.n_defer && n_ovf) {
-                // Pass 1 alone overflowed the slot of some of them, and pass 2 -- which reads the records of pass 1 back from the
-                // slot -- did not run for those (defer[]): their counts, and so the batch's total, its largest count and the offsets
-                // fmi_compact derives from the counts, are not final yet.  A launch of the second round's kernel over the overflowed
-                // reads, with slots that hold the largest count so far (all of any read's pass 1), settles the counts; it keeps the
-                // counts of what the first round left out and drops the rest, and what it writes into the slots is not used.
-                rc = plan();
-                if (rc) return rc;
-                GAB_HIP(hipMemsetAsync(&d_ct->total, 0, sizeof(d_ct->total), s));
-                GAB_HIP(hipMemsetAsync(&d_ct->max_per_read, 0, sizeof(d_ct->max_per_read), s));
-                GAB_HIP(hipEventRecord(h->ev[0], s));
-                for (int64_t i0 = 0; i0 < n_ovf; i0 += round) {
-                    rc = seed(first, nb, (int32_t)std::min<int64_t>(round, n_ovf - i0), d_ids + i0, h->slots2.as<OutRec>(), over_cap, nullptr);
-                    if (rc) return rc;
-                }
-                GAB_HIP(hipEventRecord(h->ev[1], s));
-                GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(FmiCounters), hipMemcpyDeviceToHost, s));
-                GAB_HIP(hipStreamSynchronize(s));
-                GAB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-                kms += ms;
-                const FmiCounters &r = *h->h_ct;              // extensions, records, positions: the first round's and what this launch kept
-                c.ext_calls = r.ext_calls; c.rec_reads = r.rec_reads; c.tab_reads = r.tab_reads;
-                c.positions = r.positions; c.spills = r.spills; c.list_sum = r.list_sum;
-                c.total = c.total - r.ovf_sum + r.total;      // the overflowed reads' SMEMs, counted again
-                c.max_per_read = std::max(c.max_per_read, r.max_per_read);
-                over_cap = c.max_per_read;
-            }
-            rc = plan();
-            if (rc) return rc;
+        if ((rc = h->slots.reserve(sizeof(OutRec) * (size_t)kSlotCap * (size_t)nb)) != GAB_OK) return rc;
+        // ---- first round (again without hand-over if the candidates outgrew their queue); its counters are the batch's
+        if ((rc = fmi_first_round(c, first, nb, &seed_blocks_dbg, &ms)) != GAB_OK) return rc;
+        FmiCounters cnt = *h->h_ct;                           // (a copy: the pinned one is read into again below)
+        // ---- settle: which reads overflowed their slot, and the counts of those whose pass 2 had to wait
+        FmiOverflow ovf;
+        ovf.over_cap = cnt.max_per_read > kSlotCap ? cnt.max_per_read : 0;
+        if (ovf.over_cap) {
+            if ((rc = fmi_find_overflowed(c, nb, &ovf)) != GAB_OK) return rc;
+            if (cnt.n_defer && ovf.n && (rc = fmi_settle(c, first, &ovf, &cnt, &ms)) != GAB_OK) return rc;
+            if ((rc = fmi_size_parts(c, &ovf)) != GAB_OK) return rc;
         }
-        ext_total += c.ext_calls + c.tab_reads; rec_total += c.rec_reads;
-        {   // the counters of the round that is kept
-            pt[GAB_FMI_PATH_BATCHES]++;
-            pt[GAB_FMI_PATH_POSITIONS] += (int64_t)c.positions; pt[GAB_FMI_PATH_LIST_SUM] += (int64_t)c.list_sum; pt[GAB_FMI_PATH_SPILLS] += (int64_t)c.spills;
-            pt[GAB_FMI_PATH_INDEX_EXT] += (int64_t)c.ext_calls; pt[GAB_FMI_PATH_TABLE_EXT] += (int64_t)c.tab_reads;
-            if (handover && ldsq) {
-                pt[GAB_FMI_PATH_WIDE_ITEMS] += std::min<int64_t>(std::max(c.wide_items, 0), wide_cap(nb));
-                pt[GAB_FMI_PATH_WIDE_ENTRIES] += (int64_t)c.wide_top; pt[GAB_FMI_PATH_WIDE_CANDS] += c.wide_cands;
-            }
-            pt[GAB_FMI_PATH_MAX_PER_READ] = std::max<int64_t>(pt[GAB_FMI_PATH_MAX_PER_READ], c.max_per_read);
-            pt[GAB_FMI_PATH_OVERFLOW_READS] += n_ovf; pt[GAB_FMI_PATH_SECOND_ROUND_PARTS] += n_ovf ? gab_ceil_div((int64_t)n_ovf, round) : 0;
-        }
+        ext_total += cnt.ext_calls + cnt.tab_reads; rec_total += cnt.rec_reads;
+        fmi_book_paths(c, cnt, ovf, nb);
         if (h->tun.fmi_debug)
             fprintf(stderr, "[gab_fmi] batch of %d reads: %d waves (%d per CU), %.3f ms, %llu index extensions + %llu table look-ups, %llu wave steps -> %.1f extensions per step; %llu positions, %llu spilled, mean list %.2f\n",
-                    nb, seed_blocks_dbg, waves_per_cu, ms, c.ext_calls, c.tab_reads, c.wave_steps,
-                    (double)(c.ext_calls + c.tab_reads) / (double)(c.wave_steps ? c.wave_steps : 1), c.positions,
-                    c.spills, (double)c.list_sum / (double)(c.positions ? c.positions : 1));
-        if (h->tun.fmi_debug && c.wide_items)
+                    nb, seed_blocks_dbg, p.waves_per_cu, ms, cnt.ext_calls, cnt.tab_reads, cnt.wave_steps,
+                    (double)(cnt.ext_calls + cnt.tab_reads) / (double)(cnt.wave_steps ? cnt.wave_steps : 1), cnt.positions,
+                    cnt.spills, (double)cnt.list_sum / (double)(cnt.positions ? cnt.positions : 1));
+        if (h->tun.fmi_debug && cnt.wide_items)
             fprintf(stderr, "[gab_fmi]   %d wide backward phases handed over (%u list entries), %d re-seeding candidates from them\n",
-                    c.wide_items, c.wide_top, c.wide_cands);
-        const int64_t add = (int64_t)c.total;
-        if ((size_t)(total + add) > out_cap) {
-            // grow, keeping what earlier batches wrote
-            size_t ncap = std::max<size_t>(out_cap * 2, (size_t)(total + add));
-            gab_devbuf bigger;
-            rc = bigger.reserve(ncap * sizeof(gab_smem));
-            if (rc) return rc;
-            GAB_HIP(hipMemcpyAsync(bigger.p, h->out.p, (size_t)total * sizeof(gab_smem), hipMemcpyDeviceToDevice, s));
-            GAB_HIP(hipStreamSynchronize(s));
-            h->out.release();
-            h->out = bigger;
-            out_cap = ncap;
-            pt[GAB_FMI_PATH_OUT_GROWTHS]++;
-        }
-        hipLaunchKernelGGL(fmi_block_sums, dim3(blocks), dim3(256), 0, s, d_counts, nb, d_bs);
-        hipLaunchKernelGGL(fmi_scan_blocks, dim3(1), dim3(1024), 0, s, d_bs, blocks, total);
-        hipLaunchKernelGGL(fmi_compact, dim3(blocks), dim3(256), 0, s, d_counts, nb, d_bs, h->slots.as<OutRec>(), cap, first,
-                           h->roff.as<int64_t>(), h->out.as<gab_smem>());
-        GAB_HIP(hipGetLastError());
-        if (n_ovf) {
-            // the second round: every count is final, and so is what the kernels counted; this round's counts are dropped
+                    cnt.wide_items, cnt.wide_top, cnt.wide_cands);
+        // ---- append
+        const int64_t add = (int64_t)cnt.total;
+        if ((rc = fmi_append_batch(c, first, nb, total, add, &out_cap)) != GAB_OK) return rc;
+        // ---- second round: every count is final, and so is what the kernels counted; this round's counts are dropped
+        if (ovf.n) {
             if (h->tun.fmi_debug)
                 fprintf(stderr, "[gab_fmi] %d read(s) overflowed their %d-record slot (worst: %d records): second round in %lld part(s)\n",
-                        n_ovf, cap, over_cap, (long long)gab_ceil_div((int64_t)n_ovf, round));
-            GAB_HIP(hipEventRecord(h->ev[0], s));
-            for (int64_t i0 = 0; i0 < n_ovf; i0 += round) {
-                const int32_t cnt = (int32_t)std::min<int64_t>(round, n_ovf - i0);
-                rc = seed(first, nb, cnt, d_ids + i0, h->slots2.as<OutRec>(), over_cap, nullptr);
-                if (rc) return rc;
-                hipLaunchKernelGGL(fmi_compact_overflowed, dim3((unsigned)gab_ceil_div((int64_t)cnt, 256)), dim3(256), 0, s, d_counts, d_ids + i0,
-                                   cnt, h->slots2.as<OutRec>(), over_cap, first, h->roff.as<int64_t>(), h->out.as<gab_smem>());
-                GAB_HIP(hipGetLastError());
-            }
-            GAB_HIP(hipEventRecord(h->ev[1], s));
-            GAB_HIP(hipEventSynchronize(h->ev[1]));
-            GAB_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-            kms += ms;
+                        ovf.n, kSlotCap, ovf.over_cap, (long long)gab_ceil_div((int64_t)ovf.n, ovf.round));
+            if ((rc = fmi_run_overflowed(c, first, ovf, true, &ms)) != GAB_OK) return rc;
         }
         total += add;
         first += nb;
@@ -1497,12 +1571,35 @@ extern "C" int gab_fmi_seed_device(gab_fmi *h, const uint8_t *d_enc, int32_t str
     GAB_HIP(hipStreamSynchronize(s));
     *nout = total;
     if (d_out) *d_out = h->out.as<gab_smem>();
-    h->ext_calls = (int64_t)ext_total; h->rec_reads = (int64_t)rec_total; h->nsmem = total; h->kernel_ms = kms;
-    pt[GAB_FMI_PATH_FORM] = ldsq ? 1 : 0; pt[GAB_FMI_PATH_LDS_ENTRIES] = lds_entries; pt[GAB_FMI_PATH_LIST_ENTRY_BYTES] = ldsq ? (narrow_lists ? 13 : 16) : 0;
-    pt[GAB_FMI_PATH_KMER_DEPTH] = ldsq ? h->ix.kmer_depth : 0;
-    pt[GAB_FMI_PATH_WIDE_MIN] = ldsq && handover ? (h->handover_env > 1 ? h->handover_env : kWideMin) : 0;   // (0 too once a batch had to run again without)
-    memcpy(h->paths, pt, sizeof pt);
-    h->have_stats = true;
+    int64_t *pt = c.pt;
+    pt[GAB_FMI_PATH_FORM] = p.ldsq ? 1 : 0; pt[GAB_FMI_PATH_LDS_ENTRIES] = p.lds_entries; pt[GAB_FMI_PATH_LIST_ENTRY_BYTES] = p.ldsq ? (p.narrow_lists ? 13 : 16) : 0;
+    pt[GAB_FMI_PATH_KMER_DEPTH] = p.ldsq ? h->ix.kmer_depth : 0;
+    pt[GAB_FMI_PATH_WIDE_MIN] = p.ldsq && c.handover ? fmi_wide_min(h) : 0;   // (0 too once a batch had to run again without)
+    h->last.ext_calls = (int64_t)ext_total; h->last.rec_reads = (int64_t)rec_total; h->last.nsmem = total; h->last.kernel_ms = c.kms;
+    memcpy(h->last.paths, pt, sizeof c.pt);
+    h->last.have = true;
+    return GAB_OK;
+}
+
+// The host-pointer entry points: where the reads (o_len bytes reserved) and their lengths lie in the staging buffer ...
+static size_t fmi_io_bytes(int64_t nreads, int32_t stride, size_t *o_len) {
+    *o_len = ((size_t)nreads * (size_t)stride + 255) & ~(size_t)255;
+    return *o_len + 4 * (size_t)nreads;
+}
+// ... and the copy there, on the handle's private stream
+static int fmi_stage_reads(gab_fmi *h, const uint8_t *enc, int32_t stride, const int32_t *len, int64_t nreads, hipStream_t *s,
+                           const uint8_t **d_enc, const int32_t **d_len) {
+    size_t o_len = 0;
+    int rc = h->io.reserve(fmi_io_bytes(nreads, stride, &o_len));
+    if (rc) return rc;
+    if ((rc = h->hs.get(s)) != GAB_OK) return rc;
+    char *b = h->io.as<char>();
+    *d_enc = (const uint8_t *)b; *d_len = (const int32_t *)(b + o_len);
+    // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
+    std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
+    GAB_HIP(hipMemcpyAsync(b, enc, (size_t)nreads * (size_t)stride, hipMemcpyHostToDevice, *s));
+    GAB_HIP(hipMemcpyAsync(b + o_len, len, 4 * (size_t)nreads, hipMemcpyHostToDevice, *s));
+    GAB_HIP(hipStreamSynchronize(*s));
     return GAB_OK;
 }
 
@@ -1515,23 +1612,13 @@ extern "C" int gab_fmi_seed(gab_fmi *h, const uint8_t *enc, int32_t stride, cons
     if (nreads == 0) return GAB_OK;
     GAB_CHECK(enc && len && stride > 0, "gab_fmi_seed: NULL buffer");
     gab_device_guard g(h->device);
-    const size_t eb = (size_t)nreads * (size_t)stride;
-    const size_t o_len = (eb + 255) & ~(size_t)255;
-    int rc = h->io.reserve(o_len + 4 * (size_t)nreads);
-    if (rc) return rc;
     hipStream_t s = nullptr;
-    if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    char *b = h->io.as<char>();
-    {   // the copies of one chunk at a time per GPU (gab_core.hip: the workers of a GPU must not copy in lockstep)
-        std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
-        GAB_HIP(hipMemcpyAsync(b, enc, eb, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_len, len, 4 * (size_t)nreads, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
+    const uint8_t *d_enc = nullptr; const int32_t *d_len = nullptr;
+    int rc = fmi_stage_reads(h, enc, stride, len, nreads, &s, &d_enc, &d_len);
+    if (rc) return rc;
     const gab_smem *d_out = nullptr;
     int64_t n = 0;
-    rc = gab_fmi_seed_device(h, (const uint8_t *)b, stride, (const int32_t *)(b + o_len), nreads, min_seed_len, &d_out,
-                             nullptr, &n, s);
+    rc = gab_fmi_seed_device(h, d_enc, stride, d_len, nreads, min_seed_len, &d_out, nullptr, &n, s);
     if (rc) return rc;
     gab_smem *host = (gab_smem *)malloc(sizeof(gab_smem) * (size_t)(n > 0 ? n : 1));
     if (!host) { gab_set_error("gab_fmi_seed: out of host memory"); return GAB_ENOMEM; }
@@ -1559,23 +1646,13 @@ extern "C" int gab_fmi_seed_into(gab_fmi *h, const uint8_t *enc, int32_t stride,
     if (nreads == 0) return GAB_OK;
     GAB_CHECK(enc && len && stride > 0, "gab_fmi_seed_into: NULL buffer");
     gab_device_guard g(h->device);
-    const size_t eb = (size_t)nreads * (size_t)stride;
-    const size_t o_len = (eb + 255) & ~(size_t)255;
-    int rc = h->io.reserve(o_len + 4 * (size_t)nreads);
-    if (rc) return rc;
     hipStream_t s = nullptr;
-    if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
-    char *b = h->io.as<char>();
-    {
-        std::lock_guard<std::mutex> gate(gab_h2d_mutex(h->device));
-        GAB_HIP(hipMemcpyAsync(b, enc, eb, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipMemcpyAsync(b + o_len, len, 4 * (size_t)nreads, hipMemcpyHostToDevice, s));
-        GAB_HIP(hipStreamSynchronize(s));
-    }
+    const uint8_t *d_enc = nullptr; const int32_t *d_len = nullptr;
+    int rc = fmi_stage_reads(h, enc, stride, len, nreads, &s, &d_enc, &d_len);
+    if (rc) return rc;
     const gab_smem *d_out = nullptr;
     int64_t n = 0;
-    rc = gab_fmi_seed_device(h, (const uint8_t *)b, stride, (const int32_t *)(b + o_len), nreads, min_seed_len, &d_out,
-                             nullptr, &n, s);
+    rc = gab_fmi_seed_device(h, d_enc, stride, d_len, nreads, min_seed_len, &d_out, nullptr, &n, s);
     if (rc) return rc;
     *nout = n;
     if (n > capacity) {
@@ -1594,25 +1671,20 @@ extern "C" int gab_fmi_reserve(gab_fmi *h, int64_t max_reads, int32_t stride) {
     GAB_CHECK(max_reads >= 0 && max_reads < (1ll << 31) && stride > 0, "gab_fmi_reserve: size out of range");
     if (max_reads == 0) return GAB_OK;
     gab_device_guard g(h->device);
-    const size_t eb = (size_t)max_reads * (size_t)stride, o_len = (eb + 255) & ~(size_t)255;
-    int rc = h->io.reserve(std::max<size_t>(o_len + 4 * (size_t)max_reads, (size_t)4 << 20));
+    size_t o_len = 0;
+    const size_t io_bytes = fmi_io_bytes(max_reads, stride, &o_len);
+    int rc = h->io.reserve(std::max<size_t>(io_bytes, (size_t)4 << 20));
     if (rc) return rc;
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
     // max_reads reads of length 0: every buffer of the path gets the size a real batch of that many reads starts with, every
     // kernel runs once, nothing is found
-    GAB_HIP(hipMemsetAsync(h->io.p, 0, o_len + 4 * (size_t)max_reads, s));
+    GAB_HIP(hipMemsetAsync(h->io.p, 0, io_bytes, s));
     const gab_smem *d_out = nullptr;
     int64_t n = 0;
-    const bool had = h->have_stats;                          // the answers of gab_fmi_last_* stay those of the last real run
-    const int64_t ext_was = h->ext_calls, rec_was = h->rec_reads, nsmem_was = h->nsmem;
-    const float ms_was = h->kernel_ms;
-    int64_t paths_were[GAB_FMI_PATHS];
-    memcpy(paths_were, h->paths, sizeof paths_were);
+    const FmiLast was = h->last;                             // the answers of gab_fmi_last_* stay those of the last real run
     rc = gab_fmi_seed_device(h, h->io.as<uint8_t>(), stride, (const int32_t *)(h->io.as<char>() + o_len), max_reads, 19, &d_out, nullptr, &n, s);
-    h->have_stats = had;
-    h->ext_calls = ext_was; h->rec_reads = rec_was; h->nsmem = nsmem_was; h->kernel_ms = ms_was;
-    memcpy(h->paths, paths_were, sizeof paths_were);
+    h->last = was;
     if (rc) return rc;
     // the output of a real batch: ~8 records per read of 151 bases (the device array grows by doubling from 16 per read)
     return gab_warm_copy_engines(s, h->io.p, h->io.cap);
@@ -1620,25 +1692,25 @@ extern "C" int gab_fmi_reserve(gab_fmi *h, int64_t max_reads, int32_t stride) {
 
 extern "C" int gab_fmi_last_stats(gab_fmi *h, int64_t *ext_calls, int64_t *nsmem, float *kernel_ms) {
     GAB_CHECK(h, "gab_fmi_last_stats: NULL handle");
-    GAB_CHECK(h->have_stats, "gab_fmi_last_stats: no completed run on this handle");
-    if (ext_calls) *ext_calls = h->ext_calls;
-    if (nsmem) *nsmem = h->nsmem;
-    if (kernel_ms) *kernel_ms = h->kernel_ms;
+    GAB_CHECK(h->last.have, "gab_fmi_last_stats: no completed run on this handle");
+    if (ext_calls) *ext_calls = h->last.ext_calls;
+    if (nsmem) *nsmem = h->last.nsmem;
+    if (kernel_ms) *kernel_ms = h->last.kernel_ms;
     return GAB_OK;
 }
 
 extern "C" int gab_fmi_last_paths(gab_fmi *h, int64_t paths[GAB_FMI_PATHS]) {
     GAB_CHECK(h, "gab_fmi_last_paths: NULL handle");
     GAB_CHECK(paths, "gab_fmi_last_paths: NULL argument");
-    GAB_CHECK(h->have_stats, "gab_fmi_last_paths: no completed run on this handle");
-    memcpy(paths, h->paths, sizeof h->paths);
+    GAB_CHECK(h->last.have, "gab_fmi_last_paths: no completed run on this handle");
+    memcpy(paths, h->last.paths, sizeof h->last.paths);
     return GAB_OK;
 }
 
 extern "C" int gab_fmi_last_records(gab_fmi *h, int64_t *cp_occ_records) {
     GAB_CHECK(h, "gab_fmi_last_records: NULL handle");
-    GAB_CHECK(h->have_stats, "gab_fmi_last_records: no completed run on this handle");
-    if (cp_occ_records) *cp_occ_records = h->rec_reads;
+    GAB_CHECK(h->last.have, "gab_fmi_last_records: no completed run on this handle");
+    if (cp_occ_records) *cp_occ_records = h->last.rec_reads;
     return GAB_OK;
 }
 

@@ -97,3 +97,32 @@ def test_last_paths_needs_a_run_and_survives_reserve(monkeypatch):
     f.reserve(500, 151)
     assert f.last_paths() == before and f.last_stats()["ext_calls"] == stats["ext_calls"]
     f.close()
+
+
+def test_clone_takes_the_hand_over_from_its_source_and_the_ring_from_its_own_environment(monkeypatch):
+    """gab_fmi_clone: the scratch budget, batch, waves, hand-over threshold and queue places are the SOURCE handle's, whatever the
+    environment says when the clone is made; ring entries, list format and debug are read from that environment"""
+    from genarchbench_amd.fmi import FMI_search
+    idx, reads = cases.load("nested")
+    w, woff, _ = oracle_of("nested", 19)
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("GAB_FMI_WIDE", "4"); monkeypatch.setenv("GAB_FMI_BATCH", "1024")
+    owner = FMI_search(arrays=(idx.ref_seq_len, idx.count, idx.cp_occ, idx.sentinel_index))
+    try:
+        monkeypatch.setenv("GAB_FMI_WIDE", "0"); monkeypatch.setenv("GAB_FMI_LDS_ENTRIES", "4")
+        clone = owner.clone()
+        try:
+            got, goff = clone.seed(reads, 19)
+            paths = clone.last_paths()
+        finally:
+            clone.close()
+    finally:
+        owner.close()
+    print(f"\nclone: {paths}")
+    assert paths["wide_min"] == 4 and paths["wide_items"] > 0      # the source's GAB_FMI_WIDE=4, not the environment's 0
+    assert paths["lds_entries"] == 4                               # the clone's own environment
+    np.testing.assert_array_equal(goff, woff)
+    assert len(got) == len(w)
+    for fld in ("rid", "m", "n", "k", "l", "s"):
+        np.testing.assert_array_equal(got[fld], w[fld], err_msg=fld)
