@@ -13,3 +13,4 @@ import os as _os
 _os.environ.setdefault("GPU_PINNED_MIN_XFER_SIZE", "1000000")
 
 from ._lib import GabError, build, lib, version  # noqa: F401
+from .abea import EventAligner  # noqa: F401

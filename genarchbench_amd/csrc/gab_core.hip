@@ -137,6 +137,7 @@ void gab_tuning_load(gab_tuning *t) {
     t->fmi_wide_lists = num("GAB_FMI_WIDE_LISTS", 0) != 0; t->fmi_debug = on("GAB_FMI_DEBUG");
     t->fmi_batch = num("GAB_FMI_BATCH", 0); t->fmi_scratch_mb = num("GAB_FMI_SCRATCH_MB", 0);
     t->kmer_part_floor = num("GAB_KMER_PART_FLOOR", 0) != 0;
+    t->abea_trace_bytes = num("GAB_ABEA_TRACE_BYTES", 0);
 }
 
 // ---- plain device-memory helpers for C callers that keep data on the GPU between two entry points ----------------

@@ -114,6 +114,8 @@ struct gab_tuning {
     long long fmi_batch = 0, fmi_scratch_mb = 0;
     // kmer-cnt
     bool kmer_part_floor = false;                    // GAB_KMER_PART_FLOOR: a partitioned count starts in the 16-line floor table
+    // abea
+    long long abea_trace_bytes = 0;                  // GAB_ABEA_TRACE_BYTES: trace budget of one launch, 0 = the default
 };
 void gab_tuning_load(gab_tuning *t);
 bool gab_tuning_live();                             // $GAB_TUNING_LIVE

@@ -716,6 +716,56 @@ int gab_chain_parse_device(gab_parser *p, const char *d_text, int64_t nbytes, ga
 /* last parse: kernel milliseconds (HIP events on the launch stream, excluding the host-to-device copy of the text) */
 int gab_parser_last_stats(gab_parser *p, float *kernel_ms);
 
+/* ---- abea: adaptive banded event alignment (f5c / nanopolish) ------------------------------------------
+ * Replaces  the loop of align_db over align_single -> align()      abea/src/f5c.c:1367-1394
+ *           (where the reference's own, disabled, align_cuda hook sits; semantics: align(), abea/src/align.c:169-548).
+ * One call aligns a batch of reads: the events of each read against the 6-mers of its base string, Suzuki-Kasahara adaptive
+ * band of 100 cells, traceback, the reference's three quality checks.  The arithmetic is the reference's built WITHOUT fused
+ * multiply-add (-msse4.1 / -mavx2, the first two choices of its Makefile): fp32 emission rounded after every operation, the
+ * three transition sums in double rounded to float once, per-read constants in double with libm on the host.
+ * One defined deviation: when no event has the last k-mer inside its band (the end scan of align.c:418-434 finds nothing
+ * finite) the reference backtracks from a cell outside the band; this library returns 0 pairs, path_len 0, end_event 0,
+ * max_gap 0, avg_log_emission 0 and the flag GAB_ABEA_NO_END alone.
+ * Input rules: a byte outside "ACGT" ranks as 'A' (get_rank, align.c:10-23; lower case is not mapped); seq_len >= 6 and
+ * n_events >= 1, anything else is GAB_EINVAL naming the read.  Out of scope: event detection, the scaling estimate
+ * (estimate_scalings_using_mom, align.c:49-97: the caller passes scale and shift), postalign and what follows it. */
+#define GAB_ABEA_K 6
+#define GAB_ABEA_BANDWIDTH 100
+#define GAB_ABEA_NKMER 4096
+typedef struct gab_abea gab_abea;
+typedef struct { int32_t ref_pos, read_pos; } gab_abea_pair;        /* AlignedPair, f5c.h:163-166: k-mer index, event index */
+enum { GAB_ABEA_LOW_EMISSION = 1, GAB_ABEA_NOT_SPANNED = 2, GAB_ABEA_GAP = 4, GAB_ABEA_NO_END = 8 };
+typedef struct {
+    int32_t n_pairs;      /* what align() returns: 0 when a quality check failed */
+    int32_t path_len;     /* pairs on the path before the checks; pairs[] holds them (in read order, as the reference leaves them) even when n_pairs = 0 */
+    int32_t end_event, max_gap;
+    uint32_t flags; int32_t pad;
+    double avg_log_emission;
+    int64_t fills;        /* cells filled, the reference's `fills` */
+} gab_abea_read;
+/* the pore model: GAB_ABEA_NKMER entries indexed by k-mer rank; level_log_stdv NULL = (float)log(level_stdv), model.c:53 */
+int gab_abea_create(int device, const float *level_mean, const float *level_stdv, const float *level_log_stdv, gab_abea **out);
+void gab_abea_destroy(gab_abea *h);
+/* optional: size the handle's buffers for host calls of up to max_reads reads, max_bases bases and max_events events in all */
+int gab_abea_reserve(gab_abea *h, int64_t max_reads, int64_t max_bases, int64_t max_events);
+/* Host buffers.  Read i: bases seq[seq_off[i] .. +seq_len[i]), events event_mean[event_off[i] .. +n_events[i]), scalings
+ * scale[i], shift[i].  Its pairs go to pairs[pair_off[i] ..]: the caller gives n_events[i] + seq_len[i] - 5 pairs of room per
+ * read (the reference gives 2 * n_events and asserts), regions disjoint; res[i] is the read's record. */
+int gab_abea_align(gab_abea *h, const char *seq, const int64_t *seq_off, const int32_t *seq_len,
+                   const float *event_mean, const int64_t *event_off, const int32_t *n_events,
+                   const float *scale, const float *shift, int64_t n_reads,
+                   gab_abea_pair *pairs, const int64_t *pair_off, gab_abea_read *res);
+/* Device buffers.  seq_bytes / event_count / pair_count = sizes of the three slabs (bytes, floats, pairs), for bounds
+ * validation.  Synchronises `stream` twice: once at the start (the launch plan needs the lengths on the host) and once at
+ * the end (the stage times of gab_abea_last_stats), so pairs and res are complete when it returns. */
+int gab_abea_align_device(gab_abea *h, const char *seq, int64_t seq_bytes, const int64_t *seq_off, const int32_t *seq_len,
+                          const float *event_mean, int64_t event_count, const int64_t *event_off, const int32_t *n_events,
+                          const float *scale, const float *shift, int64_t n_reads,
+                          gab_abea_pair *pairs, int64_t pair_count, const int64_t *pair_off, gab_abea_read *res, void *stream);
+/* last call: cells filled (the sum of `fills`), bands swept, launches the call was cut into (GAB_ABEA_TRACE_BYTES: the
+ * trace budget of one launch), device time of the DP kernels and of all kernels (HIP events on the stream, ms).  Any may be NULL. */
+int gab_abea_last_stats(gab_abea *h, int64_t *cells, int64_t *bands, int64_t *launches, float *kernel_ms, float *total_ms);
+
 #ifdef __cplusplus
 }
 #endif
