@@ -1,5 +1,7 @@
 """Host-side mirror of the adaptive banded event alignment, align() (abea/src/align.c:169-548), over the C ABI
-(include/gab.h: gab_abea_align, gab_abea_align_device): the loop of align_db over its reads (abea/src/f5c.c:1367-1394) as one call."""
+(include/gab.h: gab_abea_align, gab_abea_align_device): the loop of align_db over its reads (abea/src/f5c.c:1367-1394) as one call;
+and of the two steps before it, event detection and the scaling estimate (gab_abea_events, gab_abea_scalings: event_single,
+f5c.c:1241-1264), so that raw samples go in and aligned pairs come out (EventAligner.signal_to_pairs)."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +12,7 @@ K = 6             # GAB_ABEA_K
 BANDWIDTH = 100   # GAB_ABEA_BANDWIDTH
 NKMER = 4096      # GAB_ABEA_NKMER
 LOW_EMISSION, NOT_SPANNED, GAP, NO_END = 1, 2, 4, 8      # gab_abea_read.flags
+ERANGE = -34      # GAB_ERANGE
 
 PAIR = np.dtype([("ref_pos", np.int32), ("read_pos", np.int32)])
 READ = np.dtype([("n_pairs", np.int32), ("path_len", np.int32), ("end_event", np.int32), ("max_gap", np.int32), ("flags", np.uint32),
@@ -35,6 +38,24 @@ def pack_reads(reads):
     events = np.concatenate([np.asarray(r[1], np.float32) for r in reads]) if reads else np.zeros(0, np.float32)
     scale = np.array([r[2] for r in reads], np.float32); shift = np.array([r[3] for r in reads], np.float32)
     return seq, seq_off, seq_len, events, event_off, n_events, scale, shift, pair_off
+
+
+def events_shape():
+    """(chunk, warm-up) in samples of the speculative peak detector: GAB_ABEA_EVENTS_CHUNK, GAB_ABEA_EVENTS_WARMUP"""
+    chunk = C.c_int32(0); warmup = C.c_int32(0)
+    check(lib().gab_abea_events_shape(C.byref(chunk), C.byref(warmup)))
+    return chunk.value, warmup.value
+
+
+def pack_signals(signals):
+    """list of (raw samples, range, digitisation, offset) -> raw, raw_off, n_samples, range, digitisation, offset"""
+    n_samples = np.array([np.size(s[0]) for s in signals], np.int32)
+    raw_off = np.zeros(len(signals), np.int64)
+    if len(signals) > 1:
+        raw_off[1:] = np.cumsum(n_samples[:-1], dtype=np.int64)
+    raw = np.concatenate([np.asarray(s[0], np.float32).reshape(-1) for s in signals]) if signals else np.zeros(0, np.float32)
+    par = [np.array([s[t] for s in signals], np.float32) for t in (1, 2, 3)]
+    return raw, raw_off, n_samples, par[0], par[1], par[2]
 
 
 def pair_room(seq_len, n_events):
@@ -99,6 +120,118 @@ class EventAligner:
             C.c_void_p(events.data_ptr()), C.c_int64(events.numel()), C.c_void_p(event_off.data_ptr()), C.c_void_p(n_events.data_ptr()),
             C.c_void_p(scale.data_ptr()), C.c_void_p(shift.data_ptr()), C.c_int64(n), C.c_void_p(pairs.data_ptr()), C.c_int64(pairs.numel() // 2),
             C.c_void_p(pair_off.data_ptr()), C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+
+    # ---- event detection and the scaling estimate (gab_abea_events, gab_abea_scalings) ----------------------------------------
+    def events(self, raw, raw_off, n_samples, rng, digitisation, offset, event_cap=None, slabs=None):
+        """packed numpy arrays (pack_signals gives them) -> (rc, n_events, event_off, total, mean, stdv, start, length); rc is 0, or
+        ERANGE when the events do not fit event_cap (default: one per sample, always enough) -- the counts are valid then and the
+        slabs untouched.  slabs: four arrays (mean, stdv, start, length) to write into instead of new ones."""
+        raw = np.ascontiguousarray(raw, np.float32); raw_off = np.ascontiguousarray(raw_off, np.int64)
+        n_samples = np.ascontiguousarray(n_samples, np.int32)
+        rng = np.ascontiguousarray(rng, np.float32); digitisation = np.ascontiguousarray(digitisation, np.float32)
+        offset = np.ascontiguousarray(offset, np.float32)
+        n = n_samples.size
+        if event_cap is None:
+            event_cap = int(np.maximum(n_samples, 0).sum())
+        if slabs is None:
+            slabs = (np.zeros(event_cap, np.float32), np.zeros(event_cap, np.float32), np.zeros(event_cap, np.int32), np.zeros(event_cap, np.float32))
+        mean, stdv, start, length = slabs
+        if not (mean.dtype == stdv.dtype == length.dtype == np.float32 and start.dtype == np.int32) or min(a.size for a in slabs) < event_cap:
+            raise ValueError("slabs: float32, float32, int32, float32 arrays of event_cap entries at least")
+        n_events = np.zeros(n, np.int32); event_off = np.zeros(n, np.int64); total = C.c_int64(0)
+        rc = lib().gab_abea_events(self._h, _p(raw), _p(raw_off), _p(n_samples), _p(rng), _p(digitisation), _p(offset), C.c_int64(n),
+                                   _p(n_events), _p(event_off), _p(mean), _p(stdv), _p(start), _p(length), C.c_int64(event_cap), C.byref(total))
+        if rc not in (0, ERANGE):
+            check(rc)
+        return rc, n_events, event_off, total.value, mean, stdv, start, length
+
+    def detect_events(self, signals):
+        """list of (raw samples, range, digitisation, offset) -> per read a dict of its event table: mean, stdv, start, length"""
+        rc, n_events, event_off, _, mean, stdv, start, length = self.events(*pack_signals(signals))
+        check(rc)
+        return [dict(mean=mean[o:o + k], stdv=stdv[o:o + k], start=start[o:o + k], length=length[o:o + k]) for o, k in zip(event_off, n_events)]
+
+    def detect_events_device(self, raw, raw_off, n_samples, rng, digitisation, offset, n_events, event_off, mean, stdv, start, length, total, stream=0,
+                             event_cap=None):
+        """torch tensors on the handle's GPU: float32, int64, int32, float32 x 3 in; int32 n_events, int64 event_off, the four slabs
+        (float32, float32, int32, float32; their room, or event_cap if that is less) and a one-element int64 `total` out.
+        -> 0 or ERANGE"""
+        cap = min(mean.numel(), stdv.numel(), start.numel(), length.numel())
+        cap = cap if event_cap is None else min(cap, int(event_cap))
+        rc = lib().gab_abea_events_device(
+            self._h, C.c_void_p(raw.data_ptr()), C.c_int64(raw.numel()), C.c_void_p(raw_off.data_ptr()), C.c_void_p(n_samples.data_ptr()),
+            C.c_void_p(rng.data_ptr()), C.c_void_p(digitisation.data_ptr()), C.c_void_p(offset.data_ptr()), C.c_int64(n_samples.numel()),
+            C.c_void_p(n_events.data_ptr()), C.c_void_p(event_off.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(stdv.data_ptr()),
+            C.c_void_p(start.data_ptr()), C.c_void_p(length.data_ptr()), C.c_int64(cap), C.c_void_p(total.data_ptr()), C.c_void_p(stream))
+        if rc not in (0, ERANGE):
+            check(rc)
+        return rc
+
+    def scalings(self, seq, seq_off, seq_len, events, event_off, n_events):
+        """packed numpy arrays -> (scale, shift), float32 per read"""
+        seq = np.ascontiguousarray(seq, np.uint8); events = np.ascontiguousarray(events, np.float32)
+        seq_off = np.ascontiguousarray(seq_off, np.int64); event_off = np.ascontiguousarray(event_off, np.int64)
+        seq_len = np.ascontiguousarray(seq_len, np.int32); n_events = np.ascontiguousarray(n_events, np.int32)
+        n = seq_len.size
+        scale = np.zeros(n, np.float32); shift = np.zeros(n, np.float32)
+        check(lib().gab_abea_scalings(self._h, _p(seq), _p(seq_off), _p(seq_len), _p(events), _p(event_off), _p(n_events), C.c_int64(n), _p(scale), _p(shift)))
+        return scale, shift
+
+    def scalings_last_stats(self):
+        """the last scalings call: reads, and those whose event sum / k-mer level sum / sum of squared levels was added in order"""
+        v = [C.c_int64(-1) for _ in range(4)]
+        check(lib().gab_abea_scalings_last_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("reads", "event_sums_in_order", "kmer_sums_in_order", "kmer_sq_sums_in_order"), (x.value for x in v)))
+
+    def estimate_scalings(self, reads):
+        """list of (bases, event means) -> (scale, shift) by the method of moments against the handle's pore model"""
+        packed = pack_reads([(r[0], r[1], 0.0, 0.0) for r in reads])
+        return self.scalings(*packed[:6])
+
+    def estimate_scalings_device(self, seq, seq_off, seq_len, events, event_off, n_events, scale, shift, stream=0):
+        """torch tensors on the handle's GPU: uint8, int64, int32, float32, int64, int32 in; float32 scale and shift out"""
+        check(lib().gab_abea_scalings_device(
+            self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(seq_off.data_ptr()), C.c_void_p(seq_len.data_ptr()),
+            C.c_void_p(events.data_ptr()), C.c_int64(events.numel()), C.c_void_p(event_off.data_ptr()), C.c_void_p(n_events.data_ptr()),
+            C.c_int64(seq_len.numel()), C.c_void_p(scale.data_ptr()), C.c_void_p(shift.data_ptr()), C.c_void_p(stream)))
+
+    def signal_to_pairs(self, signals, seqs):
+        """signals: list of (raw samples, range, digitisation, offset); seqs: the reads' bases.  Events, then scalings, then the
+        alignment, on device buffers: only n_events comes to the host in between (the room of the pairs depends on it).
+        -> (pairs, pair_off, records, n_events, scale, shift) as numpy arrays"""
+        import torch
+        packed = pack_signals(signals)
+        n = len(signals)
+        dev = [torch.from_numpy(a).cuda() for a in packed]
+        cap = max(int(packed[2].sum()), 1)
+        n_events = torch.zeros(n, dtype=torch.int32, device="cuda"); event_off = torch.zeros(n, dtype=torch.int64, device="cuda")
+        mean = torch.empty(cap, dtype=torch.float32, device="cuda"); stdv = torch.empty_like(mean); length = torch.empty_like(mean)
+        start = torch.empty(cap, dtype=torch.int32, device="cuda"); total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        check(self.detect_events_device(*dev, n_events, event_off, mean, stdv, start, length, total))
+        ne = n_events.cpu().numpy()
+        seq_len = np.array([len(s) for s in seqs], np.int32)
+        seq_off = np.zeros(n, np.int64); pair_off = np.zeros(n, np.int64)
+        room = pair_room(seq_len, ne)
+        if n > 1:
+            seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64); pair_off[1:] = np.cumsum(room[:-1])
+        seq = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8).copy()
+        d_seq, d_so, d_sl, d_po = (torch.from_numpy(a).cuda() for a in (seq, seq_off, seq_len, pair_off))
+        scale = torch.zeros(n, dtype=torch.float32, device="cuda"); shift = torch.zeros_like(scale)
+        self.estimate_scalings_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift)
+        pairs = torch.full((max(int(room.sum()), 1), 2), -1, dtype=torch.int32, device="cuda")
+        res = torch.zeros(n * READ.itemsize, dtype=torch.uint8, device="cuda")
+        self.align_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift, pairs, d_po, res)
+        return (pairs.cpu().numpy().reshape(-1).view(PAIR), pair_off, res.cpu().numpy().view(READ), ne, scale.cpu().numpy(), shift.cpu().numpy())
+
+    def events_last_stats(self):
+        """the last detect_events call: samples, events, reads whose sums were added in order, chunks, chunks run again, kernel and
+        whole-call device time, and the kernel time by stage (ms)"""
+        v = [C.c_int64(-1) for _ in range(5)]; kms = C.c_float(-1); tms = C.c_float(-1); st = [C.c_float(-1) for _ in range(3)]
+        check(lib().gab_abea_events_last_stats(self._h, *[C.byref(x) for x in v], C.byref(kms), C.byref(tms)))
+        check(lib().gab_abea_events_stage_ms(self._h, *[C.byref(x) for x in st]))
+        names = ("samples", "events", "reads_serial_sums", "chunks", "chunks_redone")
+        return {**{k: x.value for k, x in zip(names, v)}, "kernel_ms": kms.value, "total_ms": tms.value,
+                "sums_ms": st[0].value, "detect_ms": st[1].value, "fill_ms": st[2].value}
 
     def last_stats(self):
         """cells filled, bands swept, launches, and the device time of the DP kernels and of all kernels (ms) of the last call"""

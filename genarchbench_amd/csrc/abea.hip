@@ -23,6 +23,7 @@
 #include <vector>
 #include "gab_internal.h"
 #include "gab_pair_stage.h"
+#include "abea_handle.h"
 
 #pragma clang fp contract(off)
 
@@ -226,17 +227,7 @@ __global__ __launch_bounds__(64) void abea_backtrack(const abea_job *jobs, const
 
 }  // namespace
 
-struct gab_abea {
-    gab_host_stream hs;
-    int device = 0;
-    gab_devbuf model;       // mean | stdv | log stdv
-    gab_devbuf io;          // staging of the host-pointer entry point
-    gab_devbuf jobs, ends, kparam, trace;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // before prep, before the sweep, after it, after the backtrack
-    gab_tuning tune = gab_tuning_loaded();
-    int64_t cells = 0, bands = 0, launches = 0;
-    float kernel_ms = 0.f, total_ms = 0.f;
-};
+// struct gab_abea: abea_handle.h (shared with abea_events.hip)
 
 extern "C" int gab_abea_create(int device, const float *level_mean, const float *level_stdv, const float *level_log_stdv, gab_abea **out) {
     if (!out || !level_mean || !level_stdv) { gab_set_error("gab_abea_create: NULL argument"); return GAB_EINVAL; }

@@ -1,0 +1,29 @@
+// The abea handle, shared by abea.hip (align) and abea_events.hip (event detection, scaling estimate).
+#pragma once
+#include "gab_internal.h"
+
+// what abea_events.hip keeps on the handle; its destructor (abea_events.hip) frees it when the handle is deleted
+struct gab_abea_events_state {
+    gab_devbuf io;          // staging of the host-pointer entry points
+    gab_devbuf plan;        // jobs | chunk -> read
+    gab_devbuf scratch;     // prefix sums, t-statistics, per-chunk peaks and detector states
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // start, after sums + t-statistics, after the detector, before / after the fill
+    int64_t samples = 0, events = 0, reads_serial_sums = 0, chunks = 0, chunks_redone = 0;
+    float sums_ms = 0.f, detect_ms = 0.f, fill_ms = 0.f, total_ms = 0.f;
+    gab_devbuf sc_ctr;      // the scaling estimate's counters
+    int64_t sc_reads = 0, sc_in_order[3] = {0, 0, 0};      // last gab_abea_scalings*: reads, and those whose event / k-mer / k-mer square sum was added in order
+    ~gab_abea_events_state();
+};
+
+struct gab_abea {
+    gab_host_stream hs;
+    int device = 0;
+    gab_devbuf model;       // mean | stdv | log stdv
+    gab_devbuf io;          // staging of the host-pointer entry point
+    gab_devbuf jobs, ends, kparam, trace;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // before prep, before the sweep, after it, after the backtrack
+    gab_tuning tune = gab_tuning_loaded();
+    int64_t cells = 0, bands = 0, launches = 0;
+    float kernel_ms = 0.f, total_ms = 0.f;
+    gab_abea_events_state events;
+};

@@ -727,8 +727,9 @@ int gab_parser_last_stats(gab_parser *p, float *kernel_ms);
  * finite) the reference backtracks from a cell outside the band; this library returns 0 pairs, path_len 0, end_event 0,
  * max_gap 0, avg_log_emission 0 and the flag GAB_ABEA_NO_END alone.
  * Input rules: a byte outside "ACGT" ranks as 'A' (get_rank, align.c:10-23; lower case is not mapped); seq_len >= 6 and
- * n_events >= 1, anything else is GAB_EINVAL naming the read.  Out of scope: event detection, the scaling estimate
- * (estimate_scalings_using_mom, align.c:49-97: the caller passes scale and shift), postalign and what follows it. */
+ * n_events >= 1, anything else is GAB_EINVAL naming the read.  The two steps before align() in the reference's timed region,
+ * event detection and the scaling estimate, are gab_abea_events and gab_abea_scalings below: their outputs are what this call
+ * takes.  Out of scope: postalign and what follows it. */
 #define GAB_ABEA_K 6
 #define GAB_ABEA_BANDWIDTH 100
 #define GAB_ABEA_NKMER 4096
@@ -765,6 +766,71 @@ int gab_abea_align_device(gab_abea *h, const char *seq, int64_t seq_bytes, const
 /* last call: cells filled (the sum of `fills`), bands swept, launches the call was cut into (GAB_ABEA_TRACE_BYTES: the
  * trace budget of one launch), device time of the DP kernels and of all kernels (HIP events on the stream, ms).  Any may be NULL. */
 int gab_abea_last_stats(gab_abea *h, int64_t *cells, int64_t *bands, int64_t *launches, float *kernel_ms, float *total_ms);
+
+/* ---- abea: event detection and the scaling estimate ------------------------------------------------------
+ * Replaces  event_single of event_db                                abea/src/f5c.c:1241-1264
+ *           = the pA conversion (f5c.c:1249-1253), getevents (abea/src/events.c:552-568) and
+ *             estimate_scalings_using_mom (abea/src/align.c:49-97), per read.
+ * Raw samples go in; the event table (structure of arrays) and the scalings come out in the layout gab_abea_align_device
+ * takes.  Bit for bit the reference built WITHOUT fused multiply-add: prefix sums in double (the square taken in float),
+ * compute_tstat for windows 3 and 6 with its mixed float / double evaluation (compiled as C++: fabs and sqrt at events.c:359
+ * are the float overloads), short_long_peak_detector as written (DNA parameters), create_event in float with correctly rounded
+ * sqrtf and divisions, the four sums of the scaling estimate in double in the reference's order, rounded to float once.
+ * NOT built: trim_and_segment_raw -- getevents discards what it returns (events.c:562), so it has no effect on the result.
+ * One defined deviation: for a read in which no peak fires the reference indexes peaks[n - 2] with n = 1, which is undefined;
+ * this library returns ONE event covering [0, n_samples), mean and stdv by create_event's formulas.
+ * Input rules: n_samples >= 1 (an int32_t, so below 2^31) and digitisation != 0, anything else is GAB_EINVAL naming the read;
+ * n_reads = 0 returns GAB_OK and writes nothing.  Signal already in pA: range = digitisation = 1, offset = 0 (the conversion
+ * (raw + offset) * (range / digitisation) in float is then the identity).
+ * How it runs: a read's sums are added wide when a per-read reduction proves them exact in any order (every addend a multiple
+ * of 2^q, their magnitudes summing to less than 2^(q + 53)), in the reference's order otherwise (reads_serial_sums; a tiny or
+ * huge sample, a NaN, an infinity or a denormal forces it).  The detector runs every chunk of GAB_ABEA_EVENTS_CHUNK samples at
+ * once from a cold state GAB_ABEA_EVENTS_WARMUP samples before it; a chunk whose assumed state at its boundary is not the state
+ * the chunk before it ended in is run again from the true state (chunks_redone). */
+#define GAB_ABEA_EVENTS_CHUNK 1024
+#define GAB_ABEA_EVENTS_WARMUP 64
+/* Host buffers.  Read i: samples raw[raw_off[i] .. +n_samples[i]), range[i], digitisation[i], offset[i].  Written: n_events[i],
+ * event_off[i] (the exclusive prefix sum of n_events: read i's events sit at event_off[i], back to back), *total_events, and
+ * the four slabs event_mean / event_stdv / event_start (first sample) / event_length (samples, float as the reference holds
+ * it), each with room for event_cap events.  More events than event_cap: GAB_ERANGE, the slabs are not touched, n_events,
+ * event_off and *total_events are complete and valid -- size the slabs and call again. */
+int gab_abea_events(gab_abea *h, const float *raw, const int64_t *raw_off, const int32_t *n_samples,
+                    const float *range, const float *digitisation, const float *offset, int64_t n_reads,
+                    int32_t *n_events, int64_t *event_off,
+                    float *event_mean, float *event_stdv, int32_t *event_start, float *event_length,
+                    int64_t event_cap, int64_t *total_events);
+/* Device buffers (total_events too); raw_count = floats in the raw slab, for bounds validation.  Synchronises `stream` at the
+ * start (the chunk plan needs the lengths on the host), once in the middle (n_events come to the host for event_off; nothing
+ * else does) and at the end.  The call needs about 40 bytes of scratch per sample on the handle. */
+int gab_abea_events_device(gab_abea *h, const float *raw, int64_t raw_count, const int64_t *raw_off, const int32_t *n_samples,
+                           const float *range, const float *digitisation, const float *offset, int64_t n_reads,
+                           int32_t *n_events, int64_t *event_off,
+                           float *event_mean, float *event_stdv, int32_t *event_start, float *event_length,
+                           int64_t event_cap, int64_t *total_events, void *stream);
+/* scale[i], shift[i] of read i by the method of moments, against the handle's pore model.  The k-mer rank rule is that of
+ * gab_abea_align (a byte outside "ACGT" ranks as 'A'); seq_len >= 6 and n_events >= 1, anything else is GAB_EINVAL naming the
+ * read.  The sums of the event means, of the k-mer levels and of the levels' squares are each added wide when the proof above
+ * shows them exact in any order, and in the reference's order otherwise; the sum of the squared double differences is not exact
+ * in any order and is always added in order. */
+int gab_abea_scalings(gab_abea *h, const char *seq, const int64_t *seq_off, const int32_t *seq_len,
+                      const float *event_mean, const int64_t *event_off, const int32_t *n_events, int64_t n_reads,
+                      float *scale, float *shift);
+/* Device buffers; seq_bytes / event_count = sizes of the two slabs, for bounds validation.  Complete when it returns. */
+int gab_abea_scalings_device(gab_abea *h, const char *seq, int64_t seq_bytes, const int64_t *seq_off, const int32_t *seq_len,
+                             const float *event_mean, int64_t event_count, const int64_t *event_off, const int32_t *n_events, int64_t n_reads,
+                             float *scale, float *shift, void *stream);
+/* last gab_abea_events* call: samples read, events found, reads whose sums were added in order, chunks, chunks run again,
+ * device time of the kernels and of the whole call from first to last kernel (HIP events on the stream, ms).  Any may be NULL. */
+int gab_abea_events_last_stats(gab_abea *h, int64_t *samples, int64_t *events, int64_t *reads_serial_sums,
+                               int64_t *chunks, int64_t *chunks_redone, float *kernel_ms, float *total_ms);
+/* last gab_abea_scalings* call: reads, and how many of them had the sum of their event means, of their k-mer levels and of the
+ * levels' squares added in the reference's order because it could not be proved order-free.  Any may be NULL. */
+int gab_abea_scalings_last_stats(gab_abea *h, int64_t *reads, int64_t *event_sums_in_order, int64_t *kmer_sums_in_order,
+                                 int64_t *kmer_sq_sums_in_order);
+/* the last gab_abea_events* call's kernel time by stage: proof + sums + t-statistics | detector + verification | event starts + fill */
+int gab_abea_events_stage_ms(gab_abea *h, float *sums_ms, float *detect_ms, float *fill_ms);
+/* GAB_ABEA_EVENTS_CHUNK and GAB_ABEA_EVENTS_WARMUP as the library was built (no GPU needed) */
+int gab_abea_events_shape(int32_t *chunk, int32_t *warmup);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,9 @@
 """abea throughput: a generated set of reads resident in HBM through gab_abea_align_device; median of warm repeats.
 
     python tools/abea_bench.py [--reads 4096] [--min-bases 5000] [--max-bases 15000] [--repeats 7] [--seed 1] [--json out.json]
+    python tools/abea_bench.py --signal --reads 1024      raw signal for the same kind of reads through gab_abea_events_device,
+                                                          gab_abea_scalings_device and gab_abea_align_device: samples/s, events/s,
+                                                          the stage times, chunks_redone and reads_serial_sums
 
 Reports reads/s, band cells/s (cells filled, the reference's `fills`), ms per launch, and the DP kernel's share of the device time
 against the rest (k-mer table and backtrack).  Wall time is taken around the call, which synchronises its stream before it returns."""
@@ -45,12 +48,103 @@ def generate(rng, n_reads, lo, hi):
                           np.array(scale, np.float32), np.array(shift, np.float32), off(room)), int(room.sum())
 
 
+RANGE, DIGITISATION = 1402.882, 8192.0      # pA over the ADC's span: a grid of about 0.17 pA
+
+
+def generate_signal(rng, mean, seq, seq_off, seq_len):
+    """raw samples for the same reads: the level of every k-mer held for 3 + geometric(1/6) samples (about 9), Gaussian noise of
+    1.5 pA, quantised to ADC codes (kept as float, as the reference holds them); one offset per read"""
+    from genarchbench_amd import abea
+    code_of = np.zeros(256, np.int64); code_of[np.frombuffer(b"ACGT", np.uint8)] = np.arange(4)
+    unit = RANGE / DIGITISATION
+    raws, offsets = [], []
+    for o, n in zip(seq_off, seq_len):
+        codes = code_of[seq[o:o + n]]
+        nk = int(n) - abea.K + 1
+        ranks = np.zeros(nk, np.int64)
+        for t in range(abea.K):
+            ranks = ranks * 4 + codes[t:t + nk]
+        dwell = 3 + rng.geometric(1 / 6.0, nk)
+        pa = np.repeat(mean[ranks].astype(np.float64), dwell) + 1.5 * rng.standard_normal(int(dwell.sum()))
+        offset = float(rng.integers(-20, 21))
+        raws.append(np.clip(np.rint(pa / unit - offset), -32768, 32767).astype(np.float32)); offsets.append(offset)
+    n_samples = np.array([r.size for r in raws], np.int32)
+    raw_off = np.concatenate([[0], np.cumsum(n_samples[:-1], dtype=np.int64)]).astype(np.int64)
+    n = len(raws)
+    return (np.concatenate(raws), raw_off, n_samples, np.full(n, RANGE, np.float32), np.full(n, DIGITISATION, np.float32), np.array(offsets, np.float32))
+
+
+def main_signal(a):
+    """the chain on the resident set: events, scalings, align; per stage the median wall time of the warm repeats"""
+    import genarchbench_amd  # noqa: F401
+    import torch
+    from genarchbench_amd import abea
+    rng = np.random.default_rng(a.seed)
+    (mean, stdv), packed, _ = generate(rng, a.reads, a.min_bases, a.max_bases)
+    sig = generate_signal(rng, mean, packed[0], packed[1], packed[2])
+    h = abea.EventAligner(mean, stdv)
+    n = a.reads
+    d_sig = [torch.from_numpy(x).cuda() for x in sig]
+    d_seq, d_so, d_sl = (torch.from_numpy(x).cuda() for x in packed[:3])
+    cap = int(sig[2].sum()) // 2 + n
+    n_events = torch.zeros(n, dtype=torch.int32, device="cuda"); event_off = torch.zeros(n, dtype=torch.int64, device="cuda")
+    ev_mean = torch.empty(cap, dtype=torch.float32, device="cuda"); ev_stdv = torch.empty_like(ev_mean); ev_len = torch.empty_like(ev_mean)
+    ev_start = torch.empty(cap, dtype=torch.int32, device="cuda"); total = torch.zeros(1, dtype=torch.int64, device="cuda")
+    scale = torch.zeros(n, dtype=torch.float32, device="cuda"); shift = torch.zeros_like(scale)
+    res = torch.zeros(n * abea.READ.itemsize, dtype=torch.uint8, device="cuda")
+    pairs = None
+    runs = []
+    for it in range(a.repeats + 1):                                  # the first run allocates: not counted
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = h.detect_events_device(*d_sig, n_events, event_off, ev_mean, ev_stdv, ev_start, ev_len, total)
+        t1 = time.perf_counter()
+        if rc:
+            raise SystemExit(f"{int(total.item())} events do not fit {cap}")
+        est = h.events_last_stats()
+        ne = n_events.cpu().numpy()
+        room = abea.pair_room(packed[2], ne)
+        pair_off = np.concatenate([[0], np.cumsum(room[:-1])]).astype(np.int64)
+        d_po = torch.from_numpy(pair_off).cuda()
+        if pairs is None:
+            pairs = torch.empty((int(room.sum()), 2), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        h.estimate_scalings_device(d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift)
+        t3 = time.perf_counter()
+        h.align_device(d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift, pairs, d_po, res)
+        t4 = time.perf_counter()
+        runs.append({"events_ms": (t1 - t0) * 1e3, "scalings_ms": (t3 - t2) * 1e3, "align_ms": (t4 - t3) * 1e3, "ev": est, "sc": h.scalings_last_stats(), "al": h.last_stats()})
+    warm = runs[1:]
+    med = lambda f: float(np.median([f(r) for r in warm]))
+    rec = res.cpu().numpy().view(abea.READ)
+    est = warm[-1]["ev"]
+    ev_ms = med(lambda r: r["events_ms"])
+    out = {"mode": "signal", "reads": n, "bases": int(packed[2].sum()), "samples": est["samples"], "events": est["events"], "repeats": a.repeats,
+           "events_wall_ms_median": round(ev_ms, 3), "events_wall_ms_all": [round(r["events_ms"], 3) for r in warm],
+           "samples_per_s": round(est["samples"] / (ev_ms * 1e-3), 1), "events_per_s": round(est["events"] / (ev_ms * 1e-3), 1),
+           "sums_tstat_kernels_ms": round(med(lambda r: r["ev"]["sums_ms"]), 3), "detector_kernels_ms": round(med(lambda r: r["ev"]["detect_ms"]), 3),
+           "fill_kernels_ms": round(med(lambda r: r["ev"]["fill_ms"]), 3), "events_first_to_last_kernel_ms": round(med(lambda r: r["ev"]["total_ms"]), 3),
+           "chunks": est["chunks"], "chunks_redone": est["chunks_redone"], "reads_serial_sums": est["reads_serial_sums"],
+           "scalings_wall_ms_median": round(med(lambda r: r["scalings_ms"]), 3), "scalings_sums_in_order": warm[-1]["sc"], "align_wall_ms_median": round(med(lambda r: r["align_ms"]), 3),
+           "align_all_kernels_ms": round(med(lambda r: r["al"]["total_ms"]), 3), "reads_passing": int((rec["n_pairs"] > 0).sum()),
+           "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(out))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1); f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=4096); ap.add_argument("--min-bases", type=int, default=5000)
     ap.add_argument("--max-bases", type=int, default=15000); ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--seed", type=int, default=1); ap.add_argument("--json")
+    ap.add_argument("--signal", action="store_true", help="raw signal in: event detection, scalings and align, timed per stage")
     a = ap.parse_args()
+    if a.signal:
+        return main_signal(a)
     import genarchbench_amd  # noqa: F401  (before torch: the runtime's default for pageable copies)
     import torch
     from genarchbench_amd import abea
