@@ -1,7 +1,9 @@
 """Host-side mirror of the adaptive banded event alignment, align() (abea/src/align.c:169-548), over the C ABI
 (include/gab.h: gab_abea_align, gab_abea_align_device): the loop of align_db over its reads (abea/src/f5c.c:1367-1394) as one call;
 and of the two steps before it, event detection and the scaling estimate (gab_abea_events, gab_abea_scalings: event_single,
-f5c.c:1241-1264), so that raw samples go in and aligned pairs come out (EventAligner.signal_to_pairs)."""
+f5c.c:1241-1264), so that raw samples go in and aligned pairs come out (EventAligner.signal_to_pairs); and of the block after it,
+postalign, recalibrate_model and the read checks (gab_abea_calibrate: f5c.c:1438-1501), so that calibrated reads with their
+base-to-event map come out (EventAligner.signal_to_calibrated)."""
 import ctypes as C
 
 import numpy as np
@@ -17,7 +19,12 @@ ERANGE = -34      # GAB_ERANGE
 PAIR = np.dtype([("ref_pos", np.int32), ("read_pos", np.int32)])
 READ = np.dtype([("n_pairs", np.int32), ("path_len", np.int32), ("end_event", np.int32), ("max_gap", np.int32), ("flags", np.uint32),
                  ("pad", np.int32), ("avg_log_emission", np.float64), ("fills", np.int64)])      # gab_abea_read, 40 bytes
-assert PAIR.itemsize == 8 and READ.itemsize == 40
+FAILED_CALIBRATION, FAILED_ALIGNMENT, FAILED_QUALITY_CHK = 1, 2, 4      # gab_abea_calib.read_stat_flag
+RANGE = np.dtype([("start", np.int32), ("stop", np.int32)])      # gab_abea_range: stop inclusive, -1 / -1 = no event
+CALIB = np.dtype([("n_alignment", np.int32), ("n_m_state", np.int32), ("read_stat_flag", np.uint32), ("recalibrated", np.int32),
+                  ("scale", np.float32), ("shift", np.float32), ("var", np.float32), ("log_var", np.float32),
+                  ("events_per_base", np.float64)])                  # gab_abea_calib, 40 bytes
+assert PAIR.itemsize == 8 and READ.itemsize == 40 and RANGE.itemsize == 8 and CALIB.itemsize == 40
 
 
 def _p(a):
@@ -222,6 +229,99 @@ class EventAligner:
         res = torch.zeros(n * READ.itemsize, dtype=torch.uint8, device="cuda")
         self.align_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift, pairs, d_po, res)
         return (pairs.cpu().numpy().reshape(-1).view(PAIR), pair_off, res.cpu().numpy().view(READ), ne, scale.cpu().numpy(), shift.cpu().numpy())
+
+    # ---- base-to-event map, recalibration and read checks (gab_abea_calibrate) ---------------------------------------------------
+    def calibrate(self, seq, seq_off, seq_len, events, event_off, n_events, scale, shift, pairs, pair_off, n_pairs, map_off=None, out=None):
+        """the packed arrays of align(), its pairs (a PAIR array or an int32 array of shape (n, 2)), pair_off and the n_pairs of its
+        records -> (map, map_off, records): map a RANGE array in which read i's seq_len[i] - 5 entries start at map_off[i] (back to
+        back unless map_off is given), records a CALIB array.  out: (map, records) to write into instead of new arrays."""
+        seq = np.ascontiguousarray(seq, np.uint8); events = np.ascontiguousarray(events, np.float32)
+        seq_off = np.ascontiguousarray(seq_off, np.int64); event_off = np.ascontiguousarray(event_off, np.int64)
+        seq_len = np.ascontiguousarray(seq_len, np.int32); n_events = np.ascontiguousarray(n_events, np.int32)
+        scale = np.ascontiguousarray(scale, np.float32); shift = np.ascontiguousarray(shift, np.float32)
+        pairs = np.asarray(pairs)
+        pairs = np.ascontiguousarray(pairs if pairs.dtype == PAIR else pairs.astype(np.int32))
+        pair_off = np.ascontiguousarray(pair_off, np.int64); n_pairs = np.ascontiguousarray(n_pairs, np.int32)
+        n = seq_len.size
+        n_kmers = np.maximum(seq_len.astype(np.int64) - K + 1, 0)
+        if map_off is None:
+            map_off = np.zeros(n, np.int64)
+            if n > 1:
+                map_off[1:] = np.cumsum(n_kmers[:-1])
+        map_off = np.ascontiguousarray(map_off, np.int64)
+        if out is None:
+            total = int((map_off + n_kmers).max()) if n else 0
+            out = (np.full(total, -1, np.int32).repeat(2).view(RANGE), np.zeros(n, CALIB))
+        rmap, res = out
+        if rmap.dtype != RANGE or res.dtype != CALIB or res.size < n or (n and rmap.size < int((map_off + n_kmers).max())):
+            raise ValueError("out: a RANGE array with room for every read's map and a CALIB array of one record per read")
+        check(lib().gab_abea_calibrate(self._h, _p(seq), _p(seq_off), _p(seq_len), _p(events), _p(event_off), _p(n_events), _p(scale), _p(shift),
+                                       _p(pairs), _p(pair_off), _p(n_pairs), C.c_int64(n), _p(rmap), _p(map_off), _p(res)))
+        return rmap, map_off, res
+
+    def calibrate_reads(self, reads, paths):
+        """reads: list of (bases, event means, scale, shift); paths: per read the pairs of its alignment, (n, 2) of (ref_pos,
+        read_pos), empty for a read that align() failed -> (map, map_off, records)"""
+        n_pairs = np.array([len(p) for p in paths], np.int32)
+        pair_off = np.zeros(len(paths), np.int64)
+        if len(paths) > 1:
+            pair_off[1:] = np.cumsum(n_pairs[:-1], dtype=np.int64)
+        flat = np.concatenate([np.asarray(p, np.int32).reshape(-1, 2) for p in paths]) if paths else np.zeros((0, 2), np.int32)
+        return self.calibrate(*pack_reads(reads)[:8], flat, pair_off, n_pairs)
+
+    def calibrate_device(self, seq, seq_off, seq_len, events, event_off, n_events, scale, shift, pairs, pair_off, n_pairs, rmap, map_off, res, stream=0):
+        """torch tensors on the handle's GPU: the inputs and the pairs of align_device, int32 n_pairs; rmap an int32 tensor of shape
+        (entries, 2) and res a uint8 tensor of 40 bytes per read, both filled in place (complete when the call returns)"""
+        n = seq_len.numel()
+        if pairs.numel() % 2 or rmap.numel() % 2 or res.numel() * res.element_size() < n * CALIB.itemsize:
+            raise ValueError("pairs and rmap hold int32 pairs, res 40 bytes per read")
+        check(lib().gab_abea_calibrate_device(
+            self._h, C.c_void_p(seq.data_ptr()), C.c_int64(seq.numel()), C.c_void_p(seq_off.data_ptr()), C.c_void_p(seq_len.data_ptr()),
+            C.c_void_p(events.data_ptr()), C.c_int64(events.numel()), C.c_void_p(event_off.data_ptr()), C.c_void_p(n_events.data_ptr()),
+            C.c_void_p(scale.data_ptr()), C.c_void_p(shift.data_ptr()), C.c_void_p(pairs.data_ptr()), C.c_int64(pairs.numel() // 2),
+            C.c_void_p(pair_off.data_ptr()), C.c_void_p(n_pairs.data_ptr()), C.c_int64(n), C.c_void_p(rmap.data_ptr()), C.c_int64(rmap.numel() // 2),
+            C.c_void_p(map_off.data_ptr()), C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+
+    def calibrate_last_stats(self):
+        """the last calibrate call: reads, reads recalibrated, 'M' entries of all reads, device time of its check, map and fit
+        kernels and of the whole call (ms)"""
+        v = [C.c_int64(-1) for _ in range(3)]; kms = C.c_float(-1); tms = C.c_float(-1)
+        check(lib().gab_abea_calibrate_last_stats(self._h, *[C.byref(x) for x in v], C.byref(kms), C.byref(tms)))
+        return {"reads": v[0].value, "recalibrated": v[1].value, "m_states": v[2].value, "kernel_ms": kms.value, "total_ms": tms.value}
+
+    def signal_to_calibrated(self, signals, seqs):
+        """signal_to_pairs' three steps and then the calibration, everything resident: raw samples go in, calibrated reads with
+        their base-to-event map come out.  Only n_events comes to the host in between.
+        -> (map, map_off, calibration records, pairs, pair_off, alignment records, n_events) as numpy arrays"""
+        import torch
+        packed = pack_signals(signals)
+        n = len(signals)
+        dev = [torch.from_numpy(a).cuda() for a in packed]
+        cap = max(int(packed[2].sum()), 1)
+        n_events = torch.zeros(n, dtype=torch.int32, device="cuda"); event_off = torch.zeros(n, dtype=torch.int64, device="cuda")
+        mean = torch.empty(cap, dtype=torch.float32, device="cuda"); stdv = torch.empty_like(mean); length = torch.empty_like(mean)
+        start = torch.empty(cap, dtype=torch.int32, device="cuda"); total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        check(self.detect_events_device(*dev, n_events, event_off, mean, stdv, start, length, total))
+        ne = n_events.cpu().numpy()
+        seq_len = np.array([len(s) for s in seqs], np.int32)
+        seq_off = np.zeros(n, np.int64); pair_off = np.zeros(n, np.int64); map_off = np.zeros(n, np.int64)
+        room = pair_room(seq_len, ne)
+        n_kmers = seq_len.astype(np.int64) - K + 1
+        if n > 1:
+            seq_off[1:] = np.cumsum(seq_len[:-1], dtype=np.int64); pair_off[1:] = np.cumsum(room[:-1]); map_off[1:] = np.cumsum(n_kmers[:-1])
+        seq = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8).copy()
+        d_seq, d_so, d_sl, d_po, d_mo = (torch.from_numpy(a).cuda() for a in (seq, seq_off, seq_len, pair_off, map_off))
+        scale = torch.zeros(n, dtype=torch.float32, device="cuda"); shift = torch.zeros_like(scale)
+        self.estimate_scalings_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift)
+        pairs = torch.full((max(int(room.sum()), 1), 2), -1, dtype=torch.int32, device="cuda")
+        res = torch.zeros(n * READ.itemsize, dtype=torch.uint8, device="cuda")
+        self.align_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift, pairs, d_po, res)
+        n_pairs = res.view(torch.int32).view(n, READ.itemsize // 4)[:, 0].contiguous()      # gab_abea_read.n_pairs
+        rmap = torch.full((max(int(n_kmers.sum()), 1), 2), -1, dtype=torch.int32, device="cuda")
+        cal = torch.zeros(n * CALIB.itemsize, dtype=torch.uint8, device="cuda")
+        self.calibrate_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift, pairs, d_po, n_pairs, rmap, d_mo, cal)
+        return (rmap.cpu().numpy().reshape(-1).view(RANGE), map_off, cal.cpu().numpy().view(CALIB),
+                pairs.cpu().numpy().reshape(-1).view(PAIR), pair_off, res.cpu().numpy().view(READ), ne)
 
     def events_last_stats(self):
         """the last detect_events call: samples, events, reads whose sums were added in order, chunks, chunks run again, kernel and

@@ -1,4 +1,5 @@
-// The abea handle, shared by abea.hip (align) and abea_events.hip (event detection, scaling estimate).
+// The abea handle, shared by abea.hip (align), abea_events.hip (event detection, scaling estimate) and abea_calib.hip (base-to-event
+// map, recalibration, read checks).
 #pragma once
 #include "gab_internal.h"
 
@@ -15,6 +16,16 @@ struct gab_abea_events_state {
     ~gab_abea_events_state();
 };
 
+// what abea_calib.hip keeps on the handle; its destructor (abea_calib.hip) frees it when the handle is deleted
+struct gab_abea_calib_state {
+    gab_devbuf io;          // staging of the host-pointer entry point
+    gab_devbuf scratch;     // counters | the double var of every read | its log_var
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // before / after the check, before the map, after the fit, after log_var is stored
+    int64_t reads = 0, recalibrated = 0, m_states = 0;
+    float kernel_ms = 0.f, total_ms = 0.f;
+    ~gab_abea_calib_state();
+};
+
 struct gab_abea {
     gab_host_stream hs;
     int device = 0;
@@ -26,4 +37,5 @@ struct gab_abea {
     int64_t cells = 0, bands = 0, launches = 0;
     float kernel_ms = 0.f, total_ms = 0.f;
     gab_abea_events_state events;
+    gab_abea_calib_state calib;
 };

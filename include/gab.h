@@ -729,7 +729,8 @@ int gab_parser_last_stats(gab_parser *p, float *kernel_ms);
  * Input rules: a byte outside "ACGT" ranks as 'A' (get_rank, align.c:10-23; lower case is not mapped); seq_len >= 6 and
  * n_events >= 1, anything else is GAB_EINVAL naming the read.  The two steps before align() in the reference's timed region,
  * event detection and the scaling estimate, are gab_abea_events and gab_abea_scalings below: their outputs are what this call
- * takes.  Out of scope: postalign and what follows it. */
+ * takes; the fixed block after it, postalign, recalibrate_model and the three read checks, is gab_abea_calibrate at the end
+ * of this header.  Out of scope: the methylation HMM and realign_read. */
 #define GAB_ABEA_K 6
 #define GAB_ABEA_BANDWIDTH 100
 #define GAB_ABEA_NKMER 4096
@@ -831,6 +832,65 @@ int gab_abea_scalings_last_stats(gab_abea *h, int64_t *reads, int64_t *event_sum
 int gab_abea_events_stage_ms(gab_abea *h, float *sums_ms, float *detect_ms, float *fill_ms);
 /* GAB_ABEA_EVENTS_CHUNK and GAB_ABEA_EVENTS_WARMUP as the library was built (no GPU needed) */
 int gab_abea_events_shape(int32_t *chunk, int32_t *warmup);
+
+/* ---- abea: base-to-event map, recalibration and read checks ----------------------------------------------
+ * Replaces  the block of process_single after align_single          abea/src/f5c.c:1438-1501
+ *           = postalign (abea/src/align.c:550-650), recalibrate_model (align.c:655-762) and the three checks that set
+ *             read_stat_flag (f5c.c:1474-1501), per read.
+ * The pairs of gab_abea_align go in; the base-to-event map, events_per_base, the recalibrated scalings and the read's flag
+ * come out: everything the methylation HMM and realign_read take from the alignment.  Bit for bit the reference built WITHOUT
+ * fused multiply-add.
+ * Map (align.c:561-585): a pair counts only when its event differs from the previous pair's event; `start` is the first such
+ * event of the k-mer, `stop` the last.  events_per_base = (double)(max_event - min_event) / n_kmers over all pairs.
+ * Event alignment (align.c:595-646): k-mers in order, those without events skipped, one entry per event of start..stop; an
+ * entry is 'M' when its k-mer's rank differs from the rank of the previous ENTRY, 'E' otherwise -- so the first entry of a
+ * k-mer is 'E' when the previous k-mer that had events has the same rank, and every later entry of a k-mer is 'E'.  The
+ * entries are counted (n_alignment, n_m_state), not written: nothing downstream reads them.
+ * recalibrate_model runs when n_m_state >= 200: five double sums over the 'M' entries in entry order (inv_var = 1. / (stdv *
+ * stdv); mu * inv_var; (mu * mu) * inv_var; e * inv_var; (mu * e) * inv_var; e the float mean of the entry's event), the 2 x 2
+ * solve, a second in-order sum of (yi * yi) / (stdv * stdv) with yi = e - x0 - x1 * mu on the double x0, x1, a division by
+ * n_m_state and a correctly rounded sqrt; shift, scale and var rounded to float once, log_var = (float)log(var) of the double
+ * var with libm on the host.
+ * Defined where the reference leaves fields unset.  n_pairs = 0: flag GAB_ABEA_FAILED_ALIGNMENT, the map all -1 / -1,
+ * events_per_base 0, n_alignment 0.  Not recalibrated (that case, or fewer than 200 'M' entries): scale and shift as given,
+ * var 1, log_var 0 (what align()'s emission assumes, align.c:128,138).
+ * Flags, at most one, in the reference's order: not recalibrated or (double)var > 2.5 (MIN_CALIBRATION_VAR, f5cmisc.h:9) ->
+ * GAB_ABEA_FAILED_CALIBRATION; otherwise events_per_base > 5.0 -> GAB_ABEA_FAILED_QUALITY_CHK.  A NaN var (a pore model
+ * whose normal equations are singular) fails neither comparison.
+ * Input rules: seq_len >= 6 and n_events >= 1; 0 <= n_pairs[i] <= n_events[i] + seq_len[i] - 5; every pair has 0 <= ref_pos <
+ * n_kmers and 0 <= read_pos < n_events, both non-decreasing along the list (what align() emits).  Anything else is GAB_EINVAL
+ * naming the read, and nothing is written.  The k-mer rank rule is that of gab_abea_align.  n_reads = 0 returns GAB_OK and
+ * writes nothing. */
+enum { GAB_ABEA_FAILED_CALIBRATION = 1, GAB_ABEA_FAILED_ALIGNMENT = 2, GAB_ABEA_FAILED_QUALITY_CHK = 4 };      /* f5c.h:49-51 */
+typedef struct { int32_t start, stop; } gab_abea_range;      /* index_pair_t, f5c.h:169-172: stop inclusive; -1 / -1 = no event */
+typedef struct {
+    int32_t n_alignment;      /* what postalign returns */
+    int32_t n_m_state;        /* entries with hmm_state 'M' */
+    uint32_t read_stat_flag;  /* at most one bit: the reference returns at the first failed check */
+    int32_t recalibrated;     /* recalibrate_model's return */
+    float scale, shift, var, log_var;
+    double events_per_base;
+} gab_abea_calib;
+/* Host buffers.  seq*, event*, scale, shift, pairs and pair_off are the buffers of gab_abea_align; n_pairs[i] is res[i].n_pairs
+ * of the alignment.  Read i's map, seq_len[i] - 5 entries, goes to map[map_off[i] ..]; res[i] is its record. */
+int gab_abea_calibrate(gab_abea *h, const char *seq, const int64_t *seq_off, const int32_t *seq_len,
+                       const float *event_mean, const int64_t *event_off, const int32_t *n_events,
+                       const float *scale, const float *shift,
+                       const gab_abea_pair *pairs, const int64_t *pair_off, const int32_t *n_pairs, int64_t n_reads,
+                       gab_abea_range *map, const int64_t *map_off, gab_abea_calib *res);
+/* Device buffers.  seq_bytes / event_count / pair_count / map_count = sizes of the four slabs (bytes, floats, pairs, map
+ * entries), for bounds validation.  Three kernels, and a fourth that stores log_var.  Synchronises `stream` at the start (the
+ * lengths are validated on the host), after the first kernel (it checks every pair and writes nothing but a verdict: a broken
+ * rule returns GAB_EINVAL here) and at the end (the double var comes to the host for log_var). */
+int gab_abea_calibrate_device(gab_abea *h, const char *seq, int64_t seq_bytes, const int64_t *seq_off, const int32_t *seq_len,
+                              const float *event_mean, int64_t event_count, const int64_t *event_off, const int32_t *n_events,
+                              const float *scale, const float *shift,
+                              const gab_abea_pair *pairs, int64_t pair_count, const int64_t *pair_off, const int32_t *n_pairs, int64_t n_reads,
+                              gab_abea_range *map, int64_t map_count, const int64_t *map_off, gab_abea_calib *res, void *stream);
+/* last gab_abea_calibrate* call: reads, reads recalibrated, 'M' entries of all reads, device time of the check, map and fit
+ * kernels and of the whole call from first to last kernel, the host's turns between them included (HIP events on the stream,
+ * ms).  Any may be NULL. */
+int gab_abea_calibrate_last_stats(gab_abea *h, int64_t *reads, int64_t *recalibrated, int64_t *m_states, float *kernel_ms, float *total_ms);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
     python tools/abea_bench.py --signal --reads 1024      raw signal for the same kind of reads through gab_abea_events_device,
                                                           gab_abea_scalings_device and gab_abea_align_device: samples/s, events/s,
                                                           the stage times, chunks_redone and reads_serial_sums
+    python tools/abea_bench.py [--signal] --calibrate     adds gab_abea_calibrate_device on the pairs of the alignment to either mode and
+                                                          prints its time next to align's
 
 Reports reads/s, band cells/s (cells filled, the reference's `fills`), ms per launch, and the DP kernel's share of the device time
 against the rest (k-mer table and backtrack).  Wall time is taken around the call, which synchronises its stream before it returns."""
@@ -93,6 +95,10 @@ def main_signal(a):
     scale = torch.zeros(n, dtype=torch.float32, device="cuda"); shift = torch.zeros_like(scale)
     res = torch.zeros(n * abea.READ.itemsize, dtype=torch.uint8, device="cuda")
     pairs = None
+    n_kmers = packed[2].astype(np.int64) - abea.K + 1
+    d_mo = torch.from_numpy(np.concatenate([[0], np.cumsum(n_kmers[:-1])]).astype(np.int64)).cuda()
+    rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
+    cal = torch.zeros(n * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
     runs = []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
@@ -115,6 +121,8 @@ def main_signal(a):
         h.align_device(d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift, pairs, d_po, res)
         t4 = time.perf_counter()
         runs.append({"events_ms": (t1 - t0) * 1e3, "scalings_ms": (t3 - t2) * 1e3, "align_ms": (t4 - t3) * 1e3, "ev": est, "sc": h.scalings_last_stats(), "al": h.last_stats()})
+        if a.calibrate:
+            runs[-1].update(timed_calibrate(h, torch, (d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift), pairs, d_po, res, rmap, d_mo, cal))
     warm = runs[1:]
     med = lambda f: float(np.median([f(r) for r in warm]))
     rec = res.cpu().numpy().view(abea.READ)
@@ -129,11 +137,33 @@ def main_signal(a):
            "scalings_wall_ms_median": round(med(lambda r: r["scalings_ms"]), 3), "scalings_sums_in_order": warm[-1]["sc"], "align_wall_ms_median": round(med(lambda r: r["align_ms"]), 3),
            "align_all_kernels_ms": round(med(lambda r: r["al"]["total_ms"]), 3), "reads_passing": int((rec["n_pairs"] > 0).sum()),
            "device": torch.cuda.get_device_name(0)}
+    if a.calibrate:
+        out.update(calibrate_report(warm, cal.cpu().numpy().view(abea.CALIB)))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1); f.write("\n")
+
+
+def timed_calibrate(h, torch, inputs, pairs, d_po, res, rmap, d_mo, cal):
+    """gab_abea_calibrate_device on the alignment's pairs and records, all resident; n_pairs is the first field of every record"""
+    from genarchbench_amd import abea
+    n = inputs[2].numel()
+    n_pairs = res.view(torch.int32).view(n, abea.READ.itemsize // 4)[:, 0].contiguous()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    h.calibrate_device(*inputs, pairs, d_po, n_pairs, rmap, d_mo, cal)
+    return {"calibrate_ms": (time.perf_counter() - t0) * 1e3, "cal": h.calibrate_last_stats()}
+
+
+def calibrate_report(warm, rec):
+    med = lambda f: float(np.median([f(r) for r in warm]))
+    st = warm[-1]["cal"]
+    return {"calibrate_wall_ms_median": round(med(lambda r: r["calibrate_ms"]), 3), "calibrate_wall_ms_all": [round(r["calibrate_ms"], 3) for r in warm],
+            "calibrate_kernels_ms": round(med(lambda r: r["cal"]["kernel_ms"]), 3), "calibrate_first_to_last_kernel_ms": round(med(lambda r: r["cal"]["total_ms"]), 3),
+            "reads_recalibrated": st["recalibrated"], "m_states": st["m_states"],
+            "read_stat_flags": {str(k): int((rec["read_stat_flag"] == k).sum()) for k in (0, 1, 2, 4)}}
 
 
 def main():
@@ -142,6 +172,7 @@ def main():
     ap.add_argument("--max-bases", type=int, default=15000); ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--seed", type=int, default=1); ap.add_argument("--json")
     ap.add_argument("--signal", action="store_true", help="raw signal in: event detection, scalings and align, timed per stage")
+    ap.add_argument("--calibrate", action="store_true", help="add the base-to-event map, recalibration and read checks after align, timed")
     a = ap.parse_args()
     if a.signal:
         return main_signal(a)
@@ -153,12 +184,18 @@ def main():
     dev = [torch.from_numpy(x).cuda() for x in packed]
     pairs = torch.empty((room, 2), dtype=torch.int32, device="cuda")
     res = torch.zeros(a.reads * abea.READ.itemsize, dtype=torch.uint8, device="cuda")
-    walls, stats = [], []
+    n_kmers = packed[2].astype(np.int64) - abea.K + 1
+    d_mo = torch.from_numpy(np.concatenate([[0], np.cumsum(n_kmers[:-1])]).astype(np.int64)).cuda()
+    rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
+    cal = torch.zeros(a.reads * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
+    walls, stats, cals = [], [], []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         h.align_device(*dev[:8], pairs, dev[8], res)
         walls.append(time.perf_counter() - t0); stats.append(h.last_stats())
+        if a.calibrate:
+            cals.append(timed_calibrate(h, torch, dev[:8], pairs, dev[8], res, rmap, d_mo, cal))
     rec = res.cpu().numpy().view(abea.READ)
     order = np.argsort(walls[1:]); mid = 1 + int(order[len(order) // 2])
     st, wall = stats[mid], walls[mid]
@@ -168,6 +205,8 @@ def main():
            "ms_per_launch": round(wall * 1e3 / st["launches"], 3), "dp_kernel_ms": round(st["kernel_ms"], 3), "all_kernels_ms": round(st["total_ms"], 3),
            "dp_share": round(st["kernel_ms"] / st["total_ms"], 4), "reads_passing": int((rec["n_pairs"] > 0).sum()),
            "device": torch.cuda.get_device_name(0)}
+    if a.calibrate:
+        out.update(calibrate_report(cals[1:], cal.cpu().numpy().view(abea.CALIB)))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
