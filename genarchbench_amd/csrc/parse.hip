@@ -264,7 +264,8 @@ __global__ __launch_bounds__(256) void pairs_meta(const char *__restrict__ text,
 // read_call (chain/src/host_data_io.cpp:13-51) is token based: 6 header fields, n x "x y", everything up to "EOR".  The
 // files the suite ships (and print_return-style writers produce) are line based: one header line, n anchor lines, one
 // "EOR" line.  The GPU path handles exactly that layout and verifies it (header n == number of anchor lines, two
-// unsigned decimal tokens per anchor line); anything else is declined.  The header lines themselves are parsed on the
+// unsigned decimal tokens per anchor line, nothing but white space after the last "EOR" line); anything else is declined,
+// a last call whose "EOR" lacks its newline included.  The header lines themselves are parsed on the
 // host with the reference's own fscanf format, so the float avg_qspan is converted by the C library as in the reference.
 constexpr int kHdrSlot = 128;             // bytes reserved per header line handed to the host
 
@@ -328,7 +329,23 @@ __global__ __launch_bounds__(256) void chain_headers(const char *__restrict__ te
     for (int64_t k = 0; k < len; k++) hdr_text[c * kHdrSlot + k] = text[s + k];
     hdr_text[c * kHdrSlot + len] = 0;
 }
-// one thread per line: an anchor line is "<x> <y>" with unsigned decimal tokens (fscanf "%llu%llu")
+// what fscanf skips between tokens, the newline aside
+__device__ __forceinline__ bool is_blank(char ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\v' || ch == '\f'; }
+// the bytes after the last newline, [ls[nlines], nbytes): they belong to no line, so no other kernel sees them.  To read_call
+// they are tokens like any others (a final "EOR" without its newline closes a call there); here anything but white space
+// is declined as call `ncalls`, the call those bytes would open or close.
+__global__ __launch_bounds__(256) void chain_tail(const char *__restrict__ text, int64_t nbytes, const int64_t *__restrict__ ls,
+                                                  int64_t nlines, int64_t ncalls, ParseFlags *fl) {
+    int bad = 0;                                               // one workgroup: the tail is empty in every file a writer ends properly
+    for (int64_t p = ls[nlines] + threadIdx.x; p < nbytes; p += 256) bad |= !is_blank(text[p]);
+    bad = __syncthreads_or(bad);
+    if (bad && threadIdx.x == 0) {                             // counts as one line
+        atomicAdd(&fl->bad, 1);
+        atomicMin((unsigned int *)&fl->first_bad, (unsigned int)(ncalls > 0x7ffffffe ? 0x7ffffffe : ncalls));
+    }
+}
+// one thread per line: an anchor line is "<x> <y>" with unsigned decimal tokens (fscanf "%llu%llu"); a line after the last
+// EOR line must be blank
 __global__ __launch_bounds__(256) void chain_anchors(const char *__restrict__ text, const int64_t *__restrict__ ls, int64_t nlines,
                                                      const int32_t *__restrict__ is_eor, const int64_t *__restrict__ eor_before,
                                                      const int64_t *__restrict__ eor_line, const int64_t *__restrict__ call_off,
@@ -336,10 +353,19 @@ __global__ __launch_bounds__(256) void chain_anchors(const char *__restrict__ te
     const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (l >= nlines || is_eor[l]) return;
     const int64_t c = eor_before[l];
-    if (c >= ncalls) return;                                   // trailing lines after the last EOR: read_call stops there
+    int64_t p = ls[l]; const int64_t e = ls[l + 1] - 1;
+    if (c >= ncalls) {
+        // a line after the last EOR line: read_call is token based and would read on (a header plus anchors is a call to it
+        // even without "EOR"), so only white space may stand here; anything else is declined as call `ncalls`
+        while (p < e && is_blank(text[p])) p++;
+        if (p < e) {
+            atomicAdd(&fl->bad, 1);
+            atomicMin((unsigned int *)&fl->first_bad, (unsigned int)(c > 0x7ffffffe ? 0x7ffffffe : c));
+        }
+        return;
+    }
     const int64_t h = c == 0 ? 0 : eor_line[c - 1] + 1;
     if (l == h) return;                                        // the header line
-    int64_t p = ls[l]; const int64_t e = ls[l + 1] - 1;
     uint64_t v[2] = {0, 0};
     bool ok = true;
     for (int t = 0; t < 2 && ok; t++) {
@@ -360,8 +386,9 @@ __global__ __launch_bounds__(256) void chain_anchors(const char *__restrict__ te
         atomicMin((unsigned int *)&fl->first_bad, (unsigned int)(c > 0x7ffffffe ? 0x7ffffffe : c));
         return;
     }
-    const int64_t o = call_off[c] + (l - h - 1);
-    x[o] = v[0]; y[o] = v[1];
+    const int64_t k = l - h - 1;
+    if (k >= call_off[c + 1] - call_off[c]) return;           // (chain_headers refused the header: the call has no room)
+    x[call_off[c] + k] = v[0]; y[call_off[c] + k] = v[1];
 }
 
 }  // namespace
@@ -618,22 +645,29 @@ extern "C" int gab_chain_parse_device(gab_parser *p, const char *d_text, int64_t
     int64_t nlines = 0; const int64_t *d_ls = nullptr;
     int rc = build_line_index(p, d_text, nbytes, s, &nlines, &d_ls);
     if (rc) return rc;
-    if (nlines == 0) return GAB_OK;
+    ParseFlags *d_fl = (ParseFlags *)p->ws.as<char>();
+    ParseFlags hf = {0, 0x7fffffff};
+    GAB_HIP(hipMemcpyAsync(d_fl, &hf, sizeof hf, hipMemcpyHostToDevice, s));
+    if (nlines == 0) {                                   // no newline at all: no call, if the bytes are blank
+        hipLaunchKernelGGL(chain_tail, dim3(1), dim3(256), 0, s, d_text, nbytes, d_ls, nlines, (int64_t)0, d_fl);
+        GAB_HIP(hipGetLastError());
+        GAB_HIP(hipMemcpyAsync(&hf, d_fl, sizeof hf, hipMemcpyDeviceToHost, s));
+        GAB_HIP(hipStreamSynchronize(s));
+        if (hf.bad) { gab_set_error("gab_chain_parse: call 0: no \"EOR\" line found"); return GAB_EINVAL; }
+        return GAB_OK;
+    }
     // chain buffer: is_eor int32[nlines] | eor_before int64[nlines + 1] | then per-call arrays (sized after the scan)
     const size_t o_before = (4 * (size_t)nlines + 63) & ~(size_t)63, o_calls = o_before + ((8 * (size_t)(nlines + 1) + 63) & ~(size_t)63);
     rc = p->chain.reserve(o_calls);
     if (rc) return rc;
     int32_t *d_eor = p->chain.as<int32_t>();
     int64_t *d_before = (int64_t *)(p->chain.as<char>() + o_before);
-    ParseFlags *d_fl = (ParseFlags *)p->ws.as<char>();
-    ParseFlags hf = {0, 0x7fffffff};
-    GAB_HIP(hipMemcpyAsync(d_fl, &hf, sizeof hf, hipMemcpyHostToDevice, s));
     const int64_t lblocks = gab_ceil_div(nlines, 256);
     hipLaunchKernelGGL(chain_mark_eor, dim3((unsigned)lblocks), dim3(256), 0, s, d_text, d_ls, nlines, d_eor);
     int64_t ncalls = 0;
     rc = scan_flags(p, d_eor, nlines, d_before, &ncalls, s);
     if (rc) return rc;
-    if (ncalls == 0) { gab_set_error("gab_chain_parse: no \"EOR\" line found"); return GAB_EINVAL; }
+    if (ncalls == 0) { gab_set_error("gab_chain_parse: call 0: no \"EOR\" line found"); return GAB_EINVAL; }
     GAB_CHECK(ncalls < (1ll << 31), "gab_chain_parse_device: too many calls");
     // per-call arrays live in a second buffer so that the per-line arrays above stay valid
     const size_t c_eorl = 0, c_na = (8 * (size_t)ncalls + 63) & ~(size_t)63, c_off = c_na + ((4 * (size_t)ncalls + 63) & ~(size_t)63);
@@ -655,6 +689,7 @@ extern "C" int gab_chain_parse_device(gab_parser *p, const char *d_text, int64_t
     uint64_t *d_x = p->anchors.as<uint64_t>(), *d_y = d_x + std::max<int64_t>(total, 1);
     hipLaunchKernelGGL(chain_anchors, dim3((unsigned)lblocks), dim3(256), 0, s, d_text, d_ls, nlines, d_eor, d_before, d_eorl, d_coff,
                        ncalls, d_x, d_y, d_fl);
+    hipLaunchKernelGGL(chain_tail, dim3(1), dim3(256), 0, s, d_text, nbytes, d_ls, nlines, ncalls, d_fl);
     GAB_HIP(hipGetLastError());
     GAB_HIP(hipEventRecord(p->ev[1], s));
     // host side of the call table: offsets + headers (parsed with the reference's fscanf format)
@@ -672,7 +707,8 @@ extern "C" int gab_chain_parse_device(gab_parser *p, const char *d_text, int64_t
     GAB_HIP(hipMemcpyAsync(&hf, d_fl, sizeof hf, hipMemcpyDeviceToHost, s));
     GAB_HIP(hipStreamSynchronize(s));
     if (hf.bad) {
-        gab_set_error("gab_chain_parse: %d line(s) are not in the one-record-per-line layout (first: call %d)", hf.bad, hf.first_bad);
+        gab_set_error("gab_chain_parse: %d line(s) are not in the one-record-per-line layout (first: call %d%s)", hf.bad, hf.first_bad,
+                      hf.first_bad >= ncalls ? ", after the last \"EOR\" line" : "");
         return GAB_EINVAL;
     }
     for (int64_t c2 = 0; c2 < ncalls; c2++) {

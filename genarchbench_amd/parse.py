@@ -60,6 +60,17 @@ class InputParser:
         check(lib().gab_bsw_parse_pairs_device(self._h, C.c_void_p(d_text), C.c_int64(nbytes), C.byref(out), C.c_void_p(stream)))
         return out
 
+    def pairs_device(self, d_text, nbytes, swap_longer_first, stream=0):
+        out = PairsPacked()
+        check(lib().gab_pairs_parse_device(self._h, C.c_void_p(d_text), C.c_int64(nbytes), C.c_int(1 if swap_longer_first else 0),
+                                           C.byref(out), C.c_void_p(stream)))
+        return out
+
+    def chain_device(self, d_text, nbytes, stream=0):
+        out = ChainPacked()
+        check(lib().gab_chain_parse_device(self._h, C.c_void_p(d_text), C.c_int64(nbytes), C.byref(out), C.c_void_p(stream)))
+        return out
+
     def pairs(self, text: bytes, swap_longer_first, stream=0):
         """bpm / wfa input text ('>' / '<' line pairs) -> PairsPacked"""
         out = PairsPacked()

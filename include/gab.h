@@ -704,7 +704,9 @@ int gab_pairs_parse_device(gab_parser *p, const char *d_text, int64_t nbytes, in
 /* chain / fast-chain (chain/src/host_data_io.cpp:13-51): files in the one-record-per-line layout -- a header line
  * "n avg_qspan max_dist_x max_dist_y bw n_segs", n lines "x y", one line "EOR" -- become the inputs of
  * gab_chain_run_device: anchors on the device, the call table (offsets and headers) on the host, as that entry point
- * takes it.  The header lines are converted on the host with the reference's own fscanf format. */
+ * takes it.  The header lines are converted on the host with the reference's own fscanf format.  After the last "EOR"
+ * line only white space may follow: anything else (a further call without its "EOR" line, an "EOR" without its newline)
+ * is GAB_EINVAL, and the message names the index that call would have had. */
 typedef struct {
     int64_t ncalls, total;                       /* calls, anchors of all calls */
     const uint64_t *d_x, *d_y;                   /* device: anchors of all calls back to back */
