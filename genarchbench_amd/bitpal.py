@@ -25,9 +25,11 @@ class BitpalEngine:
 
     __del__ = close
 
-    def benchmark_bitpal(self, batch):
-        """batch: PairBatch (swapped or not: the score is symmetric) -> printed scores (int32)"""
-        out = np.full(batch.n, 12345, np.int32)
+    def benchmark_bitpal(self, batch, out=None):
+        """batch: PairBatch (swapped or not: the score is symmetric) -> printed scores (int32), written to `out` when given"""
+        if out is None:
+            out = np.full(batch.n, 12345, np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size >= batch.n
         check(lib().gab_bitpal_run(self._h, _p(batch.pat), _p(batch.pat_off), _p(batch.pat_len), _p(batch.txt),
                                    _p(batch.txt_off), _p(batch.txt_len), C.c_int64(batch.n), _p(out)))
         return out
@@ -44,3 +46,11 @@ class BitpalEngine:
         ce = C.c_int64(0); lp = C.c_int64(0); k = C.c_float(0); t = C.c_float(0)
         check(lib().gab_bitpal_last_stats(self._h, C.byref(ce), C.byref(lp), C.byref(k), C.byref(t)))
         return {"cells": ce.value, "long_pairs": lp.value, "kernel_ms": k.value, "total_ms": t.value}
+
+    PATH_KEYS = ("bv_words", "bv_pairs", "lds_pairs", "lds_rows", "global_pairs", "global_blocks", "global_rows", "id_lists")
+
+    def last_paths(self):
+        """which kernel scored what in the last run (gab_bitpal_last_paths, keys in the order of GAB_BITPAL_PATH_*)"""
+        v = (C.c_int64 * len(self.PATH_KEYS))()
+        check(lib().gab_bitpal_last_paths(self._h, v))
+        return dict(zip(self.PATH_KEYS, (int(x) for x in v)))

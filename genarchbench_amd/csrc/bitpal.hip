@@ -354,6 +354,7 @@ struct gab_bitpal {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     BpCounters *h_ct = nullptr;
     bool have_stats = false;
+    int64_t paths[GAB_BITPAL_PATHS] = {};      // which kernel scored what in the last run (gab_bitpal_last_paths)
 };
 
 extern "C" int gab_bitpal_create(int algorithm, int device, gab_bitpal **out) {
@@ -422,6 +423,7 @@ extern "C" int gab_bitpal_run_device(gab_bitpal *h, const char *pat, int64_t pat
         return GAB_EINVAL;
     }
     uint32_t n_lds = h->h_ct->n_lds, n_big = h->h_ct->n_big;
+    int64_t pt[GAB_BITPAL_PATHS] = {};
     const bool scored = h->sc.match != 0;
     gab_tuning_refresh(&h->tun);
     const bool bitvec = !scored && !h->tun.bitpal_no_bv;      // (GAB_BITPAL_NO_BV)   // -a bitpal-edit: Myers' bit-vector, the integer DP for its rejects
@@ -443,13 +445,17 @@ extern "C" int gab_bitpal_run_device(gab_bitpal *h, const char *pat, int64_t pat
         GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(BpCounters), hipMemcpyDeviceToHost, s));
         GAB_HIP(hipStreamSynchronize(s));
         n_lds = h->h_ct->cursors[0]; n_big = h->h_ct->cursors[1];      // what is left for the integer DP
+        pt[GAB_BITPAL_PATH_BV_WORDS] = std::min((rows + 31) / 32, 8);
+        pt[GAB_BITPAL_PATH_BV_PAIRS] = n - (int64_t)n_lds - (int64_t)n_big;
     } else {
         if (n_big) hipLaunchKernelGGL(bitpal_scatter, dim3(grid), dim3(256), 0, s, io, d_ct->cursors, l_lds, l_big);
         else l_lds = nullptr;
         GAB_HIP(hipEventRecord(h->ev[1], s));
     }
+    pt[GAB_BITPAL_PATH_ID_LISTS] = (n_lds || n_big) && l_lds;
     if (n_lds) {
         const size_t lds = (size_t)(h->h_ct->max_rows_lds + 1) * 64;
+        pt[GAB_BITPAL_PATH_LDS_PAIRS] = n_lds; pt[GAB_BITPAL_PATH_LDS_ROWS] = h->h_ct->max_rows_lds;
         auto kern = scored ? bitpal_dp<true, true> : bitpal_dp<true, false>;
         hipLaunchKernelGGL(kern, dim3((n_lds + 63) / 64), dim3(64), lds, s, io, l_lds, n_lds, h->sc, nullptr, 0, d_ct);
         GAB_HIP(hipGetLastError());
@@ -457,6 +463,7 @@ extern "C" int gab_bitpal_run_device(gab_bitpal *h, const char *pat, int64_t pat
     if (n_big) {
         const int64_t per_block = (int64_t)(h->h_ct->max_rows_big + 1) * 64;
         const int blocks = (int)std::min<int64_t>((n_big + 63) / 64, kBigBlocks);
+        pt[GAB_BITPAL_PATH_GLOBAL_PAIRS] = n_big; pt[GAB_BITPAL_PATH_GLOBAL_BLOCKS] = blocks; pt[GAB_BITPAL_PATH_GLOBAL_ROWS] = h->h_ct->max_rows_big;
         rc = h->scratch.reserve((size_t)per_block * 4 * (size_t)blocks);
         if (rc) return rc;
         auto kern = scored ? bitpal_dp<false, true> : bitpal_dp<false, false>;
@@ -467,6 +474,7 @@ extern "C" int gab_bitpal_run_device(gab_bitpal *h, const char *pat, int64_t pat
     GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(BpCounters), hipMemcpyDeviceToHost, s));
     GAB_HIP(hipEventRecord(h->ev[2], s));
     GAB_HIP(hipStreamSynchronize(s));
+    memcpy(h->paths, pt, sizeof(pt));
     h->have_stats = true;
     return GAB_OK;
 }
@@ -476,6 +484,7 @@ extern "C" int gab_bitpal_run(gab_bitpal *h, const char *pat, const int64_t *pat
                               int32_t *score_out) {
     GAB_CHECK(h, "gab_bitpal_run: NULL handle");
     GAB_CHECK(n >= 0 && n < (1ll << 31), "gab_bitpal_run: n=%lld out of range", (long long)n);
+    h->have_stats = false;                   // (also when the scan below refuses the batch: no stale answer from last_stats / last_paths)
     if (n == 0) return GAB_OK;
     GAB_CHECK(pat && pat_off && pat_len && txt && txt_off && txt_len && score_out, "gab_bitpal_run: NULL buffer");
     gab_device_guard g(h->device);
@@ -519,5 +528,13 @@ extern "C" int gab_bitpal_last_stats(gab_bitpal *h, int64_t *cells, int64_t *lon
     if (long_pairs) *long_pairs = (int64_t)h->h_ct->n_big;
     if (kernel_ms) GAB_HIP(hipEventElapsedTime(kernel_ms, h->ev[1], h->ev[2]));
     if (total_ms) GAB_HIP(hipEventElapsedTime(total_ms, h->ev[0], h->ev[2]));
+    return GAB_OK;
+}
+
+extern "C" int gab_bitpal_last_paths(gab_bitpal *h, int64_t paths[GAB_BITPAL_PATHS]) {
+    GAB_CHECK(h, "gab_bitpal_last_paths: NULL handle");
+    GAB_CHECK(paths, "gab_bitpal_last_paths: NULL argument");
+    GAB_CHECK(h->have_stats, "gab_bitpal_last_paths: no completed run on this handle");
+    memcpy(paths, h->paths, sizeof(h->paths));
     return GAB_OK;
 }

@@ -247,6 +247,20 @@ int gab_bitpal_run_device(gab_bitpal *h, const char *pat, int64_t pat_bytes, con
 /* last run: DP cells (pattern_length x text_length summed), pairs that took the global-scratch path,
  * device time of the DP kernels and of the whole call (HIP events, ms) */
 int gab_bitpal_last_stats(gab_bitpal *h, int64_t *cells, int64_t *long_pairs, float *kernel_ms, float *total_ms);
+/* last run: which kernel scored what.  Values the host side holds after the run anyway: the call launches, allocates and copies
+ * nothing.  GAB_EINVAL without a completed run, like gab_bitpal_last_stats. */
+enum {
+    GAB_BITPAL_PATH_BV_WORDS,      /* D of the bitpal_edit_bv launch; 0: not launched */
+    GAB_BITPAL_PATH_BV_PAIRS,      /* pairs the bit-vector kernel scored (n minus its rejects) */
+    GAB_BITPAL_PATH_LDS_PAIRS,     /* pairs bitpal_dp<true, .> scored */
+    GAB_BITPAL_PATH_LDS_ROWS,      /* rows its LDS column was sized for (0: not launched) */
+    GAB_BITPAL_PATH_GLOBAL_PAIRS,  /* pairs bitpal_dp<false, .> scored */
+    GAB_BITPAL_PATH_GLOBAL_BLOCKS, /* its workgroups (0: not launched) */
+    GAB_BITPAL_PATH_GLOBAL_ROWS,   /* rows its scratch slices were sized for */
+    GAB_BITPAL_PATH_ID_LISTS,      /* 1: the DP kernels read id lists, 0: slot = pair (or no DP kernel ran) */
+    GAB_BITPAL_PATHS
+};
+int gab_bitpal_last_paths(gab_bitpal *h, int64_t paths[GAB_BITPAL_PATHS]);
 
 /* ---- wfa: gap-affine wavefront alignment with CIGAR ---------------------------------------
  * Replaces  affine_wavefronts_clear(wf); affine_wavefronts_align(wf, pattern, plen, text, tlen);

@@ -113,8 +113,13 @@ def test_long_pairs_global_path(eng):
 def test_limits_are_reported(eng):
     from genarchbench_amd._lib import GabError
     b = gabgen.pairs_from_lists([b"A" * 16321], [b"A"])
-    with pytest.raises(GabError):
+    with pytest.raises(GabError) as ei:
         eng.benchmark_bitpal(b)
+    assert ei.value.code == -22 and "1 pair(s) violate the limits (first: pair 0)" in str(ei.value)
+    b = gabgen.pairs_from_lists([b"ACGT", b"A", b"A" * 16320], [b"ACG", b"A" * 16321, b"C"])
+    with pytest.raises(GabError) as ei:
+        eng.benchmark_bitpal(b)
+    assert ei.value.code == -22 and "1 pair(s) violate the limits (first: pair 1)" in str(ei.value) and "<= 16320" in str(ei.value)
 
 
 def test_device_resident(eng):
