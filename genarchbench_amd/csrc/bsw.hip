@@ -153,6 +153,22 @@ constexpr int kTBuckets = 256;            // min(tlen >> 3, 255)
 constexpr int kNumKeys = kQBuckets * kTBuckets;
 constexpr int kClassStep = 16;            // query-length classes for LDS sizing
 constexpr int kNumClasses = kQBuckets / kClassStep;
+constexpr int kSlices = 2;                // a large batch is sorted in this many slices of its pair range (bsw_run_device_impl)
+// The three constants are measured, profiles/bsw_slices.md (10 M read-like pairs; the unsliced call takes 24.94 ms per step):
+//   kSlice0: 786 432 pairs 24.57 ms, 1 048 576 pairs 24.35, 1 572 864 pairs 24.31.  Slice 0's DP has to outlast slice 1's sort
+//     and the host's wait for it (1.0 ms; the class launches of 2^20 pairs keep their two streams busy for 5 ms), and every
+//     pair of slice 0 sits in a small launch: 2^20 pairs in 8 classes are 2 300 waves each, little more than the chip holds
+//     at once (2 048).  The smaller of the two sizes that measured equal.
+//   kSliceMin: a sliced call pays for sixteen class launches instead of eight and gains the sort of slice 1.  It measured
+//     0.23 ms faster than the unsliced call at 3 M pairs, 0.37 at 4 M, 0.46 at 6 M, 0.68 at 8 M; 2^22 is the first size whose
+//     gain stands clear of the spread of the runs.
+//   kSortGridBeside: at the 1 024 workgroups of a sort that has the GPU to itself, the sort beside the DP costs the DP 0.3 ms
+//     (the DP runs two waves per SIMD and hides little memory latency; the sort saturates the atomic rate); at 256 and at 64
+//     nothing measurable, and slice 1's sort still ends 1.0 ms into the step.
+constexpr int64_t kSlice0 = 1 << 20;      // pairs in slice 0 of a sliced call
+constexpr int64_t kSliceMin = 1 << 22;    // fewest pairs of a sliced call
+constexpr int kSortGridBeside = 256;      // workgroups of bsw_hist / bsw_scatter when they run beside DP kernels
+static_assert(kSliceMin >= (1 << 21) && kSlice0 < kSliceMin && kSlice0 >= 64 * 8192, "slice 0 has to fill the chip with its class launches, and calls below 2^21 pairs stay unsliced");
 
 struct BswConst {
     int32_t o_del, e_del, o_ins, e_ins, zdrop, end_bonus, w, max_sc;
@@ -195,13 +211,14 @@ static_assert((kNumKeys & (kNumKeys - 1)) == 0, "bsw_hslot needs a power-of-two 
 // ---- pass 1: validate + histogram ------------------------------------------------------
 // The value the histogram atomic returns is the pair's rank inside its bucket: it is kept, so that the scatter pass
 // needs no second round of 10 M atomics (each pass was atomic-throughput bound at ~13 G/s).
-__global__ __launch_bounds__(256) void bsw_hist(BswIO io, uint32_t *hist, uint32_t *rank, BswStats *st) {
+// Pairs lo .. hi - 1 of the batch (one slice of it, or all): hist and st are the slice's own, rank is indexed by the pair.
+__global__ __launch_bounds__(256) void bsw_hist(BswIO io, int64_t lo, int64_t hi, uint32_t *hist, uint32_t *rank, BswStats *st) {
     __shared__ int cls_h0[kNumClasses];      // largest h0 per query-length class among this workgroup's pairs
     if (threadIdx.x < kNumClasses) cls_h0[threadIdx.x] = 0;
     __syncthreads();
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < io.n; i += stride) {
+    for (; i < hi; i += stride) {
         int ql = io.len2[i], tl = io.len1[i], h = io.h0[i];
         int64_t ro = io.ref_off[i], qo = io.qry_off[i];
         bool ok = ql >= 1 && ql <= GAB_BSW_MAX_QLEN && tl >= 1 && tl <= GAB_BSW_MAX_TLEN && h >= 0 &&
@@ -262,11 +279,13 @@ __global__ __launch_bounds__(1024) void bsw_scan_b(uint32_t *__restrict__ start,
 // 3.2 GB of the 7.6 GB the DP fetched per 10 M pairs against 2.1 GB of algorithmic bytes).
 struct __attribute__((aligned(32))) BswRec { int64_t ref_off, qry_off; int32_t len1, len2, h0; uint32_t id; };
 
-__global__ __launch_bounds__(256) void bsw_scatter(BswIO io, const uint32_t *__restrict__ start, const uint32_t *__restrict__ rank,
-                                                   BswRec *recs) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// (pairs lo .. hi - 1 as in bsw_hist; start counts from the slice's first record, recs is where the slice's records begin, and
+// rec.id stays the pair's index in the whole batch)
+__global__ __launch_bounds__(256) void bsw_scatter(BswIO io, int64_t lo, int64_t hi, const uint32_t *__restrict__ start,
+                                                   const uint32_t *__restrict__ rank, BswRec *recs) {
+    int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < io.n; i += stride) {
+    for (; i < hi; i += stride) {
         int ql = io.len2[i], tl = io.len1[i];
         if (rank[i] == ~0u) continue;      // failed bsw_hist's validation (the host returns GAB_EINVAL after this pass)
         BswRec r;
@@ -993,10 +1012,15 @@ struct gab_bsw {
     static constexpr int kAux = 1;        // 3 measured equal to 1
     hipStream_t aux[kAux] = {nullptr};
     hipEvent_t fork = nullptr, join[kAux] = {nullptr};
+    // a large batch is sorted in slices (bsw_run_device_impl): the sort of slice 1 runs on this stream beside slice 0's DP.
+    // Made by the first sliced call, so that a handle that never sees a large batch opens no third queue.
+    hipStream_t sort = nullptr;
+    hipEvent_t sort_fork = nullptr, sort_join = nullptr;
     bool have_stats = false;
-    uint32_t *h_qstart = nullptr;   // pinned, kQBuckets + 1
-    BswStats *h_stats = nullptr;    // pinned
-    int64_t last_cells = 0;
+    int stat_slices = 1;            // slices of the last run: its cells are the sum of their counters
+    uint32_t *h_qstart[kSlices] = {nullptr};   // pinned, kQBuckets + 1 per slice (one allocation)
+    BswStats *h_stats[kSlices] = {nullptr};    // pinned, per slice (one allocation with h_init)
+    BswStats *h_init = nullptr;     // pinned: what a slice's counters start from, written once
     bool out_of_order = false;      // gab_bsw_run: a batch's sequences did not lie in pair order (its sampled window was rejected by the device)
 };
 
@@ -1043,10 +1067,14 @@ extern "C" int gab_bsw_create(const gab_bsw_params *p, int device, gab_bsw **out
         if (hipFuncSetAttribute((const void *)bsw_dp8_kernel(k & 4, k & 2, k & 1), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64) != hipSuccess) {
             gab_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); delete h; return GAB_EDEVICE;
         }
-    if (hipHostMalloc((void **)&h->h_qstart, sizeof(uint32_t) * (kQBuckets + 1)) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_stats, sizeof(BswStats)) != hipSuccess) {
-        gab_set_error("hipHostMalloc failed"); delete h; return GAB_ENOMEM;
+    if (hipHostMalloc((void **)&h->h_qstart[0], sizeof(uint32_t) * (kQBuckets + 1) * kSlices) != hipSuccess ||
+        hipHostMalloc((void **)&h->h_stats[0], sizeof(BswStats) * (kSlices + 1)) != hipSuccess) {
+        gab_set_error("hipHostMalloc failed"); gab_bsw_destroy(h); return GAB_ENOMEM;
     }
+    for (int k = 1; k < kSlices; k++) { h->h_qstart[k] = h->h_qstart[0] + (size_t)k * (kQBuckets + 1); h->h_stats[k] = h->h_stats[0] + k; }
+    h->h_init = h->h_stats[0] + kSlices;
+    memset(h->h_init, 0, sizeof(BswStats));
+    h->h_init->first_bad = 0x7fffffff;      // (bsw_hist takes an atomicMin on it)
     *out = h;
     return GAB_OK;
 }
@@ -1061,10 +1089,30 @@ extern "C" void gab_bsw_destroy(gab_bsw *h) {
         if (h->join[k]) (void)hipEventDestroy(h->join[k]);
         if (h->aux[k]) (void)hipStreamDestroy(h->aux[k]);
     }
-    if (h->h_qstart) (void)hipHostFree(h->h_qstart);
-    if (h->h_stats) (void)hipHostFree(h->h_stats);
+    if (h->sort_fork) (void)hipEventDestroy(h->sort_fork);
+    if (h->sort_join) (void)hipEventDestroy(h->sort_join);
+    if (h->sort) (void)hipStreamDestroy(h->sort);
+    if (h->h_qstart[0]) (void)hipHostFree(h->h_qstart[0]);
+    if (h->h_stats[0]) (void)hipHostFree(h->h_stats[0]);
     delete h;
 }
+
+// The sort workspace: per slice a block of hist | start | qstart | sums | stats (slice 1's sort writes its own while slice 0's DP
+// adds to slice 0's cells), then the records of all n pairs in bucket order, slice after slice, then the n ranks.
+struct BswLayout {
+    size_t o_start, o_qstart, o_sums, o_stats, blk;   // inside a slice's block (hist at 0); blk = the block's size
+    size_t o_recs, o_rank, total;
+    explicit BswLayout(size_t n) {
+        o_start = sizeof(uint32_t) * kNumKeys;
+        o_qstart = o_start + sizeof(uint32_t) * (kNumKeys + 1);
+        o_sums = o_qstart + sizeof(uint32_t) * (kQBuckets + 1);
+        o_stats = (o_sums + sizeof(uint32_t) * kScanBlocks + 15) & ~(size_t)15;
+        blk = (o_stats + sizeof(BswStats) + 255) & ~(size_t)255;
+        o_recs = blk * kSlices;
+        o_rank = o_recs + ((sizeof(BswRec) * n + 255) & ~(size_t)255);
+        total = o_rank + sizeof(uint32_t) * n;
+    }
+};
 
 static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes, const int64_t *ref_off,
                                const uint8_t *qry, int64_t qry_bytes, const int64_t *qry_off,
@@ -1093,103 +1141,178 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
     gab_device_guard g(h->device);
     hipStream_t s = (hipStream_t)stream_;
 
-    // workspace carve-up
-    const size_t o_hist = 0;
-    const size_t o_start = o_hist + sizeof(uint32_t) * kNumKeys;
-    const size_t o_qstart = o_start + sizeof(uint32_t) * (kNumKeys + 1);
-    const size_t o_sums = o_qstart + sizeof(uint32_t) * (kQBuckets + 1);
-    const size_t o_stats = (o_sums + sizeof(uint32_t) * kScanBlocks + 15) & ~(size_t)15;
-    const size_t o_recs = (o_stats + sizeof(BswStats) + 255) & ~(size_t)255;
-    const size_t o_rank = o_recs + ((sizeof(BswRec) * (size_t)n + 255) & ~(size_t)255);
-    int rc = h->ws.reserve(o_rank + sizeof(uint32_t) * (size_t)n);
+    // A batch of at least slice_min pairs is cut into slice 0, pairs 0 .. slice0 - 1, and slice 1, the rest.  Each slice is
+    // sorted by itself into its own part of the records and gets its own class launches; see the launch comment below.
+    const int64_t slice0 = h->tun.bsw_slice[0] > 0 ? h->tun.bsw_slice[0] : kSlice0;
+    const int64_t slice_min = std::max<int64_t>(h->tun.bsw_slice[1] > 0 ? h->tun.bsw_slice[1] : kSliceMin, slice0 + 1);
+    const int nsl = n >= slice_min ? kSlices : 1;
+    const int64_t cut[kSlices + 1] = {0, nsl > 1 ? slice0 : n, n};
+    if (nsl > 1 && !h->sort) {
+        if (hipStreamCreateWithFlags(&h->sort, hipStreamNonBlocking) != hipSuccess) { h->sort = nullptr; gab_set_error("gab_bsw_run_device: stream creation failed"); return GAB_EDEVICE; }
+        if (!h->sort_fork) GAB_HIP(hipEventCreateWithFlags(&h->sort_fork, hipEventDisableTiming));
+        if (!h->sort_join) GAB_HIP(hipEventCreateWithFlags(&h->sort_join, hipEventDisableTiming));
+    }
+
+    const BswLayout L((size_t)n);
+    int rc = h->ws.reserve(L.total);
     if (rc) return rc;
     char *base = h->ws.as<char>();
-    uint32_t *d_hist = (uint32_t *)(base + o_hist), *d_start = (uint32_t *)(base + o_start);
-    uint32_t *d_qstart = (uint32_t *)(base + o_qstart);
-    BswStats *d_stats = (BswStats *)(base + o_stats);
-    BswRec *d_recs = (BswRec *)(base + o_recs);             // the pairs' records in bucket order
-    uint32_t *d_rank = (uint32_t *)(base + o_rank);
+    BswRec *d_recs = (BswRec *)(base + L.o_recs);             // the pairs' records in bucket order, slice after slice
+    uint32_t *d_rank = (uint32_t *)(base + L.o_rank);
+    auto d_stats = [&](int k) { return (BswStats *)(base + L.blk * k + L.o_stats); };
 
     BswIO io{ref, ref_off, qry, qry_off, len1, len2, h0, ref_bytes, qry_bytes, n, ref_lo, qry_lo, ref_hi, qry_hi};
-    GAB_HIP(hipEventRecord(h->ev[0], s));
-    GAB_HIP(hipMemsetAsync(base, 0, o_recs, s));
-    {
-        BswStats init; memset(&init, 0, sizeof(init)); init.first_bad = 0x7fffffff;
+    // the sort of slice k on stream q; its class boundaries and statistics end up in the slice's host mirrors
+    auto enqueue_sort = [&](int k, hipStream_t q) -> hipError_t {
+        char *b = base + L.blk * k;
+        uint32_t *d_hist = (uint32_t *)b, *d_start = (uint32_t *)(b + L.o_start), *d_qstart = (uint32_t *)(b + L.o_qstart);
+        uint32_t *d_sums = (uint32_t *)(b + L.o_sums);
+        const int64_t lo = cut[k], hi = cut[k + 1];
+        hipError_t e = hipMemsetAsync(b, 0, L.blk, q);
         // first_bad uses atomicMin, so it starts at INT_MAX (set by a tiny H2D after the memset)
-        *h->h_stats = init;
-        GAB_HIP(hipMemcpyAsync(d_stats, h->h_stats, sizeof(BswStats), hipMemcpyHostToDevice, s));
-    }
-    int grid = (int)(gab_ceil_div(n, 256) < 1024 ? gab_ceil_div(n, 256) : 1024);   // (one same-address atomicMax per wave)
-    hipLaunchKernelGGL(bsw_hist, dim3(grid), dim3(256), 0, s, io, d_hist, d_rank, d_stats);
-    hipLaunchKernelGGL(bsw_scan_a, dim3(kScanBlocks), dim3(1024), 0, s, d_hist, d_start, (uint32_t *)(base + o_sums));
-    hipLaunchKernelGGL(bsw_scan_b, dim3(kScanBlocks), dim3(1024), 0, s, d_start, (const uint32_t *)(base + o_sums), d_qstart);
-    hipLaunchKernelGGL(bsw_scatter, dim3(grid), dim3(256), 0, s, io, d_start, d_rank, d_recs);
-    GAB_HIP(hipMemcpyAsync(h->h_qstart, d_qstart, sizeof(uint32_t) * (kQBuckets + 1), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipMemcpyAsync(h->h_stats, d_stats, sizeof(BswStats), hipMemcpyDeviceToHost, s));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stats(k), h->h_init, sizeof(BswStats), hipMemcpyHostToDevice, q);
+        if (e != hipSuccess) return e;
+        const int gmax = k > 0 ? kSortGridBeside : 1024;
+        const int grid = (int)(gab_ceil_div(hi - lo, 256) < gmax ? gab_ceil_div(hi - lo, 256) : gmax);   // (one same-address atomicMax per wave)
+        hipLaunchKernelGGL(bsw_hist, dim3(grid), dim3(256), 0, q, io, lo, hi, d_hist, d_rank, d_stats(k));
+        hipLaunchKernelGGL(bsw_scan_a, dim3(kScanBlocks), dim3(1024), 0, q, d_hist, d_start, d_sums);
+        hipLaunchKernelGGL(bsw_scan_b, dim3(kScanBlocks), dim3(1024), 0, q, d_start, (const uint32_t *)d_sums, d_qstart);
+        hipLaunchKernelGGL(bsw_scatter, dim3(grid), dim3(256), 0, q, io, lo, hi, d_start, d_rank, d_recs + lo);
+        e = hipMemcpyAsync(h->h_qstart[k], d_qstart, sizeof(uint32_t) * (kQBuckets + 1), hipMemcpyDeviceToHost, q);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->h_stats[k], d_stats(k), sizeof(BswStats), hipMemcpyDeviceToHost, q);
+        return e;
+    };
+    GAB_HIP(hipEventRecord(h->ev[0], s));
+    GAB_HIP(enqueue_sort(0, s));
     GAB_HIP(hipStreamSynchronize(s));   // launch geometry of the DP depends on the class sizes
-    if (h->h_stats->bad) {
-        gab_set_error("gab_bsw_run_device: %d pair(s) violate the limits (first: pair %d): need 1<=len2<=%d, "
-                      "1<=len1<=%d, 0<=h0, offsets inside the slabs with 3 more readable bytes behind every sequence",
-                      h->h_stats->bad, h->h_stats->first_bad - 1, GAB_BSW_MAX_QLEN, GAB_BSW_MAX_TLEN);
-        return GAB_EINVAL;
-    }
-    int max_h0 = 0;
-    for (int cls = 0; cls < kNumClasses; cls++) max_h0 = h->h_stats->max_h0[cls] > max_h0 ? h->h_stats->max_h0[cls] : max_h0;
     const bool sym = h->cst.o_del + h->cst.e_del == h->cst.o_ins + h->cst.e_ins;
     const bool ms1 = h->cst.max_sc <= 1;
 
-    GAB_HIP(hipEventRecord(h->ev[1], s));
+    // From here on kernels may be in flight on up to three streams, and those of the DP write the caller's outputs: an error
+    // return waits for all of them first, so that nothing still writes score_out / result_out after the call has returned.
+    hipStream_t s_main = s;
+    auto join_all = [&]() {
+        (void)hipStreamSynchronize(s_main);
+        for (int k = 0; k < gab_bsw::kAux; k++) (void)hipStreamSynchronize(h->aux[k]);
+        if (nsl > 1) (void)hipStreamSynchronize(h->sort);
+    };
+#define BSW_HIP_JOINED(call)                                                                                       \
+    do {                                                                                                           \
+        hipError_t e_ = (call);                                                                                    \
+        if (e_ != hipSuccess) {                                                                                    \
+            gab_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_));                    \
+            join_all();                                                                                            \
+            return e_ == hipErrorOutOfMemory ? GAB_ENOMEM : GAB_EDEVICE;                                           \
+        }                                                                                                          \
+    } while (0)
+    // Launch order of a sliced call.  The sort of 10 M pairs takes 0.8 ms in which no DP kernel runs, and the DP cannot start
+    // before the host has read the class sizes.  So only slice 0 is sorted with the GPU otherwise idle.  The sort of slice 1 goes
+    // to a stream of its own just before slice 0's class launches, which go out as an unsliced call's do (longest class first,
+    // alternating over the caller's stream and the aux stream); the host waits for the sort while the GPU works on slice 0,
+    // and then enqueues slice 1's class launches over all three streams (below).  Slice 0 is sized so that its DP outlasts
+    // that sort and no more, because its launches are small ones: see kSlice0.
     GAB_HIP(hipEventRecord(h->fork, s));
     for (int k = 0; k < gab_bsw::kAux; k++) GAB_HIP(hipStreamWaitEvent(h->aux[k], h->fork, 0));
     int nlaunch = 0;
-    hipStream_t s_main = s;
+    constexpr int kRing = gab_bsw::kAux + 2;
+    hipStream_t ring[kRing] = {nsl > 1 ? h->sort : nullptr, s_main};
+    for (int k = 0; k < gab_bsw::kAux; k++) ring[k + 2] = h->aux[k];
+    for (int sl = 0; sl < nsl; sl++) {
+    if (sl > 0) BSW_HIP_JOINED(hipStreamSynchronize(h->sort));      // (the GPU is busy with the DP of the slice before)
+    const BswStats &hst = *h->h_stats[sl];
+    const uint32_t *qstart = h->h_qstart[sl];
+    if (hst.bad) {
+        // (slice 0 is refused before any DP kernel runs and before slice 1 is looked at, so the count is slice 0's; a bad pair of
+        // slice 1 is found with slice 0's DP in flight: none of slice 1's runs, and the outputs are unspecified)
+        gab_set_error("gab_bsw_run_device: %d pair(s) violate the limits (first: pair %d): need 1<=len2<=%d, "
+                      "1<=len1<=%d, 0<=h0, offsets inside the slabs with 3 more readable bytes behind every sequence",
+                      hst.bad, hst.first_bad - 1, GAB_BSW_MAX_QLEN, GAB_BSW_MAX_TLEN);
+        join_all();
+        return GAB_EINVAL;
+    }
+    const bool last = sl + 1 == nsl;
+    if (!last) {
+        BSW_HIP_JOINED(hipEventRecord(h->sort_fork, s_main));
+        BSW_HIP_JOINED(hipStreamWaitEvent(h->sort, h->sort_fork, 0));
+        BSW_HIP_JOINED(enqueue_sort(sl + 1, h->sort));
+    }
+    if (sl == 0) BSW_HIP_JOINED(hipEventRecord(h->ev[1], s));
+    int max_h0 = 0;
+    for (int cls = 0; cls < kNumClasses; cls++) max_h0 = hst.max_h0[cls] > max_h0 ? hst.max_h0[cls] : max_h0;
+    char slice_tag[16] = "";
+    if (nsl > 1) snprintf(slice_tag, sizeof slice_tag, " slice %d", sl);
     // Small batches (fewer waves than fill the chip a few times over) go out as ONE launch sized for their longest query:
     // eight class launches of a couple of hundred waves each leave most CUs idle and pay eight launch latencies
     // (100 k pairs: 3.0 -> 1.x ms); the records are in key order, so the heaviest waves still start first.
-    const bool one_launch = n <= (int64_t)64 * 8192;
+    const bool one_launch = nsl == 1 && n <= (int64_t)64 * 8192;
     int top_cls = kNumClasses - 1;
-    while (top_cls > 0 && h->h_qstart[(top_cls + 1) * kClassStep] <= h->h_qstart[top_cls * kClassStep]) top_cls--;
+    while (top_cls > 0 && qstart[(top_cls + 1) * kClassStep] <= qstart[top_cls * kClassStep]) top_cls--;
+    // Slice 1's launches rotate over the sort stream, idle by now, the caller's and the aux stream.  The other two still hold
+    // launches of slice 0, so the rotation is phased to give the idle stream the heaviest (pairs x qcap) of the first round's
+    // launches: that one starts at once.  In a read set the longest class holds few pairs and the second one is the heavy one.
+    int ring_phase = 0;
+    if (sl > 0) {
+        int64_t heaviest = 0;
+        for (int cls = kNumClasses - 1, k = 0; cls >= 0 && k < kRing; cls--) {
+            const int64_t w = ((int64_t)qstart[(cls + 1) * kClassStep] - (int64_t)qstart[cls * kClassStep]) * (cls + 1);
+            if (w <= 0) continue;
+            if (w > heaviest) { heaviest = w; ring_phase = k; }
+            k++;
+        }
+        nlaunch = 0;
+    }
     for (int cls = kNumClasses - 1; cls >= 0; cls--) {      // longest queries first: the tail of the step is made of short work
-        int64_t kb = h->h_qstart[cls * kClassStep], ke = h->h_qstart[(cls + 1) * kClassStep];
+        int64_t kb = qstart[cls * kClassStep], ke = qstart[(cls + 1) * kClassStep];
         if (one_launch) { if (cls != top_cls) continue; kb = 0; }
         if (ke <= kb) continue;
         const int qcap = (cls + 1) * kClassStep;
         const int blocks = (int)gab_ceil_div(ke - kb, 64);
         s = (nlaunch % (gab_bsw::kAux + 1)) ? h->aux[nlaunch % (gab_bsw::kAux + 1) - 1] : s_main;
+        if (sl > 0) s = ring[(nlaunch - ring_phase + kRing) % kRing];
         nlaunch++;
         // every H / E value of the launch is at most h0 + qlen * max_sc (max_sc >= 0: bsw_create starts its max at 0):
-        // 8-bit cells when that fits a byte, 16-bit packed cells when it fits 15 bits, else 32-bit cells
-        const int64_t hmax = (int64_t)(one_launch ? max_h0 : h->h_stats->max_h0[cls]) + (int64_t)qcap * h->cst.max_sc;
+        // 8-bit cells when that fits a byte, 16-bit packed cells when it fits 15 bits, else 32-bit cells.  max_h0 is the
+        // slice's own, so the two slices of a call may run different kernels for the same class
+        const int64_t hmax = (int64_t)(one_launch ? max_h0 : hst.max_h0[cls]) + (int64_t)qcap * h->cst.max_sc;
         const bool wide = hmax > 32767;
-        if (h->tun.bsw_trace)     // GAB_BSW_TRACE: which DP kernel each launch runs
-            fprintf(stderr, "[gab_bsw_dp %p] class %d qcap %d pairs %lld bits %d sym %d ms1 %d\n", (void *)h, cls, qcap,
-                    (long long)(ke - kb), hmax <= 255 ? 8 : wide ? 32 : 16, (int)sym, (int)ms1);
+        if (h->tun.bsw_trace)     // GAB_BSW_TRACE: which DP kernel each launch runs (a sliced call says which slice)
+            fprintf(stderr, "[gab_bsw_dp %p] class %d qcap %d pairs %lld bits %d sym %d ms1 %d%s\n", (void *)h, cls, qcap,
+                    (long long)(ke - kb), hmax <= 255 ? 8 : wide ? 32 : 16, (int)sym, (int)ms1, slice_tag);
+        kb += cut[sl]; ke += cut[sl];      // (the slice's records start at record cut[sl])
+        BswStats *const d_st = d_stats(sl);
         if (hmax <= 255 && h->cst.max_sc >= 0) {
             // qcap / 2 + 1 rows of cells, the nibble rows (at least one) and one spare row: the kernel reads up to pair word
             // qlen / 2 + 2 (row start, band trimming, the row maximum's candidates), which this layout holds for every qcap >= qlen
             const size_t lds8 = sizeof(uint32_t) * 64 * ((size_t)(qcap + 2) / 2 + ((size_t)(qcap + 1) / 2 + 3) / 4 + 1);
             auto kern = bsw_dp8_kernel(sym, ms1, result_out == nullptr);      // (score-only is a template argument of bsw_dp8)
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds8, s, io, h->cst, d_recs, kb, ke, qcap,
-                               score_out, result_out, d_stats);
+                               score_out, result_out, d_st);
             continue;
         }
         const size_t lds = sizeof(uint32_t) * 64 * ((size_t)(wide ? 2 : 1) * (qcap + 1) + (size_t)(qcap + 3) / 4);
         if (wide)
             hipLaunchKernelGGL(bsw_dp<true>, dim3(blocks), dim3(64), lds, s, io, h->cst, d_recs, kb, ke, qcap,
-                               score_out, result_out, d_stats);
+                               score_out, result_out, d_st);
         else
             hipLaunchKernelGGL(bsw_dp<false>, dim3(blocks), dim3(64), lds, s, io, h->cst, d_recs, kb, ke, qcap,
-                               score_out, result_out, d_stats);
+                               score_out, result_out, d_st);
     }
     s = s_main;
-    GAB_HIP(hipGetLastError());
-    for (int k = 0; k < gab_bsw::kAux; k++) {
-        GAB_HIP(hipEventRecord(h->join[k], h->aux[k]));
-        GAB_HIP(hipStreamWaitEvent(s, h->join[k], 0));
+    BSW_HIP_JOINED(hipGetLastError());
+    }      // (slices)
+    if (nsl > 1) {
+        BSW_HIP_JOINED(hipEventRecord(h->sort_join, h->sort));
+        BSW_HIP_JOINED(hipStreamWaitEvent(s, h->sort_join, 0));
     }
-    GAB_HIP(hipEventRecord(h->ev[2], s));
-    GAB_HIP(hipMemcpyAsync(h->h_stats, d_stats, sizeof(BswStats), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipEventRecord(h->ev[3], s));
+    for (int k = 0; k < gab_bsw::kAux; k++) {
+        BSW_HIP_JOINED(hipEventRecord(h->join[k], h->aux[k]));
+        BSW_HIP_JOINED(hipStreamWaitEvent(s, h->join[k], 0));
+    }
+    BSW_HIP_JOINED(hipEventRecord(h->ev[2], s));
+    for (int k = 0; k < nsl; k++) BSW_HIP_JOINED(hipMemcpyAsync(h->h_stats[k], d_stats(k), sizeof(BswStats), hipMemcpyDeviceToHost, s));
+    BSW_HIP_JOINED(hipEventRecord(h->ev[3], s));
+#undef BSW_HIP_JOINED
+    h->stat_slices = nsl;
     h->have_stats = true;
     return GAB_OK;
 }
@@ -1294,7 +1417,7 @@ extern "C" int gab_bsw_reserve(gab_bsw *h, int64_t max_pairs, int64_t max_ref_by
     int rc = h->io.reserve(std::max<size_t>((((size_t)max_ref_bytes + 3 + 511) & ~(size_t)255) + (((size_t)max_qry_bytes + 3 + 511) & ~(size_t)255) + 32 * nn + 1024,
                                             (size_t)4 << 20));      // (at least the 4 MB gab_warm_copy_engines moves)
     if (rc) return rc;
-    rc = h->ws.reserve(sizeof(uint32_t) * (2 * kNumKeys + kQBuckets + 4) + sizeof(BswStats) + 1024 + (sizeof(BswRec) + sizeof(uint32_t)) * nn);
+    rc = h->ws.reserve(BswLayout(nn).total);
     if (rc) return rc;
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
@@ -1321,7 +1444,10 @@ extern "C" int gab_bsw_last_stats(gab_bsw *h, int64_t *cells, float *kernel_ms, 
     GAB_CHECK(h->have_stats, "gab_bsw_last_stats: no completed run on this handle");
     gab_device_guard g(h->device);
     GAB_HIP(hipEventSynchronize(h->ev[3]));
-    if (cells) *cells = (int64_t)h->h_stats->cells;
+    if (cells) {
+        *cells = 0;
+        for (int k = 0; k < h->stat_slices; k++) *cells += (int64_t)h->h_stats[k]->cells;
+    }
     if (kernel_ms) GAB_HIP(hipEventElapsedTime(kernel_ms, h->ev[1], h->ev[2]));
     if (total_ms) GAB_HIP(hipEventElapsedTime(total_ms, h->ev[0], h->ev[3]));
     return GAB_OK;

@@ -114,6 +114,11 @@ void gab_tuning_load(gab_tuning *t) {
     auto on = [](const char *name) { return getenv(name) != nullptr; };
     auto num = [](const char *name, long long unset) { const char *e = getenv(name); return e ? atoll(e) : unset; };
     t->bsw_trace = on("GAB_BSW_TRACE"); t->bsw_full_scan = on("GAB_BSW_FULL_SCAN");
+    if (const char *e = getenv("GAB_BSW_SLICE")) {
+        const int k = sscanf(e, "%lld,%lld", &t->bsw_slice[0], &t->bsw_slice[1]);
+        if (k < 2) t->bsw_slice[1] = -1;
+        if (k < 1) t->bsw_slice[0] = -1;
+    }
     t->bpm_score64 = on("GAB_BPM_SCORE64"); t->bitpal_no_bv = on("GAB_BITPAL_NO_BV"); t->bpm_slices = (int)num("GAB_BPM_SLICES", 0);
     t->bpm_trace = on("GAB_BPM_TRACE");
     if (const char *e = getenv("GAB_WFA_TUNE")) {

@@ -92,6 +92,7 @@ static inline double gab_now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, 
 struct gab_tuning {
     // bsw
     bool bsw_trace = false, bsw_full_scan = false;
+    long long bsw_slice[2] = {-1, -1};               // GAB_BSW_SLICE=S0[,MIN]: pairs in slice 0, fewest pairs of a sliced call; -1 = unset
     // bpm / bitpal
     bool bpm_score64 = false, bitpal_no_bv = false, bpm_trace = false;
     int bpm_slices = 0;                              // 0 = by batch size

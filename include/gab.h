@@ -107,7 +107,8 @@ int gab_bsw_run(gab_bsw *h, const uint8_t *ref, const int64_t *ref_off, const ui
  * sequence slabs, used for bounds validation: the kernels read a sequence four bytes at a time from its own (possibly
  * unaligned) start, so every sequence must be followed by at least 3 more bytes INSIDE its slab (off + len + 3 <= bytes;
  * their contents do not matter).  result_out may be NULL;
- * when given it receives all six result fields per pair. */
+ * when given it receives all six result fields per pair.  On GAB_EINVAL the contents of score_out and result_out are
+ * unspecified (nothing writes them any more once the call has returned). */
 int gab_bsw_run_device(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes, const int64_t *ref_off,
                        const uint8_t *qry, int64_t qry_bytes, const int64_t *qry_off,
                        const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n,
