@@ -16,9 +16,17 @@
  *     that calls on several handles of one GPU overlap); "_run_device" variants take DEVICE pointers
  *     (hipMalloc'ed or a torch tensor's data_ptr) and enqueue on `stream` (a hipStream_t passed
  *     as void*, NULL = the default stream); each entry says where it synchronises `stream`
- *     internally.  Some of them (bsw, bpm) run part of their
- *     kernels on an internal second stream; it is forked from and joined back into `stream` by events
- *     inside the call, so the caller only ever has to order against `stream`.
+ *     internally.  Three of them run part of their kernels on streams of the handle: bsw (an aux stream for every
+ *     other class launch and, in a sliced call, a sort stream), bpm (an aux stream for the band kernels) and chain (one
+ *     stream for the latency form and one for the table form, beside the throughput form on `stream`).  These are forked
+ *     from and joined back into `stream` by events inside the call, so the caller only ever has to order against `stream`:
+ *     inputs that earlier work on `stream` produces are read after it, the host's own planning copies (lengths, offsets,
+ *     counters) go through `stream` too, and once the call's work on `stream` has completed nothing of the call reads an
+ *     input or writes an output any more.  tests/test_stream_order_gpu.py holds every `_device` entry point to this.
+ *   - a handle's work buffers belong to one call at a time, and some entry points (bsw, bpm) return with kernels still
+ *     queued.  The next call on the same handle may be issued on the SAME stream at once; on ANOTHER stream only after
+ *     the previous call's work on its stream has completed (synchronise that stream first): nothing inside the library
+ *     orders the streams of two calls against each other, and the second call would reuse the workspace under the first.
  *   - a handle is bound to one GPU; calls on distinct handles are thread-safe, so the
  *     multi-GPU drivers run one host thread (or one process) per GPU with no collective.
  */
@@ -207,8 +215,10 @@ int gab_bpm_run(gab_bpm *h, const char *pat, const int64_t *pat_off, const int32
                 int32_t *score_out);
 /* device buffers; pat_bytes / txt_bytes = slab sizes: every sequence must be followed by at least 3 more bytes
  * inside its slab (off + len + 3 <= bytes; the kernels read four bytes at a time from the sequence's own start).
- * Synchronises `stream` internally (the second kernel's launch
- * geometry depends on the first one's queue length). */
+ * Synchronises `stream` once near the start (the sizes of the pattern-length classes come to the host for the launch
+ * geometry) and, only when the batch holds patterns of more than 256 bases, again per batch of those pairs.  The score,
+ * band, window and full-column launches of the other pairs are asynchronous, the band kernels on the handle's aux stream
+ * joined back into `stream`: order later work against `stream` (or synchronise it) before reading score_out. */
 int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes, const int64_t *pat_off,
                        const int32_t *pat_len, const char *txt, int64_t txt_bytes,
                        const int64_t *txt_off, const int32_t *txt_len, int64_t n,
@@ -311,13 +321,15 @@ int gab_wfa_run_packed(gab_wfa *h, const char *pat, const int64_t *pat_off, cons
                        int32_t *score_out, int64_t *cigar_bytes);
 /* The same for pairs that are already on the device (the read phase parsed the file there: gab_pairs_parse): DEVICE pointers in as
  * for gab_wfa_run_device -- `ops` / `ops_off` is operation room on the device, pattern_length + text_length bytes per pair, scratch
- * of the caller -- and the printed text, offsets, lengths and scores out to HOST memory as above (GAB_ERANGE likewise). */
+ * of the caller -- and the printed text, offsets, lengths and scores out to HOST memory as above (GAB_ERANGE likewise).
+ * It takes no stream: it runs on the handle's private stream, which orders against no other, and returns when the results
+ * are in host memory.  The device inputs must be complete before the call (gab_pairs_parse is, when it returns). */
 int gab_wfa_run_packed_device(gab_wfa *h, const char *pat, int64_t pat_bytes, const int64_t *pat_off, const int32_t *pat_len,
                               const char *txt, int64_t txt_bytes, const int64_t *txt_off, const int32_t *txt_len, int64_t n,
                               char *ops, const int64_t *ops_off, char *cigar_out, int64_t capacity, int64_t *cigar_off_out,
                               int32_t *cigar_len_out, int32_t *score_out, int64_t *cigar_bytes);
 /* device buffers (sequence slabs readable to a multiple of 4 bytes past the last base);
- * synchronises `stream` internally between its passes */
+ * synchronises `stream` internally between its passes and behind the last one: the outputs are complete when it returns */
 int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes, const int64_t *pat_off,
                        const int32_t *pat_len, const char *txt, int64_t txt_bytes,
                        const int64_t *txt_off, const int32_t *txt_len, int64_t n, char *ops_out,
@@ -423,7 +435,9 @@ int gab_fmi_set_sa(gab_fmi *h, const int8_t *sa_ms_byte, const uint32_t *sa_ls_w
 int gab_fmi_sa_lookup(gab_fmi *h, const gab_smem *smems, int64_t n, int32_t max_occ, int64_t **coords,
                       int64_t **coord_off, int64_t *total);
 void gab_fmi_free_coords(int64_t *p);
-/* device buffers; the outputs point into memory owned by the handle, valid until the next call on it */
+/* device buffers; the outputs point into memory owned by the handle, valid until the next call on it.  Synchronises `stream`
+ * twice: after the counting pass (the total sizes the coordinate array) and at the end (lf_steps), so the coordinates are
+ * complete when it returns */
 int gab_fmi_sa_lookup_device(gab_fmi *h, const gab_smem *d_smems, int64_t n, int32_t max_occ,
                              const int64_t **d_coords, const int64_t **d_coord_off, int64_t *total, void *stream);
 /* last look-up: LF-mapping steps taken (one random 64-byte CP_OCC record each) and kernel ms */
@@ -659,6 +673,8 @@ typedef struct {
 int gab_kmer_index_solid(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
                          int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, float repeat_kmer_rate,
                          gab_kmer_solid_result *res);
+/* device pointers as gab_kmer_count_device (off / len are copied to the host first); res: host.  Synchronises `stream` between
+ * its stages (the host computes the threshold) and before it returns */
 int gab_kmer_index_solid_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len, int64_t n_reads,
                                 int k, int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq,
                                 float repeat_kmer_rate, gab_kmer_solid_result *res, void *stream);
@@ -668,6 +684,7 @@ int gab_kmer_index_solid_device(gab_kmer *h, const char *seq, int64_t seq_bytes,
 int gab_kmer_solid_positions(gab_kmer *h, const char *seq, const int64_t *off, const int32_t *len, int64_t n_reads, int k,
                              int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq, int64_t *read_start,
                              int32_t *pos, int64_t capacity, int64_t *nout);
+/* seq / off / len / read_start / pos: device pointers, nout: host, as gab_kmer_sketch_device.  Synchronises `stream`. */
 int gab_kmer_solid_positions_device(gab_kmer *h, const char *seq, int64_t seq_bytes, const int64_t *off, const int32_t *len,
                                     int64_t n_reads, int k, int32_t min_len_exclusive, int min_freq, float select_rate, int tandem_freq,
                                     int64_t *read_start, int32_t *pos, int64_t capacity, int64_t *nout, void *stream);
@@ -709,7 +726,9 @@ typedef struct {
 } gab_pairs_packed;
 int gab_parser_create(int device, gab_parser **out);
 void gab_parser_destroy(gab_parser *p);
-/* text: host pointer (copied to the device) or, for the _device variants, device pointer */
+/* text: host pointer (copied to the device) or, for the _device variants, device pointer (16-byte aligned).  Every parse call
+ * enqueues on `stream` and synchronises it several times -- after the newline count, after the scans whose totals size the
+ * outputs, for chain when the header lines have come to the host -- and at the end: the outputs are complete when it returns */
 int gab_bsw_parse_pairs(gab_parser *p, const char *text, int64_t nbytes, gab_bsw_packed *out, void *stream);
 int gab_bsw_parse_pairs_device(gab_parser *p, const char *d_text, int64_t nbytes, gab_bsw_packed *out, void *stream);
 /* swap_longer_first != 0: the longer line becomes the pattern (bpm, align_benchmark.c:177-181); 0: '>' is the pattern (wfa) */
