@@ -1670,6 +1670,7 @@ struct gab_chain {
         size_t ntab = 0, nfast = 0;          // the sorted list: [0, ntab) table form, [ntab, ntab + nfast) latency form
         int helpers = 0;                     // helper waves of the single launch when neither form took a call (chain_launch)
         std::vector<int32_t> n;              // anchors of every call in the caller's order: the sorted order is rebuilt from it
+        int through = GAB_CHAIN_THROUGH_NONE;      // gab_chain_last_through: how the host arrays of that call were filled
     } split;
     ChainTab tab;                            // the table form's buffers (chain_tab.hip)
     hipStream_t ts = nullptr;                // ... and its stream: it runs beside the other two forms
@@ -1904,7 +1905,10 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     GAB_CHECK(ncalls >= 0 && ncalls < (1ll << 31), "gab_chain_run_device: ncalls out of range");
     h->have_stats = false;
     h->split.valid = false;
-    if (ncalls == 0) { h->split = gab_chain::Split(); h->split.valid = true; return GAB_OK; }
+    // (a batch without an anchor -- no call, or only empty ones: nothing is launched, written or copied; asked for, that counts as
+    // written through: no launch that does not write through took part, and no copy was made)
+    const int through_of_nothing = host_score ? GAB_CHAIN_THROUGH_WRITTEN : GAB_CHAIN_THROUGH_NONE;
+    if (ncalls == 0) { h->split = gab_chain::Split(); h->split.through = through_of_nothing; h->split.valid = true; return GAB_OK; }
     GAB_CHECK(call_off && hdr, "gab_chain_run_device: NULL call table");
     int64_t total = 0;
     int rc = chain_check_hdrs(hdr, call_off, ncalls, &total);
@@ -1921,7 +1925,7 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     const size_t o_ev = (sizeof(ChainWork) * nw + 15) & ~(size_t)15;
     rc = h->work.reserve(o_ev + 16);
     if (rc) return rc;
-    if (nw == 0) { h->split.legacy_only = false; h->split.ntab = h->split.nfast = 0; h->split.helpers = 0; h->split.valid = true; return GAB_OK; }
+    if (nw == 0) { h->split.legacy_only = false; h->split.ntab = h->split.nfast = 0; h->split.helpers = 0; h->split.through = through_of_nothing; h->split.valid = true; return GAB_OK; }
     GAB_CHECK_ATOMIC64(o_ev);
     ChainWork *d_work = h->work.as<ChainWork>();
     unsigned long long *d_ev = (unsigned long long *)(h->work.as<char>() + o_ev);
@@ -1987,14 +1991,17 @@ static int chain_run_device_impl(gab_chain *h, int mode, const uint64_t *d_x, co
     if (written_through && ntab) { h_bail.resize(ntab); GAB_HIP(hipMemcpyAsync(h_bail.data(), d_bail, 4 * ntab, hipMemcpyDeviceToHost, s)); }
     if (host_score && !written_through && (rc = chain_copy_results(host_score, host_parent, d_score, d_parent, (size_t)total, s)) != GAB_OK) return rc;
     GAB_HIP(hipStreamSynchronize(s));    // wk (host vector) must outlive the H2D copy
+    int route = !host_score ? GAB_CHAIN_THROUGH_NONE : written_through ? GAB_CHAIN_THROUGH_WRITTEN : can_through ? GAB_CHAIN_THROUGH_COPIED_FORM : GAB_CHAIN_THROUGH_COPIED_PAGEABLE;
     if (written_through && ntab && std::any_of(h_bail.begin(), h_bail.end(), [](uint32_t b) { return b != 0; })) {
         // a call the table form handed back ran in the latency form, which writes to the device arrays only: copy after all
+        route = GAB_CHAIN_THROUGH_WRITTEN_COPIED;
         if ((rc = chain_copy_results(host_score, host_parent, d_score, d_parent, (size_t)total, s)) != GAB_OK) return rc;
         GAB_HIP(hipStreamSynchronize(s));
     }
     if (ntab && h->tun.chain_trace) chain_tab_report(&h->tab, ntab);
     h->have_stats = true;
     h->split.legacy_only = sp.legacy_only; h->split.ntab = ntab; h->split.nfast = nfast; h->split.helpers = sp.helpers;
+    h->split.through = route;
     h->split.valid = true;
     return GAB_OK;
 }
@@ -2374,6 +2381,15 @@ extern "C" int gab_chain_run(gab_chain *h, int mode, const uint64_t *x, const ui
     if (rc) return rc;
     if ((rc = chain_copy_results(score_out, parent_out, ds, dp, t, s)) != GAB_OK) return rc;
     GAB_HIP(hipStreamSynchronize(s));
+    return GAB_OK;
+}
+
+// How the host arrays of the last gab_chain_run_device[_through] call were filled (include/gab.h): host state of that call, nothing
+// is recorded on the device for it and nothing is read back here.
+extern "C" int gab_chain_last_through(gab_chain *h, int *route) {
+    GAB_CHECK(h && route, "gab_chain_last_through: NULL argument");
+    GAB_CHECK(h->split.valid, "gab_chain_last_through: no completed gab_chain_run_device call on this handle");
+    *route = h->split.through;
     return GAB_OK;
 }
 

@@ -140,6 +140,12 @@ int gab_bsw_last_stats(gab_bsw *h, int64_t *cells, float *kernel_ms, float *tota
  * call_off[c] + hdr[c].n).  x, y are minimap2's mm128_t words (chain/src/host_data.h:18-21):
  * x = ref id/strand/pos (ascending), y = seg_id << 48 | q_span << 32 | query_pos.
  * Outputs are return_t.scores / return_t.parents (host_data.h:30-36).
+ * call_off need not ascend and may leave gaps between calls; an empty call may point anywhere.  The arrays hold `total` elements,
+ * total = the largest call_off[c] + hdr[c].n.  Every element of a call receives its result.  The elements of the HOST result
+ * arrays (score_out / parent_out, host_score / host_parent) that lie below `total` but inside no call may be overwritten with
+ * unspecified values -- they are wherever the arrays are filled by a copy of [0, total), and keep their contents where the
+ * kernels write them through --, and x / y may be read there; the kernels store to the calls' own elements of d_score /
+ * d_parent only.  Nothing at or beyond `total` is touched.
  */
 #define GAB_CHAIN 0      /* chain:      max_skip / max_iter heuristics, 64-bit coordinates   */
 #define GAB_FASTCHAIN 1  /* fast-chain: no max_skip, 32-bit coordinates, AVX2/AVX-512 rounding */
@@ -191,6 +197,20 @@ int gab_chain_last_stats(gab_chain *h, int64_t *evals, float *kernel_ms);
  * handle's buffers, where it stays until the handle's next run (or gab_chain_reserve_mode call, whose warm-up run uses them).
  * GAB_EINVAL: no such run since, or another ncalls. */
 int gab_chain_last_split(gab_chain *h, int64_t ncalls, uint8_t *form, int64_t counters[4]);
+/* how host_score / host_parent of the last gab_chain_run_device / _through call on this handle were filled.  Valid when
+ * gab_chain_last_split is (GAB_EINVAL otherwise), and like it host state of that call: a run records nothing for it on the device
+ * and copies nothing.
+ * A batch without an anchor (ncalls == 0, or only empty calls) launches, writes and copies nothing: GAB_CHAIN_THROUGH_WRITTEN when
+ * host arrays were passed, whether page-locked or not (no launch that does not write through took part, no copy was made), else
+ * GAB_CHAIN_THROUGH_NONE. */
+#define GAB_CHAIN_THROUGH_NONE 0             /* not asked for (gab_chain_run_device) */
+#define GAB_CHAIN_THROUGH_WRITTEN 1          /* written through by the kernels while they ran, no copy */
+#define GAB_CHAIN_THROUGH_COPIED_PAGEABLE 2  /* copied at the end: the host arrays are not page-locked */
+#define GAB_CHAIN_THROUGH_COPIED_FORM 3      /* copied at the end: a launch that does not write through took part (the latency form; the
+                                              * legacy-only launch with 5 or 7 helper waves or the walk kernel; a batch in the throughput
+                                              * form alone that is given seven helper waves: last anchor's end <= 326 x its longest call) */
+#define GAB_CHAIN_THROUGH_WRITTEN_COPIED 4   /* written through, then copied after all: the table form handed a call back */
+int gab_chain_last_through(gab_chain *h, int *route);
 
 /* ---- bpm: bit-parallel Myers edit distance (+ backtrace-derived score) -----------------
  * Replaces  it->score = benchmark_edit_bpm(&align_input)   bpm/tools/align_benchmark.c:243-257

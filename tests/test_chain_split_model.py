@@ -53,6 +53,52 @@ def test_standing_floors():
     assert chain_split_margins(n, 1)[1] > 1.1
 
 
+def test_written_through_has_no_standing_floors():
+    """gab_chain_run_device_through on page-locked arrays (through=True): the same 16 382 500 anchors stay in the throughput form, all of
+    them, in both modes -- nobody is waited for and the floors do not apply; pageable arrays (through=False) keep them"""
+    n = [4095] * 1000 + [8192] * 500 + [4096] * 1000 + [8191] * 500
+    for mode in (0, 1):
+        assert chain_split_model(n, mode, through=True).tolist() == [P] * 3000
+        assert chain_split_model(n, mode, through=False).tolist() == model(n, mode) != [P] * 3000
+        assert all(m < 0.9 for m in chain_split_margins(n, mode, through=True))
+    # a batch that waits keeps the rule itself: a quarter of the throughput time, 2 048 anchors at least (22.06 M anchors: 6 450)
+    n = [5000] * 3000 + [60000] + [7000] * 1000
+    for mode in (0, 1):
+        assert chain_split_model(n, mode, through=True).tolist() == [P] * 3000 + [T] + [T] * 1000
+    # ... and the pins: GAB_CHAIN_TAB_MIN decides with or without floors
+    assert chain_split_model([5000, 300], 1, {"GAB_CHAIN_TAB_MIN": "301", "GAB_CHAIN_FAST_CALLS": "0"}, through=True).tolist() == [T, P]
+
+
+def test_extent_with_gaps_counts_as_anchors():
+    """total: the arrays' extent where the calls do not lie back to back.  100 x 300 back to back waits for its longest call (30 000
+    <= 1 140 x 300) and [300] x 100 + [600] sends the 600 to the latency form; spread over 1 000 000 elements nobody waits"""
+    n = [300] * 100 + [600]
+    assert model(n, 0) == [P] * 100 + [L]
+    assert chain_split_model(n, 0, total=1_000_000).tolist() == [P] * 101
+    assert chain_split_margins(n, 0, total=1_000_000)[0] == pytest.approx(1140 * 600 / 1_000_000)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_through_route(mode):
+    from tests.util import chain_through_route as route
+    n, off = [500, 500, 500], None
+    assert route(n, off, mode, {}, None) == 0 and route([], off, mode, {}, None) == 0
+    assert route([], off, mode, {}, True) == route([0, 0], off, mode, {}, False) == 1
+    assert route(n, off, mode, {}, False) == 2
+    assert route(n, off, mode, {}, True) == 3                                   # 1 500 <= 326 x 500: seven helpers
+    assert route([500] * 326, off, mode, {}, True) == 3 and route([500] * 327, off, mode, {}, True) == 1
+    assert route(n, [0, 1000, 326 * 500 - 499], mode, {}, True) == 1            # the extent counts, gaps included: 163 001 > 163 000
+    assert route(n, [0, 1000, 326 * 500 - 500], mode, {}, True) == 3
+    assert route(n, off, mode, {"GAB_CHAIN_HELPERS": "3"}, True) == 1 and route(n, off, mode, {"GAB_CHAIN_HELPERS": "5"}, True) == 3
+    assert route([500] * 327, off, mode, {"GAB_CHAIN_HELPERS": "7"}, True) == 3
+    assert route([500] * 327, off, mode, {"GAB_CHAIN_KERNEL": "walk"}, True) == (3 if mode == 0 else 1)
+    assert route([500] * 30 + [1500], off, mode, {}, True) == 3                # the latency form takes the 1 500
+    tab = {"GAB_CHAIN_TAB_MIN": "1"}
+    assert route(n, off, mode, tab, True) == route(n, off, mode, tab, True, [3, 3, 3]) == 1
+    assert route(n, off, mode, tab, True, [3, 4, 3]) == route(n, off, mode, tab, True, [5, 3, 3]) == 4
+    assert route(n, off, mode, tab, False, [3, 4, 3]) == 2
+
+
 @pytest.mark.parametrize("mode", [0, 1])
 def test_env_pins(mode):
     n = [300, 2047, 400, 30000, 511, 3000, 512, 2048, 600, 2500, 1000, 0]

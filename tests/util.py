@@ -919,7 +919,7 @@ CHAIN_DISPATCH = {                      # the four settings tests/test_chain_gpu
 CHAIN_SPLIT_KNOBS = ("GAB_CHAIN_TAB", "GAB_CHAIN_TAB_MIN", "GAB_CHAIN_FAST_MIN", "GAB_CHAIN_FAST_CALLS", "GAB_CHAIN_KERNEL", "GAB_CHAIN_HELPERS")
 
 
-def chain_split_model(n_per_call, mode, env=None):
+def chain_split_model(n_per_call, mode, env=None, through=False, total=None):
     """the form gab_chain_run_device sends every call of a batch to, BEFORE the forms' own eligibility tests: 0 empty call,
     1 throughput form, 2 latency form, 3 table form, 6 the legacy-only launch -- per call, in the caller's order.  n_per_call: anchors of
     the calls (back to back: the batch's anchors are their sum); mode 0 chain, 1 fast-chain; env: the GAB_CHAIN_* pins that are set.
@@ -927,8 +927,10 @@ def chain_split_model(n_per_call, mode, env=None):
     The rule, as chain.hip words it.  The calls are sorted longest first (stable).  The throughput form takes ~0.30 us per anchor of a
     call and does ~2.85 G anchors/s over all calls; a batch whose longest call needs at least 0.75 of the batch's throughput time WAITS
     for it.  Such a batch hands to the table form every call that would take a quarter of that time, 2 048 anchors at least; whatever
-    the batch, fast-chain sends calls of >= 4 096 anchors there and chain those of >= 8 192 (not modelled: the written-through entry
-    point has no such floors).  GAB_CHAIN_TAB_MIN pins the table form's smallest call, GAB_CHAIN_TAB=0 turns the form off.  The same test on what is left
+    the batch, fast-chain sends calls of >= 4 096 anchors there and chain those of >= 8 192 -- except with through=True, a
+    gab_chain_run_device_through call on page-locked host arrays (asked for AND page-locked: pageable arrays keep the floors), whose
+    results would leave the table form in too short a burst for the bus.  total: the arrays' extent as chain.hip computes it, the
+    largest call_off + n, where the calls do not lie back to back (gaps count as anchors of the batch).  GAB_CHAIN_TAB_MIN pins the table form's smallest call, GAB_CHAIN_TAB=0 turns the form off.  The same test on what is left
     (its anchors, its longest call) hands every remaining call of >= 512 anchors to the latency form; GAB_CHAIN_FAST_MIN pins that
     length and GAB_CHAIN_FAST_CALLS the number of calls (FAST_MIN alone: as many as there are).  The rest is the throughput form's.
     GAB_CHAIN_HELPERS, and GAB_CHAIN_KERNEL=walk for chain, send everything through one launch of the older kernels instead."""
@@ -943,12 +945,12 @@ def chain_split_model(n_per_call, mode, env=None):
         form[order] = CHAIN_FORM_LEGACY
         return form
     srt = [int(n[c]) for c in order]
-    total, per_anchor, rate, wait = sum(srt), 0.30e-6, 2.85e9, 0.75
+    total, per_anchor, rate, wait = sum(srt) if total is None else int(total), 0.30e-6, 2.85e9, 0.75
     ntab = 0
     if pin("GAB_CHAIN_TAB") != 0:
         tp = total / rate
         least = max(2048, int(0.25 * tp / per_anchor)) if per_anchor * srt[0] >= wait * tp else None
-        floor = 4096 if mode == 1 else 8192
+        floor = float("inf") if through else 4096 if mode == 1 else 8192
         least = floor if least is None else min(least, floor)
         if pin("GAB_CHAIN_TAB_MIN") >= 0:
             least = pin("GAB_CHAIN_TAB_MIN")
@@ -957,7 +959,7 @@ def chain_split_model(n_per_call, mode, env=None):
     rest = srt[ntab:]
     nfast = 0
     if rest:
-        tp = sum(rest) / rate
+        tp = (total - sum(srt[:ntab])) / rate
         least, most = (512, len(rest)) if per_anchor * rest[0] >= wait * tp else (0, 0)
         if pin("GAB_CHAIN_FAST_MIN") >= 0:
             least = pin("GAB_CHAIN_FAST_MIN")
@@ -972,13 +974,61 @@ def chain_split_model(n_per_call, mode, env=None):
     return form
 
 
-def chain_split_margins(n_per_call, mode):
+def chain_split_margins(n_per_call, mode, through=False, total=None):
     """how far the floating-point comparisons of the default rule are from flipping on this batch: the ratios (longest call's time) /
     (0.75 of the throughput time) of the two stages, for the table form and for what it leaves -- a test batch keeps both 10 %
-    away from 1 (the lengths themselves are compared as integers)"""
+    away from 1 (the lengths themselves are compared as integers).  through, total: as chain_split_model takes them"""
     n = sorted((int(v) for v in n_per_call if v > 0), reverse=True)
-    ntab = int((chain_split_model(n, mode) == CHAIN_FORM_TABLE).sum())
-    out = [0.30e-6 * n[0] / (0.75 * sum(n) / 2.85e9)]
+    total = sum(n) if total is None else int(total)
+    ntab = int((chain_split_model(n, mode, through=through, total=total) == CHAIN_FORM_TABLE).sum())
+    out = [0.30e-6 * n[0] / (0.75 * total / 2.85e9)]
     if n[ntab:]:
-        out.append(0.30e-6 * n[ntab] / (0.75 * sum(n[ntab:]) / 2.85e9))
+        out.append(0.30e-6 * n[ntab] / (0.75 * (total - sum(n[:ntab])) / 2.85e9))
     return out
+
+
+CHAIN_THROUGH_NONE, CHAIN_THROUGH_WRITTEN, CHAIN_THROUGH_PAGEABLE, CHAIN_THROUGH_FORM, CHAIN_THROUGH_WRITTEN_COPIED = 0, 1, 2, 3, 4
+CHAIN_SEVEN_HELPERS = 326              # chain_helpers_for: seven helper waves when the arrays' extent <= 326 x the longest call
+
+
+def chain_extent(n_per_call, call_off=None):
+    """`total` as chain_check_hdrs computes it: the largest call_off + n over ALL calls, empty ones included (0 without a call);
+    call_off None: the calls lie back to back"""
+    n = np.asarray(n_per_call, np.int64)
+    if call_off is None:
+        return int(n.sum())
+    return int((np.asarray(call_off, np.int64) + n).max()) if len(n) else 0
+
+
+def chain_through_route(n_per_call, call_off, mode, env, pinned, forms=None):
+    """what gab_chain_last_through reports after a run of this batch (include/gab.h): 0 not asked for (pinned None: gab_chain_run_device),
+    1 written through by the kernels, 2 copied because the host arrays are pageable, 3 copied because a launch that does not write
+    through took part, 4 written through and copied after all.  pinned: the host arrays of gab_chain_run_device_through are
+    page-locked; forms: what gab_chain_last_split reported, which alone tells 1 from 4 -- whether the table form handed a call back (4:
+    not eligible, 5: no room or by the fold); without it, 1.
+
+    The rules, as chain_run_device_impl words them.  A batch without an anchor launches and copies nothing: 1 (0 when not asked for).
+    Pageable arrays: 2.  Otherwise the split decides (chain_split_model with through=True).  If the table or the latency form took a
+    call: the latency form does not write through (3), the table form and the throughput launch beside it do (1 / 4).  If neither
+    did, ONE launch runs everything and writes through only as the three-helper throughput kernel: GAB_CHAIN_HELPERS=3 does (as form
+    6), 5 and 7 do not, the walk kernel (GAB_CHAIN_KERNEL=walk, chain) does not, and without a pin chain_helpers_for gives seven
+    helpers to a batch whose extent -- gaps included -- is at most 326 times its longest call (3)."""
+    env = env or {}
+    n = np.asarray(n_per_call, np.int64)
+    if pinned is None:
+        return CHAIN_THROUGH_NONE
+    if not (n > 0).any():
+        return CHAIN_THROUGH_WRITTEN
+    if not pinned:
+        return CHAIN_THROUGH_PAGEABLE
+    total = chain_extent(n, call_off)
+    split = chain_split_model(n, mode, env, through=True, total=total)
+    if (split == CHAIN_FORM_LATENCY).any():
+        return CHAIN_THROUGH_FORM
+    if (split == CHAIN_FORM_TABLE).any():
+        back = forms is not None and bool(np.isin(np.asarray(forms), (4, 5)).any())
+        return CHAIN_THROUGH_WRITTEN_COPIED if back else CHAIN_THROUGH_WRITTEN
+    if mode == 0 and env.get("GAB_CHAIN_KERNEL") == "walk":
+        return CHAIN_THROUGH_FORM
+    helpers = int(env["GAB_CHAIN_HELPERS"]) if env.get("GAB_CHAIN_HELPERS") in ("3", "5", "7") else (7 if total <= CHAIN_SEVEN_HELPERS * int(n.max()) else 3)
+    return CHAIN_THROUGH_WRITTEN if helpers == 3 else CHAIN_THROUGH_FORM
