@@ -529,17 +529,20 @@ __device__ __forceinline__ s16x2 pk_splat(int v) { s16x2 r; r.x = (short)v; r.y 
 // Packed 16-bit instructions the compiler does not form by itself: the x {0,1} product (as a C multiply it becomes
 // compare + select per half), the u16 min, and the op_sel forms that route one half of a register to the other
 // half of the result.  They are plain (non-volatile) asm so the scheduler may still move them.
+// The packed max, min and saturating subtract ARE formed from the vector builtins, one instruction each, and are written that
+// way: the compiler counts no wait state across an inline-asm statement and takes every asm result for a partial (dst_sel)
+// write, so a chain of asm leaves got an s_nop wherever a reader followed within asm leaves only (profiles/bsw_row_edges.md).
 __device__ __forceinline__ uint32_t pk_mul_lo(uint32_t a, uint32_t b) {
     uint32_t r; asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
 }
 __device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+    return as_u32(__builtin_elementwise_max(as_s16x2(a), as_s16x2(b)));
 }
 __device__ __forceinline__ uint32_t pk_subsat_u16_k(uint32_t a, uint32_t k) {    // max(half - k, 0), unsigned halves
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(k)); return r;
+    return as_u32(__builtin_elementwise_sub_sat(as_u16x2(a), as_u16x2(k)));
 }
 __device__ __forceinline__ uint32_t pk_subsat_u16_v(uint32_t a, uint32_t b) {    // max(half of a - half of b, 0), unsigned halves
-    uint32_t r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r;
+    return as_u32(__builtin_elementwise_sub_sat(as_u16x2(a), as_u16x2(b)));
 }
 __device__ __forceinline__ uint32_t and_or_b32(uint32_t a, uint32_t mask, uint32_t k) {   // (a & mask) | k, mask uniform
     uint32_t r; asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(k)); return r;
@@ -548,7 +551,7 @@ __device__ __forceinline__ uint32_t pk_max_i16_0(uint32_t a) {
     uint32_t r; asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(a)); return r;
 }
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
+    return as_u32(__builtin_elementwise_min(as_u16x2(a), as_u16x2(b)));
 }
 __device__ __forceinline__ uint32_t pk_min_u16_1(uint32_t a) {                    // min(half, 1) on both halves
     uint32_t r; asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(r) : "v"(a)); return r;
@@ -557,9 +560,6 @@ __device__ __forceinline__ uint32_t pk_min_u16_1(uint32_t a) {                  
 // a 16-bit VOP2 instruction reads the low halves of its sources and writes zero to the upper half of its destination.
 __device__ __forceinline__ uint32_t max_i16_lo(uint32_t a, uint32_t b) {
     uint32_t r; asm("v_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ uint32_t sub_u16_lo(uint32_t a, uint32_t b) {
-    uint32_t r; asm("v_sub_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
 }
 __device__ __forceinline__ uint32_t shr16(uint32_t a) {
     uint32_t r; asm("v_lshrrev_b32 %0, 16, %1" : "=v"(r) : "v"(a)); return r;
@@ -571,6 +571,29 @@ typedef __attribute__((address_space(3))) uint32_t bsw_lds_u32;       // 32-bit 
 typedef __attribute__((address_space(3))) const uint8_t bsw_lds_u8;
 __device__ __forceinline__ uint32_t max_i16_hi_lo(uint32_t a, uint32_t b) {      // max(upper half of a, low half of b) -> low half, upper half zero
     uint32_t r; asm("v_max_i16_sdwa %0, %1, %2 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0" : "=v"(r) : "v"(a), "v"(b)); return r;
+}
+// The per-row products as 24-bit multiplies (v_mul_i32_i24 / v_mad_i32_i24, profiles/bsw_row_edges.md): both operands lie inside
+// +-2^23 and the product inside 32 bits at every use -- max_sc <= 127, column counts <= qcap <= 256, row counts and |di - dj|
+// <= GAB_BSW_MAX_TLEN + 256 < 2^16, gap penalties < 2^15.
+__device__ __forceinline__ int mul24(int a, int b) { return __mul24(a, b); }
+// The F step of the carry chain, max(t, f - e_ins), as one leaf per column: the subtraction's result has one reader, so the pair
+// needs no register of its own and is one unit for the scheduler.  Neither instruction selects a part of its destination, so the
+// second may read the first one's result in the next issue slot (no wait state between them).
+__device__ __forceinline__ uint32_t f_step_lo(uint32_t t, uint32_t f, uint32_t e) {        // max(low half of t, f - e) -> low half
+    uint32_t r; asm("v_sub_u16 %0, %2, %3\n\tv_max_i16 %0, %1, %0" : "=&v"(r) : "v"(t), "v"(f), "v"(e)); return r;
+}
+__device__ __forceinline__ uint32_t f_step_hi(uint32_t t, uint32_t f, uint32_t e) {        // max(upper half of t, f - e) -> low half
+    uint32_t r;
+    asm("v_sub_u16 %0, %2, %3\n\tv_max_i16_sdwa %0, %1, %0 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0"
+        : "=&v"(r) : "v"(t), "v"(f), "v"(e));
+    return r;
+}
+// The row-maximum key of a loop trip folded into the running key: max(key, max(a, b, c) << 16 | j), a, b and c in low halves.
+__device__ __forceinline__ uint32_t rowkey_fold(uint32_t key, uint32_t a, uint32_t b, uint32_t c, uint32_t j) {
+    uint32_t t;
+    asm("v_max_i16 %1, %2, %3\n\tv_max_i16 %1, %1, %4\n\tv_lshl_or_b32 %1, %1, 16, %5\n\tv_max_u32 %0, %0, %1"
+        : "+v"(key), "=&v"(t) : "v"(a), "v"(b), "v"(c), "v"(j));
+    return key;
 }
 struct BswCellOut { int h, en, f; };
 __device__ __forceinline__ BswCellOut bsw_cell(int diag, int e, int f, uint32_t qc, uint32_t rlo, uint32_t rhi, int oe_del,
@@ -643,6 +666,12 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             lim = lim > 1 ? lim : 1; w = w < lim ? w : lim;
         }
         // the prunes need every cell that row 0's band clamp leaves behind to be zero, and a z-drop that rarely sends pairs back (header comment)
+        // per-lane copies of wave-uniform constants of the column sweep, made once per pair (they were seven v_mov_b32 per row):
+        // the third VOP3 source of v_and_or_b32, and the operands of the 2-cycle instructions of the sweep (an SGPR or literal
+        // source makes them 4-cycle instructions, r02_valu_issue.md), the pointer and column steps of a loop trip among them
+        uint32_t k_selz = 0x0c000c00u, k_lo8 = 0x00ff00ffu, v_e_ins = (uint32_t)e_ins;
+        uint32_t k_cstep = 512u, k_qstep = 128u, k_jstep = 4u;
+        asm volatile("" : "+v"(k_selz), "+v"(k_lo8), "+v"(v_e_ins), "+v"(k_cstep), "+v"(k_qstep), "+v"(k_jstep));
         bool prune = SO && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
         int best, best_i, best_j, g_i, gscore, max_off;
       for (;;) {                                            // second trip: a pair one of the guards sent back, prunes off
@@ -660,10 +689,11 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         }
         best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
         int beg = 0, end = qlen;
+        int hrow = h0 - c.o_del - e_del;                    // row i's left edge h0 - o_del - e_del * (i + 1), carried from row to row
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
         bool dropped = false, abandon = false;              // a prune has dropped a live cell; one of the three guards fired
         uint32_t tw = load_u32_unaligned(t);
-        for (int i = 0; i < tlen; i++) {
+        for (int i = 0; i < tlen; i++, hrow -= e_del) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
             if ((i & 3) == 3 && i + 1 < tlen) tw = load_u32_unaligned(t + i + 1);
             // the packed score vector of this row's reference base: one 8-byte LDS read (five v_cmp + ten v_cndmask + the SGPR
@@ -671,10 +701,10 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             const uint2 rr = *reinterpret_cast<const uint2 *>(&row_tab[2 * (tc < 4 ? tc : 4)]);
             const uint32_t rlo = rr.x, rhi = rr.y;
             if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + c.max_sc * (qlen - end)); }
+            if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + mul24(c.max_sc, qlen - end)); }
             if (end > qlen) end = qlen;
             int hleft = 0;
-            if (beg == 0) { hleft = h0 - (c.o_del + e_del * (i + 1)); hleft = hleft > 0 ? hleft : 0; }
+            if (beg == 0) hleft = hrow > 0 ? hrow : 0;
             int f = 0;
             uint32_t rowpk = 0;                   // (row max << 16) | column; ties -> later column
             int j = beg;
@@ -702,10 +732,6 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 const uint32_t k_oe_del = as_u32(pk_splat(oe_del)), k_e_del = as_u32(pk_splat(e_del));
                 const uint32_t k_oe_ins = as_u32(pk_splat(oe_ins));
                 const uint32_t k_bias = 0x00800080u, k_nib = 0x000f000fu;
-                // per-lane copies of wave-uniform constants: the third VOP3 source of v_and_or_b32, and the operands of the
-                // 2-cycle instructions below (an SGPR or literal source makes them 4-cycle instructions, r02_valu_issue.md)
-                uint32_t k_selz = 0x0c000c00u, k_lo8 = 0x00ff00ffu, v_e_ins = (uint32_t)e_ins;
-                asm volatile("" : "+v"(k_selz), "+v"(k_lo8), "+v"(v_e_ins));
                 // carried between pairs, both in the LOW half of their register (high half zero):
                 // HB = H of the previous column, FV = F entering the pair
                 uint32_t HB = (uint32_t)hleft, FV = (uint32_t)f;
@@ -729,10 +755,10 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         const uint32_t T = SYM ? Md : pk_subsat_u16_k(M, k_oe_ins);                                              \
         const uint32_t ME = pk_max_i16(M, e2);                                                                   \
         const uint32_t HA = max_i16_lo(ME, FV);                                  /* H[j] */                      \
-        const uint32_t FA = max_i16_lo(T, sub_u16_lo(FV, v_e_ins));              /* F leaving column j */        \
+        const uint32_t FA = f_step_lo(T, FV, v_e_ins);                           /* F leaving column j */        \
         const uint32_t hprev = HB;                                                                               \
         HB = max_i16_hi_lo(ME, FA);                                           /* H[j+1] */                    \
-        FV = max_i16_hi_lo(T, sub_u16_lo(FA, v_e_ins));                     /* F leaving column j+1 */      \
+        FV = f_step_hi(T, FA, v_e_ins);                                  /* F leaving column j+1 */      \
         /* byte 0 = H[j-1] (hprev), byte 1 = E'[j], byte 2 = H[j] (HA byte 0), byte 3 = E'[j+1] */               \
         (OUT) = (EN << 8) | __builtin_amdgcn_perm(HA, hprev, 0x0c040c00u);                                       \
         (HJ) = HA;                                                                                               \
@@ -741,14 +767,13 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 // in the 2-cycle v_max_i16.  Trips cover disjoint, increasing column ranges, so the key that wins names the
                 // LAST group that holds the row maximum; which of its columns is the last one that holds it is read back from
                 // the stored row after the sweep (behind CELL16(end) below).  The cells outside the loop keep exact keys.
-                // No register copies in the loop (the compiler put three into the plain form of it): the pointers and the
-                // column are bumped in place at the end of a trip by 2-cycle adds on VGPR constants, behind every LDS access
-                // of the trip, and the loads of the two halves stay two ds_read_b32 (one LDS instruction more per trip):
+                // The trip's three maxima, the key and its fold into rowpk are one leaf (rowkey_fold): no reader of an asm result
+                // sits right behind it.  No register copies in the loop (the compiler put three into the plain form of it): the
+                // pointers are bumped in place at the end of a trip by 2-cycle adds on VGPR constants, behind every LDS access
+                // of the trip (the column by a plain add of such a constant, which the loop test may follow at once), and the loads of the two halves stay two ds_read_b32 (one LDS instruction more per trip):
                 // merged into one two-word read they land in a register pair that the next trip's read overwrites.
                 bsw_lds_u32 *cl = (bsw_lds_u32 *)cw;
                 bsw_lds_u8 *ql = (bsw_lds_u8 *)qp;
-                uint32_t k_cstep = 512u, k_qstep = 128u, k_jstep = 4u;
-                asm volatile("" : "+v"(k_cstep), "+v"(k_qstep), "+v"(k_jstep));
                 const int jlast = end - 3;
                 while (j < jlast) {
                     const uint32_t v1 = cl[64], q1 = ql[64];
@@ -758,10 +783,9 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     asm volatile("" ::: "memory");                   // keeps the next load from merging with v1's above
                     v0 = cl[128]; q0 = ql[128];                      // pair index <= end / 2: inside the row allocation
                     BSW_PAIR(v1, q1, cl[64], h2j)
-                    const uint32_t m4 = max_i16_lo(m01, max_i16_lo(h2j, HB));
-                    rowpk = max(rowpk, (m4 << 16) | (uint32_t)j);
-                    asm volatile("v_add_u32 %0, %0, %3\n\tv_add_u32 %1, %1, %4\n\tv_add_u32 %2, %2, %5"
-                                 : "+v"(cl), "+v"(ql), "+v"(j) : "v"(k_cstep), "v"(k_qstep), "v"(k_jstep) : "memory");
+                    rowpk = rowkey_fold(rowpk, h2j, HB, m01, (uint32_t)j);
+                    asm volatile("v_add_u32 %0, %0, %2\n\tv_add_u32 %1, %1, %3" : "+v"(cl), "+v"(ql) : "v"(k_cstep), "v"(k_qstep) : "memory");
+                    j += (int)k_jstep;
                 }
                 if (j + 1 < end) {
                     const uint32_t v1 = cl[64], q1 = ql[64];         // the word a trailing single column lives in
@@ -795,8 +819,8 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             if (rowmax == 0) {                              // zero-row guard of the right prune (header comment, step 10)
                 if constexpr (SO) {
                     if (dropped && beg == 0) {
-                        const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
-                        abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                        // (hrow: this row's left edge, stored cell 0)
+                        abandon = hrow > 0 && hrow + mul24(c.max_sc, min(tlen - 1 - i, qlen)) > best;
                     }
                 }
                 break;
@@ -836,7 +860,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             bool stop = false;
             if (c.zdrop > 0) {                              // (wave-uniform)
                 const int di = i - best_i, dj = rowmax_j - best_j;
-                const int gap = di > dj ? (di - dj) * e_del : (dj - di) * e_ins;
+                const int gap = di > dj ? mul24(di - dj, e_del) : mul24(dj - di, e_ins);
                 stop = !raised && best - rowmax - gap > c.zdrop;
                 if constexpr (SO) {                         // z-drop guard: the reference's row maximum may differ here
                     abandon = !raised && dropped && rowmax < best - c.zdrop;
@@ -844,7 +868,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 }
             }
             // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
-            const bool try_exit = SO && !raised && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
+            const bool try_exit = SO && !raised && rowmax + mul24(c.max_sc, min(rows_left, qlen - 1 - rowmax_j)) <= best;
             if (raised) {
                 best = rowmax; best_i = i; best_j = rowmax_j;
                 if constexpr (!SO) {
@@ -855,7 +879,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             if constexpr (SO) {
                 // right-edge guard of the left prune (header comment, step 5); a row that the z-drop test ends does not reach it
                 const bool guard = !stop && dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
-                                   hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best;
+                                   hleft - e_ins + mul24(c.max_sc, min(rows_left, qlen - end - 1)) > best;
                 abandon = abandon || guard;
                 stop = stop || guard;
             }
@@ -882,8 +906,8 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     // whose zero trim runs past a window (lz == 4, tz == 4) has all four halves zero under either operand
                     // and prunes nothing on that side.
                     const int rq = min(rows_left, qlen);
-                    const int hb = h0 - c.o_del - e_del * (i + 2);
-                    edge_pot = hb > 0 ? hb + c.max_sc * rq : 0;
+                    const int hb = hrow - e_del;                           // the next row's left edge
+                    edge_pot = hb > 0 ? hb + mul24(c.max_sc, rq) : 0;
                     const bool go = prune && base < qlen && (base != 0 || edge_pot <= best);
                     const uint32_t r2 = as_u32(pk_splat(rq)), m2 = as_u32(pk_splat(c.max_sc));
                     const uint32_t bestL = (uint32_t)(go ? best : 0) * 0x00010001u, bestR = (uint32_t)(prune ? best : 0) * 0x00010001u;

@@ -7,10 +7,12 @@
 // and stamps s_memtime around the loop: cycles per instruction per SIMD = wave cycles / (instructions x W ... see main).
 //
 //   hipcc --offload-arch=gfx950 -O3 valu_issue.hip -o valu_issue && ./valu_issue > profiles/rNN_valu_issue.md
+//   ./valu_issue v_mul_lo_u32 v_mad_u64      only the rows whose name holds one of the arguments
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <stdint.h>
+#include <string.h>
 #include <vector>
 #include <algorithm>
 
@@ -19,6 +21,12 @@
 #define ROW(INSN)                                                                                         \
     asm volatile(INSN(0) INSN(1) INSN(2) INSN(3) INSN(4) INSN(5) INSN(6) INSN(7)                          \
                  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)         \
+                 : "v"(x), "v"(y) : "vcc");
+
+// the same row for an instruction with a 64-bit destination: eight 64-bit accumulator chains (register pairs)
+#define ROW64(INSN)                                                                                       \
+    asm volatile(INSN(0) INSN(1) INSN(2) INSN(3) INSN(4) INSN(5) INSN(6) INSN(7)                          \
+                 : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4), "+v"(b5), "+v"(b6), "+v"(b7)         \
                  : "v"(x), "v"(y) : "vcc");
 
 #define I_ADD(k) "v_add_u32 %" #k ", %" #k ", %8\n"
@@ -113,19 +121,22 @@
 #define I_CNDAFTERCMP(k) "v_cndmask_b32 %" #k ", %" #k ", %8, vcc\n"
 #define I_READLANE(k) "v_readfirstlane_b32 s5, %" #k "\n"
 #define I_MBCNT(k) "v_mbcnt_lo_u32_b32 %" #k ", %8, %" #k "\n"
+#define I_MADU64(k) "v_mad_u64_u32 %" #k ", vcc, %8, %9, %" #k "\n"
+#define I_MULHI(k) "v_mul_hi_u32 %" #k ", %" #k ", %8\n"
 
 enum { OP_ADD, OP_PKADD, OP_PKMAX, OP_PKSUBC, OP_PKMUL, OP_PKMAXSEL, OP_PERM, OP_SDWA, OP_MAX3, OP_MAX, OP_AND, OP_ANDOR, OP_LSHL, OP_BFE,
-       OP_ALIGN, OP_ADD3, OP_LSHLADD, OP_MULLO, OP_MADU24, OP_DPP, OP_MOVDPP, OP_FMA, OP_PKFMA16, OP_CNDMASK, OP_CMP, OP_SADU8, OP_MIN3U, OP_SUB, OP_OR, OP_XOR, OP_MOV, OP_MINU, OP_MAXU, OP_LSHR, OP_ADDF, OP_SUBF, OP_MULF, OP_MAXF, OP_MINF, OP_MAX3F, OP_MED3F, OP_ADDF16, OP_MAXF16, OP_PKMAXF16, OP_PKADDF16, OP_ADDU16, OP_MAXI16, OP_MUL24, OP_CVTUB0, OP_CVTUB2, OP_CVTI, OP_CVTU8PK, OP_BFI, OP_XNOR, OP_DOT4, OP_ADDCO, OP_CMPCND, OP_SUBREVSDWA, OP_ANDE64, OP_ADDE64, OP_ADDFE64NEG, OP_MAXFE64ABS, OP_ANDSGPR, OP_ADDLIT, OP_ADDINL, OP_LSHL8, OP_LSHLV, OP_LSHL16, OP_LSHR16, OP_ASHR, OP_LSHLOR, OP_MINU16, OP_MAXU16, OP_MINI16, OP_SUBU16, OP_SUBU16C, OP_ADDU16C, OP_SUBU32C, OP_MULLO16, OP_MADU16, OP_MINF16, OP_SUBF16, OP_MULF16, OP_FMAF16, OP_MACF32, OP_MAXI16S, OP_ADDSGPR, OP_MAXI16LIT, OP_CNDAFTERCMP, OP_READLANE, OP_MBCNT, OP_COUNT };
+       OP_ALIGN, OP_ADD3, OP_LSHLADD, OP_MULLO, OP_MADU24, OP_DPP, OP_MOVDPP, OP_FMA, OP_PKFMA16, OP_CNDMASK, OP_CMP, OP_SADU8, OP_MIN3U, OP_SUB, OP_OR, OP_XOR, OP_MOV, OP_MINU, OP_MAXU, OP_LSHR, OP_ADDF, OP_SUBF, OP_MULF, OP_MAXF, OP_MINF, OP_MAX3F, OP_MED3F, OP_ADDF16, OP_MAXF16, OP_PKMAXF16, OP_PKADDF16, OP_ADDU16, OP_MAXI16, OP_MUL24, OP_CVTUB0, OP_CVTUB2, OP_CVTI, OP_CVTU8PK, OP_BFI, OP_XNOR, OP_DOT4, OP_ADDCO, OP_CMPCND, OP_SUBREVSDWA, OP_ANDE64, OP_ADDE64, OP_ADDFE64NEG, OP_MAXFE64ABS, OP_ANDSGPR, OP_ADDLIT, OP_ADDINL, OP_LSHL8, OP_LSHLV, OP_LSHL16, OP_LSHR16, OP_ASHR, OP_LSHLOR, OP_MINU16, OP_MAXU16, OP_MINI16, OP_SUBU16, OP_SUBU16C, OP_ADDU16C, OP_SUBU32C, OP_MULLO16, OP_MADU16, OP_MINF16, OP_SUBF16, OP_MULF16, OP_FMAF16, OP_MACF32, OP_MAXI16S, OP_ADDSGPR, OP_MAXI16LIT, OP_CNDAFTERCMP, OP_READLANE, OP_MBCNT, OP_MADU64, OP_MULHI, OP_COUNT };
 static const char *kNames[OP_COUNT] = {"v_add_u32", "v_pk_add_u16", "v_pk_max_i16", "v_pk_sub_u16 clamp", "v_pk_mul_lo_u16", "v_pk_max_i16 op_sel",
     "v_perm_b32", "v_add_u32_sdwa (BYTE_1)", "v_max3_i32", "v_max_i32", "v_and_b32", "v_and_or_b32", "v_lshlrev_b32", "v_bfe_u32",
     "v_alignbyte_b32", "v_add3_u32", "v_lshl_add_u32", "v_mul_lo_u32", "v_mad_u32_u24", "v_add_u32_dpp row_shr:1", "v_mov_b32_dpp row_shr:1",
-    "v_fma_f32", "v_pk_fma_f16", "v_cndmask_b32 (vcc)", "v_cmp_lt_u32 (vcc)", "v_sad_u8", "v_min3_u32", "v_sub_u32", "v_or_b32", "v_xor_b32", "v_mov_b32", "v_min_u32", "v_max_u32", "v_lshrrev_b32", "v_add_f32", "v_sub_f32", "v_mul_f32", "v_max_f32", "v_min_f32", "v_max3_f32", "v_med3_f32", "v_add_f16", "v_max_f16", "v_pk_max_f16", "v_pk_add_f16", "v_add_u16", "v_max_i16", "v_mul_u32_u24", "v_cvt_f32_ubyte0", "v_cvt_f32_ubyte2", "v_cvt_f32_i32", "v_cvt_pk_u8_f32", "v_bfi_b32", "v_xnor_b32", "v_dot4_i32_i8", "v_add_co_u32 (vcc)", "v_cmp_eq_u32 + v_cndmask_b32 (pair = 2 instr)", "v_sub_u32_sdwa (WORD_1)", "v_and_b32_e64 (VOP3 encoding)", "v_add_u32_e64 (VOP3 encoding)", "v_add_f32_e64 with neg modifier", "v_max_f32_e64 with abs modifier", "v_and_b32 with SGPR operand", "v_add_u32 with literal", "v_add_u32 with inline constant", "v_lshlrev_b32 by 8", "v_lshlrev_b32 by VGPR", "v_lshlrev_b16 by 1", "v_lshrrev_b16 by 1", "v_ashrrev_i32 by 1", "v_lshl_or_b32", "v_min_u16", "v_max_u16", "v_min_i16", "v_sub_u16", "v_sub_u16 clamp", "v_add_u16 clamp", "v_sub_u32 clamp", "v_mul_lo_u16", "v_mad_u16", "v_min_f16", "v_sub_f16", "v_mul_f16", "v_fma_f16", "v_fmac_f32", "v_max_i16 with SGPR operand", "v_add_u32 with SGPR operand", "v_max_i16 with inline constant", "v_cndmask_b32 x8 after one v_cmp (8 instr)", "v_readfirstlane_b32 s5 (SALU dest)", "v_mbcnt_lo_u32_b32"};
+    "v_fma_f32", "v_pk_fma_f16", "v_cndmask_b32 (vcc)", "v_cmp_lt_u32 (vcc)", "v_sad_u8", "v_min3_u32", "v_sub_u32", "v_or_b32", "v_xor_b32", "v_mov_b32", "v_min_u32", "v_max_u32", "v_lshrrev_b32", "v_add_f32", "v_sub_f32", "v_mul_f32", "v_max_f32", "v_min_f32", "v_max3_f32", "v_med3_f32", "v_add_f16", "v_max_f16", "v_pk_max_f16", "v_pk_add_f16", "v_add_u16", "v_max_i16", "v_mul_u32_u24", "v_cvt_f32_ubyte0", "v_cvt_f32_ubyte2", "v_cvt_f32_i32", "v_cvt_pk_u8_f32", "v_bfi_b32", "v_xnor_b32", "v_dot4_i32_i8", "v_add_co_u32 (vcc)", "v_cmp_eq_u32 + v_cndmask_b32 (pair = 2 instr)", "v_sub_u32_sdwa (WORD_1)", "v_and_b32_e64 (VOP3 encoding)", "v_add_u32_e64 (VOP3 encoding)", "v_add_f32_e64 with neg modifier", "v_max_f32_e64 with abs modifier", "v_and_b32 with SGPR operand", "v_add_u32 with literal", "v_add_u32 with inline constant", "v_lshlrev_b32 by 8", "v_lshlrev_b32 by VGPR", "v_lshlrev_b16 by 1", "v_lshrrev_b16 by 1", "v_ashrrev_i32 by 1", "v_lshl_or_b32", "v_min_u16", "v_max_u16", "v_min_i16", "v_sub_u16", "v_sub_u16 clamp", "v_add_u16 clamp", "v_sub_u32 clamp", "v_mul_lo_u16", "v_mad_u16", "v_min_f16", "v_sub_f16", "v_mul_f16", "v_fma_f16", "v_fmac_f32", "v_max_i16 with SGPR operand", "v_add_u32 with SGPR operand", "v_max_i16 with inline constant", "v_cndmask_b32 x8 after one v_cmp (8 instr)", "v_readfirstlane_b32 s5 (SALU dest)", "v_mbcnt_lo_u32_b32", "v_mad_u64_u32 (64-bit accumulator, vcc carry)", "v_mul_hi_u32"};
 
 template <int OP>
 __global__ __launch_bounds__(256) void issue(uint32_t *out, unsigned long long *cyc, uint32_t seed) {
     extern __shared__ uint32_t lds[];
     uint32_t a0 = threadIdx.x + seed, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 * 11, a5 = a0 * 13, a6 = a0 * 17, a7 = a0 * 19;
     uint32_t x = seed * 0x9E3779B9u + threadIdx.x, y = 0x03020100u ^ (seed & 0x01010101u);
+    unsigned long long b0 = a0, b1 = a1, b2 = a2, b3 = a3, b4 = a4, b5 = a5, b6 = a6, b7 = a7;      // (OP_MADU64 only)
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #pragma unroll 1
     for (int r = 0; r < REPS; r++) {
@@ -222,10 +233,13 @@ __global__ __launch_bounds__(256) void issue(uint32_t *out, unsigned long long *
             else if constexpr (OP == OP_CNDAFTERCMP) { ROW(I_CNDAFTERCMP) }
             else if constexpr (OP == OP_READLANE) { ROW(I_READLANE) }
             else if constexpr (OP == OP_MBCNT) { ROW(I_MBCNT) }
+            else if constexpr (OP == OP_MADU64) { ROW64(I_MADU64) }
+            else if constexpr (OP == OP_MULHI) { ROW(I_MULHI) }
         }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    const uint32_t acc = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;
+    uint32_t acc = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;
+    if constexpr (OP == OP_MADU64) { const unsigned long long b = b0 ^ b1 ^ b2 ^ b3 ^ b4 ^ b5 ^ b6 ^ b7; acc ^= (uint32_t)b ^ (uint32_t)(b >> 32); }
     if (acc == 0x12345678u) lds[threadIdx.x] = acc;          // keeps the LDS allocation and the chains alive
     out[blockIdx.x * 256 + threadIdx.x] = acc;
     if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * 4 + (threadIdx.x >> 6)] = t1 - t0;
@@ -238,7 +252,7 @@ template <int OP> static void reg(kern_t *tab) {
     if constexpr (OP + 1 < OP_COUNT) reg<OP + 1>(tab);
 }
 
-int main() {
+int main(int argc, char **argv) {      // optional arguments: substrings of instruction names; only matching rows are run
     kern_t tab[OP_COUNT];
     reg<0>(tab);
     hipDeviceProp_t prop;
@@ -262,6 +276,9 @@ int main() {
     for (int i = 0; i < 4; i++) printf("---|---|---|");
     printf("\n");
     for (int op = 0; op < OP_COUNT; op++) {
+        bool want = argc < 2;
+        for (int a = 1; a < argc; a++) want = want || strstr(kNames[op], argv[a]) != nullptr;
+        if (!want) continue;
         printf("| `%s` |", kNames[op]);
         for (int wi = 0; wi < 4; wi++) {
             const int W = waves[wi], blocks = cus * W * rounds;

@@ -9,7 +9,8 @@ A listing whose bsw_dp8 has two template arguments only (before score-only becam
 Prints, for bsw_dp8<SYM, MS1, SO>: the innermost column loop (the deepest innermost loop with the most VALU instructions) -- VALU, slow / fast
 split, DS, v_mov_b32 count and the weighted cost slow x 4.22 + fast x 2.56 -- and the VALU count of the blocks of the loop around it that lie outside
 every inner loop (the per-row code), with the SALU instructions (s_waitcnt, s_nop and s_branch / s_cbranch_* not counted among
-them), the branches and the basic blocks of the same blocks.
+them), the branches and the basic blocks of the same blocks; and, for both, the s_nop (wait states the compiler had to pad), and
+the full 32-bit / 64-bit multiplies (v_mul_lo_u32, v_mul_hi_*, v_mad_u64_u32), and the v_mov_b32 of the per-row blocks.
 
 Slow class (one instruction every ~4.2 cycles at two waves per SIMD): packed 16-bit, VOP3-only integer ops (v_perm, v_lshl_or,
 v_and_or, v_max3, v_bfi, v_bfe, v_alignbit, v_add3, v_lshl_add, v_mad), 32-bit max / min, 24-bit and 32-bit multiplies, left
@@ -23,6 +24,7 @@ FAST = 2.56
 SLOW_OPS = re.compile(r"^v_(pk_|perm_|lshl_or|and_or|or3|max3|min3|med3|bfi|bfe|alignb|add3|lshl_add|add_lshl|mad_|mul_|"
                       r"max_[iu]32|min_[iu]32|lshlrev_b32|lshlrev_b64|lshrrev_b64|cmp|cndmask|add_co|sub_co|subrev_co|addc|subb|readfirstlane|readlane|"
                       r"mbcnt|xnor|cvt_|ffb|sad_|dot)")
+WIDE_MUL = re.compile(r"^v_(mul_lo_[iu]32|mul_hi_[iu]32|mad_[iu]64_[iu]32)")      # full multiplies (4 cycles like the 24-bit forms, profiles/bsw_row_edges.md)
 INLINE = re.compile(r"^(-?\d+|0x[0-9a-f]+)$")
 
 
@@ -97,6 +99,7 @@ def main():
     fast = len(valu) - slow
     ds = sum(i.startswith("ds_") for i in body)
     mov = sum(i.startswith("v_mov_b32") for i in valu)
+    nop = sum(i.startswith("s_nop") for i in body)
     # the row loop's own blocks: its header and the blocks annotated as its members (other loops of the same depth, such as the
     # one that writes row -1, are not per-row code)
     rowblocks = [b for b in blocks if b[1] == cdepth - 1 and not b[3] and (b[0] == "." + rowloop or (b[4] and b[4][-1] == rowloop and "Loop Header" not in b[0]))]
@@ -104,9 +107,14 @@ def main():
     branch = sum(i.startswith(("s_branch", "s_cbranch")) for b in rowblocks for i in b[2])
     salu = sum(i.startswith("s_") and not i.startswith(("s_waitcnt", "s_nop", "s_branch", "s_cbranch")) for b in rowblocks for i in b[2])
     lds = sum(i.startswith("ds_") for b in rowblocks for i in b[2])
+    rownop = sum(i.startswith("s_nop") for b in rowblocks for i in b[2])
+    rowmov = sum(i.startswith("v_mov_b32") for b in rowblocks for i in b[2])
+    rowmul = sum(bool(WIDE_MUL.match(i)) for b in rowblocks for i in b[2])
+    loopmul = sum(bool(WIDE_MUL.match(i)) for i in valu)
     print(f"bsw_dp8<{sym},{ms1}{',' + so if three else ''}> column loop {label}: VALU {len(valu)} (slow {slow}, fast {fast}), DS {ds}, v_mov_b32 {mov}, "
+          f"s_nop {nop}, 32/64-bit multiplies {loopmul}, "
           f"weighted {slow * SLOW + fast * FAST:.1f} cycles; per-row blocks outside the inner loops: VALU {row}, SALU {salu}, "
-          f"branches {branch}, DS {lds}, basic blocks {len(rowblocks)}")
+          f"branches {branch}, DS {lds}, basic blocks {len(rowblocks)}, s_nop {rownop}, v_mov_b32 {rowmov}, 32/64-bit multiplies {rowmul}")
     if "-v" in sys.argv:
         for i in valu:
             print(f"  {classify(i):4s} {i}")
