@@ -8,9 +8,10 @@
 //   one pair strictly sequential.  The MI355X equivalent of that idea is one pair per
 //   wavefront lane:
 //
-//   1. bucket  -- counting sort of the pairs by (query length, reference length / 8) so
-//                 that the 64 lanes of a wave carry near-identical work and diverge little
-//                 (the reference sorts by len1 for the same reason, bandedSWA.cpp:372-407);
+//   1. bucket  -- counting sort of the pairs by (query length, deficit of the ungapped
+//                 extension: bsw_key) so that the 64 lanes of a wave carry near-identical work
+//                 and diverge little (the reference sorts by len1 for the same reason,
+//                 bandedSWA.cpp:372-407);
 //   2. bsw_dp  -- one wave (= one workgroup) per 64 sorted pairs.  The H/E row of every
 //                 lane lives in LDS as [column][lane] dwords (bank = lane, conflict-free
 //                 for any per-lane column), H and E packed as two u16 in one dword when
@@ -128,6 +129,55 @@
 //      two guards.  With a dead or zero edge nothing the reference still holds can exceed best, and ending returns its score.
 //      (9 of the 10 M read-like pairs at the defaults; found by the model at a mismatch score of -128, where rows of zeros are common.)
 //
+// Seeded prune of score-only calls (same calls, same pairs: restrictions (a) and (b); the six-field form is untouched;
+// profiles/bsw_seeded_prune.md).  `best` is the score reached SO FAR, about h0 early in a pair, so the tests above keep every cell
+// within about (qlen - i) / 2 columns of the diagonal although the pair ends far above h0.  A lower bound L of the pair's FINAL score is
+// known before row 0, and a cell whose potential is below L cannot lead to the final score whatever `best` is at its row.
+//   L (pass 0 of the sort, one scan of both sequences: inside bsw_hist<true>, or bsw_seed beside DP kernels; the record carries it).  d_0 = h0 and d_{k+1} = d_k +
+//     mat[ref[k]][qry[k]] for k = 0 .. min(qlen, tlen) - 1, codes above 4 as N, stopped at the first d <= 0;
+//         L = max( h0,  max_k d_k )                                                    with zdrop == 0,
+//         L = max( h0,  max_k min( d_k,  zdrop + 1 + min_{m < k} d_m ) )               with zdrop > 0.
+//     L <= the reference's score: while every d so far is positive, cell (k, k) takes M from a non-zero diagonal, so H(k, k) >= d_{k+1}
+//     (the DP is monotone in its inputs; cell (0, 0) reads h0).  The cell is inside the reference's band in every row: |i - j| = 0 <= w,
+//     and the zero trims pass only zero cells while stored cell k + 1 = H(k, k) > 0.  Its row is not a zero row.  So if the reference
+//     sweeps row k its score is at least d_{k+1}; the only other way its row loop ends earlier is a z-drop in a row i < k, which needs
+//     best - rowmax_i - gap > zdrop with gap >= 0 and rowmax_i >= H(i, i) >= d_{i+1}: its score, that `best`, then exceeds
+//     d_{i+1} + zdrop.  (The minimum above also runs over d_0: more conservative than needed.)  The score is never below h0.
+//   Threshold thr = max(best, L - 1) replaces `best` in the left prune's cell test and its column-0 edge test, in the right prune's cell
+//     test, in the right-edge guard and in the zero-row guard.  L - 1 and not L: a cell of the diagonal path of a perfect ungapped
+//     match has potential exactly L (tools/gen/bsw_exit_model.c has that wrong rule as a negative control).  The z-drop guard, `best`
+//     itself and the exit's bound <= best are unchanged.
+//   Prune of row -1.  Before row 0 the cells of row -1 are dropped from the right under the right prune's test with R = tlen rows left and
+//     best = h0 (stored cell j is the diagonal of cell (0, j)); cell 0 stays.  Value and potential both fall from left to right, so
+//     the live cells are a prefix, and no cap applies.  end = min(jl + 2, qlen) for the last live cell jl, and an `end` below
+//     min(qlen, w + 1), what the reference sweeps row 0 with, counts as a drop: row 0's F runs on right of the last live cell of
+//     row -1, and only the right-edge guard judges the F that leaves the narrowed band.
+//   Gates (economy, not correctness; measured on the CPU model, profiles/bsw_seeded_prune.md).  The threshold is on wherever the
+//     prunes are.  The prune of row -1 is on only with max_sc <= e_ins: where a match is worth more than an inserted base costs, the
+//     right-edge guard sends 40 - 70 % of the read-like pairs through a second pass and the cell count rises by up to a third.  Both are
+//     off for a pair whose band cannot hold more than nine cells, min(qlen, 2 w + 1) <= 9: such a band is swept in at most two loop trips
+//     and the seed removes next to nothing (and the tests of the narrow band's edge-cell paths read their cases off the rule's trace).
+// Proof, continued.  Call a cell dead when value + max_sc * min(rows left, columns left) <= thr, S the reference's score (L <= S).
+//  11. thr never falls (best never falls, L is fixed) and thr < S until `best` reaches S, so steps 1, 2 and 8 hold with thr for `best`:
+//      what is dead stays dead, a dropped cell is zero or stands for a dead cell, P <= reference, and P == reference wherever the
+//      reference's cell is not dead.  The prune of row -1 is step 8 applied to the initial row; it keeps (a) (it only writes zeros).
+//  12. Step 3 becomes: the pruned run's `best` may LAG the reference's in a row (a cell above `best` but with potential <= L - 1 may
+//      have been dropped), never lead it.  The first cell that holds S has potential >= S along its whole chain of largest sources,
+//      which is above thr at every row before it (thr <= max(best, L - 1) < S there): none of them is dead, the pruned run holds
+//      them at equal values, and its `best` reaches S in the same row, unless a guard has sent the pair back before.  Nothing
+//      else reads best_i / best_j of a pair that has dropped a cell: its own z-drop test cannot fire before the z-drop guard does.
+//  13. The run does not end early with best < S.  Exit: the chain to S is held and its potential exceeds best, so the bound does.
+//      Zero row: the held cells are zero, so the chain runs through the left edge (the zero-row guard abandons: that edge's potential
+//      is >= S > thr), or through cells right of `end`, which are zero by (a).  Right edge: an F that leaves the band with potential
+//      above thr abandons the pass (step 5 with thr); every other F is dead.
+//  14. Step 7 (z-drop).  In a row where the reference z-drops its `best` is S and the row did not raise it, so S was reached in an
+//      earlier row and by step 12 the pruned run's `best` is S too; its rowmax <= the reference's < S - zdrop, so the z-drop guard
+//      abandons the pass (a pair that has dropped nothing IS the reference).  In a row where the reference does not z-drop the pruned
+//      run either goes on or abandons the pass; the second pass is the exit alone.
+// The sort key of a score-only call (a six-field call keeps (query length, reference length / 8, h0 / 32) and computes no L) is
+// (query length, deficit) with deficit = qlen - (L - h0) / max_sc, the query bases the ungapped extension does not
+// match: under the threshold a cell survives within about deficit / 2 columns of the diagonal, so the deficit is the pair's band width.
+//
 // Where the rule lives in bsw_dp8 (the 8-bit kernel; profiles/bsw_row_tail.md): score-only is a template argument, so the six-field
 // form holds none of the above and the score-only form none of the six-field bookkeeping.  Behind a row's sweep the zero trim and
 // both prunes are ONE evaluation of the two four-cell windows -- a zero cell is a dropped cell, so with `best` taken as 0 the
@@ -154,24 +204,32 @@ constexpr int kNumKeys = kQBuckets * kTBuckets;
 constexpr int kClassStep = 16;            // query-length classes for LDS sizing
 constexpr int kNumClasses = kQBuckets / kClassStep;
 constexpr int kSlices = 2;                // a large batch is sorted in this many slices of its pair range (bsw_run_device_impl)
-// The three constants are measured, profiles/bsw_slices.md (10 M read-like pairs; the unsliced call takes 24.94 ms per step):
-//   kSlice0: 786 432 pairs 24.57 ms, 1 048 576 pairs 24.35, 1 572 864 pairs 24.31.  Slice 0's DP has to outlast slice 1's sort
-//     and the host's wait for it (1.0 ms; the class launches of 2^20 pairs keep their two streams busy for 5 ms), and every
-//     pair of slice 0 sits in a small launch: 2^20 pairs in 8 classes are 2 300 waves each, little more than the chip holds
-//     at once (2 048).  The smaller of the two sizes that measured equal.
-//   kSliceMin: a sliced call pays for sixteen class launches instead of eight and gains the sort of slice 1.  It measured
-//     0.23 ms faster than the unsliced call at 3 M pairs, 0.37 at 4 M, 0.46 at 6 M, 0.68 at 8 M; 2^22 is the first size whose
-//     gain stands clear of the spread of the runs.
-//   kSortGridBeside: at the 1 024 workgroups of a sort that has the GPU to itself, the sort beside the DP costs the DP 0.3 ms
-//     (the DP runs two waves per SIMD and hides little memory latency; the sort saturates the atomic rate); at 256 and at 64
-//     nothing measurable, and slice 1's sort still ends 1.0 ms into the step.
-constexpr int64_t kSlice0 = 1 << 20;      // pairs in slice 0 of a sliced call
+// The constants are measured (10 M read-like pairs, score-only).  kSlice0, kSortGridBeside and kSeedGridBeside with the seeded
+// prune, profiles/bsw_seeded_prune.md; kSliceMin was NOT measured again and is the value of profiles/bsw_slices.md.
+//   kSlice0: slice 0's DP has to outlast slice 1's sort and the host's wait for it, and every pair of slice 0 sits in a small
+//     launch (2^20 pairs in 8 classes are 2 300 waves each, little more than the chip holds at once).  With bsw_seed in front of
+//     the histogram slice 1's sort ends 2.3 ms into the step, not 1.0.  Medians of three runs per size, runs within 0.13 ms:
+//     1 048 576 pairs 21.95 ms, 1 572 864 pairs 21.62, 2 097 152 pairs 22.00 (a second series with 786 432 pairs in it: 22.12,
+//     22.11, 21.76, 22.10).  Too small and the GPU waits for slice 1's sort, too large and too many pairs sit
+//     in slice 0's small launches.
+//   kSliceMin (before the seeded prune): a sliced call pays for sixteen class launches instead of eight and gains the sort of
+//     slice 1.  It measured 0.23 ms faster than the unsliced call at 3 M pairs, 0.37 at 4 M, 0.46 at 6 M, 0.68 at 8 M; 2^22 is
+//     the first size whose gain stood clear of the spread of the runs.
+//   kSortGridBeside: medians of three runs, 64 workgroups 22.05 ms, 256 workgroups 21.66, 1 024 workgroups 21.76 (runs within
+//     0.07 ms).  At 64 the histogram and the scatter of slice 1 outlast slice 0's DP; at 1 024 they take wave slots from it.
+//   kSeedGridBeside: bsw_seed is VALU work like the DP (about fifteen instructions per base) and takes every wave slot it is
+//     given: at 2 048 workgroups slice 0's class launches wait for it (22.32 ms per step), at 512 22.11, at 256 22.63 and at 128
+//     24.56 -- there the pass outlasts slice 0's DP and the GPU waits for slice 1's sort.
+constexpr int64_t kSlice0 = 1572864;      // pairs in slice 0 of a sliced score-only call
+constexpr int64_t kSlice0Full = 1 << 20;  // ... of a sliced six-field call: its sort has no scan in it, the value of profiles/bsw_slices.md stays
 constexpr int64_t kSliceMin = 1 << 22;    // fewest pairs of a sliced call
 constexpr int kSortGridBeside = 256;      // workgroups of bsw_hist / bsw_scatter when they run beside DP kernels
-static_assert(kSliceMin >= (1 << 21) && kSlice0 < kSliceMin && kSlice0 >= 64 * 8192, "slice 0 has to fill the chip with its class launches, and calls below 2^21 pairs stay unsliced");
+constexpr int kSeedGridBeside = 512;      // workgroups of bsw_seed (it only runs beside DP kernels: bsw_hist<true> makes L otherwise)
+static_assert(kSliceMin >= (1 << 21) && kSlice0 < kSliceMin && kSlice0Full >= 64 * 8192 && kSlice0 >= kSlice0Full, "slice 0 has to fill the chip with its class launches, and calls below 2^21 pairs stay unsliced");
 
 struct BswConst {
     int32_t o_del, e_del, o_ins, e_ins, zdrop, end_bonus, w, max_sc;
+    int32_t seed;         // economy gates of the seeded prune (header comment): bit 0 the threshold max(best, L - 1), bit 1 the prune of row -1
     uint32_t row_lo[5];   // biased (+128) scores mat[t][0..3], one byte each
     uint32_t row_hi[5];   // biased score mat[t][4] in byte 0
 };
@@ -194,12 +252,23 @@ struct BswIO {
     int64_t ref_hi, qry_hi;        // end of the bytes that really hold the caller's data (= ref_bytes / qry_bytes for device slabs; the
 };                                 // end of what gab_bsw_run COPIED: its window is padded to 256 bytes, and the padding is not the caller's data)
 
-// (query length, reference length / 8, h0 / 32): lanes of a wave then run the same number of rows AND start with bands of
-// similar width (row -1 is non-zero up to column ~h0, and the band stays ~2 x score wide until it reaches w)
-__device__ __forceinline__ int bsw_key(int qlen, int tlen, int h0) {
-    int tb = tlen >> 3; if (tb > kTBuckets / 4 - 1) tb = kTBuckets / 4 - 1;
-    int hc = h0 >> 5; if (hc > 3) hc = 3;
-    return (qlen - 1) * kTBuckets + tb * 4 + hc;
+// (query length, deficit): deficit = qlen - (L - h0) / max_sc is the number of query bases that the ungapped extension behind the
+// seeded prune's lower bound L (bsw_seed) does NOT match, 0 for a perfect ungapped match.  Lanes of a wave then run the same number
+// of rows, and bands of similar width: with thr = max(best, L - 1) a cell survives while it lies within about deficit / 2 columns of
+// the diagonal.  On the read-like input the deficit alone predicts a pair's cell count (correlation 0.91; reference length and h0,
+// the minor parts of the key before: 0.07 and 0.05); profiles/bsw_seeded_prune.md has the candidates this one was picked from.
+// A six-field call (seeded == 0) has no exit and no prune: its rows are the reference's, as many as the reference is long, and its
+// band starts as wide as h0 allows.  It keeps the key it had, (query length, reference length / 8, h0 / 32), and bsw_seed only
+// validates for it: under the deficit key its step at 10 M pairs measured 47.1 ms against 39.3 (profiles/bsw_seeded_prune.md).
+__device__ __forceinline__ int bsw_key(int qlen, int tlen, int h0, int L, int max_sc, int seeded) {
+    if (!seeded) {
+        int tb = tlen >> 3; if (tb > kTBuckets / 4 - 1) tb = kTBuckets / 4 - 1;
+        int hc = h0 >> 5; if (hc > 3) hc = 3;
+        return (qlen - 1) * kTBuckets + tb * 4 + hc;
+    }
+    int d = qlen - (L - h0) / (max_sc > 1 ? max_sc : 1);
+    d = d < 0 ? 0 : d > kTBuckets - 1 ? kTBuckets - 1 : d;
+    return (qlen - 1) * kTBuckets + d;
 }
 
 // A 151-bp read set puts almost all pairs into ~256 NEIGHBOURING keys (one query length), i.e. 1 KB of counters behind a
@@ -208,31 +277,112 @@ __device__ __forceinline__ int bsw_key(int qlen, int tlen, int h0) {
 __device__ __forceinline__ int bsw_hslot(int key) { return (int)(((uint32_t)key * 4099u) & (uint32_t)(kNumKeys - 1)); }
 static_assert((kNumKeys & (kNumKeys - 1)) == 0, "bsw_hslot needs a power-of-two key space");
 
-// ---- pass 1: validate + histogram ------------------------------------------------------
+__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    return w;
+}
+
+// ---- pass 0: validate + the seeded prune's lower bound L per pair ---------------------------
+// L (header comment): the ungapped extension from d = h0 along the main diagonal, stopped at the first d <= 0, every prefix held
+// down by what a z-drop of the reference in an earlier row would still return.  seed[i] = L, or -1 for a pair that fails the
+// validation (L >= h0 >= 0 otherwise): bsw_hist and bsw_scatter read it instead of validating again.  One thread per pair reads both
+// sequences; the pass issues no atomics, and beside the DP kernels of another slice its grid is kSeedGridBeside.
+// (seeded == 0, a six-field call: validation only, L = h0; no sequence is read)
+// Where it runs: a call's only sort, and slice 0's, have the GPU to themselves and make L inside bsw_hist<true> -- no launch of
+// its own, which a batch of 100 000 pairs cannot hide -- while slice 1's sort runs beside slice 0's DP kernels, where the scan
+// wants another grid than the histogram's atomics: bsw_seed, then bsw_hist<false>.
+__device__ __forceinline__ void bsw_seed_mat(const BswConst &c, int *s_mat) {      // the 25 scores, for per-lane look-ups; the caller syncs
+    if (threadIdx.x < 25) {
+        const int t = threadIdx.x / 5, q = threadIdx.x % 5;
+        s_mat[threadIdx.x] = (int)((q < 4 ? c.row_lo[t] >> (8 * q) : c.row_hi[t]) & 0xffu) - 128;
+    }
+}
+__device__ __forceinline__ int bsw_seed_of(const BswIO &io, const BswConst &c, const int *s_mat, int seeded, int64_t i) {
+    {
+        const int ql = io.len2[i], tl = io.len1[i], h = io.h0[i];
+        const int64_t ro = io.ref_off[i], qo = io.qry_off[i];
+        const bool ok = ql >= 1 && ql <= GAB_BSW_MAX_QLEN && tl >= 1 && tl <= GAB_BSW_MAX_TLEN && h >= 0 &&
+                        h <= (1 << 29) && ro >= io.ref_lo && qo >= io.qry_lo &&
+                        ro + tl + 3 <= io.ref_bytes && qo + ql + 3 <= io.qry_bytes &&   // (the kernels read dwords from the sequence's own start)
+                        ro + tl <= io.ref_hi && qo + ql <= io.qry_hi;
+        if (!ok) return -1;
+        if (!seeded) return h;                              // (wave-uniform)
+        const uint8_t *const t = io.ref + ro, *const q = io.qry + qo;
+        const int n = ql < tl ? ql : tl;
+        // Sixteen bases per trip, one 16-byte load per sequence: a pair costs ten memory round trips instead of the seventy-six of a
+        // dword per trip (that form was bound by their latency: 0.30 ms per million pairs, against 0.13).  Nothing is read further
+        // than three bytes past either sequence's end: the last trip falls back to dwords, each read only where it holds a base.
+        int d = h, L = h, mn = h;
+        bool live = h > 0;                                  // the scan goes on: no d <= 0 so far and bases left
+        for (int k = 0; k < n && live; k += 16) {
+            uint32_t tw[4], qw[4];
+            if (k + 16 <= n + 3) {                          // one 16-byte load per sequence: a quarter of the cache-line requests
+                __builtin_memcpy(tw, t + k, 16);
+                __builtin_memcpy(qw, q + k, 16);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const bool in = k + 4 * b < n;
+                    tw[b] = in ? load_u32_unaligned(t + k + 4 * b) : 0u;
+                    qw[b] = in ? load_u32_unaligned(q + k + 4 * b) : 0u;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 16; b++) {
+                const uint32_t tc = (tw[b >> 2] >> (8 * (b & 3))) & 0xffu, qc = (qw[b >> 2] >> (8 * (b & 3))) & 0xffu;
+                const int nd = d + s_mat[(tc < 4u ? tc : 4u) * 5u + (qc < 4u ? qc : 4u)];
+                live = live && k + b < n && nd > 0;
+                if (live) {
+                    d = nd;
+                    int v = d;
+                    if (c.zdrop > 0 && d - mn > c.zdrop) v = c.zdrop + 1 + mn;
+                    L = v > L ? v : L;
+                    mn = d < mn ? d : mn;
+                }
+            }
+        }
+        return L;
+    }
+}
+__global__ __launch_bounds__(256) void bsw_seed(BswIO io, BswConst c, int seeded, int64_t lo, int64_t hi, int32_t *__restrict__ seed) {
+    __shared__ int s_mat[25];
+    bsw_seed_mat(c, s_mat);
+    __syncthreads();
+    int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < hi; i += stride) seed[i] = bsw_seed_of(io, c, s_mat, seeded, i);
+}
+
+// ---- pass 1: histogram -----------------------------------------------------------------------
 // The value the histogram atomic returns is the pair's rank inside its bucket: it is kept, so that the scatter pass
 // needs no second round of 10 M atomics (each pass was atomic-throughput bound at ~13 G/s).
 // Pairs lo .. hi - 1 of the batch (one slice of it, or all): hist and st are the slice's own, rank is indexed by the pair.
-__global__ __launch_bounds__(256) void bsw_hist(BswIO io, int64_t lo, int64_t hi, uint32_t *hist, uint32_t *rank, BswStats *st) {
+// FUSED: the pass makes seed[i] itself (pass 0 above) instead of reading what bsw_seed wrote.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void bsw_hist(BswIO io, BswConst c, int seeded, int64_t lo, int64_t hi, int32_t *seed,
+                                                uint32_t *hist, uint32_t *rank, BswStats *st) {
     __shared__ int cls_h0[kNumClasses];      // largest h0 per query-length class among this workgroup's pairs
+    __shared__ int s_mat[25];
+    const int max_sc = c.max_sc;
     if (threadIdx.x < kNumClasses) cls_h0[threadIdx.x] = 0;
+    if (FUSED) bsw_seed_mat(c, s_mat);
     __syncthreads();
     int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < hi; i += stride) {
-        int ql = io.len2[i], tl = io.len1[i], h = io.h0[i];
-        int64_t ro = io.ref_off[i], qo = io.qry_off[i];
-        bool ok = ql >= 1 && ql <= GAB_BSW_MAX_QLEN && tl >= 1 && tl <= GAB_BSW_MAX_TLEN && h >= 0 &&
-                  h <= (1 << 29) && ro >= io.ref_lo && qo >= io.qry_lo &&
-                  ro + tl + 3 <= io.ref_bytes && qo + ql + 3 <= io.qry_bytes &&   // (the kernels read dwords from the sequence's own start)
-                  ro + tl <= io.ref_hi && qo + ql <= io.qry_hi;
-        if (!ok) {
+        const int L = FUSED ? bsw_seed_of(io, c, s_mat, seeded, i) : seed[i];
+        if (FUSED) seed[i] = L;            // (bsw_scatter and the records read it)
+        if (L < 0) {                       // failed the validation of pass 0
             atomicAdd(&st->bad, 1);
             atomicMin((unsigned int *)&st->first_bad, (unsigned int)(i + 1 > 0x7fffffff ? 0x7fffffff : i + 1));
             rank[i] = ~0u;                 // (the scatter pass is already queued behind this one: it must not place this pair)
             continue;
         }
+        const int ql = io.len2[i], h = io.h0[i];
+        const int tl = seeded ? 0 : io.len1[i];             // (the seeded key does not read it)
         if (h > 0) atomicMax(&cls_h0[(ql - 1) / kClassStep], h);
-        rank[i] = atomicAdd(&hist[bsw_hslot(bsw_key(ql, tl, h))], 1u);
+        rank[i] = atomicAdd(&hist[bsw_hslot(bsw_key(ql, tl, h, L, max_sc, seeded))], 1u);
     }
     __syncthreads();
     if (threadIdx.x < kNumClasses && cls_h0[threadIdx.x] > 0) atomicMax(&st->max_h0[threadIdx.x], cls_h0[threadIdx.x]);
@@ -277,29 +427,26 @@ __global__ __launch_bounds__(1024) void bsw_scan_b(uint32_t *__restrict__ start,
 // One 32-byte record per pair, written here from coalesced reads of the five input arrays and read coalesced by the DP
 // kernels: the DP kernels used to gather the five fields through the permutation (five random 64-byte sectors per pair,
 // 3.2 GB of the 7.6 GB the DP fetched per 10 M pairs against 2.1 GB of algorithmic bytes).
-struct __attribute__((aligned(32))) BswRec { int64_t ref_off, qry_off; int32_t len1, len2, h0; uint32_t id; };
+// (lens = len1 | len2 << 16: len1 <= GAB_BSW_MAX_TLEN < 2^15, len2 <= GAB_BSW_MAX_QLEN; L is bsw_seed's)
+struct __attribute__((aligned(32))) BswRec { int64_t ref_off, qry_off; int32_t lens, h0, L; uint32_t id; };
+static_assert(sizeof(BswRec) == 32 && GAB_BSW_MAX_TLEN < (1 << 16) && GAB_BSW_MAX_QLEN < (1 << 15), "BswRec packs both lengths into one word");
 
 // (pairs lo .. hi - 1 as in bsw_hist; start counts from the slice's first record, recs is where the slice's records begin, and
 // rec.id stays the pair's index in the whole batch)
-__global__ __launch_bounds__(256) void bsw_scatter(BswIO io, int64_t lo, int64_t hi, const uint32_t *__restrict__ start,
-                                                   const uint32_t *__restrict__ rank, BswRec *recs) {
+__global__ __launch_bounds__(256) void bsw_scatter(BswIO io, int max_sc, int seeded, int64_t lo, int64_t hi, const int32_t *__restrict__ seed,
+                                                   const uint32_t *__restrict__ start, const uint32_t *__restrict__ rank, BswRec *recs) {
     int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < hi; i += stride) {
         int ql = io.len2[i], tl = io.len1[i];
-        if (rank[i] == ~0u) continue;      // failed bsw_hist's validation (the host returns GAB_EINVAL after this pass)
+        if (rank[i] == ~0u) continue;      // failed bsw_seed's validation (the host returns GAB_EINVAL after this pass)
         BswRec r;
-        r.ref_off = io.ref_off[i]; r.qry_off = io.qry_off[i]; r.len1 = tl; r.len2 = ql; r.h0 = io.h0[i]; r.id = (uint32_t)i;
-        recs[start[bsw_key(ql, tl, r.h0)] + rank[i]] = r;
+        r.ref_off = io.ref_off[i]; r.qry_off = io.qry_off[i]; r.lens = tl | ql << 16; r.h0 = io.h0[i]; r.L = seed[i]; r.id = (uint32_t)i;
+        recs[start[bsw_key(ql, tl, r.h0, r.L, max_sc, seeded)] + rank[i]] = r;
     }
 }
 
 // ---- pass 4: the DP ------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
-    uint32_t w;
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
 
 // WIDE = false: H and E packed as (E << 16) | H in one dword per column (both < 2^15).
 // WIDE = true : H at lds[j*64+lane], E at lds[(qcap+1+j)*64+lane].
@@ -312,7 +459,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
     const int lane = threadIdx.x;
     const int64_t k = kbeg + (int64_t)(gridDim.x - 1 - blockIdx.x) * 64 + lane;   // heaviest waves (largest key) first
     const bool valid = k < kend;
-    BswRec rec; rec.ref_off = rec.qry_off = 0; rec.len1 = rec.len2 = rec.h0 = 0; rec.id = 0u;
+    BswRec rec; rec.ref_off = rec.qry_off = 0; rec.lens = rec.h0 = rec.L = 0; rec.id = 0u;
     if (valid) rec = recs[k];
     const uint32_t id = rec.id;
 
@@ -323,7 +470,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
 
     unsigned long long cells = 0;
     if (valid) {
-        const int qlen = rec.len2, tlen = rec.len1, h0 = rec.h0;
+        const int qlen = rec.lens >> 16, tlen = rec.lens & 0xffff, h0 = rec.h0;
         const uint8_t *q = io.qry + rec.qry_off;
         const uint8_t *t = io.ref + rec.ref_off;
         const int oe_del = c.o_del + c.e_del, oe_ins = c.o_ins + c.e_ins;
@@ -362,6 +509,20 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
         int beg = 0, end = qlen;
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
         bool dropped = false, abandon = false;              // a prune has dropped a live cell; one of the three guards fired
+        // seeded prune (header comment): the prunes and two of the guards test against thr = max(best, Lm1); 0 leaves thr == best
+        const bool seed_ok = prune && min(qlen, 2 * w + 1) > 9;      // (a band that can hold more than nine cells)
+        const int Lm1 = seed_ok && (c.seed & 1) ? rec.L - 1 : 0;
+        if (seed_ok && (c.seed & 2)) {                      // the prune of row -1: cell 0 stays
+            const int thr = max(best, Lm1);
+            int jl = qlen;
+            for (; jl >= 1; jl--) {
+                const int m = (int)H[jl * 64];              // (E = 0)
+                if (m && m + c.max_sc * min(tlen, qlen - jl) > thr) break;
+                H[jl * 64] = 0u;
+            }
+            end = jl + 2 < qlen ? jl + 2 : qlen;
+            dropped = end < min(qlen, w + 1);               // the reference sweeps row 0 up to there
+        }
         uint32_t tw = load_u32_unaligned(t);       // 4 reference bases, refreshed every 4 rows
         for (int i = 0; i < tlen; i++) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -420,7 +581,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
             if (rowmax == 0) {                              // zero-row guard of the right prune (header comment, step 10)
                 if (dropped && beg == 0) {
                     const int hb = h0 - c.o_del - e_del * (i + 1);              // this row's left edge: stored cell 0
-                    abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > best;
+                    abandon = hb > 0 && hb + c.max_sc * min(tlen - 1 - i, qlen) > max(best, Lm1);
                 }
                 break;
             }
@@ -440,9 +601,10 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
                 try_exit = score_only && rowmax + c.max_sc * min(rows_left, qlen - 1 - rowmax_j) <= best;
             }
+            const int thr = max(best, Lm1);                 // (best is this row's already)
             // right-edge guard of the left prune (header comment, step 5)
             if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
-                hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > best) { abandon = true; break; }
+                hleft - e_ins + c.max_sc * min(rows_left, qlen - end - 1) > thr) { abandon = true; break; }
             // trim all-zero cells from both band edges (bandedSWA.cpp:234-237)
             if (WIDE) {
                 for (j = beg; j < end && H[j * 64] == 0u && E[j * 64] == 0u; j++) {}
@@ -459,13 +621,13 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 bool go = true;
                 if (beg == 0) {
                     const int hb = h0 - c.o_del - e_del * (i + 2);
-                    go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= best;
+                    go = hb <= 0 || hb + c.max_sc * min(rows_left, qlen) <= thr;
                 }
                 if (go) {
                     const int lcap = min(end, beg0 + 4);
                     for (j = beg; j < lcap; j++) {
                         const int m = WIDE ? max((int)H[j * 64], (int)E[j * 64]) : max((int)(H[j * 64] & 0xffffu), (int)(H[j * 64] >> 16));
-                        if (m && m + c.max_sc * min(rows_left, qlen - j) > best) break;
+                        if (m && m + c.max_sc * min(rows_left, qlen - j) > thr) break;
                     }
                     dropped = dropped || j > beg;
                     beg = j;
@@ -475,7 +637,7 @@ __global__ __launch_bounds__(64) void bsw_dp(BswIO io, BswConst c, const BswRec 
                 const int from = jl;
                 for (; jl >= beg && jl > end0 - 4; jl--) {
                     const int m = WIDE ? max((int)H[jl * 64], (int)E[jl * 64]) : max((int)(H[jl * 64] & 0xffffu), (int)(H[jl * 64] >> 16));
-                    if (m && m + c.max_sc * min(rows_left, qlen - jl) > best) break;
+                    if (m && m + c.max_sc * min(rows_left, qlen - jl) > thr) break;
                     H[jl * 64] = 0u;
                     if (WIDE) E[jl * 64] = 0u;
                 }
@@ -627,7 +789,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
     const int lane = threadIdx.x;
     const int64_t k = kbeg + (int64_t)(gridDim.x - 1 - blockIdx.x) * 64 + lane;   // heaviest waves (largest key) first
     const bool valid = k < kend;
-    BswRec rec; rec.ref_off = rec.qry_off = 0; rec.len1 = rec.len2 = rec.h0 = 0; rec.id = 0u;
+    BswRec rec; rec.ref_off = rec.qry_off = 0; rec.lens = rec.h0 = rec.L = 0; rec.id = 0u;
     if (valid) rec = recs[k];
     const uint32_t id = rec.id;
     const int ncell_dw = (qcap + 2) / 2;
@@ -640,7 +802,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
 
     unsigned long long cells = 0;
     if (valid) {
-        const int qlen = rec.len2, tlen = rec.len1, h0 = rec.h0;
+        const int qlen = rec.lens >> 16, tlen = rec.lens & 0xffff, h0 = rec.h0;
         const uint8_t *q = io.qry + rec.qry_off;
         const uint8_t *t = io.ref + rec.ref_off;
         const int oe_del = c.o_del + c.e_del, oe_ins = c.o_ins + c.e_ins;
@@ -678,20 +840,37 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         // row -1 (bandedSWA.cpp:159-161); E = 0.  Cell 0 is h0 and cell j >= 1 is max(h0 - oe_ins - (j - 1) * e_ins, 0): two cells
         // per dword store.  Pair word qlen / 2 ends on cell qlen + 1 when qlen is even -- inside the cell rows (qcap is even), and a
         // cell the sweep never reads as part of a band.
+        // Seeded prune (header comment): the prunes and two of the guards test against thr = max(best, Lm1), 0 leaves thr == best;
+        // and the prune of row -1: cell j >= 1 is stored only while it is live, value + max_sc * min(tlen, qlen - j) > thr0 -- both
+        // terms fall from left to right, so the live cells are a prefix and jm1 ends on the last of them.  With that prune off
+        // thr0 = -1 keeps every positive cell and `end` stays qlen.
+        const bool seed_ok = SO && prune && min(qlen, 2 * w + 1) > 9;      // (a band that can hold more than nine cells)
+        const int Lm1 = seed_ok && (c.seed & 1) ? rec.L - 1 : 0;
+        const bool row_prune = seed_ok && (c.seed & 2);
+        int jm1 = 0;
         {
+            const int thr0 = row_prune ? max(h0, Lm1) : -1;
             int v = h0 - oe_ins;                            // cell 2p - 1
-            CW[0] = (uint32_t)h0 | (uint32_t)max(v, 0) << 16;
+            int cl = qlen - 1;                              // columns left of cell 2p - 1
+            const bool l1 = v > 0 && v + mul24(c.max_sc, min(tlen, cl)) > thr0;
+            jm1 = l1 ? 1 : 0;
+            CW[0] = (uint32_t)h0 | (uint32_t)(l1 ? v : 0) << 16;
             for (int p = 1; p <= (qlen >> 1); p++) {
                 const int lo = v - e_ins;
                 v = lo - e_ins;
-                CW[p * 64] = (uint32_t)max(lo, 0) | (uint32_t)max(v, 0) << 16;
+                cl -= 2;
+                const bool la = lo > 0 && lo + mul24(c.max_sc, min(tlen, cl + 1)) > thr0;
+                const bool lb = v > 0 && v + mul24(c.max_sc, min(tlen, cl)) > thr0;
+                jm1 = la ? 2 * p : jm1; jm1 = lb ? 2 * p + 1 : jm1;
+                CW[p * 64] = (uint32_t)(la ? lo : 0) | (uint32_t)(lb ? v : 0) << 16;
             }
         }
         best = h0; best_i = -1; best_j = -1; g_i = -1; gscore = -1; max_off = 0;
-        int beg = 0, end = qlen;
+        int beg = 0, end = row_prune && jm1 + 2 < qlen ? jm1 + 2 : qlen;
         int hrow = h0 - c.o_del - e_del;                    // row i's left edge h0 - o_del - e_del * (i + 1), carried from row to row
         int stale_pot = 0;                                  // bound on what the cells the band clamp cut can still lead to
-        bool dropped = false, abandon = false;              // a prune has dropped a live cell; one of the three guards fired
+        bool dropped = row_prune && end < min(qlen, w + 1); // a prune has dropped a live cell (row -1: the reference sweeps row 0 up to there)
+        bool abandon = false;                               // one of the three guards fired
         uint32_t tw = load_u32_unaligned(t);
         for (int i = 0; i < tlen; i++, hrow -= e_del) {
             const int tc = (tw >> ((i & 3) * 8)) & 0xff;
@@ -820,7 +999,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 if constexpr (SO) {
                     if (dropped && beg == 0) {
                         // (hrow: this row's left edge, stored cell 0)
-                        abandon = hrow > 0 && hrow + mul24(c.max_sc, min(tlen - 1 - i, qlen)) > best;
+                        abandon = hrow > 0 && hrow + mul24(c.max_sc, min(tlen - 1 - i, qlen)) > max(best, Lm1);
                     }
                 }
                 break;
@@ -876,10 +1055,11 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     max_off = off > max_off ? off : max_off;
                 }
             }
+            const int thr = max(best, Lm1);                 // (best is this row's already; only the score-only form reads it)
             if constexpr (SO) {
                 // right-edge guard of the left prune (header comment, step 5); a row that the z-drop test ends does not reach it
                 const bool guard = !stop && dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
-                                   hleft - e_ins + mul24(c.max_sc, min(rows_left, qlen - end - 1)) > best;
+                                   hleft - e_ins + mul24(c.max_sc, min(rows_left, qlen - end - 1)) > thr;
                 abandon = abandon || guard;
                 stop = stop || guard;
             }
@@ -900,7 +1080,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 int lp = lz, tp = tz;                                      // cells either edge moves over, of its window
                 if constexpr (SO) {
                     // The windows judged in packed 16-bit halves: m = max(H, E) <= 255 and max_sc * columns left <= 255.  A half is
-                    // non-zero where its cell is live and its potential exceeds the lane's operand -- `best` where the edge
+                    // non-zero where its cell is live and its potential exceeds the lane's operand -- thr where the edge
                     // may be pruned; 0 where it may only be trimmed (prune off; or the left edge at column 0 in front of a live
                     // next-row edge, or at qlen), which leaves exactly the non-zero cells: lp == lz, tp == tz there.  A row
                     // whose zero trim runs past a window (lz == 4, tz == 4) has all four halves zero under either operand
@@ -908,9 +1088,9 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     const int rq = min(rows_left, qlen);
                     const int hb = hrow - e_del;                           // the next row's left edge
                     edge_pot = hb > 0 ? hb + mul24(c.max_sc, rq) : 0;
-                    const bool go = prune && base < qlen && (base != 0 || edge_pot <= best);
+                    const bool go = prune && base < qlen && (base != 0 || edge_pot <= thr);
                     const uint32_t r2 = as_u32(pk_splat(rq)), m2 = as_u32(pk_splat(c.max_sc));
-                    const uint32_t bestL = (uint32_t)(go ? best : 0) * 0x00010001u, bestR = (uint32_t)(prune ? best : 0) * 0x00010001u;
+                    const uint32_t bestL = (uint32_t)(go ? thr : 0) * 0x00010001u, bestR = (uint32_t)(prune ? thr : 0) * 0x00010001u;
                     const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
                     const uint32_t cr01 = ((uint32_t)(qlen - end0 + 3) & 0xffffu) | (uint32_t)(qlen - end0 + 2) << 16;
 #define BSW_STAY(W, CL, B2, OUT)                                                                                   \
@@ -1069,6 +1249,7 @@ extern "C" int gab_bsw_create(const gab_bsw_params *p, int device, gab_bsw **out
     int mx = 0;
     for (int k = 0; k < 25; k++) mx = p->mat[k] > mx ? p->mat[k] : mx;
     c.max_sc = mx;
+    c.seed = 1 | (mx <= p->e_ins ? 2 : 0);
     for (int t = 0; t < 5; t++) {
         uint32_t lo = 0;
         for (int q = 0; q < 4; q++) lo |= (uint32_t)(uint8_t)(p->mat[t * 5 + q] + 128) << (8 * q);
@@ -1122,10 +1303,11 @@ extern "C" void gab_bsw_destroy(gab_bsw *h) {
 }
 
 // The sort workspace: per slice a block of hist | start | qstart | sums | stats (slice 1's sort writes its own while slice 0's DP
-// adds to slice 0's cells), then the records of all n pairs in bucket order, slice after slice, then the n ranks.
+// adds to slice 0's cells), then the records of all n pairs in bucket order, slice after slice, then the n ranks and the n
+// lower bounds of bsw_seed.
 struct BswLayout {
     size_t o_start, o_qstart, o_sums, o_stats, blk;   // inside a slice's block (hist at 0); blk = the block's size
-    size_t o_recs, o_rank, total;
+    size_t o_recs, o_rank, o_seed, total;
     explicit BswLayout(size_t n) {
         o_start = sizeof(uint32_t) * kNumKeys;
         o_qstart = o_start + sizeof(uint32_t) * (kNumKeys + 1);
@@ -1134,7 +1316,8 @@ struct BswLayout {
         blk = (o_stats + sizeof(BswStats) + 255) & ~(size_t)255;
         o_recs = blk * kSlices;
         o_rank = o_recs + ((sizeof(BswRec) * n + 255) & ~(size_t)255);
-        total = o_rank + sizeof(uint32_t) * n;
+        o_seed = o_rank + ((sizeof(uint32_t) * n + 255) & ~(size_t)255);
+        total = o_seed + sizeof(int32_t) * n;
     }
 };
 
@@ -1167,7 +1350,7 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
 
     // A batch of at least slice_min pairs is cut into slice 0, pairs 0 .. slice0 - 1, and slice 1, the rest.  Each slice is
     // sorted by itself into its own part of the records and gets its own class launches; see the launch comment below.
-    const int64_t slice0 = h->tun.bsw_slice[0] > 0 ? h->tun.bsw_slice[0] : kSlice0;
+    const int64_t slice0 = h->tun.bsw_slice[0] > 0 ? h->tun.bsw_slice[0] : result_out ? kSlice0Full : kSlice0;
     const int64_t slice_min = std::max<int64_t>(h->tun.bsw_slice[1] > 0 ? h->tun.bsw_slice[1] : kSliceMin, slice0 + 1);
     const int nsl = n >= slice_min ? kSlices : 1;
     const int64_t cut[kSlices + 1] = {0, nsl > 1 ? slice0 : n, n};
@@ -1183,6 +1366,7 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
     char *base = h->ws.as<char>();
     BswRec *d_recs = (BswRec *)(base + L.o_recs);             // the pairs' records in bucket order, slice after slice
     uint32_t *d_rank = (uint32_t *)(base + L.o_rank);
+    int32_t *d_seed = (int32_t *)(base + L.o_seed);
     auto d_stats = [&](int k) { return (BswStats *)(base + L.blk * k + L.o_stats); };
 
     BswIO io{ref, ref_off, qry, qry_off, len1, len2, h0, ref_bytes, qry_bytes, n, ref_lo, qry_lo, ref_hi, qry_hi};
@@ -1198,10 +1382,17 @@ static int bsw_run_device_impl(gab_bsw *h, const uint8_t *ref, int64_t ref_bytes
         if (e != hipSuccess) return e;
         const int gmax = k > 0 ? kSortGridBeside : 1024;
         const int grid = (int)(gab_ceil_div(hi - lo, 256) < gmax ? gab_ceil_div(hi - lo, 256) : gmax);   // (one same-address atomicMax per wave)
-        hipLaunchKernelGGL(bsw_hist, dim3(grid), dim3(256), 0, q, io, lo, hi, d_hist, d_rank, d_stats(k));
+        const int sgrid = (int)(gab_ceil_div(hi - lo, 256) < kSeedGridBeside ? gab_ceil_div(hi - lo, 256) : kSeedGridBeside);
+        const int seeded = result_out == nullptr;      // score-only: L and the deficit key; six-field: validation and the key it had
+        if (k > 0) {      // beside slice 0's DP kernels: the scan on a grid of its own
+            hipLaunchKernelGGL(bsw_seed, dim3(sgrid), dim3(256), 0, q, io, h->cst, seeded, lo, hi, d_seed);
+            hipLaunchKernelGGL(bsw_hist<false>, dim3(grid), dim3(256), 0, q, io, h->cst, seeded, lo, hi, d_seed, d_hist, d_rank, d_stats(k));
+        } else {
+            hipLaunchKernelGGL(bsw_hist<true>, dim3(grid), dim3(256), 0, q, io, h->cst, seeded, lo, hi, d_seed, d_hist, d_rank, d_stats(k));
+        }
         hipLaunchKernelGGL(bsw_scan_a, dim3(kScanBlocks), dim3(1024), 0, q, d_hist, d_start, d_sums);
         hipLaunchKernelGGL(bsw_scan_b, dim3(kScanBlocks), dim3(1024), 0, q, d_start, (const uint32_t *)d_sums, d_qstart);
-        hipLaunchKernelGGL(bsw_scatter, dim3(grid), dim3(256), 0, q, io, lo, hi, d_start, d_rank, d_recs + lo);
+        hipLaunchKernelGGL(bsw_scatter, dim3(grid), dim3(256), 0, q, io, h->cst.max_sc, seeded, lo, hi, (const int32_t *)d_seed, d_start, d_rank, d_recs + lo);
         e = hipMemcpyAsync(h->h_qstart[k], d_qstart, sizeof(uint32_t) * (kQBuckets + 1), hipMemcpyDeviceToHost, q);
         if (e == hipSuccess) e = hipMemcpyAsync(h->h_stats[k], d_stats(k), sizeof(BswStats), hipMemcpyDeviceToHost, q);
         return e;

@@ -103,7 +103,8 @@ def bsw_from_arrays(refs, qrys, h0s):
     return BswBatch(ref, ref_off, qry, qry_off, len1, len2, np.array(h0s, np.int32))
 
 
-BSW_PRUNE_RULES = {"default": 1, "wrong_left": 2, "parent": 3, "wrong_right": 4, "left_cap_only": 5, "right_only": 6}
+BSW_PRUNE_RULES = {"default": 7, "capped": 1, "wrong_left": 2, "parent": 3, "wrong_right": 4, "left_cap_only": 5, "right_only": 6,
+                   "wrong_seed": 8, "seed_thr_only": 9, "seed_row_only": 10, "seed_ungated": 11}
 
 
 def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, wrong_potential=False, rule="default"):
@@ -112,7 +113,10 @@ def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, w
     (include/gab.h).  early_exit=False: the reference's full sweep.  prune=False: the exit alone.  restarts=True appends a fifth
     array: 1 where the pair abandoned its pruned pass for the z-drop guard and ran again without the prune.  wrong_potential=True
     is the tests' negative control (the left prune's potential counts two columns too few).  rule picks among the model's prune
-    rules: "default" is what the kernels do (left prune capped at four cells per row, right prune); "parent" the rule before the
+    rules: "default" is what the kernels do (left prune capped at four cells per row, right prune, both seeded with the ungapped
+    lower bound L of the score where the parameters pass the rule's gates); "capped" the rule before the seed; "seed_thr_only" /
+    "seed_row_only" the seed's two parts (the threshold max(best, L - 1); the prune of row -1), "seed_ungated" both at every parameter
+    set; "wrong_seed" the seed's negative control (threshold L); "parent" the rule before the
     right prune (left uncapped, no right prune); "left_cap_only", "right_only" its two halves; "wrong_right" the right side's
     negative control (its potential counts two columns too few)"""
     n = batch.n
@@ -128,6 +132,15 @@ def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, w
 
 BSW_TRACE_FLAGS = {"lz4": 1, "tz4": 2, "left_drop": 4, "right_drop": 8, "bound_pass": 16, "zdrop_guard": 32, "right_edge_guard": 64,
                    "zero_row_guard": 128}
+
+
+def bsw_seed_bound(batch, params):
+    """the seeded prune's lower bound L of every pair's score: h0 plus the best prefix of the ungapped extension along the main
+    diagonal, held down by the z-drop (tools/gen/bsw_exit_model.c, seed_bound) -> int32 [n]"""
+    L = np.zeros(batch.n, np.int32)
+    lib().gab_bsw_seed_bound(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
+                             _p(batch.len2), _p(batch.h0), C.c_int64(batch.n), _p(L))
+    return L
 
 
 def bsw_exit_trace(batch, params, early_exit=True, prune=True, rule="default"):

@@ -52,10 +52,25 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
  * hb + max_sc * min(R, qlen) > best abandons the pass too (the reference's row may hold dead cells that keep it going until that
  * edge raises the score).
  *
- * `prune` selects the rule:  0 off;  1 what the kernels do (left prune capped, right prune);  3 the rule before the right prune
- * (left prune uncapped, no right prune);  5 left prune capped, no right prune;  6 left prune uncapped, right prune.
- * TEST-ONLY wrong rules, the negative controls of tests/test_bsw_left_prune.py and tests/test_bsw_right_prune.py:
- * 2 is rule 1 with the left potential's columns short by two, 4 is rule 1 with the right potential's columns short by two. */
+ *
+ * Seeded prune (same scope, same pairs; bsw.hip's header has the proof).  The ungapped extension along the main diagonal is a path
+ * of the DP, so a lower bound L of the pair's FINAL score is known before row 0 (seed_bound below), and a cell whose potential is
+ * below L cannot lead to the final score whatever `best` is at its row.  With thr = max(best, L - 1):
+ *   thr replaces `best` in the left prune's cell test and its column-0 edge test, in the right prune's cell test, in the right-edge
+ *   guard and in the zero-row guard; the z-drop guard, `best` itself and the exit's bound <= best are unchanged;
+ *   before row 0 the cells of row -1 are dropped from the right under the right prune's test (R = tlen, best = h0, no cap: row -1
+ *   and its potential both fall from left to right); an `end` below min(qlen, w + 1), what the reference sweeps row 0 with, counts
+ *   as a drop, because row 0's F runs on right of the last live cell of row -1 and only the right-edge guard judges it.
+ * Economy gates, on the parameters (seed_gates below) and per pair on the band (min(qlen, 2 w + 1) > 9, at model_one): thr == best
+ * and row -1 stays whole where a gate is shut.
+ *
+ * `prune` selects the rule:  0 off;  7 what the kernels do (left prune capped, right prune, seeded);  1 the rule before the seed
+ * (left prune capped, right prune);  3 the rule before the right prune (left prune uncapped, no right prune);  5 left prune capped,
+ * no right prune;  6 left prune uncapped, right prune;  9 rule 7 without the prune of row -1;  10 rule 7 with thr == best (the prune
+ * of row -1 alone);  11 rule 7 with its gates open at every parameter set (what the gates are measured against).
+ * TEST-ONLY wrong rules, the negative controls of tests/test_bsw_left_prune.py, tests/test_bsw_right_prune.py and
+ * tests/test_bsw_seeded_prune.py: 2 is rule 1 with the left potential's columns short by two, 4 is rule 1 with the right potential's
+ * columns short by two, 8 is rule 7 with thr = max(best, L): a cell of the diagonal path can have potential exactly L. */
 /* Row trace (gab_bsw_exit_trace below; NULL for the other entry points): per swept row of every pass, the abandoned one included,
  * the [beg, end) the row was swept with and which of the kernels' per-row paths the row takes. */
 enum { TR_LZ4 = 1,        /* the left zero trim ran past its four-cell window */
@@ -68,6 +83,33 @@ enum { TR_LZ4 = 1,        /* the left zero trim ran past its four-cell window */
        TR_ZROW = 128 };   /*                             zero-row guard */
 typedef struct { int16_t *beg, *end; uint8_t *flags, *drops; int64_t cap, n; } row_trace;   /* drops: live and zero cells the left prune
                                                                                              * moved over beyond the zero trim | the right one's << 4 */
+
+/* L: the ungapped extension from d = h0 along the main diagonal, k = 0 .. min(qlen, tlen) - 1, codes above 4 as N, stopped at the
+ * first d <= 0.  While every d so far is positive, cell (k, k) holds at least d_{k+1} (M of a non-zero diagonal), lies inside the
+ * reference's band (|i - j| = 0 <= w, and the zero trims pass only zero cells) and its row is not zero.  So the reference's score is
+ * at least d_{k+1} if it sweeps row k, and if it z-drops in an earlier row i its score exceeds rowmax_i + zdrop >= d_{i+1} + zdrop. */
+static int seed_bound(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0) {
+    int d = h0, L = h0, mn = h0;
+    const int n = qlen < tlen ? qlen : tlen;
+    for (int k = 0; k < n && d > 0; k++) {
+        d += p->mat[5 * (target[k] > 4 ? 4 : target[k]) + (query[k] > 4 ? 4 : query[k])];
+        if (d <= 0) break;
+        int v = d;
+        if (p->zdrop > 0 && d - mn > p->zdrop) v = p->zdrop + 1 + mn;
+        if (v > L) L = v;
+        if (d < mn) mn = d;
+    }
+    return L;
+}
+
+/* Economy gates of the seeded prune, on the parameters alone (bit 0: thr = max(best, L - 1); bit 1: the prune of row -1).  The
+ * threshold is open wherever the prunes are: it measured no more cells than the rule before it at any parameter set.  The prune of
+ * row -1 is open only with max_sc <= e_ins.  Where a match is worth more than an inserted base costs, the right-edge guard (the F
+ * that leaves the narrowed band) sends 40 - 70 % of the read-like pairs through a second pass and the cell count rises by up to a
+ * third; with max_sc <= e_ins that guard did not fire once for the row -1 prune (profiles/bsw_seeded_prune.md). */
+static int seed_gates(const gab_bsw_model_params *p, int max_sc) {
+    return 1 | (max_sc <= p->e_ins ? 2 : 0);
+}
 
 static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0,
                       int early_exit, int prune, int32_t *Hd, int32_t *Ev, int32_t *score, int32_t *rows, int64_t *cells,
@@ -89,6 +131,16 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                          (p->zdrop == 0 || p->zdrop >= 8 * max_sc);
     const int short_by = prune == 2 ? 2 : 0, short_r = prune == 4 ? 2 : 0;
     const int left_cap = !(prune == 3 || prune == 6), right_prune = prune != 3 && prune != 5;
+    const int seeded = prune >= 7 && prune <= 11;
+    /* per pair: a band that can hold more than nine cells, min(qlen, 2 w + 1) > 9.  A narrower one is swept in at most two loop trips
+     * of the kernels and the seed has next to nothing to remove there (with w <= 8 restriction (a) already fails for every h0 above
+     * oe_ins + 9 e_ins); the narrow bands are also where the kernels' edge-cell paths live, whose tests read their cases off the
+     * default rule's trace */
+    const int seed_ok = seeded && (qlen < 2 * w + 1 ? qlen : 2 * w + 1) > 9;
+    const int gates = !seed_ok ? 0 : prune == 11 ? 3 : seed_gates(p, max_sc) & (prune == 9 ? 1 : prune == 10 ? 2 : 3);
+    /* thr = max(best, Lm1): Lm1 = 0 leaves thr == best (best >= h0 >= 0) */
+    const int Lm1 = prune_ok && (gates & 1) ? seed_bound(p, qlen, query, tlen, target, h0) - (prune == 8 ? 0 : 1) : 0;
+    const int row_prune = prune_ok && (gates & 2);
 
     int best = h0, i = 0, redo = 0;
     for (int pass = 0; pass < 2; pass++) {
@@ -103,6 +155,19 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
         int best_i = -1, best_j = -1, stale_pot = 0;
         int beg = 0, end = qlen;
         best = h0;
+        if (do_prune && row_prune) {
+            /* the prune of row -1: stored cell j is the diagonal of cell (0, j), tlen rows and qlen - j columns are left.  Cell 0
+             * stays (its potential is that of the whole pair) */
+            const int thr = best > Lm1 ? best : Lm1;
+            int jl = qlen;
+            for (; jl >= 1; jl--) {
+                int cl = qlen - jl;
+                if (Hd[jl] && Hd[jl] + max_sc * (tlen < cl ? tlen : cl) > thr) break;
+                Hd[jl] = 0;
+            }
+            end = jl + 2 < qlen ? jl + 2 : qlen;
+            if (end < (qlen < w + 1 ? qlen : w + 1)) dropped = 1;      /* the reference sweeps row 0 up to there */
+        }
         for (i = 0; i < tlen; i++) {
             const int8_t *srow = p->mat + 5 * (target[i] > 4 ? 4 : target[i]);
             const int R = tlen - 1 - i;
@@ -148,7 +213,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                  * the reference may go on from that edge */
                 if (dropped && beg == 0) {
                     int hb = h0 - p->o_del - e_del * (i + 1);
-                    if (hb > 0 && hb + max_sc * (R < qlen ? R : qlen) > best) abandon = 1;
+                    if (hb > 0 && hb + max_sc * (R < qlen ? R : qlen) > (best > Lm1 ? best : Lm1)) abandon = 1;
                 }
                 if (trf && abandon) *trf |= TR_ZROW;
                 i++; break;
@@ -169,11 +234,12 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 int cl = qlen - 1 - rowmax_j;
                 try_exit = early_exit && rowmax + max_sc * (R < cl ? R : cl) <= best;
             }
+            const int thr = best > Lm1 ? best : Lm1;      /* (best is this row's already) */
             /* right-edge guard: the F that leaves the band's last column is at most hleft - e_ins; the reference, whose band may
              * reach further right than a pruned pair's, carries it on */
             if (dropped && end < qlen && end != i + w + 1 && hleft > e_ins) {
                 int cl = qlen - end - 1;
-                if (hleft - e_ins + max_sc * (R < cl ? R : cl) > best) { abandon = 1; if (trf) *trf |= TR_RGUARD; i++; break; }
+                if (hleft - e_ins + max_sc * (R < cl ? R : cl) > thr) { abandon = 1; if (trf) *trf |= TR_RGUARD; i++; break; }
             }
             for (j = beg; j < end && Hd[j] == 0 && Ev[j] == 0; j++) {}
             beg = j;
@@ -185,14 +251,14 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 int go = 1;
                 if (beg == 0) {                    /* (cell 0 is live here: the zero trim stopped at it) */
                     int hb = h0 - p->o_del - e_del * (i + 2);
-                    go = hb <= 0 || hb + max_sc * (R < qlen ? R : qlen) <= best;
+                    go = hb <= 0 || hb + max_sc * (R < qlen ? R : qlen) <= thr;
                 }
                 if (go) {
                     const int from = beg;
                     for (; beg < end && !(left_cap && beg >= beg0 + 4); beg++) {
                         int m = Hd[beg] > Ev[beg] ? Hd[beg] : Ev[beg];
                         int cl = qlen - beg - short_by;
-                        if (m && m + max_sc * (R < cl ? R : cl) > best) break;
+                        if (m && m + max_sc * (R < cl ? R : cl) > thr) break;
                     }
                     if (beg > from) dropped = 1;   /* (cell `from` is live) */
                     if (trf && beg > from) { *trf |= TR_LDROP; tr->drops[tr->n - 1] |= (uint8_t)(beg - from > 15 ? 15 : beg - from); }
@@ -203,7 +269,7 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                 for (; jl >= beg && jl > end0 - 4; jl--) {
                     int m = Hd[jl] > Ev[jl] ? Hd[jl] : Ev[jl];
                     int cl = qlen - jl - short_r;
-                    if (m && m + max_sc * (R < cl ? R : cl) > best) break;
+                    if (m && m + max_sc * (R < cl ? R : cl) > thr) break;
                     Hd[jl] = 0; Ev[jl] = 0;
                 }
                 if (jl < from) { dropped = 1; end = jl + 2 < qlen ? jl + 2 : qlen; }
@@ -286,4 +352,11 @@ void gab_bsw_exit_trace(const gab_bsw_model_params *p, const uint8_t *ref, const
         }
         free(buf);
     }
+}
+
+/* the seeded prune's lower bound L of every pair's score (seed_bound above), whatever the gates say */
+void gab_bsw_seed_bound(const gab_bsw_model_params *p, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry,
+                        const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n, int32_t *L) {
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < n; k++) L[k] = seed_bound(p, len2[k], qry + qry_off[k], len1[k], ref + ref_off[k], h0[k]);
 }
