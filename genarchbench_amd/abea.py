@@ -3,7 +3,9 @@
 and of the two steps before it, event detection and the scaling estimate (gab_abea_events, gab_abea_scalings: event_single,
 f5c.c:1241-1264), so that raw samples go in and aligned pairs come out (EventAligner.signal_to_pairs); and of the block after it,
 postalign, recalibrate_model and the read checks (gab_abea_calibrate: f5c.c:1438-1501), so that calibrated reads with their
-base-to-event map come out (EventAligner.signal_to_calibrated)."""
+base-to-event map come out (EventAligner.signal_to_calibrated); and of the step after that, realign_read (gab_abea_realign:
+f5c.c:1508-1515), which turns a calibrated read, its reference substring and its CIGAR into the event alignment records of
+eventalign (EventAligner.realign, eventalign_rows)."""
 import ctypes as C
 
 import numpy as np
@@ -24,7 +26,11 @@ RANGE = np.dtype([("start", np.int32), ("stop", np.int32)])      # gab_abea_rang
 CALIB = np.dtype([("n_alignment", np.int32), ("n_m_state", np.int32), ("read_stat_flag", np.uint32), ("recalibrated", np.int32),
                   ("scale", np.float32), ("shift", np.float32), ("var", np.float32), ("log_var", np.float32),
                   ("events_per_base", np.float64)])                  # gab_abea_calib, 40 bytes
-assert PAIR.itemsize == 8 and READ.itemsize == 40 and RANGE.itemsize == 8 and CALIB.itemsize == 40
+REALIGN_SKIPPED, REALIGN_NO_PAIRS, REALIGN_NO_EVENT, REALIGN_STRAND = 1, 2, 4, 8      # gab_abea_realign_read.flags
+EALN = np.dtype([("ref_position", np.int32), ("event_idx", np.int32), ("hmm_state", np.uint8), ("pad", np.uint8, 3)])      # gab_abea_ealn, 12 bytes
+REALIGN = np.dtype([("n_entries", np.int32), ("hmm_segments", np.int32), ("max_rows", np.int32), ("flags", np.uint32), ("cells", np.int64)])      # gab_abea_realign_read
+CIGAR_OPS = "MIDNSHP=X"
+assert PAIR.itemsize == 8 and READ.itemsize == 40 and RANGE.itemsize == 8 and CALIB.itemsize == 40 and EALN.itemsize == 12 and REALIGN.itemsize == 24
 
 
 def _p(a):
@@ -68,6 +74,40 @@ def pack_signals(signals):
 def pair_room(seq_len, n_events):
     """pairs of room a read needs at its pair_off: n_events + n_kmers"""
     return np.asarray(n_events, np.int64) + np.asarray(seq_len, np.int64) - K + 1
+
+
+def realign_shape():
+    """rows of a wavefront's backpointer trace: GAB_ABEA_REALIGN_ROWS as the library was built"""
+    rows = C.c_int32(0)
+    check(lib().gab_abea_realign_shape(C.byref(rows)))
+    return rows.value
+
+
+def realign_room(n_events, cigar, cigar_off, n_cigar):
+    """entries of room a read needs at its out_off: n_events * (1 + its number of N operations)"""
+    cigar = np.asarray(cigar, np.uint32)
+    skips = np.array([int(((cigar[o:o + k] & 15) == 3).sum()) for o, k in zip(cigar_off, n_cigar)], np.int64)
+    return np.asarray(n_events, np.int64) * (1 + skips)
+
+
+_FIRST_BASE = bytes.maketrans(b"ACGTMRWSYKVHDBN", b"ACGTAAACCGAAACA")
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def eventalign_rows(ref, ref_pos, is_rev, entries):
+    """one read's reference bases (as given to realign), position, strand and EALN entries -> per entry (position, reference_kmer,
+    event_index, model_kmer, hmm_state), the columns of events.tsv that the suite's check reads.  reference_kmer is the six
+    upper-cased, disambiguated reference bases at the position; model_kmer is NNNNNN for a 'B', otherwise that k-mer, reverse-
+    complemented for a reverse read (eventalign.c:1474, 1486-1503)."""
+    seq = bytes(ref).upper().translate(_FIRST_BASE)
+    rows = []
+    for e in entries:
+        at = int(e["ref_position"]) - int(ref_pos)
+        kmer = seq[at:at + K]
+        state = chr(int(e["hmm_state"]))
+        model = b"N" * K if state == "B" else kmer.translate(_COMPLEMENT)[::-1] if is_rev else kmer
+        rows.append((int(e["ref_position"]), kmer.decode(), int(e["event_idx"]), model.decode(), state))
+    return rows
 
 
 class EventAligner:
@@ -322,6 +362,88 @@ class EventAligner:
         self.calibrate_device(d_seq, d_so, d_sl, mean, event_off, n_events, scale, shift, pairs, d_po, n_pairs, rmap, d_mo, cal)
         return (rmap.cpu().numpy().reshape(-1).view(RANGE), map_off, cal.cpu().numpy().view(CALIB),
                 pairs.cpu().numpy().reshape(-1).view(PAIR), pair_off, res.cpu().numpy().view(READ), ne)
+
+    # ---- realign_read: the event alignment records (gab_abea_realign) ---------------------------------------------------------------
+    def realign(self, ref, ref_off, ref_len, ref_pos, is_rev, cigar, cigar_off, n_cigar, seq_len, events, event_off, n_events, rmap, map_off, calib,
+                region=(-1, -1), out_off=None, out=None):
+        """packed numpy arrays: the reference bases of every read (uint8), where they start and how many, the position of the first,
+        the strand, the CIGARs in BAM encoding (uint32) with offsets and counts, and seq_len, the events, the map (RANGE) and the
+        calibration records (CALIB) as calibrate() returned them -> (entries, out_off, records): entries an EALN array in which read
+        i's are entries[out_off[i] : out_off[i] + records[i]["n_entries"]], records a REALIGN array.  out: (entries, records) to
+        write into instead of new arrays."""
+        ref = np.ascontiguousarray(ref, np.uint8); cigar = np.ascontiguousarray(cigar, np.uint32); events = np.ascontiguousarray(events, np.float32)
+        ref_off = np.ascontiguousarray(ref_off, np.int64); cigar_off = np.ascontiguousarray(cigar_off, np.int64)
+        event_off = np.ascontiguousarray(event_off, np.int64); map_off = np.ascontiguousarray(map_off, np.int64)
+        ref_len = np.ascontiguousarray(ref_len, np.int32); ref_pos = np.ascontiguousarray(ref_pos, np.int32); n_cigar = np.ascontiguousarray(n_cigar, np.int32)
+        seq_len = np.ascontiguousarray(seq_len, np.int32); n_events = np.ascontiguousarray(n_events, np.int32)
+        is_rev = np.ascontiguousarray(is_rev, np.uint8)
+        rmap = np.ascontiguousarray(rmap); calib = np.ascontiguousarray(calib)
+        if rmap.dtype != RANGE or calib.dtype != CALIB:
+            raise ValueError("rmap is a RANGE array, calib a CALIB array")
+        n = seq_len.size
+        room = realign_room(np.maximum(n_events, 0), cigar, cigar_off, n_cigar) if n else np.zeros(0, np.int64)
+        if out_off is None:
+            out_off = np.zeros(n, np.int64)
+            if n > 1:
+                out_off[1:] = np.cumsum(room[:-1])
+        out_off = np.ascontiguousarray(out_off, np.int64)
+        if out is None:
+            out = (np.zeros(int((out_off + room).max()) if n else 0, EALN), np.zeros(n, REALIGN))
+        entries, res = out
+        if entries.dtype != EALN or res.dtype != REALIGN or res.size < n:
+            raise ValueError("out: an EALN array and a REALIGN array of one record per read")
+        check(lib().gab_abea_realign(self._h, _p(ref), _p(ref_off), _p(ref_len), _p(ref_pos), _p(is_rev), _p(cigar), _p(cigar_off), _p(n_cigar), _p(seq_len),
+                                     _p(events), _p(event_off), _p(n_events), _p(rmap), _p(map_off), _p(calib), C.c_int32(region[0]), C.c_int32(region[1]),
+                                     C.c_int64(n), _p(entries), _p(out_off), _p(res)))
+        return entries, out_off, res
+
+    def realign_reads(self, reads, region=(-1, -1)):
+        """list of (reference bases, ref_pos, is_rev, cigar as uint32 in BAM encoding, seq_len, event means, map as (n_kmers, 2) or
+        RANGE, calibration record) -> (entries, out_off, records)"""
+        def offsets(lens):
+            o = np.zeros(len(lens), np.int64)
+            if len(lens) > 1:
+                o[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+            return o
+        cat = lambda xs, dt: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs]) if xs else np.zeros(0, dt)
+        ref_len = np.array([len(r[0]) for r in reads], np.int32); n_cigar = np.array([len(r[3]) for r in reads], np.int32)
+        seq_len = np.array([r[4] for r in reads], np.int32); n_events = np.array([len(r[5]) for r in reads], np.int32)
+        maps = [np.ascontiguousarray(r[6] if np.asarray(r[6]).dtype == RANGE else np.asarray(r[6], np.int32)).view(np.int32).reshape(-1, 2) for r in reads]
+        calib = np.zeros(len(reads), CALIB)
+        for i, r in enumerate(reads):
+            for f in CALIB.names:
+                calib[i][f] = r[7][f] if not isinstance(r[7], np.void) or f in r[7].dtype.names else 0
+        return self.realign(cat([np.frombuffer(bytes(r[0]), np.uint8) for r in reads], np.uint8), offsets(ref_len), ref_len, np.array([r[1] for r in reads], np.int32),
+                            np.array([r[2] for r in reads], np.uint8), cat([r[3] for r in reads], np.uint32), offsets(n_cigar), n_cigar, seq_len,
+                            cat([r[5] for r in reads], np.float32), offsets(n_events), n_events, cat(maps, np.int32).view(RANGE),
+                            offsets(np.array([len(m) for m in maps], np.int64)), calib, region)
+
+    def realign_device(self, ref, ref_off, ref_len, ref_pos, is_rev, cigar, cigar_off, n_cigar, seq_len, events, event_off, n_events, rmap, map_off, calib,
+                       out, out_off, res, region=(-1, -1), stream=0):
+        """torch tensors on the handle's GPU: uint8, int64, int32, int32, uint8 | int32 (the uint32 CIGAR words), int64, int32 | int32 |
+        float32, int64, int32 | rmap an int32 tensor of shape (entries, 2) and calib a uint8 tensor of 40 bytes per read, both as
+        calibrate_device filled them | out a uint8 tensor of 12 bytes per entry, int64 out_off and res a uint8 tensor of 24 bytes per
+        read, filled in place (complete when the call returns)"""
+        n = seq_len.numel()
+        if rmap.numel() % 2 or calib.numel() * calib.element_size() < n * CALIB.itemsize or res.numel() * res.element_size() < n * REALIGN.itemsize:
+            raise ValueError("rmap holds int32 pairs, calib 40 bytes and res 24 bytes per read")
+        check(lib().gab_abea_realign_device(
+            self._h, C.c_void_p(ref.data_ptr()), C.c_int64(ref.numel()), C.c_void_p(ref_off.data_ptr()), C.c_void_p(ref_len.data_ptr()), C.c_void_p(ref_pos.data_ptr()),
+            C.c_void_p(is_rev.data_ptr()), C.c_void_p(cigar.data_ptr()), C.c_int64(cigar.numel()), C.c_void_p(cigar_off.data_ptr()), C.c_void_p(n_cigar.data_ptr()),
+            C.c_void_p(seq_len.data_ptr()), C.c_void_p(events.data_ptr()), C.c_int64(events.numel()), C.c_void_p(event_off.data_ptr()), C.c_void_p(n_events.data_ptr()),
+            C.c_void_p(rmap.data_ptr()), C.c_int64(rmap.numel() // 2), C.c_void_p(map_off.data_ptr()), C.c_void_p(calib.data_ptr()),
+            C.c_int32(region[0]), C.c_int32(region[1]), C.c_int64(n), C.c_void_p(out.data_ptr()), C.c_int64(out.numel() * out.element_size() // EALN.itemsize),
+            C.c_void_p(out_off.data_ptr()), C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+
+    def realign_last_stats(self):
+        """the last realign call: reads, calls of profile_hmm_align, their rows and cells, reads finished by the second launch, device
+        time of the kernels and of the whole call, and the time by stage (ms)"""
+        v = [C.c_int64(-1) for _ in range(5)]; kms = C.c_float(-1); tms = C.c_float(-1); st = [C.c_float(-1) for _ in range(3)]
+        check(lib().gab_abea_realign_last_stats(self._h, *[C.byref(x) for x in v], C.byref(kms), C.byref(tms)))
+        check(lib().gab_abea_realign_stage_ms(self._h, *[C.byref(x) for x in st]))
+        names = ("reads", "hmm_segments", "rows", "cells", "reads_requeued")
+        return {**{k: x.value for k, x in zip(names, v)}, "kernel_ms": kms.value, "total_ms": tms.value,
+                "prep_ms": st[0].value, "viterbi_ms": st[1].value, "requeue_ms": st[2].value}
 
     def events_last_stats(self):
         """the last detect_events call: samples, events, reads whose sums were added in order, chunks, chunks run again, kernel and

@@ -1,5 +1,5 @@
 // The abea handle, shared by abea.hip (align), abea_events.hip (event detection, scaling estimate) and abea_calib.hip (base-to-event
-// map, recalibration, read checks).
+// map, recalibration, read checks) and abea_realign.hip (realign_read).
 #pragma once
 #include "gab_internal.h"
 
@@ -26,6 +26,17 @@ struct gab_abea_calib_state {
     ~gab_abea_calib_state();
 };
 
+// what abea_realign.hip keeps on the handle; its destructor (abea_realign.hip) frees it when the handle is deleted
+struct gab_abea_realign_state {
+    gab_devbuf io;          // staging of the host-pointer entry point
+    gab_devbuf scratch;     // verdict | jobs | states | launch items | CIGAR runs | segments | k-mer ranks of the references
+    gab_devbuf trace;       // the wavefronts' backpointer traces
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // before / after the preparation, after the first launch, after the requeue
+    int64_t reads = 0, hmm_segments = 0, rows = 0, cells = 0, reads_requeued = 0;
+    float prep_ms = 0.f, viterbi_ms = 0.f, requeue_ms = 0.f, total_ms = 0.f;
+    ~gab_abea_realign_state();
+};
+
 struct gab_abea {
     gab_host_stream hs;
     int device = 0;
@@ -38,4 +49,5 @@ struct gab_abea {
     float kernel_ms = 0.f, total_ms = 0.f;
     gab_abea_events_state events;
     gab_abea_calib_state calib;
+    gab_abea_realign_state realign;
 };

@@ -786,7 +786,7 @@ int gab_parser_last_stats(gab_parser *p, float *kernel_ms);
  * n_events >= 1, anything else is GAB_EINVAL naming the read.  The two steps before align() in the reference's timed region,
  * event detection and the scaling estimate, are gab_abea_events and gab_abea_scalings below: their outputs are what this call
  * takes; the fixed block after it, postalign, recalibrate_model and the three read checks, is gab_abea_calibrate at the end
- * of this header.  Out of scope: the methylation HMM and realign_read. */
+ * of this header, and realign_read, the step after that, is gab_abea_realign behind it.  Out of scope: the methylation HMM. */
 #define GAB_ABEA_K 6
 #define GAB_ABEA_BANDWIDTH 100
 #define GAB_ABEA_NKMER 4096
@@ -894,8 +894,8 @@ int gab_abea_events_shape(int32_t *chunk, int32_t *warmup);
  *           = postalign (abea/src/align.c:550-650), recalibrate_model (align.c:655-762) and the three checks that set
  *             read_stat_flag (f5c.c:1474-1501), per read.
  * The pairs of gab_abea_align go in; the base-to-event map, events_per_base, the recalibrated scalings and the read's flag
- * come out: everything the methylation HMM and realign_read take from the alignment.  Bit for bit the reference built WITHOUT
- * fused multiply-add.
+ * come out: everything the methylation HMM and realign_read (gab_abea_realign below) take from the alignment.  Bit for bit the
+ * reference built WITHOUT fused multiply-add.
  * Map (align.c:561-585): a pair counts only when its event differs from the previous pair's event; `start` is the first such
  * event of the k-mer, `stop` the last.  events_per_base = (double)(max_event - min_event) / n_kmers over all pairs.
  * Event alignment (align.c:595-646): k-mers in order, those without events skipped, one entry per event of start..stop; an
@@ -947,6 +947,89 @@ int gab_abea_calibrate_device(gab_abea *h, const char *seq, int64_t seq_bytes, c
  * kernels and of the whole call from first to last kernel, the host's turns between them included (HIP events on the stream,
  * ms).  Any may be NULL. */
 int gab_abea_calibrate_last_stats(gab_abea *h, int64_t *reads, int64_t *recalibrated, int64_t *m_states, float *kernel_ms, float *total_ms);
+
+/* ---- abea: realign_read, the event alignment records of eventalign ------------------------------------------
+ * Replaces  realign_read of process_single                          abea/src/f5c.c:1508-1515
+ *           = align_read_to_ref (abea/src/eventalign.c:1263-1540) around profile_hmm_align (eventalign.c:703-911), per read.
+ * The reference substring, position, strand and CIGAR of a read's BAM record and what gab_abea_calibrate wrote go in; the event
+ * alignment records come out, the rows of events.tsv whose reference_kmer and model_kmer columns the suite's check compares
+ * (abea/scripts/regression_small.sh:78-88).  Bit for bit the reference built WITHOUT fused multiply-add.
+ * Which reads run: those with calib[i].read_stat_flag == 0 (f5c.c:1474-1501 return before realign_read otherwise); the others
+ * get 0 entries and the flag GAB_ABEA_REALIGN_SKIPPED.
+ * Reference string (eventalign.c:1294-1301): upper-cased, IUPAC codes replaced by their first base (disambiguate, :1091-1109),
+ * and its reverse complement.  CIGAR (get_aligned_segments_two_params, :1112-1179): M = X emit pairs, D advances the reference,
+ * I and S the read, H nothing, N closes a segment and opens the next.  Per segment the region trim (:932-943, when region_start
+ * and region_end are not -1) and the trim to read positions <= seq_len - 6 (:947-957); an empty segment ends the read (:1335-1337,
+ * GAB_ABEA_REALIGN_NO_PAIRS).  Then the loop of :1373-1534: get_end_pair 100 reference bases on, the three breaks (fewer than 12
+ * bases, a stop event less than 2 from the start event, nothing emitted), the Viterbi fill of profile_hmm_fill_generic_r9
+ * (:345-610, hmm_flags 0, CACHED_LOG emission, update_cell's comparisons as written, :621-633) and the backtrack from (last row,
+ * last k-mer, MATCH); of its entries the first 50 that are not K states and not the start event's, or all of them in the last
+ * section, are emitted, and the next section starts at the last one.  Not built: summarize_alignment (--summary only), the SAM
+ * writer, the numeric columns of the TSV.
+ * The transitions are per-read constants in float from calib[i].events_per_base (calculate_transitions, :171-240), their
+ * logarithms taken on the host with libm, as log_var is.
+ * Records: ref_kmer and model_kmer are not stored because they follow from a record.  ref_kmer is the six bases of the prepared
+ * (upper-cased, disambiguated) reference at ref_position (:1474).  model_kmer (:1486-1503) is "NNNNNN" for a 'B'; otherwise, forward,
+ * fwd_subseq.substr(kmer_idx, 6) = the same six bases, and, reverse, rc_subseq.substr(len - kmer_idx - 6, 6) with rc_subseq the
+ * reverse complement of fwd_subseq, which is the reverse complement of those six bases.
+ * Room: read i's entries go to out[out_off[i] ..], n_events[i] * (1 + its number of N operations) entries of room, regions
+ * disjoint.  That is enough: a section never emits its start event (:1468) and its events lie strictly on one side of it, the
+ * next section starts at the last event emitted, and the loop runs towards last_event only, so within one BAM segment every event
+ * is emitted at most once; each N operation opens one more segment.  Less room is GAB_EINVAL.
+ * Input rules: seq_len >= 6; n_events >= 1; every reference byte valid for isValid after toupper (ACGT and the IUPAC codes
+ * MRWSYKVHDBN, either case); CIGAR operations in MIDNSH=X; the CIGAR's reference span <= ref_len and its read span <= seq_len;
+ * event means, scale, shift, var and log_var finite, var > 0; map entries -1 or inside [0, n_events).  Anything else is
+ * GAB_EINVAL naming the read, and nothing is written.  n_reads = 0 returns GAB_OK and writes nothing.
+ * Defined where the reference has undefined behaviour or aborts: get_closest_event_to returns -1 for the first, last or stop
+ * event (the reference indexes event[-1]) -> GAB_ABEA_REALIGN_NO_EVENT; the event stride disagrees with the strand (the assert of
+ * :363) -> GAB_ABEA_REALIGN_STRAND.  The read ends there with the entries it has.  Everything else is the reference's, also
+ * events_per_base <= 1, where p_stay <= 0 makes transitions -inf or NaN and update_cell's comparisons decide.
+ * How it runs: one wavefront per read, two k-mer blocks per lane, the backpointers in a trace of GAB_ABEA_REALIGN_ROWS rows per
+ * wavefront; a read that meets a section of more rows stops there and is finished by a second launch (reads_requeued). */
+#define GAB_ABEA_REALIGN_ROWS 512
+typedef struct { int32_t ref_position, event_idx; uint8_t hmm_state /* 'M' or 'B' */, pad[3]; } gab_abea_ealn;
+enum { GAB_ABEA_REALIGN_SKIPPED = 1,   /* calib[i].read_stat_flag != 0: the reference never calls realign_read */
+       GAB_ABEA_REALIGN_NO_PAIRS = 2,  /* a segment was empty after the trims: the reference returns what it has */
+       GAB_ABEA_REALIGN_NO_EVENT = 4,  /* defined deviation, above */
+       GAB_ABEA_REALIGN_STRAND = 8 };  /* defined deviation, above */
+typedef struct {
+    int32_t n_entries;     /* records written at out[out_off[i] ..] */
+    int32_t hmm_segments;  /* calls of profile_hmm_align */
+    int32_t max_rows;      /* events of the longest of them */
+    uint32_t flags;
+    int64_t cells;         /* events x k-mers over them */
+} gab_abea_realign_read;
+/* Host buffers.  Read i: the reference bases ref[ref_off[i] .. +ref_len[i]) of [ref_pos[i], ref_pos[i] + ref_len[i]) (what the
+ * reference's fasta_cache holds), is_rev[i] (bam_is_rev), its CIGAR cigar[cigar_off[i] .. +n_cigar[i]) in BAM encoding (len << 4 |
+ * op), seq_len[i] (read_length), its event means, its map at map[map_off[i] ..] and calib[i] exactly as gab_abea_calibrate wrote
+ * them.  region_start = region_end = -1: no region (the driver's default). */
+int gab_abea_realign(gab_abea *h, const char *ref, const int64_t *ref_off, const int32_t *ref_len, const int32_t *ref_pos,
+                     const uint8_t *is_rev, const uint32_t *cigar, const int64_t *cigar_off, const int32_t *n_cigar,
+                     const int32_t *seq_len, const float *event_mean, const int64_t *event_off, const int32_t *n_events,
+                     const gab_abea_range *map, const int64_t *map_off, const gab_abea_calib *calib,
+                     int32_t region_start, int32_t region_end, int64_t n_reads,
+                     gab_abea_ealn *out, const int64_t *out_off, gab_abea_realign_read *res);
+/* Device buffers.  ref_bytes / cigar_count / event_count / map_count / out_count = sizes of the five slabs (bytes, operations,
+ * floats, map entries, records), for bounds validation.  Synchronises `stream` at the start (lengths, offsets, calibration
+ * records and CIGARs come to the host and are validated there; the CIGARs' run-length tables go back), after the first launch
+ * (the requeue decision, and the verdict of the checks that ran on the device: a broken rule returns GAB_EINVAL here, and the
+ * kernels have written nothing), once per requeue batch if there is one, and at the end, so out and res are complete when it
+ * returns. */
+int gab_abea_realign_device(gab_abea *h, const char *ref, int64_t ref_bytes, const int64_t *ref_off, const int32_t *ref_len, const int32_t *ref_pos,
+                            const uint8_t *is_rev, const uint32_t *cigar, int64_t cigar_count, const int64_t *cigar_off, const int32_t *n_cigar,
+                            const int32_t *seq_len, const float *event_mean, int64_t event_count, const int64_t *event_off, const int32_t *n_events,
+                            const gab_abea_range *map, int64_t map_count, const int64_t *map_off, const gab_abea_calib *calib,
+                            int32_t region_start, int32_t region_end, int64_t n_reads,
+                            gab_abea_ealn *out, int64_t out_count, const int64_t *out_off, gab_abea_realign_read *res, void *stream);
+/* last gab_abea_realign* call: reads, calls of profile_hmm_align, their rows (events) and cells (events x k-mers), reads finished
+ * by the second launch, device time of the kernels and of the whole call from first to last kernel, the host's turn between the
+ * launches included (HIP events on the stream, ms).  Any may be NULL. */
+int gab_abea_realign_last_stats(gab_abea *h, int64_t *reads, int64_t *hmm_segments, int64_t *rows, int64_t *cells,
+                                int64_t *reads_requeued, float *kernel_ms, float *total_ms);
+/* the last gab_abea_realign* call's time by stage: preparation | first launch | requeue */
+int gab_abea_realign_stage_ms(gab_abea *h, float *prep_ms, float *viterbi_ms, float *requeue_ms);
+/* GAB_ABEA_REALIGN_ROWS as the library was built (no GPU needed) */
+int gab_abea_realign_shape(int32_t *rows_cap);
 
 #ifdef __cplusplus
 }

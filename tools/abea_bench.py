@@ -7,6 +7,10 @@
                                                           the stage times, chunks_redone and reads_serial_sums
     python tools/abea_bench.py [--signal] --calibrate     adds gab_abea_calibrate_device on the pairs of the alignment to either mode and
                                                           prints its time next to align's
+    python tools/abea_bench.py [--signal] --calibrate --realign
+                                                          adds gab_abea_realign_device behind that: a generated reference and CIGAR per read
+                                                          (substitutions, insertions and deletions at 3 % each, half the reads reverse); wall
+                                                          time, rows/s, cells/s, reads_requeued and the preparation / Viterbi / requeue split
 
 Reports reads/s, band cells/s (cells filled, the reference's `fills`), ms per launch, and the DP kernel's share of the device time
 against the rest (k-mer table and backtrack).  Wall time is taken around the call, which synchronises its stream before it returns."""
@@ -99,6 +103,7 @@ def main_signal(a):
     d_mo = torch.from_numpy(np.concatenate([[0], np.cumsum(n_kmers[:-1])]).astype(np.int64)).cuda()
     rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
     cal = torch.zeros(n * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
+    realign = Realign(torch, rng, packed) if a.realign else None
     runs = []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
@@ -123,6 +128,8 @@ def main_signal(a):
         runs.append({"events_ms": (t1 - t0) * 1e3, "scalings_ms": (t3 - t2) * 1e3, "align_ms": (t4 - t3) * 1e3, "ev": est, "sc": h.scalings_last_stats(), "al": h.last_stats()})
         if a.calibrate:
             runs[-1].update(timed_calibrate(h, torch, (d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift), pairs, d_po, res, rmap, d_mo, cal))
+        if realign:
+            runs[-1].update(realign.timed(h, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal))
     warm = runs[1:]
     med = lambda f: float(np.median([f(r) for r in warm]))
     rec = res.cpu().numpy().view(abea.READ)
@@ -139,6 +146,8 @@ def main_signal(a):
            "device": torch.cuda.get_device_name(0)}
     if a.calibrate:
         out.update(calibrate_report(warm, cal.cpu().numpy().view(abea.CALIB)))
+    if realign:
+        out.update(realign.report(warm))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
@@ -157,6 +166,70 @@ def timed_calibrate(h, torch, inputs, pairs, d_po, res, rmap, d_mo, cal):
     return {"calibrate_ms": (time.perf_counter() - t0) * 1e3, "cal": h.calibrate_last_stats()}
 
 
+def generate_alignments(rng, seq, seq_off, seq_len, rate=0.03):
+    """per read a reference and a CIGAR, as a mapper would report them: every read base is an insertion, a substitution or a match,
+    a deletion of one reference base goes before some; every other read maps to the reverse strand (its BAM record holds the reverse
+    complement).  -> ref, ref_off, ref_len, ref_pos, is_rev, cigar (BAM encoding), cigar_off, n_cigar"""
+    comp = np.zeros(256, np.uint8); comp[np.frombuffer(b"ACGT", np.uint8)] = np.frombuffer(b"TGCA", np.uint8)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    refs, cigars = [], []
+    for i, (o, n) in enumerate(zip(seq_off, seq_len)):
+        bases = seq[o:o + n]
+        if i % 2:
+            bases = comp[bases[::-1]]
+        u = rng.random(int(n))
+        u[0] = u[-1] = 1.0                               # the CIGAR begins and ends with a match
+        ins = u < rate; dele = (u >= rate) & (u < 2 * rate); sub = (u >= 2 * rate) & (u < 3 * rate)
+        own = np.where(sub, acgt[(np.searchsorted(acgt, bases) + rng.integers(1, 4, int(n))) % 4], bases)
+        two = np.stack([acgt[rng.integers(0, 4, int(n))], own], 1)      # (a deleted reference base, the base's own)
+        keep = np.stack([dele, ~ins], 1)
+        refs.append(two[keep])
+        ops = np.stack([np.full(int(n), 2), np.where(ins, 1, 0)], 1)[np.stack([dele, np.ones(int(n), bool)], 1)]      # D before the base; I or M
+        cut = np.flatnonzero(np.diff(ops)) + 1
+        starts = np.concatenate([[0], cut]); lens = np.diff(np.concatenate([starts, [ops.size]]))
+        cigars.append((lens.astype(np.uint32) << 4) | ops[starts].astype(np.uint32))
+    ref_len = np.array([r.size for r in refs], np.int32); n_cigar = np.array([c.size for c in cigars], np.int32)
+    off = lambda ln: np.concatenate([[0], np.cumsum(ln[:-1], dtype=np.int64)]).astype(np.int64)
+    return (np.concatenate(refs), off(ref_len), ref_len, rng.integers(0, 4_000_000, len(refs)).astype(np.int32), (np.arange(len(refs)) % 2).astype(np.uint8),
+            np.concatenate(cigars), off(n_cigar), n_cigar)
+
+
+class Realign:
+    """gab_abea_realign_device behind calibrate, everything resident; the entries' room is one per event (no N operations)"""
+
+    def __init__(self, torch, rng, packed):
+        self.torch = torch
+        aln = generate_alignments(rng, packed[0], packed[1], packed[2])
+        self.dev = [torch.from_numpy(np.ascontiguousarray(x if x.dtype != np.uint32 else x.view(np.int32))).cuda() for x in aln]
+        self.out = None
+
+    def timed(self, h, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal):
+        from genarchbench_amd import abea
+        torch = self.torch
+        if self.out is None:
+            self.out_off = event_off.clone()              # n_events entries of room per read, back to back as the events are
+            self.out = torch.empty(int(n_events.sum().item()) * abea.EALN.itemsize, dtype=torch.uint8, device="cuda")
+            self.res = torch.zeros(n_events.numel() * abea.REALIGN.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.realign_device(*self.dev, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal, self.out, self.out_off, self.res)
+        return {"realign_ms": (time.perf_counter() - t0) * 1e3, "rl": h.realign_last_stats()}
+
+    def report(self, warm):
+        from genarchbench_amd import abea
+        med = lambda f: float(np.median([f(r) for r in warm]))
+        st = warm[-1]["rl"]
+        ms = med(lambda r: r["realign_ms"])
+        rec = self.res.cpu().numpy().view(abea.REALIGN)
+        return {"realign_wall_ms_median": round(ms, 3), "realign_wall_ms_all": [round(r["realign_ms"], 3) for r in warm],
+                "realign_rows_per_s": round(st["rows"] / (ms * 1e-3), 1), "realign_cells_per_s": round(st["cells"] / (ms * 1e-3), 1),
+                "realign_hmm_segments": st["hmm_segments"], "realign_rows": st["rows"], "realign_cells": st["cells"], "reads_requeued": st["reads_requeued"],
+                "realign_prep_ms": round(med(lambda r: r["rl"]["prep_ms"]), 3), "realign_viterbi_ms": round(med(lambda r: r["rl"]["viterbi_ms"]), 3),
+                "realign_requeue_ms": round(med(lambda r: r["rl"]["requeue_ms"]), 3), "realign_first_to_last_kernel_ms": round(med(lambda r: r["rl"]["total_ms"]), 3),
+                "realign_entries": int(rec["n_entries"].sum()), "realign_max_rows": int(rec["max_rows"].max()),
+                "realign_flags": {str(k): int((rec["flags"] == k).sum()) for k in sorted(set(rec["flags"].tolist()))}}
+
+
 def calibrate_report(warm, rec):
     med = lambda f: float(np.median([f(r) for r in warm]))
     st = warm[-1]["cal"]
@@ -173,13 +246,17 @@ def main():
     ap.add_argument("--seed", type=int, default=1); ap.add_argument("--json")
     ap.add_argument("--signal", action="store_true", help="raw signal in: event detection, scalings and align, timed per stage")
     ap.add_argument("--calibrate", action="store_true", help="add the base-to-event map, recalibration and read checks after align, timed")
+    ap.add_argument("--realign", action="store_true", help="add realign_read after --calibrate, on a generated reference and CIGAR per read, timed")
     a = ap.parse_args()
+    if a.realign and not a.calibrate:
+        ap.error("--realign runs on what --calibrate leaves: give both")
     if a.signal:
         return main_signal(a)
     import genarchbench_amd  # noqa: F401  (before torch: the runtime's default for pageable copies)
     import torch
     from genarchbench_amd import abea
-    (mean, stdv), packed, room = generate(np.random.default_rng(a.seed), a.reads, a.min_bases, a.max_bases)
+    rng = np.random.default_rng(a.seed)
+    (mean, stdv), packed, room = generate(rng, a.reads, a.min_bases, a.max_bases)
     h = abea.EventAligner(mean, stdv)
     dev = [torch.from_numpy(x).cuda() for x in packed]
     pairs = torch.empty((room, 2), dtype=torch.int32, device="cuda")
@@ -188,6 +265,7 @@ def main():
     d_mo = torch.from_numpy(np.concatenate([[0], np.cumsum(n_kmers[:-1])]).astype(np.int64)).cuda()
     rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
     cal = torch.zeros(a.reads * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
+    realign = Realign(torch, rng, packed) if a.realign else None
     walls, stats, cals = [], [], []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
@@ -196,6 +274,8 @@ def main():
         walls.append(time.perf_counter() - t0); stats.append(h.last_stats())
         if a.calibrate:
             cals.append(timed_calibrate(h, torch, dev[:8], pairs, dev[8], res, rmap, d_mo, cal))
+        if realign:
+            cals[-1].update(realign.timed(h, dev[2], dev[3], dev[4], dev[5], rmap, d_mo, cal))
     rec = res.cpu().numpy().view(abea.READ)
     order = np.argsort(walls[1:]); mid = 1 + int(order[len(order) // 2])
     st, wall = stats[mid], walls[mid]
@@ -207,6 +287,8 @@ def main():
            "device": torch.cuda.get_device_name(0)}
     if a.calibrate:
         out.update(calibrate_report(cals[1:], cal.cpu().numpy().view(abea.CALIB)))
+    if realign:
+        out.update(realign.report(cals[1:]))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
