@@ -143,6 +143,33 @@
 //     sweeps row k its score is at least d_{k+1}; the only other way its row loop ends earlier is a z-drop in a row i < k, which needs
 //     best - rowmax_i - gap > zdrop with gap >= 0 and rowmax_i >= H(i, i) >= d_{i+1}: its score, that `best`, then exceeds
 //     d_{i+1} + zdrop.  (The minimum above also runs over d_0: more conservative than needed.)  The score is never below h0.
+//   L with hops (matrices of bwa_fill_scmat's form -- one match score a > 0, one mismatch score, one score wherever a code is 4 or
+//     above, neither above a; detected once in gab_bsw_create, BswConst::hop; every other matrix keeps the L above, scanned base by
+//     base as before; profiles/bsw_hop_bound.md).  The L above stops growing at a pair's first indel.  It is the value of a PATH of
+//     the DP, and so is every path that leaves the diagonal through a gap: from the peak of the main diagonal's scan at most three
+//     hops (kHops) follow the alignment, each onto a neighbouring diagonal.
+//       Candidates.  With kp the peak's step in the current segment (segment 0: the main diagonal; kp counts diagonal steps from the
+//         segment's start), the hop leaves from the segment's cell at step kp, kp - 4 or kp - 8 through one of three gaps: one or
+//         two reference bases deleted (o_del + g e_del) or one query base inserted (o_ins + e_ins): nine candidates.  One stays
+//         out unless (a) it lands on a positive value, (b) it lands inside the band, |i - j| <= w for the pair's clamped w, (c) its
+//         start is at least ONE diagonal step into its segment (never the h0 corner, the left edge or a gap cell), and -- economy --
+//         the first min(16, bases left) bases behind the gap hold at most four mismatches or Ns and keep `low` (below) positive.
+//         Of those that are left, the ONE with the largest d behind these first bases (the first of them in the order step kp,
+//         kp - 4, kp - 8 x del 1, del 2, ins 1 on a tie) is scanned; it becomes the next segment if its peak exceeds L, and the
+//         chain ends otherwise.
+//       A segment behind a hop is scanned in chunks of sixteen bases counted from its start, by the chunk's COUNTS alone (the lanes
+//         of a wave hold different pairs: a walk from base to base costs every lane what it costs the slowest).  With nm mismatches
+//         and nn Ns among a chunk's cnt bases, low = d - nm max(0, -mm) - nn max(0, -nsc) is at or below every prefix of the chunk
+//         and d + cnt a - nm (a - mm) - nn (a - nsc) is the exact value behind it.  The scan stops in front of the first chunk
+//         with low <= 0.  mn, the minimum the z-drop cap is made of, takes every `low` and the landing cell's value, and starts
+//         from the minimum of the previous segment up to its peak: at or below every value of the path.  A chunk's end is worth
+//         min(d, zdrop + 1 + mn) (d with zdrop == 0); the largest worth is the segment's peak.  Behind the peak's chunk the next
+//         sixteen bases are taken once more in steps of four by the same rule, and then the run of matches in front of the next
+//         mismatch or N: the peak then lies within four bases of where the diagonal really ends, which is where the next hop has to
+//         leave from.  A segment whose peak is held down by the cap starts no hop (no candidate's cap is higher).
+//       L = the largest peak.  tools/gen/bsw_exit_model.c (hop_bound) states the rule base by base; gabgen.bsw_hop_bound exports it,
+//         gabgen.bsw_seed_bound stays the ungapped L.  On the read-like input S - L falls from 20.6 to 6.1 on average and the model
+//         evaluates 0.691 of the cells.
 //   Threshold thr = max(best, L - 1) replaces `best` in the left prune's cell test and its column-0 edge test, in the right prune's cell
 //     test, in the right-edge guard and in the zero-row guard.  L - 1 and not L: a cell of the diagonal path of a perfect ungapped
 //     match has potential exactly L (tools/gen/bsw_exit_model.c has that wrong rule as a negative control).  The z-drop guard, `best`
@@ -174,8 +201,31 @@
 //      earlier row and by step 12 the pruned run's `best` is S too; its rowmax <= the reference's < S - zdrop, so the z-drop guard
 //      abandons the pass (a pair that has dropped nothing IS the reference).  In a row where the reference does not z-drop the pruned
 //      run either goes on or abandons the pass; the second pass is the exit alone.
+//  15. L with hops <= S.  Claim: every cell (i, j) of the path -- diagonal steps and gap cells -- is a cell the reference computes,
+//      in a row it reaches, at a value >= the path's value v > 0 there; then S >= every value of the path, up to the z-drop (19).
+//      Induction along the path.  A diagonal step from a cell with H >= v > 0 gives M >= v + score (the DP is monotone), and a
+//      positive cell is neither trimmed nor outside the band when |i - j| <= w (16).  A deleted reference base is E of the cell
+//      below: E(i + 1, j) >= H(i, j) - o_del - e_del, a second one E - e_del; an inserted query base is F of the cell to the right,
+//      H(i, j) - o_ins - e_ins.  The path's values are these right-hand sides, positive by (a).
+//  16. (b) The reference clamps every row to |i - j| <= w with ITS w, the pair's clamped one; a path cell outside would not be
+//      computed (w = 0, or end_bonus = -1000 which leaves w = 1).  The gate tests the landing cell; a two-base deletion's first
+//      gap cell has an i - j between the start's and the landing cell's, both inside.
+//  17. (c) A hop's start must be a cell the reference has computed as a positive H.  The h0 corner and the left edge are not
+//      cells of a row: the reference ends its row loop at a row of zeros although the left edge is still alive (a first base that
+//      mismatches under a mismatch score of -128: row 0 is zero, S = h0, and a leading deletion would claim 237).  After one
+//      diagonal step the start is stored cell j of a swept row with a positive value.  tools/gen/bsw_exit_model.c has the rule
+//      without this gate as a negative control (wrong_hop).
+//  18. (d) The inserted base lies inside the row's `end`: the start is a positive stored cell j of the previous row's sweep, so
+//      that row's right trim stopped at or behind it and end >= j + 2; the F of the cell right of the start is computed.  One base
+//      only: a longer run of inserted bases would need the same of every cell it crosses.  The deleted bases need nothing: E is
+//      carried down the start's own column, which stays inside [beg, end) while its value is positive.
+//  19. (e) Z-drop.  The reference's row loop can end before the path's last row only by its z-drop test in a row i the path has
+//      passed, which needs best - rowmax_i > zdrop with rowmax_i >= the path's value in row i >= mn: S, that `best`, exceeds
+//      mn + zdrop.  Every step's worth is held at zdrop + 1 + mn with mn at or below EVERY earlier value of the path (gap cells,
+//      earlier segments and every prefix of a chunk included: `low`), so L <= S either way.  (A row in which the path sits in a
+//      gap cell of E has rowmax >= that E.)
 // The sort key of a score-only call (a six-field call keeps (query length, reference length / 8, h0 / 32) and computes no L) is
-// (query length, deficit) with deficit = qlen - (L - h0) / max_sc, the query bases the ungapped extension does not
+// (query length, deficit) with deficit = qlen - (L - h0) / max_sc, the query bases the path behind L does not
 // match: under the threshold a cell survives within about deficit / 2 columns of the diagonal, so the deficit is the pair's band width.
 //
 // Where the rule lives in bsw_dp8 (the 8-bit kernel; profiles/bsw_row_tail.md): score-only is a template argument, so the six-field
@@ -204,23 +254,24 @@ constexpr int kNumKeys = kQBuckets * kTBuckets;
 constexpr int kClassStep = 16;            // query-length classes for LDS sizing
 constexpr int kNumClasses = kQBuckets / kClassStep;
 constexpr int kSlices = 2;                // a large batch is sorted in this many slices of its pair range (bsw_run_device_impl)
-// The constants are measured (10 M read-like pairs, score-only).  kSlice0, kSortGridBeside and kSeedGridBeside with the seeded
-// prune, profiles/bsw_seeded_prune.md; kSliceMin was NOT measured again and is the value of profiles/bsw_slices.md.
+// The constants are measured (10 M read-like pairs, score-only).  kSortGridBeside with the seeded prune, profiles/bsw_seeded_prune.md
+// (its figures below are of that time); kSlice0 and kSeedGridBeside again with the hop bound, profiles/bsw_hop_bound.md; kSliceMin
+// was NOT measured again and is the value of profiles/bsw_slices.md.
 //   kSlice0: slice 0's DP has to outlast slice 1's sort and the host's wait for it, and every pair of slice 0 sits in a small
-//     launch (2^20 pairs in 8 classes are 2 300 waves each, little more than the chip holds at once).  With bsw_seed in front of
-//     the histogram slice 1's sort ends 2.3 ms into the step, not 1.0.  Medians of three runs per size, runs within 0.13 ms:
-//     1 048 576 pairs 21.95 ms, 1 572 864 pairs 21.62, 2 097 152 pairs 22.00 (a second series with 786 432 pairs in it: 22.12,
-//     22.11, 21.76, 22.10).  Too small and the GPU waits for slice 1's sort, too large and too many pairs sit
-//     in slice 0's small launches.
+//     launch (2^20 pairs in 8 classes are 2 300 waves each, little more than the chip holds at once).  With the hops bsw_seed of
+//     slice 1 runs 3.7 ms beside slice 0's DP (1.0 ms with the ungapped bound).  Two runs per size, runs within 0.05 ms:
+//     1 048 576 pairs 21.65 ms, 1 572 864 pairs 20.73, 2 097 152 pairs 20.39, 2 621 440 pairs 20.52, 3 145 728 pairs 20.72.
+//     Too small and the GPU waits for slice 1's sort, too large and too many pairs sit in slice 0's small launches.
 //   kSliceMin (before the seeded prune): a sliced call pays for sixteen class launches instead of eight and gains the sort of
 //     slice 1.  It measured 0.23 ms faster than the unsliced call at 3 M pairs, 0.37 at 4 M, 0.46 at 6 M, 0.68 at 8 M; 2^22 is
 //     the first size whose gain stood clear of the spread of the runs.
 //   kSortGridBeside: medians of three runs, 64 workgroups 22.05 ms, 256 workgroups 21.66, 1 024 workgroups 21.76 (runs within
 //     0.07 ms).  At 64 the histogram and the scatter of slice 1 outlast slice 0's DP; at 1 024 they take wave slots from it.
-//   kSeedGridBeside: bsw_seed is VALU work like the DP (about fifteen instructions per base) and takes every wave slot it is
-//     given: at 2 048 workgroups slice 0's class launches wait for it (22.32 ms per step), at 512 22.11, at 256 22.63 and at 128
-//     24.56 -- there the pass outlasts slice 0's DP and the GPU waits for slice 1's sort.
-constexpr int64_t kSlice0 = 1572864;      // pairs in slice 0 of a sliced score-only call
+//   kSeedGridBeside: bsw_seed is VALU work like the DP and takes every wave slot it is given.  With the ungapped bound: 2 048
+//     workgroups 22.32 ms per step (slice 0's class launches wait for it), 512 22.11, 256 22.63, 128 24.56 (the pass outlasts
+//     slice 0's DP and the GPU waits for slice 1's sort).  With the hops, two runs each at kSlice0 = 1 572 864: 256 22.96, 512
+//     20.73, 1 024 20.35 with runs 0.13 ms apart -- not clear of five times that, and the larger kSlice0 answers the same wait.
+constexpr int64_t kSlice0 = 2097152;      // pairs in slice 0 of a sliced score-only call
 constexpr int64_t kSlice0Full = 1 << 20;  // ... of a sliced six-field call: its sort has no scan in it, the value of profiles/bsw_slices.md stays
 constexpr int64_t kSliceMin = 1 << 22;    // fewest pairs of a sliced call
 constexpr int kSortGridBeside = 256;      // workgroups of bsw_hist / bsw_scatter when they run beside DP kernels
@@ -232,6 +283,8 @@ struct BswConst {
     int32_t seed;         // economy gates of the seeded prune (header comment): bit 0 the threshold max(best, L - 1), bit 1 the prune of row -1
     uint32_t row_lo[5];   // biased (+128) scores mat[t][0..3], one byte each
     uint32_t row_hi[5];   // biased score mat[t][4] in byte 0
+    int32_t hop;          // the matrix has bwa_fill_scmat's three-value form: the seed pass makes the hop bound, word-parallel
+    int32_t hop_a, hop_mm, hop_n;   // ... its match, mismatch and N scores (hop_a > 0, neither of the others above it)
 };
 
 struct BswStats {          // device-side, zeroed per run
@@ -252,7 +305,7 @@ struct BswIO {
     int64_t ref_hi, qry_hi;        // end of the bytes that really hold the caller's data (= ref_bytes / qry_bytes for device slabs; the
 };                                 // end of what gab_bsw_run COPIED: its window is padded to 256 bytes, and the padding is not the caller's data)
 
-// (query length, deficit): deficit = qlen - (L - h0) / max_sc is the number of query bases that the ungapped extension behind the
+// (query length, deficit): deficit = qlen - (L - h0) / max_sc is the number of query bases that the path behind the
 // seeded prune's lower bound L (bsw_seed) does NOT match, 0 for a perfect ungapped match.  Lanes of a wave then run the same number
 // of rows, and bands of similar width: with thr = max(best, L - 1) a cell survives while it lies within about deficit / 2 columns of
 // the diagonal.  On the read-like input the deficit alone predicts a pair's cell count (correlation 0.91; reference length and h0,
@@ -285,7 +338,8 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
 
 // ---- pass 0: validate + the seeded prune's lower bound L per pair ---------------------------
 // L (header comment): the ungapped extension from d = h0 along the main diagonal, stopped at the first d <= 0, every prefix held
-// down by what a z-drop of the reference in an earlier row would still return.  seed[i] = L, or -1 for a pair that fails the
+// down by what a z-drop of the reference in an earlier row would still return -- and, for a matrix of bwa_fill_scmat's form, up to
+// three one-gap hops from its peak (bsw_hop_bound below).  seed[i] = L, or -1 for a pair that fails the
 // validation (L >= h0 >= 0 otherwise): bsw_hist and bsw_scatter read it instead of validating again.  One thread per pair reads both
 // sequences; the pass issues no atomics, and beside the DP kernels of another slice its grid is kSeedGridBeside.
 // (seeded == 0, a six-field call: validation only, L = h0; no sequence is read)
@@ -298,6 +352,148 @@ __device__ __forceinline__ void bsw_seed_mat(const BswConst &c, int *s_mat) {   
         s_mat[threadIdx.x] = (int)((q < 4 ? c.row_lo[t] >> (8 * q) : c.row_hi[t]) & 0xffu) - 128;
     }
 }
+// ---- the hop bound (header comment: "L with hops") --------------------------------------------
+// The segments behind a hop are scanned by COUNTS, sixteen bases per trip from one 16-byte load per sequence, with no walk from
+// base to base: the lanes of a wave hold different pairs, and a walk costs every lane what it costs the slowest.  e marks the
+// bytes that do not score a match (the codes differ, or one is 4 or above: an N), nb the Ns among them; a chunk's mismatches and
+// Ns are two population counts.  Nothing is read further than three bytes past either sequence's end: a chunk that would reach
+// further is read in dwords, each only where it holds a base, and the bytes behind the segment's end are masked out.
+struct BswHopSeg { int pk, kp, dk, mk; };      // the peak's worth (0: none), its step (1-based), d and mn there
+__device__ __forceinline__ uint32_t bsw_nz_bytes(uint32_t y) { return (((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u; }   // bit 7 of every non-zero byte
+// the next min(16, left) bases from t and q (left >= 1): e / nb per dword, bytes behind `left` cleared
+__device__ __forceinline__ void bsw_hop_load(const uint8_t *t, const uint8_t *q, int left, uint32_t e[4], uint32_t nb[4]) {
+    uint32_t tw[4], qw[4];
+    if (left >= 13) {
+        __builtin_memcpy(tw, t, 16);
+        __builtin_memcpy(qw, q, 16);
+    } else {
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const bool in = 4 * b < left;
+            tw[b] = in ? load_u32_unaligned(t + 4 * b) : 0u;
+            qw[b] = in ? load_u32_unaligned(q + 4 * b) : 0u;
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int vb = left - 4 * b;
+        const uint32_t m = vb >= 4 ? ~0u : vb <= 0 ? 0u : (1u << (8 * vb)) - 1u;
+        nb[b] = (tw[b] | qw[b]) & 0xfcfcfcfcu & m;
+        e[b] = ((tw[b] ^ qw[b]) & m) | nb[b];
+    }
+}
+// one chunk's rule (tools/gen/bsw_exit_model.c, hop_scan): cnt bases with nm mismatches and nn Ns behind state (d, mn); false and
+// nothing changed when the chunk's lowest possible prefix is not positive
+__device__ __forceinline__ bool bsw_hop_step(const BswConst &c, int cnt, int nm, int nn, int end, int &d, int &mn, BswHopSeg &s) {
+    const int dm = c.hop_mm < 0 ? -c.hop_mm : 0, dn = c.hop_n < 0 ? -c.hop_n : 0;
+    const int low = d - nm * dm - nn * dn;
+    if (low <= 0) return false;
+    d += cnt * c.hop_a - nm * (c.hop_a - c.hop_mm) - nn * (c.hop_a - c.hop_n);
+    mn = low < mn ? low : mn;
+    int v = d;
+    if (c.zdrop > 0 && d - mn > c.zdrop) v = c.zdrop + 1 + mn;
+    if (v > s.pk) { s.pk = v; s.kp = end; s.dk = d; s.mk = mn; }
+    return true;
+}
+// t, q: the segment's first bases; n: the bases the shorter of the two still has (may be <= 0); d > 0, mn <= d
+__device__ __forceinline__ BswHopSeg bsw_hop_scan(const BswConst &c, const uint8_t *t, const uint8_t *q, int n, int d, int mn) {
+    BswHopSeg s; s.pk = 0; s.kp = 0; s.dk = d; s.mk = mn;
+    uint32_t e[4], nb[4];
+    bool live = true;
+#pragma unroll 1
+    for (int k = 0; k < n && live; k += 16) {
+        bsw_hop_load(t + k, q + k, n - k, e, nb);
+        const int cnt = n - k < 16 ? n - k : 16;
+        int ne = 0, nn = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) ne += __popc(bsw_nz_bytes(e[b]));
+        if ((nb[0] | nb[1] | nb[2] | nb[3]) != 0u) {
+#pragma unroll
+            for (int b = 0; b < 4; b++) nn += __popc(bsw_nz_bytes(nb[b]));
+        }
+        live = bsw_hop_step(c, cnt, ne - nn, nn, k + cnt, d, mn, s);
+        if (c.zdrop > 0 && s.pk == c.zdrop + 1 + mn) live = false;    // the cap is reached: no later step can be worth more
+    }
+    // behind the peak's chunk: the next sixteen bases in steps of four, then the run of matches in front of the next marked byte
+    const int base = s.kp, left = n - base < 16 ? n - base : 16;
+    if (left >= 1) {
+        bsw_hop_load(t + base, q + base, left, e, nb);
+        d = s.dk; mn = s.mk;
+        live = true;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int cnt = left - 4 * b < 4 ? left - 4 * b : 4;
+            if (live && cnt > 0) {
+                const int nn = __popc(bsw_nz_bytes(nb[b]));
+                live = bsw_hop_step(c, cnt, __popc(bsw_nz_bytes(e[b])) - nn, nn, base + 4 * b + cnt, d, mn, s);
+            }
+        }
+        const int o = s.kp - base;                          // 0, 4, 8, 12 -- or `left`, the end of the window
+        if (o < left) {
+            const uint32_t eo = o == 0 ? e[0] : o == 4 ? e[1] : o == 8 ? e[2] : e[3];
+            const int cnt = left - o < 4 ? left - o : 4;
+            int lead = eo ? __builtin_ctz(bsw_nz_bytes(eo)) >> 3 : 4;
+            lead = lead < cnt ? lead : cnt;
+            const int d2 = s.dk + lead * c.hop_a;
+            int v = d2;
+            if (c.zdrop > 0 && d2 - s.mk > c.zdrop) v = c.zdrop + 1 + s.mk;
+            if (lead > 0 && v > s.pk) { s.pk = v; s.kp += lead; s.dk = d2; }
+        }
+    }
+    return s;
+}
+
+// L of one pair from the main diagonal's scan (L, its peak step kp, the minimum mk up to there): at most kHops times the one
+// candidate of nine around the current segment's peak whose first chunk ends highest (header comment; tools/gen/bsw_exit_model.c,
+// hop_bound, is the same rule).
+constexpr int kHops = 3, kHopEvents = 4;
+__device__ __forceinline__ int bsw_hop_bound(const BswConst &c, const uint8_t *t, int tl, const uint8_t *q, int ql, int L, int kp, int mk) {
+    int si = 0, sj = 0, dk = L;
+    // the band gate |i - j| <= w of the pair's clamped w: dist <= lim with lim = max(1, (int)(x / e + 1.)) holds iff dist <= 1 or
+    // x >= (dist - 1) * e -- no division
+    const int xi = ql * c.max_sc + c.end_bonus - c.o_ins, xd = ql * c.max_sc + c.end_bonus - c.o_del;
+    const int dm = c.hop_mm < 0 ? -c.hop_mm : 0, dn = c.hop_n < 0 ? -c.hop_n : 0;
+#pragma unroll 1
+    for (int hop = 0; hop < kHops; hop++) {
+        if (c.zdrop > 0 && L - mk > c.zdrop) break;         // the peak is held down by the cap (dk == L otherwise): no candidate's cap is higher
+        int bestv = 0, bi = 0, bj = 0, bd = 0, dd = dk;
+#pragma unroll 1
+        for (int back = 0; back <= 8; back += 4) {
+            const int cs = kp - back;                       // the start's step in its segment: (c) at least one diagonal step in
+            if (cs < 1) break;
+            if (back) {                                     // d at step cs: take back the scores of steps cs + 1 .. cs + 4
+                const uint32_t tw = load_u32_unaligned(t + si + cs), qw = load_u32_unaligned(q + sj + cs);
+                const uint32_t nb = (tw | qw) & 0xfcfcfcfcu, e = (tw ^ qw) | nb;
+                dd -= 4 * c.hop_a + __popc(bsw_nz_bytes(e)) * (c.hop_mm - c.hop_a) + __popc(bsw_nz_bytes(nb)) * (c.hop_n - c.hop_mm);
+            }
+            const int ci = si + cs, cj = sj + cs;
+#pragma unroll 1
+            for (int g = 0; g < 3; g++) {                   // 1 or 2 reference bases deleted, 1 query base inserted
+                const int ni = g < 2 ? ci + g + 1 : ci, nj = g < 2 ? cj : cj + 1;
+                const int nd = g < 2 ? dd - c.o_del - (g + 1) * c.e_del : dd - c.o_ins - c.e_ins;
+                const int dist = ni > nj ? ni - nj : nj - ni;
+                const bool band = dist <= c.w && (dist <= 1 || (xi >= (dist - 1) * c.e_ins && xd >= (dist - 1) * c.e_del));
+                int left = tl - ni < ql - nj ? tl - ni : ql - nj;
+                if (nd <= 0 || !band || left < 1) continue; // (a) a positive value, (b) inside the band
+                left = left < 16 ? left : 16;
+                uint32_t e[4], nb[4];
+                bsw_hop_load(t + ni, q + nj, left, e, nb);
+                int ne = 0, nn = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) { ne += __popc(bsw_nz_bytes(e[b])); nn += __popc(bsw_nz_bytes(nb[b])); }
+                if (ne > kHopEvents || nd - (ne - nn) * dm - nn * dn <= 0) continue;
+                const int val = nd + left * c.hop_a - (ne - nn) * (c.hop_a - c.hop_mm) - nn * (c.hop_a - c.hop_n);
+                if (val > bestv) { bestv = val; bi = ni; bj = nj; bd = nd; }
+            }
+        }
+        if (bestv == 0) break;
+        const BswHopSeg s = bsw_hop_scan(c, t + bi, q + bj, tl - bi < ql - bj ? tl - bi : ql - bj, bd, mk < bd ? mk : bd);
+        if (s.pk <= L) break;
+        L = s.pk; si = bi; sj = bj; kp = s.kp; dk = s.dk; mk = s.mk;
+    }
+    return L;
+}
+
 __device__ __forceinline__ int bsw_seed_of(const BswIO &io, const BswConst &c, const int *s_mat, int seeded, int64_t i) {
     {
         const int ql = io.len2[i], tl = io.len1[i], h = io.h0[i];
@@ -310,10 +506,7 @@ __device__ __forceinline__ int bsw_seed_of(const BswIO &io, const BswConst &c, c
         if (!seeded) return h;                              // (wave-uniform)
         const uint8_t *const t = io.ref + ro, *const q = io.qry + qo;
         const int n = ql < tl ? ql : tl;
-        // Sixteen bases per trip, one 16-byte load per sequence: a pair costs ten memory round trips instead of the seventy-six of a
-        // dword per trip (that form was bound by their latency: 0.30 ms per million pairs, against 0.13).  Nothing is read further
-        // than three bytes past either sequence's end: the last trip falls back to dwords, each read only where it holds a base.
-        int d = h, L = h, mn = h;
+        int d = h, L = h, mn = h, kp = 0, mk = h;              // kp: the first step (1-based) worth L; mk: the minimum of d_0 .. d_kp
         bool live = h > 0;                                  // the scan goes on: no d <= 0 so far and bases left
         for (int k = 0; k < n && live; k += 16) {
             uint32_t tw[4], qw[4];
@@ -337,12 +530,12 @@ __device__ __forceinline__ int bsw_seed_of(const BswIO &io, const BswConst &c, c
                     d = nd;
                     int v = d;
                     if (c.zdrop > 0 && d - mn > c.zdrop) v = c.zdrop + 1 + mn;
-                    L = v > L ? v : L;
                     mn = d < mn ? d : mn;
+                    if (v > L) { L = v; kp = k + b + 1; mk = mn; }
                 }
             }
         }
-        return L;
+        return c.hop && kp > 0 ? bsw_hop_bound(c, t, tl, q, ql, L, kp, mk) : L;
     }
 }
 __global__ __launch_bounds__(256) void bsw_seed(BswIO io, BswConst c, int seeded, int64_t lo, int64_t hi, int32_t *__restrict__ seed) {
@@ -1250,6 +1443,9 @@ extern "C" int gab_bsw_create(const gab_bsw_params *p, int device, gab_bsw **out
     for (int k = 0; k < 25; k++) mx = p->mat[k] > mx ? p->mat[k] : mx;
     c.max_sc = mx;
     c.seed = 1 | (mx <= p->e_ins ? 2 : 0);
+    c.hop_a = p->mat[0]; c.hop_mm = p->mat[1]; c.hop_n = p->mat[4];
+    c.hop = c.hop_a > 0 && c.hop_mm <= c.hop_a && c.hop_n <= c.hop_a;
+    for (int k = 0; k < 25; k++) c.hop = c.hop && p->mat[k] == (k / 5 == 4 || k % 5 == 4 ? c.hop_n : k / 5 == k % 5 ? c.hop_a : c.hop_mm);
     for (int t = 0; t < 5; t++) {
         uint32_t lo = 0;
         for (int q = 0; q < 4; q++) lo |= (uint32_t)(uint8_t)(p->mat[t * 5 + q] + 128) << (8 * q);

@@ -104,7 +104,8 @@ def bsw_from_arrays(refs, qrys, h0s):
 
 
 BSW_PRUNE_RULES = {"default": 7, "capped": 1, "wrong_left": 2, "parent": 3, "wrong_right": 4, "left_cap_only": 5, "right_only": 6,
-                   "wrong_seed": 8, "seed_thr_only": 9, "seed_row_only": 10, "seed_ungated": 11}
+                   "wrong_seed": 8, "seed_thr_only": 9, "seed_row_only": 10, "seed_ungated": 11, "seed_ungated_hops": 12,
+                   "wrong_hop": 13, "seed_no_hops": 14}
 
 
 def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, wrong_potential=False, rule="default"):
@@ -113,10 +114,12 @@ def bsw_exit_model(batch, params, early_exit=True, prune=True, restarts=False, w
     (include/gab.h).  early_exit=False: the reference's full sweep.  prune=False: the exit alone.  restarts=True appends a fifth
     array: 1 where the pair abandoned its pruned pass for the z-drop guard and ran again without the prune.  wrong_potential=True
     is the tests' negative control (the left prune's potential counts two columns too few).  rule picks among the model's prune
-    rules: "default" is what the kernels do (left prune capped at four cells per row, right prune, both seeded with the ungapped
-    lower bound L of the score where the parameters pass the rule's gates); "capped" the rule before the seed; "seed_thr_only" /
+    rules: "default" is what the kernels do (left prune capped at four cells per row, right prune, both seeded with the lower
+    bound L of the score -- bsw_hop_bound's -- where the parameters pass the rule's gates); "capped" the rule before the seed; "seed_thr_only" /
     "seed_row_only" the seed's two parts (the threshold max(best, L - 1); the prune of row -1), "seed_ungated" both at every parameter
-    set; "wrong_seed" the seed's negative control (threshold L); "parent" the rule before the
+    set with the ungapped L the gates were measured with, "seed_ungated_hops" the same with the hop bound, "seed_no_hops" the
+    default rule with the ungapped L; "wrong_seed" the seed's negative control (threshold L), "wrong_hop" the hop bound's (a hop
+    may leave from the h0 corner); "parent" the rule before the
     right prune (left uncapped, no right prune); "left_cap_only", "right_only" its two halves; "wrong_right" the right side's
     negative control (its potential counts two columns too few)"""
     n = batch.n
@@ -140,6 +143,16 @@ def bsw_seed_bound(batch, params):
     L = np.zeros(batch.n, np.int32)
     lib().gab_bsw_seed_bound(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
                              _p(batch.len2), _p(batch.h0), C.c_int64(batch.n), _p(L))
+    return L
+
+
+def bsw_hop_bound(batch, params, wrong=False):
+    """the lower bound L the kernels seed their prunes with: bsw_seed_bound's scan plus a chain of at most two one-gap hops, for
+    matrices of the three-value form; any other matrix keeps bsw_seed_bound's value (tools/gen/bsw_exit_model.c, hop_bound).
+    wrong=True is the negative control "wrong_hop" -> int32 [n]"""
+    L = np.zeros(batch.n, np.int32)
+    lib().gab_bsw_hop_bound(C.byref(params), _p(batch.ref), _p(batch.ref_off), _p(batch.qry), _p(batch.qry_off), _p(batch.len1),
+                            _p(batch.len2), _p(batch.h0), C.c_int64(batch.n), C.c_int(1 if wrong else 0), _p(L))
     return L
 
 

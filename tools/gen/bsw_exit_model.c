@@ -54,7 +54,8 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
  *
  *
  * Seeded prune (same scope, same pairs; bsw.hip's header has the proof).  The ungapped extension along the main diagonal is a path
- * of the DP, so a lower bound L of the pair's FINAL score is known before row 0 (seed_bound below), and a cell whose potential is
+ * of the DP, and so is its continuation over a gap onto a neighbouring diagonal, so a lower bound L of the pair's FINAL score is
+ * known before row 0 (seed_bound and hop_bound below: the kernels use hop_bound's), and a cell whose potential is
  * below L cannot lead to the final score whatever `best` is at its row.  With thr = max(best, L - 1):
  *   thr replaces `best` in the left prune's cell test and its column-0 edge test, in the right prune's cell test, in the right-edge
  *   guard and in the zero-row guard; the z-drop guard, `best` itself and the exit's bound <= best are unchanged;
@@ -67,10 +68,12 @@ typedef struct {                      /* same layout as gab_bsw_params (include/
  * `prune` selects the rule:  0 off;  7 what the kernels do (left prune capped, right prune, seeded);  1 the rule before the seed
  * (left prune capped, right prune);  3 the rule before the right prune (left prune uncapped, no right prune);  5 left prune capped,
  * no right prune;  6 left prune uncapped, right prune;  9 rule 7 without the prune of row -1;  10 rule 7 with thr == best (the prune
- * of row -1 alone);  11 rule 7 with its gates open at every parameter set (what the gates are measured against).
+ * of row -1 alone);  11 rule 7 with its gates open at every parameter set AND the ungapped bound (what the gates were measured
+ * against);  12 rule 11 with the hop bound;  14 rule 7 with the ungapped bound (what the hops are measured against).
  * TEST-ONLY wrong rules, the negative controls of tests/test_bsw_left_prune.py, tests/test_bsw_right_prune.py and
  * tests/test_bsw_seeded_prune.py: 2 is rule 1 with the left potential's columns short by two, 4 is rule 1 with the right potential's
- * columns short by two, 8 is rule 7 with thr = max(best, L): a cell of the diagonal path can have potential exactly L. */
+ * columns short by two, 8 is rule 7 with thr = max(best, L): a cell of the diagonal path can have potential exactly L, 13 is rule 7
+ * with the hop bound's gate (c) off (tests/test_bsw_hop_bound.py): a hop may then leave from the h0 corner. */
 /* Row trace (gab_bsw_exit_trace below; NULL for the other entry points): per swept row of every pass, the abandoned one included,
  * the [beg, end) the row was swept with and which of the kernels' per-row paths the row takes. */
 enum { TR_LZ4 = 1,        /* the left zero trim ran past its four-cell window */
@@ -88,16 +91,152 @@ typedef struct { int16_t *beg, *end; uint8_t *flags, *drops; int64_t cap, n; } r
  * first d <= 0.  While every d so far is positive, cell (k, k) holds at least d_{k+1} (M of a non-zero diagonal), lies inside the
  * reference's band (|i - j| = 0 <= w, and the zero trims pass only zero cells) and its row is not zero.  So the reference's score is
  * at least d_{k+1} if it sweeps row k, and if it z-drops in an earlier row i its score exceeds rowmax_i + zdrop >= d_{i+1} + zdrop. */
-static int seed_bound(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0) {
+/* (kp: the first step, 1-based, that is worth L -- 0 while L == h0; mk: the minimum of d_0 .. d_kp.  Either may be NULL.) */
+static int seed_scan(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0, int *kp, int *mk) {
     int d = h0, L = h0, mn = h0;
     const int n = qlen < tlen ? qlen : tlen;
+    if (kp) *kp = 0;
+    if (mk) *mk = h0;
     for (int k = 0; k < n && d > 0; k++) {
         d += p->mat[5 * (target[k] > 4 ? 4 : target[k]) + (query[k] > 4 ? 4 : query[k])];
         if (d <= 0) break;
         int v = d;
         if (p->zdrop > 0 && d - mn > p->zdrop) v = p->zdrop + 1 + mn;
-        if (v > L) L = v;
         if (d < mn) mn = d;
+        if (v > L) { L = v; if (kp) *kp = k + 1; if (mk) *mk = mn; }
+    }
+    return L;
+}
+static int seed_bound(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0) {
+    return seed_scan(p, qlen, query, tlen, target, h0, NULL, NULL);
+}
+
+/* The three-value form of bwa_fill_scmat: one match score a > 0 on the diagonal of the four bases, one mismatch score off it, one
+ * score wherever a code is 4 or above, neither above a.  The hop bound serves these matrices only; any other keeps the ungapped
+ * bound. */
+static int three_value(const gab_bsw_model_params *p, int *a, int *mm, int *nsc) {
+    *a = p->mat[0]; *mm = p->mat[1]; *nsc = p->mat[4];
+    for (int t = 0; t < 5; t++)
+        for (int q = 0; q < 5; q++)
+            if (p->mat[5 * t + q] != (t == 4 || q == 4 ? *nsc : t == q ? *a : *mm)) return 0;
+    return *a > 0 && *mm <= *a && *nsc <= *a;
+}
+
+/* One chunk of a hop segment: the next cnt <= 16 bases from target[i], query[j] -> mismatches (both codes below 4 and different),
+ * Ns (a code of 4 or above), and the matching bases in front of the first of either. */
+static void hop_chunk(const uint8_t *target, const uint8_t *query, int i, int j, int cnt, int *nm, int *nn, int *lead) {
+    *nm = *nn = 0; *lead = cnt;
+    for (int b = cnt - 1; b >= 0; b--) {
+        const int t = target[i + b], q = query[j + b];
+        if (t >= 4 || q >= 4) { ++*nn; *lead = b; }
+        else if (t != q) { ++*nm; *lead = b; }
+    }
+}
+
+/* One diagonal segment behind a hop, from state (i, j, d, mn) -- the next step reads target[i] and query[j] -- in chunks of sixteen
+ * bases counted from the segment's start (the last one shorter), by what a chunk's COUNTS say alone, so that the kernels need no
+ * walk from base to base.  With nm mismatches and nn Ns among a chunk's cnt bases
+ *     low   = d - nm * max(0, -mm) - nn * max(0, -nsc)        no prefix of the chunk is below it,
+ *     d_end = d + cnt * a - nm * (a - mm) - nn * (a - nsc)    the exact value behind the chunk.
+ * The scan stops in front of the first chunk with low <= 0 (it cannot vouch for a positive path there; stopping early only lowers L).
+ * mn takes every low: it is at or below every path value so far, which only lowers the z-drop cap.  A chunk's end is worth
+ * min(d_end, zdrop + 1 + mn); the largest worth is the peak.  Behind the peak's chunk the run of matching bases in front of the next
+ * mismatch or N (of at most sixteen bases) is added: each of its steps is a step of the path, the last one worth the most.
+ * Returns the peak's worth (0: none), its step (1-based), and d and mn there. */
+typedef struct { int pk, kp, dk, mk; } hop_seg;
+static hop_seg hop_scan(const gab_bsw_model_params *p, int a, int mm, int nsc, int qlen, const uint8_t *query, int tlen,
+                        const uint8_t *target, int i, int j, int d, int mn) {
+    hop_seg s = {0, 0, d, mn};
+    const int n = tlen - i < qlen - j ? tlen - i : qlen - j, zd = p->zdrop;
+    const int dm = mm < 0 ? -mm : 0, dn = nsc < 0 ? -nsc : 0;
+    int nm, nn, lead;
+    for (int k = 0; k < n; k += 16) {
+        const int cnt = n - k < 16 ? n - k : 16;
+        hop_chunk(target, query, i + k, j + k, cnt, &nm, &nn, &lead);
+        const int low = d - nm * dm - nn * dn;
+        if (low <= 0) break;
+        d += cnt * a - nm * (a - mm) - nn * (a - nsc);
+        if (low < mn) mn = low;
+        int v = d;
+        if (zd > 0 && d - mn > zd) v = zd + 1 + mn;
+        if (v > s.pk) { s.pk = v; s.kp = k + cnt; s.dk = d; s.mk = mn; }
+        if (zd > 0 && s.pk == zd + 1 + mn) break;           /* the cap is reached: no later step can be worth more */
+    }
+    /* behind the peak's chunk, the next (at most) sixteen bases once more in steps of four, by the same rule; then, of the four bases
+     * behind the new peak and still among those sixteen, the run of matching bases in front of the first mismatch or N */
+    const int base = s.kp, left = n - base < 16 ? n - base : 16;
+    d = s.dk; mn = s.mk;
+    for (int k = 0; k < left; k += 4) {
+        const int cnt = left - k < 4 ? left - k : 4;
+        hop_chunk(target, query, i + base + k, j + base + k, cnt, &nm, &nn, &lead);
+        const int low = d - nm * dm - nn * dn;
+        if (low <= 0) break;
+        d += cnt * a - nm * (a - mm) - nn * (a - nsc);
+        if (low < mn) mn = low;
+        int v = d;
+        if (zd > 0 && d - mn > zd) v = zd + 1 + mn;
+        if (v > s.pk) { s.pk = v; s.kp = base + k + cnt; s.dk = d; s.mk = mn; }
+    }
+    const int o = s.kp - base;
+    if (o < left) {
+        hop_chunk(target, query, i + s.kp, j + s.kp, left - o < 4 ? left - o : 4, &nm, &nn, &lead);
+        int d2 = s.dk + lead * a, v = d2;
+        if (zd > 0 && d2 - s.mk > zd) v = zd + 1 + s.mk;
+        if (lead > 0 && v > s.pk) { s.pk = v; s.kp += lead; s.dk = d2; }
+    }
+    return s;
+}
+
+/* L of the kernels: at most HOP_K one-gap hops on top of the ungapped extension (bsw.hip's header has the proof).  Segment 0 is
+ * seed_bound's scan, base by base; the segments behind a hop are hop_scan's.  From a segment's peak step kp the candidates are its
+ * cells at steps kp - {0, 4, 8}, each with three gaps: 1 or 2 reference bases deleted (o_del + g e_del), or 1 query base inserted
+ * (o_ins + e_ins).  A candidate
+ *   (c) starts at least one diagonal step into its segment (never from the h0 corner, the left edge or a gap cell),
+ *   (a) lands on a positive value,  (b) lands inside the band |i - j| <= w of the pair's clamped w,
+ *   and -- economy -- has at most HOP_EV mismatches or Ns among the first min(16, bases left) bases behind the gap, and a
+ *   positive `low` there (hop_scan).
+ * It carries mn = the minimum of the scan up to the peak and its own landing cell (at or below every value of its path: a smaller
+ * cap).  ONE candidate is scanned: the one with the largest d behind its first chunk (first in the order back 0, 4, 8 x del 1,
+ * del 2, ins 1 on a tie); it becomes the next segment if its peak exceeds L.  A segment whose peak is held down by the z-drop cap
+ * starts no hop: no candidate's cap is higher.  no_gate_c is the negative control: a hop may leave from step 0 of segment 0. */
+enum { HOP_K = 3, HOP_EV = 4 };
+static int hop_bound(const gab_bsw_model_params *p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int h0, int no_gate_c) {
+    int a, mmis, nsc, kp, mk;
+    int L = seed_scan(p, qlen, query, tlen, target, h0, &kp, &mk);
+    if (!three_value(p, &a, &mmis, &nsc) || h0 <= 0) return L;
+    int w = p->w;
+    int lim = (int)((double)(qlen * a + p->end_bonus - p->o_ins) / p->e_ins + 1.);
+    if (lim < 1) lim = 1;
+    if (w > lim) w = lim;
+    lim = (int)((double)(qlen * a + p->end_bonus - p->o_del) / p->e_del + 1.);
+    if (lim < 1) lim = 1;
+    if (w > lim) w = lim;
+    const int dm = mmis < 0 ? -mmis : 0, dn = nsc < 0 ? -nsc : 0;
+    int si = 0, sj = 0, dk = L;
+    for (int hop = 0; hop < HOP_K; hop++) {
+        if (p->zdrop > 0 && L - mk > p->zdrop) break;       /* (the peak is capped; dk = L holds otherwise) */
+        int bestv = 0, bi = 0, bj = 0, bd = 0, dd = dk;
+        for (int back = 0; back <= 8; back += 4) {
+            const int c = kp - back;                             /* the start's step in its segment */
+            if (c < (no_gate_c && hop == 0 ? 0 : 1)) break;
+            if (back) for (int m = c + 4; m > c; m--) dd -= p->mat[5 * (target[si + m - 1] > 4 ? 4 : target[si + m - 1]) + (query[sj + m - 1] > 4 ? 4 : query[sj + m - 1])];
+            const int ci = si + c, cj = sj + c;
+            for (int g = 0; g < 3; g++) {
+                const int ni = g < 2 ? ci + g + 1 : ci, nj = g < 2 ? cj : cj + 1;
+                const int nd = g < 2 ? dd - p->o_del - (g + 1) * p->e_del : dd - p->o_ins - p->e_ins;
+                int left = tlen - ni < qlen - nj ? tlen - ni : qlen - nj, nm, nn, lead;
+                if (nd <= 0 || ni - nj > w || nj - ni > w || left < 1) continue;
+                if (left > 16) left = 16;
+                hop_chunk(target, query, ni, nj, left, &nm, &nn, &lead);
+                if (nm + nn > HOP_EV || nd - nm * dm - nn * dn <= 0) continue;
+                const int val = nd + left * a - nm * (a - mmis) - nn * (a - nsc);
+                if (val > bestv) { bestv = val; bi = ni; bj = nj; bd = nd; }
+            }
+        }
+        if (bestv == 0) break;
+        const hop_seg s = hop_scan(p, a, mmis, nsc, qlen, query, tlen, target, bi, bj, bd, mk < bd ? mk : bd);
+        if (s.pk <= L) break;
+        L = s.pk; si = bi; sj = bj; kp = s.kp; dk = s.dk; mk = s.mk;
     }
     return L;
 }
@@ -131,15 +270,17 @@ static void model_one(const gab_bsw_model_params *p, int qlen, const uint8_t *qu
                          (p->zdrop == 0 || p->zdrop >= 8 * max_sc);
     const int short_by = prune == 2 ? 2 : 0, short_r = prune == 4 ? 2 : 0;
     const int left_cap = !(prune == 3 || prune == 6), right_prune = prune != 3 && prune != 5;
-    const int seeded = prune >= 7 && prune <= 11;
+    const int seeded = prune >= 7 && prune <= 14;
     /* per pair: a band that can hold more than nine cells, min(qlen, 2 w + 1) > 9.  A narrower one is swept in at most two loop trips
      * of the kernels and the seed has next to nothing to remove there (with w <= 8 restriction (a) already fails for every h0 above
      * oe_ins + 9 e_ins); the narrow bands are also where the kernels' edge-cell paths live, whose tests read their cases off the
      * default rule's trace */
     const int seed_ok = seeded && (qlen < 2 * w + 1 ? qlen : 2 * w + 1) > 9;
-    const int gates = !seed_ok ? 0 : prune == 11 ? 3 : seed_gates(p, max_sc) & (prune == 9 ? 1 : prune == 10 ? 2 : 3);
+    const int gates = !seed_ok ? 0 : prune == 11 || prune == 12 ? 3 : seed_gates(p, max_sc) & (prune == 9 ? 1 : prune == 10 ? 2 : 3);
     /* thr = max(best, Lm1): Lm1 = 0 leaves thr == best (best >= h0 >= 0) */
-    const int Lm1 = prune_ok && (gates & 1) ? seed_bound(p, qlen, query, tlen, target, h0) - (prune == 8 ? 0 : 1) : 0;
+    const int Lm1 = !(prune_ok && (gates & 1)) ? 0
+                    : prune == 11 || prune == 14 ? seed_bound(p, qlen, query, tlen, target, h0) - 1
+                    : hop_bound(p, qlen, query, tlen, target, h0, prune == 13) - (prune == 8 ? 0 : 1);
     const int row_prune = prune_ok && (gates & 2);
 
     int best = h0, i = 0, redo = 0;
@@ -359,4 +500,11 @@ void gab_bsw_seed_bound(const gab_bsw_model_params *p, const uint8_t *ref, const
                         const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n, int32_t *L) {
 #pragma omp parallel for schedule(static)
     for (int64_t k = 0; k < n; k++) L[k] = seed_bound(p, len2[k], qry + qry_off[k], len1[k], ref + ref_off[k], h0[k]);
+}
+
+/* the lower bound the kernels use: seed_bound plus the chain of one-gap hops (hop_bound above), whatever the gates say */
+void gab_bsw_hop_bound(const gab_bsw_model_params *p, const uint8_t *ref, const int64_t *ref_off, const uint8_t *qry,
+                       const int64_t *qry_off, const int32_t *len1, const int32_t *len2, const int32_t *h0, int64_t n, int wrong, int32_t *L) {
+#pragma omp parallel for schedule(static)
+    for (int64_t k = 0; k < n; k++) L[k] = hop_bound(p, len2[k], qry + qry_off[k], len1[k], ref + ref_off[k], h0[k], wrong);
 }

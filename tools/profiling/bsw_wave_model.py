@@ -2,16 +2,18 @@
 """Lockstep work of the bsw_dp8 waves, from the CPU model's row trace (tools/gen/bsw_exit_model.c, gab_bsw_exit_trace) -- no GPU.
 
     python tools/profiling/bsw_wave_model.py [--pairs 500000] [--seed 2] [--mode 0] [--key KEY] [--rule default|capped|...]
+                                             [--bound hop|ungapped]
 
 Pairs are grouped as the kernels group them: by query-length class of 16 bases (one launch each at bench size), inside a class in
-the order of the sort key bsw_key = (qlen, deficit of the seed's ungapped extension), 64 consecutive pairs to a wave (the order inside
+the order of the sort key bsw_key = (qlen, deficit of the seed's lower bound L), 64 consecutive pairs to a wave (the order inside
 one key is atomic order on the GPU; here it is input order, so expect a per cent or two of difference).  A wave sweeps row r while
 any lane has a row r (a restarted pair's second pass follows its first), and runs as many four-cell loop trips in it as its widest
 lane.  Prints wave-rows, wave-trips, the share of lanes busy in each, and for every per-row path of the kernel the share of wave-rows
 in which at least one lane takes it.  --key compares groupings: `current` is bsw_key as the kernels have it, `oracle` sorts by each
 pair's true (rows, cells), `qlen_tmin_h0` by (qlen, min(tlen, qlen + 40) / 4, h0), `parent` by the key before the seeded prune
 (qlen, min(tlen / 8, 63), min(h0 / 32, 3)).  The others are the candidates the seeded prune's key was picked from, all with qlen as
-the major part and 256 values under it; deficit = qlen - (L - h0) for the seed's lower bound L (gabgen.bsw_seed_bound):
+the major part and 256 values under it; deficit = qlen - (L - h0) for the seed's lower bound L (gabgen.bsw_hop_bound, what the
+kernels make; --bound ungapped takes gabgen.bsw_seed_bound, the bound before the hops, which goes with --rule seed_no_hops):
 `d8` (deficit), `d7_short` (deficit / 2, tlen < qlen), `d7_h1` (deficit / 2, h0 >= 64), `d6_t2` (deficit / 4, min(tlen / 32, 3)),
 `d5_t3` (deficit / 8, min(tlen / 16, 7)); `q4_d2` is (qlen / 4, deficit / 2, tlen / 8, h0 / 32), which does not fit the 65 536 bins.
 --rule picks the model's prune rule (gabgen.BSW_PRUNE_RULES)."""
@@ -66,6 +68,7 @@ def main():
     ap.add_argument("--mode", type=int, default=0)
     ap.add_argument("--key", default="current", choices=["current", "oracle", "qlen_tmin_h0", "parent"] + list(SEED_KEYS))
     ap.add_argument("--rule", default="default", choices=list(gabgen.BSW_PRUNE_RULES))
+    ap.add_argument("--bound", default="hop", choices=["hop", "ungapped"])
     a = ap.parse_args()
     b = gabgen.bsw(a.seed, a.pairs, a.mode)
     p = bsw_oracle_params(*BSW_PARAM_SETS[0])
@@ -76,7 +79,8 @@ def main():
     if a.key == "parent":
         key = (ql - 1) * 256 + np.minimum(tl >> 3, 63) * 4 + np.minimum(h0 >> 5, 3)
     elif a.key in SEED_KEYS:
-        deficit = np.clip(ql - (gabgen.bsw_seed_bound(b, p).astype(np.int64) - h0), 0, 255)
+        bound = gabgen.bsw_hop_bound if a.bound == "hop" else gabgen.bsw_seed_bound
+        deficit = np.clip(ql - (bound(b, p).astype(np.int64) - h0), 0, 255)
         key = SEED_KEYS[a.key](ql, tl, h0, deficit)
     elif a.key == "qlen_tmin_h0":
         key = ((ql - 1) * 128 + np.minimum(tl, ql + 40) // 4) * 1024 + np.minimum(h0, 1023)
