@@ -121,11 +121,6 @@ void gab_tuning_load(gab_tuning *t) {
     }
     t->bpm_score64 = on("GAB_BPM_SCORE64"); t->bitpal_no_bv = on("GAB_BITPAL_NO_BV"); t->bpm_slices = (int)num("GAB_BPM_SLICES", 0);
     t->bpm_trace = on("GAB_BPM_TRACE");
-    if (const char *e = getenv("GAB_WFA_TUNE")) {
-        t->wfa_tuned = true;
-        const int k = sscanf(e, "%d,%d,%d,%d,%d,%d,%d", &t->wfa_tune[0], &t->wfa_tune[1], &t->wfa_tune[2], &t->wfa_tune[3], &t->wfa_tune[4], &t->wfa_tune[5], &t->wfa_tune[6]);
-        t->wfa_tune_fields = k > 0 ? k : 0;
-    }
     t->wfa_no_static = on("GAB_WFA_NO_STATIC"); t->wfa_trace = on("GAB_WFA_TRACE");
     t->wfa_pool2 = (int)num("GAB_WFA_POOL2", -1); t->wfa_slots = (int)num("GAB_WFA_SLOTS", -1);
     if (const char *e = getenv("GAB_CHAIN_HELPERS")) { t->chain_helpers_set = true; t->chain_helpers = atoi(e); }

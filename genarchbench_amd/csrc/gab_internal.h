@@ -97,9 +97,7 @@ struct gab_tuning {
     bool bpm_score64 = false, bitpal_no_bv = false, bpm_trace = false;
     int bpm_slices = 0;                              // 0 = by batch size
     // wfa
-    bool wfa_tuned = false, wfa_no_static = false, wfa_trace = false;
-    int wfa_tune[7] = {0, 0, 0, 0, 0, 0, 0};         // GAB_WFA_TUNE, as many fields as it gave
-    int wfa_tune_fields = 0;
+    bool wfa_no_static = false, wfa_trace = false;
     int wfa_pool2 = -1, wfa_slots = -1;              // -1 = unset
     // chain / fast-chain
     int chain_helpers = 0;                           // 3 / 5 / 7, 0 = unset

@@ -28,6 +28,7 @@
 // LDS traffic (sum over scores of the wavefront width + the extended matches).
 #include "gab_internal.h"
 #include "gab_pair_stage.h"
+#include "wfa_plan.h"
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -39,8 +40,6 @@ namespace {
 
 constexpr int kNull = -10;                 // AFFINE_WAVEFRONT_OFFSET_NULL
 constexpr int kNone = 0x7fffffff;          // "no wavefront" marker in the directory
-constexpr int kSeqPad = 32;                // physical 'X'/'Y' padding behind each LDS sequence (>= 16 + 3 for the 16-byte extension reads)
-constexpr int kLdsMaxLen = 2040;           // longest sequence the LDS kernels accept
 
 struct WfaPen { int32_t x, o, e, min_len, max_dist; };   // the last two: adaptive reduction parameters
 
@@ -71,8 +70,7 @@ struct OffB {
     __device__ __forceinline__ explicit OffB(int x) : v((uint8_t)(x + 10)) {}
     __device__ __forceinline__ explicit operator int() const { return (int)v - 10; }
 };
-constexpr int kOffBMax = 245;
-constexpr int kOffBSafe = 240;       // an M offset above this sends the pair to the next tier (I = M + 1 of the same step is already stored)
+constexpr int kOffBSafe = 240;      // an M offset above this sends the pair to the next tier (I = M + 1 of the same step is already stored)
 
 // The work counter is statistics, but 250 000 waves of a 3 ms launch adding to ONE address serialise in L2 (~8 ns per
 // atomic = 2 ms): the waves add to one of 256 slots, 128 bytes apart, behind the counters; wfa_sum_work folds them.
@@ -154,23 +152,8 @@ struct WfStore {
     __device__ __forceinline__ int at(int base, int lo, int hi, int k) const {
         return (base != kNone && lo <= k && k <= hi) ? (int)pool[base + (k - lo)] : kNull;
     }
-    // the backtrace's view: the allocated range
-    __device__ __forceinline__ bool has_base(int base, const WfDir &w, int k) const { return base != kNone && w.lob <= k && k <= w.hib; }
-    __device__ __forceinline__ int at_base(int base, const WfDir &w, int k) const {
-        return has_base(base, w, k) ? (int)pool[base + (k - w.lo)] : kNull;
-    }
 };
 
-__device__ __forceinline__ uint32_t lds_ld4(const uint8_t *base, int byte_off) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(base + (byte_off & ~3));
-    return __builtin_amdgcn_alignbyte(w[1], w[0], (uint32_t)(byte_off & 3));
-}
-// eight bytes at any byte offset: three aligned dwords, two v_alignbyte
-__device__ __forceinline__ uint64_t lds_ld8(const uint8_t *base, int byte_off) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(base + (byte_off & ~3));
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], sh = (uint32_t)(byte_off & 3);
-    return (uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32 | __builtin_amdgcn_alignbyte(w1, w0, sh);
-}
 __device__ __forceinline__ uint32_t glb_ld4(const char *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
 // four bytes of a sequence at `pos` (a multiple of 4); bytes at or behind `len` read as `fill`.  Branch-free: the slab is
 // readable up to the next multiple of 4 (counted from the SLAB's start) behind the sequence, so the last dword is fetched
@@ -187,6 +170,98 @@ __device__ __forceinline__ uint32_t seq_ld4(const char *s, int pos, int len, uin
     return (w & m) | (fill * 0x01010101u & ~m);
 }
 
+// ---- what the pair functions share (G = lanes cooperating on a pair): first, the lanes of my group in a wave-wide vote
+template <int G> __device__ __forceinline__ uint64_t wfa_group_mask() { return (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1)) << (threadIdx.x & 63 & ~(G - 1)); }
+// Both strings of pair `id` into LDS, padded with kSeqPad bytes of 'X' / 'Y': four bytes per lane and step (the LDS copies are
+// dword-aligned and have room to the next multiple of four).  Returns whether this lane met a pattern byte 'Y' or a text byte
+// 'X', which could match the OTHER string's padding outside the strings (only wfa_lds_static asks).
+template <int G> __device__ __forceinline__ bool wfa_stage(const WfaIO &io, uint32_t id, uint8_t *P, int plen, uint8_t *T, int tlen, int lane) {
+    bool pad_byte = false;
+    auto stage = [&](uint8_t *dst, const char *slab, int64_t off, int len, uint32_t fill, uint32_t probe) {
+        const int end_lo = (int)((off + len) & 3);
+        for (int i = 4 * lane; i < len + kSeqPad; i += 4 * G) {
+            const uint32_t w = seq_ld4(slab + off, i, len, fill, end_lo), x = w ^ (probe * 0x01010101u);
+            *reinterpret_cast<uint32_t *>(dst + i) = w;
+            pad_byte = pad_byte || ((x - 0x01010101u) & ~x & 0x80808080u) != 0;       // some byte of w is `probe`
+        }
+    };
+    const int64_t po = io.pat_off[id], to = io.txt_off[id];      // (both before the first loop: the loads overlap)
+    stage(P, io.pat, po, plen, (uint32_t)'X', (uint32_t)'Y');
+    stage(T, io.txt, to, tlen, (uint32_t)'Y', (uint32_t)'X');
+    return pad_byte;
+}
+
+// affine_wavefronts_extend_mwavefront_compute (the padded strings: affine_wavefront_extend.c:51-83), sixteen bases at a time:
+// the number of leading bases of p[0 .. 15] and t[0 .. 15] in LDS that match, 0 .. 16 (the 'X' / 'Y' padding behind the strings
+// never matches).  One 16-byte LDS read per string at ANY byte address (gfx950 reads LDS unaligned; aligned dwords +
+// v_alignbyte cost three times the instructions).
+__device__ __forceinline__ int wfa_match16(const uint8_t *p, const uint8_t *t) {
+    uint4 a, b;
+    __builtin_memcpy(&a, p, 16); __builtin_memcpy(&b, t, 16);
+    const uint64_t d8 = ((uint64_t)(a.y ^ b.y) << 32) | (a.x ^ b.x), e8 = ((uint64_t)(a.w ^ b.w) << 32) | (a.z ^ b.z);
+    if ((d8 | e8) == 0) return 16;
+    return d8 ? __builtin_ctzll(d8) >> 3 : 8 + (__builtin_ctzll(e8) >> 3);
+}
+// `cnt` operations `c` in front of ops[pos], written by the G lanes; writes in front of the buffer are dropped
+template <int G> __device__ __forceinline__ void wfa_put_run(char *ops, int &pos, char c, int cnt, int lane) {
+    for (int i = lane; i < cnt && pos - i >= 0; i += G) ops[pos - i] = c;
+    pos -= cnt > 0 ? cnt : 0;
+}
+// One source wavefront as the backtrace reads it: diagonal k lives at pool[base + (k - lo)] for lo <= k <= hi, the ALLOCATED
+// range (affine_wavefront_backtrace.c:75-226 reads lo_base .. hi_base); a missing wavefront is the empty range lo = 1, hi = -1.
+struct WfSrc { int base, lo, hi; };
+// affine_wavefronts_backtrace (affine_wavefront_backtrace.c:276-387), wave-uniform over the G lanes of the pair: from `offset` on
+// diagonal tlen - plen of score s back to score 0, the operations written right-aligned into ops[0, plen + tlen).
+// The caller's view of where the walk stands (score s; r is the caller's own, a table row or nothing): sources(s, r, mm, go, gi, gd)
+// = M[s-x], M[s-o-e], I[s-e], D[s-e] in `pool`, link(r, 0 | 1 | 2) = the r of score s - x | s - o - e | s - e.  match_run(pos, cnt):
+// a run of cnt matches in front of pos.  Returns the position of the first operation.
+template <int G, typename OffT, typename Sources, typename Link, typename MatchRun>
+__device__ __forceinline__ int wfa_backtrace(const OffT *pool, Sources &&sources, Link &&link, MatchRun &&match_run, char *ops, const WfaPen &pen,
+                                             int plen, int tlen, int s, int r, int offset, int lane) {
+    const int ak = tlen - plen;
+    int pos = plen + tlen - 1, k = ak, type = 0;            // type: 0 = M, 1 = I, 2 = D
+    auto valid_loc = [&](int kk, int oo) { return oo - kk > 0 && oo - kk <= plen && oo > 0 && oo <= tlen; };
+    bool valid = valid_loc(k, offset);
+    int v = offset - k, h = offset;
+    auto put = [&](char c) { if (lane == 0 && pos >= 0) ops[pos] = c; pos--; };
+    auto in = [](const WfSrc &w, int kk) { return w.lo <= kk && kk <= w.hi; };
+    auto at = [&](const WfSrc &w, int kk) { return (int)pool[w.base + (kk - w.lo)]; };
+    while (v > 0 && h > 0 && s > 0) {
+        if (!valid && (valid = valid_loc(k, offset))) {
+            if (k < ak) wfa_put_run<G>(ops, pos, 'I', ak - k, lane);
+            else if (k > ak) wfa_put_run<G>(ops, pos, 'D', k - ak, lane);
+        }
+        WfSrc mm, go, gi, gd;
+        sources(s, r, mm, go, gi, gd);
+        auto step = [&](int to) { s -= to == 0 ? pen.x : to == 1 ? pen.o + pen.e : pen.e; r = link(r, to); };
+        const int del_ext = (type == 1 || !in(gd, k + 1)) ? kNull : at(gd, k + 1);
+        const int del_open = (type == 1 || !in(go, k + 1)) ? kNull : at(go, k + 1);
+        const int ins_ext = (type == 2 || !in(gi, k - 1)) ? kNull : at(gi, k - 1) + 1;
+        const int ins_open = (type == 2 || !in(go, k - 1)) ? kNull : at(go, k - 1) + 1;
+        const int misms = (type != 0 || !in(mm, k)) ? kNull : at(mm, k) + 1;
+        const int max_all = max(misms, max(max(ins_ext, ins_open), max(del_ext, del_open)));
+        if (type == 0) { match_run(pos, offset - max_all); offset = max_all; }
+        if (max_all == del_ext) { if (valid) put('D'); step(2); k++; type = 2; }
+        else if (max_all == del_open) { if (valid) put('D'); step(1); k++; type = 0; }
+        else if (max_all == ins_ext) { if (valid) put('I'); step(2); k--; offset--; type = 1; }
+        else if (max_all == ins_open) { if (valid) put('I'); step(1); k--; offset--; type = 0; }
+        else { if (valid) put('X'); step(0); offset--; }
+        v = offset - k; h = offset;
+    }
+    if (s == 0) match_run(pos, offset);
+    else { wfa_put_run<G>(ops, pos, 'D', v, lane); wfa_put_run<G>(ops, pos, 'I', h, lane); }
+    // (writes in front of the buffer were dropped: a CIGAR longer than plen + tlen -- a sequence matching the other's padding
+    // byte beyond its end, where the reference overflows its buffer -- keeps its last plen + tlen operations)
+    return max(pos, -1) + 1;
+}
+// the finished CIGAR from LDS to the pair's output region, four bytes per lane and store (unaligned LDS read, unaligned global
+// store), its last 0 .. 3 bytes singly
+template <int G> __device__ __forceinline__ void wfa_copy_out(char *dst, const char *src, int nops, int lane) {
+    const int n4 = nops & ~3;
+    for (int i = 4 * lane; i < n4; i += 4 * G) { uint32_t w4; __builtin_memcpy(&w4, src + i, 4); __builtin_memcpy(dst + i, &w4, 4); }
+    if (lane < nops - n4) dst[n4 + lane] = src[n4 + lane];
+}
+
 // One pair, one wave.  LDSSEQ: P/T are LDS copies padded with kSeqPad bytes of 'X'/'Y';
 // otherwise they are the global sequences (readable to a multiple of 4 bytes past the end).
 // Returns false if the history did not fit (nothing has been written to the outputs then).
@@ -200,8 +275,7 @@ __device__ bool wfa_pair(WfStore<OffT, ADAPT> &st, const WfaPen pen, const uint8
     // once, left-aligned and coalesced), else the pair's own output region (shifted in place afterwards)
     char *ops = ops_lds ? ops_lds : ops_global;
     const int lane = threadIdx.x & (G - 1);
-    const int x = pen.x, oe = pen.o + pen.e, e = pen.e;
-    const int ak = tlen - plen;
+    const int x = pen.x, oe = pen.o + pen.e, e = pen.e, ak = tlen - plen;
     auto pch = [&](int v) -> int { return (v >= 0 && v < plen) ? (int)P[v] : (int)'X'; };
     auto tch = [&](int h) -> int { return (h >= 0 && h < tlen) ? (int)T[h] : (int)'Y'; };
 
@@ -236,31 +310,22 @@ __device__ bool wfa_pair(WfStore<OffT, ADAPT> &st, const WfaPen pen, const uint8
                 int o = (int)st.pool[cur.m + (k - cur.lo)];
                 int v = o - k, h = o;
                 for (;;) {
-                    if (LDSSEQ && v >= 0 && v <= plen && h >= 0 && h <= tlen) {
-                        // sixteen bases per step (the 'X' / 'Y' padding behind the strings never matches)
-                        uint4 qa, qb;                   // one unaligned 16-byte LDS read per string (see wfa_pair_static)
-                        __builtin_memcpy(&qa, P + v, 16); __builtin_memcpy(&qb, T + h, 16);
-                        const uint64_t d8 = ((uint64_t)(qa.y ^ qb.y) << 32) | (qa.x ^ qb.x), e8 = ((uint64_t)(qa.w ^ qb.w) << 32) | (qa.z ^ qb.z);
-                        if ((d8 | e8) == 0) { o += 16; v += 16; h += 16; work += 16; continue; }
-                        const int c8 = d8 ? __builtin_ctzll(d8) >> 3 : 8 + (__builtin_ctzll(e8) >> 3);
-                        o += c8; work += c8;
-                        break;
-                    }
                     if (v >= 0 && v <= plen && h >= 0 && h <= tlen) {
-                        uint32_t a, b;
-                        if (LDSSEQ) { a = lds_ld4(P, v); b = lds_ld4(T, h); }
+                        constexpr int kStep = LDSSEQ ? 16 : 4;          // bases compared at once
+                        int c;
+                        if (LDSSEQ) c = wfa_match16(P + v, T + h);
                         else {
                             // global strings have no physical padding: build the padded view
+                            uint32_t a, b;
                             if (v + 4 <= plen && h + 4 <= tlen) { a = glb_ld4((const char *)P + v); b = glb_ld4((const char *)T + h); }
                             else {
                                 a = (uint32_t)pch(v) | (uint32_t)pch(v + 1) << 8 | (uint32_t)pch(v + 2) << 16 | (uint32_t)pch(v + 3) << 24;
                                 b = (uint32_t)tch(h) | (uint32_t)tch(h + 1) << 8 | (uint32_t)tch(h + 2) << 16 | (uint32_t)tch(h + 3) << 24;
                             }
+                            c = a == b ? 4 : __builtin_ctz(a ^ b) >> 3;
                         }
-                        const uint32_t d = a ^ b;
-                        if (d == 0) { o += 4; v += 4; h += 4; work += 4; continue; }
-                        const int c = __builtin_ctz(d) >> 3;
                         o += c; work += c;
+                        if (c == kStep) { v += kStep; h += kStep; continue; }
                         break;
                     }
                     if (pch(v) == tch(h)) { o++; v++; h++; work++; continue; }
@@ -272,8 +337,7 @@ __device__ bool wfa_pair(WfStore<OffT, ADAPT> &st, const WfaPen pen, const uint8
             __syncthreads();
             if (sizeof(OffT) == 1) {
                 // one-byte offsets: an offset beyond the byte's range sends the pair to the next tier
-                const uint64_t gm = (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1)) << (threadIdx.x & 63 & ~(G - 1));
-                if (__ballot(too_big) & gm) return false;
+                if (__ballot(too_big) & wfa_group_mask<G>()) return false;
             }
             // ---- end reached?
             if (cur.lo <= ak && ak <= cur.hi && (int)st.pool[cur.m + (ak - cur.lo)] >= tlen) break;
@@ -351,60 +415,19 @@ __device__ bool wfa_pair(WfStore<OffT, ADAPT> &st, const WfaPen pen, const uint8
     }
 
     // ---- backtrace (wave-uniform): ops written right-aligned into [0, cap), then shifted left
-    const int cap = plen + tlen;
-    int pos = cap - 1;
-    int s = score, k = ak;
-    {
-        const WfDir w = st.get(s);
-        int offset = (int)st.pool[w.m + (k - w.lo)];
-        int type = 0;                                           // 0 = M, 1 = I, 2 = D
-        auto valid_loc = [&](int kk, int oo) { return oo - kk > 0 && oo - kk <= plen && oo > 0 && oo <= tlen; };
-        bool valid = valid_loc(k, offset);
-        int v = offset - k, h = offset;
-        auto put = [&](char c) { if (lane == 0 && pos >= 0) ops[pos] = c; pos--; };
-        auto put_run = [&](char c, int cnt) {
-            for (int i = lane; i < cnt && pos - i >= 0; i += G) ops[pos - i] = c;
-            pos -= cnt > 0 ? cnt : 0;
-        };
-        while (v > 0 && h > 0 && s > 0) {
-            if (!valid) {
-                valid = valid_loc(k, offset);
-                if (valid) {
-                    if (k < ak) put_run('I', ak - k);
-                    else if (k > ak) put_run('D', k - ak);
-                }
-            }
-            const int s_go = s - oe, s_ge = s - e, s_mm = s - x;
-            const WfDir wgo = st.get(s_go), wge = st.get(s_ge), wmm = st.get(s_mm);
-            const int del_ext = type == 1 ? kNull : st.at_base(wge.d, wge, k + 1);
-            const int del_open = type == 1 ? kNull : st.at_base(wgo.m, wgo, k + 1);
-            const int ie_raw = st.at_base(wge.i, wge, k - 1), io_raw = st.at_base(wgo.m, wgo, k - 1);
-            const bool ie_ok = st.has_base(wge.i, wge, k - 1);
-            const bool io_ok = st.has_base(wgo.m, wgo, k - 1);
-            const bool mm_ok = st.has_base(wmm.m, wmm, k);
-            const int ins_ext = (type == 2 || !ie_ok) ? kNull : ie_raw + 1;
-            const int ins_open = (type == 2 || !io_ok) ? kNull : io_raw + 1;
-            const int misms = (type != 0 || !mm_ok) ? kNull : st.at_base(wmm.m, wmm, k) + 1;
-            const int max_all = max(misms, max(max(ins_ext, ins_open), max(del_ext, del_open)));
-            if (type == 0) { put_run('M', offset - max_all); offset = max_all; }
-            if (max_all == del_ext) { if (valid) put('D'); s = s_ge; k++; type = 2; }
-            else if (max_all == del_open) { if (valid) put('D'); s = s_go; k++; type = 0; }
-            else if (max_all == ins_ext) { if (valid) put('I'); s = s_ge; k--; offset--; type = 1; }
-            else if (max_all == ins_open) { if (valid) put('I'); s = s_go; k--; offset--; type = 0; }
-            else { if (valid) put('X'); s = s_mm; offset--; }
-            v = offset - k; h = offset;
-        }
-        if (s == 0) put_run('M', offset);
-        else { put_run('D', v); put_run('I', h); }
-    }
-    // (writes in front of the buffer were dropped: a CIGAR longer than plen + tlen -- a sequence matching the other's padding
-    // byte beyond its end, where the reference overflows its buffer -- keeps its last plen + tlen operations)
-    pos = max(pos, -1) + 1;
-    const int nops = cap - pos;
+    const WfDir last = st.get(score);
+    auto sources = [&](int s, int, WfSrc &mm, WfSrc &go, WfSrc &gi, WfSrc &gd) {      // the directory entries of s - x, s - o - e, s - e
+        // (a reduction moved base along with lo: base + (lob - lo) is where diagonal lob lives)
+        auto src = [](int base, const WfDir &w) { return base == kNone ? WfSrc{0, 1, -1} : WfSrc{base + (w.lob - w.lo), w.lob, w.hib}; };
+        const WfDir wgo = st.get(s - oe), wge = st.get(s - e), wmm = st.get(s - x);
+        mm = src(wmm.m, wmm); go = src(wgo.m, wgo); gi = src(wge.i, wge); gd = src(wge.d, wge);
+    };
+    const int pos = wfa_backtrace<G>(st.pool, sources, [](int, int) { return 0; }, [&](int &at, int cnt) { wfa_put_run<G>(ops, at, 'M', cnt, lane); }, ops, pen, plen, tlen,
+                                     score, 0, (int)st.pool[last.m + (ak - last.lo)], lane);
+    const int nops = plen + tlen - pos;
     __syncthreads();
-    if (ops_lds) {
-        for (int i = lane; i < nops; i += G) ops_global[i] = ops_lds[pos + i];
-    } else if (pos > 0) {
+    if (ops_lds) wfa_copy_out<G>(ops_global, ops_lds + pos, nops, lane);
+    else if (pos > 0) {
         // shift left by `pos` bytes, G bytes per step (sources of a step are read before its stores)
         for (int c0 = 0; c0 < nops; c0 += G) {
             const int i = c0 + lane;
@@ -494,18 +517,13 @@ __global__ __launch_bounds__(64) void wfa_lds(WfaIO io, WfaPen pen, const uint32
         id = list ? list[b] : b;                             // no list: every pair of the batch is in this pass
         uint8_t *smem = smem_all + tab_bytes + (size_t)grp * group_bytes;
         int *dir = reinterpret_cast<int *>(smem);
-        uint8_t *P = smem + (size_t)dir_cap * 4 * WfStore<OffT, ADAPT>::kDirInts;
-        uint8_t *T = P + seqp;
+        uint8_t *P = smem + (size_t)dir_cap * 4 * WfStore<OffT, ADAPT>::kDirInts, *T = P + seqp;
         // the backtrace never looks at the strings (affine_wavefronts_backtrace_matches__check only counts), so their
         // LDS region doubles as the CIGAR buffer: plen + tlen <= seqp + seqt bytes
         char *opsbuf = reinterpret_cast<char *>(P);
         OffT *pool = reinterpret_cast<OffT *>(T + seqt);
         const int plen = io.pat_len[id], tlen = io.txt_len[id];
-        const char *gp = io.pat + io.pat_off[id], *gt = io.txt + io.txt_off[id];
-        // four bytes per lane and step (the LDS copies are dword-aligned and have room to the next multiple of four)
-        const int pend = (int)((io.pat_off[id] + plen) & 3), tend = (int)((io.txt_off[id] + tlen) & 3);
-        for (int i = 4 * lane; i < plen + kSeqPad; i += 4 * G) *reinterpret_cast<uint32_t *>(P + i) = seq_ld4(gp, i, plen, (uint32_t)'X', pend);
-        for (int i = 4 * lane; i < tlen + kSeqPad; i += 4 * G) *reinterpret_cast<uint32_t *>(T + i) = seq_ld4(gt, i, tlen, (uint32_t)'Y', tend);
+        (void)wfa_stage<G>(io, id, P, plen, T, tlen, lane);     // (wfa_pair looks beyond the strings' ends as the reference does: no probe)
         __syncthreads();
         WfStore<OffT, ADAPT> st;
         st.pool = pool; st.dir = dir; st.pool_cap = pool_cap; st.dir_cap = dir_cap; st.used = 0;
@@ -520,24 +538,7 @@ __global__ __launch_bounds__(64) void wfa_lds(WfaIO io, WfaPen pen, const uint32
     if (threadIdx.x == 0 && work_all) atomicAdd(wfa_work_slot(ct), work_all);
 }
 
-
-// ---- complete mode, first tier: the directory as a table of the penalties ------------------------------------------
-// Without the adaptive reduction nothing in a pair's directory depends on the data: whether M / I / D of a score exist,
-// their [lo, hi] (min / max of the sources' -1 / +1) and where they land in the pool (allocation in score order) follow
-// from the penalties alone.  gab_wfa_create lists one WfRow per score that has a wavefront, with the resolved facts of
-// its three source scores; the kernel then needs no directory in LDS (the room goes to the offset pool), no look-ups and
-// no decoding: all groups of a wave walk the rows in lockstep, so the row index is wave-uniform and the row arrives by
-// scalar loads.  A missing source is an empty range (lo = 1, hi = -1): every read of it is out of range = null.
-struct WfRow {
-    int score, lo, hi, bM, bI, bD, used_end, has_gap;     // bI / bD valid iff has_gap (I and D exist at the same scores)
-    int ms_m, ms_lo, ms_hi;                               // M[score - x]
-    int mg_m, mg_lo, mg_hi;                               // M[score - o - e]
-    int ie_i, ie_d, ie_lo, ie_hi;                         // I / D[score - e]
-    int r_ms, r_mg, r_ie;                                 // rows of the three source scores (0 when there is none)
-    int pad[3];
-};
-static_assert(sizeof(WfRow) == 96, "WfRow is read as dwords");
-
+// ---- complete mode, first tier: the directory as a table of the penalties (WfRow, wfa_table: wfa_plan.h) ----------
 // a workgroup of the LDS kernels is ONE wave: LDS instructions of a wave execute in order, so a store by one lane is seen by a
 // later load of another lane without draining the queue -- only the compiler must not reorder them
 __device__ __forceinline__ void wave_sync() {
@@ -553,25 +554,14 @@ __device__ bool wfa_pair_static(OffB *pool, int pool_cap, const WfRow *__restric
     // r_start > 0: the pool already holds the wavefronts of rows 0 .. r_start - 1 (a smaller tier ran out of room there);
     // resume_row > 0 on a false return: the same for the next tier (rows 0 .. resume_row - 1 are complete in `pool`)
     resume_row = 0;
-    const int lane = threadIdx.x & (G - 1);
-    const int ak = tlen - plen;
+    const int lane = threadIdx.x & (G - 1), ak = tlen - plen;
     if (pool_cap < 1 || nrows < 1) return false;
     auto at = [&](int base, int lo, int hi, int k) { return (lo <= k && k <= hi) ? (int)pool[base + (k - lo)] : kNull; };
-    // affine_wavefronts_extend_mwavefront_compute (the padded strings: affine_wavefront_extend.c:51-83), sixteen bases at a time:
-    // the number of leading bases of P[v ..] and T[h ..] that match, 0 .. 16 (outside the strings 'X' meets 'Y': 0 -- the kernel
-    // keeps pairs that contain the other's padding byte out of this tier; the LDS copies carry kSeqPad bytes of padding)
-    auto match16 = [&](int v, int h) -> int {
-        if (!(v >= 0 && v <= plen && h >= 0 && h <= tlen)) return 0;
-        // one 16-byte LDS read per string at ANY byte address (gfx950 reads LDS unaligned; aligned dwords + v_alignbyte cost
-        // three times the instructions)
-        uint4 a, b;
-        __builtin_memcpy(&a, P + v, 16); __builtin_memcpy(&b, T + h, 16);
-        const uint64_t d8 = ((uint64_t)(a.y ^ b.y) << 32) | (a.x ^ b.x), e8 = ((uint64_t)(a.w ^ b.w) << 32) | (a.z ^ b.z);
-        if ((d8 | e8) == 0) return 16;
-        return d8 ? __builtin_ctzll(d8) >> 3 : 8 + (__builtin_ctzll(e8) >> 3);
-    };
+    // the leading bases of P[v ..] and T[h ..] that match, 0 .. 16 (outside the strings 'X' meets 'Y': 0 -- the kernel keeps
+    // pairs that contain the other's padding byte out of this tier)
+    auto match16 = [&](int v, int h) -> int { return (v >= 0 && v <= plen && h >= 0 && h <= tlen) ? wfa_match16(P + v, T + h) : 0; };
     const int wl = threadIdx.x & 63, gbase = wl & ~(G - 1);
-    const uint64_t group_mask = (G == 64 ? ~0ull : ((1ull << G) - 1)) << gbase;
+    const uint64_t group_mask = wfa_group_mask<G>();
     // Extension of the diagonals of one pass (lane = diagonal k, offset o; `active` lanes only).  Every lane compares the first
     // sixteen bases of its own diagonal; most stop there.  A diagonal that goes on -- usually the one the alignment follows,
     // for ~50 bases -- used to keep its lane looping alone while the others waited; now the G lanes of the group take G
@@ -603,8 +593,7 @@ __device__ bool wfa_pair_static(OffB *pool, int pool_cap, const WfRow *__restric
         extend_all(o, 0, lane == 0);
         if (lane == 0) {
             pool[0] = OffB(o);
-            at_end = ak == 0 && o >= tlen;
-            too_big = o > kOffBSafe;
+            at_end = ak == 0 && o >= tlen; too_big = o > kOffBSafe;
         }
     }
     for (;;) {
@@ -634,8 +623,7 @@ __device__ bool wfa_pair_static(OffB *pool, int pool_cap, const WfRow *__restric
             extend_all(best, k, active);
             if (active) {
                 pool[n.bM + (k - n.lo)] = OffB(best);
-                at_end = at_end || (k == ak && best >= tlen);
-                too_big = too_big || best > kOffBSafe;
+                at_end = at_end || (k == ak && best >= tlen); too_big = too_big || best > kOffBSafe;
             }
         }
         work += (lane == 0) ? (unsigned)(n.hi - n.lo + 1) : 0u;
@@ -643,67 +631,20 @@ __device__ bool wfa_pair_static(OffB *pool, int pool_cap, const WfRow *__restric
     wave_sync();
 
     // ---- backtrace: as in wfa_pair, the directory entries of s - o - e, s - e, s - x being the source fields of row(s)
-    const int cap = plen + tlen;
-    int pos = cap - 1;
-    int k = ak;
-    const int x = pen.x, oe = pen.o + pen.e, e = pen.e;
-    const int score = rows[r].score;
-    {
-        int s = score;
-        int offset = (int)pool[rows[r].bM + (k - rows[r].lo)];
-        int type = 0;                                           // 0 = M, 1 = I, 2 = D
-        auto valid_loc = [&](int kk, int oo) { return oo - kk > 0 && oo - kk <= plen && oo > 0 && oo <= tlen; };
-        bool valid = valid_loc(k, offset);
-        int v = offset - k, h = offset;
-        // the buffer (the strings' LDS, no longer needed) is filled with 'M' once, 16 bytes per lane and store: a run of matches
-        // -- most of the CIGAR -- then only moves the cursor
-        for (int i = 16 * lane; i < cap; i += 16 * G) *reinterpret_cast<uint4 *>(ops + i) = make_uint4(0x4d4d4d4du, 0x4d4d4d4du, 0x4d4d4d4du, 0x4d4d4d4du);
-        wave_sync();
-        auto put = [&](char ch) { if (lane == 0 && pos >= 0) ops[pos] = ch; pos--; };
-        auto put_run = [&](char ch, int cnt) {
-            for (int i = lane; i < cnt && pos - i >= 0; i += G) ops[pos - i] = ch;
-            pos -= cnt > 0 ? cnt : 0;
-        };
-        auto skip_matches = [&](int cnt) { pos -= cnt > 0 ? cnt : 0; };
-        auto in = [&](int lo, int hi, int kk) { return lo <= kk && kk <= hi; };
-        while (v > 0 && h > 0 && s > 0) {
-            if (!valid) {
-                valid = valid_loc(k, offset);
-                if (valid) {
-                    if (k < ak) put_run('I', ak - k);
-                    else if (k > ak) put_run('D', k - ak);
-                }
-            }
-            const WfRow w = rows[r];
-            const int del_ext = type == 1 ? kNull : at(w.ie_d, w.ie_lo, w.ie_hi, k + 1);
-            const int del_open = type == 1 ? kNull : at(w.mg_m, w.mg_lo, w.mg_hi, k + 1);
-            const bool ie_ok = in(w.ie_lo, w.ie_hi, k - 1), io_ok = in(w.mg_lo, w.mg_hi, k - 1), mm_ok = in(w.ms_lo, w.ms_hi, k);
-            const int ins_ext = (type == 2 || !ie_ok) ? kNull : (int)pool[w.ie_i + (k - 1 - w.ie_lo)] + 1;
-            const int ins_open = (type == 2 || !io_ok) ? kNull : (int)pool[w.mg_m + (k - 1 - w.mg_lo)] + 1;
-            const int misms = (type != 0 || !mm_ok) ? kNull : (int)pool[w.ms_m + (k - w.ms_lo)] + 1;
-            const int max_all = max(misms, max(max(ins_ext, ins_open), max(del_ext, del_open)));
-            if (type == 0) { skip_matches(offset - max_all); offset = max_all; }
-            if (max_all == del_ext) { if (valid) put('D'); s -= e; r = w.r_ie; k++; type = 2; }
-            else if (max_all == del_open) { if (valid) put('D'); s -= oe; r = w.r_mg; k++; type = 0; }
-            else if (max_all == ins_ext) { if (valid) put('I'); s -= e; r = w.r_ie; k--; offset--; type = 1; }
-            else if (max_all == ins_open) { if (valid) put('I'); s -= oe; r = w.r_mg; k--; offset--; type = 0; }
-            else { if (valid) put('X'); s -= x; r = w.r_ms; offset--; }
-            v = offset - k; h = offset;
-        }
-        if (s == 0) skip_matches(offset);
-        else { put_run('D', v); put_run('I', h); }
-    }
-    // (writes in front of the buffer were dropped: a CIGAR longer than plen + tlen -- a sequence matching the other's padding
-    // byte beyond its end, where the reference overflows its buffer -- keeps its last plen + tlen operations)
-    pos = max(pos, -1) + 1;
+    const int cap = plen + tlen, score = rows[r].score, offset = (int)pool[rows[r].bM + (ak - rows[r].lo)];
+    // the buffer (the strings' LDS, no longer needed) is filled with 'M' once, 16 bytes per lane and store: a run of matches
+    // -- most of the CIGAR -- then only moves the cursor
+    for (int i = 16 * lane; i < cap; i += 16 * G) *reinterpret_cast<uint4 *>(ops + i) = make_uint4(0x4d4d4d4du, 0x4d4d4d4du, 0x4d4d4d4du, 0x4d4d4d4du);
+    wave_sync();
+    auto sources = [&](int, int row, WfSrc &mm, WfSrc &go, WfSrc &gi, WfSrc &gd) {      // the source fields of the row
+        const WfRow &w = rows[row];
+        mm = {w.ms_m, w.ms_lo, w.ms_hi}; go = {w.mg_m, w.mg_lo, w.mg_hi}; gi = {w.ie_i, w.ie_lo, w.ie_hi}; gd = {w.ie_d, w.ie_lo, w.ie_hi};
+    };
+    auto link = [&](int row, int to) { return to == 0 ? rows[row].r_ms : to == 1 ? rows[row].r_mg : rows[row].r_ie; };
+    const int pos = wfa_backtrace<G>(pool, sources, link, [](int &at, int cnt) { at -= cnt > 0 ? cnt : 0; }, ops, pen, plen, tlen, score, r, offset, lane);
     const int nops = cap - pos;
     wave_sync();
-    // the CIGAR leaves the CU four bytes per lane and store (unaligned LDS read, unaligned global store), its last 0 .. 3 bytes singly
-    {
-        const int n4 = nops & ~3;
-        for (int i = 4 * lane; i < n4; i += 4 * G) { uint32_t w4; __builtin_memcpy(&w4, ops + pos + i, 4); __builtin_memcpy(ops_global + i, &w4, 4); }
-        if (lane < nops - n4) ops_global[n4 + lane] = ops[pos + n4 + lane];
-    }
+    wfa_copy_out<G>(ops_global, ops + pos, nops, lane);
     if (lane == 0) { *ops_len_out = nops; *score_out = score; }
     return true;
 }
@@ -712,6 +653,7 @@ __device__ bool wfa_pair_static(OffB *pool, int pool_cap, const WfRow *__restric
 // What a static tier leaves behind for a pair it ran out of room for: the row to resume at and the work done so far; the pool
 // bytes (rows 0 .. row - 1, the same layout in every static tier) sit in a slot of `save_pool`.  row = 0: start over.
 struct WfResume { int32_t row; uint32_t pad; unsigned long long work; };
+static_assert(sizeof(WfResume) == kResumeHdrBytes, "wfa_plan.h sizes the resume headers");
 
 template <int G, bool CHAINED>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 7))) void wfa_lds_static(WfaIO io, WfaPen pen, const uint32_t *__restrict__ list, uint32_t count,
@@ -737,22 +679,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 7))) void
         uint8_t *P = smem_all + (size_t)grp * group_bytes, *T = P + seqp;
         OffB *pool = reinterpret_cast<OffB *>(T + seqt);
         const int plen = io.pat_len[id], tlen = io.txt_len[id];
-        const char *gp = io.pat + io.pat_off[id], *gt = io.txt + io.txt_off[id];
         // A pattern byte 'Y' or a text byte 'X' could match the OTHER string's padding outside the strings; wfa_pair_static
         // does not look there, so such a pair (never a DNA read) goes to the general kernel.
-        auto has_byte = [](uint32_t w, uint32_t c) { const uint32_t x = w ^ (c * 0x01010101u); return ((x - 0x01010101u) & ~x & 0x80808080u) != 0; };
-        bool pad_byte = false;
-        const int pend = (int)((io.pat_off[id] + plen) & 3), tend = (int)((io.txt_off[id] + tlen) & 3);
-        for (int i = 4 * lane; i < plen + kSeqPad; i += 4 * G) {
-            const uint32_t w = seq_ld4(gp, i, plen, (uint32_t)'X', pend);
-            *reinterpret_cast<uint32_t *>(P + i) = w;
-            pad_byte = pad_byte || has_byte(w, 'Y');
-        }
-        for (int i = 4 * lane; i < tlen + kSeqPad; i += 4 * G) {
-            const uint32_t w = seq_ld4(gt, i, tlen, (uint32_t)'Y', tend);
-            *reinterpret_cast<uint32_t *>(T + i) = w;
-            pad_byte = pad_byte || has_byte(w, 'X');
-        }
+        const bool pad_byte = wfa_stage<G>(io, id, P, plen, T, tlen, lane);
         // a pair the previous static tier ran out of room for continues where it stopped: its wavefronts come back from the slot
         int r_start = 0;
         if (CHAINED && in_hdr && b < in_slots) {
@@ -765,7 +694,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 7))) void
                 if (lane == 0) work = hd.work;
             }
         }
-        const uint64_t gm = (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1)) << (threadIdx.x & 63 & ~(G - 1));
+        const uint64_t gm = wfa_group_mask<G>();
         wave_sync();
         int resume_row = 0;
         // wfa_pair_static fetches its rows by scalar loads: the row index must be the same in every group that is inside it
@@ -833,11 +762,11 @@ using WfaLdsKernel = void (*)(WfaIO, WfaPen, const uint32_t *, uint32_t, const u
 // the LDS kernel for G lanes per pair; byte_offsets: the one-byte history of the first tier
 WfaLdsKernel wfa_lds_kernel(int G, bool adaptive, bool byte_offsets) {
 #define GAB_WFA_K(g) (byte_offsets ? (adaptive ? wfa_lds<g, true, OffB> : wfa_lds<g, false, OffB>) : (adaptive ? wfa_lds<g, true, int16_t> : wfa_lds<g, false, int16_t>))
-    return G == 8 ? GAB_WFA_K(8) : G == 16 ? GAB_WFA_K(16) : G == 32 ? GAB_WFA_K(32) : GAB_WFA_K(64);
+    return G == 16 ? GAB_WFA_K(16) : GAB_WFA_K(64);
 #undef GAB_WFA_K
 }
 bool wfa_lds_allow_big() {
-    for (int G : {8, 16, 32, 64})
+    for (int G : {16, 64})
         for (int a = 0; a < 2; a++)
             for (int b = 0; b < 2; b++)
                 if (hipFuncSetAttribute((const void *)wfa_lds_kernel(G, a != 0, b != 0), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
@@ -959,63 +888,13 @@ extern "C" int gab_wfa_create_reduced(const gab_wfa_penalties *p, int min_wavefr
         !wfa_lds_allow_big()) {
         gab_set_error("gab_wfa_create: pinned allocation / LDS attribute failed"); delete h; return GAB_EDEVICE;
     }
-    {   // scores that have a wavefront: M[s] exists iff M[s-x], M[s-o-e], I[s-e] or D[s-e] does; I[s] / D[s] iff M[s-o-e] or
-        // I[s-e] / D[s-e] does (affine_wavefront_align.c:283-321) -- no data involved
-        constexpr int kSteps = 1024;                      // >= the largest LDS directory
-        const int x = h->pen.x, oe = h->pen.o + h->pen.e, e = h->pen.e;
-        std::vector<uint8_t> m(kSteps + 1, 0), g(kSteps + 1, 0), step(kSteps, 1);
-        m[0] = 1;
-        for (int sc = 1; sc <= kSteps; sc++) {
-            g[sc] = (sc >= oe && m[sc - oe]) || (sc >= e && g[sc - e]);
-            m[sc] = (sc >= x && m[sc - x]) || g[sc];
-        }
-        int next = kSteps + 255;
-        for (int sc = kSteps - 1; sc >= 0; sc--) {
-            if (m[sc + 1]) next = sc + 1;
-            step[sc] = (uint8_t)std::min(next - sc, 255);
-        }
-        if (h->steps.reserve(kSteps) != GAB_OK || hipMemcpy(h->steps.p, step.data(), kSteps, hipMemcpyHostToDevice) != hipSuccess) {
-            gab_set_error("gab_wfa_create: score-step table upload failed"); gab_wfa_destroy(h); return GAB_EDEVICE;
-        }
-    }
-    if (!h->adaptive) {
-        // the same DP with ranges and pool positions: what wfa_pair would write into its directory, pair after pair
-        // (affine_wavefront_align.c:85-106 compute_limits, :56-84 allocate_wavefronts, :283-321)
-        constexpr int kMaxRows = 240, kMaxScore = 1024;
-        struct Ent { bool m = false, g = false; int lo = 1, hi = -1, bm = 0, bi = 0, bd = 0, row = 0; };
-        std::vector<Ent> ent(kMaxScore + 1);
-        std::vector<WfRow> rows;
-        const int x = h->pen.x, oe = h->pen.o + h->pen.e, e = h->pen.e;
-        ent[0].m = true; ent[0].lo = ent[0].hi = 0; ent[0].bm = 0; ent[0].row = 0;
-        WfRow r0; memset(&r0, 0, sizeof r0);
-        r0.used_end = 1; r0.ms_lo = r0.mg_lo = r0.ie_lo = 1; r0.ms_hi = r0.mg_hi = r0.ie_hi = -1;
-        rows.push_back(r0);
-        int used = 1;
-        const Ent none;
-        for (int sc = 1; sc <= kMaxScore && (int)rows.size() < kMaxRows; sc++) {
-            const Ent &ms = sc >= x ? ent[sc - x] : none, &mg = sc >= oe ? ent[sc - oe] : none, &ie = sc >= e ? ent[sc - e] : none;
-            const bool n_ms = !ms.m, n_mg = !mg.m, n_ie = !ie.g;
-            if (n_ms && n_mg && n_ie) continue;
-            Ent &t = ent[sc];
-            t.lo = std::min(std::min(n_ms ? 1 : ms.lo, n_mg ? 1 : mg.lo), n_ie ? 1 : ie.lo) - 1;
-            t.hi = std::max(std::max(n_ms ? -1 : ms.hi, n_mg ? -1 : mg.hi), n_ie ? -1 : ie.hi) + 1;
-            const int width = t.hi - t.lo + 1;
-            t.m = true; t.g = !n_mg || !n_ie;
-            t.bm = used; t.bi = used + width; t.bd = used + 2 * width;
-            used += width * (t.g ? 3 : 1);
-            if (used > 60000 || t.lo < -120 || t.hi > 120) break;
-            t.row = (int)rows.size();
-            WfRow r; memset(&r, 0, sizeof r);
-            r.score = sc; r.lo = t.lo; r.hi = t.hi; r.bM = t.bm; r.bI = t.bi; r.bD = t.bd; r.used_end = used; r.has_gap = t.g;
-            r.ms_m = n_ms ? 0 : ms.bm; r.ms_lo = n_ms ? 1 : ms.lo; r.ms_hi = n_ms ? -1 : ms.hi; r.r_ms = n_ms ? 0 : ms.row;
-            r.mg_m = n_mg ? 0 : mg.bm; r.mg_lo = n_mg ? 1 : mg.lo; r.mg_hi = n_mg ? -1 : mg.hi; r.r_mg = n_mg ? 0 : mg.row;
-            r.ie_i = n_ie ? 0 : ie.bi; r.ie_d = n_ie ? 0 : ie.bd; r.ie_lo = n_ie ? 1 : ie.lo; r.ie_hi = n_ie ? -1 : ie.hi; r.r_ie = n_ie ? 0 : ie.row;
-            rows.push_back(r);
-        }
-        h->nrows = (int)rows.size();
-        if (h->rows.reserve(sizeof(WfRow) * rows.size()) != GAB_OK ||
-            hipMemcpy(h->rows.p, rows.data(), sizeof(WfRow) * rows.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            gab_set_error("gab_wfa_create: directory table upload failed"); gab_wfa_destroy(h); return GAB_EDEVICE;
+    {   // what the penalties alone decide (wfa_plan.h): the score steps of every kernel, and in complete mode the directory rows
+        const WfaTable t = wfa_table(h->pen.x, h->pen.o, h->pen.e);
+        const size_t row_bytes = h->adaptive ? 0 : sizeof(WfRow) * t.rows.size();
+        h->nrows = h->adaptive ? 0 : (int)t.rows.size();
+        if (h->steps.reserve(t.step.size()) != GAB_OK || hipMemcpy(h->steps.p, t.step.data(), t.step.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            (row_bytes && (h->rows.reserve(row_bytes) != GAB_OK || hipMemcpy(h->rows.p, t.rows.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess))) {
+            gab_set_error("gab_wfa_create: score table upload failed"); gab_wfa_destroy(h); return GAB_EDEVICE;
         }
     }
     *out = h;
@@ -1029,6 +908,30 @@ extern "C" void gab_wfa_destroy(gab_wfa *h) {
     for (int k = 0; k < 4; k++) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     if (h->h_ct) (void)hipHostFree(h->h_ct);
     delete h;
+}
+
+// One round of the global-history kernel over `list`, what overflows it to `spill` (counted in n_over).  count_ptr: the count is
+// on the device (what the last LDS tier left): a few workgroups with the history room the handle already has.  Else `count` pairs
+// in as many workgroups as the budget holds.
+static int wfa_global_round(gab_wfa *h, hipStream_t s, const WfaIO &io, WfaCounters *d_ct, const WfaLaunch &l, const uint32_t *list,
+                            uint32_t count, const uint32_t *count_ptr, uint32_t *spill) {
+    const int64_t per_block = wfa_global_ints(l);
+    const int64_t fit = (int64_t)(h->scratch.cap / ((size_t)per_block * 4));
+    int64_t blocks = count_ptr ? 16 : std::min<int64_t>(std::min<int64_t>(count, std::max<int64_t>(1, (int64_t)(h->scratch_budget / 4) / per_block)), 2048);
+    // what is already there (gab_wfa_reserve) is used as it is when it holds 64 workgroups' histories or more (count on the
+    // device: any, up to 64): an allocation here stalls every stream of the device for milliseconds (the workgroups stride over
+    // the pairs anyway)
+    if (fit >= (count_ptr ? 1 : 64)) blocks = std::min<int64_t>(count_ptr ? 64 : blocks, fit);
+    if ((size_t)per_block * 4 > h->scratch_budget) {
+        gab_set_error("gab_wfa_run_device: a pair needs more than %zu bytes of wavefront history", h->scratch_budget);
+        return GAB_ENOMEM;
+    }
+    if (int rc = h->scratch.reserve((size_t)per_block * 4 * blocks)) return rc;
+    GAB_HIP(hipMemsetAsync(&d_ct->n_over, 0, 4, s));
+    hipLaunchKernelGGL(l.adaptive ? wfa_global<true> : wfa_global<false>, dim3((unsigned)blocks), dim3(64), 0, s, io, h->pen, list, count, count_ptr,
+                       h->scratch.as<int32_t>(), per_block, (int)l.dir, (int)l.pool, spill, d_ct);
+    GAB_HIP(hipGetLastError());
+    return GAB_OK;
 }
 
 extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes, const int64_t *pat_off,
@@ -1052,6 +955,7 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
     uint32_t *l_a = (uint32_t *)(base + o_l0), *l_b = (uint32_t *)(base + o_l1), *l_big = (uint32_t *)(base + o_l2);
     WfaIO io{pat, pat_off, pat_len, txt, txt_off, txt_len, pat_bytes, txt_bytes, n, ops_out, ops_off, ops_len_out, score_out};
 
+    // ---- step 1, classify: validate, count the pairs per path, the longest strings of the LDS path
     GAB_HIP(hipEventRecord(h->ev[0], s));
     memset(h->h_ct, 0, sizeof(WfaCounters));
     h->h_ct->first_bad = 0x7fffffff;
@@ -1068,158 +972,71 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
         return GAB_EINVAL;
     }
     const uint32_t n_lds = h->h_ct->n_lds, n_big = h->h_ct->n_big;
-    const int seqp = ((h->h_ct->max_plen + kSeqPad + 8) + 15) & ~15, seqt = ((h->h_ct->max_tlen + kSeqPad + 8) + 15) & ~15;
-    int64_t requeued = 0;
+
+    // ---- step 2, plan: the launches up to the first wfa_global, as data (wfa_plan.h)
+    const WfaPlan plan = wfa_plan(h->adaptive, h->nrows, h->h_ct->max_plen, h->h_ct->max_tlen, n_lds, {h->tun.wfa_no_static, h->tun.wfa_pool2, h->tun.wfa_slots});
     // GAB_WFA_TRACE: one record per launch, printed after the call's last synchronisation.  in_tier / left_tier >= 0: the count is
     // tier_over[that index] (read back with the counters anyway), in_tier = -2: all eligible pairs, left_tier = -2: n_over
     const bool trace = h->tun.wfa_trace;
-    struct TraceLaunch { char kernel[40]; long long pool, dir, in, left, resumed; int in_tier, left_tier; };
+    int64_t requeued = 0;
+    struct TraceLaunch { WfaLaunch l; long long in, left, resumed; int in_tier, left_tier; };
     std::vector<TraceLaunch> tl;
     std::vector<WfResume> tl_hdr;                            // the first static launch's hand-over headers (trace only)
-    auto note = [&](const char *templ, int g, const char *a, const char *b, long long pool, long long dir, int in_tier, int left_tier, long long in) {
-        TraceLaunch t; memset(&t, 0, sizeof t);
-        if (g) snprintf(t.kernel, sizeof t.kernel, "%s<%d,%s%s%s>", templ, g, a, *b ? "," : "", b);
-        else snprintf(t.kernel, sizeof t.kernel, "%s<%s>", templ, a);
-        t.pool = pool; t.dir = dir; t.in = in; t.left = -1; t.resumed = -1; t.in_tier = in_tier; t.left_tier = left_tier;
-        tl.push_back(t);
-    };
-
+    auto note = [&](const WfaLaunch &l, int in_tier, int left_tier, long long in) { if (trace) tl.push_back({l, in, -1, -1, in_tier, left_tier}); };
     GAB_HIP(hipEventRecord(h->ev[1], s));
-    // LDS passes: (1) four pairs per wave with one-byte offsets -- complete mode: wfa_lds_static with a ~1.5 K and then a 3 K
-    // history; adaptive mode: wfa_lds<16, OffB> with its directory in LDS; int16 offsets in a 2 KB pool when the strings are
-    // too long for bytes -- (2) one pair per wave with 12 KB of int16 offsets, (3) one pair per wave with 96 KB; whatever
-    // overflows goes to global memory
     if (n_big) hipLaunchKernelGGL(wfa_scatter, dim3(grid), dim3(256), 0, s, io, d_ct->cursors, l_a, l_big);
     uint32_t *cur = n_big ? l_a : nullptr, *nxt = l_b;      // nullptr: identity
-    uint32_t cnt = n_lds;
-    bool ev2 = false;
-    int pool_bytes[3] = {2 * 1024, 12 * 1024, 96 * 1024};
-    int dir_caps[3] = {48, 128, 640};
-    int groups[3] = {16, 64, 64};
-    int byte_tier = 1;
-    const bool tuned = h->tun.wfa_tuned;                    // GAB_WFA_TUNE: tuning runs only
-    if (tuned) {
-        int *dst[7] = {&pool_bytes[0], &dir_caps[0], &pool_bytes[1], &dir_caps[1], &groups[0], &groups[1], &byte_tier};
-        for (int k = 0; k < h->tun.wfa_tune_fields && k < 7; k++) *dst[k] = h->tun.wfa_tune[k];
+    WfResume *d_hdr = nullptr; uint8_t *d_slots = nullptr;  // the resume slots: a header per pair, a first-launch pool per slot
+    const uint32_t slot_bytes = (uint32_t)plan.static_pool;
+    if (plan.resume) {
+        if ((rc = h->scratch.reserve(wfa_resume_bytes(n_lds, plan.slots, slot_bytes))) != GAB_OK) return rc;
+        d_hdr = (WfResume *)h->scratch.as<char>(); d_slots = (uint8_t *)h->scratch.as<char>() + wfa_resume_hdr_bytes(n_lds);
     }
-    // First tier with one-byte offsets (OffB) when no offset can leave the byte's range: text length + one per score step.
-    // Its LDS is budgeted per pair: 2496 B = 10 032 B per wave of four pairs = 16 waves per CU, the measured optimum (the
-    // next allocation step down, 14 waves, costs 9 %; 18-20 waves with a smaller history re-queue too many pairs).  In
-    // complete mode the history a pair needs is a function of its score alone (lo / hi do not depend on the data), so the
-    // directory is sized to the scores the pool can hold: 56 scores, ~1.9 K offsets.
-    bool byte_ok = byte_tier != 0;
-    if (byte_ok && !(tuned && byte_tier > 1)) {
-        dir_caps[0] = h->adaptive ? 48 : 56;
-        const int room = 2496 - dir_caps[0] * (h->adaptive ? 16 : 4) - (seqp + seqt);
-        if (room < 1024) byte_ok = false;
-        byte_tier = std::min(room & ~15, 2032);
-    }
-    if (byte_ok && h->h_ct->max_tlen + dir_caps[0] + 2 > kOffBMax) byte_ok = false;
-    if (!byte_ok && !tuned) dir_caps[0] = 48;
-    // complete mode: the first tier takes its directory from the penalties' table (wfa_pair_static) -- no directory in LDS
-    const int static_rows = std::min(h->nrows, kOffBMax - 2 - h->h_ct->max_tlen);
-    // LDS per pair of the first launch: 1568 B = 6272 B per wave of four = 24 waves per CU, six per SIMD (the kernel is
-    // compiled for seven: 65 VGPRs, no scratch; six would do), i.e. ~1.2 K offsets behind two 151-bp strings = scores below 44 = 96 % of the
-    // pairs.  Measured: 1 520 offsets at 20 waves 382 M/s, 1 344 at 23 waves 391, 1 088-1 184 at 24 waves 405; the history a
-    // pair needs steps with its score, so 1 216-1 312 offsets buy nothing over 1 184 and cost a wave.
-    const int static_pool = tuned && byte_tier > 1 ? byte_tier : std::min(1568 - (seqp + seqt), 4080) & ~15;
-    const bool use_static = !h->adaptive && byte_tier != 0 && !h->tun.wfa_no_static && (groups[0] == 16 || groups[0] == 8) && static_rows >= 16 && static_pool >= 1024;
-    // The tiers are launched back to back: tier k + 1 reads the number of pairs tier k left ON THE DEVICE and is sized by an
-    // estimate (its waves stride over whatever there is), so the host looks at the counters once, after the last LDS tier
-    // (three round trips of ~30 us less per call: 0.56 -> 0.46 ms per 100 k pairs, 2.65 -> 2.55 ms per 1 M).
+    // ---- step 3, the LDS tiers, launched back to back: tier k + 1 reads the number of pairs tier k left ON THE DEVICE and is
+    // sized by an estimate (its waves stride over whatever there is), so the host looks at the counters once, after the last
+    // LDS tier (three round trips of ~30 us less per call: 0.56 -> 0.46 ms per 100 k pairs, 2.65 -> 2.55 ms per 1 M).
     int tier = 0;                                            // LDS tiers launched so far
-    const uint32_t cnt0 = cnt;
-    auto next_grid = [&](double share, uint32_t per_wave, uint32_t floor_) {   // waves for a tier behind another one
-        const uint32_t est = (uint32_t)((double)cnt0 * share) / per_wave + 1;
-        return std::max<uint32_t>(std::min<uint32_t>(est, (cnt0 + per_wave - 1) / per_wave), std::min<uint32_t>(floor_, (cnt0 + per_wave - 1) / per_wave));
-    };
-    auto after_launch = [&]() {
+    bool ev2 = false;
+    for (const WfaLaunch &l : plan.launches) {
+        if (l.kind == kWfaGlobal) break;
+        const dim3 blocks(wfa_launch_grid(l, n_lds));
+        const size_t lds = wfa_lds_bytes(l.kind, l.G, l.dir, l.group_bytes);
+        const uint32_t *cptr = l.chained ? &d_ct->tier_over[tier - 1] : nullptr;
+        if (l.kind == kWfaLdsStatic) {                      // the first writes the resume slots, the chained one reads them
+            const bool rd = l.chained;
+            auto kern = rd ? wfa_lds_static<16, true> : wfa_lds_static<16, false>;
+            hipLaunchKernelGGL(kern, blocks, dim3(64), lds, s, io, h->pen, cur, n_lds, cptr,
+                               plan.seqp, plan.seqt, (int)l.pool, (uint32_t)l.group_bytes, nxt, &d_ct->tier_over[tier], d_ct, h->rows.as<WfRow>(), (int)l.dir,
+                               rd ? (const WfResume *)d_hdr : nullptr, rd ? (const uint8_t *)d_slots : nullptr, plan.slots, slot_bytes,
+                               rd ? nullptr : d_hdr, rd ? nullptr : d_slots, plan.slots, slot_bytes);
+        } else
+            hipLaunchKernelGGL(wfa_lds_kernel(l.G, l.adaptive, l.off_bytes == 1), blocks, dim3(64), lds, s, io, h->pen, cur, n_lds, cptr, (int)l.dir,
+                               plan.seqp, plan.seqt, (int)l.pool, (uint32_t)l.group_bytes, nxt, &d_ct->tier_over[tier], d_ct, h->steps.as<uint8_t>());
+        GAB_HIP(hipGetLastError());
+        if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
+        note(l, tier ? tier - 1 : -2, tier, n_lds);
+        if (trace && l.kind == kWfaLdsStatic) {
+            if (!l.chained && plan.resume && plan.slots) {  // the headers before a later kernel reuses the scratch buffer
+                tl_hdr.resize(plan.slots);
+                GAB_HIP(hipMemcpyAsync(tl_hdr.data(), d_hdr, sizeof(WfResume) * plan.slots, hipMemcpyDeviceToHost, s));
+                GAB_HIP(hipStreamSynchronize(s));
+            }
+            if (l.chained) tl.back().resumed = 0;
+        }
         if (cur) std::swap(cur, nxt);
         else { cur = nxt; nxt = l_a; }                      // the identity pass: its overflow list becomes the input
         tier++;
-    };
-    const double shares[4] = {1.0, 0.10, 0.02, 0.005};       // expected share of the batch that reaches tier k (151-bp reads at 2 %: 4 %, 0.07 %, ~0)
-    if (cnt && use_static) {
-        // two launches: the small pool takes 96 % of the 151-bp pairs at 24 waves per CU, a 2.5 KB pool the scores up to ~64 of
-        // the rest (measured: 2048-2560 B best, 4080 B 4 % slower)
-        int static_pool2 = 2560;
-        if (h->tun.wfa_pool2 >= 0) static_pool2 = h->tun.wfa_pool2;      // GAB_WFA_POOL2
-        const int pools[2] = {static_pool, static_pool2};
-        // the first launch leaves the wavefronts of the pairs it ran out of room for in slots of the scratch buffer and the second
-        // continues them (the pool layout is the table's in both): it does not repeat the ~40 score steps they had come
-        const bool two = pools[1] > pools[0];
-        // (a multiple of the pairs per wave, so that the boundary between resumed and restarted pairs falls between waves;
-        // the kernel copes with a mixed wave anyway.  GAB_WFA_SLOTS: tests force the boundary into a wave.)
-        uint32_t slots = two ? (uint32_t)std::min<uint64_t>(cnt, std::max<uint64_t>(65536, cnt / 8)) & ~7u : 0;
-        if (h->tun.wfa_slots >= 0 && two) slots = (uint32_t)std::min<uint64_t>(cnt, (uint64_t)h->tun.wfa_slots);      // GAB_WFA_SLOTS
-        const size_t o_slots = ((size_t)sizeof(WfResume) * cnt + 255) & ~(size_t)255;
-        WfResume *d_hdr = nullptr; uint8_t *d_slots = nullptr;
-        if (two) {
-            if ((rc = h->scratch.reserve(o_slots + (size_t)slots * pools[0])) != GAB_OK) return rc;
-            d_hdr = (WfResume *)h->scratch.as<char>(); d_slots = (uint8_t *)h->scratch.as<char>() + o_slots;
-        }
-        for (int k = 0; k < 2; k++) {
-            if (k == 1 && !two) break;
-            const size_t per_group = (size_t)(seqp + seqt) + pools[k];
-            const uint32_t per_wave = groups[0] == 8 ? 8 : 4;
-            const uint32_t blocks = tier == 0 ? (cnt + per_wave - 1) / per_wave : next_grid(shares[std::min(tier, 3)], per_wave, 256);
-            const uint32_t *cptr = tier == 0 ? nullptr : &d_ct->tier_over[tier - 1];
-            auto kern = groups[0] == 8 ? (tier ? wfa_lds_static<8, true> : wfa_lds_static<8, false>) : (tier ? wfa_lds_static<16, true> : wfa_lds_static<16, false>);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), per_group * per_wave, s, io, h->pen, cur, cnt, cptr, seqp, seqt, pools[k],
-                               (uint32_t)per_group, nxt, &d_ct->tier_over[tier], d_ct, h->rows.as<WfRow>(), static_rows,
-                               k == 1 ? (const WfResume *)d_hdr : nullptr, k == 1 ? (const uint8_t *)d_slots : nullptr, slots, (uint32_t)pools[0],
-                               k == 0 ? d_hdr : nullptr, k == 0 ? d_slots : nullptr, slots, (uint32_t)pools[0]);
-            GAB_HIP(hipGetLastError());
-            if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
-            if (trace) {
-                note("wfa_lds_static", groups[0] == 8 ? 8 : 16, tier ? "true" : "false", "", pools[k], static_rows, tier ? tier - 1 : -2, tier, cnt);
-                if (k == 0 && two && slots) {               // the headers before a later kernel reuses the scratch buffer
-                    tl_hdr.resize(slots);
-                    GAB_HIP(hipMemcpyAsync(tl_hdr.data(), d_hdr, sizeof(WfResume) * slots, hipMemcpyDeviceToHost, s));
-                    GAB_HIP(hipStreamSynchronize(s));
-                }
-                if (k == 1) tl.back().resumed = 0;
-            }
-            after_launch();
-        }
     }
-    for (int pass = use_static ? 1 : 0; pass < 3 && cnt; pass++) {
-        const int dir_cap = dir_caps[pass], G = groups[pass];
-        const bool bytes = pass == 0 && byte_ok;
-        if (bytes) pool_bytes[0] = std::min(byte_tier, 2046);
-        const size_t per_group = (((size_t)dir_cap * (h->adaptive ? 16 : bytes ? 4 : 12) + (size_t)(seqp + seqt) + pool_bytes[pass]) + 15) & ~(size_t)15;
-        const size_t lds = per_group * (64 / G) + (((size_t)dir_cap + 15) & ~(size_t)15);
-        if (lds > 160 * 1024 - 512) continue;            // sequences too long for this pool: let the next stage take them
-        const uint32_t per_wave = 64 / G;
-        const uint32_t blocks = tier == 0 ? (cnt + per_wave - 1) / per_wave : next_grid(shares[std::min(tier, 3)], per_wave, pass == 2 ? 64 : 256);
-        const uint32_t *cptr = tier == 0 ? nullptr : &d_ct->tier_over[tier - 1];
-        WfaLdsKernel kern = wfa_lds_kernel(G, h->adaptive, bytes);
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, s, io, h->pen, cur, cnt, cptr, dir_cap, seqp, seqt,
-                           pool_bytes[pass] / (bytes ? 1 : 2), (uint32_t)per_group, nxt, &d_ct->tier_over[tier], d_ct, h->steps.as<uint8_t>());
-        GAB_HIP(hipGetLastError());
-        if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
-        if (trace) note("wfa_lds", G, h->adaptive ? "true" : "false", bytes ? "OffB" : "int16_t", pool_bytes[pass] / (bytes ? 1 : 2), dir_cap, tier ? tier - 1 : -2, tier, cnt);
-        after_launch();
-    }
-    // r04: what the last LDS tier leaves (almost never anything) goes to the global-history kernel WITHOUT asking the device how
-    // many pairs that is: one launch of a few workgroups that reads the count itself, with the history room the handle already
-    // has; the host looks at the counters once, at the end of the call, and only continues (a bigger pool) for pairs that
-    // overflowed even that.  One round trip of ~40 us less per call.
-    bool first_global_done = false;
-    if (tier && cnt) {
-        const int64_t pool_cap0 = 1 << 20, dir_cap0 = 4096;
-        const int64_t per_block0 = dir_cap0 * (h->adaptive ? 7 : 5) + pool_cap0;
-        int blocks0 = 16;
-        if (const int64_t fit = (int64_t)(h->scratch.cap / ((size_t)per_block0 * 4)); fit >= 1) blocks0 = (int)std::min<int64_t>(64, fit);
-        else if ((rc = h->scratch.reserve((size_t)per_block0 * 4 * blocks0)) != GAB_OK) return rc;
-        GAB_HIP(hipMemsetAsync(&d_ct->n_over, 0, 4, s));
-        hipLaunchKernelGGL(h->adaptive ? wfa_global<true> : wfa_global<false>, dim3(blocks0), dim3(64), 0, s, io, h->pen, cur, 0u, (const uint32_t *)&d_ct->tier_over[tier - 1],
-                           h->scratch.as<int32_t>(), per_block0, (int)dir_cap0, (int)pool_cap0, nxt, d_ct);
-        GAB_HIP(hipGetLastError());
-        if (trace) note("wfa_global", 0, h->adaptive ? "true" : "false", "", pool_cap0, dir_cap0, tier - 1, -2, 0);
-        first_global_done = true;
-    }
+    // ---- step 4, the global-history tier.  r04: what the last LDS tier leaves (almost never anything) goes to wfa_global WITHOUT
+    // asking the device how many pairs that is: one launch of a few workgroups that reads the count itself, with the history room
+    // the handle already has; the host looks at the counters once, at the end of the call, and only continues (a bigger pool) for
+    // pairs that overflowed even that.  One round trip of ~40 us less per call.
+    uint32_t cnt = n_lds;
     if (tier) {
+        const WfaLaunch &l = plan.launches.back();
+        if ((rc = wfa_global_round(h, s, io, d_ct, l, cur, 0u, &d_ct->tier_over[tier - 1], nxt)) != GAB_OK) return rc;
+        note(l, tier - 1, -2, 0);
+        // ---- step 5, the counters, once
         hipLaunchKernelGGL(wfa_sum_work, dim3(1), dim3(kWorkSlots), 0, s, d_ct);
         GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(WfaCounters), hipMemcpyDeviceToHost, s));
         if (!ev2) { GAB_HIP(hipEventRecord(h->ev[2], s)); ev2 = true; }
@@ -1231,45 +1048,23 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
             if (t.resumed == 0)
                 for (size_t k = 0; k < tl_hdr.size() && k < h->h_ct->tier_over[0]; k++) t.resumed += tl_hdr[k].row > 0;
         }
-        cnt = first_global_done ? h->h_ct->n_over : h->h_ct->tier_over[tier - 1];
-        if (first_global_done) { requeued += cnt; std::swap(cur, nxt); }      // (what overflowed the first global pass sits in nxt)
+        requeued += cnt = h->h_ct->n_over; std::swap(cur, nxt);      // (what overflowed the first global round sits in nxt)
     }
     if (!ev2) GAB_HIP(hipEventRecord(h->ev[2], s));
-    // pass 3+: global history; first the LDS leftovers, then the long pairs; pool grows on overflow
+    // further rounds: first what the first one left, then the long pairs; the pool grows on overflow
     for (int which = 0; which < 2; which++) {
-        uint32_t *list = which == 0 ? cur : l_big;
-        uint32_t *spill = which == 0 ? nxt : (cur == l_a ? l_b : l_a);
+        uint32_t *list = which == 0 ? cur : l_big, *spill = which == 0 ? nxt : (cur == l_a ? l_b : l_a);
         uint32_t c = which == 0 ? cnt : n_big;
-        int64_t pool_cap = 1 << 20;                       // int32 elements per block
-        int64_t dir_cap = 4096;
-        if (which == 0 && first_global_done) { pool_cap *= 8; dir_cap *= 4; }      // (the first size has been tried)
-        while (c) {
-            int64_t per_block = dir_cap * (h->adaptive ? 7 : 5) + pool_cap;
-            int blocks = (int)std::min<int64_t>(c, std::max<int64_t>(1, (int64_t)(h->scratch_budget / 4) / per_block));
-            blocks = std::min(blocks, 2048);
-            // what is already there (gab_wfa_reserve) is used as it is when it holds 64 workgroups' histories or more: an
-            // allocation here stalls every stream of the device for milliseconds (the workgroups stride over the pairs anyway)
-            if (const int64_t fit = (int64_t)(h->scratch.cap / ((size_t)per_block * 4)); fit >= 64) blocks = (int)std::min<int64_t>(blocks, fit);
-            if ((size_t)per_block * 4 > h->scratch_budget) {
-                gab_set_error("gab_wfa_run_device: a pair needs more than %zu bytes of wavefront history", h->scratch_budget);
-                return GAB_ENOMEM;
-            }
-            rc = h->scratch.reserve((size_t)per_block * 4 * blocks);
-            if (rc) return rc;
-            GAB_HIP(hipMemsetAsync(&d_ct->n_over, 0, 4, s));
-            hipLaunchKernelGGL(h->adaptive ? wfa_global<true> : wfa_global<false>, dim3(blocks), dim3(64), 0, s, io, h->pen, list, c, (const uint32_t *)nullptr, h->scratch.as<int32_t>(),
-                               per_block, (int)dir_cap, (int)pool_cap, spill, d_ct);
-            GAB_HIP(hipGetLastError());
-            if (trace) note("wfa_global", 0, h->adaptive ? "true" : "false", "", pool_cap, dir_cap, -1, -2, c);
+        for (int round = which == 0 && tier ? 1 : 0; c; round++) {      // (with LDS tiers the first size has been tried)
+            const WfaLaunch l = wfa_global_launch(h->adaptive, round, false);
+            if ((rc = wfa_global_round(h, s, io, d_ct, l, list, c, nullptr, spill)) != GAB_OK) return rc;
+            note(l, -1, -2, c);
             hipLaunchKernelGGL(wfa_sum_work, dim3(1), dim3(kWorkSlots), 0, s, d_ct);
             GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(WfaCounters), hipMemcpyDeviceToHost, s));
             GAB_HIP(hipStreamSynchronize(s));
-            c = h->h_ct->n_over;
+            requeued += c = h->h_ct->n_over;
             if (trace) tl.back().left = c;
-            requeued += c;
             std::swap(list, spill);
-            pool_cap *= 8; dir_cap *= 4;
-            if (dir_cap > (1 << 22)) dir_cap = 1 << 22;
         }
     }
     GAB_HIP(hipEventRecord(h->ev[3], s));
@@ -1279,7 +1074,9 @@ extern "C" int gab_wfa_run_device(gab_wfa *h, const char *pat, int64_t pat_bytes
     if (trace) {
         for (size_t k = 0; k < tl.size(); k++) {
             const TraceLaunch &t = tl[k];
-            fprintf(stderr, "[gab_wfa] launch %zu kernel %s pool %lld dir %lld in %lld left %lld", k, t.kernel, t.pool, t.dir, t.in, t.left);
+            char kernel[40];
+            wfa_launch_name(t.l, kernel, sizeof kernel);
+            fprintf(stderr, "[gab_wfa] launch %zu kernel %s pool %lld dir %lld in %lld left %lld", k, kernel, t.l.pool, t.l.dir, t.in, t.left);
             if (t.resumed >= 0) fprintf(stderr, " resumed %lld", t.resumed);
             fputc('\n', stderr);
         }
@@ -1458,11 +1255,11 @@ extern "C" int gab_wfa_reserve(gab_wfa *h, int64_t max_pairs, int64_t max_seq_by
     if ((rc = h->ws.reserve(kCountersBytes + kSlotsBytes + 3 * 4 * nn + 1024)) != GAB_OK) return rc;
     {   // the hand-over slots of the two static tiers (gab_wfa_run_device: headers of all pairs + a pool per slot): 80 MB for a
         // chunk of 2^18 pairs, which the first call of a timed region must not have to allocate and map
-        const size_t slots = std::min<size_t>(nn, std::max<size_t>(65536, nn / 8));
+        const size_t resume = wfa_resume_bytes(nn, wfa_default_slots(nn), kStaticPairBytes);
         // ... nor the first round of the global-history tier (4.3 MB per workgroup; the few pairs per chunk that outgrow the LDS
         // tiers): 64 .. 256 workgroups' worth
-        const size_t global_tier = (size_t)(4096 * (h->adaptive ? 7 : 5) + (1 << 20)) * 4 * std::min<size_t>(256, std::max<size_t>(64, nn / 1024));
-        if ((rc = h->scratch.reserve(std::max(((sizeof(WfResume) * nn + 255) & ~(size_t)255) + slots * 1568, std::min(global_tier, h->scratch_budget)))) != GAB_OK) return rc;
+        const size_t global_tier = (size_t)wfa_global_ints(wfa_global_launch(h->adaptive, 0, true)) * 4 * std::min<size_t>(256, std::max<size_t>(64, nn / 1024));
+        if ((rc = h->scratch.reserve(std::max(resume, std::min(global_tier, h->scratch_budget)))) != GAB_OK) return rc;
     }
     hipStream_t s = nullptr;
     if ((rc = h->hs.get(&s)) != GAB_OK) return rc;
