@@ -970,7 +970,15 @@ __device__ __forceinline__ BswCellOut bsw_cell(int diag, int e, int f, uint32_t 
 // trimming -- the zero trim and, in the score-only form, both prunes are the same evaluation of the four-cell windows next to the
 // two edges (a zero cell is a dropped cell; with `best` taken as 0 the prune's test IS the zero trim), so a lane whose prune is off
 // or whose left edge may not move gets a zero operand instead of a branch.  Only the cell-by-cell loops of a zero trim that has
-// run past its window, the zeroing of dropped cells and the exit's bound pass are divergent regions.
+// run past its window, the predicated zeroing of a band that ends left of column 3, the zero-row guard and the exit's bound pass
+// are divergent regions.
+// The rest of the row tail is straight code (profiles/bsw_row_start.md): every flag is computed for every lane and joined with
+// & and |; `best` and its row and column, the band clamp, the windows' one-cell moves and the next row's left-edge potential are
+// selects or shift counts; the wave-uniform operands of that code (gap penalties, max_sc plain and packed, masks, packed steps)
+// are per-lane copies made once per pair.
+// NOT here, measured and taken out (same document): fetching the next row's first pair words behind the zeroing stores, in two
+// forms -- both removed an LDS wait and both were slower -- and a row loop with one way out (the zero row and the last reference
+// base as operands of `stop`), which cut scalar instructions and was no faster.
 template <bool SYM, bool MS1, bool SO>
 __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec *__restrict__ recs, int64_t kbeg,
                                               int64_t kend, int qcap, int32_t *__restrict__ score_out,
@@ -1027,6 +1035,12 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
         uint32_t k_selz = 0x0c000c00u, k_lo8 = 0x00ff00ffu, v_e_ins = (uint32_t)e_ins;
         uint32_t k_cstep = 512u, k_qstep = 128u, k_jstep = 4u;
         asm volatile("" : "+v"(k_selz), "+v"(k_lo8), "+v"(v_e_ins), "+v"(k_cstep), "+v"(k_qstep), "+v"(k_jstep));
+        // ... and of the code behind the sweep (profiles/bsw_row_start.md): the gap penalties and max_sc as plain and as packed
+        // operands, the masks and the packed steps of the window test.  As SGPRs or literals they were copied into VGPRs every
+        // row (inline assembly takes VGPRs only) or made a 2-cycle instruction a 4-cycle one.
+        int v_e_del = e_del, v_max_sc = c.max_sc, v_zdrop = c.zdrop;
+        uint32_t k_m2 = as_u32(pk_splat(c.max_sc)), k_lo16 = 0x0000ffffu, k_two2 = 0x00020002u, k_hi1 = 0x00010000u, k_254 = 254u, k_256 = 256u;
+        asm volatile("" : "+v"(v_e_del), "+v"(v_max_sc), "+v"(v_zdrop), "+v"(k_m2), "+v"(k_lo16), "+v"(k_two2), "+v"(k_hi1), "+v"(k_254), "+v"(k_256));
         bool prune = SO && (qlen <= w + 1 || h0 - oe_ins - (w + 1) * e_ins <= 0) && (c.zdrop == 0 || c.zdrop >= 8 * c.max_sc);
         int best, best_i, best_j, g_i, gscore, max_off;
       for (;;) {                                            // second trip: a pair one of the guards sent back, prunes off
@@ -1073,10 +1087,13 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             const uint2 rr = *reinterpret_cast<const uint2 *>(&row_tab[2 * (tc < 4 ? tc : 4)]);
             const uint32_t rlo = rr.x, rhi = rr.y;
             if (beg < i - w) beg = i - w;
-            if (end > i + w + 1) { end = i + w + 1; stale_pot = max(stale_pot, best + mul24(c.max_sc, qlen - end)); }
-            if (end > qlen) end = qlen;
-            int hleft = 0;
-            if (beg == 0) hleft = hrow > 0 ? hrow : 0;
+            {                                               // the band clamp: both sides computed, a select keeps one
+                const int ec = i + w + 1;
+                const int sp = max(stale_pot, best + mul24(v_max_sc, qlen - ec));
+                stale_pot = end > ec ? sp : stale_pot;
+                end = min(min(end, ec), qlen);
+            }
+            int hleft = beg == 0 ? max(hrow, 0) : 0;
             int f = 0;
             uint32_t rowpk = 0;                   // (row max << 16) | column; ties -> later column
             int j = beg;
@@ -1202,7 +1219,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             // `end` holds H(i, end - 1), so the candidates kj .. kj + 3 are cells kj + 1 .. kj + 4: pair words
             // (kj + 1) / 2 .. + 2, the last one at most qlen / 2 + 2 -- behind the cell rows come the query nibbles and
             // one spare row, so it is inside the launch's LDS (see lds8 at the launch), and a word past cell `end` is masked.
-            const int kj = (int)(rowpk & 0xffffu);
+            const int kj = (int)(rowpk & k_lo16);
             const int pb = beg >> 1, pe = end >> 1;
             const uint32_t *const rw = CW + ((kj + 1) >> 1) * 64;
             const uint32_t r0 = rw[0], r1 = rw[64], r2 = rw[128];
@@ -1215,7 +1232,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             {
                 const uint32_t sh = (uint32_t)((kj + 1) & 1) << 4;
                 const uint32_t c01 = __builtin_amdgcn_alignbit(r1, r0, sh), c23 = __builtin_amdgcn_alignbit(r2, r1, sh);
-                const uint32_t rm2 = (uint32_t)rowmax * 0x00010001u;
+                const uint32_t rm2 = (uint32_t)rowmax << 16 | (uint32_t)rowmax;
                 // 1 per 16-bit half whose H differs from the row maximum, gathered into bytes 0..3 = candidates 0..3
                 const uint32_t ne = __builtin_amdgcn_perm(pk_min_u16_1((c23 ^ rm2) & 0x00ff00ffu), pk_min_u16_1((c01 ^ rm2) & 0x00ff00ffu),
                                                           0x06040200u);
@@ -1229,32 +1246,35 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             // guard, and the exit's bound last.
             const int rows_left = tlen - 1 - i;
             const bool raised = rowmax > best;
-            bool stop = false;
-            if (c.zdrop > 0) {                              // (wave-uniform)
-                const int di = i - best_i, dj = rowmax_j - best_j;
-                const int gap = di > dj ? mul24(di - dj, e_del) : mul24(dj - di, e_ins);
-                stop = !raised && best - rowmax - gap > c.zdrop;
+            // Every flag below is computed for every lane and joined with & and |, and `best` and its row and column are selects:
+            // a short-circuit form or an `if` around one to five instructions became an exec-mask region each, two scalar
+            // instructions and the wait states in front of them for a lane mask that a v_cndmask takes as it is.
+            const bool zd_on = c.zdrop > 0;                 // (wave-uniform; with zdrop == 0 neither z-drop flag can be set)
+            const bool keeps = !raised;
+            bool stop;
+            {
+                const int di = i - best_i, dj = rowmax_j - best_j, dd = di - dj;
+                const int gap = mul24(dd > 0 ? dd : -dd, dd > 0 ? v_e_del : (int)v_e_ins);
+                stop = zd_on & keeps & (best - rowmax - gap > v_zdrop);
                 if constexpr (SO) {                         // z-drop guard: the reference's row maximum may differ here
-                    abandon = !raised && dropped && rowmax < best - c.zdrop;
-                    stop = stop || abandon;
+                    abandon = zd_on & keeps & dropped & (rowmax < best - v_zdrop);
+                    stop = stop | abandon;
                 }
             }
             // the row maximum's own potential: while it exceeds best no exit is possible and the bound pass is skipped
-            const bool try_exit = SO && !raised && rowmax + mul24(c.max_sc, min(rows_left, qlen - 1 - rowmax_j)) <= best;
-            if (raised) {
-                best = rowmax; best_i = i; best_j = rowmax_j;
-                if constexpr (!SO) {
-                    int off = rowmax_j - i; off = off < 0 ? -off : off;
-                    max_off = off > max_off ? off : max_off;
-                }
+            const bool try_exit = SO & keeps & (rowmax + mul24(v_max_sc, min(rows_left, qlen - 1 - rowmax_j)) <= best);
+            best = max(best, rowmax); best_i = raised ? i : best_i; best_j = raised ? rowmax_j : best_j;
+            if constexpr (!SO) {
+                int off = rowmax_j - i; off = off < 0 ? -off : off;
+                max_off = raised && off > max_off ? off : max_off;
             }
             const int thr = max(best, Lm1);                 // (best is this row's already; only the score-only form reads it)
             if constexpr (SO) {
                 // right-edge guard of the left prune (header comment, step 5); a row that the z-drop test ends does not reach it
-                const bool guard = !stop && dropped && end < qlen && end != i + w + 1 && hleft > e_ins &&
-                                   hleft - e_ins + mul24(c.max_sc, min(rows_left, qlen - end - 1)) > thr;
-                abandon = abandon || guard;
-                stop = stop || guard;
+                const bool guard = !stop & dropped & (end < qlen) & (end != i + w + 1) & (hleft > e_ins) &
+                                   (hleft - (int)v_e_ins + mul24(v_max_sc, min(rows_left, qlen - end - 1)) > thr);
+                abandon = abandon | guard;
+                stop = stop | guard;
             }
             // Band trimming (bandedSWA.cpp:234-237) and, in the score-only form, both prunes (header comment).  The four cells
             // next to either edge are fetched in ONE LDS round trip (whole pair words): x = cells beg0 .. beg0 + 3, y = cells
@@ -1264,10 +1284,11 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
             int edge_pot = 0;
             {
                 const int beg0 = beg, end0 = end;
-                uint64_t x = (uint64_t)b1 << 32 | b0;                      // cells 2pb .. 2pb+3, low half first
-                if (beg0 & 1) x = (x >> 16) | (uint64_t)(b2 & 0xffffu) << 48;
-                uint64_t y = (uint64_t)e2 << 32 | e1;                      // cells 2pe-2 .. 2pe+1; cell `end` goes on top
-                if (!(end0 & 1)) y = (y << 16) | (e0 >> 16);
+                // x: cells 2pb .. 2pb+3, low half first, moved down one cell for an odd beg0; y: cells 2pe-2 .. 2pe+1 with cell
+                // `end` on top, moved up one cell for an even end0.  The move is a shift count, not a branch.
+                const uint32_t xs = (uint32_t)(beg0 & 1) << 4, ys = ((uint32_t)(end0 & 1) << 4) + 16u;
+                const uint64_t x = (uint64_t)__builtin_amdgcn_alignbit(b2, b1, xs) << 32 | __builtin_amdgcn_alignbit(b1, b0, xs);
+                const uint64_t y = (((uint64_t)e2 << 32 | e1) >> ys) << 32 | (uint32_t)(((uint64_t)e1 << 32 | e0) >> ys);
                 const int lz = x ? __builtin_ctzll(x) >> 4 : 4, tz = y ? __builtin_clzll(y) >> 4 : 4;
                 int base = min(beg0 + lz, end0);                           // the zero trim's left edge: the first live cell
                 int lp = lz, tp = tz;                                      // cells either edge moves over, of its window
@@ -1280,22 +1301,25 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     // and prunes nothing on that side.
                     const int rq = min(rows_left, qlen);
                     const int hb = hrow - e_del;                           // the next row's left edge
-                    edge_pot = hb > 0 ? hb + mul24(c.max_sc, rq) : 0;
-                    const bool go = prune && base < qlen && (base != 0 || edge_pot <= thr);
-                    const uint32_t r2 = as_u32(pk_splat(rq)), m2 = as_u32(pk_splat(c.max_sc));
-                    const uint32_t bestL = (uint32_t)(go ? thr : 0) * 0x00010001u, bestR = (uint32_t)(prune ? thr : 0) * 0x00010001u;
-                    const uint32_t cl01 = ((uint32_t)(qlen - beg0) & 0xffffu) | (uint32_t)(qlen - beg0 - 1) << 16;
-                    const uint32_t cr01 = ((uint32_t)(qlen - end0 + 3) & 0xffffu) | (uint32_t)(qlen - end0 + 2) << 16;
+                    const int hpot = hb + mul24(v_max_sc, rq);
+                    edge_pot = hb > 0 ? hpot : 0;
+                    const bool go = prune & (base < qlen) & ((base != 0) | (edge_pot <= thr));
+                    const uint32_t r2 = (uint32_t)rq << 16 | (uint32_t)rq;             // (rq >= 0)
+                    const uint32_t thr2 = (uint32_t)thr << 16 | (uint32_t)thr;
+                    const uint32_t bestL = go ? thr2 : 0u, bestR = prune ? thr2 : 0u;
+                    // columns left of the windows' first two cells, per half: (a, a - 1) = a * 0x10001 - 0x10000 for a >= 1
+                    const uint32_t ca = (uint32_t)(qlen - beg0), cb = (uint32_t)(qlen - end0 + 3);
+                    const uint32_t cl01 = (ca << 16 | ca) - k_hi1, cr01 = (cb << 16 | cb) - k_hi1;
 #define BSW_STAY(W, CL, B2, OUT)                                                                                   \
     {                                                                                                             \
-        const uint32_t m = pk_max_i16((W) & 0x00ff00ffu, ((W) >> 8) & 0x00ff00ffu);                              \
-        (OUT) = pk_mul_lo(pk_subsat_u16_v(add_u32_v(m, pk_mul_lo(pk_min_u16((CL), r2), m2)), (B2)), pk_min_u16_1(m)); \
+        const uint32_t m = pk_max_i16((W) & k_lo8, __builtin_amdgcn_perm(0u, (W), 0x0c030c01u));   /* max(H, E) per cell */ \
+        (OUT) = pk_mul_lo(pk_subsat_u16_v(add_u32_v(m, pk_mul_lo(pk_min_u16((CL), r2), k_m2)), (B2)), pk_min_u16_1(m)); \
     }
                     uint32_t sll, slh, srl, srh;
                     BSW_STAY((uint32_t)x, cl01, bestL, sll)
-                    BSW_STAY((uint32_t)(x >> 32), cl01 - 0x00020002u, bestL, slh)
+                    BSW_STAY((uint32_t)(x >> 32), cl01 - k_two2, bestL, slh)
                     BSW_STAY((uint32_t)y, cr01, bestR, srl)
-                    BSW_STAY((uint32_t)(y >> 32), cr01 - 0x00020002u, bestR, srh)
+                    BSW_STAY((uint32_t)(y >> 32), cr01 - k_two2, bestR, srh)
 #undef BSW_STAY
                     const uint64_t stl = (uint64_t)slh << 32 | sll, str = (uint64_t)srh << 32 | srl;
                     lp = stl ? __builtin_ctzll(stl) >> 4 : 4;
@@ -1313,7 +1337,7 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 beg = bl < endz ? bl : endz;
                 int jl = jlz;
                 if constexpr (SO) {
-                    dropped = dropped || beg > base;                       // (cell `base` is live)
+                    dropped = dropped | (beg > base);                      // (cell `base` is live)
                     // Right edge: jn = where the prune stops, never left of beg - 1 and, with tz == 4, never left of jlz.  The
                     // dropped cells jn + 1 .. jlz lie in y's window and are set to zero with 16-bit stores (nothing waits for
                     // them; no word write-back: with end0 <= 3 the edge words are clamped duplicates).  With end0 >= 3 all four
@@ -1322,17 +1346,18 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                     // they hold.  Only a band that ends left of column 3 takes the predicated form.
                     int jn = end0 - tp;
                     jn = jn > beg - 1 ? jn : beg - 1;
-                    dropped = dropped || jn < jlz;
+                    dropped = dropped | (jn < jlz);
                     jl = jn < jlz ? jn : jlz;
                     if (__builtin_expect(end0 >= 3, 1)) {
                         const int nz = end0 - jl;                          // >= 0; cells of the window to clear, from the top
                         const uint64_t yz = nz >= 4 ? 0ull : y & (~0ull >> (16 * nz));
                         uint8_t *const a0 = CB + (end0 >> 1) * 256 + (end0 & 1) * 2;          // cell end0; cell end0 - 2 is 256 bytes below
-                        const int d1 = (end0 & 1) ? 2 : 254;                                  // cell end0 - 1 (and end0 - 3 below end0 - 2)
+                        const uint32_t d1 = (end0 & 1) ? 2u : k_254;                                  // cell end0 - 1 (and end0 - 3 below end0 - 2)
                         *reinterpret_cast<uint16_t *>(a0) = (uint16_t)(yz >> 48);
                         *reinterpret_cast<uint16_t *>(a0 - d1) = (uint16_t)(yz >> 32);
-                        *reinterpret_cast<uint16_t *>(a0 - 256) = (uint16_t)(yz >> 16);
-                        *reinterpret_cast<uint16_t *>(a0 - 256 - d1) = (uint16_t)yz;
+                        uint8_t *const a2 = a0 - k_256;
+                        *reinterpret_cast<uint16_t *>(a2) = (uint16_t)(yz >> 16);
+                        *reinterpret_cast<uint16_t *>(a2 - d1) = (uint16_t)yz;
                     } else if (jn < jlz) {
 #pragma unroll
                         for (int k = 0; k < 3; k++) {                      // (end0 <= 2)
@@ -1343,27 +1368,28 @@ __global__ __launch_bounds__(64) void bsw_dp8(BswIO io, BswConst c, const BswRec
                 }
                 end = jl + 2 < qlen ? jl + 2 : qlen;
             }
-            if (try_exit && !stop) {
-                int bound = stale_pot;
-                if (beg == 0) bound = max(bound, edge_pot);
-                if (bound <= best) {
+            {
+                // (edge_pot and stale_pot are never negative)  The bound pass is the one divergent region here: a lane enters
+                // it only when the cheap terms of the bound leave the exit open.
+                int bound = max(stale_pot, beg == 0 ? edge_pot : 0);
+                if (try_exit & !stop & (bound <= best)) {
                     // pot() of columns 2p (low half) and 2p + 1 (high half) of every pair word that holds a cell of [beg, end];
                     // the halves outside the band are masked to Hd = 0.  All halves stay below 2^15: Hd <= 255,
                     // max_sc * (columns left) <= max_sc * qcap <= 255.
                     const int pb = beg >> 1, pe = end >> 1;
-                    const uint32_t r2 = as_u32(pk_splat(rows_left)), m2 = as_u32(pk_splat(c.max_sc));
+                    const uint32_t r2 = as_u32(pk_splat(rows_left));
                     uint32_t cl2 = (uint32_t)(qlen - 2 * pb) | (uint32_t)(qlen - 2 * pb - 1) << 16;    // columns left, per half
                     uint32_t acc = 0;
                     for (int p = pb; p <= pe; p++, cl2 -= 0x00020002u) {
                         uint32_t d2 = CW[p * 64] & 0x00ff00ffu;
                         if (p == pb && (beg & 1)) d2 &= 0xffff0000u;
                         if (p == pe && !(end & 1)) d2 &= 0x0000ffffu;
-                        const uint32_t gain = pk_mul_lo(pk_min_u16(cl2, r2), m2);
+                        const uint32_t gain = pk_mul_lo(pk_min_u16(cl2, r2), k_m2);
                         acc = pk_max_i16(acc, pk_mul_lo(add_u32_v(d2, gain), pk_min_u16_1(d2)));
                     }
                     bound = max(bound, max((int)(acc & 0xffffu), (int)(acc >> 16)));
+                    stop = bound <= best;
                 }
-                stop = bound <= best;
             }
             if (stop) break;
         }
