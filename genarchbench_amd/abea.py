@@ -5,7 +5,9 @@ f5c.c:1241-1264), so that raw samples go in and aligned pairs come out (EventAli
 postalign, recalibrate_model and the read checks (gab_abea_calibrate: f5c.c:1438-1501), so that calibrated reads with their
 base-to-event map come out (EventAligner.signal_to_calibrated); and of the step after that, realign_read (gab_abea_realign:
 f5c.c:1508-1515), which turns a calibrated read, its reference substring and its CIGAR into the event alignment records of
-eventalign (EventAligner.realign, eventalign_rows)."""
+eventalign (EventAligner.realign, eventalign_rows); and of the other branch of the same step, calculate_methylation_for_read
+(gab_abea_meth: f5c.c:1397-1411), which scores every CpG group of a calibrated read, plain and methylated, against a CpG model
+(EventAligner.set_cpg_model, call_methylation, methylation_rows)."""
 import ctypes as C
 
 import numpy as np
@@ -30,6 +32,14 @@ REALIGN_SKIPPED, REALIGN_NO_PAIRS, REALIGN_NO_EVENT, REALIGN_STRAND = 1, 2, 4, 8
 EALN = np.dtype([("ref_position", np.int32), ("event_idx", np.int32), ("hmm_state", np.uint8), ("pad", np.uint8, 3)])      # gab_abea_ealn, 12 bytes
 REALIGN = np.dtype([("n_entries", np.int32), ("hmm_segments", np.int32), ("max_rows", np.int32), ("flags", np.uint32), ("cells", np.int64)])      # gab_abea_realign_read
 CIGAR_OPS = "MIDNSHP=X"
+NKMER_CPG = 15625     # GAB_ABEA_METH_NKMER: k-mers over A C G M T
+LOGSUM_TBL = 16000    # GAB_ABEA_METH_LOGSUM
+METH_SKIPPED, METH_NO_EVENT, METH_STRAND, METH_TRANSITIONS = 1, 2, 4, 8      # gab_abea_meth_read.flags
+SITE = np.dtype([("start_position", np.int32), ("end_position", np.int32), ("n_cpg", np.int32), ("first_cpg", np.int32), ("event_start", np.int32),
+                 ("event_stop", np.int32), ("ll_unmethylated", np.float32), ("ll_methylated", np.float32)])      # gab_abea_site, 32 bytes
+METH = np.dtype([("n_sites", np.int32), ("groups", np.int32), ("skipped_start", np.int32), ("skipped_span", np.int32), ("skipped_unbounded", np.int32),
+                 ("skipped_short", np.int32), ("flags", np.uint32), ("pad", np.int32), ("cells", np.int64)])      # gab_abea_meth_read, 40 bytes
+assert SITE.itemsize == 32 and METH.itemsize == 40
 assert PAIR.itemsize == 8 and READ.itemsize == 40 and RANGE.itemsize == 8 and CALIB.itemsize == 40 and EALN.itemsize == 12 and REALIGN.itemsize == 24
 
 
@@ -90,6 +100,29 @@ def realign_room(n_events, cigar, cigar_off, n_cigar):
     return np.asarray(n_events, np.int64) * (1 + skips)
 
 
+def meth_shape():
+    """(k-mer blocks a lane of the methylation scoring kernel owns in a wide group, k-mers up to which a group runs with one block a
+    lane): GAB_ABEA_METH_BLOCKS_PER_LANE, GAB_ABEA_METH_ONE_BLOCK_KMERS as the library was built"""
+    v = C.c_int32(0); w = C.c_int32(0)
+    check(lib().gab_abea_meth_shape(C.byref(v), C.byref(w)))
+    return v.value, w.value
+
+
+def meth_logsum():
+    """the 16000 floats of the logsum table as the library builds them (no GPU needed)"""
+    t = np.zeros(LOGSUM_TBL, np.float32)
+    check(lib().gab_abea_meth_logsum(_p(t)))
+    return t
+
+
+def meth_room(ref, ref_off, ref_len):
+    """site records of room a read needs at its out_off: the CpG groups of its prepared reference (gab_abea_meth_groups, no GPU needed)"""
+    ref = np.ascontiguousarray(ref, np.uint8); ref_off = np.ascontiguousarray(ref_off, np.int64); ref_len = np.ascontiguousarray(ref_len, np.int32)
+    groups = np.zeros(ref_len.size, np.int32)
+    check(lib().gab_abea_meth_groups(_p(ref), _p(ref_off), _p(ref_len), C.c_int64(ref_len.size), _p(groups)))
+    return groups.astype(np.int64)
+
+
 _FIRST_BASE = bytes.maketrans(b"ACGTMRWSYKVHDBN", b"ACGTAAACCGAAACA")
 _COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
 
@@ -107,6 +140,43 @@ def eventalign_rows(ref, ref_pos, is_rev, entries):
         state = chr(int(e["hmm_state"]))
         model = b"N" * K if state == "B" else kmer.translate(_COMPLEMENT)[::-1] if is_rev else kmer
         rows.append((int(e["ref_position"]), kmer.decode(), int(e["event_idx"]), model.decode(), state))
+    return rows
+
+
+def pack_aligned_reads(reads):
+    """list of (reference bases, ref_pos, is_rev, cigar as uint32 in BAM encoding, seq_len, event means, map as (n_kmers, 2) or RANGE,
+    calibration record) -> the packed arrays that realign() and call_methylation() take, in their order"""
+    def offsets(lens):
+        o = np.zeros(len(lens), np.int64)
+        if len(lens) > 1:
+            o[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        return o
+    cat = lambda xs, dt: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs]) if xs else np.zeros(0, dt)
+    ref_len = np.array([len(r[0]) for r in reads], np.int32); n_cigar = np.array([len(r[3]) for r in reads], np.int32)
+    seq_len = np.array([r[4] for r in reads], np.int32); n_events = np.array([len(r[5]) for r in reads], np.int32)
+    maps = [np.ascontiguousarray(r[6] if np.asarray(r[6]).dtype == RANGE else np.asarray(r[6], np.int32)).view(np.int32).reshape(-1, 2) for r in reads]
+    calib = np.zeros(len(reads), CALIB)
+    for i, r in enumerate(reads):
+        for f in CALIB.names:
+            calib[i][f] = r[7][f] if not isinstance(r[7], np.void) or f in r[7].dtype.names else 0
+    return (cat([np.frombuffer(bytes(r[0]), np.uint8) for r in reads], np.uint8), offsets(ref_len), ref_len, np.array([r[1] for r in reads], np.int32),
+            np.array([r[2] for r in reads], np.uint8), cat([r[3] for r in reads], np.uint32), offsets(n_cigar), n_cigar, seq_len,
+            cat([r[5] for r in reads], np.float32), offsets(n_events), n_events, cat(maps, np.int32).view(RANGE),
+            offsets(np.array([len(m) for m in maps], np.int64)), calib)
+
+
+def methylation_rows(contig, qname, ref, ref_pos, sites):
+    """one read's reference bases (as given to call_methylation), position and SITE records -> the text lines of call-methylation in
+    output version 1 (f5c.c:1746-1753): contig, start, end, read name, %.2lf of ll_methylated - ll_unmethylated, of ll_methylated and
+    of ll_unmethylated as doubles, strands scored (1), CpGs in the group, and the prepared reference from five bases before the first
+    CpG to six behind the start of the last (meth.c:639-643)"""
+    seq = bytes(ref).upper().translate(_FIRST_BASE)
+    rows = []
+    for s in sites:
+        m, u = float(s["ll_methylated"]), float(s["ll_unmethylated"])
+        a = int(s["first_cpg"]); b = a + int(s["end_position"]) - int(s["start_position"])
+        rows.append("%s\t%d\t%d\t%s\t%.2f\t%.2f\t%.2f\t%d\t%d\t%s" % (contig, s["start_position"], s["end_position"], qname, m - u, m, u, 1, s["n_cpg"],
+                                                                         seq[a - K + 1:b + K].decode()))
     return rows
 
 
@@ -400,23 +470,7 @@ class EventAligner:
     def realign_reads(self, reads, region=(-1, -1)):
         """list of (reference bases, ref_pos, is_rev, cigar as uint32 in BAM encoding, seq_len, event means, map as (n_kmers, 2) or
         RANGE, calibration record) -> (entries, out_off, records)"""
-        def offsets(lens):
-            o = np.zeros(len(lens), np.int64)
-            if len(lens) > 1:
-                o[1:] = np.cumsum(lens[:-1], dtype=np.int64)
-            return o
-        cat = lambda xs, dt: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs]) if xs else np.zeros(0, dt)
-        ref_len = np.array([len(r[0]) for r in reads], np.int32); n_cigar = np.array([len(r[3]) for r in reads], np.int32)
-        seq_len = np.array([r[4] for r in reads], np.int32); n_events = np.array([len(r[5]) for r in reads], np.int32)
-        maps = [np.ascontiguousarray(r[6] if np.asarray(r[6]).dtype == RANGE else np.asarray(r[6], np.int32)).view(np.int32).reshape(-1, 2) for r in reads]
-        calib = np.zeros(len(reads), CALIB)
-        for i, r in enumerate(reads):
-            for f in CALIB.names:
-                calib[i][f] = r[7][f] if not isinstance(r[7], np.void) or f in r[7].dtype.names else 0
-        return self.realign(cat([np.frombuffer(bytes(r[0]), np.uint8) for r in reads], np.uint8), offsets(ref_len), ref_len, np.array([r[1] for r in reads], np.int32),
-                            np.array([r[2] for r in reads], np.uint8), cat([r[3] for r in reads], np.uint32), offsets(n_cigar), n_cigar, seq_len,
-                            cat([r[5] for r in reads], np.float32), offsets(n_events), n_events, cat(maps, np.int32).view(RANGE),
-                            offsets(np.array([len(m) for m in maps], np.int64)), calib, region)
+        return self.realign(*pack_aligned_reads(reads), region)
 
     def realign_device(self, ref, ref_off, ref_len, ref_pos, is_rev, cigar, cigar_off, n_cigar, seq_len, events, event_off, n_events, rmap, map_off, calib,
                        out, out_off, res, region=(-1, -1), stream=0):
@@ -444,6 +498,78 @@ class EventAligner:
         names = ("reads", "hmm_segments", "rows", "cells", "reads_requeued")
         return {**{k: x.value for k, x in zip(names, v)}, "kernel_ms": kms.value, "total_ms": tms.value,
                 "prep_ms": st[0].value, "viterbi_ms": st[1].value, "requeue_ms": st[2].value}
+
+    # ---- call-methylation: the two log-likelihoods of every CpG group (gab_abea_meth) ----------------------------------------------
+    def set_cpg_model(self, level_mean, level_stdv, level_log_stdv):
+        """the CpG model: 15625 entries each, k-mers over A C G M T ranked base 5"""
+        a = [np.ascontiguousarray(x, np.float32) for x in (level_mean, level_stdv, level_log_stdv)]
+        if any(x.size != NKMER_CPG for x in a):
+            raise ValueError(f"the CpG model has {NKMER_CPG} entries")
+        check(lib().gab_abea_set_cpg_model(self._h, _p(a[0]), _p(a[1]), _p(a[2])))
+
+    def call_methylation(self, ref, ref_off, ref_len, ref_pos, is_rev, cigar, cigar_off, n_cigar, seq_len, events, event_off, n_events, rmap, map_off, calib,
+                         out_off=None, out=None):
+        """the packed numpy arrays of realign() -> (sites, out_off, records): sites a SITE array in which read i's are
+        sites[out_off[i] : out_off[i] + records[i]["n_sites"]] in ascending start_position, records a METH array.  out: (sites,
+        records) to write into instead of new arrays."""
+        ref = np.ascontiguousarray(ref, np.uint8); cigar = np.ascontiguousarray(cigar, np.uint32); events = np.ascontiguousarray(events, np.float32)
+        ref_off = np.ascontiguousarray(ref_off, np.int64); cigar_off = np.ascontiguousarray(cigar_off, np.int64)
+        event_off = np.ascontiguousarray(event_off, np.int64); map_off = np.ascontiguousarray(map_off, np.int64)
+        ref_len = np.ascontiguousarray(ref_len, np.int32); ref_pos = np.ascontiguousarray(ref_pos, np.int32); n_cigar = np.ascontiguousarray(n_cigar, np.int32)
+        seq_len = np.ascontiguousarray(seq_len, np.int32); n_events = np.ascontiguousarray(n_events, np.int32)
+        is_rev = np.ascontiguousarray(is_rev, np.uint8)
+        rmap = np.ascontiguousarray(rmap); calib = np.ascontiguousarray(calib)
+        if rmap.dtype != RANGE or calib.dtype != CALIB:
+            raise ValueError("rmap is a RANGE array, calib a CALIB array")
+        n = seq_len.size
+        if out_off is None:
+            room = meth_room(ref, ref_off, ref_len)
+            out_off = np.zeros(n, np.int64)
+            if n > 1:
+                out_off[1:] = np.cumsum(room[:-1])
+            total = int(room.sum())
+        else:
+            total = None
+        out_off = np.ascontiguousarray(out_off, np.int64)
+        if out is None:
+            if total is None:
+                total = int((out_off + meth_room(ref, ref_off, ref_len)).max()) if n else 0
+            out = (np.zeros(total, SITE), np.zeros(n, METH))
+        sites, res = out
+        if sites.dtype != SITE or res.dtype != METH or res.size < n:
+            raise ValueError("out: a SITE array and a METH array of one record per read")
+        check(lib().gab_abea_meth(self._h, _p(ref), _p(ref_off), _p(ref_len), _p(ref_pos), _p(is_rev), _p(cigar), _p(cigar_off), _p(n_cigar), _p(seq_len),
+                                  _p(events), _p(event_off), _p(n_events), _p(rmap), _p(map_off), _p(calib), C.c_int64(n), _p(sites), _p(out_off), _p(res)))
+        return sites, out_off, res
+
+    def call_methylation_reads(self, reads):
+        """list of (reference bases, ref_pos, is_rev, cigar as uint32 in BAM encoding, seq_len, event means, map as (n_kmers, 2) or
+        RANGE, calibration record) -> (sites, out_off, records)"""
+        return self.call_methylation(*pack_aligned_reads(reads))
+
+    def call_methylation_device(self, ref, ref_off, ref_len, ref_pos, is_rev, cigar, cigar_off, n_cigar, seq_len, events, event_off, n_events, rmap, map_off,
+                                calib, out, out_off, res, stream=0):
+        """torch tensors on the handle's GPU as realign_device takes them | out a uint8 tensor of 32 bytes per site record, int64
+        out_off and res a uint8 tensor of 40 bytes per read, filled in place (complete when the call returns)"""
+        n = seq_len.numel()
+        if rmap.numel() % 2 or calib.numel() * calib.element_size() < n * CALIB.itemsize or res.numel() * res.element_size() < n * METH.itemsize:
+            raise ValueError("rmap holds int32 pairs, calib 40 bytes and res 40 bytes per read")
+        check(lib().gab_abea_meth_device(
+            self._h, C.c_void_p(ref.data_ptr()), C.c_int64(ref.numel()), C.c_void_p(ref_off.data_ptr()), C.c_void_p(ref_len.data_ptr()), C.c_void_p(ref_pos.data_ptr()),
+            C.c_void_p(is_rev.data_ptr()), C.c_void_p(cigar.data_ptr()), C.c_int64(cigar.numel()), C.c_void_p(cigar_off.data_ptr()), C.c_void_p(n_cigar.data_ptr()),
+            C.c_void_p(seq_len.data_ptr()), C.c_void_p(events.data_ptr()), C.c_int64(events.numel()), C.c_void_p(event_off.data_ptr()), C.c_void_p(n_events.data_ptr()),
+            C.c_void_p(rmap.data_ptr()), C.c_int64(rmap.numel() // 2), C.c_void_p(map_off.data_ptr()), C.c_void_p(calib.data_ptr()),
+            C.c_int64(n), C.c_void_p(out.data_ptr()), C.c_int64(out.numel() * out.element_size() // SITE.itemsize),
+            C.c_void_p(out_off.data_ptr()), C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+
+    def meth_last_stats(self):
+        """the last call_methylation call: reads, CpG groups, sites scored, their rows and cells, device time of the kernels and of the
+        whole call, and the time by stage (ms)"""
+        v = [C.c_int64(-1) for _ in range(5)]; kms = C.c_float(-1); tms = C.c_float(-1); st = [C.c_float(-1) for _ in range(2)]
+        check(lib().gab_abea_meth_last_stats(self._h, *[C.byref(x) for x in v], C.byref(kms), C.byref(tms)))
+        check(lib().gab_abea_meth_stage_ms(self._h, *[C.byref(x) for x in st]))
+        names = ("reads", "groups", "sites", "rows", "cells")
+        return {**{k: x.value for k, x in zip(names, v)}, "kernel_ms": kms.value, "total_ms": tms.value, "prep_ms": st[0].value, "score_ms": st[1].value}
 
     def events_last_stats(self):
         """the last detect_events call: samples, events, reads whose sums were added in order, chunks, chunks run again, kernel and

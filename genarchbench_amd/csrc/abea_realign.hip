@@ -73,18 +73,6 @@ struct rl_reads {                                          // the call's per-rea
     const gab_abea_range *map; const int64_t *map_off; const int32_t *seq_len;
 };
 
-// toupper, isValid and getPossibleSymbols(c)[0] (eventalign.c:991-1109) in one: the base's rank, or -1
-__device__ __forceinline__ int rl_code(char c) {
-    if (c >= 'a' && c <= 'z') c = (char)(c - 32);
-    switch (c) {
-        case 'A': case 'M': case 'R': case 'W': case 'V': case 'H': case 'D': case 'N': return 0;
-        case 'C': case 'S': case 'Y': case 'B': return 1;
-        case 'G': case 'K': return 2;
-        case 'T': return 3;
-        default: return -1;
-    }
-}
-
 __global__ __launch_bounds__(256) void rl_prep(rl_reads R, const rl_job *jobs, uint32_t *rk, rl_verdict *verdict) {
     const int r = blockIdx.x;
     const rl_job J = jobs[r];
@@ -93,7 +81,7 @@ __global__ __launch_bounds__(256) void rl_prep(rl_reads R, const rl_job *jobs, u
     for (int p = threadIdx.x; p < J.ref_len; p += 256) {
         uint32_t f = 0, c = 0;
         for (int t = 0; t < K; t++) {
-            const int b = p + t < J.ref_len ? rl_code(ref[p + t]) : 0;
+            const int b = p + t < J.ref_len ? gab_abea_base_code(ref[p + t]) : 0;
             bad |= b < 0;
             f = (f << 2) | (uint32_t)(b & 3);
             c |= (uint32_t)(3 - (b & 3)) << (2 * t);       // the reverse complement's base K-1-t is the complement of base t
@@ -355,19 +343,6 @@ __global__ __launch_bounds__(64) void rl_viterbi(rl_reads R, const rl_job *jobs,
     }
 }
 
-// calculate_transitions (eventalign.c:171-240) and pre_flank[0] (eventalign.c:124), once per read.  The reference's compiler folds the
-// logarithms of the constants (correctly rounded); only the two that depend on events_per_base are calls of logf.
-void rl_transitions(double events_per_base, float *t) {
-    const float p_stay = 1 - (1 / events_per_base);
-    const float p_skip = 0.0025, p_bad = 0.001, p_bad_self = p_bad, p_skip_self = 0.3;
-    const float p_mk = p_skip, p_mb = p_bad, p_mm_self = p_stay, p_mm_next = 1.0f - p_mm_self - p_mk - p_mb;
-    const float p_bb = p_bad_self, p_bk = (1.0f - p_bb) / 3, p_kk = p_skip_self, p_km = 1.0f - p_kk;
-    auto folded = [](float p) { return (float)log((double)p); };
-    t[0] = logf(p_mm_self); t[1] = logf(p_mm_next); t[2] = folded(p_bk); t[3] = folded(p_bk); t[4] = folded(p_km);
-    t[5] = 0.0f + (float)log(0.5);
-    t[6] = folded(p_mb); t[7] = folded(p_bb); t[8] = folded(p_mk); t[9] = folded(p_bk); t[10] = folded(p_kk);
-}
-
 void rl_reset(gab_abea_realign_state &S) {
     S.reads = S.hmm_segments = S.rows = S.cells = S.reads_requeued = 0;
     S.prep_ms = S.viterbi_ms = S.requeue_ms = S.total_ms = 0.f;
@@ -448,7 +423,7 @@ extern "C" int gab_abea_realign_device(gab_abea *h, const char *ref, int64_t ref
         J.rk_off = rk_total; J.ev_off = eo[i]; J.map_off = mo[i]; J.out_off = oo[i]; J.run_off = (int64_t)runs.size(); J.seg_off = (int64_t)segs.size();
         J.ref_pos = rp[i]; J.ref_len = rl[i]; J.seq_len = sl[i]; J.n_events = ne[i]; J.is_rev = rv[i] != 0; J.skipped = c.read_stat_flag != 0;
         J.scale = c.scale; J.shift = c.shift; J.var = c.var; J.log_var = c.log_var;
-        rl_transitions(c.events_per_base, J.t);
+        gab_abea_transitions(c.events_per_base, J.t);
         rk_total += std::max(rl[i] - K + 1, 0);
         int64_t ref_at = rp[i], read_at = 0, pair_at = 0, n_skip = 0;
         segs.push_back((int32_t)(runs.size() - (size_t)J.run_off));

@@ -786,7 +786,8 @@ int gab_parser_last_stats(gab_parser *p, float *kernel_ms);
  * n_events >= 1, anything else is GAB_EINVAL naming the read.  The two steps before align() in the reference's timed region,
  * event detection and the scaling estimate, are gab_abea_events and gab_abea_scalings below: their outputs are what this call
  * takes; the fixed block after it, postalign, recalibrate_model and the three read checks, is gab_abea_calibrate at the end
- * of this header, and realign_read, the step after that, is gab_abea_realign behind it.  Out of scope: the methylation HMM. */
+ * of this header, and realign_read, the step after that, is gab_abea_realign behind it; the other branch of that step, the methylation HMM of
+ * call-methylation, is gab_abea_meth at the very end. */
 #define GAB_ABEA_K 6
 #define GAB_ABEA_BANDWIDTH 100
 #define GAB_ABEA_NKMER 4096
@@ -1030,6 +1031,104 @@ int gab_abea_realign_last_stats(gab_abea *h, int64_t *reads, int64_t *hmm_segmen
 int gab_abea_realign_stage_ms(gab_abea *h, float *prep_ms, float *viterbi_ms, float *requeue_ms);
 /* GAB_ABEA_REALIGN_ROWS as the library was built (no GPU needed) */
 int gab_abea_realign_shape(int32_t *rows_cap);
+
+/* ---- abea: call-methylation, the log-likelihoods of every CpG group of a read --------------------------------
+ * Replaces  calculate_methylation_for_read of meth_single             abea/src/f5c.c:1397-1411
+ *           = abea/src/meth.c:501-658 around profile_hmm_score (abea/src/hmm.c:620-674), per read.
+ * It takes what gab_abea_realign takes, without the region: the reference substring, position, strand and CIGAR of a read's BAM
+ * record, its event means, and the map and calibration record that gab_abea_calibrate wrote.  Per scored CpG group one site
+ * record comes out, with the two floats that the reference prints (f5c.c:1730-1754).  Bit for bit the reference built WITHOUT
+ * fused multiply-add and with ESL_LOG_SUM 1 (abea/src/f5c.h:70): add_logs is the table-driven p7_FLogsum (abea/src/logsum.h:61-71).
+ * Which reads run: those with calib[i].read_stat_flag == 0; the others get no sites and GAB_ABEA_METH_SKIPPED.
+ * Reference string: upper-cased, IUPAC codes replaced by their first base (disambiguate, meth.c:288-306), as for realign.
+ * Groups (meth.c:532-558): every i with ref[i] == 'C' and ref[i + 1] == 'G' is a site; consecutive sites at most 10 apart form a
+ * group (first, last, n_cpg).  Per group (meth.c:560-603): sub_start = first - 10, sub_end = last + 10; skipped when
+ * sub_start <= 10 (skipped_start) or last - first > 200 (skipped_span); the sub-sequence is ref[sub_start .. sub_end], cut at the
+ * end of the string as substr cuts it.
+ * Event alignment record (meth.c:124-185), one per read: the CIGAR walk of get_aligned_segments (meth.c:15-87; M = X emit pairs, D
+ * advances the reference, I and S the read, H nothing), the pairs with read_pos < 6 or read_pos + 6 >= seq_len dropped, the k-mer
+ * index flipped for a reverse read, the event of a pair by get_closest_event_to as written (meth.c:92-117: its loops leave their
+ * stop index out); the record is emptied when its first and last event are equal.
+ * Bounds (find_by_ref_bounds, meth.c:422-467): the two lower bounds of sub_start + ref_pos and sub_end + ref_pos among the pairs'
+ * reference positions and the left / right tests as written; not bounded -> skipped_unbounded.  Then (meth.c:597-603) the group
+ * is skipped when abs(e2 - e1) <= 10 (skipped_short).  The third test there, ratio > MAX_EVENT_TO_BP_RATIO, divides by
+ * calling_start - calling_end, which is negative: the ratio is never positive and the test never fires; it is not built.
+ * Scores: profile_hmm_score on the sub-sequence and its reverse complement, and on methylate() of it (meth.c:359-382: every
+ * complete CG becomes MG) and reverse_complement_meth of that (meth.c:387-420), with hmm_flags = PRE_CLIP | POST_CLIP,
+ * event_stride = e1 <= e2 ? 1 : -1 and rc = is_rev.  The fill is hmm.c:305-524 with the forward output of hmm.c:549-600:
+ * |e2 - e1| + 1 rows, strlen - 5 k-mers ranked base 5 over A C G M T (hmm.c:21-52; of m_rc_seq + len - ki - 6 for rc, hmm.c:382-393),
+ * the CACHED_LOG emission (hmm.c:55-100), the six scores of a state folded left to right by p7_FLogsum in the order written with
+ * the emission added last (hmm.c:558-566), KMER_SKIP reading the same row of the previous block (hmm.c:468-474), and lp_end folding
+ * M, B and K of the last k-mer of every row in row order (hmm.c:479-487).  HMM_REVERSE_FIX is not defined.
+ * Host-side constants: the ten transition logarithms per read (hmm.c:231-298) as for realign; the flanks (hmm.c:132-205), one
+ * table for both because post_flank read from its end is pre_flank expression for expression, doubles stored as floats; the
+ * 16000-entry table of p7_FLogsumInit (logsum.h:35-48).  All with the host's libm.
+ * Sites of a read are written in ascending start_position (the order in which the reference's std::map iterates), n_sites of
+ * them at out[out_off[i] ..].  Room: gab_abea_meth_groups()[i] records (one per CpG group of the read, scored or not), regions
+ * disjoint.  Less room is GAB_EINVAL.  A read that is not run (GAB_ABEA_METH_SKIPPED) needs no room: its groups are not counted
+ * and its record says groups = 0.
+ * Input rules: those of gab_abea_realign, and a CIGAR that holds an N operation is GAB_EINVAL naming the read (the reference
+ * exits on spliced alignments, meth.c:54-58).  On GAB_EINVAL nothing is written.  n_reads = 0 returns GAB_OK.  Before
+ * gab_abea_set_cpg_model the calls return GAB_EINVAL.
+ * Defined where the reference has undefined behaviour or asserts; the group is not scored and the read is flagged:
+ * e1 or e2 is -1 (the reference indexes event -1) -> GAB_ABEA_METH_NO_EVENT (checked after the bounds, before the short test);
+ * the stride disagrees with the strand (the assert of hmm.c:322) -> GAB_ABEA_METH_STRAND; events_per_base < 1 (or no number),
+ * where the transition logarithms are NaN and the table index undefined -> GAB_ABEA_METH_TRANSITIONS, no group of the read is
+ * scored (groups is still counted).
+ * How it runs: one wavefront per read prepares it (codes of the reference, groups, bounds, the work list); one wavefront per
+ * group scores both variants, one k-mer block per lane for groups of up to GAB_ABEA_METH_ONE_BLOCK_KMERS k-mers and
+ * GAB_ABEA_METH_BLOCKS_PER_LANE for wider ones, the lanes one row apart from each other so that every fold meets its operands in
+ * the reference's order.  No trace, so no row cap. */
+#define GAB_ABEA_METH_NKMER 15625
+#define GAB_ABEA_METH_LOGSUM 16000
+#define GAB_ABEA_METH_BLOCKS_PER_LANE 4
+#define GAB_ABEA_METH_ONE_BLOCK_KMERS 64      /* groups of up to this many k-mers run with one block per lane */
+typedef struct { int32_t start_position, end_position, n_cpg, first_cpg /* index into the read's reference substring */, event_start, event_stop;
+                 float ll_unmethylated, ll_methylated; } gab_abea_site;
+enum { GAB_ABEA_METH_SKIPPED = 1,       /* calib[i].read_stat_flag != 0: the reference never scores the read */
+       GAB_ABEA_METH_NO_EVENT = 2,      /* defined deviation, above */
+       GAB_ABEA_METH_STRAND = 4,        /* defined deviation, above */
+       GAB_ABEA_METH_TRANSITIONS = 8 }; /* defined deviation, above */
+typedef struct {
+    int32_t n_sites;       /* records written at out[out_off[i] ..] */
+    int32_t groups;        /* CpG groups of the prepared reference */
+    int32_t skipped_start, skipped_span, skipped_unbounded, skipped_short;
+    uint32_t flags;
+    int32_t pad;
+    int64_t cells;         /* rows x k-mers over the scored groups, both variants */
+} gab_abea_meth_read;
+/* the CpG model: 15625 entries each (k-mers over A C G M T, base 5), copied to the device.  The first call on a handle also builds its
+ * logsum table (p7_FLogsumInit), once; a later call replaces the model only. */
+int gab_abea_set_cpg_model(gab_abea *h, const float *level_mean, const float *level_stdv, const float *level_log_stdv);
+/* No GPU needed.  groups[i] = CpG groups of read i's prepared reference: the room read i needs at out[out_off[i] ..]. */
+int gab_abea_meth_groups(const char *ref, const int64_t *ref_off, const int32_t *ref_len, int64_t n_reads, int32_t *groups);
+/* No GPU needed.  The 16000 floats of p7_FLogsumInit as the library builds them. */
+int gab_abea_meth_logsum(float *table16000);
+/* GAB_ABEA_METH_BLOCKS_PER_LANE and GAB_ABEA_METH_ONE_BLOCK_KMERS as the library was built (no GPU needed).  Either may be NULL. */
+int gab_abea_meth_shape(int32_t *blocks_per_lane, int32_t *one_block_kmers);
+/* Host buffers, as gab_abea_realign. */
+int gab_abea_meth(gab_abea *h, const char *ref, const int64_t *ref_off, const int32_t *ref_len, const int32_t *ref_pos,
+                  const uint8_t *is_rev, const uint32_t *cigar, const int64_t *cigar_off, const int32_t *n_cigar,
+                  const int32_t *seq_len, const float *event_mean, const int64_t *event_off, const int32_t *n_events,
+                  const gab_abea_range *map, const int64_t *map_off, const gab_abea_calib *calib, int64_t n_reads,
+                  gab_abea_site *out, const int64_t *out_off, gab_abea_meth_read *res);
+/* Device buffers, with the sizes of the five slabs for bounds validation; a read's room is what lies between its out_off and the
+ * next larger one (or out_count).  Synchronises `stream` at the start (lengths, offsets, calibration records and CIGARs come to
+ * the host and are validated there; the CIGARs' run tables go back) and at the end (the verdict of the checks that ran on the
+ * device, the reference bytes, event means, map entries and the room among them: a broken rule returns GAB_EINVAL here and the
+ * kernels have written nothing; and the per-read records for the statistics), so out and res are complete when it returns.
+ * A call whose longest read has more events than that of any call before it on the handle synchronises once more in between: the
+ * flank table is made longer and uploaded then. */
+int gab_abea_meth_device(gab_abea *h, const char *ref, int64_t ref_bytes, const int64_t *ref_off, const int32_t *ref_len, const int32_t *ref_pos,
+                         const uint8_t *is_rev, const uint32_t *cigar, int64_t cigar_count, const int64_t *cigar_off, const int32_t *n_cigar,
+                         const int32_t *seq_len, const float *event_mean, int64_t event_count, const int64_t *event_off, const int32_t *n_events,
+                         const gab_abea_range *map, int64_t map_count, const int64_t *map_off, const gab_abea_calib *calib, int64_t n_reads,
+                         gab_abea_site *out, int64_t out_count, const int64_t *out_off, gab_abea_meth_read *res, void *stream);
+/* last gab_abea_meth* call: reads, CpG groups, sites scored, their rows (events) and cells (rows x k-mers, both variants), device
+ * time of the kernels and of the whole call from first to last kernel (HIP events on the stream, ms).  Any may be NULL. */
+int gab_abea_meth_last_stats(gab_abea *h, int64_t *reads, int64_t *groups, int64_t *sites, int64_t *rows, int64_t *cells, float *kernel_ms, float *total_ms);
+/* the last gab_abea_meth* call's time by stage: preparation | scoring */
+int gab_abea_meth_stage_ms(gab_abea *h, float *prep_ms, float *score_ms);
 
 #ifdef __cplusplus
 }

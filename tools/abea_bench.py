@@ -11,6 +11,10 @@
                                                           adds gab_abea_realign_device behind that: a generated reference and CIGAR per read
                                                           (substitutions, insertions and deletions at 3 % each, half the reads reverse); wall
                                                           time, rows/s, cells/s, reads_requeued and the preparation / Viterbi / requeue split
+    python tools/abea_bench.py [--signal] --calibrate --meth
+                                                          adds gab_abea_meth_device on the same references and CIGARs (realign runs too, so that
+                                                          align, realign and call-methylation are timed in one session) with a seeded CpG model:
+                                                          wall time, sites/s, cells/s and the preparation / scoring split
 
 Reports reads/s, band cells/s (cells filled, the reference's `fills`), ms per launch, and the DP kernel's share of the device time
 against the rest (k-mer table and backtrack).  Wall time is taken around the call, which synchronises its stream before it returns."""
@@ -104,6 +108,7 @@ def main_signal(a):
     rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
     cal = torch.zeros(n * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
     realign = Realign(torch, rng, packed) if a.realign else None
+    meth = Meth(torch, rng, h, mean, stdv, realign.dev, realign.aln) if a.meth else None
     runs = []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
@@ -130,6 +135,8 @@ def main_signal(a):
             runs[-1].update(timed_calibrate(h, torch, (d_seq, d_so, d_sl, ev_mean, event_off, n_events, scale, shift), pairs, d_po, res, rmap, d_mo, cal))
         if realign:
             runs[-1].update(realign.timed(h, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal))
+        if meth:
+            runs[-1].update(meth.timed(h, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal))
     warm = runs[1:]
     med = lambda f: float(np.median([f(r) for r in warm]))
     rec = res.cpu().numpy().view(abea.READ)
@@ -148,6 +155,8 @@ def main_signal(a):
         out.update(calibrate_report(warm, cal.cpu().numpy().view(abea.CALIB)))
     if realign:
         out.update(realign.report(warm))
+    if meth:
+        out.update(meth.report(warm))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
@@ -199,7 +208,7 @@ class Realign:
 
     def __init__(self, torch, rng, packed):
         self.torch = torch
-        aln = generate_alignments(rng, packed[0], packed[1], packed[2])
+        aln = self.aln = generate_alignments(rng, packed[0], packed[1], packed[2])
         self.dev = [torch.from_numpy(np.ascontiguousarray(x if x.dtype != np.uint32 else x.view(np.int32))).cuda() for x in aln]
         self.out = None
 
@@ -230,6 +239,52 @@ class Realign:
                 "realign_flags": {str(k): int((rec["flags"] == k).sum()) for k in sorted(set(rec["flags"].tolist()))}}
 
 
+def cpg_model(rng, mean, stdv):
+    """15625 entries over A C G M T from the nucleotide model: a k-mer with M takes the values of the k-mer with C in its place, its
+    mean shifted by -4 .. +4"""
+    from genarchbench_amd import abea
+    digits = np.stack([(np.arange(abea.NKMER_CPG) // 5 ** (abea.K - 1 - t)) % 5 for t in range(abea.K)], 1)
+    r4 = (np.array([0, 1, 2, 1, 3])[digits] * 4 ** np.arange(abea.K - 1, -1, -1)).sum(1)
+    has_m = (digits == 3).any(1)
+    m = np.where(has_m, mean[r4] + rng.uniform(-4, 4, abea.NKMER_CPG), mean[r4]).astype(np.float32)
+    sd = stdv[r4].astype(np.float32)
+    return m, sd, np.log(sd.astype(np.float64)).astype(np.float32)
+
+
+class Meth:
+    """gab_abea_meth_device behind calibrate on Realign's references and CIGARs, everything resident; a site record of room per CpG group"""
+
+    def __init__(self, torch, rng, h, mean, stdv, aln_dev, aln_host):
+        from genarchbench_amd import abea
+        self.torch, self.dev = torch, aln_dev
+        h.set_cpg_model(*cpg_model(rng, mean, stdv))
+        room = abea.meth_room(aln_host[0], aln_host[1], aln_host[2])
+        self.out_off = torch.from_numpy(np.concatenate([[0], np.cumsum(room[:-1])]).astype(np.int64)).cuda()
+        self.out = torch.empty(max(int(room.sum()), 1) * abea.SITE.itemsize, dtype=torch.uint8, device="cuda")
+        self.res = torch.zeros(room.size * abea.METH.itemsize, dtype=torch.uint8, device="cuda")
+
+    def timed(self, h, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal):
+        torch = self.torch
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.call_methylation_device(*self.dev, d_sl, ev_mean, event_off, n_events, rmap, d_mo, cal, self.out, self.out_off, self.res)
+        return {"meth_ms": (time.perf_counter() - t0) * 1e3, "mt": h.meth_last_stats()}
+
+    def report(self, warm):
+        from genarchbench_amd import abea
+        med = lambda f: float(np.median([f(r) for r in warm]))
+        st = warm[-1]["mt"]
+        ms = med(lambda r: r["meth_ms"])
+        rec = self.res.cpu().numpy().view(abea.METH)
+        return {"meth_wall_ms_median": round(ms, 3), "meth_wall_ms_all": [round(r["meth_ms"], 3) for r in warm],
+                "meth_sites_per_s": round(st["sites"] / (ms * 1e-3), 1), "meth_cells_per_s": round(st["cells"] / (ms * 1e-3), 1),
+                "meth_groups": st["groups"], "meth_sites": st["sites"], "meth_rows": st["rows"], "meth_cells": st["cells"],
+                "meth_prep_ms": round(med(lambda r: r["mt"]["prep_ms"]), 3), "meth_score_ms": round(med(lambda r: r["mt"]["score_ms"]), 3),
+                "meth_first_to_last_kernel_ms": round(med(lambda r: r["mt"]["total_ms"]), 3),
+                "meth_skipped": {k: int(rec[k].sum()) for k in ("skipped_start", "skipped_span", "skipped_unbounded", "skipped_short")},
+                "meth_flags": {str(k): int((rec["flags"] == k).sum()) for k in sorted(set(rec["flags"].tolist()))}}
+
+
 def calibrate_report(warm, rec):
     med = lambda f: float(np.median([f(r) for r in warm]))
     st = warm[-1]["cal"]
@@ -247,9 +302,11 @@ def main():
     ap.add_argument("--signal", action="store_true", help="raw signal in: event detection, scalings and align, timed per stage")
     ap.add_argument("--calibrate", action="store_true", help="add the base-to-event map, recalibration and read checks after align, timed")
     ap.add_argument("--realign", action="store_true", help="add realign_read after --calibrate, on a generated reference and CIGAR per read, timed")
+    ap.add_argument("--meth", action="store_true", help="add call-methylation after --calibrate, on the references and CIGARs of --realign (which it implies), timed")
     a = ap.parse_args()
+    a.realign = a.realign or a.meth
     if a.realign and not a.calibrate:
-        ap.error("--realign runs on what --calibrate leaves: give both")
+        ap.error("--realign and --meth run on what --calibrate leaves: give both")
     if a.signal:
         return main_signal(a)
     import genarchbench_amd  # noqa: F401  (before torch: the runtime's default for pageable copies)
@@ -266,6 +323,7 @@ def main():
     rmap = torch.empty((int(n_kmers.sum()), 2), dtype=torch.int32, device="cuda") if a.calibrate else None
     cal = torch.zeros(a.reads * abea.CALIB.itemsize, dtype=torch.uint8, device="cuda")
     realign = Realign(torch, rng, packed) if a.realign else None
+    meth = Meth(torch, rng, h, mean, stdv, realign.dev, realign.aln) if a.meth else None
     walls, stats, cals = [], [], []
     for it in range(a.repeats + 1):                                  # the first run allocates: not counted
         torch.cuda.synchronize()
@@ -276,6 +334,8 @@ def main():
             cals.append(timed_calibrate(h, torch, dev[:8], pairs, dev[8], res, rmap, d_mo, cal))
         if realign:
             cals[-1].update(realign.timed(h, dev[2], dev[3], dev[4], dev[5], rmap, d_mo, cal))
+        if meth:
+            cals[-1].update(meth.timed(h, dev[2], dev[3], dev[4], dev[5], rmap, d_mo, cal))
     rec = res.cpu().numpy().view(abea.READ)
     order = np.argsort(walls[1:]); mid = 1 + int(order[len(order) // 2])
     st, wall = stats[mid], walls[mid]
@@ -289,6 +349,8 @@ def main():
         out.update(calibrate_report(cals[1:], cal.cpu().numpy().view(abea.CALIB)))
     if realign:
         out.update(realign.report(cals[1:]))
+    if meth:
+        out.update(meth.report(cals[1:]))
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
