@@ -1,12 +1,14 @@
 """abea's event detection and scaling estimate on the GPU: gab_abea_events / gab_abea_scalings and their device forms against the
 model (tests/abea_events_model.py) on every output array and count, bit for bit (NaNs by bit pattern), against the reference's
-recorded results on the golden fixture, and the counters that show which route a read's sums and a chunk's detector took."""
+recorded results on the golden fixture and on the case fixture (tests/golden/abea_events_cases.npz), and the counters that show which route a read's sums and a chunk's detector took."""
 import numpy as np
 import pytest
 
+import abea_events_cases as CASES
 import abea_events_model as M
 import abea_model as A
-from test_abea_events_model import load_events_fixture, model_events_of_fixture
+from abea_events_cases import signal
+from test_abea_events_model import load_events_fixture, model_events_of_case_fixture, model_events_of_fixture
 from test_abea_model import load_fixture
 
 pytestmark = pytest.mark.gpu
@@ -26,11 +28,6 @@ def aligner():
 @pytest.fixture(scope="module")
 def level_mean():
     return load_fixture()[0][0]
-
-
-def signal(sig):
-    """a generated read (codes, range, digitisation, offset, bases) as the library takes it: float samples"""
-    return (sig[0].astype(F), sig[1], sig[2], sig[3])
 
 
 def model_of(s):
@@ -62,29 +59,8 @@ def shape():
 
 @pytest.fixture(scope="module")
 def mixed(level_mean, shape):
-    """37 reads of every kind in shuffled order, with the model's answer for each"""
-    chunk, warmup = shape
-    rng = np.random.default_rng(23)
-    _, fixture, _ = load_events_fixture()
-    named = {}
-    for n in (1, 2, 5, 6, 11, 12, 13, 24):
-        named[f"tiny_{n}"] = signal(M.make_signal(rng, n, level_mean))
-    for n in (chunk - 1, chunk, chunk + 1, 2 * chunk + warmup):
-        named[f"chunk_{n}"] = signal(M.make_signal(rng, n, level_mean))
-    named["flat_run"] = signal(M.find_flat_run_read(level_mean, chunk, warmup)[0])
-    named["flat_read"] = (np.full(300, 417.0, F), F(1402.882), F(8192.0), F(3.0))
-    for v in (1e-30, 3e30, np.nan, np.inf):
-        sig = M.make_signal(rng, 1500, level_mean)
-        named[f"planted_{v}"] = M.with_planted(*sig[:4], 1100, v)
-    small = sorted(range(len(fixture)), key=lambda i: fixture[i][0].size)[:4]
-    for i in small:
-        named[f"fixture_{i}"] = signal(fixture[i])
-    for t in range(37 - len(named)):
-        named[f"plain_{t}"] = signal(M.make_signal(rng, int(rng.integers(50, 1800)), level_mean))
-    names = list(named)
-    names = [names[i] for i in rng.permutation(len(names))]
-    assert len(names) == 37
-    signals = [named[n] for n in names]
+    """37 reads of every kind in shuffled order (tests/abea_events_cases.py), with the model's answer for each"""
+    names, signals, _ = CASES.mixed_cases(level_mean, *shape)
     return names, signals, [model_of(s) for s in signals]
 
 
@@ -145,14 +121,10 @@ def test_a_peak_near_the_end_whose_event_is_the_last(aligner, level_mean):
     run(aligner, [s], [w], ["step_at_the_end"])
 
 
-def test_the_mixed_batch_in_host_and_device_form(aligner, mixed, shape):
+def device_form(aligner, signals, want, names):
+    """the device entry on torch tensors: counts, offsets, total, the four slabs against `want`, and nothing behind the events"""
     import torch
     from genarchbench_amd import abea
-    names, signals, want = mixed
-    _, st = run(aligner, signals, want, names)
-    redo = sum(M.chunks_to_redo(*w["tstat"], *shape) for w in want)
-    assert st["reads_serial_sums"] == 4 and st["chunks_redone"] == redo >= 1
-    assert st["chunks"] == sum(-(-s[0].size // shape[0]) for s in signals)
     packed = abea.pack_signals(signals)
     dev = [torch.from_numpy(a).cuda() for a in packed]
     n, total = len(signals), sum(w["mean"].size for w in want)
@@ -166,6 +138,16 @@ def test_the_mixed_batch_in_host_and_device_form(aligner, mixed, shape):
     got = [dict(zip(ARRAYS, (a[o:o + k] for a in host))) for o, k in zip(eo, ne)]
     check_events(got, want, names)
     assert all((a[total:] == -7).all() for a in host)                 # nothing behind the events
+    return got
+
+
+def test_the_mixed_batch_in_host_and_device_form(aligner, mixed, shape):
+    names, signals, want = mixed
+    _, st = run(aligner, signals, want, names)
+    redo = sum(M.chunks_to_redo(*w["tstat"], *shape) for w in want)
+    assert st["reads_serial_sums"] == 4 and st["chunks_redone"] == redo >= 1
+    assert st["chunks"] == sum(-(-s[0].size // shape[0]) for s in signals)
+    device_form(aligner, signals, want, names)
     st2 = aligner.events_last_stats()
     assert {k: st2[k] for k in ("samples", "events", "reads_serial_sums", "chunks", "chunks_redone")} == {k: st[k] for k in ("samples", "events", "reads_serial_sums", "chunks", "chunks_redone")}
     assert 0 < st2["sums_ms"] and 0 < st2["detect_ms"] and 0 < st2["fill_ms"] and st2["kernel_ms"] <= st2["total_ms"] * 1.001
@@ -227,20 +209,12 @@ def test_the_golden_fixture_equals_the_reference(aligner, level_mean):
 
 
 def test_scalings_edge_cases(aligner, level_mean):
-    rng = np.random.default_rng(31)
-    bases = lambda n: bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n).tolist())
-    seq = bases(120)
     # 20 000 events: the order of addition shows in the sum of the squared double differences, and for events of every magnitude
     # in the plain sum too
-    many = (rng.uniform(60, 130, 20000) + rng.standard_normal(20000) * 0.37).astype(F)
+    reads, many, wild = CASES.scalings_edge_cases()
     d = many.astype(np.float64) - 0.123456789
     assert M.pairwise_sum(d * d) != np.add.accumulate(d * d)[-1]
-    wild = (many * 10.0 ** rng.uniform(-8, 8, 20000)).astype(F)
     assert M.pairwise_sum(wild.astype(np.float64)) != np.add.accumulate(wild.astype(np.float64))[-1]
-    reads = [(bases(6), np.array([93.25], F)),                        # one k-mer, one event
-             (seq[:40] + b"N" + seq[41:80] + b"a" + seq[81:], rng.uniform(60, 130, 200).astype(F)),
-             (bases(3000), many), (bases(2500), wild),
-             (bases(70), rng.uniform(60, 130, 64).astype(F)), (bases(69), rng.uniform(60, 130, 65).astype(F))]
     check_scalings(aligner, reads, level_mean)
     scale, _ = aligner.estimate_scalings(reads[:1])
     assert scale[0] == 1.0                                            # one event on one k-mer: the shift takes all of the difference
@@ -264,16 +238,13 @@ def test_scalings_take_every_route(level_mean):
     """a pore model on a grid of 1/4 pA makes the sum of squared levels provable too; one with a level of 1e-30 forces the two
     k-mer sums of a read that has that k-mer into the reference's order"""
     from genarchbench_amd.abea import EventAligner
-    rng = np.random.default_rng(41)
-    bases = lambda n: bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n).tolist())
     stdv = np.full(A.NKMER, 2.0, F)
-    reads = [(bases(400), rng.uniform(60, 130, 700).astype(F)), (bases(90) + b"AAAAAA" + bases(50), rng.uniform(60, 130, 300).astype(F))]
-    coarse = (np.round(level_mean * 4) / 4).astype(F)
+    reads = CASES.scalings_route_cases()
+    coarse, tiny = (CASES.route_models(level_mean)[m] for m in ("coarse", "tiny"))
     h = EventAligner(coarse, stdv)
     st = check_scalings(h, reads, coarse)
     assert (st["event_sums_in_order"], st["kmer_sums_in_order"], st["kmer_sq_sums_in_order"]) == (0, 0, 0)
     h.close()
-    tiny = level_mean.copy(); tiny[0] = F(1e-30)                      # rank 0: AAAAAA
     h = EventAligner(tiny, stdv)
     st = check_scalings(h, reads, tiny)
     assert (st["event_sums_in_order"], st["kmer_sums_in_order"], st["kmer_sq_sums_in_order"]) == (0, 1, 2)
@@ -297,3 +268,63 @@ def test_signal_to_pairs_equals_the_model_aligned_on_the_references_events(align
         assert got == rec, f"read {i}: {got} != {rec}"
         p = pairs[pair_off[t]:pair_off[t] + rec["path_len"]]
         assert np.array_equal(p["ref_pos"], path[:, 0]) and np.array_equal(p["read_pos"], path[:, 1]), i
+
+
+# ---- the case fixture: the reference's record of the constructed reads --------------------------------------------------------------
+@pytest.fixture(scope="module")
+def case_fixture():
+    """abea_events_cases.npz: level_mean, signals (with their bases), scalings reads, the reference's record, the model's event tables"""
+    lm, signals, given, exp = CASES.load_cases()
+    return lm, signals, given, exp, model_events_of_case_fixture()
+
+
+def against_the_reference(got, exp):
+    for g, want in zip(got, exp["reads"]):
+        if want["name"] not in exp["undefined_in_reference"]:         # (the flat read, which the reference refuses: model only)
+            assert (g["mean"].size, M.events_digest(g)) == (want["n_events"], want["events"]), want["name"]
+
+
+def test_the_case_fixture_equals_the_reference_and_the_model_in_host_and_device_form(aligner, case_fixture, shape):
+    """the reads around the chunk size, the flat run that makes a chunk run again, the four planted reads whose sums go in order, reads
+    of 1000 and 1001 samples, two square waves: the four arrays and n_events of every read against the reference's digest and against
+    the model, in one host call and in the device form, with the route counters"""
+    _, signals, _, exp, want = case_fixture
+    names = [r["name"] for r in exp["reads"]][:len(signals)]
+    sigs = [s[:4] for s in signals]
+    got, st = run(aligner, sigs, want, names)
+    against_the_reference(got, exp)
+    redo = sum(M.chunks_to_redo(*w["tstat"], *shape) for w in want)
+    assert st["reads_serial_sums"] == sum(n.startswith("planted_") for n in names) == 4 and st["chunks_redone"] == redo >= 1
+    assert st["chunks"] == sum(-(-s[0].size // shape[0]) for s in sigs)
+    against_the_reference(device_form(aligner, sigs, want, names), exp)
+    st2 = aligner.events_last_stats()
+    assert all(st2[k] == st[k] for k in ("samples", "events", "reads_serial_sums", "chunks", "chunks_redone"))
+
+
+def test_the_scalings_of_the_case_fixture_equal_the_reference(aligner, case_fixture, level_mean):
+    """scale and shift of every read the reference accepted, on the events the library detects, and of the scaling edge cases; then the
+    two reads of the extra pore models (levels on a grid of 1/4 pA; a level of 1e-30) on handles of their own"""
+    from genarchbench_amd.abea import EventAligner
+    lm, signals, given, exp, _ = case_fixture
+    assert lm.tobytes() == level_mean.tobytes()
+    got = aligner.detect_events([s[:4] for s in signals])
+    reads = [(s[4], g["mean"]) for s, g in zip(signals, got)] + given
+    records = exp["reads"]
+    assert len(reads) == len(records)
+    main = [i for i, w in enumerate(records) if w["pore_model"] == "level_mean" and w["name"] not in exp["undefined_in_reference"]]
+    scale, shift = aligner.estimate_scalings([reads[i] for i in main])
+    assert [float(x).hex() for x in scale] == [records[i]["scale"] for i in main]
+    assert [float(x).hex() for x in shift] == [records[i]["shift"] for i in main]
+    # ... and against the model bit for bit, with the counters of the sums added in order, where the result is a number (the reads with
+    # a planted NaN or inf give a NaN, whose sign no rule fixes: the record above, "nan", is all the reference says of it)
+    numbers = [i for i in main if "nan" not in (records[i]["scale"], records[i]["shift"])]
+    assert len(numbers) == len(main) - 2
+    check_scalings(aligner, [reads[i] for i in numbers], level_mean)
+    for name, model in CASES.route_models(level_mean).items():
+        pick = [i for i, w in enumerate(records) if w["pore_model"] == name]
+        assert len(pick) == 2
+        h = EventAligner(model, np.full(A.NKMER, 2.0, F))
+        scale, shift = h.estimate_scalings([reads[i] for i in pick])
+        h.close()
+        assert [float(x).hex() for x in scale] == [records[i]["scale"] for i in pick]
+        assert [float(x).hex() for x in shift] == [records[i]["shift"] for i in pick]

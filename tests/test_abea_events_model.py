@@ -10,20 +10,12 @@ import os
 import numpy as np
 import pytest
 
+import abea_events_cases as CASES
 import abea_events_model as M
+from abea_events_cases import load_events_fixture  # noqa: F401  (the other abea tests import it from here)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 F = np.float32
-
-
-def load_events_fixture():
-    """-> (level_mean, reads as (codes int16, range, digitisation, offset, bases), the recorded reference)"""
-    z = np.load(os.path.join(GOLDEN, "abea_events_small.npz"))
-    exp = json.load(open(os.path.join(GOLDEN, "abea_events_expected.json")))
-    so = np.concatenate([[0], np.cumsum(z["n_samples"], dtype=np.int64)]); qo = np.concatenate([[0], np.cumsum(z["seq_len"], dtype=np.int64)])
-    reads = [(z["codes"][so[i]:so[i + 1]], z["range"][i], z["digitisation"][i], z["offset"][i], z["seq"][qo[i]:qo[i + 1]].tobytes())
-             for i in range(z["n_samples"].size)]
-    return np.load(os.path.join(GOLDEN, "abea_small.npz"))["level_mean"], reads, exp
 
 
 _MODEL_EVENTS = {}
@@ -31,10 +23,65 @@ _MODEL_EVENTS = {}
 
 def model_events_of_fixture():
     """the model's event table of every fixture read, computed once per process"""
-    if not _MODEL_EVENTS:
+    if "ev" not in _MODEL_EVENTS:
         _, reads, _ = load_events_fixture()
         _MODEL_EVENTS["ev"] = [M.events_of(r[0].astype(F), r[1], r[2], r[3]) for r in reads]
     return _MODEL_EVENTS["ev"]
+
+
+def model_events_of_case_fixture():
+    """the model's event table of every signal of abea_events_cases.npz, computed once per process"""
+    if "cases" not in _MODEL_EVENTS:
+        _, signals, _, _ = CASES.load_cases()
+        _MODEL_EVENTS["cases"] = [M.events_of(*s[:4]) for s in signals]
+    return _MODEL_EVENTS["cases"]
+
+
+def pore_models(level_mean):
+    return {"level_mean": level_mean, **CASES.route_models(level_mean)}
+
+
+def test_the_case_fixture_is_the_one_the_reference_ran_on():
+    """abea_events_cases.npz by its hash, and its reads byte for byte those that abea_events_cases.py builds for the GPU tests"""
+    level_mean, signals, given, exp = CASES.load_cases()
+    path = os.path.join(GOLDEN, exp["fixture"])
+    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == exp["fixture_sha256"] and os.path.getsize(path) < 500_000
+    names, built, seqs = CASES.reference_signals(level_mean)
+    assert [r["name"] for r in exp["reads"]][:len(names)] == names and exp["signals"] == len(signals) == len(names)
+    for n, s, q, g in zip(names, built, seqs, signals):
+        assert g[0].tobytes() == np.asarray(s[0], F).tobytes() and g[4] == q, n
+        assert [F(x).tobytes() for x in g[1:4]] == [F(x).tobytes() for x in s[1:4]], n
+    edge, route = CASES.scalings_edge_cases()[0], CASES.scalings_route_cases()
+    assert [r["name"] for r in exp["reads"]][len(names):len(names) + len(edge)] == list(CASES.EDGE_NAMES)
+    for (q, e), g in zip(edge + route + route, given):
+        assert g[0] == q and g[1].tobytes() == e.tobytes()
+    # what the reference was not given (below 1000 samples) or refused (the flat read: its discarded trim step finds no start)
+    assert set(CASES.not_run_in_reference(level_mean)) | {"flat_1500"} == set(exp["undefined_in_reference"])
+    assert exp["undefined_in_reference"]["flat_1500"] == "rt.end > rt.start"
+    for n in [f"chunk_{k}" for k in (1023, 1024, 1025, 2112)] + ["flat_run", "samples_1000", "samples_1001", "square_wave_14", "square_wave_6"] + \
+            [f"planted_{v}" for v in (1e-30, 3e30, np.nan, np.inf)]:
+        assert n in names and n not in exp["undefined_in_reference"], n
+
+
+def test_model_reproduces_the_reference_on_every_defined_case():
+    """the four event arrays and n_events of every signal the reference accepted, and scale / shift of every read under its pore model
+    (the scaling edge cases and the two extra pore models included), bit for bit"""
+    level_mean, signals, given, exp = CASES.load_cases()
+    models = pore_models(level_mean)
+    events = model_events_of_case_fixture()
+    reads = [(s[4], ev["mean"]) for s, ev in zip(signals, events)] + given
+    assert len(reads) == len(exp["reads"])
+    defined = 0
+    for i, ((seq, means), want) in enumerate(zip(reads, exp["reads"])):
+        if want["name"] in exp["undefined_in_reference"]:
+            assert want.get("undefined_in_reference")
+            continue
+        if i < len(signals):
+            assert (events[i]["mean"].size, M.events_digest(events[i])) == (want["n_events"], want["events"]), want["name"]
+        scale, shift = M.scalings(seq, means, models[want["pore_model"]])
+        assert (float(scale).hex(), float(shift).hex()) == (want["scale"], want["shift"]), want["name"]
+        defined += 1
+    assert defined == len(reads) - 1
 
 
 def test_the_fixture_is_the_one_the_reference_ran_on():

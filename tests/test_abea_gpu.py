@@ -1,53 +1,33 @@
 """abea on the GPU: gab_abea_align / gab_abea_align_device against the model (tests/abea_model.py) on every field of gab_abea_read
-and every pair of the path, bit for bit, and against the reference's recorded results on the golden fixture."""
+and every pair of the path, bit for bit, and against the reference's recorded results on the golden fixture and on the case fixture
+(tests/golden/abea_cases.npz: the constructed reads of tests/abea_cases.py), where the fields the reference computes but does not
+return are also compared with their recomputation from the path (tests/abea_path_checks.py)."""
 import numpy as np
 import pytest
 
+import abea_cases as CASES
 import abea_model as M
-from test_abea_model import load_fixture
+import abea_path_checks as P
+from test_abea_model import load_fixture, model_of_cases, recorded
 
 pytestmark = pytest.mark.gpu
 FIELDS = ("n_pairs", "path_len", "end_event", "max_gap", "flags", "avg_log_emission", "fills")
 
 
-def _bases(rng, n):
-    return bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), n).tolist())
+@pytest.fixture(scope="module")
+def cases():
+    """model, the named edge cases and the three long reads of the fixture (tests/abea_cases.py), in shuffled order, with the model's
+    answer for each"""
+    (mean, stdv, lstd), names, reads = CASES.named_cases()
+    want = [M.align(r[0], r[1], mean, stdv, lstd, r[2], r[3]) for r in reads]
+    return (mean, stdv, lstd), names, reads, want
 
 
 @pytest.fixture(scope="module")
-def cases():
-    """model, the named edge cases and the three long reads of the fixture, in shuffled order, with the model's answer for each"""
-    rng = np.random.default_rng(11)
-    (mean, stdv, lstd), fixture, _ = load_fixture()
-    named = {}
-    one = _bases(rng, 6)
-    for n in (1, 2, 300):                                            # one k-mer
-        named[f"one_kmer_{n}_events"] = (one, M.make_events(rng, one, mean, stdv, counts=[n]), 1.0, 0.0)
-    named["under_100_bands_a"] = M.make_read(rng, 20, mean, stdv)    # clipped on all four sides
-    named["under_100_bands_b"] = M.make_read(rng, 35, mean, stdv, counts=np.full(30, 1))
-    s = _bases(rng, 45)
-    named["bands_99"] = (s, M.make_events(rng, s, mean, stdv, counts=[2] * 17 + [1] * 23), 1.0, 0.0)      # 40 k-mers + 57 events + 2
-    named["bands_100"] = (s, M.make_events(rng, s, mean, stdv, counts=[2] * 18 + [1] * 22), 1.0, 0.0)
-    named["bands_101"] = (s, M.make_events(rng, s, mean, stdv, counts=[2] * 19 + [1] * 21), 1.0, 0.0)
-    named["half_an_event_per_kmer"] = M.make_read(rng, 405, mean, stdv, counts=np.arange(400) % 2)
-    named["five_events_per_kmer"] = M.make_read(rng, 150, mean, stdv, counts=np.full(145, 5))
-    named["one_event_300_bases"] = (_bases(rng, 300), np.array([95.0], np.float32), 1.0, 0.0)
-    named["no_end_nan_events"] = (_bases(rng, 80), np.full(120, np.nan, np.float32), 1.0, 0.0)
-    named["gap_one_event_60_kmers"] = (_bases(rng, 65), np.array([95.0], np.float32), 1.0, 0.0)
-    named["gap_run_of_55"] = M.make_gap_read(rng, mean, stdv)
-    seq, ev, sc, sh = M.make_read(rng, 200, mean, stdv)
-    named["wrong_shift"] = (seq, ev, sc, np.float32(sh + np.float32(15.0)))
-    seq, ev, sc, sh = M.make_read(rng, 180, mean, stdv)
-    named["non_acgt"] = (seq[:50] + b"N" + seq[51:90] + b"a" + seq[91:], ev, sc, sh)
-    named["plain"] = M.make_read(rng, 260, mean, stdv)
-    longs = sorted(range(len(fixture)), key=lambda i: -len(fixture[i][0]))[:3]
-    for i in longs:
-        named[f"long_{i}"] = fixture[i]
-    names = list(named)
-    names = [names[i] for i in rng.permutation(len(names))]
-    reads = [named[n] for n in names]
-    want = [M.align(r[0], r[1], mean, stdv, lstd, r[2], r[3]) for r in reads]
-    return (mean, stdv, lstd), names, reads, want
+def case_fixture():
+    """abea_cases.npz: names, reads, the reference's record and the model's answers"""
+    model, names, reads, exp = CASES.load_cases()
+    return model, names, reads, exp, model_of_cases()
 
 
 @pytest.fixture(scope="module")
@@ -111,10 +91,10 @@ def test_a_small_trace_budget_cuts_the_call_into_launches_with_the_same_output(c
     check(names[:5], want[:5], pairs, pair_off, res)
 
 
-def test_device_call_with_torch_tensors_equals_the_host_call(cases, aligner):
+def device_call(aligner, reads):
+    """the host call and the device call on torch tensors -> (pair_off, host pairs, host records, device pairs, device records)"""
     import torch
     from genarchbench_amd import abea
-    _, names, reads, want = cases
     packed = abea.pack_reads(reads)
     host_pairs, pair_off, host_res = aligner.align(*packed)
     dev = [torch.from_numpy(a).cuda() for a in packed]
@@ -122,11 +102,76 @@ def test_device_call_with_torch_tensors_equals_the_host_call(cases, aligner):
     pairs = torch.full((room, 2), -1, dtype=torch.int32, device="cuda")
     res = torch.zeros(len(reads) * abea.READ.itemsize, dtype=torch.uint8, device="cuda")
     aligner.align_device(*dev[:8], pairs, dev[8], res)
-    got_res = res.cpu().numpy().view(abea.READ)
-    got_pairs = pairs.cpu().numpy().reshape(-1).view(abea.PAIR)
+    return pair_off, host_pairs, host_res, pairs.cpu().numpy().reshape(-1).view(abea.PAIR), res.cpu().numpy().view(abea.READ)
+
+
+def test_device_call_with_torch_tensors_equals_the_host_call(cases, aligner):
+    _, names, reads, want = cases
+    pair_off, _, host_res, got_pairs, got_res = device_call(aligner, reads)
     assert got_res.tobytes() == host_res.tobytes()
     check(names, want, got_pairs, pair_off, got_res)
     assert aligner.last_stats()["cells"] == int(got_res["fills"].sum())
+
+
+# ---- the case fixture: the reference's record, the recomputation from the path, the model ------------------------------------------
+def check_case_fixture(case_fixture, pairs, pair_off, res):
+    """every read of abea_cases.npz: n_pairs, path_len and the path against the reference's record; end_event, max_gap, flags and
+    avg_log_emission (an equal double) against the recomputation from the path (tests/abea_path_checks.py) and against what the
+    golden script recorded of it from the reference's own path; every field and pair against the model.  fills depends on the band
+    moves, which the reference does not show: it is compared with the model only."""
+    model, names, reads, exp, want = case_fixture
+    check(names, want, pairs, pair_off, res)
+    for i, (name, r, w) in enumerate(zip(names, reads, exp["reads"])):
+        if name in exp["undefined_in_reference"]:
+            continue
+        if name == exp["deviation"]["name"]:                          # the reference backtracks from event 0; the library's rule
+            assert res[i]["flags"] == M.NO_END and res[i]["path_len"] == 0
+            continue
+        p = pairs[pair_off[i]:pair_off[i] + res[i]["path_len"]]
+        path = np.stack([p["ref_pos"], p["read_pos"]], 1)
+        assert (int(res[i]["n_pairs"]), int(res[i]["path_len"]), M.pairs_digest(path)) == (w["n_pairs"], w["path_len"], w["pairs"]), name
+        chk = P.recompute(r[0], r[1], *model, r[2], r[3], path)
+        assert P.agrees(res[i], chk), f"{name}: {res[i]} != {chk}"
+        assert (chk["end_event"], chk["admissible"], np.float64(chk["avg_log_emission"]).tobytes()) == recorded(w), name
+
+
+def test_the_case_fixture_in_one_host_call_and_in_the_device_call(case_fixture, aligner):
+    reads = case_fixture[2]
+    pair_off, host_pairs, host_res, dev_pairs, dev_res = device_call(aligner, reads)
+    assert aligner.last_stats()["launches"] == 1
+    check_case_fixture(case_fixture, host_pairs, pair_off, host_res)
+    assert dev_res.tobytes() == host_res.tobytes()
+    check_case_fixture(case_fixture, dev_pairs, pair_off, dev_res)
+
+
+def test_the_case_fixture_cut_into_launches(case_fixture, aligner, monkeypatch):
+    reads = case_fixture[2]
+    bands = sum(len(r[0]) - M.K + 1 + len(r[1]) + 2 for r in reads)
+    monkeypatch.setenv("GAB_ABEA_TRACE_BYTES", str(32 * (bands // 4)))      # 32 bytes of trace per band: four launches at least
+    pairs, pair_off, res = aligner.align_reads(reads)
+    st = aligner.last_stats()
+    assert st["launches"] >= 3 and st["bands"] == bands
+    check_case_fixture(case_fixture, pairs, pair_off, res)
+
+
+def test_the_threshold_cases_by_name(case_fixture, aligner):
+    """max_gap 50 passes and 51 sets GAP alone; the two reads whose shifts are neighbouring floats differ in LOW_EMISSION alone; the
+    path lengths around the 64 lanes of the emission sum and of the move of the path; the paths that all but fill their room"""
+    model, names, reads, exp, _ = case_fixture
+    pick = ["max_gap_50", "max_gap_51", "emission_above", "emission_below", "room_one_short", "room_tightest"] + [f"path_len_{n}" for n in CASES.PATH_LENGTHS]
+    pairs, pair_off, res = aligner.align_reads([reads[names.index(n)] for n in pick])
+    got = dict(zip(pick, res))
+    assert (got["max_gap_50"]["max_gap"], got["max_gap_50"]["flags"]) == (50, 0) and got["max_gap_50"]["n_pairs"] == got["max_gap_50"]["path_len"] > 0
+    assert (got["max_gap_51"]["max_gap"], got["max_gap_51"]["flags"], got["max_gap_51"]["n_pairs"]) == (51, M.GAP, 0)
+    above, below = got["emission_above"], got["emission_below"]
+    assert (float(above["avg_log_emission"]).hex(), float(below["avg_log_emission"]).hex()) == (exp["emission_bracket"]["above"], exp["emission_bracket"]["below"])
+    assert above["avg_log_emission"] >= -5.0 > below["avg_log_emission"]
+    assert (above["flags"], below["flags"]) == (0, M.LOW_EMISSION) and above["n_pairs"] == above["path_len"] > 0 and below["n_pairs"] == 0
+    for n in CASES.PATH_LENGTHS:
+        assert got[f"path_len_{n}"]["path_len"] == got[f"path_len_{n}"]["n_pairs"] == n
+    room = lambda n: len(reads[names.index(n)][0]) - M.K + 1 + len(reads[names.index(n)][1])
+    assert room("room_one_short") - got["room_one_short"]["path_len"] == 1
+    assert room("room_tightest") - got["room_tightest"]["path_len"] == exp["room_tightest"]
 
 
 def test_the_golden_fixture_equals_the_reference(aligner):
