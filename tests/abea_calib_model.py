@@ -190,6 +190,37 @@ def changing_bases(rng, n_kmers):
             return seq
 
 
+def changing_bases_repaired(rng, n_kmers):
+    """the same property for a read so long that a draw without a run of K + 1 equal bases is rare: the last base of every such run
+    is replaced until there is none"""
+    seq = bytearray(bases(rng, n_kmers + K - 1))
+    while True:
+        same = np.flatnonzero(np.diff(A.kmer_ranks(bytes(seq))) == 0)
+        if same.size == 0:
+            return bytes(seq)
+        for k in same.tolist():                       # k-mers k and k + 1 are equal: bases k .. k + K are one base
+            seq[k + K] = int(rng.choice([b for b in b"ACGT" if b != seq[k]]))
+
+
+LONG_SEED = 20251202
+LONG_KMERS = (16384, 16385, 32769)                    # the map kernel's threads take k-mers 16384 apart: one trip, a second for one k-mer, a third
+STRIDE_EDGES = (16383, 16384, 32768)
+
+
+def long_reads(mean, stdv):
+    """name -> (bases, events, scale, shift, path): reads of LONG_KMERS k-mers, generated where they are used and never stored.  A
+    tenth of the k-mers have no event; in one variant the k-mers on both sides of the stride are among them, in the other they have one"""
+    out = {}
+    for n in LONG_KMERS:
+        for with_events in (0, 1):
+            rng = np.random.default_rng([LONG_SEED, n, with_events])
+            counts = rng.choice(3, n, p=(0.1, 0.6, 0.3))
+            counts[0] = 1
+            counts[[k for k in STRIDE_EDGES if k < n]] = with_events
+            out[f"kmers_{n}_{'events' if with_events else 'none'}_at_the_stride"] = read_of_counts(rng, changing_bases_repaired(rng, n), counts, mean, stdv)
+    return out
+
+
 VAR_FACTORS = (2.0, 2.4, 2.6, 3.0)
 EPB_COUNTS = (5, 6)
 M_COUNTS = (199, 200, 201)

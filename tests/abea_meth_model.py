@@ -402,8 +402,39 @@ def make_cases(model, bpl=BLOCKS_PER_LANE, one=ONE_BLOCK_KMERS):
     c["strand"] = simple(140, [60])                      # a forward read whose sub_end looks up an event far before sub_start's
     c["strand"]["map"][70] = (3, 3)
     c["transitions"] = simple(120, [60], epb=0.8)
+    # the window of get_closest_event_to around the k-mer of sub_start (read position first CpG - 10 of a forward read): back from
+    # k_idx to k_idx - 999, never entry k_idx - 1000 and never entry 0; then ahead from k_idx to k_idx + 999, never the last entry
+    for name, (n, first, empty) in WINDOW_CASES.items():
+        cnt = np.ones(n - K + 1, np.int64)
+        cnt[list(empty)] = 0
+        c[name] = simple(n, [first], counts=cnt)
+        assert (c[name]["map"][:, 0] == -1).sum() == (cnt == 0).sum()
+    # group starts on the edges of the 64 reference positions that the kernel looks at per step, and look-backs and groups across them
+    for name, (n, at, rev) in STEP_CASES.items():
+        c[name] = simple(n, at, rev=rev)
     return c
 
 
-DEVIATIONS = ("no_event", "strand", "transitions")
+# name -> (bases, position of the one CpG, the k-mers that have no event: their map entries are (-1, -1)); k_idx = first - 10
+WINDOW_CASES = {
+    **{f"behind_{d}": (200, 110, range(100 - d + 1, 101)) for d in (63, 64, 65)},   # the nearest event behind k_idx at distance d
+    "behind_999": (1200, 1060, range(52, 1051)),                     # found: the last entry the walk back reads
+    "behind_1000": (1200, 1060, range(51, 1051)),                    # entry 50 is not read: the event is entry 1051's, from the walk ahead
+    "behind_1000_nothing_ahead": (2100, 1020, range(11, 2010)),      # ... and entries 1010 .. 2009 have none: entry 2010 is not read, NO_EVENT
+    "ahead_999": (1200, 21, range(0, 1010)),                         # nothing behind k_idx = 11; entry 1010 is the last the walk ahead reads
+    "ahead_1000": (1200, 21, range(0, 1011)),                        # entry 1011 is not read: NO_EVENT
+    "entry_0_only": (200, 21, range(1, 12)),                         # entry 0 is not read going back from 11, the lowest k_idx of a scored group
+    "last_entry_only": (200, 100, range(0, 194)),                    # the last entry, 194, is not read: the first and the last pair find no
+}                                                                    # event, the record is emptied and the group is unbounded
+WINDOW_NO_EVENT = ("behind_1000_nothing_ahead", "ahead_1000")
+# name -> (bases, CpG positions, reverse read)
+STEP_CASES = {
+    **{f"start_{p}": (200, [p], False) for p in (63, 64, 127, 128)},
+    "start_64_reverse": (200, [64], True), "start_127_reverse": (200, [127], True),
+    "sites_54_64": (200, [54, 64], False), "sites_54_64_reverse": (200, [54, 64], True),      # one group: the look-back from 64 crosses the step
+    "sites_53_64": (200, [53, 64], False), "sites_53_64_reverse": (200, [53, 64], True),      # two groups
+    "group_60_to_130": (220, group_of(60, 70), False), "group_60_to_130_reverse": (220, group_of(60, 70), True),
+    "site_at_ref_len_minus_2": (120, [60, 118], False),              # the last position a site can have; its sub-sequence ends past the reference
+}
+DEVIATIONS = ("no_event", "strand", "transitions") + WINDOW_NO_EVENT
 FLAT_CASES = ("flat_model",)

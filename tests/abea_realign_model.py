@@ -485,10 +485,29 @@ def make_cases(model):
     c["strand"]["map"][:, :] += 50
     c["strand"]["events"] = np.concatenate([np.full(50, 90.0, F), c["strand"]["events"]])
     c["strand"]["map"][100] = (10, 11)
+    # the window of get_closest_event_to around the k-mer looked up first: read position k_idx, behind a soft clip of that length.
+    # Back from k_idx to k_idx - 999, never entry k_idx - 1000 and never entry 0; then ahead from k_idx to k_idx + 999, never the last entry
+    for name, (n, k_idx, empty) in WINDOW_CASES.items():
+        cnt = np.full(n - K + 1, 2, np.int64)
+        cnt[[e for e in empty if e < n - K + 1]] = 0
+        c[name] = case(rng, model, B(n), ops=[("S", k_idx), ("M", n - k_idx)], counts=cnt)
+        assert (c[name]["map"][:, 0] == -1).sum() == (cnt == 0).sum()
     return c
 
 
-DEVIATIONS = ("no_event", "strand")
+# name -> (bases, k_idx, the k-mers that have no event: their map entries are (-1, -1))
+WINDOW_CASES = {
+    **{f"behind_{d}": (200, 70, range(70 - d + 1, 71)) for d in (63, 64, 65)},      # the nearest event behind k_idx at distance d: a 64-entry chunk ends there
+    "behind_999": (1200, 1050, range(52, 1051)),                     # found: the last entry the walk back reads
+    "behind_1000": (1200, 1050, range(51, 1051)),                    # entry 50 is not read: the event is entry 1051's, from the walk ahead
+    "behind_1000_nothing_ahead": (2100, 1010, range(11, 2010)),      # ... and entries 1010 .. 2009 have none: entry 2010 is not read, NO_EVENT
+    "ahead_999": (1200, 5, range(0, 1004)),                          # nothing behind; entry 1004 is the last the walk ahead reads
+    "ahead_1000": (1200, 5, range(0, 1005)),                         # entry 1005 is not read: NO_EVENT
+    "entry_0_only": (200, 5, range(1, 6)),                           # entry 0 is not read going back from 5: the event is entry 6's
+    "last_entry_only": (200, 5, range(0, 194)),                      # the last entry, 194, is not read going ahead: NO_EVENT
+}
+WINDOW_NO_EVENT = ("behind_1000_nothing_ahead", "ahead_1000", "last_entry_only")
+DEVIATIONS = ("no_event", "strand") + WINDOW_NO_EVENT
 FLAT_CASES = ("flat_model",)
 
 

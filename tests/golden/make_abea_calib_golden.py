@@ -2,7 +2,8 @@
 """Build machine only: writes tests/golden/abea_calib_small.npz (the reference's path for every read of abea_small.npz, one byte per
 pair, and the constructed cases of tests/abea_calib_model.py's seeded generator: bases, event means, scalings and lattice paths) and
 tests/golden/abea_calib_expected.json (what the reference's postalign, abea/src/align.c:550-650, and recalibrate_model,
-align.c:655-762, return per read, and the flag that the checks of abea/src/f5c.c:1474-1501 set).
+align.c:655-762, return per read, and the flag that the checks of abea/src/f5c.c:1474-1501 set; under "long" the same for the
+generator's reads of 16384 k-mers and more, whose inputs are not stored).
 
 The reference's align.c is compiled on its own in a temporary directory outside the repository, with the stand-in headers of
 make_abea_golden.py, -O2 -std=c++11 -ffp-contract=off, and a small harness of this script's own that declares the three prototypes,
@@ -168,6 +169,12 @@ def main():
     cases = M.make_cases(model[0], model[1], fixture[longest][:4] + (got[longest][1][:got[longest][0]],))
     names = list(cases)
     got_c, t_post_c, t_recal_c = run_reference(ref, model, [cases[n] for n in names])
+    # the reads longer than the map kernel's stride: regenerated by seed wherever they are used, only the reference's record (with the
+    # digest of its map) is kept
+    long_reads = M.long_reads(model[0], model[1])
+    got_l, _, _ = run_reference(ref, model, list(long_reads.values()))
+    for (n, r), g in zip(long_reads.items(), got_l):
+        assert g[0] == len(r[4]) and len(g[3]) in M.LONG_KMERS and g[2]["recalibrated"] and (g[3][:, 0] == -1).sum() > len(g[3]) // 12, n
 
     # the conditions on the fixture
     recs = [g[2] for g in got]
@@ -208,7 +215,8 @@ def main():
            "reference_build": "g++ -O2 -std=c++11 -ffp-contract=off, align.c alone",
            "reference_postalign_seconds": round(t_post + t_post_c, 5), "reference_recalibrate_seconds": round(t_recal + t_recal_c, 5),
            "reference_host": "build host CPU, one thread", "counts": {k: int(v) for k, v in count.items()},
-           "reads": [M.record_of(g[2], g[3]) for g in got], "cases": {n: M.record_of(g[2], g[3]) for n, g in zip(names, got_c)}}
+           "reads": [M.record_of(g[2], g[3]) for g in got], "cases": {n: M.record_of(g[2], g[3]) for n, g in zip(names, got_c)},
+           "long": {n: M.record_of(g[2], g[3]) for n, g in zip(long_reads, got_l)}}
     old = os.path.join(HERE, "abea_calib_expected.json")
     if "--keep-times" in sys.argv and os.path.exists(old):      # reproduce the committed file: its times
         was = json.load(open(old))

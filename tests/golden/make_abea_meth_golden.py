@@ -193,6 +193,7 @@ def main():
     assert table.tobytes() == M.TABLE.tobytes(), "the logsum table"
     cases = M.make_cases(model)
     names = [n for n in cases if n not in M.DEVIATIONS and int(cases[n]["calib"]["read_stat_flag"]) == 0]
+    assert (set(M.WINDOW_CASES) | set(M.STEP_CASES)) - set(M.WINDOW_NO_EVENT) <= set(names)      # the window cases that find an event, every step case
     plain = [n for n in names if n not in M.FLAT_CASES]; flat = [n for n in names if n in M.FLAT_CASES]
     _, got_c, _ = run_reference(ref_dir, cpg, [cases[n] for n in plain])
     _, got_f, _ = run_reference(ref_dir, M.FLAT_CPG, [cases[n] for n in flat])

@@ -216,7 +216,8 @@ def main():
              for r, a in zip(fixture, aln)]
     got, seconds = run_reference(ref_dir, model, reads)
     cases = M.make_cases(model)
-    names = [n for n in cases if n not in M.DEVIATIONS]      # the reference cannot run the two defined deviations
+    names = [n for n in cases if n not in M.DEVIATIONS]      # the reference cannot run the defined deviations: it indexes event -1 or asserts
+    assert set(M.WINDOW_CASES) - set(M.WINDOW_NO_EVENT) <= set(names)      # ... but it runs every window case that finds an event
     flat = [n for n in names if n in M.FLAT_CASES]
     plain = [n for n in names if n not in M.FLAT_CASES]
 

@@ -155,6 +155,60 @@ def test_reads_around_the_chunks_of_64_kmers(aligner, boundary):
     check(device_form(aligner, flat), [want[n] for n in names], names)
 
 
+def test_reads_longer_than_the_map_kernels_stride(aligner):
+    """cal_map runs at most 64 blocks of 256 threads a read and strides: a thread takes k-mers 16384 apart.  Reads of 16384 k-mers (one
+    trip), 16385 (a second trip for one k-mer) and 32769 (a third), a tenth of their k-mers without an event, the k-mers on both sides
+    of a stride (16383, 16384, 32768) among them in one variant and with an event in the other; a read of 102 bases in the same call, so
+    that the blocks of a read are sized by another read.  The map entry for entry and the record against the model, and both against
+    the reference's record of the same reads (regenerated by seed, tests/golden/abea_calib_expected.json holds no input of theirs)."""
+    from test_abea_calib_model import model_of_long_reads
+    model, _, _, exp = load_calib_fixture()
+    reads, want_long = model_of_long_reads()
+    short = counted(np.random.default_rng(71), model, np.ones(97, np.int64))
+    names = ["bases_102"] + list(reads)
+    want = [model_of(model, short)] + [want_long[n] for n in reads]
+    assert len(short[0]) == 102 and [len(w[1]) for w in want[1:]] == [16384, 16384, 16385, 16385, 32769, 32769] and 64 * 256 == 16384
+    flat, got, _ = run(aligner, [short] + list(reads.values()), want, names)
+    for form in (got, device_form(aligner, flat)):
+        check(form, want, names)
+        rmap, map_off, res = form
+        for i, n in enumerate(names[1:], 1):
+            m = rmap[map_off[i]:map_off[i] + len(want[i][1])]
+            assert M.record_of(res[i], np.stack([m["start"], m["stop"]], 1)) == exp["long"][n], n
+    assert form[0].size == int(map_off[-1]) + 32769 + 8 and (form[0][int(map_off[-1]) + 32769:].view(np.int32) == -7).all()      # nothing behind the last map
+
+
+def test_the_host_entry_with_slabs_that_do_not_start_at_0(aligner, boundary):
+    """the three input slabs with a junk prefix of an odd length, the reads in reverse order with gaps, two reads on the same bases and
+    events, the maps in reverse order with gaps behind a prefix: byte for byte the result of the same reads packed from 0, and not a byte
+    of the map written outside a read's entries.  The junk is what the input rules refuse."""
+    from genarchbench_amd import abea
+    from test_abea_realign_launch_gpu import relay, scattered_room
+    named, want = boundary
+    names = ["kmers_65", "m_200_at_chunk_ends", "six_bases_one_pair", "homopolymer_63_64", "kmers_129", "no_event_at_lane_0_and_63", "kmers_65"]
+    flat = flat_of([named[n] for n in names])
+    plain = aligner.calibrate(*flat)
+    check(plain, [want[n] for n in names], names)
+    seq, seq_off, seq_len, events, event_off, n_events, scale, shift, pairs, pair_off, n_pairs = flat
+    rng = np.random.default_rng(73)
+    path_len = np.array([len(named[n][5]) for n in names], np.int64)
+    seq2, seq_off2 = relay(seq, seq_off, seq_len, ord("!"), 7, rng, (6, 0))
+    events2, event_off2 = relay(events, event_off, n_events, np.nan, 5, rng, (6, 0))
+    pairs2, pair_off2 = relay(np.ascontiguousarray(pairs, np.int32).view(np.int64).reshape(-1), pair_off, path_len, np.array([-1, -1], np.int32).view(np.int64)[0], 3, rng)
+    assert seq_off2[6] == seq_off2[0] and event_off2[6] == event_off2[0] and seq_off2.min() == 7 and event_off2.min() == 5 and pair_off2.min() == 3
+    n_kmers = seq_len.astype(np.int64) - A.K + 1
+    map_off, total = scattered_room(n_kmers, 74)
+    out = (np.full(total, -7, np.int32).repeat(2).view(abea.RANGE), np.frombuffer(bytes([0xa5]) * 40 * (len(names) + 1), abea.CALIB).copy())
+    got = aligner.calibrate(seq2, seq_off2, seq_len, events2, event_off2, n_events, scale, shift, pairs2.view(np.int32).reshape(-1, 2), pair_off2, n_pairs, map_off=map_off, out=out)
+    check((got[0], got[1], got[2][:len(names)]), [want[n] for n in names], names)
+    assert out[1][:len(names)].tobytes() == plain[2].tobytes() and out[1][len(names):].tobytes() == bytes([0xa5]) * 40
+    written = np.zeros(total, bool)
+    for i, n in enumerate(names):
+        assert out[0][map_off[i]:map_off[i] + n_kmers[i]].tobytes() == plain[0][plain[1][i]:plain[1][i] + n_kmers[i]].tobytes(), f"{n} (read {i})"
+        written[map_off[i]:map_off[i] + n_kmers[i]] = True
+    assert (out[0][~written].view(np.int32) == -7).all() and (~written).sum() >= 11 + len(names)
+
+
 def test_a_flat_pore_model_sets_no_calibration_flag():
     from genarchbench_amd.abea import EventAligner
     rng = np.random.default_rng(2)

@@ -86,6 +86,26 @@ def test_model_reproduces_the_reference_on_every_constructed_case():
         [(199, 0, 1), (200, 1, 0), (201, 1, 0)]
 
 
+def model_of_long_reads():
+    """the generator's reads of 16384 k-mers and more, and the model's (record, map) of each, computed once per process"""
+    if "long" not in _CACHE:
+        model = load_calib_fixture()[0]
+        reads = {n: (*r[:4], len(r[4]), r[4]) for n, r in M.long_reads(model[0], model[1]).items()}
+        _CACHE["long"] = (reads, {n: model_of(model, r) for n, r in reads.items()})
+    return _CACHE["long"]
+
+
+def test_model_reproduces_the_reference_on_the_reads_longer_than_the_map_kernels_stride():
+    exp = load_calib_fixture()[3]["long"]
+    reads, got = model_of_long_reads()
+    assert list(got) == list(exp) and sorted({len(r[0]) - M.K + 1 for r in reads.values()}) == list(M.LONG_KMERS)
+    for name, (rec, m) in got.items():
+        assert M.record_of(rec, m) == exp[name], name
+        edges = [k for k in M.STRIDE_EDGES if k < len(m)]
+        assert ((m[edges, 0] == -1) == ("none" in name)).all() and m[0, 0] == 0, name
+        assert len(m) // 12 < (m[:, 0] == -1).sum() < len(m) // 8 and rec["recalibrated"] == 1 and rec["n_m_state"] > len(m) // 2, name
+
+
 def test_the_first_entry_of_a_kmer_is_E_after_a_kmer_of_the_same_rank():
     """a homopolymer run, and a period-2 repeat whose middle k-mer got no event: in both the previous k-mer that had events has
     the same rank, so the k-mer's first entry is 'E' and is not counted; every later entry of a k-mer is 'E' anyway"""

@@ -138,6 +138,82 @@ def test_every_kmer_count_of_a_group(aligner, part):
             check(got, k, want[n], f"{n} k-mers, {form} form")
 
 
+SCORE_WAVEFRONTS = 2048 * 4                              # `SCORE_BLOCKS` x `SCORE_WAVES` of abea_meth.hip: the persistent wavefronts that take items off one counter
+
+
+def test_more_items_than_scoring_wavefronts_and_more_than_64_sites_a_read(aligner):
+    """135 reads of 70 scored groups each, three distinct ones (one of them reverse) 45 times over in a seeded order: 9450 items for
+    8192 wavefronts, so some wavefront takes a second item whatever the scheduling; and 70 sites in a read, so that the slot of a site
+    is carried over from a step in which all 64 positions' worth of earlier sites were counted"""
+    model, cpg, _, _, _ = load_meth_fixture()
+    rng = np.random.default_rng(20251203)
+    distinct, want = [], []
+    for rev in (False, True, False):
+        at = (30 + np.concatenate([[0], np.cumsum(rng.integers(20, 49, 69))])).tolist()      # isolated: more than ten bases apart, and scoreable
+        read = M.bases_with_cpgs(rng, at[-1] + 40, at)
+        c = R.case(rng, model, R.revcomp(read) if rev else read, rev=rev, per=1)
+        w = want_of_model(*model_of(cpg, c))
+        assert 2200 < len(read) <= 2500 and w["n_sites"] == w["groups"] == 70 and w["flags"] == 0 and w["cells"] == 70 * 2 * 21 * 16
+        distinct.append(read_of(c)); want.append(w)
+    order = np.random.default_rng(20251204).permutation(np.repeat(np.arange(3), 45))
+    batch = [distinct[j] for j in order]
+    assert len(batch) == 135 and 70 * len(batch) > SCORE_WAVEFRONTS + 1000
+    for got, form in ((aligner.call_methylation_reads(batch), "host"), (device_form(aligner, batch), "device")):
+        st = aligner.meth_last_stats()
+        for k, j in enumerate(order):
+            check(got, k, want[j], f"read {k} (a copy of read {j}), {form} form")
+        assert st["reads"] == 135 and st["sites"] == int(got[2]["n_sites"].sum()) == 70 * 135 and st["groups"] == 70 * 135
+        assert st["cells"] == int(got[2]["cells"].sum()) == 135 * want[0]["cells"] and st["rows"] == 135 * 70 * 21
+
+
+def test_the_flank_table_grows_with_the_longest_read_of_a_call():
+    """a fresh handle: a read of 120 events, then one of 6000 with a group on 401 rows, then the first again"""
+    from genarchbench_amd.abea import EventAligner
+    model, cpg, _, _, _ = load_meth_fixture()
+    rng = np.random.default_rng(20251205)
+    short = R.case(rng, model, M.bases_with_cpgs(rng, 125, [60]), per=1)
+    cnt = np.ones(5620, np.int64); cnt[50:70] = 20
+    long = R.case(rng, model, M.bases_with_cpgs(rng, 5625, [60, 3000, 5500]), counts=cnt, epb=4.0)
+    want_short, want_long = want_of_model(*model_of(cpg, short)), want_of_model(*model_of(cpg, long))
+    assert short["events"].size == 120 and long["events"].size == 6000 and want_short["n_sites"] == 1 and want_long["n_sites"] == 3
+    assert want_long["sites"][0][5] - want_long["sites"][0][4] == 400
+    h = EventAligner(*model)
+    try:
+        h.set_cpg_model(*cpg)
+        for c, want, name in ((short, want_short, "120 events"), (long, want_long, "6000 events"), (short, want_short, "120 events again")):
+            check(h.call_methylation_reads([read_of(c)]), 0, want, name)
+            check(device_form(h, [read_of(c)]), 0, want, name + ", device form")
+    finally:
+        h.close()
+
+
+def test_the_host_entry_with_slabs_that_do_not_start_at_0(aligner):
+    """every slab with a junk prefix of an odd length, the reads in reverse order with gaps, two reads on the same reference bytes and
+    events: byte for byte the result of the same reads packed from 0, and not a byte written outside a read's sites"""
+    from genarchbench_amd import abea
+    from test_abea_realign_launch_gpu import scattered_room, windowed
+    _, _, _, cases, _ = load_meth_fixture()
+    names = ["separation_11", "lower_case_and_iupac", "kmers_64_reverse", "no_cpg", "cigar_operations", "single_cpg", "separation_11"]
+    want = model_of_cases()
+    packed = abea.pack_aligned_reads([read_of(cases[n]) for n in names])
+    plain = aligner.call_methylation(*packed)
+    w = windowed(packed, (6, 0), 41)
+    assert w[1][6] == w[1][0] and w[10][6] == w[10][0] and w[1].min() == 7 and w[6].min() == 3 and w[10].min() == 5 and w[13].min() == 9
+    room = abea.meth_room(w[0], w[1], w[2])
+    assert room.tolist() == [2, 3, 1, 0, 3, 1, 2]
+    out_off, total = scattered_room(room, 42)
+    out = (np.frombuffer(bytes([0xa5]) * 32 * total, abea.SITE).copy(), np.frombuffer(bytes([0xa5]) * 40 * (len(names) + 1), abea.METH).copy())
+    got = aligner.call_methylation(*w, out_off=out_off, out=out)
+    assert out[1][:len(names)].tobytes() == plain[2].tobytes() and out[1][len(names):].tobytes() == bytes([0xa5]) * 40
+    written = np.zeros(total, bool)
+    for i, n in enumerate(names):
+        check(got, i, want_of_model(*want[n]), f"{n} (read {i})")
+        k = int(plain[2][i]["n_sites"])
+        assert out[0][out_off[i]:out_off[i] + k].tobytes() == plain[0][plain[1][i]:plain[1][i] + k].tobytes(), f"{n} (read {i})"
+        written[out_off[i]:out_off[i] + k] = True
+    assert out[0][~written].tobytes() == bytes([0xa5]) * 32 * int((~written).sum()) and written.sum() == 12
+
+
 def test_repeatable_and_independent_of_the_batch_order(aligner):
     _, _, reads, cases, _ = load_meth_fixture()
     names = [n for n in cases if n not in M.FLAT_CASES]

@@ -132,6 +132,48 @@ def test_the_defined_deviations():
     assert got["no_event"][1]["flags"] == M.NO_EVENT and got["no_event"][1]["n_sites"] == 1 and got["no_event"][1]["groups"] == 2
     assert got["strand"][1]["flags"] == M.STRAND and not got["strand"][0]
     assert got["transitions"][1]["flags"] == M.TRANSITIONS and got["transitions"][1]["groups"] == 1 and not got["transitions"][0]
+    for n in M.WINDOW_NO_EVENT:
+        assert got[n][1]["flags"] == M.NO_EVENT and got[n][1]["groups"] == 1 and not got[n][0], n
+
+
+def test_the_window_of_the_closest_event():
+    """what each window case is there for, by the map it was made with and by the model's answer"""
+    _, _, _, cases, exp = load_meth_fixture()
+    got = model_of_cases()
+    assert all(exp["cases"][n]["by_reference"] == (n not in M.WINDOW_NO_EVENT) for n in M.WINDOW_CASES)
+    event_of = lambda n, k: int(cases[n]["map"][k, 0])
+    e1_of = lambda n: M.closest_event(M.WINDOW_CASES[n][1] - M.MIN_SEPARATION, cases[n]["map"][:, 0], len(cases[n]["map"]))
+    site = lambda n: (got[n][0][0]["event_start"], got[n][0][0]["event_stop"])
+    for d in (63, 64, 65):
+        n = f"behind_{d}"
+        assert (cases[n]["map"][100 - d + 1:101] == -1).all() and site(n) == (event_of(n, 100 - d), event_of(n, 120)) and site(n)[0] == e1_of(n) >= 0, n
+    assert site("behind_999") == (event_of("behind_999", 51), event_of("behind_999", 1070)) and (cases["behind_999"]["map"][52:1051] == -1).all()
+    assert event_of("behind_1000", 50) == 50 and site("behind_1000") == (event_of("behind_1000", 1051), event_of("behind_1000", 1070)) == (51, 70)
+    c = cases["behind_1000_nothing_ahead"]
+    assert c["map"][10, 0] >= 0 and c["map"][2010, 0] >= 0 and (c["map"][11:2010] == -1).all() and e1_of("behind_1000_nothing_ahead") == -1
+    assert e1_of("ahead_999") == event_of("ahead_999", 1010) == 0 and (cases["ahead_999"]["map"][:1010] == -1).all()
+    assert got["ahead_999"][1]["skipped_short"] == 1 and got["ahead_999"][1]["flags"] == 0        # both ends of the group find entry 1010's event
+    assert event_of("ahead_1000", 1011) == 0 and (cases["ahead_1000"]["map"][:1011] == -1).all() and e1_of("ahead_1000") == -1
+    assert event_of("entry_0_only", 0) == 0 and site("entry_0_only") == (event_of("entry_0_only", 12), event_of("entry_0_only", 31)) == (1, 20)
+    c = cases["last_entry_only"]                         # neither the first nor the last pair finds an event: the record is emptied (meth.c:169-178)
+    assert c["map"][-1, 0] == 0 and (c["map"][:-1] == -1).all() and got["last_entry_only"][1]["skipped_unbounded"] == 1 and got["last_entry_only"][1]["flags"] == 0
+
+
+def test_the_groups_on_the_edges_of_a_step_of_64_positions():
+    _, _, _, cases, exp = load_meth_fixture()
+    got = model_of_cases()
+    assert all(exp["cases"][n]["by_reference"] for n in M.STEP_CASES)
+    firsts = lambda n: [(s["first_cpg"], s["n_cpg"]) for s in got[n][0]]
+    for p in (63, 64, 127, 128):
+        assert firsts(f"start_{p}") == [(p, 1)] and cases[f"start_{p}"]["ref"][p:p + 2] == b"CG"
+    for r in ("", "_reverse"):
+        assert firsts("start_64" + r) == [(64, 1)] and firsts("sites_54_64" + r) == [(54, 2)] and firsts("sites_53_64" + r) == [(53, 1), (64, 1)]
+        assert firsts("group_60_to_130" + r) == [(60, 8)] and got["group_60_to_130" + r][0][0]["end_position"] - got["group_60_to_130" + r][0][0]["start_position"] == 70
+        assert bool(cases["start_64" + r]["is_rev"]) == bool(r)
+    assert firsts("start_127_reverse") == [(127, 1)]
+    c = cases["site_at_ref_len_minus_2"]
+    assert c["ref"][-2:] == b"CG" and len(c["ref"]) == 120 and firsts("site_at_ref_len_minus_2") == [(60, 1)]
+    assert got["site_at_ref_len_minus_2"][1]["groups"] == 2 and got["site_at_ref_len_minus_2"][1]["skipped_unbounded"] == 1
 
 
 def test_a_subset_of_the_fixture_equals_the_reference():

@@ -125,7 +125,8 @@ def test_the_golden_fixture_equals_the_reference(aligner):
 def test_the_constructed_cases_equal_the_reference_and_the_model(aligner, flat_aligner):
     """reference length 11 / 12, stop event 1 / 2 away, 49 / 50 / 51 emittable entries, last pair at +100 / +101, deletions of 95 and 101,
     96 k-mers on 6 rows (a K run across every lane), events_per_base 1.0 / 0.8 / 5.0, a reverse read, lower case and IUPAC, leading S, H
-    and I, an empty second segment, three segments, a region that cuts both ends, NO_EVENT and STRAND"""
+    and I, an empty second segment, three segments, a region that cuts both ends, NO_EVENT and STRAND, and the nearest event 63, 64, 65,
+    999 and 1000 entries behind the k-mer looked up, 999 and 1000 ahead of it, at entry 0 and at the last entry"""
     _, _, cases, exp = load_realign_fixture()
     want = model_of_cases()
     names = [n for n in cases if n not in M.FLAT_CASES and not n.startswith("rows_") and n != "region_cuts_both_ends"]
@@ -137,7 +138,8 @@ def test_the_constructed_cases_equal_the_reference_and_the_model(aligner, flat_a
                 check_golden(got, i, exp["cases"][n], n)
     flags = {n: int(got[2][i]["flags"]) for i, n in enumerate(names)}
     assert flags["no_event"] == M.NO_EVENT and flags["strand"] == M.STRAND and flags["second_segment_empty"] == M.NO_PAIRS
-    assert sum(flags.values()) == M.NO_EVENT + M.STRAND + M.NO_PAIRS
+    assert all(flags[n] == M.NO_EVENT for n in M.WINDOW_NO_EVENT)      # the event one entry outside the window of get_closest_event_to is not found
+    assert sum(flags.values()) == M.NO_EVENT * (1 + len(M.WINDOW_NO_EVENT)) + M.STRAND + M.NO_PAIRS
     c = cases["region_cuts_both_ends"]
     for got in (aligner.realign_reads([read_of(c)], region=c["region"]), device_form(aligner, [read_of(c)], region=c["region"])):
         check_model(got, 0, want["region_cuts_both_ends"], "region"); check_golden(got, 0, exp["cases"]["region_cuts_both_ends"], "region")

@@ -145,6 +145,32 @@ def test_the_two_defined_deviations_end_the_read():
     c = cases["strand"]
     first, stop = M.closest_event(0, c["map"][:, 0], len(c["map"])), M.closest_event(100, c["map"][:, 0], len(c["map"]))
     assert not c["is_rev"] and stop < first - 1 and rec["flags"] == M.STRAND and len(e) == 0 and rec["hmm_segments"] == 0
+    for n in M.WINDOW_NO_EVENT:
+        e, rec = got[n]
+        assert (cases[n]["map"] != -1).any() and rec["flags"] == M.NO_EVENT and len(e) == 0 and rec["hmm_segments"] == 0, n
+
+
+def test_the_window_of_the_closest_event():
+    """what each window case is there for, by the map it was made with and by the model's answer"""
+    _, _, cases, exp = load_realign_fixture()
+    got = model_of_cases()
+    assert set(M.WINDOW_CASES) <= set(cases) and set(M.WINDOW_CASES) - set(M.WINDOW_NO_EVENT) <= set(exp["cases"])
+    first_of = lambda n: M.closest_event(M.WINDOW_CASES[n][1], cases[n]["map"][:, 0], len(cases[n]["map"]))
+    event_of = lambda n, k: int(cases[n]["map"][k, 0])
+    for d in (63, 64, 65):                               # the k-mer d behind is the nearest with an event, and the read starts on its first event
+        n = f"behind_{d}"
+        assert (cases[n]["map"][70 - d + 1:71] == -1).all() and first_of(n) == event_of(n, 70 - d) >= 0 and got[n][0][0, 1] == first_of(n) + 1, n
+    assert first_of("behind_999") == event_of("behind_999", 51) >= 0 and (cases["behind_999"]["map"][52:1051] == -1).all()
+    assert event_of("behind_1000", 50) >= 0 and first_of("behind_1000") == event_of("behind_1000", 1051) == event_of("behind_1000", 50) + 2
+    assert got["behind_999"][1]["n_entries"] > 100 and got["behind_1000"][1]["n_entries"] > 100
+    assert got["behind_999"][0][:, 1].min() == first_of("behind_999") + 1 and got["behind_1000"][0][:, 1].min() == first_of("behind_1000") + 1
+    c = cases["behind_1000_nothing_ahead"]
+    assert c["map"][10, 0] >= 0 and c["map"][2010, 0] >= 0 and (c["map"][11:2010] == -1).all() and first_of("behind_1000_nothing_ahead") == -1
+    assert first_of("ahead_999") == event_of("ahead_999", 1004) == 0 and (cases["ahead_999"]["map"][:1004] == -1).all() and got["ahead_999"][1]["flags"] == 0
+    assert event_of("ahead_1000", 1005) == 0 and (cases["ahead_1000"]["map"][:1005] == -1).all() and first_of("ahead_1000") == -1
+    assert event_of("entry_0_only", 0) == 0 and first_of("entry_0_only") == event_of("entry_0_only", 6) == 2 and got["entry_0_only"][0][0, 1] == 3
+    c = cases["last_entry_only"]
+    assert c["map"][-1, 0] == 0 and (c["map"][:-1] == -1).all() and first_of("last_entry_only") == -1
 
 
 def test_an_event_is_emitted_once_per_bam_segment_at_most():
