@@ -6,8 +6,10 @@ is equality; every output buffer is pre-filled with a sentinel by the Python mir
 an overfull line is the one pushed on depends on the order of the inserts.  The sum of the partitions' probes therefore equals the
 unpartitioned call's exactly when no line of any of the tables is the home of more than eight keys -- no_line_overfull says so from
 the model alone -- and every probes count then equals its inserts.  That holds for every k = 1 and k = 3 case here (asserted), and
-the equalities are asserted wherever it holds; where it does not, what is asserted is what always holds: probes >= inserts per
-partition.  `merged` has no such condition and adds up in every case."""
+the equalities are asserted wherever it holds.  Where lines are overfull but every key of the input occurs once, the walks are
+still the same number in any order (tests/kmer_table_cases.py: expected_probes) and every probes count is asserted against it;
+where keys repeat, what is asserted is what always holds: probes >= inserts per partition.  `merged` has no such condition and
+adds up in every case."""
 import json
 import threading
 
@@ -15,7 +17,8 @@ import numpy as np
 import pytest
 
 from tests import kmer_model
-from tests.kmer_parts_util import SLOTS, fields, merged_keys, no_line_overfull, np_part_of, restrict
+from tests.kmer_parts_util import SLOTS, fields, merged_keys, no_line_overfull, np_line_of, np_part_of, restrict
+from tests.kmer_table_cases import expected_probes
 from tests.util import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +104,10 @@ def test_every_partition_equals_the_model(kc, name, k, nparts):
     if exact:
         assert [st["probes"] for _, st in got] == [parts[p]["inserts"] for p in range(nparts)]
         assert sum(st["probes"] for _, st in got) == whole_st["probes"] == m["positions"] - m["merged"]
+    elif m["max_count"] == 1:                      # lines spill, but every key is inserted once: the walks add up to the same number in any order
+        nl, nl1 = table_slots(m["positions"], k, nparts) // SLOTS, table_slots(m["positions"], k, 1) // SLOTS
+        assert [st["probes"] for _, st in got] == [expected_probes(np_line_of(parts[p]["kmers"], nparts, nl), nl) for p in range(nparts)]
+        assert whole_st["probes"] == expected_probes(np_line_of(m["kmers"], 1, nl1), nl1)
     if nparts == 1:                                # part 0 of 1 IS the unpartitioned count
         assert got[0][0] == whole
         assert got[0][1]["merged"] == whole_st["merged"] and (got[0][1]["probes"] == whole_st["probes"] or not exact)
