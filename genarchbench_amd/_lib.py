@@ -41,7 +41,24 @@ def lib():
         _lib = C.CDLL(_SO)
         _lib.gab_version.restype = C.c_char_p
         _lib.gab_last_error.restype = C.c_char_p
+        _dbg_prototypes(_lib)
     return _lib
+
+
+def _dbg_prototypes(so):
+    """argument and result types of the gab_dbg_* entry points (include/gab.h, dbg section)"""
+    P, I64, I32 = C.c_void_p, C.c_int64, C.c_int32
+    so.gab_dbg_create.argtypes = [C.c_int, P]
+    so.gab_dbg_destroy.argtypes = [P]
+    so.gab_dbg_destroy.restype = None
+    so.gab_dbg_reserve.argtypes = [P, I64, I64, I64]
+    so.gab_dbg_room.argtypes = [P, P, P, P, P, I64, I64, C.c_int, P]
+    so.gab_dbg_room.restype = I64
+    so.gab_dbg_build.argtypes = [P, P, P, P, P, P, P, P, P, P, P, I64, P, P, I64, P, P, I64, P]
+    so.gab_dbg_build_device.argtypes = [P, P, P, I64, P, P, P, P, P, I64, P, P, P, I64, P, P, I64, P, P, I64, P, P]
+    so.gab_dbg_last_stats.argtypes = [P, P]
+    so.gab_dbg_last_phases.argtypes = [P, P, P, P]
+    so.gab_dbg_plan_regions.argtypes = [I32, I32, P, P, I64, I32, P, I64, P]
 
 
 def version():

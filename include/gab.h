@@ -1130,6 +1130,97 @@ int gab_abea_meth_last_stats(gab_abea *h, int64_t *reads, int64_t *groups, int64
 /* the last gab_abea_meth* call's time by stage: preparation | scoring */
 int gab_abea_meth_stage_ms(gab_abea *h, float *prep_ms, float *score_ms);
 
+/* ---- dbg: the de Bruijn graph of Platypus' local assembly, one graph per assembly region ------------------------------
+ * Replaces  assembleReadsAndDetectVariants(...) once per region, the OpenMP loop of dbg/src/debruijn.cpp:1646-1661, which with the
+ *           cycle search commented out (:1437-1457) is
+ *           createDeBruijnGraph                                          dbg/src/debruijn.cpp:846-861
+ *           loadReferenceIntoGraph                                       dbg/src/debruijn.cpp:1291-1317
+ *           loadBAMDataIntoGraph -> loadReadIntoGraph                    dbg/src/debruijn.cpp:1399-1414, 1351-1396
+ *           -> DeBruijnGraph_AddEdge -> NodeDict_FindOrInsert            dbg/src/debruijn.cpp:917-949, 759-843
+ *           and what the verbose line prints of the graph (printDeBruijnGraph, dbg/src/debruijn.cpp:881-889, 1458-1465).
+ * The BAM and FASTA reading (htslib) is outside the reference's timed region and stays with the caller: INTEGRATION.md.
+ *
+ * For one region, with k-mer size k (the reference's 15) and min_qual (its 20); everything is an integer:
+ *   reference   for i in 0 .. ref_len - k - 2: an edge from the k-mer at i to the k-mer at i + 1, colour 1 (REF), positions ref_start + i
+ *               and ref_start + i + 1, node weight 1 each, edge weight 1.  Every byte counts, N included.
+ *   reads       read_begin .. read_end - 1 in order, without those whose flag has bit 512 (QC fail).  For i in 0 .. len - k - 2: q = the lowest
+ *               quality of the k + 1 bases i .. i + k; if q >= min_qual and none of them is N, an edge from the k-mer at i to the one at i + 1,
+ *               colour 2 (READ), position -1, node weight q on both, edge weight q.  Every other letter is an ordinary letter.
+ *   an edge     finds or inserts its start node, then its end node (twice the same node for a homopolymer: its weight counts twice); a
+ *               found node gets colours |=, weight +=, and keeps the position and source of its first occurrence.  Then the first of the start
+ *               node's four slots that is empty or already leads to the end node takes the edge (weight +=); with four other successors
+ *               present the edge is dropped, the nodes having been updated.
+ * Nodes come out in the order of their first occurrence (the reference's allNodes), a node's edges in the order of theirs.  The reference's
+ * hash function and buckets show nowhere.  Its weights are doubles that only ever hold sums of integers; here they are int64.
+ *
+ * Input, n_regions regions over one reference slab and one read slab: region r has the reference bytes ref[ref_off[r] .. + ref_len[r])
+ * (slices may overlap, as neighbouring regions' do), ref_start[r], and the reads read_begin[r] .. read_end[r] - 1 (the reference's
+ * windowStart / windowEnd: one read belongs to two or three regions); read j has seq and qual bytes at read_off[j] .. + read_len[j] of
+ * their slabs and read_flag[j].  Qualities are any byte.
+ * Output: node_off[n_regions + 1] and the records nodes[node_off[r] .. node_off[r + 1]) of region r.  src_read / src_off say where the
+ * node's k-mer first stood (src_read -1: the region's reference; else the read's index in the call), which is the reference's `sequence`
+ * pointer: its verbose line is "%d %d " of ref_start twice and, per node, the rest of that reference slice or read from src_off on.
+ * edge_to is a node index within the region; unused slots hold -1 and weight 0.
+ * Capacity as for gab_kmer_dump: when the graphs hold more than `capacity` nodes nothing is written, *nout gets the need and the call
+ * returns GAB_ERANGE; gab_dbg_room gives an upper bound from lengths alone (a sequence with e > 0 edges has at most e + 1 k-mers).
+ * Limits: 1 <= k <= GAB_DBG_MAX_K (sixteen letters of 4 bits: a k-mer is one 64-bit key; the one key that is all ones has a slot of its
+ * own, so every value is a valid k-mer).  A byte that is none of =ACMGRSVTWYHKDBN in a region's reference slice or in one of its reads
+ * (QC-fail ones included) is GAB_EINVAL naming the first such region, and nothing is written; lower case is such a byte: the reference
+ * compares bytes, so a soft-masked reference never matches a read there, and upper-casing is the caller's decision.
+ * A region may offer at most GAB_DBG_MAX_OCCURRENCES edge occurrences (reference and unfiltered reads together), else GAB_EINVAL: an
+ * occurrence's two node indices 2t and 2t + 1 are kept in 32 bits, which alone would admit 2^31; the bound is 2^24 so that one region's
+ * tables stay below 2 GiB.  Weights are summed in 64 bits: at most 2 x 255 x 2^24 per node.
+ * How it runs: one work-group per region, the region's tables in global memory (DESIGN.md says why not LDS); every occurrence has its
+ * index in the reference's order and a table entry keeps the lowest index it saw, so the result does not depend on the order in which
+ * the atomics land.  Scratch is about 60 bytes per edge occurrence offered, all regions of a call at once: callers with more regions
+ * than memory call in slices. */
+#define GAB_DBG_MAX_K 16
+#define GAB_DBG_MAX_OCCURRENCES (1 << 24)
+#define GAB_DBG_REGION_SIZE 1500        /* assemblyRegionSize, dbg/src/debruijn.cpp:1576 */
+typedef struct gab_dbg gab_dbg;
+typedef struct { int32_t k, min_qual; } gab_dbg_params;
+typedef struct {
+    int32_t src_read, src_off;          /* first occurrence: -1 = the region's reference, else the read; the offset of the k-mer there */
+    int32_t colours;                    /* 1 REF, 2 READ, 3 both */
+    int32_t position;                   /* ref_start + src_off, or -1 for a node first seen in a read */
+    int64_t weight;
+    int32_t n_edges, edge_to[4], pad;
+    int64_t edge_weight[4];
+} gab_dbg_node;                          /* 80 bytes */
+typedef struct { int64_t regions, occurrences /* offered */, passed /* the filter */, nodes, edges, probes /* node-table slots the inserts looked at */;
+                 float kernel_ms, total_ms; } gab_dbg_stats;
+typedef struct { int32_t start, ref_start, ref_len, pad; int64_t read_begin, read_end; } gab_dbg_region;
+int gab_dbg_create(int device, gab_dbg **out);
+void gab_dbg_destroy(gab_dbg *h);
+/* optional: scratch for calls of up to this many regions, reads and edge occurrences offered, so that no call allocates */
+int gab_dbg_reserve(gab_dbg *h, int64_t max_regions, int64_t max_reads, int64_t max_occurrences);
+/* No GPU needed.  The nodes the regions can have at most (the sum; per_region, may be NULL, gets each region's), or a negative GAB_E* code. */
+int64_t gab_dbg_room(const int32_t *ref_len, const int32_t *read_len, const int32_t *read_flag, const int64_t *read_begin, const int64_t *read_end,
+                     int64_t n_reads, int64_t n_regions, int k, int64_t *per_region);
+/* Host buffers. */
+int gab_dbg_build(gab_dbg *h, const gab_dbg_params *params, const char *ref, const int64_t *ref_off, const int32_t *ref_len, const int32_t *ref_start,
+                  const char *seq, const uint8_t *qual, const int64_t *read_off, const int32_t *read_len, const int32_t *read_flag, int64_t n_reads,
+                  const int64_t *read_begin, const int64_t *read_end, int64_t n_regions, int64_t *node_off, gab_dbg_node *nodes, int64_t capacity, int64_t *nout);
+/* Device buffers (params and nout on the host), with the sizes of the two slabs for bounds validation.  Synchronises `stream` three
+ * times: at the start (offsets, lengths, flags and read ranges come to the host, are validated there and sized into the scratch
+ * layout), after the graphs are built and counted (the verdict on the bytes, the node counts: GAB_EINVAL and GAB_ERANGE return here and
+ * nothing of the caller's has been written) and at the end (the statistics), so node_off and nodes are complete when it returns. */
+int gab_dbg_build_device(gab_dbg *h, const gab_dbg_params *params, const char *ref, int64_t ref_bytes, const int64_t *ref_off, const int32_t *ref_len,
+                         const int32_t *ref_start, const char *seq, const uint8_t *qual, int64_t seq_bytes, const int64_t *read_off, const int32_t *read_len,
+                         const int32_t *read_flag, int64_t n_reads, const int64_t *read_begin, const int64_t *read_end, int64_t n_regions,
+                         int64_t *node_off, gab_dbg_node *nodes, int64_t capacity, int64_t *nout, void *stream);
+/* last gab_dbg_build* call; the times are HIP events on the stream (ms): the kernels, and first to last kernel (the host's sizing of
+ * the output in between included).  probes depends on which of two k-mers claimed a contested slot first: it is no part of the result. */
+int gab_dbg_last_stats(gab_dbg *h, gab_dbg_stats *out);
+/* the last call's kernel time by phase: tables cleared and filled | nodes numbered | records written.  Any may be NULL. */
+int gab_dbg_last_phases(gab_dbg *h, float *insert_ms, float *number_ms, float *emit_ms);
+/* No GPU needed.  The batch loop of the reference's main (dbg/src/debruijn.cpp:1576-1592) over [beg, end) of a contig of contig_len
+ * bases: a region every max(100, min(1000, 1500 / 2)) bases, its reference span [max(0, start - 1500), min(start + 1500, end) + 1500)
+ * cut at the contig's end as faidx_fetch_seq cuts it, and its reads by setWindowPointers / bisectReadsLeft (dbg/src/common.cpp:161-227)
+ * from pos[] (ascending, soft clips subtracted as getRead does) and read_end[].  Capacity as above: *nout regions are needed. */
+int gab_dbg_plan_regions(int32_t beg, int32_t end, const int32_t *pos, const int32_t *read_end, int64_t n_reads, int32_t contig_len,
+                         gab_dbg_region *out, int64_t capacity, int64_t *nout);
+
 #ifdef __cplusplus
 }
 #endif
