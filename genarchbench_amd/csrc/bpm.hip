@@ -13,14 +13,16 @@
 // every backtrace step follows an optimal DP move, so the count is exactly the DP distance
 // (bpm) -- no matrix needed.  Otherwise two reference quirks can make the count differ
 // (code 4 aliases onto the next block's 'A' mask; diagonal steps are classified by raw bytes), and
-// the pair takes the full path.  Hence two kernels, one pair per lane in both:
-//
-//   bpm_score<W>   all pairs, bucketed by W = ceil(plen/64) in 1..4: Pv/Mv in registers, the
-//                  4W+1 match masks of each lane in LDS as [mask][lane] (conflict-free b64 reads),
-//                  built with ds_or; writes -distance for clean pairs, queues the rest.
-//   bpm_full<W>    queued pairs (and every pair with W > 4, W = 0 instantiation): same recurrence,
-//                  but each column's Pv/Mv is stored to a per-pair region of a global scratch,
-//                  followed by the reference's backtrace on that region.
+// the pair needs the backtrace.  Hence a cascade of five stages, one pair per lane in all of them; pairs are bucketed by
+// W = ceil(plen/64) into the classes 1..4 (class 0: W > 4), and each stage queues what it cannot finish for the next:
+//   score    bpm_score32<D> / bpm_score32_wide<D> (D = 2W - 1 or 2W 32-bit words; GAB_BPM_SCORE64: bpm_score<W>, the 64-row
+//            block form): all pairs of a class, no history.  Pv/Mv in registers, the 4W+1 match masks of each lane in LDS as
+//            [mask][lane] (conflict-free b64 reads), built with ds_or; writes -distance for clean pairs, queues the rest.
+//   band     bpm_band<D>: the queued pairs of a slice, behind its score kernel on a second stream; history = the 8 rows
+//            around the diagonal, in LDS.      window   bpm_win<W>: the 64 rows around the diagonal, in global scratch.
+//   full     bpm_full<W>: complete columns; finishes every pair.      generic   bpm_full<0>: every pair with W > 4.
+// The history stages share the reference's backtrace (bpm_backtrace) over three views; the host side is a sequence of named
+// steps (gab_bpm_run_device) over one launch table.
 //
 // Roofline: ~36 VALU per (text char x 64-row block); 306 B of input per 151-bp pair.  The score
 // path is integer-VALU bound at about 16 k VALU per pair; its HBM traffic is the algorithmic
@@ -92,24 +94,181 @@ __device__ __forceinline__ uint32_t ld_u32(const char *p) { uint32_t w; __builti
 // re-fetched from HBM up to 16 times (profiles/r01_hbm_traffic.md: 8.7x the algorithmic bytes, HBM-bound)
 __device__ __forceinline__ uint4 ld_u128(const char *p) { uint4 w; __builtin_memcpy(&w, p, 16); return w; }
 
-// Wave-aggregated "counters[cls] += 1" returning each lane's slot: one atomic per (wave, class present)
-// instead of one per lane (all 10 M pairs of the 151-bp workload share one class, i.e. one address).
-__device__ __forceinline__ uint32_t wave_class_add(uint32_t *counters, int cls, bool active) {
-    uint32_t slot = 0;
-    unsigned long long todo = __ballot(active);
-    const unsigned long long lt = (1ull << (threadIdx.x & 63)) - 1;
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const int c = __shfl(cls, leader);
-        const unsigned long long same = __ballot(active && cls == c) & todo;
-        uint32_t base = 0;
-        if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(&counters[c], (uint32_t)__popcll(same));
-        base = __shfl(base, leader);
-        if (active && cls == c) slot = base + (uint32_t)__popcll(same & lt);
-        todo &= ~same;
+// ---- pieces every stage shares ---------------------------------------------------------------------------
+// the pair a lane works on
+struct BpmPair {
+    uint32_t id; int n, m; const char *p, *t;     // n = plen, m = tlen
+    __device__ __forceinline__ BpmPair(const BpmIO &io, uint32_t id_)
+        : id(id_), n(io.pat_len[id_]), m(io.txt_len[id_]), p(io.pat + io.pat_off[id_]), t(io.txt + io.txt_off[id_]) {}
+};
+
+// The one walk over a sequence's raw bytes, f(position, byte): sixteen bases per 16-byte load, then dwords (the slabs are
+// readable up to three bytes behind a sequence).  Decoding stays with the caller: bpm_code where code 4 matters.  (The score
+// frame, which decodes four bases at once and takes thirty-two per trip, keeps a copy of its own: see bpm_score_frame.)
+template <class F>
+__device__ __forceinline__ void bpm_text_walk(const char *s, int len, F &&f) {
+    int i0 = 0;
+    for (; i0 + 16 <= len; i0 += 16) {
+        const uint4 q = ld_u128(s + i0);
+        const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 16; k++) f(i0 + k, (ws[k >> 2] >> ((k & 3) * 8)) & 0xffu);
     }
-    return slot;
+    for (; i0 < len; i0 += 4) {
+        uint32_t w = ld_u32(s + i0);
+        for (int k = 0; k < 4 && i0 + k < len; k++, w >>= 8) f(i0 + k, w & 0xffu);
+    }
 }
+
+// Appends `id` of the lanes with `wanted` to a list: one atomic per wave (gab_wave_slot), input order kept within a wave.
+__device__ __forceinline__ void bpm_wave_append(uint32_t *counter, uint32_t *__restrict__ list, uint32_t id, bool wanted) {
+    const uint32_t slot = gab_wave_slot(counter, wanted);
+    if (wanted) list[slot] = id;
+}
+// *counter += the block steps of the wave: one atomic per wave ...
+__device__ __forceinline__ void bpm_steps_add_wave(unsigned long long *counter, unsigned long long steps) {
+    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
+    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(counter, steps);
+}
+// ... or one per workgroup, not per wave: 160 000 waves in 5 ms on one address keep an L2 atomic unit a quarter busy
+__device__ __forceinline__ void bpm_steps_add_block(unsigned long long *counter, unsigned long long steps) {
+    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
+    __shared__ unsigned long long s_steps[kBlock / 64];
+    if ((threadIdx.x & 63) == 0) s_steps[threadIdx.x >> 6] = steps;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0;
+        for (int k = 0; k < kBlock / 64; k++) all += s_steps[k];
+        if (all) atomicAdd(counter, all);
+    }
+}
+
+// First of the ROWS rows kept of column `col` around the diagonal (shifted by cshift = (plen - tlen) / 2), clamped into the
+// 64 W rows of the class: the band keeps 8 rows, the window 64.
+template <int ROWS, int W>
+__device__ __forceinline__ int bpm_rows_start(int col, int cshift) {
+    int r = col + cshift - ROWS / 2;
+    r = r < 0 ? 0 : r;
+    return r > 64 * W - ROWS ? 64 * W - ROWS : r;
+}
+
+// The reference's backtrace (edit_bpm.c:289-313) and its score, -edit_cigar_score_edit: Pv of column h + 1, else Mv of column
+// h, else a diagonal step that counts when the raw bytes differ.  The view says where the bits come from:
+//   holds(v, h)      columns h + 1 and h both hold row v (false: the walk left the rows this view keeps -- a miss)
+//   pv(h1, v), mv(h, v), differ(h, v)
+//   enter(v, h)      the walk stands on (v, h) and will read it
+//   moved_h(h), moved_v(v)   h / v has just been decremented (look-ahead)
+// Returns false on a miss, else *score is set.
+template <class View>
+__device__ __forceinline__ bool bpm_backtrace(int n, int m, View &view, int *score) {
+    int ops = 0, v = n - 1, h = m - 1;
+    while (v >= 0 && h >= 0) {
+        if (!view.holds(v, h)) return false;
+        view.enter(v, h);
+        const bool pv = view.pv(h + 1, v), mv = view.mv(h, v);
+        if (pv) { ops++; v--; view.moved_v(v); }
+        else if (mv) { ops++; h--; view.moved_h(h); }
+        else { ops += view.differ(h, v); h--; v--; view.moved_h(h); view.moved_v(v); }
+    }
+    *score = -(ops + (h + 1) + (v + 1));
+    return true;
+}
+
+// View 1, bpm_band: B[c * 64] = {Pv, Mv} bits of the 8 rows kept of column c, in LDS.
+// The walk itself only needs the band bits (LDS); the two bases of a diagonal step only feed the count, but as byte
+// loads at the step they put a global-memory round trip (~0.7 us) into every step.  Both strings are read backwards,
+// at most one byte per step, so each is held as the 8-byte chunk under the cursor plus the chunk below it, which is
+// requested when the cursor enters a chunk: a load has eight steps to arrive.
+template <int W>
+struct BpmBandView {
+    const uint16_t *B;
+    int cshift;
+    const char *p, *t;
+    int n4, m4, tk, pk;                              // readable bytes (the slabs are padded to dwords); chunks under the cursors
+    int r1, rh;                                      // first rows kept of columns h + 1 and h (set by holds)
+    uint32_t tlo, thi, tnlo, tnhi, plo, phi, pnlo, pnhi;
+    static __device__ __forceinline__ void chunk(const char *q, int k, int len4, uint32_t &lo, uint32_t &hi) {
+        lo = hi = 0;
+        if (k >= 0) { lo = ld_u32(q + 8 * k); if (8 * k + 4 < len4) hi = ld_u32(q + 8 * k + 4); }
+    }
+    __device__ __forceinline__ BpmBandView(const uint16_t *B_, int cshift_, const BpmPair &pr)
+        : B(B_), cshift(cshift_), p(pr.p), t(pr.t), n4((pr.n + 3) & ~3), m4((pr.m + 3) & ~3), tk((pr.m - 1) >> 3), pk((pr.n - 1) >> 3) {
+        chunk(t, tk, m4, tlo, thi); chunk(t, tk - 1, m4, tnlo, tnhi);
+        chunk(p, pk, n4, plo, phi); chunk(p, pk - 1, n4, pnlo, pnhi);
+    }
+    __device__ __forceinline__ int start(int col) const { return bpm_rows_start<kBandRows, W>(col, cshift); }
+    __device__ __forceinline__ bool holds(int v, int h) {
+        r1 = start(h + 1); rh = start(h);
+        return !(v < r1 || v >= r1 + kBandRows || v < rh || v >= rh + kBandRows);
+    }
+    __device__ __forceinline__ bool pv(int h1, int v) const { return ((uint32_t)B[h1 * 64] >> (v - r1)) & 1; }
+    __device__ __forceinline__ bool mv(int h, int v) const { return ((uint32_t)B[h * 64] >> (kBandRows + v - rh)) & 1; }
+    __device__ __forceinline__ bool differ(int h, int v) const {
+        const uint32_t tc = (((h & 4) ? thi : tlo) >> ((h & 3) * 8)) & 0xffu, pc = (((v & 4) ? phi : plo) >> ((v & 3) * 8)) & 0xffu;
+        return tc != pc;
+    }
+    __device__ __forceinline__ void enter(int v, int h) {
+        if ((h >> 3) != tk) { tk--; tlo = tnlo; thi = tnhi; chunk(t, tk - 1, m4, tnlo, tnhi); }
+        if ((v >> 3) != pk) { pk--; plo = pnlo; phi = pnhi; chunk(p, pk - 1, n4, pnlo, pnhi); }
+    }
+    __device__ __forceinline__ void moved_h(int) {}
+    __device__ __forceinline__ void moved_v(int) {}
+};
+
+// View 2, bpm_win: H[c] = {Pv, Mv} of the 64 rows kept of column c, in global memory.  The backtrace visits the columns
+// m, m - 1, ... in this order whatever path it takes, and the rows n - 1, n - 2, ... likewise: the view keeps the next eight
+// column records and the next dword of each string in registers, requested before they are needed.
+template <int W>
+struct BpmWinView {
+    static constexpr int kAhead = 8;                 // R[k] = record of column h + 1 - k
+    const ulonglong2 *H;
+    int cshift;
+    const char *p, *t;
+    ulonglong2 R[kAhead];
+    uint32_t tw, tw_n, pw, pw_n;
+    int r1, rh;                                      // first rows kept of columns h + 1 and h (set by holds)
+    // (the strings' dwords: bytes up to three behind a sequence are readable, and a dword in front of its first byte is
+    // never asked for: the index is clamped at 0)
+    __device__ __forceinline__ BpmWinView(const ulonglong2 *H_, int cshift_, const BpmPair &pr) : H(H_), cshift(cshift_), p(pr.p), t(pr.t) {
+        const int v = pr.n - 1, h = pr.m - 1;
+#pragma unroll
+        for (int k = 0; k < kAhead; k++) R[k] = H[h + 1 - k > 0 ? h + 1 - k : 0];
+        tw = h >= 0 ? ld_u32(t + (h & ~3)) : 0; tw_n = h >= 4 ? ld_u32(t + (h & ~3) - 4) : 0;
+        pw = v >= 0 ? ld_u32(p + (v & ~3)) : 0; pw_n = v >= 4 ? ld_u32(p + (v & ~3) - 4) : 0;
+    }
+    __device__ __forceinline__ int start(int col) const { return bpm_rows_start<64, W>(col, cshift); }
+    __device__ __forceinline__ bool holds(int v, int h) {
+        r1 = start(h + 1); rh = start(h);
+        return !(v < r1 || v >= r1 + 64 || v < rh || v >= rh + 64);
+    }
+    __device__ __forceinline__ void enter(int, int) {}
+    __device__ __forceinline__ bool pv(int h1, int v) const { return (R[0].x >> (v - r1)) & 1; }
+    __device__ __forceinline__ bool mv(int h, int v) const { return (R[1].y >> (v - rh)) & 1; }
+    __device__ __forceinline__ bool differ(int h, int v) const { return ((tw >> ((h & 3) * 8)) & 0xffu) != ((pw >> ((v & 3) * 8)) & 0xffu); }
+    __device__ __forceinline__ void moved_h(int h) {
+#pragma unroll
+        for (int k = 0; k + 1 < kAhead; k++) R[k] = R[k + 1];
+        const int col = h + 1 - (kAhead - 1);
+        R[kAhead - 1] = H[col > 0 ? col : 0];
+        if ((h & 3) == 3) { tw = tw_n; tw_n = h >= 4 ? ld_u32(t + (h & ~3) - 4) : 0; }
+    }
+    __device__ __forceinline__ void moved_v(int v) { if ((v & 3) == 3) { pw = pw_n; pw_n = v >= 4 ? ld_u32(p + (v & ~3) - 4) : 0; } }
+};
+
+// View 3, bpm_full: complete columns, word b of column c as {Pv, Mv} at bpm_full_at(H, Wd, c, b); every row is held.
+__device__ __forceinline__ uint64_t *bpm_full_at(uint64_t *H, int Wd, int col, int b) { return H + ((int64_t)col * Wd + b) * 2; }
+struct BpmFullView {
+    uint64_t *H;
+    int Wd;
+    const char *p, *t;
+    __device__ __forceinline__ bool holds(int, int) const { return true; }
+    __device__ __forceinline__ void enter(int, int) {}
+    __device__ __forceinline__ bool pv(int h1, int v) const { return (bpm_full_at(H, Wd, h1, v >> 6)[0] >> (v & 63)) & 1; }
+    __device__ __forceinline__ bool mv(int h, int v) const { return (bpm_full_at(H, Wd, h, v >> 6)[1] >> (v & 63)) & 1; }
+    __device__ __forceinline__ bool differ(int h, int v) const { return t[h] != p[v]; }
+    __device__ __forceinline__ void moved_h(int) {}
+    __device__ __forceinline__ void moved_v(int) {}
+};
 
 // ---- pass 1: validate + count per class ---------------------------------------------------
 // counts are accumulated per lane over the grid-stride loop and reduced once per wave: a single atomic per class and
@@ -195,25 +354,10 @@ template <int W, int kBlock = 256>
 __device__ __forceinline__ bool bpm_build_peq(uint64_t *peq, const char *p, int n) {
     for (int k = 0; k < 4 * W + 1; k++) peq[k * kBlock] = 0;
     bool clean = true;
-    int i0 = 0;
-    for (; i0 + 16 <= n; i0 += 16) {
-        const uint4 q = ld_u128(p + i0);
-        const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int i = i0 + k;
-            const int c = bpm_code((ws[k >> 2] >> ((k & 3) * 8)) & 0xffu, clean);
-            atomicOr((unsigned long long *)&peq[((i >> 6) * 4 + c) * kBlock], 1ull << (i & 63));
-        }
-    }
-    for (; i0 < n; i0 += 4) {
-        uint32_t w = ld_u32(p + i0);
-        for (int k = 0; k < 4 && i0 + k < n; k++, w >>= 8) {
-            const int i = i0 + k;
-            const int c = bpm_code(w & 0xffu, clean);
-            atomicOr((unsigned long long *)&peq[((i >> 6) * 4 + c) * kBlock], 1ull << (i & 63));
-        }
-    }
+    bpm_text_walk(p, n, [&](int i, uint32_t byte) {
+        const int c = bpm_code(byte, clean);
+        atomicOr((unsigned long long *)&peq[((i >> 6) * 4 + c) * kBlock], 1ull << (i & 63));
+    });
     // padding rows n .. 64W-1 match every code 0..3 (edit_bpm.c:106-113)
     if (n & 63) {
         const uint64_t pad = ~0ull << (n & 63);
@@ -223,77 +367,27 @@ __device__ __forceinline__ bool bpm_build_peq(uint64_t *peq, const char *p, int 
 }
 
 // ---- score path: W in 1..4 -------------------------------------------------------------------
-template <int W>
-__global__ __launch_bounds__(kBlock) void bpm_score(BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg,
-                                                    uint32_t kend, int32_t *__restrict__ score_out,
-                                                    uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
-    __shared__ uint64_t peq_s[(4 * W + 1) * kBlock];
-    const uint32_t k = kbeg + blockIdx.x * kBlock + threadIdx.x;
-    unsigned long long steps = 0;
-    int64_t queue_id = -1;
-    if (k < kend) {
-        const uint32_t id = perm ? perm[k] : k;        // perm == nullptr: all pairs share this class, identity order
-        const int n = io.pat_len[id], m = io.txt_len[id];
-        const char *p = io.pat + io.pat_off[id], *t = io.txt + io.txt_off[id];
-        uint64_t *peq = peq_s + threadIdx.x;
-        bool clean = bpm_build_peq<W>(peq, p, n);
-        uint64_t P[W], M[W];
+// The column engine of the 64-row block form (GAB_BPM_SCORE64, kept under test): W blocks on bpm_step, the distance tracked
+// column by column from the top block's horizontal deltas.
+template <int W_>
+struct BpmBlockEngine {
+    static constexpr int W = W_, kTrip = 16;
+    const uint64_t *peq;
+    uint64_t P[W], M[W], top_mask;
+    int score;
+    __device__ __forceinline__ BpmBlockEngine(const uint64_t *peq_, int n) : peq(peq_), top_mask((n & 63) ? 1ull << ((n & 63) - 1) : 1ull << 63), score(n) {
 #pragma unroll
         for (int b = 0; b < W; b++) { P[b] = ~0ull; M[b] = 0; }
-        const uint64_t top_mask = (n & 63) ? 1ull << ((n & 63) - 1) : 1ull << 63;
-        int score = n;
-        int h0 = 0;
-        for (; h0 + 16 <= m; h0 += 16) {
-            const uint4 q = ld_u128(t + h0);
-            // (codes of four text bases at a time: bpm_code per base was 8 of the 54 instructions a base costs)
-            const uint32_t cs[4] = {bpm_codes4(q.x, clean), bpm_codes4(q.y, clean), bpm_codes4(q.z, clean), bpm_codes4(q.w, clean)};
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) {
-                const int c = (int)((cs[kk >> 2] >> ((kk & 3) * 8)) & 3u);
-                uint32_t PH = 1, MH = 0;
-#pragma unroll
-                for (int b = 0; b < W; b++)
-                    bpm_step(peq[(b * 4 + c) * kBlock], b == W - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
-                score += (int)PH - (int)MH;
-            }
-        }
-        for (; h0 < m; h0 += 4) {
-            uint32_t w = ld_u32(t + h0);
-            for (int kk = 0; kk < 4 && h0 + kk < m; kk++, w >>= 8) {
-                const int c = bpm_code(w & 0xffu, clean);
-                uint32_t PH = 1, MH = 0;
-#pragma unroll
-                for (int b = 0; b < W; b++)
-                    bpm_step(peq[(b * 4 + (c & 3)) * kBlock], b == W - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
-                score += (int)PH - (int)MH;
-            }
-        }
-        steps = (unsigned long long)m * W;
-        if (clean) score_out[id] = -score;
-        else queue_id = (int64_t)id;
     }
-    {
-        // append the unclean pairs of this wave with one atomic
-        const unsigned long long q = __ballot(queue_id >= 0);
-        if (q) {
-            const int leader = __builtin_ctzll(q);
-            uint32_t base = 0;
-            if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(wl_counter, (uint32_t)__popcll(q));
-            base = __shfl(base, leader);
-            if (queue_id >= 0) worklist[base + (uint32_t)__popcll(q & ((1ull << (threadIdx.x & 63)) - 1))] = (uint32_t)queue_id;
-        }
+    __device__ __forceinline__ void step(int c) {
+        uint32_t PH = 1, MH = 0;
+#pragma unroll
+        for (int b = 0; b < W; b++)
+            bpm_step(peq[(b * 4 + c) * kBlock], b == W - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
+        score += (int)PH - (int)MH;
     }
-    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
-    // one atomic per workgroup, not per wave: 160 000 waves in 5 ms on one address keep an L2 atomic unit a quarter busy
-    __shared__ unsigned long long s_steps[kBlock / 64];
-    if ((threadIdx.x & 63) == 0) s_steps[threadIdx.x >> 6] = steps;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int k = 0; k < kBlock / 64; k++) all += s_steps[k];
-        if (all) atomicAdd(&ct->steps, all);
-    }
-}
+    __device__ __forceinline__ int printed(int, int) const { return -score; }
+};
 
 // ---- score path in 32-bit words: D = ceil(plen / 32) in 1..8, the whole column as ONE D-word integer ----------------
 // BPM_ADVANCE_BLOCK chains 64-row blocks through its horizontal carries (edit_bpm.c:47-66); the vertical deltas it leaves are
@@ -318,50 +412,53 @@ __device__ __forceinline__ void bpm_step32(const uint64_t *e, uint32_t (&P)[D], 
     gab_myers_step32<D>(Eq, P, M);
 }
 
+// The column engine of the D-word form.
 template <int D>
-__device__ __forceinline__ void bpm_score32_body(uint64_t *peq_s, BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg,
-                                                 uint32_t kend, int32_t *__restrict__ score_out,
-                                                 uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
-    constexpr int W = (D + 1) / 2;
+struct BpmWordEngine {
+    static constexpr int W = (D + 1) / 2, kTrip = 32;
+    const uint64_t *peq;
+    uint32_t P[D], M[D];
+    __device__ __forceinline__ BpmWordEngine(const uint64_t *peq_, int) : peq(peq_) {
+#pragma unroll
+        for (int d = 0; d < D; d++) { P[d] = ~0u; M[d] = 0; }
+    }
+    __device__ __forceinline__ void step(int c) { bpm_step32<D, kBlock>(peq + (size_t)c * kBlock, P, M); }
+    // the distance from the vertical deltas of the last column: nothing is tracked per column
+    __device__ __forceinline__ int printed(int n, int m) const { return -gab_myers_distance32<D>(P, M, n, m); }
+};
+
+// The score stage of one workgroup: pair k of [kbeg, kend) per lane (perm == nullptr: all pairs share this class, identity
+// order); the engine holds the column and says how it advances, how many bases a trip takes and what is printed.  Clean
+// pairs get their score, the others are appended to the worklist.
+// The trips over the text are bpm_text_walk<kTrip> with BpmCleanCodes, WRITTEN OUT: with the loops in a function of their
+// own the bpm_score32 kernels (held at waves_per_eu(6, 6)) come out as the same instructions in another order, with other
+// register and scratch figures (profiles/bpm_refactor.md).  This is the one copy outside the walk.
+template <class Engine>
+__device__ __forceinline__ void bpm_score_frame(uint64_t *peq_s, BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg,
+                                                uint32_t kend, int32_t *__restrict__ score_out,
+                                                uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
     const uint32_t k = kbeg + blockIdx.x * kBlock + threadIdx.x;
     unsigned long long steps = 0;
     int64_t queue_id = -1;
     if (k < kend) {
-        const uint32_t id = perm ? perm[k] : k;
-        const int n = io.pat_len[id], m = io.txt_len[id];
-#ifdef GAB_KO_BPM_LOCAL_TEXT      // measurement only (wrong results; bench inputs only, whose offsets ascend): every lane of a wave reads
-                                  // the strings of the wave's FIRST pair -- what a perfectly coalesced text layout could gain at most
-        const uint32_t id0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
-        const char *p = io.pat + io.pat_off[id0], *t = io.txt + io.txt_off[id0];
-#else
-        const char *p = io.pat + io.pat_off[id], *t = io.txt + io.txt_off[id];
-#endif
+        const BpmPair pr(io, perm ? perm[k] : k);
+        const int m = pr.m;
+        const char *p = pr.p, *t = pr.t;
         uint64_t *peq = peq_s + threadIdx.x;
-        bool clean = bpm_build_peq<W>(peq, p, n);
-        uint32_t P[D], M[D];
-#pragma unroll
-        for (int d = 0; d < D; d++) { P[d] = ~0u; M[d] = 0; }
-        auto step = [&](int c) { bpm_step32<D, kBlock>(peq + (size_t)c * kBlock, P, M); };
+        bool clean = bpm_build_peq<Engine::W>(peq, p, pr.n);
+        Engine e(peq, pr.n);
+        auto step = [&](int c) { e.step(c); };
         int h0 = 0;
-#ifdef GAB_BPM_TRIP64             // experiment (profiles/r04_kernel_bounds.md): sixty-four bases per trip, four 16-byte loads at once
-        for (; h0 + 64 <= m; h0 += 64) {
-            const uint4 q0 = ld_u128(t + h0), q1 = ld_u128(t + h0 + 16), q2 = ld_u128(t + h0 + 32), q3 = ld_u128(t + h0 + 48);
-            const uint32_t cs[16] = {bpm_codes4(q0.x, clean), bpm_codes4(q0.y, clean), bpm_codes4(q0.z, clean), bpm_codes4(q0.w, clean),
-                                     bpm_codes4(q1.x, clean), bpm_codes4(q1.y, clean), bpm_codes4(q1.z, clean), bpm_codes4(q1.w, clean),
-                                     bpm_codes4(q2.x, clean), bpm_codes4(q2.y, clean), bpm_codes4(q2.z, clean), bpm_codes4(q2.w, clean),
-                                     bpm_codes4(q3.x, clean), bpm_codes4(q3.y, clean), bpm_codes4(q3.z, clean), bpm_codes4(q3.w, clean)};
-#pragma unroll
-            for (int kk = 0; kk < 64; kk++) step((int)((cs[kk >> 2] >> ((kk & 3) * 8)) & 3u));
-        }
-#endif
         // thirty-two bases per trip, both 16-byte loads at once: a 64-byte line is visited twice instead of four times
-        for (; h0 + 32 <= m; h0 += 32) {
-            const uint4 q = ld_u128(t + h0), r = ld_u128(t + h0 + 16);
-            const uint32_t cs[8] = {bpm_codes4(q.x, clean), bpm_codes4(q.y, clean), bpm_codes4(q.z, clean), bpm_codes4(q.w, clean),
-                                    bpm_codes4(r.x, clean), bpm_codes4(r.y, clean), bpm_codes4(r.z, clean), bpm_codes4(r.w, clean)};
+        if (Engine::kTrip == 32)
+            for (; h0 + 32 <= m; h0 += 32) {
+                const uint4 q = ld_u128(t + h0), r = ld_u128(t + h0 + 16);
+                // (codes of four text bases at a time: bpm_code per base was 8 of the 54 instructions a base costs)
+                const uint32_t cs[8] = {bpm_codes4(q.x, clean), bpm_codes4(q.y, clean), bpm_codes4(q.z, clean), bpm_codes4(q.w, clean),
+                                        bpm_codes4(r.x, clean), bpm_codes4(r.y, clean), bpm_codes4(r.z, clean), bpm_codes4(r.w, clean)};
 #pragma unroll
-            for (int kk = 0; kk < 32; kk++) step((int)((cs[kk >> 2] >> ((kk & 3) * 8)) & 3u));
-        }
+                for (int kk = 0; kk < 32; kk++) step((int)((cs[kk >> 2] >> ((kk & 3) * 8)) & 3u));
+            }
         for (; h0 + 16 <= m; h0 += 16) {
             const uint4 q = ld_u128(t + h0);
             const uint32_t cs[4] = {bpm_codes4(q.x, clean), bpm_codes4(q.y, clean), bpm_codes4(q.z, clean), bpm_codes4(q.w, clean)};
@@ -372,33 +469,21 @@ __device__ __forceinline__ void bpm_score32_body(uint64_t *peq_s, BpmIO io, cons
             uint32_t w = ld_u32(t + h0);
             for (int kk = 0; kk < 4 && h0 + kk < m; kk++, w >>= 8) step(bpm_code(w & 0xffu, clean) & 3);
         }
-        steps = (unsigned long long)m * W;
-        // the distance from the vertical deltas of the last column: nothing is tracked per column
-        if (clean) score_out[id] = -gab_myers_distance32<D>(P, M, n, m);
-        else queue_id = (int64_t)id;
+        steps = (unsigned long long)m * Engine::W;
+        if (clean) score_out[pr.id] = e.printed(pr.n, m);
+        else queue_id = (int64_t)pr.id;
     }
-    {
-        // append the unclean pairs of this wave with one atomic
-        const unsigned long long q = __ballot(queue_id >= 0);
-        if (q) {
-            const int leader = __builtin_ctzll(q);
-            uint32_t base = 0;
-            if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(wl_counter, (uint32_t)__popcll(q));
-            base = __shfl(base, leader);
-            if (queue_id >= 0) worklist[base + (uint32_t)__popcll(q & ((1ull << (threadIdx.x & 63)) - 1))] = (uint32_t)queue_id;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
-    __shared__ unsigned long long s_steps[kBlock / 64];
-    if ((threadIdx.x & 63) == 0) s_steps[threadIdx.x >> 6] = steps;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int k2 = 0; k2 < kBlock / 64; k2++) all += s_steps[k2];
-        if (all) atomicAdd(&ct->steps, all);
-    }
+    bpm_wave_append(wl_counter, worklist, (uint32_t)queue_id, queue_id >= 0);
+    bpm_steps_add_block(&ct->steps, steps);
 }
 
+template <int W>
+__global__ __launch_bounds__(kBlock) void bpm_score(BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg,
+                                                    uint32_t kend, int32_t *__restrict__ score_out,
+                                                    uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
+    __shared__ uint64_t peq_s[(4 * W + 1) * kBlock];
+    bpm_score_frame<BpmBlockEngine<W>>(peq_s, io, perm, kbeg, kend, score_out, worklist, wl_counter, ct);
+}
 // Up to six words the kernel needs 54 VGPRs when the compiler is told to fit six waves per SIMD (left alone it takes 114 for
 // the sixteen unrolled columns, four waves): 24 waves per CU, what the 26.6 KB of masks per workgroup allow (bpm-large +4 %).
 // Seven and eight words do not fit that budget and keep the uncapped form.
@@ -407,14 +492,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 6)))
 void bpm_score32(BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg, uint32_t kend, int32_t *__restrict__ score_out,
                  uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
     __shared__ uint64_t peq_s[(4 * ((D + 1) / 2) + 1) * kBlock];
-    bpm_score32_body<D>(peq_s, io, perm, kbeg, kend, score_out, worklist, wl_counter, ct);
+    bpm_score_frame<BpmWordEngine<D>>(peq_s, io, perm, kbeg, kend, score_out, worklist, wl_counter, ct);
 }
 template <int D>
 __global__ __launch_bounds__(kBlock)
 void bpm_score32_wide(BpmIO io, const uint32_t *__restrict__ perm, uint32_t kbeg, uint32_t kend, int32_t *__restrict__ score_out,
                       uint32_t *__restrict__ worklist, uint32_t *wl_counter, BpmCounters *ct) {
     __shared__ uint64_t peq_s[(4 * ((D + 1) / 2) + 1) * kBlock];
-    bpm_score32_body<D>(peq_s, io, perm, kbeg, kend, score_out, worklist, wl_counter, ct);
+    bpm_score_frame<BpmWordEngine<D>>(peq_s, io, perm, kbeg, kend, score_out, worklist, wl_counter, ct);
 }
 
 // ---- LDS band path: 8 rows around the diagonal per column, history never leaves the CU ------------------------
@@ -429,7 +514,7 @@ template <int D>
 // of queued pairs is read on the device and the workgroups behind it leave at once (a capped grid striding over the slots
 // was measured 3 % slower).  The columns advance in the D-word form of bpm_score32 (D = 2W - 1 or 2W words for the class
 // W = ceil(plen / 64); the masks keep the 64-row layout, code-4 aliasing of edit_bpm.c included).
-__global__ __launch_bounds__(64) void bpm_band(BpmIO io, const uint32_t *__restrict__ list, const uint32_t *__restrict__ nslots_ptr, int cols,
+__global__ __launch_bounds__(64) void bpm_band(BpmIO io, const uint32_t *__restrict__ list, const uint32_t *__restrict__ nslots_ptr,
                                                int32_t *__restrict__ score_out, uint32_t *__restrict__ miss_list,
                                                BpmCounters *ct) {
     constexpr int W = (D + 1) / 2;
@@ -438,34 +523,34 @@ __global__ __launch_bounds__(64) void bpm_band(BpmIO io, const uint32_t *__restr
     const uint32_t nslots = *nslots_ptr;
     if (blockIdx.x * 64u >= nslots) return;
     const uint32_t s = blockIdx.x * 64 + lane;
-    int64_t miss_id = -1;
+    uint32_t id = 0;
+    bool miss = false;
     unsigned long long steps = 0;
     if (s < nslots) {
-        const uint32_t id = list[s];
-        const int n = io.pat_len[id], m = io.txt_len[id];
-        const char *p = io.pat + io.pat_off[id], *t = io.txt + io.txt_off[id];
+        const BpmPair pr(io, list[s]);
         uint64_t *peq = band_smem + lane;
         uint16_t *B = reinterpret_cast<uint16_t *>(band_smem + (4 * W + 1) * 64) + lane;      // column c at B[c * 64]
-        bpm_build_peq<W, 64>(peq, p, n);
-        const int cshift = (n - m) / 2;
-        auto start = [&](int col) { int r = col + cshift - kBandRows / 2; r = r < 0 ? 0 : r; return r > 64 * W - kBandRows ? 64 * W - kBandRows : r; };
+        bpm_build_peq<W, 64>(peq, pr.p, pr.n);
+        const int cshift = (pr.n - pr.m) / 2;
         uint32_t P[D], M[D];
 #pragma unroll
         for (int d = 0; d < D; d++) { P[d] = ~0u; M[d] = 0; }
         B[0] = (uint16_t)((1u << kBandRows) - 1u);                // column 0: Pv = 1..1, Mv = 0
         bool dummy = true;
-        auto column = [&](int h, uint32_t byte) {
+        // sixteen columns per load, as in the score kernel
+        bpm_text_walk(pr.t, pr.m, [&](int h, uint32_t byte) {
             const int c = bpm_code(byte, dummy);
             bpm_step32<D, 64>(peq + (size_t)c * 64, P, M);
             // the 8 rows of the band from row r0 on: rows of the pattern end below 32 D (r0 <= plen - 4), a word past the
             // last one reads as 0 (rows the walk never stands on)
-            const int r0 = start(h + 1);
+            const int r0 = bpm_rows_start<kBandRows, W>(h + 1, cshift);
             const int b0 = r0 >> 5;
             const uint32_t sh = (uint32_t)(r0 & 31);
             uint32_t plo = P[0], phi = D > 1 ? P[D > 1 ? 1 : 0] : 0, mlo = M[0], mhi = D > 1 ? M[D > 1 ? 1 : 0] : 0;
             // which word the band starts in is the same for the whole wave except in the few columns where the lanes
             // cross a word boundary (their diagonals differ by a row or two): then the words are named by a scalar switch
-            // instead of being selected per lane
+            // instead of being selected per lane.  (The two copies stay pasted: behind one helper the scalar switch
+            // became branches, profiles/bpm_refactor.md.)
             const int b0u = __builtin_amdgcn_readfirstlane(b0);
             if (D > 1 && __ballot(b0 != b0u) == 0) {
 #pragma unroll
@@ -480,63 +565,16 @@ __global__ __launch_bounds__(64) void bpm_band(BpmIO io, const uint32_t *__restr
             const uint32_t pw = __builtin_amdgcn_alignbit(phi, plo, sh) & bm;     // ({hi, lo} >> sh): sh = 0 gives lo
             const uint32_t mw = __builtin_amdgcn_alignbit(mhi, mlo, sh) & bm;
             B[(h + 1) * 64] = (uint16_t)(pw | mw << kBandRows);
-        };
-        int h0 = 0;
-        for (; h0 + 16 <= m; h0 += 16) {                     // sixteen columns per load, as in the score kernel
-            const uint4 q = ld_u128(t + h0);
-            const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) column(h0 + kk, (ws[kk >> 2] >> ((kk & 3) * 8)) & 0xffu);
-        }
-        for (; h0 < m; h0 += 4) {
-            uint32_t w4 = ld_u32(t + h0);
-            for (int kk = 0; kk < 4 && h0 + kk < m; kk++, w4 >>= 8) column(h0 + kk, w4 & 0xffu);
-        }
-        steps = (unsigned long long)m * W;
-        (void)cols;
-        int ops = 0, v = n - 1, h = m - 1;
-        bool miss = false;
-        // The walk itself only needs the band bits (LDS); the two bases of a diagonal step only feed the count, but as byte
-        // loads at the step they put a global-memory round trip (~0.7 us) into every step.  Both strings are read backwards,
-        // at most one byte per step, so each is held as the 8-byte chunk under the cursor plus the chunk below it, which is
-        // requested when the cursor enters a chunk: a load has eight steps to arrive.
-        const int n4 = (n + 3) & ~3, m4 = (m + 3) & ~3;                    // readable bytes (the slabs are padded to dwords)
-        auto chunk = [](const char *q, int k, int len4, uint32_t &lo, uint32_t &hi) {
-            lo = hi = 0;
-            if (k >= 0) { lo = ld_u32(q + 8 * k); if (8 * k + 4 < len4) hi = ld_u32(q + 8 * k + 4); }
-        };
-        int tk = h >> 3, pk = v >> 3;
-        uint32_t tlo, thi, tnlo, tnhi, plo2, phi2, pnlo, pnhi;
-        chunk(t, tk, m4, tlo, thi); chunk(t, tk - 1, m4, tnlo, tnhi);
-        chunk(p, pk, n4, plo2, phi2); chunk(p, pk - 1, n4, pnlo, pnhi);
-        while (v >= 0 && h >= 0) {
-            const int r1 = start(h + 1), rh = start(h);
-            if (v < r1 || v >= r1 + kBandRows || v < rh || v >= rh + kBandRows) { miss = true; break; }
-            if ((h >> 3) != tk) { tk--; tlo = tnlo; thi = tnhi; chunk(t, tk - 1, m4, tnlo, tnhi); }
-            if ((v >> 3) != pk) { pk--; plo2 = pnlo; phi2 = pnhi; chunk(p, pk - 1, n4, pnlo, pnhi); }
-            const uint32_t bc = B[(h + 1) * 64], bp = B[h * 64];
-            if ((bc >> (v - r1)) & 1) { ops++; v--; }
-            else if ((bp >> (kBandRows + v - rh)) & 1) { ops++; h--; }
-            else {
-                const uint32_t tc = (((h & 4) ? thi : tlo) >> ((h & 3) * 8)) & 0xffu, pc = (((v & 4) ? phi2 : plo2) >> ((v & 3) * 8)) & 0xffu;
-                ops += tc != pc; h--; v--;
-            }
-        }
-        if (miss) miss_id = (int64_t)id;
-        else score_out[id] = -(ops + (h + 1) + (v + 1));
+        });
+        steps = (unsigned long long)pr.m * W;
+        BpmBandView<W> view(B, cshift, pr);
+        int score;
+        id = pr.id;
+        miss = !bpm_backtrace(pr.n, pr.m, view, &score);
+        if (!miss) score_out[id] = score;
     }
-    {
-        const unsigned long long q = __ballot(miss_id >= 0);
-        if (q) {
-            const int leader = __builtin_ctzll(q);
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(&ct->wl1_count[W], (uint32_t)__popcll(q));
-            base = __shfl(base, leader);
-            if (miss_id >= 0) miss_list[base + (uint32_t)__popcll(q & ((1ull << lane) - 1))] = (uint32_t)miss_id;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
-    if (lane == 0 && steps) atomicAdd(&ct->full_steps, steps);
+    bpm_wave_append(&ct->wl1_count[W], miss_list, id, miss);
+    bpm_steps_add_wave(&ct->full_steps, steps);
 }
 
 // ---- windowed path: history of a 64-row diagonal window + backtrace -----------------------------------------
@@ -545,12 +583,7 @@ __global__ __launch_bounds__(64) void bpm_band(BpmIO io, const uint32_t *__restr
 // the diagonal are kept: 16 bytes per column, four columns per 64-byte line (3x less scratch written, ~5x fewer
 // lines read back by the backtrace than with full columns).  If the walk ever steps outside the window the pair is
 // queued once more and handled by bpm_full with complete columns, so the result is exact in every case.
-template <int W>
-__device__ __forceinline__ int bpm_win_start(int col, int cshift) {
-    int r = col + cshift - 32;
-    r = r < 0 ? 0 : r;
-    return r > 64 * W - 64 ? 64 * W - 64 : r;
-}
+// the 64 rows from row r0 on of a column held in W 64-bit words
 template <int W>
 __device__ __forceinline__ uint64_t bpm_win_take(const uint64_t (&X)[W], int r0) {
     const int b0 = r0 >> 6, s = r0 & 63;
@@ -571,182 +604,119 @@ __global__ __launch_bounds__(kBlock) void bpm_win(BpmIO io, const uint32_t *__re
     const uint32_t nslots = *nslots_ptr;
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
     unsigned long long steps = 0;
-  for (uint32_t sbase = blockIdx.x * kBlock; sbase < nslots; sbase += gridDim.x * kBlock) {
-    const uint32_t s = sbase + threadIdx.x;
-    int64_t miss_id = -1;
-    if (s < nslots) {
-        const uint32_t id = list[s];
-        const int n = io.pat_len[id], m = io.txt_len[id];
-        const char *p = io.pat + io.pat_off[id], *t = io.txt + io.txt_off[id];
-        uint64_t *peq = peq_s + threadIdx.x;
-        bpm_build_peq<W>(peq, p, n);
-        ulonglong2 *H = hist + (int64_t)slot * per_slot;        // record of column c: {Pv window, Mv window}
-        const int cshift = (n - m) / 2;
-        const uint64_t top_mask = (n & 63) ? 1ull << ((n & 63) - 1) : 1ull << 63;
-        uint64_t P[W], M[W];
-#pragma unroll
-        for (int b = 0; b < W; b++) { P[b] = ~0ull; M[b] = 0; }
-        H[0] = make_ulonglong2(~0ull, 0ull);
-        bool dummy = true;
-        // r04: the handful of pairs that come here are the LAST thing a call waits for (0.3 ms behind the last band kernel of
-        // bpm-large, a quarter of the step of a 1.25 M-pair share), and what they waited for was memory latency: a byte load per
-        // column in front of every step, and two to four dependent loads per backtrace step.  The text now arrives sixteen bases
-        // per load, and the backtrace -- which visits the columns m, m - 1, ... in this order whatever path it takes, and the
-        // rows n - 1, n - 2, ... likewise -- keeps the next eight column records and the next dword of each string in
-        // registers, requested before they are needed.  bpm_win on bpm-large (~100 pairs): 0.306 -> 0.223 ms.
-        auto column = [&](int h, int c) {
-            uint32_t PH = 1, MH = 0;
-#pragma unroll
-            for (int b = 0; b < W; b++)
-                bpm_step(peq[(b * 4 + c) * kBlock], b == W - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
-            const int r0 = bpm_win_start<W>(h + 1, cshift);
-            H[h + 1] = make_ulonglong2(bpm_win_take<W>(P, r0), bpm_win_take<W>(M, r0));
-        };
-        int hh = 0;
-        for (; hh + 16 <= m; hh += 16) {
-            const uint4 q = ld_u128(t + hh);
-            const uint32_t ws[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 16; k++) column(hh + k, bpm_code((ws[k >> 2] >> ((k & 3) * 8)) & 0xffu, dummy));
-        }
-        for (; hh < m; hh += 4) {
-            uint32_t w4 = ld_u32(t + hh);
-            for (int k = 0; k < 4 && hh + k < m; k++, w4 >>= 8) column(hh + k, bpm_code(w4 & 0xffu, dummy));
-        }
-        steps += (unsigned long long)m * W;
-        // backtrace (edit_bpm.c:289-313) on the windows
-        int ops = 0, v = n - 1, h = m - 1;
+    for (uint32_t sbase = blockIdx.x * kBlock; sbase < nslots; sbase += gridDim.x * kBlock) {
+        const uint32_t s = sbase + threadIdx.x;
+        uint32_t id = 0;
         bool miss = false;
-        constexpr int kAhead = 8;                     // R[k] = record of column h + 1 - k
-        ulonglong2 R[kAhead];
+        if (s < nslots) {
+            const BpmPair pr(io, list[s]);
+            uint64_t *peq = peq_s + threadIdx.x;
+            bpm_build_peq<W>(peq, pr.p, pr.n);
+            ulonglong2 *H = hist + (int64_t)slot * per_slot;        // record of column c: {Pv window, Mv window}
+            const int cshift = (pr.n - pr.m) / 2;
+            const uint64_t top_mask = (pr.n & 63) ? 1ull << ((pr.n & 63) - 1) : 1ull << 63;
+            uint64_t P[W], M[W];
 #pragma unroll
-        for (int k = 0; k < kAhead; k++) R[k] = H[h + 1 - k > 0 ? h + 1 - k : 0];
-        // (the strings' dwords: bytes up to three behind a sequence are readable, and a dword in front of its first byte is
-        // never asked for: the index is clamped at 0)
-        uint32_t tw = h >= 0 ? ld_u32(t + (h & ~3)) : 0, tw_n = h >= 4 ? ld_u32(t + (h & ~3) - 4) : 0;
-        uint32_t pw = v >= 0 ? ld_u32(p + (v & ~3)) : 0, pw_n = v >= 4 ? ld_u32(p + (v & ~3) - 4) : 0;
-        auto step_h = [&]() {                         // h has just been decremented
+            for (int b = 0; b < W; b++) { P[b] = ~0ull; M[b] = 0; }
+            H[0] = make_ulonglong2(~0ull, 0ull);
+            bool dummy = true;
+            // r04: the handful of pairs that come here are the LAST thing a call waits for (0.3 ms behind the last band kernel of
+            // bpm-large, a quarter of the step of a 1.25 M-pair share), and what they waited for was memory latency: a byte load per
+            // column in front of every step, and two to four dependent loads per backtrace step.  The text now arrives sixteen bases
+            // per load, and the backtrace keeps its look-ahead in registers (BpmWinView).  bpm_win on bpm-large (~100 pairs):
+            // 0.306 -> 0.223 ms.
+            bpm_text_walk(pr.t, pr.m, [&](int h, uint32_t byte) {
+                const int c = bpm_code(byte, dummy);
+                uint32_t PH = 1, MH = 0;
 #pragma unroll
-            for (int k = 0; k + 1 < kAhead; k++) R[k] = R[k + 1];
-            const int col = h + 1 - (kAhead - 1);
-            R[kAhead - 1] = H[col > 0 ? col : 0];
-            if ((h & 3) == 3) { tw = tw_n; tw_n = h >= 4 ? ld_u32(t + (h & ~3) - 4) : 0; }
-        };
-        auto step_v = [&]() {                         // v has just been decremented
-            if ((v & 3) == 3) { pw = pw_n; pw_n = v >= 4 ? ld_u32(p + (v & ~3) - 4) : 0; }
-        };
-        while (v >= 0 && h >= 0) {
-            const int r1 = bpm_win_start<W>(h + 1, cshift), rh = bpm_win_start<W>(h, cshift);
-            if (v < r1 || v >= r1 + 64 || v < rh || v >= rh + 64) { miss = true; break; }
-            if ((R[0].x >> (v - r1)) & 1) { ops++; v--; step_v(); }
-            else if ((R[1].y >> (v - rh)) & 1) { ops++; h--; step_h(); }
-            else { ops += ((tw >> ((h & 3) * 8)) & 0xffu) != ((pw >> ((v & 3) * 8)) & 0xffu); h--; v--; step_h(); step_v(); }
+                for (int b = 0; b < W; b++)
+                    bpm_step(peq[(b * 4 + c) * kBlock], b == W - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
+                const int r0 = bpm_rows_start<64, W>(h + 1, cshift);
+                H[h + 1] = make_ulonglong2(bpm_win_take<W>(P, r0), bpm_win_take<W>(M, r0));
+            });
+            steps += (unsigned long long)pr.m * W;
+            BpmWinView<W> view(H, cshift, pr);
+            int score;
+            id = pr.id;
+            miss = !bpm_backtrace(pr.n, pr.m, view, &score);
+            if (!miss) score_out[id] = score;
         }
-        if (miss) miss_id = (int64_t)id;
-        else score_out[id] = -(ops + (h + 1) + (v + 1));
+        bpm_wave_append(&ct->wl2_count[W], miss_list, id, miss);
     }
-    {
-        const unsigned long long q = __ballot(miss_id >= 0);
-        if (q) {
-            const int leader = __builtin_ctzll(q);
-            uint32_t base = 0;
-            if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(&ct->wl2_count[W], (uint32_t)__popcll(q));
-            base = __shfl(base, leader);
-            if (miss_id >= 0) miss_list[base + (uint32_t)__popcll(q & ((1ull << (threadIdx.x & 63)) - 1))] = (uint32_t)miss_id;
-        }
-    }
-  }
-    for (int o = 32; o > 0; o >>= 1) steps += __shfl_xor(steps, o);
-    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(&ct->full_steps, steps);
+    bpm_steps_add_wave(&ct->full_steps, steps);
 }
 
 // ---- full path: history + backtrace ---------------------------------------------------------------
-// slot s of this launch works on pair list[s]; element (col, b) of its history lives at
-//   hist[base + ((col * Wd + b) * 2 + {0: P, 1: M}) * estride]       (u64 units)
+// slot s of this launch works on pair list[s]; word b of column col of its history lives at
+//   bpm_full_at(H, Wd, col, b)[{0: P, 1: M}]       (u64 units)
 // REGW > 0: W == REGW for every slot, each slot owns a contiguous (64W+1) x W x 2 region (its 16-byte
 //           column records merge into full lines in the write-back L2, and the backtrace of a lane
 //           stays inside its own few KB instead of striding across the whole scratch); masks in LDS.
-// REGW == 0: any W (<= 255), base = slot_base[s]; the 4W+1 masks sit in front of the history.
+//           The grid is sized for the history room and a thread takes the entries slot, slot + threads, ...
+//           with ITS history slot (see bpm_win).
+// REGW == 0: any W (<= 255), the region of list entry s starts at slot_base[s]; the 4W+1 masks sit in front of the history.
+// The list's length is read from *nslots_ptr in both.
 template <int REGW>
-__global__ __launch_bounds__(kBlock) void bpm_full(BpmIO io, const uint32_t *__restrict__ list, uint32_t nslots_arg, const uint32_t *__restrict__ nslots_ptr,
+__global__ __launch_bounds__(kBlock) void bpm_full(BpmIO io, const uint32_t *__restrict__ list, const uint32_t *__restrict__ nslots_ptr,
                                                    uint64_t *__restrict__ hist, const int64_t *__restrict__ slot_base,
                                                    int32_t *__restrict__ score_out, BpmCounters *ct) {
     __shared__ uint64_t peq_s[(REGW ? 4 * REGW + 1 : 1) * kBlock];
-    // nslots_ptr (REGW > 0): the list's length is read here, the grid is sized for the history room and a thread takes the
-    // entries slot, slot + threads, ... with ITS history slot (see bpm_win)
-    const uint32_t nslots = nslots_ptr ? *nslots_ptr : nslots_arg;
+    const uint32_t nslots = *nslots_ptr;
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
-  for (uint32_t s = slot; s < nslots; s += gridDim.x * kBlock) {
-    const uint32_t id = list[s];
-    const int n = io.pat_len[id], m = io.txt_len[id];
-    const char *p = io.pat + io.pat_off[id], *t = io.txt + io.txt_off[id];
-    const int Wd = REGW ? REGW : (n + 63) >> 6;
-    const int64_t estride = 1;
-    uint64_t *H;                 // history origin of this slot
-    uint64_t *peq;               // mask k at peq[k * pstride]
-    int64_t pstride;
-    bool dummy = true;
-    if (REGW) {
-        H = hist + (int64_t)slot * ((64 * REGW + 1) * REGW * 2);
-        peq = peq_s + threadIdx.x; pstride = kBlock;
-        bpm_build_peq<(REGW ? REGW : 1)>(peq, p, n);
-    } else {
-        peq = hist + slot_base[s]; pstride = 1;
-        H = peq + 4 * Wd + 1;
-        for (int k = 0; k < 4 * Wd + 1; k++) peq[k] = 0;
-        for (int i = 0; i < n; i++) peq[(i >> 6) * 4 + bpm_code((uint8_t)p[i], dummy)] |= 1ull << (i & 63);
-        if (n & 63) for (int c = 0; c < 4; c++) peq[(Wd - 1) * 4 + c] |= ~0ull << (n & 63);
-    }
-    const uint64_t top_mask = (n & 63) ? 1ull << ((n & 63) - 1) : 1ull << 63;
-#define HP(col, b) H[(((int64_t)(col) * Wd + (b)) * 2) * estride]
-#define HM(col, b) H[(((int64_t)(col) * Wd + (b)) * 2 + 1) * estride]
-    uint64_t P[REGW ? REGW : 1], M[REGW ? REGW : 1];
-    if (REGW) {
-#pragma unroll
-        for (int b = 0; b < REGW; b++) { P[b] = ~0ull; M[b] = 0; HP(0, b) = ~0ull; HM(0, b) = 0; }
-    } else {
-        for (int b = 0; b < Wd; b++) { HP(0, b) = ~0ull; HM(0, b) = 0; }
-    }
-    for (int h = 0; h < m; h++) {
-        const int c = bpm_code((uint8_t)t[h], dummy);
-        uint32_t PH = 1, MH = 0;
+    unsigned long long steps = 0;
+    for (uint32_t s = slot; s < nslots; s += gridDim.x * kBlock) {
+        const BpmPair pr(io, list[s]);
+        const int n = pr.n, m = pr.m;
+        const int Wd = REGW ? REGW : (n + 63) >> 6;
+        uint64_t *H;                 // history origin of this slot
+        uint64_t *peq;               // mask k at peq[k * pstride]
+        int64_t pstride;
+        bool dummy = true;
+        if (REGW) {
+            H = hist + (int64_t)slot * ((64 * REGW + 1) * REGW * 2);
+            peq = peq_s + threadIdx.x; pstride = kBlock;
+            bpm_build_peq<(REGW ? REGW : 1)>(peq, pr.p, n);
+        } else {
+            peq = hist + slot_base[s]; pstride = 1;
+            H = peq + 4 * Wd + 1;
+            for (int k = 0; k < 4 * Wd + 1; k++) peq[k] = 0;
+            for (int i = 0; i < n; i++) peq[(i >> 6) * 4 + bpm_code((uint8_t)pr.p[i], dummy)] |= 1ull << (i & 63);
+            if (n & 63) for (int c = 0; c < 4; c++) peq[(Wd - 1) * 4 + c] |= ~0ull << (n & 63);
+        }
+        const uint64_t top_mask = (n & 63) ? 1ull << ((n & 63) - 1) : 1ull << 63;
+        auto put = [&](int col, int b, uint64_t Pb, uint64_t Mb) { uint64_t *e = bpm_full_at(H, Wd, col, b); e[0] = Pb; e[1] = Mb; };
+        uint64_t P[REGW ? REGW : 1], M[REGW ? REGW : 1];
         if (REGW) {
 #pragma unroll
-            for (int b = 0; b < REGW; b++) {
-                bpm_step(peq[(b * 4 + c) * pstride], b == REGW - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
-                HP(h + 1, b) = P[b]; HM(h + 1, b) = M[b];
-            }
+            for (int b = 0; b < REGW; b++) { P[b] = ~0ull; M[b] = 0; put(0, b, ~0ull, 0); }
         } else {
-            for (int b = 0; b < Wd; b++) {
-                uint64_t Pb = HP(h, b), Mb = HM(h, b);
-                bpm_step(peq[b * 4 + c], b == Wd - 1 ? top_mask : 1ull << 63, Pb, Mb, PH, MH);
-                HP(h + 1, b) = Pb; HM(h + 1, b) = Mb;
+            for (int b = 0; b < Wd; b++) put(0, b, ~0ull, 0);
+        }
+        for (int h = 0; h < m; h++) {
+            const int c = bpm_code((uint8_t)pr.t[h], dummy);
+            uint32_t PH = 1, MH = 0;
+            if (REGW) {
+#pragma unroll
+                for (int b = 0; b < REGW; b++) {
+                    bpm_step(peq[(b * 4 + c) * pstride], b == REGW - 1 ? top_mask : 1ull << 63, P[b], M[b], PH, MH);
+                    put(h + 1, b, P[b], M[b]);
+                }
+            } else {
+                for (int b = 0; b < Wd; b++) {
+                    const uint64_t *e = bpm_full_at(H, Wd, h, b);
+                    uint64_t Pb = e[0], Mb = e[1];
+                    bpm_step(peq[b * 4 + c], b == Wd - 1 ? top_mask : 1ull << 63, Pb, Mb, PH, MH);
+                    put(h + 1, b, Pb, Mb);
+                }
             }
         }
+        BpmFullView view{H, Wd, pr.p, pr.t};
+        int score;
+        bpm_backtrace(n, m, view, &score);
+        score_out[pr.id] = score;
+        steps += (unsigned long long)m * Wd;
     }
-    // backtrace (edit_bpm.c:289-313), counting non-match operations
-    int ops = 0, v = n - 1, h = m - 1;
-    while (v >= 0 && h >= 0) {
-        const int b = v >> 6;
-        const uint64_t bit = 1ull << (v & 63);
-        if (HP(h + 1, b) & bit) { ops++; v--; }
-        else if (HM(h, b) & bit) { ops++; h--; }
-        else { ops += t[h] != p[v]; h--; v--; }
-    }
-    ops += (h + 1) + (v + 1);
-    score_out[id] = -ops;
-    {
-        // one atomic per wave for the step counter (exec mask = lanes with a slot)
-        unsigned long long st = (unsigned long long)m * Wd;
-        const unsigned long long act = __ballot(true);
-        const int leader = __builtin_ctzll(act);
-        unsigned long long sum = 0;
-        for (unsigned long long r = act; r; r &= r - 1) sum += __shfl(st, __builtin_ctzll(r));
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&ct->full_steps, sum);
-    }
-#undef HP
-#undef HM
-  }
+    bpm_steps_add_wave(&ct->full_steps, steps);
 }
 
 }  // namespace
@@ -758,6 +728,44 @@ __global__ __launch_bounds__(256) void bpm_gather_lens(const uint32_t *__restric
 }
 
 // =============================================================================== host side
+// ---- the launch table: every instantiation once, with the name the trace and the profilers print for it ----
+using BpmScoreFn = void (*)(BpmIO, const uint32_t *, uint32_t, uint32_t, int32_t *, uint32_t *, uint32_t *, BpmCounters *);
+using BpmBandFn = void (*)(BpmIO, const uint32_t *, const uint32_t *, int32_t *, uint32_t *, BpmCounters *);
+using BpmWinFn = void (*)(BpmIO, const uint32_t *, const uint32_t *, ulonglong2 *, int, int32_t *, uint32_t *, BpmCounters *);
+using BpmFullFn = void (*)(BpmIO, const uint32_t *, const uint32_t *, uint64_t *, const int64_t *, int32_t *, BpmCounters *);
+template <class Fn> struct BpmKernel { Fn fn; const char *name; };
+#define BPM_K(kernel, arg) {kernel<arg>, #kernel "<" #arg ">"}
+static const BpmKernel<BpmScoreFn> kScore32[9] = {{nullptr, nullptr}, BPM_K(bpm_score32, 1), BPM_K(bpm_score32, 2), BPM_K(bpm_score32, 3),       // by D
+                                                  BPM_K(bpm_score32, 4), BPM_K(bpm_score32, 5), BPM_K(bpm_score32, 6),
+                                                  BPM_K(bpm_score32_wide, 7), BPM_K(bpm_score32_wide, 8)};
+static const BpmKernel<BpmBandFn> kBand[9] = {{nullptr, nullptr}, BPM_K(bpm_band, 1), BPM_K(bpm_band, 2), BPM_K(bpm_band, 3), BPM_K(bpm_band, 4),   // by D
+                                              BPM_K(bpm_band, 5), BPM_K(bpm_band, 6), BPM_K(bpm_band, 7), BPM_K(bpm_band, 8)};
+static const BpmKernel<BpmScoreFn> kScore64[kClasses] = {{nullptr, nullptr}, BPM_K(bpm_score, 1), BPM_K(bpm_score, 2), BPM_K(bpm_score, 3), BPM_K(bpm_score, 4)};   // by W
+static const BpmKernel<BpmWinFn> kWin[kClasses] = {{nullptr, nullptr}, BPM_K(bpm_win, 1), BPM_K(bpm_win, 2), BPM_K(bpm_win, 3), BPM_K(bpm_win, 4)};
+static const BpmKernel<BpmFullFn> kFull[kClasses] = {BPM_K(bpm_full, 0), BPM_K(bpm_full, 1), BPM_K(bpm_full, 2), BPM_K(bpm_full, 3), BPM_K(bpm_full, 4)};
+#undef BPM_K
+
+// ---- the three rules of the host side, each stated once ----
+// 32-bit words the score and the band kernel of class W run with: 2W - 1 when the class's longest pattern fits them
+static int bpm_class_words(int W, int max_plen) { return max_plen <= 32 * (2 * W - 1) ? 2 * W - 1 : 2 * W; }
+// A class of `count` pairs is scored in nsl slices of `per` pairs (a multiple of the block).
+// Slices of ~600 k pairs (10 M pairs: sixteen): a launch of fewer pairs no longer fills the chip -- an eighth of bpm-large
+// (one rank's share on 8 GPUs) cut into sixteen slices of 78 k pairs took 2.66 ms where 10 M take 5.4 (r03)
+// (r04: below ~2.4 M pairs ONE slice -- every band launch has a ~0.12 ms tail of its own that the next slice's score kernel
+// does not hide at that size: 1.25 M pairs 1.12 -> 1.04 ms, 100 k pairs 0.39 ms with two slices against 0.27 with one)
+struct BpmSlicePlan { int nsl; uint32_t per; };
+static BpmSlicePlan bpm_slice_plan(uint32_t count, int forced) {
+    int nsl = count < 2400000 ? 1 : (int)std::min<uint32_t>(kSlices, count / 600000);
+    if (forced > 0) nsl = std::max(1, std::min(kSlices, forced));        // GAB_BPM_SLICES: tuning runs
+    return {nsl, ((count + nsl - 1) / nsl + kBlock - 1) / kBlock * kBlock};
+}
+// history slots of a window / full launch: one per pair of the class, as many as the scratch budget holds, at most `cap`,
+// at least one block, whole blocks
+static uint32_t bpm_history_slots(uint32_t count, size_t bytes_slot, size_t budget, size_t cap) {
+    const uint32_t slots = (uint32_t)std::max<size_t>(kBlock, std::min<size_t>({(size_t)count, budget / bytes_slot, cap}));
+    return (slots + kBlock - 1) / kBlock * kBlock;
+}
+
 struct gab_bpm {
     gab_tuning tun = gab_tuning_loaded();      // experiment knobs, read when the handle is made
     gab_host_stream hs;     // private stream of the host-pointer entry point(s)
@@ -797,9 +805,8 @@ extern "C" int gab_bpm_create(int device, gab_bpm **out) {
             gab_set_error("gab_bpm_create: event creation failed"); delete h; return GAB_EDEVICE;
         }
     bool attr_ok = true;
-    for (const void *f : {(const void *)bpm_band<1>, (const void *)bpm_band<2>, (const void *)bpm_band<3>, (const void *)bpm_band<4>,
-                          (const void *)bpm_band<5>, (const void *)bpm_band<6>, (const void *)bpm_band<7>, (const void *)bpm_band<8>})
-        attr_ok = attr_ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+    for (int D = 1; D <= 2 * kMaxRegW; D++)
+        attr_ok = attr_ok && hipFuncSetAttribute((const void *)kBand[D].fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
     if (!attr_ok) {
         gab_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"); delete h; return GAB_EDEVICE;
     }
@@ -823,53 +830,208 @@ extern "C" void gab_bpm_destroy(gab_bpm *h) {
     delete h;
 }
 
-template <int W>
-static void launch_score(hipStream_t s, const BpmIO &io, const uint32_t *perm, uint32_t kb, uint32_t ke, int32_t *score,
-                         uint32_t *wl, uint32_t *wl_counter, BpmCounters *ct, int max_plen, bool blocks64, bool trace, int slice) {
-    if (ke <= kb) return;      // (blocks64 = GAB_BPM_SCORE64: the 64-row block form, kept under test)
-    const dim3 grid((ke - kb + kBlock - 1) / kBlock);
-    const bool odd = max_plen <= 32 * (2 * W - 1);                          // the class's longest pattern fits 2W - 1 words
-    if (trace)      // GAB_BPM_TRACE: which score kernel each launch runs
-        fprintf(stderr, "[gab_bpm] score class %d slice %d pairs %u..%u kernel %s<%d>\n", W, slice, kb, ke,
-                blocks64 ? "bpm_score" : W <= 3 ? "bpm_score32" : "bpm_score32_wide", blocks64 ? W : odd ? 2 * W - 1 : 2 * W);
-    if (blocks64)
-        hipLaunchKernelGGL(bpm_score<W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
-    else if constexpr (W <= 3) {
-        if (odd)
-            hipLaunchKernelGGL(bpm_score32<2 * W - 1>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
-        else
-            hipLaunchKernelGGL(bpm_score32<2 * W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
-    } else {
-        if (odd)
-            hipLaunchKernelGGL(bpm_score32_wide<2 * W - 1>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
-        else
-            hipLaunchKernelGGL(bpm_score32_wide<2 * W>, grid, dim3(kBlock), 0, s, io, perm, kb, ke, score, wl, wl_counter, ct);
-    }
-}
-// the score kernel of one slice on `s`, its band kernel on `sb` behind the event
-template <int W>
-static int launch_slice(hipStream_t s, hipStream_t sb, hipEvent_t scored, const BpmIO &io, const uint32_t *perm, uint32_t kb,
-                        uint32_t ke, int32_t *score, uint32_t *wl, uint32_t *wl_counter, int cols, uint32_t *wl1, BpmCounters *ct, int max_plen, bool blocks64,
-                        bool trace, int slice) {
-    if (ke <= kb) return GAB_OK;
-    launch_score<W>(s, io, perm, kb, ke, score, wl, wl_counter, ct, max_plen, blocks64, trace, slice);
-    GAB_HIP(hipEventRecord(scored, s));
-    GAB_HIP(hipStreamWaitEvent(sb, scored, 0));
-    const size_t lds = sizeof(uint64_t) * 64 * (4 * W + 1) + sizeof(uint16_t) * 64 * (size_t)cols;
-    const bool odd = max_plen <= 32 * (2 * W - 1);
-    if (trace)
-        fprintf(stderr, "[gab_bpm] band class %d slice %d pairs %u..%u kernel bpm_band<%d>\n", W, slice, kb, ke, odd ? 2 * W - 1 : 2 * W);
-    if (odd)
-        hipLaunchKernelGGL(bpm_band<2 * W - 1>, dim3((ke - kb + 63) / 64), dim3(64), lds, sb, io, wl, wl_counter, cols, score, wl1, ct);
-    else
-        hipLaunchKernelGGL(bpm_band<2 * W>, dim3((ke - kb + 63) / 64), dim3(64), lds, sb, io, wl, wl_counter, cols, score, wl1, ct);
+// ---- one call of gab_bpm_run_device, step by step --------------------------------------------------------------
+struct BpmCall {                // what the steps share
+    gab_bpm *h;
+    hipStream_t s;
+    BpmIO io;
+    int32_t *score;
+    BpmCounters *d_ct;
+    // n ids each: by class | queued by the score stage | band misses | window misses; the part of class W starts at cstart[W]
+    uint32_t *d_perm, *d_wl, *d_wl1, *d_wl2;
+    int grid;                   // of bpm_count and bpm_scatter
+    uint32_t cstart[kClasses], ccount[kClasses];
+    const uint32_t *perm;       // d_perm, or nullptr: identity order
+};
+static const int kClassOrder[kClasses] = {1, 2, 3, 4, 0};      // perm = [class 1 | class 2 | class 3 | class 4 | class 0 (W > 4)]
+
+static int bpm_workspace(BpmCall &c) {
+    const size_t n = (size_t)c.io.n;
+    const size_t o_perm = (sizeof(BpmCounters) + 255) & ~(size_t)255;
+    const size_t o_wl = o_perm + sizeof(uint32_t) * n, o_wl2 = o_wl + sizeof(uint32_t) * n, o_wl1 = o_wl2 + sizeof(uint32_t) * n;
+    const int rc = c.h->ws.reserve(o_wl1 + sizeof(uint32_t) * n);
+    if (rc) return rc;
+    char *base = c.h->ws.as<char>();
+    c.d_ct = (BpmCounters *)base;
+    c.d_perm = (uint32_t *)(base + o_perm); c.d_wl = (uint32_t *)(base + o_wl); c.d_wl2 = (uint32_t *)(base + o_wl2); c.d_wl1 = (uint32_t *)(base + o_wl1);
     return GAB_OK;
 }
-template <int W>
-static void launch_full(hipStream_t s, const BpmIO &io, const uint32_t *list, uint32_t nslots, uint64_t *hist,
-                        const int64_t *slot_base, int32_t *score, BpmCounters *ct) {
-    hipLaunchKernelGGL(bpm_full<W>, dim3((nslots + kBlock - 1) / kBlock), dim3(kBlock), 0, s, io, list, nslots, (const uint32_t *)nullptr, hist,
-                       slot_base, score, ct);
+
+// bpm_count, the call's one host synchronisation, and the verdict on the input
+static int bpm_count_and_validate(BpmCall &c) {
+    BpmCounters *h_ct = c.h->h_ct;
+    GAB_HIP(hipEventRecord(c.h->ev[0], c.s));
+    memset(h_ct, 0, sizeof(BpmCounters));
+    h_ct->first_bad = 0x7fffffff;
+    GAB_HIP(hipMemcpyAsync(c.d_ct, h_ct, sizeof(BpmCounters), hipMemcpyHostToDevice, c.s));
+    c.grid = (int)std::min<int64_t>(gab_ceil_div(c.io.n, 256), 1024);
+    hipLaunchKernelGGL(bpm_count, dim3(c.grid), dim3(256), 0, c.s, c.io, c.d_ct);
+    GAB_HIP(hipMemcpyAsync(h_ct, c.d_ct, sizeof(BpmCounters), hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipStreamSynchronize(c.s));
+    if (h_ct->bad) {
+        gab_set_error("gab_bpm_run_device: %d pair(s) violate the limits (first: pair %d): need 1 <= pattern_length <= %d, "
+                      "0 <= text_length <= pattern_length (apply the driver's longer-is-pattern swap), offsets inside "
+                      "the slabs with 3 more readable bytes behind every sequence", h_ct->bad, h_ct->first_bad - 1,
+                      GAB_BPM_MAX_PLEN);
+        return GAB_EINVAL;
+    }
+    return GAB_OK;
+}
+
+// where each class starts in the lists, and whether the pairs need ordering at all
+static int bpm_layout_classes(BpmCall &c) {
+    BpmCounters *h_ct = c.h->h_ct;
+    uint32_t run = 0;
+    int populated = 0;
+    for (int k : kClassOrder) { c.ccount[k] = h_ct->cls_count[k]; c.cstart[k] = run; run += c.ccount[k]; populated += c.ccount[k] != 0; }
+    for (int k = 0; k < kClasses; k++) h_ct->cls_cursor[k] = c.cstart[k];
+    GAB_HIP(hipMemcpyAsync(c.d_ct, h_ct, sizeof(BpmCounters), hipMemcpyHostToDevice, c.s));
+    const bool identity = populated == 1 && c.ccount[0] == 0;      // one register class holds every pair: no scatter pass
+    c.perm = identity ? nullptr : c.d_perm;
+    return GAB_OK;
+}
+
+static int bpm_order(BpmCall &c) {
+    if (c.perm) hipLaunchKernelGGL(bpm_scatter, dim3(c.grid), dim3(256), 0, c.s, c.io, c.d_ct, c.d_perm);
+    return GAB_OK;
+}
+
+// score path + stage 0 of the queued (unclean) pairs (8-row band in LDS).  The worklist of class W occupies
+// d_wl[cstart[W] ..); a class is cut into slices whose score kernels run back to back on the caller's stream
+// while each slice's band kernel runs on h->aux behind an event: the latency-bound band kernel (2.7 of 7.9 ms, 23 %
+// VALU busy on its own) then runs underneath the VALU-bound score kernel of the next slice and only the last
+// slice's band is exposed.  Pairs whose backtrace leaves the band are queued once more (64-row window), and from
+// there to complete columns.
+static int bpm_score_and_band(BpmCall &c) {
+    gab_bpm *h = c.h;
+    const bool trace = h->tun.bpm_trace;
+    GAB_HIP(hipEventRecord(h->ev[1], c.s));
+    GAB_HIP(hipEventRecord(h->fork, c.s));
+    GAB_HIP(hipStreamWaitEvent(h->aux, h->fork, 0));
+    for (int W = 1; W <= kMaxRegW; W++) {
+        if (!c.ccount[W]) continue;
+        const int D = bpm_class_words(W, h->h_ct->max_plen[W]);
+        const BpmKernel<BpmScoreFn> &score = h->tun.bpm_score64 ? kScore64[W] : kScore32[D];      // GAB_BPM_SCORE64: the 64-row block form, kept under test
+        const BpmKernel<BpmBandFn> &band = kBand[D];
+        const BpmSlicePlan plan = bpm_slice_plan(c.ccount[W], h->tun.bpm_slices);
+        const size_t lds = sizeof(uint64_t) * 64 * (4 * W + 1) + sizeof(uint16_t) * 64 * (size_t)(h->h_ct->max_tlen[W] + 1);
+        for (int k = 0; k < plan.nsl; k++) {
+            const uint32_t kb = c.cstart[W] + std::min<uint32_t>(c.ccount[W], (uint32_t)k * plan.per);
+            const uint32_t ke = c.cstart[W] + std::min<uint32_t>(c.ccount[W], (uint32_t)(k + 1) * plan.per);
+            if (ke <= kb) continue;
+            uint32_t *wl = c.d_wl + kb, *cnt = &c.d_ct->wl_slice[W][k];
+            // the score kernel of the slice on the caller's stream, its band kernel on aux behind the event
+            if (trace) fprintf(stderr, "[gab_bpm] score class %d slice %d pairs %u..%u kernel %s\n", W, k, kb, ke, score.name);
+            hipLaunchKernelGGL(score.fn, dim3((ke - kb + kBlock - 1) / kBlock), dim3(kBlock), 0, c.s, c.io, c.perm, kb, ke, c.score, wl, cnt, c.d_ct);
+            GAB_HIP(hipEventRecord(h->scored[k], c.s));
+            GAB_HIP(hipStreamWaitEvent(h->aux, h->scored[k], 0));
+            if (trace) fprintf(stderr, "[gab_bpm] band class %d slice %d pairs %u..%u kernel %s\n", W, k, kb, ke, band.name);
+            hipLaunchKernelGGL(band.fn, dim3((ke - kb + 63) / 64), dim3(64), lds, h->aux, c.io, (const uint32_t *)wl, (const uint32_t *)cnt, c.score,
+                               c.d_wl1 + c.cstart[W], c.d_ct);
+        }
+    }
+    GAB_HIP(hipGetLastError());
+    GAB_HIP(hipEventRecord(h->join, h->aux));
+    GAB_HIP(hipStreamWaitEvent(c.s, h->join, 0));
+    GAB_HIP(hipEventRecord(h->ev[2], c.s));
+    return GAB_OK;
+}
+
+// stage 1: 64-row window in global memory for the pairs that left the band; stage 2 (bpm_full_regs): complete columns for the
+// pairs that left the window.  r04: both are launched without asking the device how many pairs they got (that was two host round
+// trips per call -- 0.1 of the 0.29 ms of a 100 000-pair batch): a launch is sized for the history room the handle has and
+// reads the length of its list itself; its threads take list entries in strides (bpm_win / bpm_full).
+static int bpm_window(BpmCall &c) {
+    gab_bpm *h = c.h;
+    for (int W = 1; W <= kMaxRegW; W++) {
+        if (!c.ccount[W]) continue;
+        const int per_slot = 64 * W + 1;                       // columns 0 .. tlen <= 64 W, 16 bytes each
+        const uint32_t slots = bpm_history_slots(c.ccount[W], (size_t)per_slot * 16, h->scratch_budget, (size_t)1 << 16);
+        const int rc = h->scratch.reserve((size_t)per_slot * 16 * slots);
+        if (rc) return rc;
+        if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] window class %d slots %u kernel %s\n", W, slots, kWin[W].name);
+        hipLaunchKernelGGL(kWin[W].fn, dim3(slots / kBlock), dim3(kBlock), 0, c.s, c.io, (const uint32_t *)(c.d_wl1 + c.cstart[W]),
+                           (const uint32_t *)&c.d_ct->wl1_count[W], h->scratch.as<ulonglong2>(), per_slot, c.score, c.d_wl2 + c.cstart[W], c.d_ct);
+    }
+    return GAB_OK;
+}
+static int bpm_full_regs(BpmCall &c) {
+    gab_bpm *h = c.h;
+    for (int W = 1; W <= kMaxRegW; W++) {
+        if (!c.ccount[W]) continue;
+        const size_t bytes_slot = (size_t)(64 * W + 1) * W * 16;
+        const uint32_t slots = bpm_history_slots(c.ccount[W], bytes_slot, h->scratch_budget, (size_t)1 << 14);
+        const int rc = h->scratch.reserve(bytes_slot * slots);
+        if (rc) return rc;
+        if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class %d slots %u kernel %s\n", W, slots, kFull[W].name);
+        hipLaunchKernelGGL(kFull[W].fn, dim3(slots / kBlock), dim3(kBlock), 0, c.s, c.io, (const uint32_t *)(c.d_wl2 + c.cstart[W]),
+                           (const uint32_t *)&c.d_ct->wl2_count[W], h->scratch.as<uint64_t>(), (const int64_t *)nullptr, c.score, c.d_ct);
+    }
+    GAB_HIP(hipGetLastError());
+    return GAB_OK;
+}
+
+// W > 4: every pair takes the generic full path with per-pair extents, in batches that fit the scratch budget
+static int bpm_full_generic(BpmCall &c) {
+    gab_bpm *h = c.h;
+    const uint32_t cnt0 = c.ccount[0];
+    if (!cnt0) return GAB_OK;
+    std::vector<int32_t> pl(cnt0), tl(cnt0);
+    // lengths of those pairs: gathered on the device into one buffer, one copy back (a long-read input puts EVERY
+    // pair here; two 4-byte copies per pair were minutes of host latency at 10 M pairs)
+    int rc = h->lens.reserve(8 * (size_t)cnt0);
+    if (rc) return rc;
+    int32_t *d_pl = h->lens.as<int32_t>(), *d_tl = d_pl + cnt0;
+    hipLaunchKernelGGL(bpm_gather_lens, dim3((unsigned)std::min<int64_t>(gab_ceil_div((int64_t)cnt0, 256), 4096)), dim3(256), 0, c.s,
+                       c.d_perm + c.cstart[0], cnt0, c.io.pat_len, c.io.txt_len, d_pl, d_tl);
+    GAB_HIP(hipMemcpyAsync(pl.data(), d_pl, 4 * (size_t)cnt0, hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipMemcpyAsync(tl.data(), d_tl, 4 * (size_t)cnt0, hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipStreamSynchronize(c.s));
+    uint32_t k0 = 0;
+    while (k0 < cnt0) {
+        std::vector<int64_t> sb;       // where each pair's region starts (u64 units), then the number of pairs: what bpm_full<0> reads
+        size_t used = 0; uint32_t k1 = k0;
+        while (k1 < cnt0) {
+            const size_t Wd = ((size_t)pl[k1] + 63) / 64;
+            const size_t need = 4 * Wd + 1 + ((size_t)tl[k1] + 1) * Wd * 2;
+            if (k1 > k0 && (used + need) * 8 > h->scratch_budget) break;
+            sb.push_back((int64_t)used); used += need; k1++;
+        }
+        const size_t nb = sb.size(), o_sb = (used * 8 + 63) & ~(size_t)63;
+        sb.push_back((int64_t)nb);     // (little-endian: its low dword is the kernel's *nslots_ptr)
+        rc = h->scratch.reserve(o_sb + (nb + 1) * 8);
+        if (rc) return rc;
+        int64_t *d_sb = (int64_t *)(h->scratch.as<char>() + o_sb);
+        GAB_HIP(hipMemcpyAsync(d_sb, sb.data(), (nb + 1) * 8, hipMemcpyHostToDevice, c.s));
+        if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class 0 pairs %u..%u kernel %s\n", k0, k1, kFull[0].name);
+        hipLaunchKernelGGL(kFull[0].fn, dim3(((uint32_t)nb + kBlock - 1) / kBlock), dim3(kBlock), 0, c.s, c.io, (const uint32_t *)(c.d_perm + c.cstart[0] + k0),
+                           (const uint32_t *)(d_sb + nb), h->scratch.as<uint64_t>(), (const int64_t *)d_sb, c.score, c.d_ct);
+        GAB_HIP(hipStreamSynchronize(c.s));      // sb (host) and the scratch are reused by the next batch
+        k0 = k1;
+    }
+    return GAB_OK;
+}
+
+// the counters back for last_stats(), and what GAB_BPM_TRACE prints of them
+static int bpm_finish(BpmCall &c) {
+    gab_bpm *h = c.h;
+    GAB_HIP(hipGetLastError());
+    GAB_HIP(hipMemcpyAsync(h->h_ct, c.d_ct, sizeof(BpmCounters), hipMemcpyDeviceToHost, c.s));
+    GAB_HIP(hipEventRecord(h->ev[3], c.s));
+    if (h->tun.bpm_trace) {     // GAB_BPM_TRACE: the stage each class's pairs ended in (one synchronisation per call)
+        GAB_HIP(hipStreamSynchronize(c.s));
+        for (int k : kClassOrder) {
+            if (!c.ccount[k]) continue;
+            uint32_t queued = 0;
+            for (int j = 0; j < kSlices; j++) queued += h->h_ct->wl_slice[k][j];
+            fprintf(stderr, "[gab_bpm] class %d pairs %u queued %u band_miss %u window_miss %u\n", k, c.ccount[k], queued,
+                    h->h_ct->wl1_count[k], h->h_ct->wl2_count[k]);
+        }
+        fprintf(stderr, "[gab_bpm] steps score %llu later %llu\n", h->h_ct->steps, h->h_ct->full_steps);
+    }
+    h->last_full = (int64_t)c.ccount[0];      // (+ the pairs the band kernels queued: added from the counters in gab_bpm_last_stats)
+    h->have_stats = true;
+    return GAB_OK;
 }
 
 extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes, const int64_t *pat_off,
@@ -882,182 +1044,14 @@ extern "C" int gab_bpm_run_device(gab_bpm *h, const char *pat, int64_t pat_bytes
     GAB_CHECK(pat && pat_off && pat_len && txt && txt_off && txt_len && score_out, "gab_bpm_run_device: NULL buffer");
     gab_device_guard g(h->device);
     gab_tuning_refresh(&h->tun);
-    hipStream_t s = (hipStream_t)stream_;
-
-    const size_t o_perm = (sizeof(BpmCounters) + 255) & ~(size_t)255;
-    const size_t o_wl = o_perm + sizeof(uint32_t) * (size_t)n;
-    const size_t o_wl2 = o_wl + sizeof(uint32_t) * (size_t)n;
-    const size_t o_wl1 = o_wl2 + sizeof(uint32_t) * (size_t)n;
-    int rc = h->ws.reserve(o_wl1 + sizeof(uint32_t) * (size_t)n);
-    if (rc) return rc;
-    char *base = h->ws.as<char>();
-    BpmCounters *d_ct = (BpmCounters *)base;
-    uint32_t *d_perm = (uint32_t *)(base + o_perm), *d_wl = (uint32_t *)(base + o_wl), *d_wl2 = (uint32_t *)(base + o_wl2), *d_wl1 = (uint32_t *)(base + o_wl1);
-    BpmIO io{pat, pat_off, pat_len, txt, txt_off, txt_len, pat_bytes, txt_bytes, n};
-
-    GAB_HIP(hipEventRecord(h->ev[0], s));
-    memset(h->h_ct, 0, sizeof(BpmCounters));
-    h->h_ct->first_bad = 0x7fffffff;
-    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(BpmCounters), hipMemcpyHostToDevice, s));
-    const int grid = (int)std::min<int64_t>(gab_ceil_div(n, 256), 1024);
-    hipLaunchKernelGGL(bpm_count, dim3(grid), dim3(256), 0, s, io, d_ct);
-    GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(BpmCounters), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipStreamSynchronize(s));
-    if (h->h_ct->bad) {
-        gab_set_error("gab_bpm_run_device: %d pair(s) violate the limits (first: pair %d): need 1 <= pattern_length <= %d, "
-                      "0 <= text_length <= pattern_length (apply the driver's longer-is-pattern swap), offsets inside "
-                      "the slabs with 3 more readable bytes behind every sequence", h->h_ct->bad, h->h_ct->first_bad - 1,
-                      GAB_BPM_MAX_PLEN);
-        return GAB_EINVAL;
+    BpmCall c{};
+    c.h = h; c.s = (hipStream_t)stream_; c.score = score_out;
+    c.io = BpmIO{pat, pat_off, pat_len, txt, txt_off, txt_len, pat_bytes, txt_bytes, n};
+    for (auto step : {bpm_workspace, bpm_count_and_validate, bpm_layout_classes, bpm_order, bpm_score_and_band, bpm_window, bpm_full_regs,
+                      bpm_full_generic, bpm_finish}) {
+        const int rc = step(c);
+        if (rc) return rc;
     }
-    // class starts: perm = [class 1 | class 2 | class 3 | class 4 | class 0 (W > 4)]
-    uint32_t cstart[kClasses + 1], ccount[kClasses];
-    const int order[kClasses] = {1, 2, 3, 4, 0};
-    uint32_t run = 0;
-    for (int k = 0; k < kClasses; k++) { ccount[order[k]] = h->h_ct->cls_count[order[k]]; cstart[order[k]] = run; run += ccount[order[k]]; }
-    for (int c = 0; c < kClasses; c++) h->h_ct->cls_cursor[c] = cstart[c];
-    GAB_HIP(hipMemcpyAsync(d_ct, h->h_ct, sizeof(BpmCounters), hipMemcpyHostToDevice, s));
-    int populated = 0;
-    for (int c = 0; c < kClasses; c++) populated += ccount[c] != 0;
-    const bool identity = populated == 1 && ccount[0] == 0;      // one register class holds every pair: no scatter pass
-    if (!identity) hipLaunchKernelGGL(bpm_scatter, dim3(grid), dim3(256), 0, s, io, d_ct, d_perm);
-    const uint32_t *perm_arg = identity ? nullptr : d_perm;
-
-    // score path + stage 0 of the queued (unclean) pairs (8-row band in LDS).  The worklist of class W occupies
-    // d_wl[cstart[W] ..); a class is cut into kSlices slices whose score kernels run back to back on the caller's stream
-    // while each slice's band kernel runs on h->aux behind an event: the latency-bound band kernel (2.7 of 7.9 ms, 23 %
-    // VALU busy on its own) then runs underneath the VALU-bound score kernel of the next slice and only the last
-    // slice's band is exposed.  Pairs whose backtrace leaves the band are queued once more (64-row window), and from
-    // there to complete columns.
-    GAB_HIP(hipEventRecord(h->ev[1], s));
-    GAB_HIP(hipEventRecord(h->fork, s));
-    GAB_HIP(hipStreamWaitEvent(h->aux, h->fork, 0));
-    for (int W = 1; W <= kMaxRegW; W++) {
-        if (!ccount[W]) continue;
-        // slices of ~600 k pairs (10 M pairs: sixteen): a launch of fewer pairs no longer fills the chip -- an eighth of bpm-large
-        // (one rank's share on 8 GPUs) cut into sixteen slices of 78 k pairs took 2.66 ms where 10 M take 5.4 (r03)
-        // (r04: below ~2.4 M pairs ONE slice -- every band launch has a ~0.12 ms tail of its own that the next slice's score kernel
-        // does not hide at that size: 1.25 M pairs 1.12 -> 1.04 ms, 100 k pairs 0.39 ms with two slices against 0.27 with one)
-        int nsl = ccount[W] < 2400000 ? 1 : (int)std::min<uint32_t>(kSlices, ccount[W] / 600000);
-        if (h->tun.bpm_slices > 0) nsl = std::max(1, std::min(kSlices, h->tun.bpm_slices));        // GAB_BPM_SLICES: tuning runs
-        const uint32_t per = ((ccount[W] + nsl - 1) / nsl + kBlock - 1) / kBlock * kBlock;
-        const int cols = h->h_ct->max_tlen[W] + 1;
-        for (int k = 0; k < nsl; k++) {
-            const uint32_t kb = cstart[W] + std::min<uint32_t>(ccount[W], (uint32_t)k * per);
-            const uint32_t ke = cstart[W] + std::min<uint32_t>(ccount[W], (uint32_t)(k + 1) * per);
-            uint32_t *wl = d_wl + kb, *cnt = &d_ct->wl_slice[W][k], *wl1 = d_wl1 + cstart[W];
-            switch (W) {
-                case 1: rc = launch_slice<1>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[1], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
-                case 2: rc = launch_slice<2>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[2], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
-                case 3: rc = launch_slice<3>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[3], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
-                default: rc = launch_slice<4>(s, h->aux, h->scored[k], io, perm_arg, kb, ke, score_out, wl, cnt, cols, wl1, d_ct, h->h_ct->max_plen[4], h->tun.bpm_score64, h->tun.bpm_trace, k); break;
-            }
-            if (rc) return rc;
-        }
-    }
-    GAB_HIP(hipGetLastError());
-    GAB_HIP(hipEventRecord(h->join, h->aux));
-    GAB_HIP(hipStreamWaitEvent(s, h->join, 0));
-    GAB_HIP(hipEventRecord(h->ev[2], s));
-
-    {
-        // stage 1: 64-row window in global memory for the pairs that left the band; stage 2: complete columns for the pairs that
-        // left the window.  r04: both are launched without asking the device how many pairs they got (that was two host round
-        // trips per call -- 0.1 of the 0.29 ms of a 100 000-pair batch): a launch is sized for the history room the handle has and
-        // reads the length of its list itself; its threads take list entries in strides (bpm_win / bpm_full).
-        for (int W = 1; W <= kMaxRegW; W++) {
-            if (!ccount[W]) continue;
-            const int per_slot = 64 * W + 1;                       // columns 0 .. tlen <= 64 W, 16 bytes each
-            const size_t bytes_slot = (size_t)per_slot * 16;
-            uint32_t slots = (uint32_t)std::max<size_t>(kBlock, std::min<size_t>({(size_t)ccount[W], h->scratch_budget / bytes_slot, (size_t)1 << 16}));
-            slots = (slots + kBlock - 1) / kBlock * kBlock;
-            rc = h->scratch.reserve(bytes_slot * slots);
-            if (rc) return rc;
-            const uint32_t *list = d_wl1 + cstart[W];
-            ulonglong2 *hist = h->scratch.as<ulonglong2>();
-            const dim3 g(slots / kBlock), blk(kBlock);
-            if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] window class %d slots %u kernel bpm_win<%d>\n", W, slots, W);
-            switch (W) {
-                case 1: hipLaunchKernelGGL(bpm_win<1>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[1], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
-                case 2: hipLaunchKernelGGL(bpm_win<2>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[2], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
-                case 3: hipLaunchKernelGGL(bpm_win<3>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[3], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
-                default: hipLaunchKernelGGL(bpm_win<4>, g, blk, 0, s, io, list, (const uint32_t *)&d_ct->wl1_count[4], hist, per_slot, score_out, d_wl2 + cstart[W], d_ct); break;
-            }
-        }
-        for (int W = 1; W <= kMaxRegW; W++) {
-            if (!ccount[W]) continue;
-            const size_t per_slot = (size_t)(64 * W + 1) * W * 16;
-            uint32_t slots = (uint32_t)std::max<size_t>(kBlock, std::min<size_t>({(size_t)ccount[W], h->scratch_budget / per_slot, (size_t)1 << 14}));
-            slots = (slots + kBlock - 1) / kBlock * kBlock;
-            rc = h->scratch.reserve(per_slot * slots);
-            if (rc) return rc;
-            const uint32_t *list = d_wl2 + cstart[W];
-            uint64_t *hist = h->scratch.as<uint64_t>();
-            const dim3 g(slots / kBlock), blk(kBlock);
-            if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class %d slots %u kernel bpm_full<%d>\n", W, slots, W);
-            switch (W) {
-                case 1: hipLaunchKernelGGL(bpm_full<1>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[1], hist, (const int64_t *)nullptr, score_out, d_ct); break;
-                case 2: hipLaunchKernelGGL(bpm_full<2>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[2], hist, (const int64_t *)nullptr, score_out, d_ct); break;
-                case 3: hipLaunchKernelGGL(bpm_full<3>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[3], hist, (const int64_t *)nullptr, score_out, d_ct); break;
-                default: hipLaunchKernelGGL(bpm_full<4>, g, blk, 0, s, io, list, 0u, (const uint32_t *)&d_ct->wl2_count[4], hist, (const int64_t *)nullptr, score_out, d_ct); break;
-            }
-        }
-        GAB_HIP(hipGetLastError());
-        // W > 4: every pair takes the generic full path with per-slot extents
-        const uint32_t cnt0 = ccount[0];
-        if (cnt0) {
-            std::vector<int32_t> pl(cnt0), tl(cnt0);
-            // lengths of those pairs: gathered on the device into one buffer, one copy back (a long-read input puts EVERY
-            // pair here; two 4-byte copies per pair were minutes of host latency at 10 M pairs)
-            rc = h->lens.reserve(8 * (size_t)cnt0);
-            if (rc) return rc;
-            int32_t *d_pl = h->lens.as<int32_t>(), *d_tl = d_pl + cnt0;
-            hipLaunchKernelGGL(bpm_gather_lens, dim3((unsigned)std::min<int64_t>(gab_ceil_div((int64_t)cnt0, 256), 4096)), dim3(256), 0, s,
-                               d_perm + cstart[0], cnt0, pat_len, txt_len, d_pl, d_tl);
-            GAB_HIP(hipMemcpyAsync(pl.data(), d_pl, 4 * (size_t)cnt0, hipMemcpyDeviceToHost, s));
-            GAB_HIP(hipMemcpyAsync(tl.data(), d_tl, 4 * (size_t)cnt0, hipMemcpyDeviceToHost, s));
-            GAB_HIP(hipStreamSynchronize(s));
-            uint32_t k0 = 0;
-            while (k0 < cnt0) {
-                std::vector<int64_t> sb;
-                size_t used = 0; uint32_t k1 = k0;
-                while (k1 < cnt0) {
-                    const size_t Wd = ((size_t)pl[k1] + 63) / 64;
-                    const size_t need = 4 * Wd + 1 + ((size_t)tl[k1] + 1) * Wd * 2;
-                    if (k1 > k0 && (used + need) * 8 > h->scratch_budget) break;
-                    sb.push_back((int64_t)used); used += need; k1++;
-                }
-                const size_t nb = sb.size();
-                rc = h->scratch.reserve(used * 8 + nb * 8 + 64);
-                if (rc) return rc;
-                int64_t *d_sb = (int64_t *)(h->scratch.as<char>() + ((used * 8 + 63) & ~(size_t)63));
-                rc = h->scratch.reserve(((used * 8 + 63) & ~(size_t)63) + nb * 8);
-                if (rc) return rc;
-                d_sb = (int64_t *)(h->scratch.as<char>() + ((used * 8 + 63) & ~(size_t)63));
-                GAB_HIP(hipMemcpyAsync(d_sb, sb.data(), nb * 8, hipMemcpyHostToDevice, s));
-                if (h->tun.bpm_trace) fprintf(stderr, "[gab_bpm] full class 0 pairs %u..%u kernel bpm_full<0>\n", k0, k1);
-                launch_full<0>(s, io, d_perm + cstart[0] + k0, (uint32_t)nb, h->scratch.as<uint64_t>(), d_sb, score_out, d_ct);
-                GAB_HIP(hipStreamSynchronize(s));      // sb (host) and the scratch are reused by the next batch
-                k0 = k1;
-            }
-        }
-    }
-    GAB_HIP(hipGetLastError());
-    GAB_HIP(hipMemcpyAsync(h->h_ct, d_ct, sizeof(BpmCounters), hipMemcpyDeviceToHost, s));
-    GAB_HIP(hipEventRecord(h->ev[3], s));
-    if (h->tun.bpm_trace) {     // GAB_BPM_TRACE: the stage each class's pairs ended in (one synchronisation per call)
-        GAB_HIP(hipStreamSynchronize(s));
-        for (int c : order) {
-            if (!ccount[c]) continue;
-            uint32_t queued = 0;
-            for (int k = 0; k < kSlices; k++) queued += h->h_ct->wl_slice[c][k];
-            fprintf(stderr, "[gab_bpm] class %d pairs %u queued %u band_miss %u window_miss %u\n", c, ccount[c], queued,
-                    h->h_ct->wl1_count[c], h->h_ct->wl2_count[c]);
-        }
-        fprintf(stderr, "[gab_bpm] steps score %llu later %llu\n", h->h_ct->steps, h->h_ct->full_steps);
-    }
-    h->last_full = (int64_t)ccount[0];      // (+ the pairs the band kernels queued: added from the counters in gab_bpm_last_stats)
-    h->have_stats = true;
     return GAB_OK;
 }
 

@@ -4,7 +4,7 @@ import pytest
 
 from oracle import pyoracle
 from tools import gabgen
-from tests.util import GOLDEN, bpm_handmade_pairs, bpm_model, bpm_model_batch, read_scores
+from tests.util import BPM_STAGES, BPM_TRIP_EDGE_TLEN, GOLDEN, bpm_handmade_pairs, bpm_model, bpm_model_batch, bpm_trip_edge_pairs, read_scores
 
 
 def lev(a, b):
@@ -104,6 +104,24 @@ def test_cascade_model_handmade_pairs_land_where_built():
     got = {(min((len(p) + 63) // 64, 5), st) for p, _, st in pairs}
     # every band / window / full stage of every class that can reach it (class 1's window covers all of its 64 rows)
     assert got >= {(W, st) for W in (1, 2, 3, 4) for st in ("band", "window", "full") if (W, st) != (1, "full")}
+
+
+def test_trip_edge_pairs_land_in_every_stage_at_every_text_length():
+    """bpm_trip_edge_pairs(): each of score, band, window and full gets a pair of every text length 1 .. 70 (score and band of
+    length 0 too: with an empty text there is no walk to leave the band), the pairs above 256 bases are class W = 5, and the
+    model's scores are the oracle's"""
+    pairs = bpm_trip_edge_pairs()
+    lens = {st: set() for st in BPM_STAGES}
+    for p, t, built_for, stage in pairs:
+        lens[stage].add(len(t))
+        assert stage == built_for or (len(t) == 0 and stage == "band"), (len(p), len(t), built_for, stage)
+        if built_for == "generic":
+            assert (len(p) + 63) // 64 == 5
+    full = set(range(BPM_TRIP_EDGE_TLEN + 1))
+    assert lens["score"] == full and lens["band"] == full and lens["generic"] == full
+    assert lens["window"] == full - {0} and lens["full"] == full - {0}
+    b = gabgen.pairs_from_lists([p for p, _, _, _ in pairs], [t for _, t, _, _ in pairs])
+    np.testing.assert_array_equal(bpm_model_batch(b)[0], pyoracle.bpm(b))
 
 
 def test_cascade_model_stage_rules():

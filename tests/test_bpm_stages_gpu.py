@@ -7,7 +7,7 @@ import pytest
 
 from oracle import pyoracle
 from tools import gabgen
-from tests.util import bpm_census, bpm_handmade_pairs, bpm_model_batch, parse_bpm_trace
+from tests.util import bpm_census, bpm_handmade_pairs, bpm_model_batch, bpm_trip_edge_pairs, parse_bpm_trace
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +49,7 @@ def run_checked(eng, batch, capfd):
     assert st["block_steps"] == steps
     assert st["full_pairs"] == sum(c[1] for c in census.values()) + census.get(0, (0,))[0]
     # the template argument each score / band launch printed: D = 2W - 1 words exactly when the class's longest pattern fits them
-    # (launch_score and launch_slice each make that choice), W for the 64-row block form
+    # (bpm_class_words, taken by the score and the band launch alike), W for the 64-row block form
     W_all = (batch.pat_len + 63) // 64
     for stage, cls, _, kernel in launches:
         if stage in ("score", "band"):
@@ -137,6 +137,20 @@ def test_handmade_pairs_at_the_miss_checks(eng, traced, capfd):
     batch = gabgen.pairs_from_lists([p for p, _, _ in hand], [t for _, t, _ in hand])
     census, _, _ = run_checked(eng, batch, capfd)
     assert census == bpm_census(batch, [st for _, _, st in hand])
+
+
+@pytest.mark.parametrize("score64", [False, True])
+def test_text_lengths_at_every_trip_edge(eng, traced, capfd, score64):
+    """text lengths 0 .. 70 -- every boundary of the 32-, 16- and 4-base trips of the walks over the text -- in every stage:
+    score (both forms), band, window, full (classes 2 and 3) and generic each get a pair of every length (bpm_trip_edge_pairs)"""
+    if score64:
+        traced.setenv("GAB_BPM_SCORE64", "1")
+    pairs = bpm_trip_edge_pairs()
+    batch = gabgen.pairs_from_lists([p for p, _, _, _ in pairs], [t for _, t, _, _ in pairs])
+    census, _, worked = run_checked(eng, batch, capfd)
+    assert census == bpm_census(batch, [st for _, _, _, st in pairs])
+    assert any(k.startswith("bpm_score<" if score64 else "bpm_score32") for k in worked)
+    assert {"bpm_full<2>", "bpm_full<3>", "bpm_full<0>"} <= set(worked)
 
 
 def test_more_listed_pairs_than_history_slots(eng, traced, capfd):

@@ -188,12 +188,12 @@ _BPM_CODE = {ord("A"): 0, ord("a"): 0, ord("C"): 1, ord("c"): 1, ord("G"): 2, or
 
 
 def bpm_band_start(col, cshift, W):
-    """first of the 8 rows bpm_band keeps of column `col` (its start())"""
+    """first of the 8 rows bpm_band keeps of column `col` (bpm_rows_start<8, W>)"""
     return min(max(col + cshift - 4, 0), 64 * W - 8)
 
 
 def bpm_win_start(col, cshift, W):
-    """first of the 64 rows bpm_win keeps of column `col` (bpm_win_start<W>)"""
+    """first of the 64 rows bpm_win keeps of column `col` (bpm_rows_start<64, W>)"""
     return min(max(col + cshift - 32, 0), 64 * W - 64)
 
 
@@ -360,6 +360,31 @@ def bpm_handmade_pairs():
             for ch in (b"N", b"t"):
                 q = mark(_bpm_acgt(n, 900 + mk), mk, ch)
                 out.append((q, q[:n // 3] + q[n // 3 + 2:], "band"))
+    return out
+
+
+BPM_TRIP_EDGE_TLEN = 70      # text lengths 0 .. 70: every boundary of the 32-, 16- and 4-base trips of the text walk up to 64 + 6
+
+
+def bpm_trip_edge_pairs():
+    """for every text length m in 0 .. BPM_TRIP_EDGE_TLEN one pair per stage -> [(pattern, text, stage built for, stage by bpm_model)].
+
+    A random ACGT pattern of m + k bases and, as text, the pattern with k bases deleted at (n - k) // 2: k = 2 and clean for the score
+    stage; with the last pattern base an N, k = 2 stays in the 8-row band, k = 20 leaves it for the window, k = 70 leaves the window
+    too (classes 2 and 3).  For W > 4 a 260-base pattern with its m-base prefix as text.  At m = 0 the walk is empty, so the unclean
+    pairs all end in the band: the last element is what the model says, not what the pair was built for."""
+    out = []
+    for m in range(BPM_TRIP_EDGE_TLEN + 1):
+        for j, (k, unclean, built_for) in enumerate(((2, False, "score"), (2, True, "band"), (20, True, "window"), (70, True, "full"))):
+            n = m + k
+            p = _bpm_acgt(n, 7000 + 100 * j + m)
+            if unclean:
+                p = p[:-1] + b"N"
+            at = (n - k) // 2
+            t = p[:at] + p[at + k:]
+            out.append((p, t, built_for, bpm_model(p, t)[1]))
+        p = _bpm_acgt(260, 7400 + m)
+        out.append((p, p[:m], "generic", bpm_model(p, p[:m])[1]))
     return out
 
 

@@ -1,8 +1,8 @@
 #!/bin/bash
 # A libgab_hip.so variant with extra -D flags for ONE translation unit (knock-out / tuning builds):
 #   tools/profiling/build_variant.sh <name> <unit without .hip> <flags...>   ->  variants/libgab_<name>.so
-# chain's knock-outs (-DGAB_KO_*) are not in the product source: git apply tools/experiments/chain_knockouts.patch first, build
-# the variant, then git apply -R it.
+# chain's knock-outs (-DGAB_KO_*) and bpm's two experiments (-DGAB_KO_BPM_LOCAL_TEXT, -DGAB_BPM_TRIP64) are not in the product
+# source: git apply tools/experiments/chain_knockouts.patch (bpm_experiments.patch) first, build the variant, then git apply -R it.
 # Use with GAB_LIB_PATH=variants/libgab_<name>.so.  The other objects come from genarchbench_amd/csrc/build (run make first).
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
